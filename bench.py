@@ -19,9 +19,16 @@ the GPU); under `torch.distributed.run` the ranks come from the environment.
 sentences is cut into batches of `--batch`, the batches are dealt to the ranks
 (slimt_amd.sharding.plan_shards) and a step translates the whole set once.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP events on
-the stream the kernel runs on, over the timed region) and `cpu_baseline` (the
-CPU port of the reference path, timed on this box's host cores, N=1 only).
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times `--steps`
+steps and reports the headline (`value`, `ms_per_step`, `config`). `--full`
+adds everything else: `roofline` (dominant kernel, HIP events on the stream the
+kernel runs on, over the timed region), the K/V cache forms' readouts, the
+`sustained` and `model_forward*` regions, `--all-kernels` and `cpu_baseline`
+(the CPU port of the reference path, timed on this box's host cores, N=1 only).
+
+`--dump-outputs DIR`: after the timed steps, what the last timed step handed
+back (target ids and lengths of every output slot) as DIR/<name>.npy, so that
+two builds can be compared output for output; the inputs are seeded.
 """
 import argparse
 import json
@@ -58,9 +65,14 @@ def parse(argv=None):
     ap.add_argument("--total-sentences", type=int, default=0,
                     help="strong scaling (BASELINE config 5): a fixed set of sentences, cut into batches of "
                          "--batch and dealt to the ranks; a step translates the whole set once")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline (HIP events in the timed region), K/V cache form readouts, the "
+                         "sustained and model_forward regions, --all-kernels and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (target ids, lengths) as DIR/<name>.npy")
     ap.add_argument("--profile-kernel", default="auto",
-                    help="kernel family bracketed by HIP events in the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="kernel family bracketed by HIP events in the timed region (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-sentences", type=int, default=128, help="sentences per CPU worker")
     ap.add_argument("--workers", type=int, default=20,
                     help="translate contexts (HIP streams) per GPU, like slimt::Async workers "
@@ -102,15 +114,15 @@ def parse(argv=None):
                     help="decoder sentences per workgroup by occupancy (8 or 4 while CUs would idle): -1 = library "
                          "default (on), 0 = always 16, 1 = on")
     ap.add_argument("--sustained-steps", type=int, default=40,
-                    help="after the timed region, one longer untimed-by-the-driver region of this many steps "
+                    help="--full: after the timed region, one longer untimed-by-the-driver region of this many steps "
                          "(reported as `sustained`; 0 = skip)")
     ap.add_argument("--forward-steps", type=int, default=20,
-                    help="after the timed region: Model::forward as the reference defines it (host buffers in, "
+                    help="--full: after the timed region, Model::forward as the reference defines it (host buffers in, "
                          "tokens + lengths + alignment rows back in host memory; with one fixed shortlist and with "
                          "a lexical shortlist generated per batch), this many steps each (reported as "
                          "`model_forward*`; 0 = skip), and `single_stream` (one worker alone)")
     ap.add_argument("--all-kernels", action="store_true",
-                    help="after the timed region, time every kernel family (untimed pass)")
+                    help="--full: after the timed region, time every kernel family (untimed pass)")
     return ap.parse_args(argv)
 
 
@@ -286,6 +298,29 @@ def cpu_baseline(model, S, T, n_sl, n_sent):
     return out
 
 
+DUMP_LIMIT_BYTES = 48 << 20  # a fixed, seeded sample of the sentences beyond this
+
+
+def dump_outputs(out_dir, suffix, d_outs, d_lens_out, rows):
+    """What the last timed step handed back, one row per (output slot, sentence): `tokens` [n, T] (target ids,
+    0 past the sentence's length) and `lengths` [n], float32 (ids < 2^24 are exact). Rows a slot's last call did
+    not fill are left out; above DUMP_LIMIT_BYTES a seeded sample of the rows is kept and `rows` says which."""
+    import numpy as np
+    toks = np.concatenate([o[:n].cpu().numpy() for o, n in zip(d_outs, rows)]).astype(np.int64)
+    lens = np.concatenate([l[:n].cpu().numpy() for l, n in zip(d_lens_out, rows)]).astype(np.int64)
+    keep = np.arange(lens.size)
+    row_bytes = 4 * (toks.shape[1] + 2)  # a row of each of the three files
+    if lens.size * row_bytes > DUMP_LIMIT_BYTES:
+        n = max(1, DUMP_LIMIT_BYTES // row_bytes)
+        keep = np.sort(np.random.Generator(np.random.PCG64(0)).choice(lens.size, n, replace=False))
+    toks, lens = toks[keep], lens[keep]
+    toks[np.arange(toks.shape[1])[None, :] >= lens[:, None]] = 0
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"tokens{suffix}.npy"), toks.astype(np.float32))
+    np.save(os.path.join(out_dir, f"lengths{suffix}.npy"), lens.astype(np.float32))
+    np.save(os.path.join(out_dir, f"rows{suffix}.npy"), keep.astype(np.float32))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -433,6 +468,13 @@ def main():
         def sync():
             torch.cuda.synchronize()
 
+        def last_rows(slot):
+            # sentences the last call of a step into this output slot translated (strong: the worker's last batch)
+            if not strong:
+                return B
+            js = [j for j in range(batches_per_step) if j % W == slot]
+            return my_batches[js[-1]][1] if js else 0
+
         for i in range(max(1, args.warmup)):
             step(i)
         sync()
@@ -470,8 +512,9 @@ def main():
         enc_fused, dec_fused = ctxs[0].plan(S)
         auto_kernel = "decode_fused" if dec_fused else "gemm_dec"
         prof_name = auto_kernel if args.profile_kernel == "auto" else args.profile_kernel
-        for c in ctxs:
-            c.profile_enable(kmap.get(prof_name, capi.K_NONE))
+        if args.full:
+            for c in ctxs:
+                c.profile_enable(kmap.get(prof_name, capi.K_NONE))
 
     def barrier():
         sync()
@@ -485,8 +528,14 @@ def main():
         step(i)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        if dry:
+            print("bench: dry run, no outputs to dump", file=sys.stderr)
+        else:
+            dump_outputs(args.dump_outputs, "" if world == 1 else f"_rank{rank}", d_outs, d_lens_out,
+                         [last_rows(s) for s in range(n_slots)])
     kv_forms = kv_watch = None
-    if not dry:
+    if args.full and not dry:
         # which form the last batch's K/V caches took, per sentence and decoder layer (slimt_hip_debug_kv_formats)
         seen = ctxs[0].debug_kv_formats(Ld, rows_ctx)
         if seen is not None:
@@ -519,7 +568,7 @@ def main():
 
     tokens_per_pass_all = total_tokens_per_step // RD  # one translate call on every worker of every GPU (the forward regions' step)
     sustained = None
-    if args.sustained_steps > 0 and not dry:
+    if args.full and args.sustained_steps > 0 and not dry:
         barrier()
         t1 = time.perf_counter()
         for i in range(args.sustained_steps):
@@ -532,7 +581,7 @@ def main():
     forward = None
     if args.eos_bias > -50.0:
         args.forward_steps = 0  # (the host-buffer regions check T tokens per sentence)
-    if args.forward_steps > 0 and not dry and not strong and MG > 1:
+    if args.full and args.forward_steps > 0 and not dry and not strong and MG > 1:
         # Model::forward on host buffers, merged: MG pinned batches per worker through slimt_hip_translate_many_async
         from slimt_amd import capi as _capi
         K = args.forward_steps
@@ -570,7 +619,7 @@ def main():
         for ps in pins:
             for p_ in ps:
                 p_.free()
-    elif args.forward_steps > 0 and not dry and not strong:
+    elif args.full and args.forward_steps > 0 and not dry and not strong:
         # Model::forward as the reference's workers call it (Model.cc:111-204): ids and lengths in
         # (pinned) HOST memory, tokens, lengths and the alignment rows of every step (Model.cc:84-108)
         # back in host memory -- slimt_hip_translate_async[_generated] on the same 20 x 256 workload.
@@ -635,7 +684,7 @@ def main():
                                     "note": "one worker alone (one stream, batches back to back), device-resident I/O, this rank"}
 
     per_kernel = None
-    if args.all_kernels and rank == 0 and not dry:
+    if args.full and args.all_kernels and rank == 0 and not dry:
         per_kernel = {}
         for name, kid in kmap.items():
             for c in ctxs:
@@ -656,90 +705,92 @@ def main():
         macs_sentence = algorithmic_macs_per_sentence(D, F, Le, Ld, S, T, N_out)
         sentences_per_step = args.total_sentences if strong else world * sum(c for _, c in my_batches)
         whole_job_tops = 2.0 * macs_sentence * sentences_per_step * args.steps / dt_max / 1e12
-        avg_ms = prof["total_ms"] / max(1, prof["launches"])
-        ops = 2.0 * prof["int8_macs"] / max(1, prof["launches"])       # algorithmic int8 OPs / launch
-        wbytes = prof["weight_bytes"] / max(1, prof["launches"])       # weight bytes streamed / launch
-        achieved = ops / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
-        # the committed counters are of the default workload of each preset: no figure for others
-        profiled = (args.preset in ("tiny11", "base") and B == 256 and S == 32 and n_sl == 4096 and not args.ragged and MG == 1 and
-                    args.family == "default" and args.eos_bias <= -50.0)
-        traffic, traffic_src = pmc_traffic(prof_name, args.preset) if profiled else (None, None)
-        cus = -(-(B * MG) // 16) if prof_name == "decode_fused" else 256
-        in_flight = prof["total_ms"] / (1e3 * dt) if dt > 0 else 0.0  # launches of this kernel running at once (this rank)
-        # the path is a dense int8 contraction, so the bound is the int8 MFMA
-        # roofline. `achieved` = algorithmic int8 OPs of one launch of the dominant kernel /
-        # its mean duration (HIP events on its own stream); one launch occupies `cus_per_launch`
-        # of the 256 CUs and `launches_in_flight` of them overlap (with the other workers'
-        # encoders), so the chip-level figures are given beside it.
-        roofline = {
-            "kernel": prof_name, "bound": "mfma", "achieved": achieved, "peak": PEAK_INT8_TOPS, "unit": "TOP/s",
-            "frac": achieved / PEAK_INT8_TOPS, "traffic": traffic, "traffic_source": traffic_src,
-            "algorithmic_ops_per_launch": ops, "launches": prof["launches"], "avg_launch_us": 1e3 * avg_ms,
-            "cus_per_launch": cus, "launches_in_flight": in_flight,
-            # `frac` prices ONE launch (16 CUs for a batch of 256) against the whole chip; the launches of this
-            # kernel that run at once, together, against the same peak:
-            "frac_chip": achieved * in_flight / PEAK_INT8_TOPS,
-            "measured_peak": MEASURED_INT8_TOPS, "frac_measured_peak": achieved / MEASURED_INT8_TOPS,
-            "frac_chip_measured_peak": achieved * in_flight / MEASURED_INT8_TOPS,
-            "evidence_tag": evidence_manifest().get("tag") if profiled else None,
-            "frac_of_occupied_cus": achieved / (PEAK_INT8_TOPS * cus / 256.0),
-            "counters_full_occupancy": sq_counters(prof_name, args.preset)[0] if profiled else None,
-            "counters_source": sq_counters(prof_name, args.preset)[1] if profiled else None,
-            "whole_job": {"achieved": whole_job_tops / world, "frac": whole_job_tops / world / PEAK_INT8_TOPS,
-                          "frac_measured_peak": whole_job_tops / world / MEASURED_INT8_TOPS,
-                          "note": "all kernels, per GPU: algorithmic int8 OPs of every translated sentence / "
-                                  "wall time of the timed region"},
-        }
-        if roofline["counters_full_occupancy"]:
-            roofline["mfma_busy_frac"] = roofline["counters_full_occupancy"].get("mfma_busy_frac")
-        if prof_name == "decode_fused":
-            # HBM view of the same kernel. SURVEY 8(d) counts the cross-attention K/V cache as
-            # written once and re-read on-chip: `algorithmic_bytes_per_launch` = weights + target
-            # embedding rows + K/V once. This implementation re-reads the K/V cache from the
-            # memory side every step (9..12 batches decode at a time: their caches exceed the
-            # 256 MB Infinity Cache): `implementation_bytes_per_launch`, and its ratio.
-            # The cache the decoder re-reads is the packed 24-bit form where the kernels have it
-            # (tiny11, S <= 32, not S = 1, 2, 5: slimt_hip_model_set_kv_cache_format), f32 elsewhere;
-            # SURVEY's algorithmic K/V stays the f32 tensor it names.
-            kv_once = float(B * MG) * Ld * 2 * S * D * 4
-            kv24 = (dec_fused and enc_fused and args.kv_format in (0, 2) and ((S + 3) // 4 * 4) * 3 <= S * 4 and
-                    ((D == 256 and D // H == 32 and S <= 128) or (D == 512 and D // H == 64 and S <= 32)))
-            # ... 20 bits per value where the kernels have the narrow form and the accumulators fit it (every sentence of
-            # the synthetic models does: tests/test_gpu_kv_narrow.py)
-            kv20 = (kv24 and args.kv_format == 0 and ((D == 256 and S <= 64) or (D == 512 and S <= 32)) and
-                    ((S + 7) // 8) * 5120 <= ((S + 3) // 4) * 3072)
-            kv_impl = kv_once * (0.625 if kv20 else 0.75 if kv24 else 1.0)
-            # ... 16 bits where the tight form has a reader (this launch's last batch says which sentences took which form)
-            if kv20 and kv_forms:
-                kv_impl = kv_once * (0.5 * kv_forms["int16"] + 0.625 * kv_forms["int20"] + 0.75 * kv_forms["int24"])
-            w_once = float(Ld * (4 * D * D + 2 * D * F) + D * N_out)
-            io_bytes = float(B * MG) * T * (D + 4)
-            alg_bytes = w_once + io_bytes + kv_once
-            kv_reread = kv_impl * T
-            impl_bytes = kv_reread + w_once * T + io_bytes
-            gbs = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-            roofline["hbm_view"] = {
-                "bound": "hbm", "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS,
-                "algorithmic_bytes_per_launch": alg_bytes,
-                "implementation_bytes_per_launch": impl_bytes,
-                "implementation_over_algorithmic": impl_bytes / alg_bytes,
-                "traffic_over_algorithmic": (traffic / alg_bytes) if traffic else None,
-                "kv_cache_forms_last_batch": kv_forms,
-                "kv_cache_format": ("int16 accumulators less per-column centres (2 bytes per value; 20- and 24-bit fallbacks per sentence and layer)"
-                                    if kv20 and kv_forms and kv_forms["int16"] > 0.5
-                                    else "int20 accumulators (2.5 bytes per value; 24-bit fallback per sentence and layer)" if kv20
-                                    else "int24 accumulators (3 bytes per value)" if kv24 else "f32"),
-                "bytes_model": {"kv_cache_once": kv_once, "kv_cache_reread_every_step": kv_reread,
-                                "weights_once": w_once, "weights_once_per_step": w_once * T,
-                                "embedding_rows_and_ids": io_bytes},
-                "implementation_GBs_per_launch": impl_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0,
-                "implementation_GBs_chip": impl_bytes / (avg_ms * 1e-3) / 1e9 * in_flight if avg_ms > 0 else 0.0,
-                # the PMC figure (bytes that missed the 4 MB L2s, Infinity-Cache hits included) of one launch, as a rate over
-                # the launches in flight together: what the fabric side carries for this kernel
-                "fabric_GBs_chip": (traffic / (avg_ms * 1e-3) / 1e9 * in_flight) if traffic and avg_ms > 0 else None,
-                "l2_stream_bytes_per_launch": wbytes + kv_reread,  # weights per workgroup and step + K/V
-                "l2_stream_GBs_per_cu": (wbytes + kv_reread) / (avg_ms * 1e-3) / 1e9 / cus if avg_ms > 0 else 0.0,
+        roofline = None
+        if args.full:
+            avg_ms = prof["total_ms"] / max(1, prof["launches"])
+            ops = 2.0 * prof["int8_macs"] / max(1, prof["launches"])       # algorithmic int8 OPs / launch
+            wbytes = prof["weight_bytes"] / max(1, prof["launches"])       # weight bytes streamed / launch
+            achieved = ops / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
+            # the committed counters are of the default workload of each preset: no figure for others
+            profiled = (args.preset in ("tiny11", "base") and B == 256 and S == 32 and n_sl == 4096 and not args.ragged and MG == 1 and
+                        args.family == "default" and args.eos_bias <= -50.0)
+            traffic, traffic_src = pmc_traffic(prof_name, args.preset) if profiled else (None, None)
+            cus = -(-(B * MG) // 16) if prof_name == "decode_fused" else 256
+            in_flight = prof["total_ms"] / (1e3 * dt) if dt > 0 else 0.0  # launches of this kernel running at once (this rank)
+            # the path is a dense int8 contraction, so the bound is the int8 MFMA
+            # roofline. `achieved` = algorithmic int8 OPs of one launch of the dominant kernel /
+            # its mean duration (HIP events on its own stream); one launch occupies `cus_per_launch`
+            # of the 256 CUs and `launches_in_flight` of them overlap (with the other workers'
+            # encoders), so the chip-level figures are given beside it.
+            roofline = {
+                "kernel": prof_name, "bound": "mfma", "achieved": achieved, "peak": PEAK_INT8_TOPS, "unit": "TOP/s",
+                "frac": achieved / PEAK_INT8_TOPS, "traffic": traffic, "traffic_source": traffic_src,
+                "algorithmic_ops_per_launch": ops, "launches": prof["launches"], "avg_launch_us": 1e3 * avg_ms,
+                "cus_per_launch": cus, "launches_in_flight": in_flight,
+                # `frac` prices ONE launch (16 CUs for a batch of 256) against the whole chip; the launches of this
+                # kernel that run at once, together, against the same peak:
+                "frac_chip": achieved * in_flight / PEAK_INT8_TOPS,
+                "measured_peak": MEASURED_INT8_TOPS, "frac_measured_peak": achieved / MEASURED_INT8_TOPS,
+                "frac_chip_measured_peak": achieved * in_flight / MEASURED_INT8_TOPS,
+                "evidence_tag": evidence_manifest().get("tag") if profiled else None,
+                "frac_of_occupied_cus": achieved / (PEAK_INT8_TOPS * cus / 256.0),
+                "counters_full_occupancy": sq_counters(prof_name, args.preset)[0] if profiled else None,
+                "counters_source": sq_counters(prof_name, args.preset)[1] if profiled else None,
+                "whole_job": {"achieved": whole_job_tops / world, "frac": whole_job_tops / world / PEAK_INT8_TOPS,
+                              "frac_measured_peak": whole_job_tops / world / MEASURED_INT8_TOPS,
+                              "note": "all kernels, per GPU: algorithmic int8 OPs of every translated sentence / "
+                                      "wall time of the timed region"},
             }
+            if roofline["counters_full_occupancy"]:
+                roofline["mfma_busy_frac"] = roofline["counters_full_occupancy"].get("mfma_busy_frac")
+            if prof_name == "decode_fused":
+                # HBM view of the same kernel. SURVEY 8(d) counts the cross-attention K/V cache as
+                # written once and re-read on-chip: `algorithmic_bytes_per_launch` = weights + target
+                # embedding rows + K/V once. This implementation re-reads the K/V cache from the
+                # memory side every step (9..12 batches decode at a time: their caches exceed the
+                # 256 MB Infinity Cache): `implementation_bytes_per_launch`, and its ratio.
+                # The cache the decoder re-reads is the packed 24-bit form where the kernels have it
+                # (tiny11, S <= 32, not S = 1, 2, 5: slimt_hip_model_set_kv_cache_format), f32 elsewhere;
+                # SURVEY's algorithmic K/V stays the f32 tensor it names.
+                kv_once = float(B * MG) * Ld * 2 * S * D * 4
+                kv24 = (dec_fused and enc_fused and args.kv_format in (0, 2) and ((S + 3) // 4 * 4) * 3 <= S * 4 and
+                        ((D == 256 and D // H == 32 and S <= 128) or (D == 512 and D // H == 64 and S <= 32)))
+                # ... 20 bits per value where the kernels have the narrow form and the accumulators fit it (every sentence of
+                # the synthetic models does: tests/test_gpu_kv_narrow.py)
+                kv20 = (kv24 and args.kv_format == 0 and ((D == 256 and S <= 64) or (D == 512 and S <= 32)) and
+                        ((S + 7) // 8) * 5120 <= ((S + 3) // 4) * 3072)
+                kv_impl = kv_once * (0.625 if kv20 else 0.75 if kv24 else 1.0)
+                # ... 16 bits where the tight form has a reader (this launch's last batch says which sentences took which form)
+                if kv20 and kv_forms:
+                    kv_impl = kv_once * (0.5 * kv_forms["int16"] + 0.625 * kv_forms["int20"] + 0.75 * kv_forms["int24"])
+                w_once = float(Ld * (4 * D * D + 2 * D * F) + D * N_out)
+                io_bytes = float(B * MG) * T * (D + 4)
+                alg_bytes = w_once + io_bytes + kv_once
+                kv_reread = kv_impl * T
+                impl_bytes = kv_reread + w_once * T + io_bytes
+                gbs = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+                roofline["hbm_view"] = {
+                    "bound": "hbm", "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS,
+                    "algorithmic_bytes_per_launch": alg_bytes,
+                    "implementation_bytes_per_launch": impl_bytes,
+                    "implementation_over_algorithmic": impl_bytes / alg_bytes,
+                    "traffic_over_algorithmic": (traffic / alg_bytes) if traffic else None,
+                    "kv_cache_forms_last_batch": kv_forms,
+                    "kv_cache_format": ("int16 accumulators less per-column centres (2 bytes per value; 20- and 24-bit fallbacks per sentence and layer)"
+                                        if kv20 and kv_forms and kv_forms["int16"] > 0.5
+                                        else "int20 accumulators (2.5 bytes per value; 24-bit fallback per sentence and layer)" if kv20
+                                        else "int24 accumulators (3 bytes per value)" if kv24 else "f32"),
+                    "bytes_model": {"kv_cache_once": kv_once, "kv_cache_reread_every_step": kv_reread,
+                                    "weights_once": w_once, "weights_once_per_step": w_once * T,
+                                    "embedding_rows_and_ids": io_bytes},
+                    "implementation_GBs_per_launch": impl_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0,
+                    "implementation_GBs_chip": impl_bytes / (avg_ms * 1e-3) / 1e9 * in_flight if avg_ms > 0 else 0.0,
+                    # the PMC figure (bytes that missed the 4 MB L2s, Infinity-Cache hits included) of one launch, as a rate over
+                    # the launches in flight together: what the fabric side carries for this kernel
+                    "fabric_GBs_chip": (traffic / (avg_ms * 1e-3) / 1e9 * in_flight) if traffic and avg_ms > 0 else None,
+                    "l2_stream_bytes_per_launch": wbytes + kv_reread,  # weights per workgroup and step + K/V
+                    "l2_stream_GBs_per_cu": (wbytes + kv_reread) / (avg_ms * 1e-3) / 1e9 / cus if avg_ms > 0 else 0.0,
+                }
         out = {
             "metric": "target tokens/sec, en-de tiny11 int8 greedy, batch=256",
             "value": value, "unit": "tokens/s", "n_gpus": world, "n_ranks_seen": n_ranks_seen, "steps": args.steps,
@@ -766,8 +817,9 @@ def main():
                 "int8_ops_per_token": 2.0 * macs_sentence / T,
                 "whole_job_int8_tops": whole_job_tops,
             },
-            "roofline": roofline,
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         if not dry and args.family != "default":
             out["config"]["family"] = {"name": args.family, **synth.FAMILIES[args.family]}
         if not dry and args.eos_bias > -50.0:
@@ -783,7 +835,7 @@ def main():
             out.update(forward)
         if per_kernel is not None:
             out["per_kernel"] = per_kernel
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             out["cpu_baseline"] = cpu_baseline(model, S, T, n_sl, args.cpu_sentences)
         print(json.dumps(out), flush=True)
     if dist is not None:

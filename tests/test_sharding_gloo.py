@@ -92,7 +92,7 @@ def test_bench_gpus_flag_spawns_the_ranks():
     line with n_gpus = 2. SLIMT_BENCH_DRY replaces the device work by no-ops: what
     is under test is the launcher, the barrier and the MAX / SUM reduction."""
     import json
-    lines = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--workers", "4"])
+    lines = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--workers", "4", "--full"])
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["steps"] == 3 and d["warmup"] == 1

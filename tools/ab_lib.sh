@@ -13,7 +13,7 @@ for rep in 1 2; do
       SLIMT_HIP_LIB=$PWD/$lib timeout -k 10 120 python tools/decode_phases_loaded.py > gpurun_out/${TAG}_${v}${rep}_decl.txt 2>&1 || exit 1
       echo "$v$rep decoder alone: $(grep 'step 20' gpurun_out/${TAG}_${v}${rep}_dec.txt | sed 's/.*total//')  loaded: $(grep 'total' gpurun_out/${TAG}_${v}${rep}_decl.txt | sed 's/.*total//')"
     fi
-    SLIMT_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --steps 30 --warmup 5 --profile-kernel none --no-cpu-baseline --forward-steps 0 $4 2>/dev/null | python -c "
+    SLIMT_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --profile-kernel none --no-cpu-baseline --forward-steps 0 $4 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('$v$rep bench: value %.2f M  sustained %.2f M' % (d['value']/1e6, d.get('sustained',{}).get('value',0)/1e6))" || exit 1
   done

@@ -7,7 +7,7 @@ for args in "$@"; do
   for rep in 1 2; do
     for v in A B; do
       lib=$A; [ $v = B ] && lib=$B
-      SLIMT_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --forward-steps 0 --sustained-steps 10 $args 2>/dev/null | python -c "
+      SLIMT_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --forward-steps 0 --sustained-steps 10 $args 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v$rep [$args] value %.2f M  sustained %.2f M  launch %.0f us' % (d['value']/1e6, d.get('sustained',{}).get('value',0)/1e6, d['roofline']['avg_launch_us']))" | tee -a gpurun_out/${TAG}_ab.txt || exit 1
     done

@@ -6,7 +6,7 @@ OUT=${1:-gpurun_out/r06_staggered_eos.txt}
 : > $OUT
 row() {
   label=$1; shift
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --forward-steps 0 "$@" 2>/dev/null | python -c "
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --forward-steps 0 "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 lf = d.get('decoder_tile_live_fraction')

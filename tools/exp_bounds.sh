@@ -8,7 +8,7 @@ TAG=${1:-bounds}
 OUT=gpurun_out/${TAG}.txt; : > $OUT
 run() {  # name lib mode env...
   local name=$1 lib=$2 mode=$3; shift 3
-  local v=$(env "$@" SLIMT_HIP_LIB=$PWD/slimt_amd/lib/$lib timeout -k 10 200 python bench.py --steps 30 --warmup 5 --decode-mode $mode --profile-kernel none --no-cpu-baseline --forward-steps 0 2>/dev/null | python -c "
+  local v=$(env "$@" SLIMT_HIP_LIB=$PWD/slimt_amd/lib/$lib timeout -k 10 200 python bench.py --full --steps 30 --warmup 5 --decode-mode $mode --profile-kernel none --no-cpu-baseline --forward-steps 0 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.2f M  sustained %.2f M' % (d['value']/1e6, d.get('sustained',{}).get('value',0)/1e6))")
   echo "$name mode $mode $*: $v" | tee -a $OUT

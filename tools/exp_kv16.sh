@@ -2,7 +2,7 @@
 # GPU box: timing-only bound (wrong results) of a 16-bit K/V cache form against the 24- and 20-bit ones, one box
 mkdir -p gpurun_out; OUT=gpurun_out/${1:-kv16}.txt; : > $OUT
 run() { local name=$1 lib=$2; shift 2
-  local v=$(env "$@" SLIMT_HIP_LIB=$PWD/slimt_amd/lib/$lib timeout -k 10 200 python bench.py --steps 30 --warmup 5 --profile-kernel none --no-cpu-baseline --forward-steps 0 2>/dev/null | python -c "
+  local v=$(env "$@" SLIMT_HIP_LIB=$PWD/slimt_amd/lib/$lib timeout -k 10 200 python bench.py --full --steps 30 --warmup 5 --profile-kernel none --no-cpu-baseline --forward-steps 0 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.2f M  sustained %.2f M' % (d['value']/1e6, d.get('sustained',{}).get('value',0)/1e6))")
   echo "$name: $v" | tee -a $OUT; }

@@ -35,7 +35,7 @@ for fam in families:
     ctx.close()
     gm.close()
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--family", fam, "--steps", "20", "--warmup", "5",
-                          "--forward-steps", "0", "--no-cpu-baseline", "--sustained-steps", "20"], capture_output=True, text=True)
+                          "--forward-steps", "0", "--no-cpu-baseline", "--sustained-steps", "20", "--full"], capture_output=True, text=True)
     if res.returncode != 0:
         print(f"{fam:18s} {'ok' if ok else 'FAILED':8s} bench failed: {res.stderr[-200:]}")
         continue

@@ -7,7 +7,7 @@ rc=$?; echo "[cluster tests] rc=$rc"; tail -3 gpurun_out/test_${TAG}.log
 if [ $rc -ne 0 ]; then grep -E "^(FAILED|ERROR)|Error|assert" gpurun_out/test_${TAG}.log | head -20; tail -30 gpurun_out/test_${TAG}.log; exit $rc; fi
 for rep in 1 2; do
 for args in "--decode-mode 3" "--decode-mode 2" "--decode-mode 6" "--decode-mode 0"; do
-  echo -n "[config 4 $args] "; timeout -k 10 300 python bench.py --steps 10 --warmup 2 --profile-kernel none --no-cpu-baseline --forward-steps 0 --batch 512 --shortlist 0 $args 2>/dev/null | python -c "
+  echo -n "[config 4 $args] "; timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --profile-kernel none --no-cpu-baseline --forward-steps 0 --batch 512 --shortlist 0 $args 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.2f M  sustained %.2f M' % (d['value']/1e6, d.get('sustained',{}).get('value',0)/1e6))" || exit 1
 done; done | tee gpurun_out/${TAG}_c4.txt

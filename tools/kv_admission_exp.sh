@@ -10,7 +10,7 @@ OUT=gpurun_out/${TAG}_kv_admission.txt; : > $OUT
 for cfg in "$@"; do
   set -- $cfg; BUD=$1; MODE=$2
   ARGS="--decoder-budget $BUD --decode-mode $MODE --forward-steps 0 --sustained-steps 0 --no-cpu-baseline"
-  line=$(timeout -k 10 200 python bench.py --steps 16 --warmup 4 $ARGS 2>/dev/null | python -c "
+  line=$(timeout -k 10 200 python bench.py --full --steps 16 --warmup 4 $ARGS 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('%.2f M tok/s, decoder launch %.0f us, %.1f in flight' % (d['value']/1e6, r['avg_launch_us'], r['launches_in_flight']))") || { echo "bench failed: $cfg"; exit 1; }

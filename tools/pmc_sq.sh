@@ -4,17 +4,17 @@
 # usage: tools/pmc_sq.sh [tag]
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?GRAFT_REPO_ROOT is not set (run through gpurun)}"
 TAG=${1:-sq}
-mkdir -p gpurun_out
-rocprofv3 -L 2>/dev/null | grep -o "SQ_[A-Z0-9_]*" | sort -u > gpurun_out/${TAG}_sq_counter_names.txt
-wc -l gpurun_out/${TAG}_sq_counter_names.txt
+export OUT_DIR=${OUT_DIR:-results}; mkdir -p $OUT_DIR
+rocprofv3 -L 2>/dev/null | grep -o "SQ_[A-Z0-9_]*" | sort -u > $OUT_DIR/${TAG}_sq_counter_names.txt
+wc -l $OUT_DIR/${TAG}_sq_counter_names.txt
 i=0
 while read -r c; do
   [ -z "$c" ] && continue
   i=$((i+1))
-  rm -rf gpurun_out/pmc_${TAG}_$i
-  timeout -k 10 300 rocprofv3 --pmc $c --output-format csv -d gpurun_out/pmc_${TAG}_$i -- python3 bench.py ${PRESET:+--preset $PRESET} --batch ${BATCH:-4096} --workers 1 --steps 2 --warmup 1 --sustained-steps 0 --no-cpu-baseline --profile-kernel none > gpurun_out/pmc_${TAG}_$i.log 2>&1 || { echo "pmc set $i ($c) failed"; tail -3 gpurun_out/pmc_${TAG}_$i.log; continue; }
-  f=$(ls gpurun_out/pmc_${TAG}_$i/*/*counter_collection.csv | head -1)
-  python3 - "$f" <<'PY' | tee -a gpurun_out/${TAG}_sq_pmc.txt
+  rm -rf $OUT_DIR/pmc_${TAG}_$i
+  timeout -k 10 300 rocprofv3 --pmc $c --output-format csv -d $OUT_DIR/pmc_${TAG}_$i -- python3 bench.py ${PRESET:+--preset $PRESET} --batch ${BATCH:-4096} --workers 1 --steps 2 --warmup 1 --sustained-steps 0 --no-cpu-baseline --profile-kernel none > $OUT_DIR/pmc_${TAG}_$i.log 2>&1 || { echo "pmc set $i ($c) failed"; tail -3 $OUT_DIR/pmc_${TAG}_$i.log; continue; }
+  f=$(ls $OUT_DIR/pmc_${TAG}_$i/*/*counter_collection.csv | head -1)
+  python3 - "$f" <<'PY' | tee -a $OUT_DIR/${TAG}_sq_pmc.txt
 import csv, sys, collections
 agg = collections.defaultdict(list)
 for r in csv.DictReader(open(sys.argv[1])):
@@ -32,7 +32,7 @@ TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum
 GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_I8 SQ_VALU_MFMA_COEXEC_CYCLES SQ_ACTIVE_INST_FLAT SQ_INSTS_VALU_CVT
 SETS
 # JSON digest: counters per kernel + busy fractions (profiles/<tag>_sq_pmc.json; bench.py's roofline.mfma_busy_frac)
-python3 - gpurun_out/${TAG}_sq_pmc.txt gpurun_out/${TAG}_sq_pmc.json <<'PY'
+python3 - $OUT_DIR/${TAG}_sq_pmc.txt $OUT_DIR/${TAG}_sq_pmc.json <<'PY'
 import json, re, sys, collections
 k = collections.defaultdict(dict)
 for line in open(sys.argv[1]):
