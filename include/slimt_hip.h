@@ -234,6 +234,21 @@ int slimt_hip_ctx_set_decode_mode(slimt_hip_ctx *ctx, int mode);
  * (default) = chosen per call (64-row tiles from 32 of them on),
  * 32 or 64 = forced (tuning and tests). Same results either way. */
 int slimt_hip_ctx_set_encode_rows(slimt_hip_ctx *ctx, int rows);
+/* Per-token scores for the NEXT translate call on ctx (any of the slimt_hip_translate*
+ * entry points), which consumes the setting whether it succeeds or fails; n = 0 arms
+ * nothing. scores[j] is the [B_j][Tmax_j] f32 destination of batch j: n = 1 for the
+ * single-batch calls, n = n_batches for the _many_ ones; in the memory of that
+ * call's outputs (host for the host calls -- pinned where the outputs are, so the
+ * kernels write it in place --, device for the _device ones). A mismatched n or a
+ * NULL entry fails that call.
+ * scores[b][t] for t < out_len[b] (EOS included) is the natural-log softmax
+ * probability of out_ids[b][t] over that step's output layer (the shortlist's
+ * columns, or the full vocabulary): the distribution the greedy arg-max chooses
+ * from. Entries at t >= out_len[b] are not defined. A step whose logits hold a NaN
+ * (this includes "logit 0 is NaN -> class 0") or are all -inf scores NaN. Tokens,
+ * lengths and alignments are the same as without scores. Scored calls decode with
+ * the 16-sentence tilings (decode modes 2-6 act as 2 for them). */
+int slimt_hip_ctx_set_scores(slimt_hip_ctx *ctx, float *const *scores, size_t n);
 /* Which kernels a translate call with source length S would use in the current
  * mode: *encoder_fused / *decoder_fused = 1 for the persistent kernels, 0 for
  * the per-stage ones. */

@@ -39,6 +39,7 @@ SYMBOLS = [
     "slimt_hip_encode_embedded", "slimt_hip_decode_begin_from", "slimt_hip_decode_step_states",
     "slimt_hip_translate_many_rows", "slimt_hip_translate_many_device", "slimt_hip_translate_many_async",
     "slimt_hip_debug_kv_recalibrations", "slimt_hip_translate_many_device_generated", "slimt_hip_translate_many_async_generated",
+    "slimt_hip_ctx_set_scores",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -202,6 +203,7 @@ def lib():
     L.slimt_hip_ctx_synchronize.argtypes = [vp]
     L.slimt_hip_ctx_set_decode_mode.argtypes = [vp, i32]
     L.slimt_hip_ctx_set_encode_rows.argtypes = [vp, i32]
+    L.slimt_hip_ctx_set_scores.argtypes = [vp, vp, sz]
     L.slimt_hip_ctx_plan.argtypes = [vp, sz, vp, vp]
     L.slimt_hip_translate.argtypes = [vp, vp, vp, sz, sz, vp, sz, f32, u32, vp, vp, vp]
     L.slimt_hip_translate_async.argtypes = [vp, vp, vp, sz, sz, vp, sz, f32, u32, vp, vp, vp]
@@ -579,6 +581,20 @@ class Context:
         """Rows per workgroup of the persistent D = 256 encoder: 0 = auto, 32, 64."""
         _chk(lib().slimt_hip_ctx_set_encode_rows(self.h, rows))
 
+    def set_scores(self, destinations):
+        """slimt_hip_ctx_set_scores: arm per-token scores for the NEXT translate call -- one [B_j, Tmax_j] float32
+        destination per batch, as addresses (ints; device pointers for the device calls) or numpy arrays (host calls).
+        The translate wrappers below do this themselves when asked for scores."""
+        addrs = [d.ctypes.data if isinstance(d, np.ndarray) else (int(d) if d else 0) for d in destinations]
+        arr = (C.c_void_p * max(1, len(addrs)))(*[a or None for a in addrs])
+        _chk(lib().slimt_hip_ctx_set_scores(self.h, arr, len(addrs)))
+
+    @staticmethod
+    def _scores_array(a, B: int, T: int):
+        if a.dtype != np.float32 or a.shape != (B, T) or not a.flags.c_contiguous:
+            raise ValueError("scores: a C-contiguous float32 array of shape %s expected" % ((B, T),))
+        return a
+
     def plan(self, S: int):
         """(encoder_fused, decoder_fused) for source length S in the current mode."""
         e, d = C.c_int(0), C.c_int(0)
@@ -586,8 +602,9 @@ class Context:
         return bool(e.value), bool(d.value)
 
     def translate(self, ids, lengths, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                  want_align: bool = False):
-        """Model::forward. Returns out_ids [B,Tmax], out_len [B], align|None."""
+                  want_align: bool = False, scores: bool = False):
+        """Model::forward. Returns out_ids [B,Tmax], out_len [B], align|None (+ scores [B,Tmax] float32 with
+        scores=True: the log-probability of each recorded token, include/slimt_hip.h slimt_hip_ctx_set_scores)."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
         B, S = ids.shape
@@ -597,10 +614,13 @@ class Context:
         out_ids = np.zeros((B, T), dtype=np.uint32)
         out_len = np.zeros(B, dtype=np.uint32)
         align = np.zeros((B, T, S), dtype=np.float32) if want_align else None
+        sc = np.full((B, T), np.nan, dtype=np.float32) if scores else None
+        if scores:
+            self.set_scores([sc])
         _chk(lib().slimt_hip_translate(self.h, _p(ids), _p(lengths), B, S, _p(sl),
                                        0 if sl is None else sl.size, limit_factor, eos_id,
                                        _p(out_ids), _p(out_len), _p(align)))
-        return out_ids, out_len, align
+        return (out_ids, out_len, align, sc) if scores else (out_ids, out_len, align)
 
     def pinned_buffers(self, B: int, S: int, limit_factor: float = 1.5, want_align: bool = False):
         """This context's pinned staging arrays for a [B,S] batch: (ids, lengths, out_ids, out_len, align|None)."""
@@ -610,22 +630,28 @@ class Context:
                 pin("out").array(np.uint32, (B, T)), pin("ol").array(np.uint32, (B,)),
                 pin("al").array(np.float32, (B, T, S)) if want_align else None)
 
-    def translate_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0):
+    def translate_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
+                        scores=None):
         """slimt_hip_translate_async[_generated] on arrays from pinned_buffers() (already filled);
         synchronize() before reading the outputs. `generator`: a ShortlistGenerator -- the batch's
-        lexical shortlist is then generated on this context's stream (Model.cc:117-120)."""
+        lexical shortlist is then generated on this context's stream (Model.cc:117-120).
+        scores: a float32 [B, Tmax] array (pinned: written in place) that receives the tokens' log-probabilities."""
         p_ids, p_len, p_out, p_ol, p_al = bufs
         B, S = p_ids.shape
+        if scores is not None:
+            self._scores_array(scores, B, p_out.shape[1])
+        sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
+        if scores is not None:  # (armed right before the call that takes it)
+            self.set_scores([scores])
         if generator is not None:
             _chk(lib().slimt_hip_translate_async_generated(self.h, generator.h, _p(p_ids), _p(p_len), B, S,
                                                            limit_factor, eos_id, _p(p_out), _p(p_ol), _p(p_al)))
             return
-        sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
         _chk(lib().slimt_hip_translate_async(self.h, _p(p_ids), _p(p_len), B, S, _p(sl), 0 if sl is None else sl.size,
                                              limit_factor, eos_id, _p(p_out), _p(p_ol), _p(p_al)))
 
     def translate_pinned(self, ids, lengths, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                         want_align: bool = False, generator=None):
+                         want_align: bool = False, generator=None, scores: bool = False):
         """translate() through this context's pinned staging buffers and slimt_hip_translate_async:
         the persistent kernels then read and write host memory themselves, no copy is queued (host
         pipelines with several contexts: copies of one stream wait behind other streams' kernels).
@@ -635,12 +661,14 @@ class Context:
         bufs = self.pinned_buffers(B, S, limit_factor, want_align)
         bufs[0][...] = ids
         bufs[1][...] = lengths
-        self.translate_async(bufs, shortlist, generator, limit_factor, eos_id)
+        sc = self._pinned.setdefault("sc", _Pinned()).array(np.float32, bufs[2].shape) if scores else None
+        self.translate_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc)
         self.synchronize()
-        return bufs[2].copy(), bufs[3].copy(), (bufs[4].copy() if want_align else None)
+        out = bufs[2].copy(), bufs[3].copy(), (bufs[4].copy() if want_align else None)
+        return out + (sc.copy(),) if scores else out
 
     def translate_generated(self, generator, ids, lengths, limit_factor: float = 1.5, eos_id: int = 0,
-                            want_align: bool = False):
+                            want_align: bool = False, scores: bool = False):
         """Model::forward with its shortlist step (slimt_hip_translate_generated): host arrays, blocking."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
@@ -649,36 +677,54 @@ class Context:
         out_ids = np.zeros((B, T), dtype=np.uint32)
         out_len = np.zeros(B, dtype=np.uint32)
         align = np.zeros((B, T, S), dtype=np.float32) if want_align else None
+        sc = np.full((B, T), np.nan, dtype=np.float32) if scores else None
+        if scores:
+            self.set_scores([sc])
         _chk(lib().slimt_hip_translate_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, limit_factor,
                                                  eos_id, _p(out_ids), _p(out_len), _p(align)))
-        return out_ids, out_len, align
+        return (out_ids, out_len, align, sc) if scores else (out_ids, out_len, align)
 
     def translate_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int,
                          n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int,
-                         d_out_len: int, d_align: int = 0, steps_hint: int = 0):
-        """Device pointers (ints) in and out; asynchronous when steps_hint > 0."""
+                         d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0):
+        """Device pointers (ints) in and out; asynchronous when steps_hint > 0. scores: a device pointer to
+        [B, Tmax] floats for the tokens' log-probabilities (0 = none)."""
         vp = C.c_void_p
-        _chk(lib().slimt_hip_translate_device(
-            self.h, vp(d_ids), vp(d_lengths), B, S, vp(d_shortlist) if n_shortlist else None,
-            n_shortlist, limit_factor, eos_id, vp(d_out_ids), vp(d_out_len),
-            vp(d_align) if d_align else None, steps_hint))
+        args = (self.h, vp(d_ids), vp(d_lengths), B, S, vp(d_shortlist) if n_shortlist else None,
+                n_shortlist, limit_factor, eos_id, vp(d_out_ids), vp(d_out_len),
+                vp(d_align) if d_align else None, steps_hint)
+        if scores:  # (armed right before the call that takes it)
+            self.set_scores([scores])
+        _chk(lib().slimt_hip_translate_device(*args))
 
-    def translate_many_device(self, batches, S: int, limit_factor: float, eos_id: int, steps_hint: int = 0, generator=None):
+    def translate_many_device(self, batches, S: int, limit_factor: float, eos_id: int, steps_hint: int = 0, generator=None,
+                              scores=None):
         """slimt_hip_translate_many_device: `batches` = [(d_ids, d_lengths, B, d_shortlist, n_shortlist, d_out_ids,
         d_out_len, d_align[, S_j])] of device pointers (ints; 0 = none) -- ONE encoder and ONE decoder launch for all of them;
-        S_j: that batch's own padded length (<= S; default S)."""
+        S_j: that batch's own padded length (<= S; default S). scores: one device pointer per batch ([B_j, Tmax_j] floats)."""
+        if scores is not None and len(scores) != len(batches):
+            raise ValueError(f"scores: {len(scores)} destinations for {len(batches)} batches")
         arr = (_Batch * len(batches))()
         for j, b in enumerate(batches):
             d_ids, d_len, B, d_sl, n_sl, d_out, d_ol, d_al = b[:8]
             arr[j] = _Batch(d_ids, d_len, B, b[8] if len(b) > 8 else 0, d_sl if n_sl else None, n_sl, d_out, d_ol, d_al or None)
+        if scores is not None:  # (armed right before the call that takes it)
+            self.set_scores(list(scores))
         if generator is not None:
             _chk(lib().slimt_hip_translate_many_device_generated(self.h, generator.h, arr, len(batches), S, limit_factor, eos_id, steps_hint))
             return
         _chk(lib().slimt_hip_translate_many_device(self.h, arr, len(batches), S, limit_factor, eos_id, steps_hint))
 
-    def translate_many_async(self, bufs_list, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0, generator=None):
+    def translate_many_async(self, bufs_list, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0, generator=None,
+                             scores=None):
         """slimt_hip_translate_many_async on a list of pinned buffer tuples (ids, lengths, out_ids, out_len, align|None),
-        one shortlist (host array) or none for all; synchronize() before reading the outputs."""
+        one shortlist (host array) or none for all; synchronize() before reading the outputs.
+        scores: one float32 [B_j, Tmax_j] array per batch (pinned: the merged launch writes them in place)."""
+        if scores is not None:
+            if len(scores) != len(bufs_list):
+                raise ValueError(f"scores: {len(scores)} arrays for {len(bufs_list)} batches")
+            for a, b in zip(scores, bufs_list):
+                self._scores_array(a, b[2].shape[0], b[2].shape[1])
         sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
         arr = (_Batch * len(bufs_list))()
         S = max(b[0].shape[1] for b in bufs_list)  # the launch's padded length; a batch may be padded to fewer tokens
@@ -687,6 +733,8 @@ class Context:
                             0 if sl is None else sl.size, p_out.ctypes.data, p_ol.ctypes.data,
                             None if p_al is None else p_al.ctypes.data)
         self._many_keep = (arr, sl)
+        if scores is not None:  # (armed right before the call that takes it)
+            self.set_scores(list(scores))
         if generator is not None:  # every batch's own lexical shortlist, generated inside the encoder launch
             _chk(lib().slimt_hip_translate_many_async_generated(self.h, generator.h, arr, len(bufs_list), S, limit_factor, eos_id))
             return
@@ -694,12 +742,14 @@ class Context:
 
     def translate_device_generated(self, gen: "ShortlistGenerator", d_ids: int, d_lengths: int, B: int,
                                    S: int, limit_factor: float, eos_id: int, d_out_ids: int,
-                                   d_out_len: int, d_align: int = 0, steps_hint: int = 0):
-        """Shortlist generation + translate, all on this context's stream."""
+                                   d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0):
+        """Shortlist generation + translate, all on this context's stream. scores: as in translate_device."""
         vp = C.c_void_p
-        _chk(lib().slimt_hip_translate_device_generated(
-            self.h, gen.h, vp(d_ids), vp(d_lengths), B, S, limit_factor, eos_id, vp(d_out_ids),
-            vp(d_out_len), vp(d_align) if d_align else None, steps_hint))
+        args = (self.h, gen.h, vp(d_ids), vp(d_lengths), B, S, limit_factor, eos_id, vp(d_out_ids),
+                vp(d_out_len), vp(d_align) if d_align else None, steps_hint)
+        if scores:  # (armed right before the call that takes it)
+            self.set_scores([scores])
+        _chk(lib().slimt_hip_translate_device_generated(*args))
 
     def encode(self, ids, lengths, want_embed=False, want_layers=False):
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
@@ -833,6 +883,8 @@ def host_lib():
     H.slimt_hip_service_translate.argtypes = [vp, vp, vp, sz, vp]
     H.slimt_hip_result_view.argtypes = [vp] * 8
     H.slimt_hip_result_destroy.argtypes = [vp]
+    H.slimt_hip_service_set_scores.argtypes = [vp, C.c_int]  # (include/slimt_hip_service_scores.h)
+    H.slimt_hip_result_scores.argtypes = [vp, vp]
     _host_lib = H
     return H
 
@@ -872,9 +924,20 @@ class ServiceResult:
         self.align_offsets = arr(ptrs[5], np.uint64, self.n + 1)
         self.alignments = arr(ptrs[4], np.float32, int(self.align_offsets[-1]) if self.n else 0)
         self.source_lengths = source_lengths
+        # per target token (indexed like targets) when the service scores, else None (slimt_hip_result_scores)
+        sp = C.c_void_p()
+        if host_lib().slimt_hip_result_scores(self.h, C.byref(sp)):
+            raise SlimtHipError(host_lib().slimt_hip_service_last_error().decode())
+        self.scores = arr(sp, np.float32, int(self.target_offsets[-1]) if self.n else 0) if sp.value else None
 
     def target(self, i: int) -> np.ndarray:
         return self.targets[int(self.target_offsets[i]):int(self.target_offsets[i + 1])]
+
+    def token_scores(self, i: int) -> np.ndarray:
+        """sentence i's per-token log-probabilities (EOS included); the service must score"""
+        if self.scores is None:
+            raise SlimtHipError("the service does not score (BatchService(scores=True))")
+        return self.scores[int(self.target_offsets[i]):int(self.target_offsets[i + 1])]
 
     def alignment(self, i: int) -> np.ndarray:
         a, b = int(self.align_offsets[i]), int(self.align_offsets[i + 1])
@@ -900,9 +963,11 @@ class BatchService:
     def __init__(self, models, max_words: int = 8192, wrap_length: int = 128, limit_factor: float = 1.5,
                  workers_per_device: int = 6, pad_id: int = 0, eos_id: int = 0, alignments: bool = True,
                  lexical_shortlist: bytes = b"", source_vocab: int = 0, target_vocab: int = 0,
-                 shared_vocab: bool = False, check: bool = False, shortlist=None, merge_batches: int = 0, merge_words: int = 0):
+                 shared_vocab: bool = False, check: bool = False, shortlist=None, merge_batches: int = 0, merge_words: int = 0,
+                 scores: bool = False):
         """merge_batches / merge_words: merged launches (0 = the library's defaults: up to 8 consecutive batches of one padded
-        length per launch pair within 8192 words; merge_batches = 1: never)."""
+        length per launch pair within 8192 words; merge_batches = 1: never). scores: every result carries its target tokens'
+        log-probabilities (ServiceResult.scores / token_scores; slimt_hip_service_set_scores)."""
         self._keep = []
         cfg = _ServiceConfig(max_words, wrap_length, limit_factor, workers_per_device, pad_id, eos_id,
                              1 if alignments else 0, None, 0, source_vocab, target_vocab,
@@ -921,6 +986,10 @@ class BatchService:
         self.h = C.c_void_p()
         if host_lib().slimt_hip_service_create(C.byref(cfg), arr, len(models), C.byref(self.h)):
             raise SlimtHipError(host_lib().slimt_hip_service_last_error().decode())
+        if scores and host_lib().slimt_hip_service_set_scores(self.h, 1):
+            err = host_lib().slimt_hip_service_last_error().decode()
+            self.close()
+            raise SlimtHipError(err)
 
     def translate_flat(self, tokens: np.ndarray, offsets: np.ndarray) -> ServiceResult:
         """tokens uint32 (flat), offsets uint64 [n + 1]. Blocking; thread-safe."""

@@ -911,10 +911,15 @@ __device__ __forceinline__ void attention_row(AttnRow r, int lane) {
 // the f32 and the streamed-cache variants: same-box A/B against round 5's library, profiles/r06_merge_template_ab.txt) --
 // these kernels run at the edge of their 128 registers. The 16-row tilings for sentences of up to 64 tokens have the merged
 // twin; the engine gives a merged launch one of those.
+// SC: scored (slimt_hip_ctx_set_scores): the output layer's epilogue keeps each row's sum of exp(logit - running maximum)
+// beside its arg-max (scores.h), the reductions merge it, and the row's owner writes the token's log-probability to
+// a.scores (a.sub_scores[j]) where it writes the token. Compile-time like MG: the unscored kernels are the same
+// instruction streams as without the parameter. Only the 16-sentence tilings without clusters have the scored twin.
 template <bool MG, int KSD, int KSF, int DH, bool LONG, bool NT, int RT = 1, bool KV24 = false, int MID = 0, int SPW = 16, int CL = 1,
-          int KVI = 20>
+          int KVI = 20, bool SC = false>
 __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
   static_assert(!MG || (RT == 1 && CL == 1 && MID <= 1), "merged launches: the 16-row tilings, sentences of up to 64 tokens");
+  static_assert(!SC || (RT == 1 && CL == 1 && SPW == 16), "scored launches: the 16-sentence tilings without clusters");
   constexpr bool KV20 = KVI != 24;
   static_assert(KVI == 24 || KVI == 20 || (KVI == 16 && KV24 && (KSD == 4 || KSD == 8) && (RT == 1 || (KSD == 4 && MID == 0)) && CL == 1),
                 "16-bit form: sentences of up to 128 tokens at D = 256 (the 32-sentence tiling: up to 32), up to 32 at D = 512");
@@ -963,7 +968,8 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
   char *A3 = A2 + R * LDA;
   float *red_v = reinterpret_cast<float *>(A3 + R * LDA3);  // [NW][R]
   int *red_i = reinterpret_cast<int *>(red_v + NW * R);
-  int *flags = red_i + NW * R;  // [0] = number of finished sentences of this tile
+  float *red_s = reinterpret_cast<float *>(red_i + NW * R);  // SC: [NW][R] the candidates' sums of exponentials
+  int *flags = red_i + NW * R + (SC ? NW * R : 0);  // [0] = number of finished sentences of this tile
   float *pbufs = reinterpret_cast<float *>(flags + 16);  // [NW][256] attention scratch
   float *kvpb = pbufs + NW * PBW;  // KV24: [Ld][K pb, V pb][D], or at D = 512 [Ld][K pb, K c127, V pb, V c127][D]
   // LayerNorm scale / bias of every layer in LDS ([Ld][rnn, attn, ffn][scale, bias][D]) where it fits:
@@ -1726,12 +1732,14 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
     SLIMT_STAMP(43);
     float bv[RT][4];
     int bi[RT][4];
+    [[maybe_unused]] float bs[RT][4];  // SC: sum of exp(logit - bv) over this lane's columns so far
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         bv[rt][r] = -3.402823466e+38f;
         bi[rt][r] = 0x7fffffff;
+        if constexpr (SC) bs[rt][r] = 0.0f;
       }
     stream_gemm_from<KSD, NB_OUT, 0, (KSD >= 4), RT>(
         A1, LDA, outw, wave, lane, fl, [&](int tile, int rt, const v4i &acc, int co, float pb) {
@@ -1749,6 +1757,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
 #endif
             // a lane's columns only grow, so strict > keeps its first maximum
             const bool better = in_range && v > bv[rt][r];
+            if constexpr (SC) lse_push(v, in_range, better, bv[rt][r], bs[rt][r]);
             bv[rt][r] = better ? v : bv[rt][r];
             bi[rt][r] = better ? col : bi[rt][r];
           }
@@ -1758,10 +1767,14 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        row16_argmax(bv[rt][r], bi[rt][r]);
+        if constexpr (SC)
+          row16_argmax_lse(bv[rt][r], bi[rt][r], bs[rt][r]);
+        else
+          row16_argmax(bv[rt][r], bi[rt][r]);
         if (lr == 0) {
           red_v[wave * R + 16 * rt + lg * 4 + r] = bv[rt][r];
           red_i[wave * R + 16 * rt + lg * 4 + r] = bi[rt][r];
+          if constexpr (SC) red_s[wave * R + 16 * rt + lg * 4 + r] = bs[rt][r];
         }
       }
     SLIMT_STAMP(45);
@@ -1774,10 +1787,18 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
       if (!row_wave) break;
       const int row = 16 * rr + wave;
       uint32_t tok = 0;
+      [[maybe_unused]] float score = 0.0f;  // SC: the token's log-probability (lane 0's)
       {
         int ix;
         if constexpr (CL > 1) {
           ix = cl_ix[rr];
+        } else if constexpr (SC) {
+          float v = lane < NW ? red_v[lane * R + row] : -3.402823466e+38f;
+          ix = lane < NW ? red_i[lane * R + row] : 0x7fffffff;
+          float sum = lane < NW ? red_s[lane * R + row] : 0.0f;
+          row16_argmax_lse(v, ix, sum);
+          ix = __builtin_amdgcn_readfirstlane(ix);
+          score = lse_score(sum, ix == 0x7fffffff || nan0);
         } else {
           float v = lane < NW ? red_v[lane * R + row] : -3.402823466e+38f;
           ix = lane < NW ? red_i[lane * R + row] : 0x7fffffff;
@@ -1792,8 +1813,10 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
       }
       if (live[rr] && !finished[rr]) {  // record(), Model.cc:127-137
         const int Tr = SLIMT_SUB_TMAX(rr);
-        if (lane == 0 && (int)n_out[rr] < Tr)
+        if (lane == 0 && (int)n_out[rr] < Tr) {
           (n_sub ? a.sub[SLIMT_SW(rr)].out_ids : a.out_ids)[(size_t)(bq[rr] - SLIMT_SUB_FIRST(rr)) * Tr + n_out[rr]] = tok;
+          if constexpr (SC) (n_sub ? a.sub_scores[SLIMT_SW(rr)] : a.scores)[(size_t)(bq[rr] - SLIMT_SUB_FIRST(rr)) * Tr + n_out[rr]] = score;
+        }
         n_out[rr] += 1;
         // (merged launches: a sentence also ends at its own sub-batch's step limit -- a tile may go on for the others)
         if (tok == a.eos || (n_sub && (int)n_out[rr] >= a.sub[SLIMT_SW(rr)].max_steps)) {
@@ -1885,8 +1908,9 @@ int fused_decode_grid(int B, bool tickets, int rows) {
 // ln_in_lds (out, nullable): whether the LayerNorm constants of all layers (LN_LDS in the kernel: the
 // D = 256, 16-row, non-MID variants) still fit the 160 KiB; the returned size includes them then.
 // tight: the kernels with the 16-bit cache form inlined (KVI = 16) keep its column terms [Ld][K, V][D] behind everything else.
+// scores: the scored kernels (SC) keep one more [NW][rows] float array beside the arg-max's (red_s)
 size_t fused_decode_lds_bytes(int D, int F, int Ld, int rows, bool kv24 = false, int mid = 0,
-                              bool *ln_in_lds = nullptr, bool tight = false) {
+                              bool *ln_in_lds = nullptr, bool tight = false, bool scores = false) {
   // D * rows > 256 * 16: two f32 row buffers, SSRU cells in global memory (see the kernel)
   const size_t R = (size_t)rows;
   const bool lean = (size_t)D * R > 256 * 16;
@@ -1894,7 +1918,8 @@ size_t fused_decode_lds_bytes(int D, int F, int Ld, int rows, bool kv24 = false,
   const size_t f32rows = (lean ? 2 : 3) * R * (D + 4) * 4 + cells;
   const size_t base = f32rows + 2 * R * (size_t)(D + 32) + R * (size_t)(F + 32) + 2 * NW * R * 4 + 64 +
                       NW * (mid == 2 ? 1024 : mid == 1 ? 512 : 256) * 4 + (kv24 ? (size_t)Ld * (D == 512 ? 4 : 2) * D * 4 : 0) +
-                      (tight ? (size_t)Ld * (rows > 16 ? 1 : 2) * D * 4 : 0);  // (32 sentences: the K centres only)
+                      (tight ? (size_t)Ld * (rows > 16 ? 1 : 2) * D * 4 : 0) +  // (32 sentences: the K centres only)
+                      (scores ? (size_t)NW * R * 4 : 0);
   const size_t ln = (D == 256 && rows == 16 && !mid) ? (size_t)Ld * 6 * D * 4 : 0;
   const bool fits = ln > 0 && base + ln <= 160 * 1024;
   if (ln_in_lds) *ln_in_lds = fits;
@@ -1941,22 +1966,33 @@ bool fused_decode_supported(int D, int F, int H, int Ld) {
   return shape && fused_decode_lds_bytes(D, F, Ld, 16) <= 160 * 1024;
 }
 
+// a kernel of the launcher's choice, scored (SC) or not: nullptr where the scored twin does not exist (32-sentence,
+// 8- and 4-sentence tilings, clusters) -- a scored call there fails instead of losing its scores
+template <bool MG, bool SC, int KSD, int KSF, int DH, bool LONG, bool NT, int RT = 1, bool KV24 = false, int MID = 0, int SPW = 16,
+          int CL = 1, int KVI = 20>
+static constexpr auto dfk() -> void (*)(FusedDecodeArgs) {
+  if constexpr (SC && (RT != 1 || CL != 1 || SPW != 16))
+    return nullptr;
+  else
+    return decode_fused_kernel<MG, KSD, KSF, DH, LONG, NT, RT, KV24, MID, SPW, CL, KVI, SC>;
+}
+
 // the long-sentence instantiation exists for d_head 32 only (attention_row_long), the
 // non-temporal K/V variant for d_head 32 and 64 (the buffer-load paths of attention_row)
-template <bool MG, int KSD, int KSF, int DH>
+template <bool MG, bool SC, int KSD, int KSF, int DH>
 static auto decode_fused_pick(bool long_sentences, bool nt) -> void (*)(FusedDecodeArgs) {
   if constexpr (DH == 32) {
-    if (long_sentences) return nt ? decode_fused_kernel<MG, KSD, KSF, DH, true, true> : decode_fused_kernel<MG, KSD, KSF, DH, true, false>;
+    if (long_sentences) return nt ? dfk<MG, SC, KSD, KSF, DH, true, true>() : dfk<MG, SC, KSD, KSF, DH, true, false>();
   }
   if constexpr (DH >= 32) {
-    if (nt) return decode_fused_kernel<MG, KSD, KSF, DH, false, true>;
+    if (nt) return dfk<MG, SC, KSD, KSF, DH, false, true>();
   }
   (void)long_sentences;
   (void)nt;
-  return decode_fused_kernel<MG, KSD, KSF, DH, false, false>;
+  return dfk<MG, SC, KSD, KSF, DH, false, false>();
 }
 
-template <bool MG>
+template <bool MG, bool SC>
 static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int F, int H, hipStream_t st) {
   FusedDecodeArgs a = a_in;
   if (!fused_decode_supported(D, F, H, a.Ld)) return hipErrorInvalidValue;
@@ -1973,6 +2009,7 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
                                    : a.S <= 128 && fused_decode_tight_mid_supported(D, F, H, a.Ld, mid))))
     return hipErrorInvalidValue;
   auto go = [&](void (*k)(FusedDecodeArgs), size_t lds) -> hipError_t {
+    if (!k) return hipErrorInvalidValue;
     hipError_t e = set_dynamic_lds_once(reinterpret_cast<const void *>(k), (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, grid, dim3(1024), lds, st, a);
@@ -1980,29 +2017,29 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
   };
   // the variants over the packed cache: <KSD, KSF, DH, MID> x non-temporal K/V loads x sentences per workgroup
 #define SLIMT_KV24_PICK(KSD_, KSF_, DH_, MID_)                                                                  \
-  (rows == 4   ? (a.kv_nt ? decode_fused_kernel<MG, KSD_, KSF_, DH_, false, true, 1, true, MID_, 4>                 \
-                          : decode_fused_kernel<MG, KSD_, KSF_, DH_, false, false, 1, true, MID_, 4>)               \
-   : rows == 8 ? (a.kv_nt ? decode_fused_kernel<MG, KSD_, KSF_, DH_, false, true, 1, true, MID_, 8>                 \
-                          : decode_fused_kernel<MG, KSD_, KSF_, DH_, false, false, 1, true, MID_, 8>)               \
-               : (a.kv_nt ? decode_fused_kernel<MG, KSD_, KSF_, DH_, false, true, 1, true, MID_>                    \
-                          : decode_fused_kernel<MG, KSD_, KSF_, DH_, false, false, 1, true, MID_>))
+  (rows == 4   ? (a.kv_nt ? dfk<MG, SC, KSD_, KSF_, DH_, false, true, 1, true, MID_, 4>()                 \
+                          : dfk<MG, SC, KSD_, KSF_, DH_, false, false, 1, true, MID_, 4>())               \
+   : rows == 8 ? (a.kv_nt ? dfk<MG, SC, KSD_, KSF_, DH_, false, true, 1, true, MID_, 8>()                 \
+                          : dfk<MG, SC, KSD_, KSF_, DH_, false, false, 1, true, MID_, 8>())               \
+               : (a.kv_nt ? dfk<MG, SC, KSD_, KSF_, DH_, false, true, 1, true, MID_>()                    \
+                          : dfk<MG, SC, KSD_, KSF_, DH_, false, false, 1, true, MID_>()))
   // every cache of this launch in the 24-bit form (a.kv_fmt == nullptr): the 16-sentence tilings have an instantiation
   // with that form inlined (KVI = 24); the 8- / 4-sentence ones reach it through the fallback call
 #define SLIMT_KV24_ONLY(KSD_, KSF_, DH_, MID_)                                                        \
-  (a.kv_nt ? decode_fused_kernel<MG, KSD_, KSF_, DH_, false, true, 1, true, MID_, 16, 1, 24>          \
-           : decode_fused_kernel<MG, KSD_, KSF_, DH_, false, false, 1, true, MID_, 16, 1, 24>)
+  (a.kv_nt ? dfk<MG, SC, KSD_, KSF_, DH_, false, true, 1, true, MID_, 16, 1, 24>()          \
+           : dfk<MG, SC, KSD_, KSF_, DH_, false, false, 1, true, MID_, 16, 1, 24>())
   const bool only24 = kv24 && !a.kv_fmt && rows == 16 && a.cluster <= 1;
   if constexpr (MG) {  // (the merged twins: 16-row tilings, sentences of up to 64 tokens, no clusters)
     if (rows > 16 || mid == 2 || a.cluster > 1) return hipErrorInvalidValue;
   }
   if (mid) {
     if (rows > 16 || F != 1536) return hipErrorInvalidValue;
-    const size_t ldsm = fused_decode_lds_bytes(D, F, a.Ld, 16, true, mid, nullptr, a.kv_tight);
+    const size_t ldsm = fused_decode_lds_bytes(D, F, a.Ld, 16, true, mid, nullptr, a.kv_tight, SC);
     if (ldsm > 160 * 1024) return hipErrorInvalidValue;
     if (a.kv_tight) {
 #define SLIMT_KV16_PICK(MID_, SPW_)                                                                \
-  (a.kv_nt ? decode_fused_kernel<MG, 4, 24, 32, false, true, 1, true, MID_, SPW_, 1, 16>               \
-           : decode_fused_kernel<MG, 4, 24, 32, false, false, 1, true, MID_, SPW_, 1, 16>)
+  (a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 1, true, MID_, SPW_, 1, 16>()               \
+           : dfk<MG, SC, 4, 24, 32, false, false, 1, true, MID_, SPW_, 1, 16>())
       if (mid == 1) return go(rows == 4 ? SLIMT_KV16_PICK(1, 4) : rows == 8 ? SLIMT_KV16_PICK(1, 8) : SLIMT_KV16_PICK(1, 16), ldsm);
       if constexpr (!MG) return go(rows == 4 ? SLIMT_KV16_PICK(2, 4) : rows == 8 ? SLIMT_KV16_PICK(2, 8) : SLIMT_KV16_PICK(2, 16), ldsm);
 #undef SLIMT_KV16_PICK
@@ -2014,14 +2051,14 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
     if (only24) return go(SLIMT_KV24_ONLY(4, 24, 32, 1), ldsm);
     return go(SLIMT_KV24_PICK(4, 24, 32, 1), ldsm);
   }
-  const size_t lds = fused_decode_lds_bytes(D, F, a.Ld, rows <= 16 ? 16 : rows, kv24, 0, &a.ln_in_lds, a.kv_tight);
+  const size_t lds = fused_decode_lds_bytes(D, F, a.Ld, rows <= 16 ? 16 : rows, kv24, 0, &a.ln_in_lds, a.kv_tight, SC);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   if (kv24 && D == 512) {
     if (F != 2048) return hipErrorInvalidValue;
     if (a.kv_tight) {
 #define SLIMT_KV16_PICK(SPW_)                                                                      \
-  (a.kv_nt ? decode_fused_kernel<MG, 8, 32, 64, false, true, 1, true, 0, SPW_, 1, 16>                  \
-           : decode_fused_kernel<MG, 8, 32, 64, false, false, 1, true, 0, SPW_, 1, 16>)
+  (a.kv_nt ? dfk<MG, SC, 8, 32, 64, false, true, 1, true, 0, SPW_, 1, 16>()                  \
+           : dfk<MG, SC, 8, 32, 64, false, false, 1, true, 0, SPW_, 1, 16>())
       return go(rows == 4 ? SLIMT_KV16_PICK(4) : rows == 8 ? SLIMT_KV16_PICK(8) : SLIMT_KV16_PICK(16), lds);
 #undef SLIMT_KV16_PICK
     }
@@ -2031,15 +2068,15 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
   if constexpr (!MG) {
   if (a.cluster > 1) {  // cluster logits: the 16-sentence tiling of the D = 256 packed-cache shape
     if (!(kv24 && D == 256 && F == 1536 && rows == 16 && a.cluster == 4 && a.cl_act && a.cl_part && a.cl_sync)) return hipErrorInvalidValue;
-    return go(a.kv_nt ? decode_fused_kernel<MG, 4, 24, 32, false, true, 1, true, 0, 16, 4>
-                      : decode_fused_kernel<MG, 4, 24, 32, false, false, 1, true, 0, 16, 4>, lds);
+    return go(a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 1, true, 0, 16, 4>()
+                      : dfk<MG, SC, 4, 24, 32, false, false, 1, true, 0, 16, 4>(), lds);
   }
   }
   if (only24) return go(SLIMT_KV24_ONLY(4, 24, 32, 0), lds);
   if (kv24 && rows <= 16 && a.kv_tight) {  // sentences may be in the tight 16-bit form: the kernels with it (and the 20-bit one) inlined
 #define SLIMT_KV16_PICK(SPW_)                                                                      \
-  (a.kv_nt ? decode_fused_kernel<MG, 4, 24, 32, false, true, 1, true, 0, SPW_, 1, 16>                  \
-           : decode_fused_kernel<MG, 4, 24, 32, false, false, 1, true, 0, SPW_, 1, 16>)
+  (a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 1, true, 0, SPW_, 1, 16>()                  \
+           : dfk<MG, SC, 4, 24, 32, false, false, 1, true, 0, SPW_, 1, 16>())
     return go(rows == 4 ? SLIMT_KV16_PICK(4) : rows == 8 ? SLIMT_KV16_PICK(8) : SLIMT_KV16_PICK(16), lds);
 #undef SLIMT_KV16_PICK
   }
@@ -2049,19 +2086,20 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
   if constexpr (!MG) {
   if (rows == 32) {
     if (kv24 && a.kv_tight)
-      return go(a.kv_nt ? decode_fused_kernel<MG, 4, 24, 32, false, true, 2, true, 0, 16, 1, 16>
-                        : decode_fused_kernel<MG, 4, 24, 32, false, false, 2, true, 0, 16, 1, 16>, lds);
+      return go(a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 2, true, 0, 16, 1, 16>()
+                        : dfk<MG, SC, 4, 24, 32, false, false, 2, true, 0, 16, 1, 16>(), lds);
     if (kv24 && !a.kv_fmt)  // every cache in the 24-bit form: that form inlined (KVI = 24), as for the 16-sentence tilings
-      return go(a.kv_nt ? decode_fused_kernel<MG, 4, 24, 32, false, true, 2, true, 0, 16, 1, 24>
-                        : decode_fused_kernel<MG, 4, 24, 32, false, false, 2, true, 0, 16, 1, 24>, lds);
-    auto k = kv24 ? (a.kv_nt ? decode_fused_kernel<MG, 4, 24, 32, false, true, 2, true> : decode_fused_kernel<MG, 4, 24, 32, false, false, 2, true>)
-                  : (a.kv_nt ? decode_fused_kernel<MG, 4, 24, 32, false, true, 2> : decode_fused_kernel<MG, 4, 24, 32, false, false, 2>);
+      return go(a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 2, true, 0, 16, 1, 24>()
+                        : dfk<MG, SC, 4, 24, 32, false, false, 2, true, 0, 16, 1, 24>(), lds);
+    auto k = kv24 ? (a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 2, true>() : dfk<MG, SC, 4, 24, 32, false, false, 2, true>())
+                  : (a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 2>() : dfk<MG, SC, 4, 24, 32, false, false, 2>());
     return go(k, lds);
   }
   }
 #define SLIMT_FUSED_CASE(KSD_, KSF_, DH_)                                                   \
   if (D == 64 * KSD_ && F == 64 * KSF_ && D / H == DH_) {                                    \
-    auto k = decode_fused_pick<MG, KSD_, KSF_, DH_>(a.S > 32, a.kv_nt);                           \
+    auto k = decode_fused_pick<MG, SC, KSD_, KSF_, DH_>(a.S > 32, a.kv_nt);                           \
+    if (!k) return hipErrorInvalidValue;                                                     \
     hipError_t e = set_dynamic_lds_once(reinterpret_cast<const void *>(k), (int)lds); \
     if (e != hipSuccess) return e;                                                           \
     hipLaunchKernelGGL(k, grid, dim3(1024), lds, st, a);                                     \
@@ -2074,7 +2112,9 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
 }
 
 hipError_t launch_decode_fused(const FusedDecodeArgs &a, int D, int F, int H, hipStream_t st) {
-  return a.n_sub > 0 ? launch_decode_fused_t<true>(a, D, F, H, st) : launch_decode_fused_t<false>(a, D, F, H, st);
+  if (a.scores || a.sub_scores[0])  // (scored: every sub-batch of a merged launch has its destination; the engine checks)
+    return a.n_sub > 0 ? launch_decode_fused_t<true, true>(a, D, F, H, st) : launch_decode_fused_t<false, true>(a, D, F, H, st);
+  return a.n_sub > 0 ? launch_decode_fused_t<true, false>(a, D, F, H, st) : launch_decode_fused_t<false, false>(a, D, F, H, st);
 }
 
 }  // namespace slimt_hip

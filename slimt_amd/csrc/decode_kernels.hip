@@ -252,14 +252,18 @@ __global__ __launch_bounds__(256) void dgemm_kernel(DGemmArgs a) {
         }
       }
     }
-  } else if constexpr (EPI == EPI_ARGMAX) {
+  } else if constexpr (EPI == EPI_ARGMAX || EPI == EPI_ARGMAX_SC) {
+    // SC: beside the first maximum, the sum of exp(logit - maximum) over the same columns (scores.h)
+    constexpr bool SC = EPI == EPI_ARGMAX_SC;
     __syncthreads();  // A_lds is reused as the reduction buffer
     float *red_v = reinterpret_cast<float *>(smem);
     int *red_i = reinterpret_cast<int *>(red_v + 64);
+    float *red_s = reinterpret_cast<float *>(red_i + 64);  // (SC only)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float bv = -3.402823466e+38f;
       int bi = 0x7fffffff;
+      float bs = 0.0f;
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         const int ntile = nt0 + nt;
@@ -267,6 +271,7 @@ __global__ __launch_bounds__(256) void dgemm_kernel(DGemmArgs a) {
         if (ntile < n_tiles && col < a.w.N) {
           float v = (float)(acc[nt][r] + 127 * a.w.colsum[col]) * u;
           v = v + a.w.pb[col];
+          if constexpr (SC) lse_push(v, true, v > bv, bv, bs);
           if (v > bv || (v == bv && col < bi)) {
             bv = v;
             bi = col;
@@ -277,6 +282,10 @@ __global__ __launch_bounds__(256) void dgemm_kernel(DGemmArgs a) {
       for (int m = 1; m < 16; m <<= 1) {
         const float ov = __shfl_xor(bv, m, 64);
         const int oi = __shfl_xor(bi, m, 64);
+        if constexpr (SC) {
+          float mm = bv;
+          lse_merge(mm, bs, ov, __shfl_xor(bs, m, 64));
+        }
         if (ov > bv || (ov == bv && oi < bi)) {
           bv = ov;
           bi = oi;
@@ -285,15 +294,19 @@ __global__ __launch_bounds__(256) void dgemm_kernel(DGemmArgs a) {
       if (lr == 0) {
         red_v[wave * 16 + lg * 4 + r] = bv;
         red_i[wave * 16 + lg * 4 + r] = bi;
+        if constexpr (SC) red_s[wave * 16 + lg * 4 + r] = bs;
       }
     }
     __syncthreads();
     if (tid < 16) {
       float bv = red_v[tid];
       int bi = red_i[tid];
+      float m = bv, bs = 0.0f;
+      if constexpr (SC) bs = red_s[tid];
       for (int w = 1; w < 4; ++w) {
         const float ov = red_v[w * 16 + tid];
         const int oi = red_i[w * 16 + tid];
+        if constexpr (SC) lse_merge(m, bs, ov, red_s[w * 16 + tid]);
         if (ov > bv || (ov == bv && oi < bi)) {
           bv = ov;
           bi = oi;
@@ -303,6 +316,7 @@ __global__ __launch_bounds__(256) void dgemm_kernel(DGemmArgs a) {
       if (row < a.B) {
         a.part_val[(size_t)row * a.n_parts + blockIdx.y] = bv;
         a.part_idx[(size_t)row * a.n_parts + blockIdx.y] = bi;
+        if constexpr (SC) a.part_sum[(size_t)row * a.n_parts + blockIdx.y] = bs;
       }
     }
   }
@@ -343,6 +357,8 @@ static hipError_t launch_dgemm_t(const DGemmArgs &a, int epi, dim3 grid, size_t 
     hipLaunchKernelGGL((dgemm_kernel<PF, NT, EPI_RELU_Q, false>), grid, dim3(256), lds, st, a);
   else if (epi == EPI_ARGMAX && !i8)
     hipLaunchKernelGGL((dgemm_kernel<PF, NT, EPI_ARGMAX, false>), grid, dim3(256), lds, st, a);
+  else if (epi == EPI_ARGMAX_SC && !i8 && a.part_sum)
+    hipLaunchKernelGGL((dgemm_kernel<PF, NT, EPI_ARGMAX_SC, false>), grid, dim3(256), lds, st, a);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
@@ -356,7 +372,7 @@ hipError_t launch_dgemm(const DGemmArgs &a, int epilogue, hipStream_t st) {
   int pf, nt;
   dgemm_config(K, N, a.B, &pf, &nt);
   const int col_blocks = (N + 64 * nt - 1) / (64 * nt);
-  if (epilogue == EPI_ARGMAX && a.n_parts != col_blocks) return hipErrorInvalidValue;
+  if ((epilogue == EPI_ARGMAX || epilogue == EPI_ARGMAX_SC) && a.n_parts != col_blocks) return hipErrorInvalidValue;
   const dim3 grid((a.B + 15) / 16, col_blocks);
   size_t lds = 16 * (size_t)(K + 16) + 16 * (size_t)(D + 4) * sizeof(float);
   if (lds < 1024) lds = 1024;

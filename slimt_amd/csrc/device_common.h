@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "scores.h"
 
 namespace slimt_hip {
 
@@ -187,6 +188,30 @@ __device__ __forceinline__ void row16_argmax(float &v, int &ix) {
   argmax_step<2>(v, ix);
   argmax_step<4>(v, ix);
   argmax_step<8>(v, ix);
+}
+
+// ... and the scored twin: the row's sum of exponentials relative to its maximum, s (scores.h), merges with the
+// partner's at every step (the arg-max's value IS the maximum it is relative to)
+template <int M>
+__device__ __forceinline__ void argmax_lse_step(float &v, int &ix, float &s) {
+  float a, ov;
+  butterfly_pair<M>(v, a, ov);
+  float ia, oi;
+  butterfly_pair<M>(__int_as_float(ix), ia, oi);
+  float sa, os;
+  butterfly_pair<M>(s, sa, os);
+  const int o = __float_as_int(oi);
+  const bool take = ov > v || (ov == v && o < ix);
+  float m = v;
+  lse_merge(m, s, ov, os);
+  v = take ? ov : v;
+  ix = take ? o : ix;
+}
+__device__ __forceinline__ void row16_argmax_lse(float &v, int &ix, float &s) {
+  argmax_lse_step<1>(v, ix, s);
+  argmax_lse_step<2>(v, ix, s);
+  argmax_lse_step<4>(v, ix, s);
+  argmax_lse_step<8>(v, ix, s);
 }
 
 // xor butterfly over the 64 lanes, masks ascending; all lanes end equal.

@@ -1051,7 +1051,7 @@ void sinusoid_table(int S, int D, std::vector<float> &out) {
 void ctx_free(slimt_hip_ctx *c) {
   DevBuf *bufs[] = {&c->pos, &c->ids, &c->lengths, &c->x0, &c->x1, &c->q, &c->k, &c->v, &c->att,
                     &c->h8, &c->a8, &c->ticket, &c->kv, &c->kv_fmt, &c->cl_act, &c->cl_part, &c->cl_sync, &c->dx, &c->dx_pre, &c->dh, &c->datt8, &c->dout, &c->df8,
-                    &c->state, &c->part_val, &c->part_idx, &c->prev, &c->out_ids, &c->out_len,
+                    &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag};
   for (auto *b : bufs) b->release();
@@ -1233,6 +1233,14 @@ extern "C" int slimt_hip_ctx_set_decode_mode(slimt_hip_ctx *ctx, int mode) {
   if (!ctx) return fail(-1, "ctx is NULL");
   if (mode < 0 || mode > 6) return fail(-1, "bad decode mode %d", mode);
   ctx->decode_mode = mode;
+  return 0;
+}
+
+extern "C" int slimt_hip_ctx_set_scores(slimt_hip_ctx *ctx, float *const *scores, size_t n) {
+  if (!ctx) return fail(-1, "null argument");
+  if (!scores && n) return fail(-1, "scores is NULL");
+  ctx->sc_next.assign(scores, scores + n);  // (checked by the call that takes them: ScoreCall)
+  ctx->sc_armed = n > 0;  // (n = 0: nothing armed)
   return 0;
 }
 
@@ -1433,6 +1441,38 @@ struct MergePlan {
   int max_N = 0;  // columns of the widest job
   size_t stride_wp = 0, stride_cs = 0, stride_pb = 0;
   bool dense = false;  // one output layer for all sub-batches: no holes between them (kernels.h, FusedDecodeArgs::sub_dense)
+  float *scores[kMaxMerge] = {};  // scored launches: sub-batch j's destination, device-visible (FusedDecodeArgs::sub_scores)
+};
+
+// The scores armed on a context (slimt_hip_ctx_set_scores) are taken by the translate entry point that comes next, whether
+// that call then succeeds or fails. n: the destinations the call needs (1, or its number of batches). An entry point that
+// another one calls for a batch of its own (the batch-by-batch fallbacks) finds nothing armed and keeps what its caller set.
+struct ScoreCall {
+  slimt_hip_ctx *c = nullptr;
+  std::vector<float *> dst;
+  int rc = 0;
+  ScoreCall(slimt_hip_ctx *ctx, size_t n) {
+    if (!ctx || !ctx->sc_armed) return;
+    c = ctx;
+    dst.swap(ctx->sc_next);
+    ctx->sc_armed = false;
+    ctx->sc_next.clear();
+    if (dst.size() != n) {
+      rc = fail(-1, "scores: %zu destinations armed, the call has %zu batches", dst.size(), n);
+    } else {
+      for (size_t j = 0; j < n && !rc; ++j)
+        if (!dst[j]) rc = fail(-1, "scores: destination %zu is NULL", j);
+    }
+    ctx->sc_call = rc == 0;
+    ctx->sc_user = rc == 0 && n == 1 ? dst[0] : nullptr;
+    ctx->sc_dev = nullptr;
+  }
+  ~ScoreCall() {
+    if (!c) return;
+    c->sc_call = false;
+    c->sc_user = nullptr;
+    c->sc_dev = nullptr;
+  }
 };
 
 // gen (nullable; only where fused_encoder_chosen): the batch's shortlist is generated inside the encoder launch
@@ -1930,6 +1970,13 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   ds.n_finished = c->n_finished.as<int>();
   ds.Tmax = (int)Tmax;
   ds.eos = eos_id;
+  // a scored call (ScoreCall): each recorded token's log-probability goes beside it -- to c->sc_dev, or in a merged launch
+  // to each sub-batch's mp->scores[j] (the entry points set them to addresses the kernels can write)
+  const bool scored = c->sc_call;
+  float *const d_scores = scored && !mp ? c->sc_dev : nullptr;
+  if (scored && !mp && !d_scores) return fail(-1, "scores: no destination for this batch");
+  for (int j = 0; scored && mp && j < mp->n; ++j)
+    if (!mp->scores[j]) return fail(-1, "scores: no destination for batch %d", j);
   if (lean) {
     PackArgs job;
     if (n_sl && mp) {
@@ -2020,10 +2067,12 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     // encoder is only allowed it when this context's decoders take those: kv_tight_wanted; a mode changed between the two
     // calls, or a first large output layer, ends up here)
     const bool tight = kv24 && c->kv_tight && c->kv_fmt_valid && c->kv_fmt_B == (int)B;
-    const bool clusters = cluster_ok && c->decode_mode == 6 && !tight && !mp;
+    // (scored calls: the 16-sentence tilings without clusters, the only ones with the scored twin -- decode modes 2-6 and
+    // the adaptive rows are "16 rows" for them)
+    const bool clusters = cluster_ok && c->decode_mode == 6 && !tight && !mp && !scored;
     c->expect_large_output = n_expected > 16384;
     f.kv_tight = tight;
-    f.rows_per_wg = clusters ? 16 : c->decode_mode == 2 ? 16 : c->decode_mode == 3 ? 32 : c->decode_mode == 4 ? 8 : c->decode_mode == 5 ? 4
+    f.rows_per_wg = clusters || scored ? 16 : c->decode_mode == 2 ? 16 : c->decode_mode == 3 ? 32 : c->decode_mode == 4 ? 8 : c->decode_mode == 5 ? 4
                     : (n_expected > 16384 ? 32 : 0);
     if (tight && f.rows_per_wg == 32 && !(S <= 32 && fused_decode_tight_rows32_supported(m->D, m->F, m->H, m->Ld))) f.rows_per_wg = 16;
     if (mp && f.rows_per_wg == 32) f.rows_per_wg = 16;  // (merged launches: the 16-row tilings only, decode_fused.hip)
@@ -2071,10 +2120,12 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
       f.kv_u4096[l][0] = wk.w.u * (1.0f / 4096.0f);  // ... as accS * 4096 from the narrow form (unpack20)
       f.kv_u4096[l][1] = wv.w.u * (1.0f / 4096.0f);
     }
+    f.scores = d_scores;
     if (mp) {
       f.n_sub = mp->n;
       f.sub_dense = mp->dense ? 1 : 0;
       for (int j = 0; j < mp->n; ++j) f.sub[j] = mp->out[j];
+      for (int j = 0; scored && j < mp->n; ++j) f.sub_scores[j] = mp->scores[j];
       f.out_stride_wp = mp->stride_wp;
       f.out_stride_cs = mp->stride_cs;
       f.out_stride_pb = mp->stride_pb;
@@ -2248,13 +2299,15 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   }
   const int n_parts = dgemm_col_blocks(out.w.K, out.w.N, (int)B);
   const EmbedArgs e = embed_args(c);
+  if (d_scores) HIPCHK(c->part_sum.reserve(B * (size_t)n_parts * 4));
+  float *const part_sum = d_scores ? c->part_sum.as<float>() : nullptr;
   const size_t max_steps = steps_hint > 0 ? (size_t)steps_hint : (Tmax > 1 ? Tmax : 1);
   int rc = 0;
   size_t t = 0;
   bool all_done = false;
   for (; t < max_steps && !rc; ++t) {
     hipError_t he = launch_decode_begin_step(e, ds, (int)B, t == 0, 1, c->part_val.as<float>(),
-                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st);
+                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores);
     if (he != hipSuccess) { rc = fail((int)he, "decode_begin_step: %s", hipGetErrorString(he)); break; }
     if (steps_hint <= 0 && t > 0 && (t % 8) == 0) {
       // stop as soon as every sentence has emitted EOS (Model.cc:161)
@@ -2273,15 +2326,16 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     g.part_val = c->part_val.as<float>();
     g.part_idx = c->part_idx.as<int>();
     g.n_parts = n_parts;
+    g.part_sum = part_sum;
     {
       ProfScope p(c, SLIMT_HIP_K_LOGITS, gemm_macs((int)B, out.w), gemm_bytes(out.w));
-      he = launch_dgemm(g, EPI_ARGMAX, st);
+      he = launch_dgemm(g, d_scores ? EPI_ARGMAX_SC : EPI_ARGMAX, st);
     }
     if (he != hipSuccess) { rc = fail((int)he, "logits gemm: %s", hipGetErrorString(he)); break; }
   }
   if (!rc && !all_done) {
     hipError_t he = launch_decode_begin_step(e, ds, (int)B, 0, 0, c->part_val.as<float>(),
-                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st);
+                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores);
     if (he != hipSuccess) rc = fail((int)he, "final record: %s", hipGetErrorString(he));
   }
   return rc;
@@ -2365,11 +2419,14 @@ extern "C" int slimt_hip_translate_device(slimt_hip_ctx *ctx, const uint32_t *d_
                                           float limit_factor, uint32_t eos_id,
                                           uint32_t *d_out_ids, uint32_t *d_out_len,
                                           float *d_align, int steps_hint) {
+  ScoreCall sc(ctx, 1);
+  if (sc.rc) return sc.rc;
   if (!ctx || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len) return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
   if (n_shortlist > (size_t)ctx->model->V) return fail(-1, "shortlist larger than the vocabulary");
   if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
   HIPCHK(hipSetDevice(ctx->model->device));
+  if (ctx->sc_call) ctx->sc_dev = ctx->sc_user;  // (device memory, like the other outputs)
   return translate_device(ctx, d_src_ids, d_lengths, d_shortlist, B, S, n_shortlist, limit_factor,
                           eos_id, d_out_ids, d_out_len, d_align, steps_hint);
 }
@@ -2411,11 +2468,14 @@ int translate_host(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *
                           (fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S) ||
                            long_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S));
   hclk.lap(0);
+  float *const scores = ctx->sc_call ? ctx->sc_user : nullptr;  // (a scored call: the caller's [B][Tmax] host array)
   if (!wait && persistent) {
     void *v_ids = host_device_view(src_ids), *v_len = host_device_view(lengths), *v_out = host_device_view(out_ids),
          *v_ol = host_device_view(out_len), *v_al = align ? host_device_view(align) : nullptr;
+    void *v_sc = scores ? host_device_view(scores) : nullptr;
     hclk.lap(6);
-    if (v_ids && v_len && v_out && v_ol && (!align || v_al)) {
+    if (v_ids && v_len && v_out && v_ol && (!align || v_al) && (!scores || v_sc)) {
+      ctx->sc_dev = static_cast<float *>(v_sc);
       // alignment rows (Model.cc:84-108) are staged in device memory and leave for the host once per
       // sentence, as whole 16-byte stores when its loop ends: written row by row across PCIe from
       // inside the step loop they cost the Service 28 % (12.9 against 17.9 M tok/s)
@@ -2430,6 +2490,10 @@ int translate_host(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *
   }
   HIPCHK(ctx->out_ids.reserve(B * Tmax * 4));
   if (align) HIPCHK(ctx->align.reserve(B * Tmax * S * 4));
+  if (scores) {
+    HIPCHK(ctx->sc_stage.reserve(B * Tmax * 4));
+    ctx->sc_dev = ctx->sc_stage.as<float>();
+  }
   HIPCHK(hipMemcpyAsync(ctx->ids.p, src_ids, B * S * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(ctx->lengths.p, lengths, B * 4, hipMemcpyHostToDevice, st));
   // asynchronous callers never read back inside the loop: a fixed step budget (the persistent
@@ -2441,6 +2505,7 @@ int translate_host(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *
   HIPCHK(hipMemcpyAsync(out_ids, ctx->out_ids.p, B * Tmax * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(out_len, ctx->out_len.p, B * 4, hipMemcpyDeviceToHost, st));
   if (align) HIPCHK(hipMemcpyAsync(align, ctx->align.p, B * Tmax * S * 4, hipMemcpyDeviceToHost, st));
+  if (scores) HIPCHK(hipMemcpyAsync(scores, ctx->sc_stage.p, B * Tmax * 4, hipMemcpyDeviceToHost, st));
   if (wait) RCCHK(slimt_hip_ctx_synchronize(ctx));  // sleeps on a blocking-sync event (a worker per context: no spinning)
   return 0;
 }
@@ -2451,6 +2516,8 @@ extern "C" int slimt_hip_translate(slimt_hip_ctx *ctx, const uint32_t *src_ids,
                                    const uint32_t *shortlist, size_t n_shortlist,
                                    float limit_factor, uint32_t eos_id, uint32_t *out_ids,
                                    uint32_t *out_len, float *align) {
+  ScoreCall sc(ctx, 1);
+  if (sc.rc) return sc.rc;
   return translate_host(ctx, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, true);
 }
@@ -2460,6 +2527,8 @@ extern "C" int slimt_hip_translate_async(slimt_hip_ctx *ctx, const uint32_t *src
                                          const uint32_t *shortlist, size_t n_shortlist,
                                          float limit_factor, uint32_t eos_id, uint32_t *out_ids,
                                          uint32_t *out_len, float *align) {
+  ScoreCall sc(ctx, 1);
+  if (sc.rc) return sc.rc;
   return translate_host(ctx, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, false);
 }
@@ -2561,6 +2630,8 @@ extern "C" size_t slimt_hip_translate_many_rows(const size_t *B, size_t n_batche
 
 extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_hip_batch *batches, size_t n_batches, size_t S,
                                                float limit_factor, uint32_t eos_id, int steps_hint) {
+  ScoreCall sc(ctx, n_batches);
+  if (sc.rc) return sc.rc;
   if (!ctx || !batches || n_batches == 0) return fail(-1, "null argument");
   HIPCHK(hipSetDevice(ctx->model->device));
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
@@ -2571,12 +2642,14 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
   for (size_t j = 0; j < n_batches; ++j) n_cols = std::max(n_cols, batches[j].n_shortlist ? batches[j].n_shortlist : (size_t)ctx->model->V);
   if (mergeable)
     RCCHK(build_merge_plan(ctx, batches, n_batches, S, Tmax, limit_factor, steps_hint, nullptr, mp, rows, merge_tile(ctx, n_cols)));
+  for (size_t j = 0; mergeable && ctx->sc_call && j < n_batches; ++j) mp.scores[j] = sc.dst[j];
   if (mergeable && rows <= ctx->max_B && rows * S <= ctx->max_M && S <= ctx->max_S && merge_supported(ctx, rows, S))
     return translate_device(ctx, batches[0].src_ids, batches[0].lengths, batches[0].shortlist, rows, S, (size_t)mp.max_N,
                             limit_factor, eos_id, batches[0].out_ids, batches[0].out_len, batches[0].align, steps_hint, nullptr,
                             nullptr, 0, nullptr, &mp);
   for (size_t j = 0; j < n_batches; ++j) {  // batch by batch, in order, on the same stream
     const slimt_hip_batch &b = batches[j];
+    if (ctx->sc_call) ctx->sc_user = sc.dst[j];
     RCCHK(slimt_hip_translate_device(ctx, b.src_ids, b.lengths, b.B, b.S ? b.S : S, b.shortlist, b.n_shortlist, limit_factor,
                                      eos_id, b.out_ids, b.out_len, b.align, steps_hint));
   }
@@ -2585,12 +2658,15 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
 
 extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hip_batch *batches, size_t n_batches, size_t S,
                                               float limit_factor, uint32_t eos_id) {
+  ScoreCall sc(ctx, n_batches);
+  if (sc.rc) return sc.rc;
   if (!ctx || !batches || n_batches == 0) return fail(-1, "null argument");
   const slimt_hip_model *m = ctx->model;
   HIPCHK(hipSetDevice(m->device));
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
   bool merged = n_batches > 1 && n_batches <= (size_t)kMaxMerge && S <= ctx->max_S;
   slimt_hip_batch dev[kMaxMerge];
+  float *dev_sc[kMaxMerge] = {};  // (scored: the device views of the pinned score arrays)
   bool any_align = false;
   size_t rows = 0;
   for (size_t j = 0; merged && j < n_batches; ++j) {
@@ -2610,6 +2686,7 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
     dev[j].out_len = static_cast<uint32_t *>(host_device_view(b.out_len));
     dev[j].align = b.align ? static_cast<float *>(host_device_view(b.align)) : nullptr;
     if (!dev[j].src_ids || !dev[j].lengths || !dev[j].out_ids || !dev[j].out_len || (b.align && !dev[j].align)) merged = false;
+    if (ctx->sc_call && !(dev_sc[j] = static_cast<float *>(host_device_view(sc.dst[j])))) merged = false;
     any_align = any_align || b.align != nullptr;
     rows += b.B;  // (one shortlist for all: the sub-batches follow each other densely)
   }
@@ -2617,6 +2694,7 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   if (!merged) {
     for (size_t j = 0; j < n_batches; ++j) {
       const slimt_hip_batch &b = batches[j];
+      if (ctx->sc_call) ctx->sc_user = sc.dst[j];
       RCCHK(translate_host(ctx, b.src_ids, b.lengths, b.B, b.S ? b.S : S, b.shortlist, b.n_shortlist, limit_factor, eos_id,
                            b.out_ids, b.out_len, b.align, false));
     }
@@ -2642,6 +2720,7 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   }
   MergePlan mp;
   RCCHK(build_merge_plan(ctx, dev, n_batches, S, Tmax, limit_factor, 0, any_align ? ctx->align.as<float>() : nullptr, mp, rows));
+  for (size_t j = 0; ctx->sc_call && j < n_batches; ++j) mp.scores[j] = dev_sc[j];
   return translate_device(ctx, dev[0].src_ids, dev[0].lengths, dev[0].shortlist, rows, S, (size_t)mp.max_N, limit_factor, eos_id,
                           dev[0].out_ids, dev[0].out_len, any_align ? ctx->align.as<float>() : nullptr, (int)Tmax, nullptr,
                           any_align ? dev[0].align : nullptr, 0, nullptr, &mp);
@@ -3038,6 +3117,8 @@ extern "C" int slimt_hip_translate_device_generated(slimt_hip_ctx *ctx, slimt_hi
                                                     float limit_factor, uint32_t eos_id,
                                                     uint32_t *d_out_ids, uint32_t *d_out_len,
                                                     float *d_align, int steps_hint) {
+  ScoreCall sc(ctx, 1);
+  if (sc.rc) return sc.rc;
   if (!ctx || !sl || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len)
     return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
@@ -3046,6 +3127,7 @@ extern "C" int slimt_hip_translate_device_generated(slimt_hip_ctx *ctx, slimt_hi
   if (sl->target_vocab != (size_t)m->V)
     return fail(-1, "shortlist target vocabulary %zu != model vocabulary %d", sl->target_vocab, m->V);
   HIPCHK(hipSetDevice(m->device));
+  if (ctx->sc_call) ctx->sc_dev = ctx->sc_user;  // (device memory, like the other outputs)
   return translate_generated(ctx, sl, d_src_ids, d_lengths, B, S, limit_factor, eos_id, d_out_ids, d_out_len,
                              d_align, steps_hint, nullptr);
 }
@@ -3074,10 +3156,13 @@ int translate_host_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
   const bool persistent = fused_decoder_allowed(ctx) && fused_decode_supported(m->D, m->F, m->H, m->Ld) &&
                           (fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S) ||
                            long_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S));
+  float *const scores = ctx->sc_call ? ctx->sc_user : nullptr;  // (translate_host)
   if (!wait && persistent) {  // pinned buffers: the kernels read and write host memory themselves (translate_host)
     void *v_ids = host_device_view(src_ids), *v_len = host_device_view(lengths), *v_out = host_device_view(out_ids),
          *v_ol = host_device_view(out_len), *v_al = align ? host_device_view(align) : nullptr;
-    if (v_ids && v_len && v_out && v_ol && (!align || v_al)) {
+    void *v_sc = scores ? host_device_view(scores) : nullptr;
+    if (v_ids && v_len && v_out && v_ol && (!align || v_al) && (!scores || v_sc)) {
+      ctx->sc_dev = static_cast<float *>(v_sc);
       if (align) HIPCHK(ctx->align.reserve(align_staging_bytes(ctx, B, S, Tmax, limit_factor)));
       return translate_generated(ctx, sl, static_cast<const uint32_t *>(v_ids), static_cast<const uint32_t *>(v_len),
                                  B, S, limit_factor, eos_id, static_cast<uint32_t *>(v_out),
@@ -3087,6 +3172,10 @@ int translate_host_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
   }
   HIPCHK(ctx->out_ids.reserve(B * Tmax * 4));
   if (align) HIPCHK(ctx->align.reserve(B * Tmax * S * 4));
+  if (scores) {
+    HIPCHK(ctx->sc_stage.reserve(B * Tmax * 4));
+    ctx->sc_dev = ctx->sc_stage.as<float>();
+  }
   HIPCHK(hipMemcpyAsync(ctx->ids.p, src_ids, B * S * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(ctx->lengths.p, lengths, B * 4, hipMemcpyHostToDevice, st));
   RCCHK(translate_generated(ctx, sl, ctx->ids.as<uint32_t>(), ctx->lengths.as<uint32_t>(), B, S, limit_factor,
@@ -3095,6 +3184,7 @@ int translate_host_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
   HIPCHK(hipMemcpyAsync(out_ids, ctx->out_ids.p, B * Tmax * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(out_len, ctx->out_len.p, B * 4, hipMemcpyDeviceToHost, st));
   if (align) HIPCHK(hipMemcpyAsync(align, ctx->align.p, B * Tmax * S * 4, hipMemcpyDeviceToHost, st));
+  if (scores) HIPCHK(hipMemcpyAsync(scores, ctx->sc_stage.p, B * Tmax * 4, hipMemcpyDeviceToHost, st));
   if (wait) RCCHK(slimt_hip_ctx_synchronize(ctx));  // sleeps on a blocking-sync event (a worker per context: no spinning)
   return 0;
 }
@@ -3106,7 +3196,10 @@ namespace {
 // when it is possible, else batch by batch through translate_generated
 int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const slimt_hip_batch *dev, size_t n, size_t S,
                              float limit_factor, uint32_t eos_id, int steps_hint, bool stage_align,
-                             const slimt_hip_batch *host = nullptr) {
+                             const slimt_hip_batch *host = nullptr, float *const *sc_dev = nullptr,
+                             float *const *sc_host = nullptr) {
+  // sc_dev / sc_host (a scored call): each batch's score destination as the kernels write it (device memory, or the device
+  // view of a pinned array) and, with `host`, as the caller gave it
   // host (the asynchronous entry point): the same batches with the caller's HOST pointers -- what the batch-by-batch
   // fallback hands to translate_host_generated, which knows when the kernels can use pinned arrays in place
   const slimt_hip_model *m = ctx->model;
@@ -3128,6 +3221,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
   if (!merged && host) {
     for (size_t j = 0; j < n; ++j) {
       const slimt_hip_batch &b = host[j];
+      if (ctx->sc_call) ctx->sc_user = sc_host[j];
       RCCHK(translate_host_generated(ctx, sl, b.src_ids, b.lengths, b.B, b.S ? b.S : S, limit_factor, eos_id, b.out_ids, b.out_len,
                                      b.align, false));
     }
@@ -3143,6 +3237,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
         staging = ctx->align.as<float>();
       }
       RCCHK(check_batch(ctx, b.B, Sj));
+      if (ctx->sc_call) ctx->sc_dev = sc_dev[j];
       RCCHK(translate_generated(ctx, sl, b.src_ids, b.lengths, b.B, Sj, limit_factor, eos_id, b.out_ids, b.out_len,
                                 staging ? staging : b.align, steps_hint > 0 ? std::min(steps_hint, (int)Tj) : (stage_align ? (int)Tj : 0),
                                 staging ? b.align : nullptr));
@@ -3162,6 +3257,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
   if (any_align && stage_align) HIPCHK(ctx->align.reserve(align_staging_bytes(ctx, rows, S, Tmax, limit_factor)));
   MergePlan mp;
   RCCHK(build_merge_plan(ctx, plan, n, S, Tmax, limit_factor, steps_hint, any_align && stage_align ? ctx->align.as<float>() : nullptr, mp, rows, tile));
+  for (size_t j = 0; ctx->sc_call && j < n; ++j) mp.scores[j] = sc_dev[j];
   ShortlistArgs a;
   shortlist_args(sl, plan[0].src_ids, plan[0].lengths, plan[0].B, S, ctx->shortlist.as<uint32_t>(), ctx->n_sl_dev.as<uint32_t>(), a);
   void *hint_dev = nullptr;
@@ -3185,6 +3281,8 @@ int check_generator(const slimt_hip_ctx *ctx, const slimt_hip_shortlist *sl) {
 extern "C" int slimt_hip_translate_many_device_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const slimt_hip_batch *batches,
                                                          size_t n_batches, size_t S, float limit_factor, uint32_t eos_id,
                                                          int steps_hint) {
+  ScoreCall sc(ctx, n_batches);
+  if (sc.rc) return sc.rc;
   if (!ctx || !sl || !batches || n_batches == 0) return fail(-1, "null argument");
   RCCHK(check_generator(ctx, sl));
   for (size_t j = 0; j < n_batches; ++j) {
@@ -3193,17 +3291,21 @@ extern "C" int slimt_hip_translate_many_device_generated(slimt_hip_ctx *ctx, sli
     if ((b.S ? b.S : S) > S) return fail(-1, "batch %zu is padded to %zu tokens, the launch to %zu", j, b.S, S);
   }
   HIPCHK(hipSetDevice(ctx->model->device));
-  return translate_many_generated(ctx, sl, batches, n_batches, S, limit_factor, eos_id, steps_hint, false);
+  return translate_many_generated(ctx, sl, batches, n_batches, S, limit_factor, eos_id, steps_hint, false, nullptr,
+                                  ctx->sc_call ? sc.dst.data() : nullptr);
 }
 
 extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const slimt_hip_batch *batches,
                                                         size_t n_batches, size_t S, float limit_factor, uint32_t eos_id) {
+  ScoreCall sc(ctx, n_batches);
+  if (sc.rc) return sc.rc;
   if (!ctx || !sl || !batches || n_batches == 0) return fail(-1, "null argument");
   RCCHK(check_generator(ctx, sl));
   const slimt_hip_model *m = ctx->model;
   HIPCHK(hipSetDevice(m->device));
   const uint32_t vmax = (uint32_t)std::min((size_t)m->V, sl->source_vocab);
   slimt_hip_batch dev[kMaxMerge];
+  float *dev_sc[kMaxMerge] = {};  // (scored: the device views of the pinned score arrays)
   bool pinned = n_batches <= (size_t)kMaxMerge;
   for (size_t j = 0; j < n_batches; ++j) {
     const slimt_hip_batch &b = batches[j];
@@ -3222,10 +3324,14 @@ extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slim
     dev[j].out_len = static_cast<uint32_t *>(host_device_view(b.out_len));
     dev[j].align = b.align ? static_cast<float *>(host_device_view(b.align)) : nullptr;
     if (!dev[j].src_ids || !dev[j].lengths || !dev[j].out_ids || !dev[j].out_len || (b.align && !dev[j].align)) pinned = false;
+    if (ctx->sc_call && !(dev_sc[j] = static_cast<float *>(host_device_view(sc.dst[j])))) pinned = false;
   }
-  if (pinned) return translate_many_generated(ctx, sl, dev, n_batches, S, limit_factor, eos_id, 0, true, batches);
+  if (pinned)
+    return translate_many_generated(ctx, sl, dev, n_batches, S, limit_factor, eos_id, 0, true, batches,
+                                    ctx->sc_call ? dev_sc : nullptr, ctx->sc_call ? sc.dst.data() : nullptr);
   for (size_t j = 0; j < n_batches; ++j) {  // pageable arrays, or too many batches: one by one through the copying path
     const slimt_hip_batch &b = batches[j];
+    if (ctx->sc_call) ctx->sc_user = sc.dst[j];
     RCCHK(translate_host_generated(ctx, sl, b.src_ids, b.lengths, b.B, b.S ? b.S : S, limit_factor, eos_id, b.out_ids, b.out_len,
                                    b.align, false));
   }
@@ -3235,6 +3341,8 @@ extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slim
 extern "C" int slimt_hip_translate_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const uint32_t *src_ids,
                                              const uint32_t *lengths, size_t B, size_t S, float limit_factor,
                                              uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align) {
+  ScoreCall sc(ctx, 1);
+  if (sc.rc) return sc.rc;
   return translate_host_generated(ctx, sl, src_ids, lengths, B, S, limit_factor, eos_id, out_ids, out_len, align, true);
 }
 
@@ -3242,5 +3350,7 @@ extern "C" int slimt_hip_translate_async_generated(slimt_hip_ctx *ctx, slimt_hip
                                                    const uint32_t *src_ids, const uint32_t *lengths, size_t B,
                                                    size_t S, float limit_factor, uint32_t eos_id,
                                                    uint32_t *out_ids, uint32_t *out_len, float *align) {
+  ScoreCall sc(ctx, 1);
+  if (sc.rc) return sc.rc;
   return translate_host_generated(ctx, sl, src_ids, lengths, B, S, limit_factor, eos_id, out_ids, out_len, align, false);
 }

@@ -183,6 +183,13 @@ struct slimt_hip_ctx {
   // decoder workspace
   slimt_hip::DevBuf dx, dx_pre, dh, datt8, dout, df8, state;
   slimt_hip::DevBuf part_val, part_idx;
+  // per-token scores (include/slimt_hip.h, slimt_hip_ctx_set_scores): armed for the NEXT translate call, which consumes them
+  bool sc_armed = false;
+  std::vector<float *> sc_next;
+  bool sc_call = false;      // the call in progress scores (engine.cpp, ScoreCall)
+  float *sc_user = nullptr;  // the current batch's destination as the caller gave it (host or device memory)
+  float *sc_dev = nullptr;   // ... the address the kernels write: sc_user, its pinned view, or sc_stage
+  slimt_hip::DevBuf part_sum, sc_stage;  // the step-wise path's partial sums; device staging of a host call's scores
   slimt_hip::DevBuf prev, out_ids, out_len, finished, n_finished, align;
   slimt_hip::DevBuf shortlist;
   slimt_hip::DevBuf sl_scratch;  // bitmaps of slimt_hip_shortlist_generate_device (kept zeroed)

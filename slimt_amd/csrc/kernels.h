@@ -78,6 +78,7 @@ enum GemmEpilogue {
   EPI_RES_LN = 2,  // LN(deq + res) over the full row        -> f32 [M][ldy]
   EPI_ARGMAX = 3,  // per-row first-max over this block's columns -> partials
   EPI_ACC = 4,     // raw accS                               -> int32 [M][N]
+  EPI_ARGMAX_SC = 5,  // EPI_ARGMAX + each partial's sum of exponentials (DGemmArgs::part_sum; dgemm only)
 };
 
 struct GemmArgs {
@@ -168,9 +169,12 @@ struct DecodeState {
 // Reduce the argmax partials of the previous step (if first == 0), record the
 // tokens (Model.cc:127-137) and build the next decoder input embedding
 // (Transformer.cc:133-160). with_embed == 0: sample/record only (last step).
+// part_sum / scores (both or neither): the partials' sums of exponentials (EPI_ARGMAX_SC) and the [B][Tmax]
+// destination of each recorded token's log-probability (scores.h), written beside out_ids
 hipError_t launch_decode_begin_step(const EmbedArgs &e, const DecodeState &s, int B, int first,
                                     int with_embed, const float *part_val, const int *part_idx,
-                                    int n_parts, float *x, hipStream_t st);
+                                    int n_parts, float *x, hipStream_t st, const float *part_sum = nullptr,
+                                    float *scores = nullptr);
 // set prev tokens explicitly (step-wise parity API) and embed
 hipError_t launch_embed_decoder(const EmbedArgs &e, const uint32_t *prev, int B, int first,
                                 float *x, hipStream_t st);
@@ -219,6 +223,8 @@ struct DGemmArgs {
   int *part_idx = nullptr;
   int n_parts = 0;
   float eps = 1e-6f;
+  // EPI_ARGMAX_SC: beside each partial's maximum, the sum of its columns' exp(logit - maximum) (scores.h)
+  float *part_sum = nullptr;
 };
 int dgemm_col_blocks(int K, int N, int B);
 hipError_t launch_dgemm(const DGemmArgs &a, int epilogue, hipStream_t st);
@@ -423,6 +429,10 @@ struct FusedDecodeArgs {
   // half the sentences' layer 1, ...)
   int kv_temporal_eighths = 0;
   OccTrace trace;
+  // the scored kernels (decode_fused_kernel<..., SC = true>, scores.h): per-token log-probabilities, [B][Tmax] like
+  // out_ids and written where and when it is; merged launches: sub-batch j's in sub_scores[j] (MergeOut keeps its layout)
+  float *scores = nullptr;
+  float *sub_scores[kMaxMerge] = {};
 };
 // hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), but only when
 // `bytes` exceeds what was already set for this kernel on the current device: the call takes

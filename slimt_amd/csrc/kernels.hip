@@ -588,30 +588,40 @@ hipError_t launch_embed_encoder(const EmbedArgs &e, const uint32_t *ids, int B, 
 
 // One block (64 threads) per sentence. Position is ALWAYS 0 in the decoder
 // (Transformer.cc:160); step 0 embeds zeros (Transformer.cc:138-144).
+// SC: the scored twin -- the partials' sums of exponentials merge with the same order as the arg-max (scores.h) and
+// each recorded token's log-probability goes to scores beside out_ids (the trailing arguments are not read otherwise)
+template <bool SC>
 __global__ __launch_bounds__(64) void decode_begin_step_kernel(EmbedArgs e, DecodeState s,
                                                                int first, int with_embed,
                                                                const float *part_val,
                                                                const int *part_idx, int n_parts,
-                                                               float *x) {
+                                                               float *x, const float *part_sum, float *scores) {
   const int b = blockIdx.x;
   __shared__ uint32_t tok_s;
   if (!first && threadIdx.x == 0) {
     // finish the argmax: partials are in ascending column order
     float bv = part_val[(size_t)b * n_parts];
     int bi = part_idx[(size_t)b * n_parts];
+    float m = bv, sum = 0.0f;
+    if constexpr (SC) sum = part_sum[(size_t)b * n_parts];
     for (int p = 1; p < n_parts; ++p) {
       const float v = part_val[(size_t)b * n_parts + p];
+      if constexpr (SC) lse_merge(m, sum, v, part_sum[(size_t)b * n_parts + p]);
       if (v > bv) {
         bv = v;
         bi = part_idx[(size_t)b * n_parts + p];
       }
     }
+    const bool none = bi == 0x7fffffff || (s.pb0 && (*s.pb0 != *s.pb0 || s.u_out != s.u_out));
     if (bi == 0x7fffffff) bi = 0;  // every logit NaN or -inf: class 0 (Transformer.cc:287-298), never out of range
     if (s.pb0 && (*s.pb0 != *s.pb0 || s.u_out != s.u_out)) bi = 0;  // logit[0] is NaN: the reference's scan never leaves class 0
     const uint32_t tok = s.shortlist ? s.shortlist[bi] : (uint32_t)bi;
     s.prev[b] = tok;
     if (!s.finished[b]) {  // record(), Model.cc:127-137
       const uint32_t n = s.out_len[b];
+      if constexpr (SC) {
+        if ((int)n < s.Tmax) scores[(size_t)b * s.Tmax + n] = lse_score(sum, none);
+      }
       if ((int)n < s.Tmax) s.out_ids[(size_t)b * s.Tmax + n] = tok;
       s.out_len[b] = n + 1;
       if (tok == s.eos) {
@@ -636,9 +646,15 @@ __global__ __launch_bounds__(64) void decode_begin_step_kernel(EmbedArgs e, Deco
 
 hipError_t launch_decode_begin_step(const EmbedArgs &e, const DecodeState &s, int B, int first,
                                     int with_embed, const float *part_val, const int *part_idx,
-                                    int n_parts, float *x, hipStream_t st) {
-  hipLaunchKernelGGL(decode_begin_step_kernel, dim3(B), dim3(64), 0, st, e, s, first, with_embed,
-                     part_val, part_idx, n_parts, x);
+                                    int n_parts, float *x, hipStream_t st, const float *part_sum,
+                                    float *scores) {
+  if ((part_sum != nullptr) != (scores != nullptr)) return hipErrorInvalidValue;
+  if (scores)
+    hipLaunchKernelGGL(decode_begin_step_kernel<true>, dim3(B), dim3(64), 0, st, e, s, first, with_embed,
+                       part_val, part_idx, n_parts, x, part_sum, scores);
+  else
+    hipLaunchKernelGGL(decode_begin_step_kernel<false>, dim3(B), dim3(64), 0, st, e, s, first, with_embed,
+                       part_val, part_idx, n_parts, x, part_sum, scores);
   return hipGetLastError();
 }
 

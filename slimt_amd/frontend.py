@@ -70,6 +70,10 @@ class Response:  # Response.hh: source / target with sentence + token ranges, so
     source: AnnotatedText = field(default_factory=AnnotatedText)
     target: AnnotatedText = field(default_factory=AnnotatedText)
     alignments: List[Alignment] = field(default_factory=list)
+    # translate(..., scores=True): per target sentence, the log-probability of each of its target tokens (EOS included)
+    # and their sum (no length normalisation); empty otherwise
+    token_scores: List[np.ndarray] = field(default_factory=list)
+    sentence_scores: List[float] = field(default_factory=list)
 
     def to(self, encoding: Encoding) -> None:
         self.source.to(encoding)
@@ -213,14 +217,14 @@ class Service:
         step = self.ENGINE_LIMIT - 1
         return [body[i:i + step] + [eos] for i in range(0, len(body), step)]
 
-    def _engine(self, model: Model) -> "capi.BatchService":
+    def _engine(self, model: Model, scores: bool = False) -> "capi.BatchService":
         """The C++ batching service for `model` (host/Service.{hh,cc} behind include/slimt_hip_service.h):
         token-budget batches under the rule of _batches, `workers` double-buffered workers with pinned
         staging, the batch's lexical shortlist generated on the device (Model.cc:117-120). Units,
         batches, padding and result routing used to be Python objects; they are C++ now, and one call
-        carries a whole translate()."""
+        carries a whole translate(). A scoring service is one of its own (scores are set before its first call)."""
         with self._lock:
-            eng = self._engines.get(model.id)
+            eng = self._engines.get((model.id, scores))
             if eng is None:
                 V = model.dims[2]
                 eng = capi.BatchService([model.engine], max_words=max(self.max_words, 1),
@@ -228,11 +232,13 @@ class Service:
                                         limit_factor=self.limit_factor, workers_per_device=self.workers, pad_id=0,
                                         eos_id=model.vocabulary.eos_id(), alignments=True,
                                         lexical_shortlist=model.shortlist_blob, source_vocab=V, target_vocab=V,
-                                        shared_vocab=False, check=False)  # as Model.cc:73-80 constructs it
-                self._engines[model.id] = eng
+                                        shared_vocab=False, check=False,  # as Model.cc:73-80 constructs it
+                                        scores=scores)
+                self._engines[(model.id, scores)] = eng
         return eng
 
-    def _translate_segments(self, model: Model, per_request: List[List[List[int]]]):
+    def _translate_segments(self, model: Model, per_request: List[List[List[int]]], scores: bool = False):
+        """per request, per segment: (target ids, alignment, token scores | None)"""
         eos = model.vocabulary.eos_id()
         flat, owner = [], []  # the sentences of the one request the C++ service gets; (request, index, piece)
         pieces_of = {}
@@ -254,8 +260,9 @@ class Service:
         histories = [[None] * len(segs) for segs in per_request]
         if not flat:
             return histories
-        res = self._engine(model).translate(flat)
+        res = self._engine(model, scores).translate(flat)
         targets, t_off = res.targets.copy(), res.target_offsets.astype(np.int64)
+        tok_sc = res.scores.copy() if scores else None
         align, a_off = res.alignments.copy(), res.align_offsets.astype(np.int64)
         src_len = res.source_lengths
         res.close()
@@ -270,24 +277,27 @@ class Service:
             for hist in histories:
                 for i in range(len(hist)):
                     words = words_all[to[n]:to[n + 1]]
-                    hist[i] = (words, _LazyAlignment(align, ao[n], ao[n + 1], len(words), sl[n]))
+                    hist[i] = (words, _LazyAlignment(align, ao[n], ao[n + 1], len(words), sl[n]),
+                               tok_sc[to[n]:to[n + 1]] if scores else None)
                     n += 1
             return histories
         for n, (r, i, k) in enumerate(owner):
             words = words_all[to[n]:to[n + 1]]
             alignment = _LazyAlignment(align, ao[n], ao[n + 1], len(words), sl[n])
+            sc = tok_sc[to[n]:to[n + 1]] if scores else None
             if (r, i) in pieces_of:
-                parts[(r, i, k)] = (words, alignment.array(), sl[n])
+                parts[(r, i, k)] = (words, alignment.array(), sl[n], sc)
             else:
-                histories[r][i] = (words, alignment)
+                histories[r][i] = (words, alignment, sc)
         for (r, i), n in pieces_of.items():
             # a split segment: targets concatenated (inner EOS dropped), alignment rows block-diagonal
-            # over the pieces' source tokens (the pieces' inner EOS columns dropped, the last one kept)
+            # over the pieces' source tokens (the pieces' inner EOS columns dropped, the last one kept); scores
+            # concatenated like the targets (the inner EOS tokens' dropped with them)
             got = [parts[(r, i, k)] for k in range(n)]
-            widths = [L - 1 for _, _, L in got[:-1]] + [got[-1][2]]
+            widths = [L - 1 for _, _, L, _ in got[:-1]] + [got[-1][2]]
             total = sum(widths)
-            out_words, rows, col = [], [], 0
-            for k, (words, alignment, L) in enumerate(got):
+            out_words, rows, col, out_sc = [], [], 0, []
+            for k, (words, alignment, L, sc) in enumerate(got):
                 last = k == n - 1
                 keep = len(words) if last or not len(words) or words[-1] != eos else len(words) - 1
                 for t in range(keep):
@@ -295,15 +305,18 @@ class Service:
                     row[col:col + widths[k]] = np.asarray(alignment[t], np.float32)[:widths[k]]
                     rows.append(row)
                 out_words.extend(int(w) for w in words[:keep])
+                if scores:
+                    out_sc.append(sc[:keep])
                 col += widths[k]
-            histories[r][i] = (out_words, np.stack(rows) if rows else np.zeros((0, total), np.float32))
+            histories[r][i] = (out_words, np.stack(rows) if rows else np.zeros((0, total), np.float32),
+                               np.concatenate(out_sc) if scores else None)
         return histories
 
     # -- the binding's calls -----------------------------------------------------------------------
     def _respond_many(self, model: Model, sources: Sequence[AnnotatedText], histories) -> List[Response]:
         """Request::complete (Request.cc:136-170) for a whole call: every sentence's ids decoded in
         one SentencePiece batch, the source's gaps kept, target token ranges resolved on demand."""
-        flat = [words for hist in histories for words, _ in hist]  # lists of ids
+        flat = [h[0] for hist in histories for h in hist]  # lists of ids
         decoded = model.vocabulary.decode_text_batch(flat, self.workers) if flat else []
         out, k, v = [], 0, model.vocabulary
         for source, hist in zip(sources, histories):
@@ -313,7 +326,7 @@ class Service:
             resp = Response(source=source)
             parts, sent, alignments = [], resp.target._sent, resp.alignments
             src_sent, data, prev_end, pos = source._sent, source.data, 0, 0
-            for s, (words, alignment) in enumerate(hist):
+            for s, (words, alignment, sc) in enumerate(hist):
                 w = src_sent[s]
                 lazy = type(w) is _Lazy
                 gap = data[prev_end:(w.begin if lazy else w[0])]  # source.gap_bytes(s)
@@ -325,6 +338,9 @@ class Service:
                 parts.append(text)
                 sent.append(_Lazy(begin, pos, len(words), functools.partial(_target_boundaries, v, begin, words)))
                 alignments.append(alignment)
+                if sc is not None:
+                    resp.token_scores.append(sc)
+                    resp.sentence_scores.append(float(np.sum(sc, dtype=np.float64)))
                 k += 1
             parts.append(data[prev_end:] if hist else data)  # the gap behind the last sentence
             resp.target.data = b"".join(parts)
@@ -332,7 +348,9 @@ class Service:
         return out
 
     def translate(self, model: Model, texts: Sequence[str], html: bool = False,
-                  encoding: Encoding = Encoding.UTF8) -> List[Response]:
+                  encoding: Encoding = Encoding.UTF8, scores: bool = False) -> List[Response]:
+        """scores: every Response also carries token_scores (per target sentence, each target token's log-probability,
+        EOS included; a wrapped segment's pieces concatenated) and sentence_scores (their sums)."""
         if html:
             raise NotImplementedError("HTML markup transfer is outside the ported path (SURVEY.md §2)")
         # Large calls go through in chunks of documents, pipelined: while the engine translates chunk k
@@ -342,7 +360,7 @@ class Service:
         chunk = self.pipeline_documents
         if len(texts) <= chunk:
             processed = model.processor.process_many(texts, self.wrap_length, self.workers)
-            histories = self._translate_segments(model, [segs for _, segs in processed])
+            histories = self._translate_segments(model, [segs for _, segs in processed], scores)
             out = self._respond_many(model, [src for src, _ in processed], histories)
         else:
             from concurrent.futures import ThreadPoolExecutor
@@ -353,7 +371,8 @@ class Service:
                     out.extend(self._respond_many(model, [src for src, _ in processed], fut.result()))
                 for k in range(0, len(texts), chunk):
                     processed = model.processor.process_many(texts[k:k + chunk], self.wrap_length, self.workers)
-                    pending.append((processed, pool.submit(self._translate_segments, model, [segs for _, segs in processed])))
+                    pending.append((processed, pool.submit(self._translate_segments, model, [segs for _, segs in processed],
+                                                           scores)))
                     while len(pending) > 2:
                         finish(pending.pop(0))
                 while pending:
@@ -362,14 +381,16 @@ class Service:
             r.to(encoding)
         return out
 
-    def pivot(self, first: Model, second: Model, texts: Sequence[str], html: bool = False) -> List[Response]:
+    def pivot(self, first: Model, second: Model, texts: Sequence[str], html: bool = False,
+              scores: bool = False) -> List[Response]:
         """source -> pivot with `first`, pivot -> target with `second`, sentence for sentence;
-        alignments are marginalised over the pivot tokens (Response.cc:13-195)."""
+        alignments are marginalised over the pivot tokens (Response.cc:13-195). scores: the SECOND hop's scores --
+        those of the final target tokens given the pivot text (the pivot's own probability is not in them)."""
         if html:
             raise NotImplementedError("HTML markup transfer is outside the ported path (SURVEY.md §2)")
         firsts = self.translate(first, texts, encoding=Encoding.Byte)
         second_in = [second.processor.process_annotated(r.target) for r in firsts]
-        histories = self._translate_segments(second, [segs for _, segs in second_in])
+        histories = self._translate_segments(second, [segs for _, segs in second_in], scores)
         seconds = self._respond_many(second, [src for src, _ in second_in], histories)
         return [combine(r1, r2) for r1, r2 in zip(firsts, seconds)]
 
@@ -442,4 +463,5 @@ def combine(first: Response, second: Response) -> Response:  # Response.cc:179-1
     if len(first.alignments):
         r.alignments = remap_alignments(first, second)
     r.source, r.target = first.source, second.target
+    r.token_scores, r.sentence_scores = second.token_scores, second.sentence_scores
     return r

@@ -184,6 +184,14 @@ void Worker::forward_many_async_generated(slimt_hip_shortlist *generator, const 
     raise("slimt_hip_translate_many_async_generated");
 }
 
+// (weak: the Service's sanitizer builds link a test double of the engine that predates scores; a Worker asked to score
+// there fails instead of leaving the link unresolved)
+#pragma weak slimt_hip_ctx_set_scores
+void Worker::arm_scores(float *const *scores, size_t n) {
+  if (!slimt_hip_ctx_set_scores) throw std::runtime_error("this engine has no per-token scores");
+  if (slimt_hip_ctx_set_scores(ctx_, scores, n)) raise("slimt_hip_ctx_set_scores");
+}
+
 void Worker::wait() {
   if (slimt_hip_ctx_synchronize(ctx_)) raise("slimt_hip_ctx_synchronize");
 }

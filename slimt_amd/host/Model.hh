@@ -30,6 +30,9 @@ struct Hypothesis {  // slimt/Types.hh:55-61
   // `alignment` when the producer was asked for flat rows (ServiceConfig::flat_alignments: the C ABI,
   // whose callers want arrays -- one allocation per sentence instead of one per target token)
   std::vector<float> alignment_flat;
+  // per-token log-probabilities of `target` (one per token, EOS included) when the producer was asked for them
+  // (ServiceConfig::scores; include/slimt_hip.h, slimt_hip_ctx_set_scores); empty otherwise
+  std::vector<float> scores;
   size_t padded_length = 0;  // diagnostic: the S of the batch this sentence was translated in
   uint64_t batch = 0;        // diagnostic: serial number of that batch (Service: batches in launch order)
 };
@@ -159,6 +162,9 @@ class Worker {
   // ... each batch with its own lexical shortlist, generated inside the encoder launch (slimt_hip_translate_many_async_generated)
   void forward_many_async_generated(slimt_hip_shortlist *generator, const slimt_hip_batch *batches, size_t n, size_t S,
                                     float limit_factor);
+  // the next forward_*async call also writes each token's log-probability: scores[j] = [B_j][T_j] (pinned, like the
+  // outputs) of batch j (slimt_hip_ctx_set_scores)
+  void arm_scores(float *const *scores, size_t n);
   void wait();
 
  private:

@@ -142,7 +142,7 @@ class Pinned {
 struct Service::Slot {
   std::unique_ptr<Worker> worker;
   Pinned<uint32_t> ids, lengths, out_ids, out_len, shortlist;
-  Pinned<float> align;
+  Pinned<float> align, scores;
   std::vector<Unit> batch;  // non-empty while a translate is in flight on this slot
   uint64_t serial = 0;
   // `batch` is the concatenation of the launch's batches (one, or several merged: ServiceConfig::merge_batches), each with
@@ -234,6 +234,13 @@ Service::~Service() {
                  static_cast<unsigned long long>(merged_launches_.load() - merged_base_),
                  static_cast<unsigned long long>(launches_.load() - launches_base_), n);
   }
+}
+
+bool Service::set_scores(bool on) {
+  std::lock_guard<std::mutex> lock(mutex_);  // (the workers read config_.scores only for batches queued after this)
+  if (sequence_ > 0) return false;
+  config_.scores = on;
+  return true;
 }
 
 std::future<Histories> Service::translate(std::vector<Words> sentences) {
@@ -369,6 +376,12 @@ void Service::launch(Slot &slot, std::vector<Unit> &batch, slimt_hip_shortlist *
   uint32_t *out_ids = slot.out_ids.ensure(n_out), *out_len = slot.out_len.ensure(B);
   float *align = config_.alignments ? slot.align.ensure(n_align) : nullptr;
   const Slot::Part &p0 = slot.parts[0];
+  if (config_.scores) {  // every part's [B][T] scores beside its tokens (the same offsets in the slot's staging)
+    float *scores = slot.scores.ensure(n_out);
+    std::vector<float *> dst(slot.parts.size());
+    for (size_t j = 0; j < slot.parts.size(); ++j) dst[j] = scores + slot.parts[j].out_at;
+    slot.worker->arm_scores(dst.data(), dst.size());
+  }
   if (generator && slot.parts.size() == 1) {  // the batch's own lexical shortlist, generated on the worker's stream (Model.cc:117-120)
     slot.worker->forward_async_generated(generator, ids, lengths, B, p0.S, config_.tgt_length_limit_factor, out_ids,
                                          out_len, align);
@@ -416,6 +429,14 @@ void Service::finish(Slot &slot) {
     histories.push_back(collect(slot.out_ids.get() + p.out_at, slot.out_len.get() + p.first,
                                 config_.alignments ? slot.align.get() + p.align_at : nullptr, slot.lengths.get() + p.first, p.B,
                                 p.S, p.T, /*flat=*/true));
+  if (config_.scores)
+    for (size_t j = 0; j < slot.parts.size(); ++j) {
+      const Slot::Part &p = slot.parts[j];
+      for (size_t b = 0; b < p.B; ++b) {
+        const float *row = slot.scores.get() + p.out_at + b * p.T;
+        histories[j][b]->scores.assign(row, row + histories[j][b]->target.size());
+      }
+    }
   lap.to(ns_collect_);
   std::vector<Unit> batch = std::move(slot.batch);
   slot.batch.clear();
@@ -468,6 +489,7 @@ void Service::work(const Model *model, slimt_hip_shortlist *generator) {
       s.out_len.ensure(rows);
       s.out_ids.ensure(out_tokens);
       if (config_.alignments) s.align.ensure(out_tokens * longest_);
+      s.scores.ensure(out_tokens);  // (small: allocated whether or not the service scores, set_scores may come later)
       if (config_.shortlist && !generator) {
         uint32_t *sl = s.shortlist.ensure(config_.shortlist->size());
         std::copy(config_.shortlist->begin(), config_.shortlist->end(), sl);

@@ -112,6 +112,7 @@ struct ServiceConfig {
   bool warn_hw_queues = true;
   bool alignments = true;
   bool flat_alignments = false;  // Hypothesis::alignment_flat instead of ::alignment (one block per sentence)
+  bool scores = false;           // Hypothesis::scores: every target token's log-probability (Service::set_scores)
   // Output vocabulary of a batch, one policy for the service's lifetime:
   //  * lexical_shortlist set: the reference's own -- ShortlistGenerator::generate on every batch's
   //    source words (Model.cc:60-82,117-120; Shortlist.cc:115-175) -- run on the device, on the
@@ -139,6 +140,8 @@ class Service {
   // Queue one request. Throws std::invalid_argument for an empty sentence or one longer
   // than the service accepts; a failure on a worker arrives through the future.
   std::future<Histories> translate(std::vector<Words> sentences);
+  // per-token scores on or off (ServiceConfig::scores): only before the first translate(); false once one has been made
+  bool set_scores(bool on);
   // restart the SLIMT_SERVICE_STATS counters (benchmarks: after the warm-up pass)
   void stats_reset() {
     stats_base_ = batches_.load();

@@ -10,6 +10,7 @@
 
 #include "Service.hh"
 #include "slimt_hip_service.h"
+#include "slimt_hip_service_scores.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -25,12 +26,15 @@ int fail(const char *fmt, ...) {
 struct slimt_hip_service {
   std::vector<std::unique_ptr<slimt::Model>> models;  // non-owning views of the caller's replicas
   std::unique_ptr<slimt::Service> service;
+  bool scores = false;  // slimt_hip_service_set_scores
 };
 
 struct slimt_hip_result {
   std::vector<uint32_t> targets, padded;
   std::vector<uint64_t> target_offsets, batch, align_offsets;
   std::vector<float> alignments;
+  std::vector<float> scores;  // per target token, by target_offsets (a scoring service only)
+  bool scored = false;
 };
 
 extern "C" const char *slimt_hip_service_last_error(void) { return g_err; }
@@ -107,10 +111,16 @@ extern "C" int slimt_hip_service_translate(slimt_hip_service *service, const uin
     }
     r->targets.reserve(n_tok);
     r->alignments.reserve(n_al);
+    r->scored = service->scores;
+    if (r->scored) r->scores.reserve(n_tok);
     for (size_t i = 0; i < n; ++i) {
       const slimt::Hypothesis &h = *hs[i];
       r->targets.insert(r->targets.end(), h.target.begin(), h.target.end());
       r->alignments.insert(r->alignments.end(), h.alignment_flat.begin(), h.alignment_flat.end());
+      if (r->scored) {
+        if (h.scores.size() != h.target.size()) return fail("sentence %zu: %zu scores for %zu tokens", i, h.scores.size(), h.target.size());
+        r->scores.insert(r->scores.end(), h.scores.begin(), h.scores.end());
+      }
       r->target_offsets[i + 1] = r->targets.size();
       r->align_offsets[i + 1] = r->alignments.size();
       r->padded[i] = static_cast<uint32_t>(h.padded_length);
@@ -145,5 +155,18 @@ extern "C" int slimt_hip_result_view(const slimt_hip_result *r, size_t *n, const
 
 extern "C" int slimt_hip_result_destroy(slimt_hip_result *result) {
   delete result;
+  return 0;
+}
+
+extern "C" int slimt_hip_service_set_scores(slimt_hip_service *service, int on) {
+  if (!service) return fail("null argument");
+  if (!service->service->set_scores(on != 0)) return fail("set_scores: only before the first slimt_hip_service_translate");
+  service->scores = on != 0;
+  return 0;
+}
+
+extern "C" int slimt_hip_result_scores(const slimt_hip_result *r, const float **scores) {
+  if (!r || !scores) return fail("null argument");
+  *scores = r->scored ? r->scores.data() : nullptr;
   return 0;
 }
