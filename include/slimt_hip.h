@@ -334,7 +334,7 @@ int slimt_hip_translate_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids,
  * size share one packed output layer. */
 typedef struct slimt_hip_batch {
   const uint32_t *src_ids;   /* [B][S] */
-  const uint32_t *lengths;   /* [B] */
+  const uint32_t *lengths;   /* [B]; a device length past this batch's own S is that S (host lengths past it: an error) */
   size_t B;
   size_t S;                  /* this batch's padded length, <= the call's S; 0 = the call's S */
   const uint32_t *shortlist; /* sorted unique target ids, or NULL with n_shortlist == 0: full vocabulary */

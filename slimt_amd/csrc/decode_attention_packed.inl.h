@@ -272,8 +272,8 @@ template <int KV_AUX, class F>
 __device__ __forceinline__ void attention_packed32(AttnRow r, int lane, lcf_ptr pbk, lcf_ptr pbv, const F f) {
   constexpr int D = 256, DH = 32, H = D / DH;
   constexpr int KQ = F::KQ, VQ = F::VQ, VK = F::VK, NVF = F::NVF, NG = 32 / VK;
-  const int S = r.S, len = r.len;
-  const int lenf = len > 0 ? len : S;
+  const int S = r.S, len = r.len, K = r.keys;  // (AttnRow::keys)
+  const int lenf = len > 0 ? len : K;
   const float minus_inf = -99999999.0f;  // Input.cc:56-61
   const float lowest = -3.402823466e+38f;
   const int hh = lane >> 5, j = lane & 31;
@@ -315,9 +315,9 @@ __device__ __forceinline__ void attention_packed32(AttnRow r, int lane, lcf_ptr 
     float s = __builtin_fmaf(t, f.uk, ckh[hp]);
     if (r.alpha != 1.0f) s = r.alpha * s;
     s = s + mask;
-    if (j >= S) s = lowest;
+    if (j >= K) s = lowest;
     const float m = half_max(s);
-    const float e = j < S ? exp_p(s - m) : 0.0f;
+    const float e = j < K ? exp_p(s - m) : 0.0f;
     const float sum = half_sum(e);
     const float p = e / sum;  // keys >= S: exactly 0
     const float ps = half_sum(p);  // P_h
@@ -351,8 +351,8 @@ template <int KV_AUX, class F, int PART = 0, int SPW = 16>
 __device__ __forceinline__ void attention_packed64(AttnRow r, int lane, lcf_ptr pbk, lcf_ptr pbv, const F f) {
   constexpr int D = 256, DH = 32, H = D / DH;
   constexpr int KQ = F::KQ, VQ = F::VQ, VK = F::VK, NVF = F::NVF, NG = 64 / VK;
-  const int S = r.S, len = r.len;
-  const int lenf = len > 0 ? len : S;
+  const int S = r.S, len = r.len, K = r.keys;  // (AttnRow::keys)
+  const int lenf = len > 0 ? len : K;
   const float minus_inf = -99999999.0f;  // Input.cc:56-61
   const float lowest = -3.402823466e+38f;
   const int j = lane;
@@ -389,9 +389,9 @@ __device__ __forceinline__ void attention_packed64(AttnRow r, int lane, lcf_ptr 
     float s = __builtin_fmaf(t, f.uk, r.hsum[8 + h]);
     if (r.alpha != 1.0f) s = r.alpha * s;
     s = s + mask;
-    if (j >= S) s = lowest;
+    if (j >= K) s = lowest;
     const float m = wave_max(s);
-    const float e = j < S ? exp_p(s - m) : 0.0f;
+    const float e = j < K ? exp_p(s - m) : 0.0f;
     const float sum = wave_sum(e);
     const float p = e / sum;  // keys >= S: exactly 0
     const float ps = wave_sum(p);  // P_h
@@ -442,7 +442,8 @@ __device__ __forceinline__ void attention_packed128(AttnRow r, int lane, lcf_ptr
   constexpr int D = 256, DH = 32, H = D / DH;
   constexpr int KQ = F::KQ, VQ = F::VQ, VK = F::VK, NV = F::NVL;
   const int S = __builtin_amdgcn_readfirstlane(r.S), len = __builtin_amdgcn_readfirstlane(r.len);
-  const int lenf = len > 0 ? len : S;
+  const int K = __builtin_amdgcn_readfirstlane(r.keys);  // (AttnRow::keys)
+  const int lenf = len > 0 ? len : K;
   const float minus_inf = -99999999.0f;  // Input.cc:56-61
   const float lowest = -3.402823466e+38f;
   const int j0 = lane, j1 = lane + 64;
@@ -490,11 +491,11 @@ __device__ __forceinline__ void attention_packed128(AttnRow r, int lane, lcf_ptr
     }
     s0 = s0 + mask0;
     s1 = s1 + mask1;
-    if (j0 >= S) s0 = lowest;
-    if (j1 >= S) s1 = lowest;
+    if (j0 >= K) s0 = lowest;
+    if (j1 >= K) s1 = lowest;
     const float m = wave_max(fmaxf(s0, s1));
-    const float e0 = j0 < S ? exp_p(s0 - m) : 0.0f;
-    const float e1 = j1 < S ? exp_p(s1 - m) : 0.0f;
+    const float e0 = j0 < K ? exp_p(s0 - m) : 0.0f;
+    const float e1 = j1 < K ? exp_p(s1 - m) : 0.0f;
     const float sum = wave_sum(e0 + e1);
     const float p0 = e0 / sum, p1 = e1 / sum;  // keys >= S: exactly 0
     r.pbuf[h * 128 + j0] = p0;
@@ -568,8 +569,8 @@ __device__ __forceinline__ void attention_packed32_d64(AttnRow r, int lane, lcf_
   constexpr int D = 512, DH = 64, H = D / DH;
   constexpr int KQ = F::KQ, VQ = F::VQ, VK = F::VK, NG = 32 / VK;
   static_assert(F::NVF == 2 && VK == 8, "the narrow and the tight form");
-  const int S = r.S, len = r.len;
-  const int lenf = len > 0 ? len : S;
+  const int S = r.S, len = r.len, K = r.keys;  // (AttnRow::keys)
+  const int lenf = len > 0 ? len : K;
   const float minus_inf = -99999999.0f;  // Input.cc:56-61
   const float lowest = -3.402823466e+38f;
   const int hh = lane >> 5, j = lane & 31;
@@ -596,9 +597,9 @@ __device__ __forceinline__ void attention_packed32_d64(AttnRow r, int lane, lcf_
     float s = __builtin_fmaf(t, f.uk, ch);
     if (r.alpha != 1.0f) s = r.alpha * s;
     s = s + mask;
-    if (j >= S) s = lowest;
+    if (j >= K) s = lowest;
     const float m = half_max(s);
-    const float e = j < S ? exp_p(s - m) : 0.0f;
+    const float e = j < K ? exp_p(s - m) : 0.0f;
     const float sum = half_sum(e);
     const float p = e / sum;  // keys >= S: exactly 0
     const float ps = half_sum(p);  // P_h
@@ -662,8 +663,8 @@ __device__ __forceinline__ f4 unpack24cf(int d0, int d1, int d2, f4 c127) {
 template <int KV_AUX>
 __device__ __forceinline__ void attention_row24_64(AttnRow r, int lane, lcf_ptr kc, float uk256, float uv256) {
   constexpr int D = 512, DH = 64, H = D / DH;
-  const int S = r.S, len = r.len;
-  const int lenf = len > 0 ? len : S;
+  const int S = r.S, len = r.len, K = r.keys;  // (AttnRow::keys)
+  const int lenf = len > 0 ? len : K;
   const float minus_inf = -99999999.0f;  // Input.cc:56-61
   const float lowest = -3.402823466e+38f;
   const int j = lane & 31;
@@ -705,9 +706,9 @@ __device__ __forceinline__ void attention_row24_64(AttnRow r, int lane, lcf_ptr 
     float s = __builtin_fmaf(t, uk256, ch);
     if (r.alpha != 1.0f) s = r.alpha * s;
     s = s + mask;
-    if (j >= S) s = lowest;
+    if (j >= K) s = lowest;
     const float m = half_max(s);
-    const float e = j < S ? exp_p(s - m) : 0.0f;
+    const float e = j < K ? exp_p(s - m) : 0.0f;
     const float sum = half_sum(e);
     const float p = e / sum;  // keys >= S: exactly 0
     const float ps = half_sum(p);  // P_h
@@ -795,6 +796,7 @@ __device__ __noinline__ void attention_packed_cold(AttnRow r, int lane, lcf_ptr 
   if constexpr (SHAPE != 2) {  // (the 65..128-token body does it itself)
     r.S = __builtin_amdgcn_readfirstlane(r.S);
     r.len = __builtin_amdgcn_readfirstlane(r.len);
+    r.keys = __builtin_amdgcn_readfirstlane(r.keys);
   }
   attention_packed<SHAPE, KV_AUX>(r, lane, c0, c1, f);
 }

@@ -448,6 +448,10 @@ struct AttnRow {
   SLIMT_LDS float *pbuf;  // LDS: 64 floats of per-wave scratch
   SLIMT_LDS float *hsum;  // LDS: 16 floats of per-wave scratch (the heads' probability sums P_h)
   int S, len;
+  // the sentence's keys: S, or a merged sub-batch's own padded length (MergeOut::S). Keys from there on weigh exactly 0, and an
+  // empty sentence spreads its all-masked softmax over these (tests/test_gpu_length_edges.py,
+  // test_merged_sub_batches_at_their_length_edges). S stays the K/V row stride.
+  int keys;
   float alpha, aq_o;
   gf_ptr attn;   // nullable [H][S]
   gf_ptr align;  // nullable [S]: head 0 (update_alignment, Model.cc:84-108)
@@ -483,7 +487,8 @@ template <int D, int DH, int KV_AUX>
 __device__ __noinline__ void attention_row_long(AttnRow r, int lane) {
   constexpr int H = D / DH;
   const int S = __builtin_amdgcn_readfirstlane(r.S), len = __builtin_amdgcn_readfirstlane(r.len);
-  const int lenf = len > 0 ? len : S;  // keys fetched
+  const int K = __builtin_amdgcn_readfirstlane(r.keys);
+  const int lenf = len > 0 ? len : K;  // keys fetched
   const float minus_inf = -99999999.0f;  // Input.cc:56-61
   const float lowest = -3.402823466e+38f;
   {
@@ -538,13 +543,13 @@ __device__ __noinline__ void attention_row_long(AttnRow r, int lane) {
           s = __builtin_fmaf(s, uk, ch);
           if (r.alpha != 1.0f) s = r.alpha * s;
           s = s + (1.0f - (key < len ? 1.0f : 0.0f)) * minus_inf;
-          if (key >= S) s = lowest;
+          if (key >= K) s = lowest;
         }
         sc[g] = s;
       }
       const float m = half_max(fmaxf(fmaxf(sc[0], sc[2]), fmaxf(sc[1], sc[3])));
 #pragma unroll
-      for (int g = 0; g < 4; ++g) sc[g] = (32 * g + j) < S ? exp_p(sc[g] - m) : 0.0f;
+      for (int g = 0; g < 4; ++g) sc[g] = (32 * g + j) < K ? exp_p(sc[g] - m) : 0.0f;
       const float sum = half_sum(sc[0] + sc[2]) + half_sum(sc[1] + sc[3]);
 #pragma unroll
       for (int g = 0; g < 4; ++g) sc[g] = sc[g] / sum;  // keys >= S: exactly 0
@@ -599,8 +604,8 @@ constexpr int kPastDescriptor = 0x40000000;  // lane offset no K/V descriptor re
 template <int D, int DH, bool LONG, int KV_AUX = 0>
 __device__ __forceinline__ void attention_row(AttnRow r, int lane) {
   constexpr int H = D / DH;
-  const int S = r.S, len = r.len;
-  const int lenf = len > 0 ? len : S;  // keys fetched (an empty sentence masks everything: uniform weights over real V)
+  const int S = r.S, len = r.len, K = r.keys;
+  const int lenf = len > 0 ? len : K;  // keys fetched (an empty sentence masks everything: uniform weights over real V)
   const float minus_inf = -99999999.0f;  // Input.cc:56-61
   const float lowest = -3.402823466e+38f;
   if (DH == 32 && S <= 32) {
@@ -668,9 +673,9 @@ __device__ __forceinline__ void attention_row(AttnRow r, int lane) {
       s = __builtin_fmaf(s, r.uk, ck[hp]);
       if (r.alpha != 1.0f) s = r.alpha * s;
       s = s + mask;
-      if (j >= S) s = lowest;
+      if (j >= K) s = lowest;
       const float m = half_max(s);
-      const float e = j < S ? exp_p(s - m) : 0.0f;
+      const float e = j < K ? exp_p(s - m) : 0.0f;
       const float sum = half_sum(e);  // canonical order: masks 1..16; the mask-32 step would add +0
       const float p = e / sum;        // keys >= S: exactly 0
       const float ps = half_sum(p);   // P_h
@@ -751,9 +756,9 @@ __device__ __forceinline__ void attention_row(AttnRow r, int lane) {
       s = __builtin_fmaf(s, r.uk, ch);
       if (r.alpha != 1.0f) s = r.alpha * s;
       s = s + mask;
-      if (j >= S) s = lowest;
+      if (j >= K) s = lowest;
       const float m = half_max(s);
-      const float e = j < S ? exp_p(s - m) : 0.0f;
+      const float e = j < K ? exp_p(s - m) : 0.0f;
       const float sum = half_sum(e);
       const float p = e / sum;  // keys >= S: exactly 0
       const float ps = half_sum(p);  // P_h
@@ -1069,7 +1074,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
     // limit, Model.cc:159-161), the width of its alignment rows, the steps it runs at most
     sw[rr] = n_sub && live[rr] ? __builtin_amdgcn_readfirstlane(merge_find(a.sub, n_sub, bq[rr])) : 0;
     len[rr] = live[rr] || (sharer && bq[rr] < Bv)
-                  ? checked_length(n_sub ? a.sub[sw[rr]].lengths[bq[rr] - SLIMT_SUB_FIRST(rr)] : a.lengths[bq[rr]], S)
+                  ? checked_length(n_sub ? a.sub[sw[rr]].lengths[bq[rr] - SLIMT_SUB_FIRST(rr)] : a.lengths[bq[rr]], SLIMT_SUB_S(rr))
                   : 0;
     finished[rr] = !live[rr];
     n_out[rr] = 0;
@@ -1321,6 +1326,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
           ar.uk = a.kv_u[l][0];
           ar.uv = a.kv_u[l][1];
           ar.S = S;
+          ar.keys = S;  // (!MG)
           ar.len = len[0];
           ar.alpha = a.alpha;
           ar.aq_o = L.o.a_quant;
@@ -1392,6 +1398,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
           ar.attn = (a.attn && (l + 1 == Ld)) ? (gf_ptr)(a.attn + (size_t)b * H * S) : (gf_ptr) nullptr;
           const int swr = rr ? sw[RT - 1] : sw[0];
           const int fwr = n_sub ? a.sub[swr].first : 0, Tr = n_sub ? a.sub[swr].Tmax : a.Tmax, Sr = n_sub ? a.sub[swr].S : S;
+          ar.keys = Sr;
           float *al = n_sub ? a.sub[swr].align : a.align;
           const bool want_align = al && (l + 1 == Ld) && !fin && (no < Tr);
           ar.align = want_align ? (gf_ptr)(al + ((size_t)(b - fwr) * Tr + no) * Sr) : (gf_ptr) nullptr;

@@ -427,10 +427,20 @@ __device__ __forceinline__ void pack_weight_tile(const PackArgs &a, int ntile, i
 
 // ---- merged launches (kernels.h, MergeIn / MergePack) ------------------------------------------------------------
 // global sentence g of an encoder launch: its length (a hole: 0) ...
+// A sub-batch's lengths are clamped against ITS padded length: a device length in (S_j, S] attended to the launch's padding
+// (tests/test_gpu_length_edges.py, test_merged_device_lengths_past_the_row).
 __device__ __forceinline__ int sentence_length(const FusedEncodeArgs &a, int g, int S) {
   if (a.n_sub == 0) return checked_length(a.lengths[g], S);
   const int j = merge_find(a.sub, a.n_sub, g), i = g - a.sub[j].first;
-  return i < a.sub[j].n ? checked_length(a.sub[j].lengths[i], S) : 0;
+  return i < a.sub[j].n ? checked_length(a.sub[j].lengths[i], a.sub[j].S) : 0;
+}
+// ... and its keys: the sub-batch's own padded length (S unmerged, and for a hole). Keys from there on are masked with
+// `lowest` like those past S: an empty sentence of a sub-batch padded to S_j < S spreads its all-masked softmax over S_j keys,
+// as its own call does (tests/test_gpu_length_edges.py, test_merged_sub_batches_at_their_length_edges).
+__device__ __forceinline__ int sentence_keys(const FusedEncodeArgs &a, int g, int S) {
+  if (a.n_sub == 0) return S;
+  const int j = merge_find(a.sub, a.n_sub, g), i = g - a.sub[j].first;
+  return i < a.sub[j].n ? a.sub[j].S : S;
 }
 // ... and its token ids: n of them (a hole: none; a sub-batch padded to fewer tokens than the launch: its own S). The
 // caller embeds token 0 at the positions behind them -- padding, which nobody reads.

@@ -198,6 +198,8 @@ __global__ __launch_bounds__(1024) void encode_fused_kernel(FusedEncodeArgs a) {
   // layer's clearing never meets a lagging wave's read of the layer before (encode_tall.hip)
   __shared__ int kv_wide_flag[2];
   if (tid < spw) slens[tid] = s0 + tid < B ? sentence_length(a, s0 + tid, S) : 0;
+  __shared__ int skeys[ER];  // ... and their keys (sentence_keys: a merged sub-batch's own padded length)
+  if (tid < spw) skeys[tid] = sentence_keys(a, s0 + tid, S);
 
   float *xs = reinterpret_cast<float *>(smem);
   char *Aq = reinterpret_cast<char *>(xs + ER * LDX);
@@ -346,7 +348,7 @@ __global__ __launch_bounds__(1024) void encode_fused_kernel(FusedEncodeArgs a) {
         const int sb = s0 + sl;
         if (sb >= B) continue;
         const int base = sl * S;
-        const int len = slens[sl];
+        const int len = slens[sl], keys = skeys[sl];
         const int qr = 16 * qh + n;
         const float *qp = qb + (base + (qr < S ? qr : S - 1)) * LDQQ + h * DH + g;
         float sc[2][4];
@@ -363,7 +365,7 @@ __global__ __launch_bounds__(1024) void encode_fused_kernel(FusedEncodeArgs a) {
             float v = st[r];
             v = a.alpha * v;  // (alpha == 1: the product is v, bit for bit)
             v = v + (1.0f - (m < len ? 1.0f : 0.0f)) * minus_inf;
-            if (m >= S) v = lowest;
+            if (m >= keys) v = lowest;
             sc[kt][r] = v;
           }
         }

@@ -233,6 +233,8 @@ __global__ __launch_bounds__(1024) void encode_tall_kernel(FusedEncodeArgs a) {
   __shared__ int kv_wide_flag[2];
   int kvf = 0;
   if (tid < spw) slens[tid] = s0 + tid < B ? sentence_length(a, s0 + tid, S) : 0;
+  __shared__ int skeys[TR];  // ... and their keys (sentence_keys: a merged sub-batch's own padded length)
+  if (tid < spw) skeys[tid] = sentence_keys(a, s0 + tid, S);
 
   char *Aq = smem;                       // x quantised for Q | round 1's attention output | for FFN1 | for the decoder's K / V
   char *Ak = Aq + TR * LDA;              // x quantised for K
@@ -513,7 +515,7 @@ __global__ __launch_bounds__(1024) void encode_tall_kernel(FusedEncodeArgs a) {
           const int sb = s0 + sl;
           if (sb >= B) continue;
           const int base = sl * S;
-          const int len = slens[sl];
+          const int len = slens[sl], keys = skeys[sl];
           const int qr = 16 * qh + n;
           const float *qp = qb + __mul24(base + (qr < S ? qr : S - 1), LDQ) + hl * DH + g;
           float sc[NKT][4];
@@ -530,7 +532,7 @@ __global__ __launch_bounds__(1024) void encode_tall_kernel(FusedEncodeArgs a) {
               float v = st[r];
               v = a.alpha * v;  // (alpha == 1: the product is v itself, bit for bit -- no select per score)
               v = v + (1.0f - (m < len ? 1.0f : 0.0f)) * minus_inf;
-              if (m >= S) v = lowest;
+              if (m >= keys) v = lowest;
               sc[kt][r] = v;
             }
           }

@@ -209,6 +209,8 @@ __global__ __launch_bounds__(1024) void encode_wide_kernel(FusedEncodeArgs a) {
   __shared__ int slens[WR];
   __shared__ int kv_wide_flag;  // the narrow cache form does not hold this workgroup's accumulators (the K/V phase at the end)
   if (tid < spw) slens[tid] = s0 + tid < B ? sentence_length(a, s0 + tid, S) : 0;
+  __shared__ int skeys[WR];  // ... and their keys (sentence_keys: a merged sub-batch's own padded length)
+  if (tid < spw) skeys[tid] = sentence_keys(a, s0 + tid, S);
 
   char *Abuf = smem;                 // x quantised for Q | round 1's attention output | FFN1 / decoder K/V input
   char *Akb = Abuf + WR * LDA;       // x quantised for K
@@ -375,7 +377,7 @@ __global__ __launch_bounds__(1024) void encode_wide_kernel(FusedEncodeArgs a) {
           const int sb = s0 + sl;
           if (sb >= B) continue;
           const int base = sl * S;
-          const int len = slens[sl];
+          const int len = slens[sl], keys = skeys[sl];
           const int qr = 16 * qh + n;
           const float *qp = qb + (base + (qr < S ? qr : S - 1)) * LDQ + hl * DH + g;
           float sc[2][4];
@@ -411,7 +413,7 @@ __global__ __launch_bounds__(1024) void encode_wide_kernel(FusedEncodeArgs a) {
                 float v = kt ? st1[r] : st0[r];
                 v = a.alpha * v;  // (alpha == 1: the product is v, bit for bit)
                 v = v + (1.0f - (m < len ? 1.0f : 0.0f)) * minus_inf;
-                if (m >= S) v = lowest;
+                if (m >= keys) v = lowest;
                 sc[kt][r] = v;
               }
           }
