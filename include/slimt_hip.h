@@ -567,6 +567,12 @@ int slimt_hip_debug_kv_recalibrations(slimt_hip_model *model, int *generations_s
  * HW_ID | XCC_ID << 32, 100 MHz wall clock}; events past `capacity` are
  * dropped. NULL switches it off. tools/occupancy_trace.py reads it. */
 int slimt_hip_debug_occupancy_trace(void *device_buf, size_t capacity);
+/* Diagnostic: the plan of ctx's last fused decoder launch under the decoder admission (engine.cpp,
+ * decoder_plan.h): out[0] sentences per workgroup, out[1] contexts with a decoder pending (this one included),
+ * out[2] decoders in flight (min(pending contexts, hardware queues)), out[3] admission depth n (0 = the launch
+ * waited for no event), out[4] K/V temporal eighths, out[5] the hardware queues the model saw (GPU_MAX_HW_QUEUES
+ * when it was created, else 4). All 0 before the first such launch. Results never depend on any of this. */
+int slimt_hip_debug_decoder_plan(slimt_hip_ctx *ctx, int out[6]);
 
 #ifdef __cplusplus
 }

@@ -28,7 +28,7 @@ SYMBOLS = [
     "slimt_hip_encode", "slimt_hip_decode_begin", "slimt_hip_decode_step",
     "slimt_hip_profile_enable", "slimt_hip_profile_read", "slimt_hip_profile_reset",
     "slimt_hip_debug_decode_stamps", "slimt_hip_debug_kv_formats", "slimt_hip_debug_kv_narrow_limit", "slimt_hip_debug_kv_tight_limit", "slimt_hip_debug_kv_tight_watch", "slimt_hip_debug_kv_centres", "slimt_hip_model_set_kv_centres", "slimt_hip_debug_kv_watch", "slimt_hip_debug_break_shortlist_handoff", "slimt_hip_debug_cross_attention",
-    "slimt_hip_debug_occupancy_trace", "slimt_hip_model_set_decoder_budget",
+    "slimt_hip_debug_occupancy_trace", "slimt_hip_debug_decoder_plan", "slimt_hip_model_set_decoder_budget",
     "slimt_hip_model_set_kv_cache_policy",
     "slimt_hip_model_set_xcd_affinity", "slimt_hip_model_device",
     "slimt_hip_model_set_kv_cache_format", "slimt_hip_model_set_adaptive_decoder_rows",
@@ -222,6 +222,7 @@ def lib():
     L.slimt_hip_debug_decode_stamps.argtypes = [vp, i32, vp, sz]
     L.slimt_hip_debug_occupancy_trace.argtypes = [vp, sz]
     L.slimt_hip_debug_kv_formats.argtypes = [vp, vp, sz, vp]
+    L.slimt_hip_debug_decoder_plan.argtypes = [vp, vp]
     L.slimt_hip_debug_kv_narrow_limit.argtypes = [vp, i32]
     L.slimt_hip_debug_kv_watch.argtypes = [vp, vp, vp, vp]
     L.slimt_hip_debug_kv_tight_limit.argtypes = [vp, i32]
@@ -796,6 +797,12 @@ class Context:
     def debug_break_shortlist_handoff(self, broken: bool, poll_limit: int = 1 << 24):
         """The waiters of an in-launch shortlist look for a publication that never comes (tests: the timeout path)."""
         _chk(lib().slimt_hip_debug_break_shortlist_handoff(self.h, 1 if broken else 0, int(poll_limit)))
+
+    def debug_decoder_plan(self) -> dict:
+        """The plan of this context's last fused decoder launch under the decoder admission (decoder_plan.h)."""
+        out = np.zeros(6, dtype=np.int32)
+        _chk(lib().slimt_hip_debug_decoder_plan(self.h, _p(out)))
+        return dict(zip(("rows", "contexts", "in_flight", "n", "eighths", "queues"), (int(v) for v in out)))
 
     def debug_kv_formats(self, layers: int, max_batch: int):
         """[layers][B] uint8 of the last batch: 0 = its cache is in the 20-bit form, 1 = 24-bit; None when the batch's

@@ -1,5 +1,6 @@
 // C ABI (include/slimt_hip.h) + host-side engine of the MI355X slimt backend.
 #include "engine.h"
+#include "decoder_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -724,6 +725,9 @@ extern "C" int slimt_hip_model_create(const slimt_hip_param *params, size_t n_pa
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) m->decoder_budget = 7 * prop.multiProcessorCount / 8;
   }
+  // the hardware queues the runtime started with: it has read GPU_MAX_HW_QUEUES by now (slimt_hip_device_count
+  // initialised it), and this library only ever reads the variable here (slimt_hip_request_hw_queues aside)
+  m->hw_queues = slimt_hip_hw_queues() > 0 ? slimt_hip_hw_queues() : 4;
   int rc = model_build(m, params, n_params, dims);
   if (rc) {
     model_free(m);
@@ -997,6 +1001,12 @@ extern "C" int slimt_hip_debug_kv_tight_watch(slimt_hip_model *model, unsigned *
                                               model->kv_wide_count)[1 + 4 * model->kv_gen.load(std::memory_order_relaxed) + l] : 0;
     if (submitted) submitted[l] = model->kv_tight_submitted[l].load(std::memory_order_relaxed);
   }
+  return 0;
+}
+
+extern "C" int slimt_hip_debug_decoder_plan(slimt_hip_ctx *ctx, int out[6]) {
+  if (!ctx || !out) return fail(-1, "null argument");
+  for (int i = 0; i < 6; ++i) out[i] = ctx->plan_last[i];
   return 0;
 }
 
@@ -2166,7 +2176,7 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
       }
       // K/V cache policy (decode_fused.hip, KV_AUX). The caches that are being read at any
       // moment are those of the decoders that run: at most one per context (a context is a
-      // stream) and at most n by admission. While they fit the 256 MB Infinity Cache every
+      // stream), one per hardware queue and n by admission. While they fit the 256 MB Infinity Cache every
       // step re-reads them from there and non-temporal loads only lose that; beyond it the
       // cache streams from HBM anyway and non-temporal loads keep it from displacing the
       // weights. In between, the first layers' caches stay temporal (they then fit) and the
@@ -2197,37 +2207,18 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
         }
       }
       if (!known) gm->gate_ctx.push_back({c, gm->gate_seq, kv_bytes, now});
-      // Sentences per workgroup (decode mode 0): the fewest of 16 / 8 / 4 with which the decoders of the
-      // contexts that have one pending (this launch's shape taken for all of them) still fit the budget --
-      // one batch of 256 alone runs on 64 CUs instead of 16, twenty batches of 64 on 160 instead of 80, and
-      // the headline's twenty batches of 256 stay at 16 (a workgroup of fewer sentences streams the same
-      // weights for them: worth it only for CUs that would idle). Results do not depend on it.
-      if (c->decode_mode == 0 && f.rows_per_wg == 0 && gm->adaptive_rows) {
-        for (int spw : {4, 8}) {
-          if (fused_decode_rows(m->D, m->F, m->H, m->Ld, (int)S, (int)B, spw, kv24) != spw) break;
-          static const double oversub = std::getenv("SLIMT_ROWS_OVERSUB") ? std::atof(std::getenv("SLIMT_ROWS_OVERSUB")) : 1.0;
-          if ((double)(contexts * (size_t)(((int)B + spw - 1) / spw)) <= oversub * (double)gm->decoder_budget) {
-            f.rows_per_wg = spw;
-            rows = spw;
-            tickets = (unsigned)fused_decode_grid((int)B, true, rows);
-            wgs = ((int)B + rows - 1) / rows;
-            wbytes = (double)f.max_steps * wgs *
-                     (m->Ld * (4.0 * m->D * m->D + 2.0 * m->D * m->F) + (double)m->D * out.w.n_tiles * 16);
-            break;
-          }
-        }
-      }
-      size_t n = (size_t)std::max(1, gm->decoder_budget / wgs);
-      if (n > kRing) n = kRing;
-      const double active = pending / (double)contexts * (double)std::min(contexts, n);
-      // ... in eighths of a layer's caches (kernels.h, kv_temporal_eighths): SLIMT_KV_BUDGET_MB /
+      // The plan (decoder_plan.h): sentences per workgroup (decode mode 0: the fewest of 16 / 8 / 4 with which the
+      // decoders in flight still fit the budget -- one batch of 256 alone runs on 64 CUs instead of 16; a workgroup of
+      // fewer sentences streams the same weights for them: worth it only for CUs that would idle; results do not depend
+      // on it), the admission depth n and the K/V policy below. Decoders in flight = min(pending contexts, hardware
+      // queues): with GPU_MAX_HW_QUEUES = 32 the headline's twenty contexts are twenty decoders and stay at 16
+      // sentences, n = 14; with the runtime's default four queues only four run, and they take the 8-sentence tiling
+      // (4 x 32 workgroups) with no admission waits ("queue-bound").
+      static const double oversub = std::getenv("SLIMT_ROWS_OVERSUB") ? std::atof(std::getenv("SLIMT_ROWS_OVERSUB")) : 1.0;
+      // ... the K/V caches in eighths of a layer's caches (kernels.h, kv_temporal_eighths): SLIMT_KV_BUDGET_MB /
       // SLIMT_KV_GRAIN tune the rule (defaults: 300 MB in whole layers, the measured optimum above)
       static const double budget = (std::getenv("SLIMT_KV_BUDGET_MB") ? std::atof(std::getenv("SLIMT_KV_BUDGET_MB")) : 300.0) * 1e6;
       static const int grain = std::getenv("SLIMT_KV_GRAIN") ? std::max(1, std::atoi(std::getenv("SLIMT_KV_GRAIN"))) : 8;
-      const int all = 8 * m->Ld;
-      int eighths = gm->kv_policy == 1 ? all : gm->kv_policy == 2 ? 0
-                    : (int)std::min((double)all, std::floor((double)all * budget / active));
-      if (gm->kv_policy == 0) eighths = eighths / grain * grain;
       // Round 4: WHICH caches stay temporal. "Layer 0 of every decoder" (the rule above) makes every workgroup pay one
       // cached and one streamed attention per step; keeping BOTH layers of k of every 8 launches (by admission order)
       // and streaming both layers of the others holds the same bytes but lets the kept decoders run their whole step
@@ -2237,26 +2228,62 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
       // round 5: 300 -- with the narrow form the headline's decoders hold 232 MB, k = 6 / 7 / 8 measure the same
       // (35.8 / 35.7 / 35.6 M tok/s, profiles/r05_kv_keep_sweep.txt), and every launch then runs the kept instantiation);
       // SLIMT_KV_BY_LAUNCH: 0 = the per-layer rule, 1..8 = that k.
+      // (sentences of up to 32 tokens; longer ones measured 2-3 % slower this way and keep the per-layer rule:
+      // S = 64 18.5 -> 17.9 M, S = 128 8.2 -> 8.0 M)
+      // ... and launches of which at least four fit the budget: ONE batch of 4096 holds 400 MB by itself, and keeping
+      // "all of it" thrashes where "its layer 0" fits (29.8 -> 27.2 M tok/s). With four queues the four decoders in
+      // flight hold 4 x 13-17 MB at the headline: every launch stays temporal.
       static const bool store_nt_rule = std::getenv("SLIMT_KV_STORE_NT") && std::getenv("SLIMT_KV_STORE_NT")[0] == '1';
       static const int by_launch = std::getenv("SLIMT_KV_BY_LAUNCH") ? std::atoi(std::getenv("SLIMT_KV_BY_LAUNCH")) : -1;
       static const double launch_budget =
           (std::getenv("SLIMT_KV_LAUNCH_BUDGET_MB") ? std::atof(std::getenv("SLIMT_KV_LAUNCH_BUDGET_MB")) : 300.0) * 1e6;
-      // (sentences of up to 32 tokens; longer ones measured 2-3 % slower this way and keep the per-layer rule:
-      // S = 64 18.5 -> 17.9 M, S = 128 8.2 -> 8.0 M)
-      // ... and launches of which at least four fit the budget: ONE batch of 4096 holds 400 MB by itself, and keeping
-      // "all of it" thrashes where "its layer 0" fits (29.8 -> 27.2 M tok/s)
-      if (gm->kv_policy == 0 && by_launch != 0 && eighths < all && S <= 32 && 4.0 * kv_bytes <= launch_budget) {
-        const int k = by_launch > 0 ? std::min(by_launch, 8) : (int)std::min(8.0, std::floor(8.0 * launch_budget / active));
+      DecoderPlanIn pin;
+      pin.B = (int)B; pin.S = (int)S; pin.Ld = m->Ld;
+      pin.rows = rows;
+      pin.adaptive = c->decode_mode == 0 && f.rows_per_wg == 0 && gm->adaptive_rows;
+      pin.narrow_ok = fused_decode_rows(m->D, m->F, m->H, m->Ld, (int)S, (int)B, 4, kv24) == 4 &&
+                      fused_decode_rows(m->D, m->F, m->H, m->Ld, (int)S, (int)B, 8, kv24) == 8;
+      pin.kv_bytes = kv_bytes;
+      pin.pending_kv = pending;
+      pin.contexts = contexts;
+      pin.queues = gm->hw_queues;
+      pin.budget = gm->decoder_budget;
+      pin.kv_policy = gm->kv_policy;
+      pin.ring = kRing;
+      pin.rows_oversub = oversub;
+      pin.kv_budget = budget;
+      pin.kv_grain = grain;
+      pin.by_launch = by_launch;
+      pin.launch_budget = launch_budget;
+      const DecoderPlan plan = decoder_plan(pin);
+      if (plan.rows != rows) {
+        f.rows_per_wg = plan.rows;
+        rows = plan.rows;
+        tickets = (unsigned)fused_decode_grid((int)B, true, rows);
+        wgs = plan.wgs;
+        wbytes = (double)f.max_steps * wgs *
+                 (m->Ld * (4.0 * m->D * m->D + 2.0 * m->D * m->F) + (double)m->D * out.w.n_tiles * 16);
+      }
+      const size_t n = plan.n;
+      const int all = 8 * m->Ld;
+      int eighths = plan.eighths;
+      if (plan.by_launch) {
         // (the slot was drawn when the call started, with the k of the admission before it: the encoder of a call
         // whose cache will be streamed can then write it non-temporally, SLIMT_KV_STORE_NT=1)
-        eighths = (int)(call_slot % 8) < (store_nt_rule ? call_k : k) ? all : 0;
-        gm->kv_k_last.store(k, std::memory_order_relaxed);
+        eighths = (int)(call_slot % 8) < (store_nt_rule ? call_k : plan.k) ? all : 0;
+        gm->kv_k_last.store(plan.k, std::memory_order_relaxed);
       } else {
         gm->kv_k_last.store(8, std::memory_order_relaxed);
       }
       f.kv_nt = eighths < all;
       f.kv_temporal_eighths = eighths;
-      if (gm->gate_seq >= n) HIPCHK(hipStreamWaitEvent(st, gm->gate_ev[(gm->gate_seq - n) % kRing], 0));
+      c->plan_last[0] = rows;
+      c->plan_last[1] = (int)contexts;
+      c->plan_last[2] = (int)plan.in_flight;
+      c->plan_last[3] = plan.wait ? (int)n : 0;
+      c->plan_last[4] = eighths;
+      c->plan_last[5] = gm->hw_queues;
+      if (plan.wait && gm->gate_seq >= n) HIPCHK(hipStreamWaitEvent(st, gm->gate_ev[(gm->gate_seq - n) % kRing], 0));
       clk.lap(3);
       const int n_home = gm->xcd_affinity;
       const bool affine = n_home > 0 && rows == 16 && wgs <= 16 * n_home;

@@ -78,6 +78,9 @@ struct slimt_hip_model {
   std::vector<hipEvent_t> gate_ev;  // ring, created on first use
   size_t gate_seq = 0;
   int decoder_budget = 0;
+  // hardware queues the HIP runtime started with (GPU_MAX_HW_QUEUES when the model was created, else the runtime's
+  // default of 4): the decoders in flight are at most min(pending contexts, hw_queues) (decoder_plan.h)
+  int hw_queues = 4;
   // per context: its latest admitted decoder launch and that batch's K/V bytes (choice of
   // the K/V cache policy: how much K/V do the contexts with a pending decoder hold together)
   struct GateCtx {
@@ -162,6 +165,9 @@ struct slimt_hip_ctx {
   slimt_hip::DevBuf dbg_embed, dbg_layers;
   int encode_rows = 0;  // rows per workgroup of the persistent D = 256 encoder: 0 auto, 32, 64
   int decode_mode = 0;  // 0 auto (fused when supported), 1 step-wise launches, 2 / 3 fused with 16 / 32 rows per workgroup
+  // the plan of this context's last admitted fused decoder launch (slimt_hip_debug_decoder_plan): sentences per
+  // workgroup, pending contexts, decoders in flight, admission depth (0 = no wait), K/V temporal eighths, hardware queues
+  int plan_last[6] = {0, 0, 0, 0, 0, 0};
   slimt_hip::DevBuf stamps;  // diagnostic phase stamps of the fused decoder
   int stamp_step = -1;
   // encoder workspace
