@@ -249,6 +249,31 @@ int slimt_hip_ctx_set_encode_rows(slimt_hip_ctx *ctx, int rows);
  * lengths and alignments are the same as without scores. Scored calls decode with
  * the 16-sentence tilings (decode modes 2-6 act as 2 for them). */
 int slimt_hip_ctx_set_scores(slimt_hip_ctx *ctx, float *const *scores, size_t n);
+/* Forced target prefixes for the NEXT translate call on ctx (any of the
+ * slimt_hip_translate* entry points), which consumes them whether it succeeds or
+ * fails; n = 0 arms nothing. prefix_ids[j] is batch j's [B_j][Tmax_j] uint32 array
+ * (laid out like out_ids), prefix_len[j] its [B_j] lengths P_b <= Tmax_j: n = 1 for
+ * the single-batch calls, n = n_batches for the _many_ ones; in the memory of that
+ * call's inputs (host for the host calls, device for the _device ones). A mismatched
+ * n or a NULL entry fails that call; so do, for host arrays, a P_b > Tmax_j or a
+ * prefix id >= the vocabulary.
+ * At step t < P_b, sentence b records and feeds prefix_ids[b][t] instead of the
+ * arg-max; from step P_b on it decodes greedily, P_b = 0 is an unforced sentence.
+ * Everything else is unchanged: alignments, the step limit, and the end of a
+ * sentence at EOS, forced or chosen (a prefix holding EOS ends the sentence there).
+ * Scoring a given translation: its tokens plus EOS as the prefix -- out_ids echoes
+ * them, out_len[b] = P_b, and the scores (slimt_hip_ctx_set_scores, optional) are
+ * the teacher-forced log-probabilities. A forced token outside the step's output
+ * layer (not in the shortlist, fixed or generated) is still recorded and fed; its
+ * score is -inf. A step whose logits hold a NaN scores NaN, forced or not. Forced
+ * calls decode with the 16-sentence tilings (decode modes 2-6 act as 2), like
+ * scored ones. Device arrays: see slimt_hip_translate_device. Host arrays: pinned
+ * ones (slimt_hip_host_alloc) are read in place by the kernels, pageable ones are
+ * copied asynchronously on the context's stream; for the _async calls either kind
+ * must stay valid and unchanged until the context is synchronised, like the
+ * other inputs. */
+int slimt_hip_ctx_set_target_prefix(slimt_hip_ctx *ctx, const uint32_t *const *prefix_ids,
+                                    const uint32_t *const *prefix_len, size_t n);
 /* Which kernels a translate call with source length S would use in the current
  * mode: *encoder_fused / *decoder_fused = 1 for the persistent kernels, 0 for
  * the per-stage ones. */
@@ -301,7 +326,10 @@ int slimt_hip_host_free(void *p);
  * through the library. */
 /* Device arrays cannot be checked by the host: a token or shortlist id >= the vocabulary reads the table's last
  * row instead of faulting -- that sentence's result is undefined (as in the reference, which does not check
- * either), the other sentences' results are not affected. */
+ * either), the other sentences' results are not affected. A target prefix
+ * (slimt_hip_ctx_set_target_prefix) in device memory is not checked either: a length
+ * past Tmax is taken as Tmax, and a prefix id >= the vocabulary leaves that
+ * sentence's result undefined and no other sentence's. */
 int slimt_hip_translate_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids,
                                const uint32_t *d_lengths, size_t B, size_t S,
                                const uint32_t *d_shortlist, size_t n_shortlist,

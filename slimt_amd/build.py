@@ -133,7 +133,8 @@ def build_host_lib(force: bool = False) -> str:
     build()
     srcs = [os.path.join(HOST_DIR, s) for s in HOST_LIB_SOURCES]
     deps = srcs + [os.path.join(HOST_DIR, h) for h in os.listdir(HOST_DIR)] + [
-        LIB_PATH, os.path.join(ROOT, "include", "slimt_hip_service.h"), os.path.join(ROOT, "include", "slimt_hip_service_scores.h")]
+        LIB_PATH, os.path.join(ROOT, "include", "slimt_hip_service.h"), os.path.join(ROOT, "include", "slimt_hip_service_scores.h"),
+        os.path.join(ROOT, "include", "slimt_hip_service_prefix.h")]
     if not force and os.path.exists(HOST_LIB) and all(
             os.path.getmtime(d) <= os.path.getmtime(HOST_LIB) for d in deps):
         return HOST_LIB

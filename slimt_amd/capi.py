@@ -39,7 +39,7 @@ SYMBOLS = [
     "slimt_hip_encode_embedded", "slimt_hip_decode_begin_from", "slimt_hip_decode_step_states",
     "slimt_hip_translate_many_rows", "slimt_hip_translate_many_device", "slimt_hip_translate_many_async",
     "slimt_hip_debug_kv_recalibrations", "slimt_hip_translate_many_device_generated", "slimt_hip_translate_many_async_generated",
-    "slimt_hip_ctx_set_scores",
+    "slimt_hip_ctx_set_scores", "slimt_hip_ctx_set_target_prefix",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -204,6 +204,7 @@ def lib():
     L.slimt_hip_ctx_set_decode_mode.argtypes = [vp, i32]
     L.slimt_hip_ctx_set_encode_rows.argtypes = [vp, i32]
     L.slimt_hip_ctx_set_scores.argtypes = [vp, vp, sz]
+    L.slimt_hip_ctx_set_target_prefix.argtypes = [vp, vp, vp, sz]
     L.slimt_hip_ctx_plan.argtypes = [vp, sz, vp, vp]
     L.slimt_hip_translate.argtypes = [vp, vp, vp, sz, sz, vp, sz, f32, u32, vp, vp, vp]
     L.slimt_hip_translate_async.argtypes = [vp, vp, vp, sz, sz, vp, sz, f32, u32, vp, vp, vp]
@@ -573,6 +574,7 @@ class Context:
 
     def synchronize(self):
         _chk(lib().slimt_hip_ctx_synchronize(self.h))
+        self._prefix_keep = []  # (the prefixes armed before are read by now)
 
     def set_decode_mode(self, mode: int):
         """0 = auto (persistent fused decoder when supported), 1 = step-wise launches."""
@@ -590,6 +592,37 @@ class Context:
         arr = (C.c_void_p * max(1, len(addrs)))(*[a or None for a in addrs])
         _chk(lib().slimt_hip_ctx_set_scores(self.h, arr, len(addrs)))
 
+    def set_target_prefix(self, prefixes):
+        """slimt_hip_ctx_set_target_prefix: arm forced target prefixes for the NEXT translate call -- one (ids [B_j, Tmax_j],
+        lens [B_j]) pair per batch, as numpy uint32 arrays (host calls; kept alive here until the next arming) or
+        addresses (ints: device pointers for the device calls). The translate wrappers below take `prefix=` and do this."""
+        keep, ids, lens = [], [], []
+        for p_ids, p_len in prefixes:
+            for a, out in ((p_ids, ids), (p_len, lens)):
+                if isinstance(a, np.ndarray):
+                    if a.dtype != np.uint32 or not a.flags.c_contiguous:
+                        raise ValueError("target prefix: C-contiguous uint32 arrays expected")
+                    keep.append(a)
+                    out.append(a.ctypes.data)
+                else:
+                    out.append(int(a) if a else 0)
+        # host arrays stay referenced until synchronize(): an asynchronous call reads them (pinned) or copies them (pageable)
+        # from its stream, and a temporary made above may have no other owner
+        self._prefix_keep = getattr(self, "_prefix_keep", []) + keep
+        n = len(ids)
+        a_ids = (C.c_void_p * max(1, n))(*[a or None for a in ids])
+        a_len = (C.c_void_p * max(1, n))(*[a or None for a in lens])
+        _chk(lib().slimt_hip_ctx_set_target_prefix(self.h, a_ids, a_len, n))
+
+    @staticmethod
+    def _prefix_host(prefix, B: int, T: int):
+        """(ids [B, T], lens [B]) as C-contiguous uint32 arrays (shapes checked)"""
+        p_ids = np.ascontiguousarray(prefix[0], dtype=np.uint32)
+        p_len = np.ascontiguousarray(prefix[1], dtype=np.uint32)
+        if p_ids.shape != (B, T) or p_len.shape != (B,):
+            raise ValueError("prefix: ids of shape %s and lengths of shape %s expected" % ((B, T), (B,)))
+        return p_ids, p_len
+
     @staticmethod
     def _scores_array(a, B: int, T: int):
         if a.dtype != np.float32 or a.shape != (B, T) or not a.flags.c_contiguous:
@@ -603,9 +636,10 @@ class Context:
         return bool(e.value), bool(d.value)
 
     def translate(self, ids, lengths, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                  want_align: bool = False, scores: bool = False):
+                  want_align: bool = False, scores: bool = False, prefix=None):
         """Model::forward. Returns out_ids [B,Tmax], out_len [B], align|None (+ scores [B,Tmax] float32 with
-        scores=True: the log-probability of each recorded token, include/slimt_hip.h slimt_hip_ctx_set_scores)."""
+        scores=True: the log-probability of each recorded token, include/slimt_hip.h slimt_hip_ctx_set_scores).
+        prefix: (ids [B,Tmax], lens [B]) uint32 -- forced target prefixes (slimt_hip_ctx_set_target_prefix)."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
         B, S = ids.shape
@@ -616,11 +650,15 @@ class Context:
         out_len = np.zeros(B, dtype=np.uint32)
         align = np.zeros((B, T, S), dtype=np.float32) if want_align else None
         sc = np.full((B, T), np.nan, dtype=np.float32) if scores else None
+        pre = self._prefix_host(prefix, B, T) if prefix is not None else None
         if scores:
             self.set_scores([sc])
+        if pre is not None:
+            self.set_target_prefix([pre])
         _chk(lib().slimt_hip_translate(self.h, _p(ids), _p(lengths), B, S, _p(sl),
                                        0 if sl is None else sl.size, limit_factor, eos_id,
                                        _p(out_ids), _p(out_len), _p(align)))
+        self._prefix_keep = []  # (a blocking call: done with its prefix)
         return (out_ids, out_len, align, sc) if scores else (out_ids, out_len, align)
 
     def pinned_buffers(self, B: int, S: int, limit_factor: float = 1.5, want_align: bool = False):
@@ -632,18 +670,22 @@ class Context:
                 pin("al").array(np.float32, (B, T, S)) if want_align else None)
 
     def translate_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
-                        scores=None):
+                        scores=None, prefix=None):
         """slimt_hip_translate_async[_generated] on arrays from pinned_buffers() (already filled);
         synchronize() before reading the outputs. `generator`: a ShortlistGenerator -- the batch's
         lexical shortlist is then generated on this context's stream (Model.cc:117-120).
-        scores: a float32 [B, Tmax] array (pinned: written in place) that receives the tokens' log-probabilities."""
+        scores: a float32 [B, Tmax] array (pinned: written in place) that receives the tokens' log-probabilities.
+        prefix: (ids [B, Tmax], lens [B]) uint32 host arrays, kept alive until the next call arms another one."""
         p_ids, p_len, p_out, p_ol, p_al = bufs
         B, S = p_ids.shape
         if scores is not None:
             self._scores_array(scores, B, p_out.shape[1])
+        pre = self._prefix_host(prefix, B, p_out.shape[1]) if prefix is not None else None
         sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
         if scores is not None:  # (armed right before the call that takes it)
             self.set_scores([scores])
+        if pre is not None:
+            self.set_target_prefix([pre])
         if generator is not None:
             _chk(lib().slimt_hip_translate_async_generated(self.h, generator.h, _p(p_ids), _p(p_len), B, S,
                                                            limit_factor, eos_id, _p(p_out), _p(p_ol), _p(p_al)))
@@ -652,7 +694,7 @@ class Context:
                                              limit_factor, eos_id, _p(p_out), _p(p_ol), _p(p_al)))
 
     def translate_pinned(self, ids, lengths, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                         want_align: bool = False, generator=None, scores: bool = False):
+                         want_align: bool = False, generator=None, scores: bool = False, prefix=None):
         """translate() through this context's pinned staging buffers and slimt_hip_translate_async:
         the persistent kernels then read and write host memory themselves, no copy is queued (host
         pipelines with several contexts: copies of one stream wait behind other streams' kernels).
@@ -663,14 +705,15 @@ class Context:
         bufs[0][...] = ids
         bufs[1][...] = lengths
         sc = self._pinned.setdefault("sc", _Pinned()).array(np.float32, bufs[2].shape) if scores else None
-        self.translate_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc)
+        self.translate_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix)
         self.synchronize()
         out = bufs[2].copy(), bufs[3].copy(), (bufs[4].copy() if want_align else None)
         return out + (sc.copy(),) if scores else out
 
     def translate_generated(self, generator, ids, lengths, limit_factor: float = 1.5, eos_id: int = 0,
-                            want_align: bool = False, scores: bool = False):
-        """Model::forward with its shortlist step (slimt_hip_translate_generated): host arrays, blocking."""
+                            want_align: bool = False, scores: bool = False, prefix=None):
+        """Model::forward with its shortlist step (slimt_hip_translate_generated): host arrays, blocking.
+        prefix: as in translate()."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
         B, S = ids.shape
@@ -679,30 +722,38 @@ class Context:
         out_len = np.zeros(B, dtype=np.uint32)
         align = np.zeros((B, T, S), dtype=np.float32) if want_align else None
         sc = np.full((B, T), np.nan, dtype=np.float32) if scores else None
+        pre = self._prefix_host(prefix, B, T) if prefix is not None else None
         if scores:
             self.set_scores([sc])
+        if pre is not None:
+            self.set_target_prefix([pre])
         _chk(lib().slimt_hip_translate_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, limit_factor,
                                                  eos_id, _p(out_ids), _p(out_len), _p(align)))
+        self._prefix_keep = []  # (a blocking call: done with its prefix)
         return (out_ids, out_len, align, sc) if scores else (out_ids, out_len, align)
 
     def translate_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int,
                          n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int,
-                         d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0):
+                         d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None):
         """Device pointers (ints) in and out; asynchronous when steps_hint > 0. scores: a device pointer to
-        [B, Tmax] floats for the tokens' log-probabilities (0 = none)."""
+        [B, Tmax] floats for the tokens' log-probabilities (0 = none). prefix: (d_ids, d_lens) device pointers of a
+        forced target prefix ([B, Tmax] and [B] uint32)."""
         vp = C.c_void_p
         args = (self.h, vp(d_ids), vp(d_lengths), B, S, vp(d_shortlist) if n_shortlist else None,
                 n_shortlist, limit_factor, eos_id, vp(d_out_ids), vp(d_out_len),
                 vp(d_align) if d_align else None, steps_hint)
         if scores:  # (armed right before the call that takes it)
             self.set_scores([scores])
+        if prefix is not None:
+            self.set_target_prefix([prefix])
         _chk(lib().slimt_hip_translate_device(*args))
 
     def translate_many_device(self, batches, S: int, limit_factor: float, eos_id: int, steps_hint: int = 0, generator=None,
-                              scores=None):
+                              scores=None, prefix=None):
         """slimt_hip_translate_many_device: `batches` = [(d_ids, d_lengths, B, d_shortlist, n_shortlist, d_out_ids,
         d_out_len, d_align[, S_j])] of device pointers (ints; 0 = none) -- ONE encoder and ONE decoder launch for all of them;
-        S_j: that batch's own padded length (<= S; default S). scores: one device pointer per batch ([B_j, Tmax_j] floats)."""
+        S_j: that batch's own padded length (<= S; default S). scores: one device pointer per batch ([B_j, Tmax_j] floats).
+        prefix: one (d_ids, d_lens) pair of device pointers per batch (forced target prefixes)."""
         if scores is not None and len(scores) != len(batches):
             raise ValueError(f"scores: {len(scores)} destinations for {len(batches)} batches")
         arr = (_Batch * len(batches))()
@@ -711,16 +762,24 @@ class Context:
             arr[j] = _Batch(d_ids, d_len, B, b[8] if len(b) > 8 else 0, d_sl if n_sl else None, n_sl, d_out, d_ol, d_al or None)
         if scores is not None:  # (armed right before the call that takes it)
             self.set_scores(list(scores))
+        if prefix is not None:
+            self.set_target_prefix(list(prefix))
         if generator is not None:
             _chk(lib().slimt_hip_translate_many_device_generated(self.h, generator.h, arr, len(batches), S, limit_factor, eos_id, steps_hint))
             return
         _chk(lib().slimt_hip_translate_many_device(self.h, arr, len(batches), S, limit_factor, eos_id, steps_hint))
 
     def translate_many_async(self, bufs_list, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0, generator=None,
-                             scores=None):
+                             scores=None, prefix=None):
         """slimt_hip_translate_many_async on a list of pinned buffer tuples (ids, lengths, out_ids, out_len, align|None),
         one shortlist (host array) or none for all; synchronize() before reading the outputs.
-        scores: one float32 [B_j, Tmax_j] array per batch (pinned: the merged launch writes them in place)."""
+        scores: one float32 [B_j, Tmax_j] array per batch (pinned: the merged launch writes them in place).
+        prefix: one (ids [B_j, Tmax_j], lens [B_j]) pair of uint32 host arrays per batch."""
+        pre = None
+        if prefix is not None:
+            if len(prefix) != len(bufs_list):
+                raise ValueError(f"prefix: {len(prefix)} prefixes for {len(bufs_list)} batches")
+            pre = [self._prefix_host(p, b[2].shape[0], b[2].shape[1]) for p, b in zip(prefix, bufs_list)]
         if scores is not None:
             if len(scores) != len(bufs_list):
                 raise ValueError(f"scores: {len(scores)} arrays for {len(bufs_list)} batches")
@@ -736,6 +795,8 @@ class Context:
         self._many_keep = (arr, sl)
         if scores is not None:  # (armed right before the call that takes it)
             self.set_scores(list(scores))
+        if pre is not None:
+            self.set_target_prefix(pre)
         if generator is not None:  # every batch's own lexical shortlist, generated inside the encoder launch
             _chk(lib().slimt_hip_translate_many_async_generated(self.h, generator.h, arr, len(bufs_list), S, limit_factor, eos_id))
             return
@@ -743,13 +804,15 @@ class Context:
 
     def translate_device_generated(self, gen: "ShortlistGenerator", d_ids: int, d_lengths: int, B: int,
                                    S: int, limit_factor: float, eos_id: int, d_out_ids: int,
-                                   d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0):
-        """Shortlist generation + translate, all on this context's stream. scores: as in translate_device."""
+                                   d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None):
+        """Shortlist generation + translate, all on this context's stream. scores, prefix: as in translate_device."""
         vp = C.c_void_p
         args = (self.h, gen.h, vp(d_ids), vp(d_lengths), B, S, limit_factor, eos_id, vp(d_out_ids),
                 vp(d_out_len), vp(d_align) if d_align else None, steps_hint)
         if scores:  # (armed right before the call that takes it)
             self.set_scores([scores])
+        if prefix is not None:
+            self.set_target_prefix([prefix])
         _chk(lib().slimt_hip_translate_device_generated(*args))
 
     def encode(self, ids, lengths, want_embed=False, want_layers=False):
@@ -892,6 +955,7 @@ def host_lib():
     H.slimt_hip_result_destroy.argtypes = [vp]
     H.slimt_hip_service_set_scores.argtypes = [vp, C.c_int]  # (include/slimt_hip_service_scores.h)
     H.slimt_hip_result_scores.argtypes = [vp, vp]
+    H.slimt_hip_service_translate_prefixed.argtypes = [vp, vp, vp, vp, vp, sz, vp]  # (include/slimt_hip_service_prefix.h)
     _host_lib = H
     return H
 
@@ -998,21 +1062,41 @@ class BatchService:
             self.close()
             raise SlimtHipError(err)
 
-    def translate_flat(self, tokens: np.ndarray, offsets: np.ndarray) -> ServiceResult:
-        """tokens uint32 (flat), offsets uint64 [n + 1]. Blocking; thread-safe."""
+    def translate_flat(self, tokens: np.ndarray, offsets: np.ndarray, prefix_tokens=None, prefix_offsets=None) -> ServiceResult:
+        """tokens uint32 (flat), offsets uint64 [n + 1]. Blocking; thread-safe. prefix_tokens / prefix_offsets: forced
+        target prefixes in the same form (slimt_hip_service_translate_prefixed; an empty range: not forced)."""
         tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         out = C.c_void_p()
-        if host_lib().slimt_hip_service_translate(self.h, _p(tokens), _p(offsets), offsets.size - 1, C.byref(out)):
+        if prefix_offsets is not None:
+            prefix_tokens = np.ascontiguousarray(prefix_tokens, dtype=np.uint32)
+            prefix_offsets = np.ascontiguousarray(prefix_offsets, dtype=np.uint64)
+            if prefix_offsets.size != offsets.size:
+                raise ValueError(f"prefixes: {prefix_offsets.size - 1} for {offsets.size - 1} sentences")
+            rc = host_lib().slimt_hip_service_translate_prefixed(self.h, _p(tokens), _p(offsets), _p(prefix_tokens),
+                                                                _p(prefix_offsets), offsets.size - 1, C.byref(out))
+        else:
+            rc = host_lib().slimt_hip_service_translate(self.h, _p(tokens), _p(offsets), offsets.size - 1, C.byref(out))
+        if rc:
             raise SlimtHipError(host_lib().slimt_hip_service_last_error().decode())
         return ServiceResult(out, np.diff(offsets).astype(np.int64))
 
-    def translate(self, sentences) -> ServiceResult:
+    @staticmethod
+    def _flat(sentences):
         lens = np.fromiter((len(s) for s in sentences), dtype=np.uint64, count=len(sentences))
         offsets = np.zeros(len(sentences) + 1, np.uint64)
         np.cumsum(lens, out=offsets[1:])
         tokens = np.fromiter(itertools.chain.from_iterable(sentences), dtype=np.uint32, count=int(offsets[-1]))
-        return self.translate_flat(tokens, offsets)
+        return tokens, offsets
+
+    def translate(self, sentences, prefixes=None) -> ServiceResult:
+        """prefixes: one token list per sentence (empty: not forced) -- forced target prefixes; a given translation with
+        its EOS is scored (include/slimt_hip_service_prefix.h)."""
+        if prefixes is None:
+            return self.translate_flat(*self._flat(sentences))
+        if len(prefixes) != len(sentences):
+            raise ValueError(f"prefixes: {len(prefixes)} for {len(sentences)} sentences")
+        return self.translate_flat(*self._flat(sentences), *self._flat(prefixes))
 
     def close(self):
         if getattr(self, "h", None):

@@ -920,11 +920,17 @@ __device__ __forceinline__ void attention_row(AttnRow r, int lane) {
 // beside its arg-max (scores.h), the reductions merge it, and the row's owner writes the token's log-probability to
 // a.scores (a.sub_scores[j]) where it writes the token. Compile-time like MG: the unscored kernels are the same
 // instruction streams as without the parameter. Only the 16-sentence tilings without clusters have the scored twin.
+// FP: forced (slimt_hip_ctx_set_target_prefix; always scored): a sentence's step t < its prefix length P records and feeds
+// the prefix's token instead of the arg-max. At the end of each step (and before the first) the row's owner resolves the
+// token forced at the next step to its output-layer column (device_common.h, forced_column; -1: none) into fcol_s; the
+// output layer's epilogue has the one lane that meets that column store its logit to ycap (no registers held for it
+// through the stream, no reduction), and the owner scores it with the row's maximum and sum (scores.h, forced_score).
 template <bool MG, int KSD, int KSF, int DH, bool LONG, bool NT, int RT = 1, bool KV24 = false, int MID = 0, int SPW = 16, int CL = 1,
-          int KVI = 20, bool SC = false>
+          int KVI = 20, bool SC = false, bool FP = false>
 __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
   static_assert(!MG || (RT == 1 && CL == 1 && MID <= 1), "merged launches: the 16-row tilings, sentences of up to 64 tokens");
   static_assert(!SC || (RT == 1 && CL == 1 && SPW == 16), "scored launches: the 16-sentence tilings without clusters");
+  static_assert(!FP || SC, "forced launches are scored");
   constexpr bool KV20 = KVI != 24;
   static_assert(KVI == 24 || KVI == 20 || (KVI == 16 && KV24 && (KSD == 4 || KSD == 8) && (RT == 1 || (KSD == 4 && MID == 0)) && CL == 1),
                 "16-bit form: sentences of up to 128 tokens at D = 256 (the 32-sentence tiling: up to 32), up to 32 at D = 512");
@@ -974,7 +980,9 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
   float *red_v = reinterpret_cast<float *>(A3 + R * LDA3);  // [NW][R]
   int *red_i = reinterpret_cast<int *>(red_v + NW * R);
   float *red_s = reinterpret_cast<float *>(red_i + NW * R);  // SC: [NW][R] the candidates' sums of exponentials
-  int *flags = red_i + NW * R + (SC ? NW * R : 0);  // [0] = number of finished sentences of this tile
+  [[maybe_unused]] float *ycap = red_s + NW * R;  // FP: [R] the logit of the row's forced column (-inf: not met)
+  [[maybe_unused]] int *fcol_s = reinterpret_cast<int *>(ycap + R);  // FP: [R] the forced columns of the step
+  int *flags = red_i + NW * R + (SC ? NW * R : 0) + (FP ? 2 * R : 0);  // [0] = number of finished sentences of this tile
   float *pbufs = reinterpret_cast<float *>(flags + 16);  // [NW][256] attention scratch
   float *kvpb = pbufs + NW * PBW;  // KV24: [Ld][K pb, V pb][D], or at D = 512 [Ld][K pb, K c127, V pb, V c127][D]
   // LayerNorm scale / bias of every layer in LDS ([Ld][rnn, attn, ffn][scale, bias][D]) where it fits:
@@ -1173,6 +1181,29 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
   // from logits[0] and only moves on `value > max`, so it stays at class 0 (Transformer.cc:287-298); the arg-max
   // below skips NaNs, so the rule is applied where the token is taken
   const bool nan0 = outw.pb[0] != outw.pb[0] || a.out.u != a.out.u;
+  // FP: each row's prefix length (clamped to its row of outputs) and the token forced at the current step (0xffffffff:
+  // none); step 0's column goes to fcol_s here -- the barriers of the step's layers order it before the epilogue
+  [[maybe_unused]] uint32_t plen[RT], ftok[RT];
+  if constexpr (FP) {
+    const uint32_t *const fsl = n_sub ? a.sub[sj].shortlist : a.shortlist;  // (the tile's output layer)
+#pragma unroll
+    for (int rr = 0; rr < RT; ++rr) {
+      plen[rr] = 0;
+      if (live[rr]) {
+        const uint32_t pl = (n_sub ? a.sub_prefix_len[SLIMT_SW(rr)] : a.prefix_len)[bq[rr] - SLIMT_SUB_FIRST(rr)];
+        plen[rr] = __builtin_amdgcn_readfirstlane(pl < (uint32_t)SLIMT_SUB_TMAX(rr) ? pl : (uint32_t)SLIMT_SUB_TMAX(rr));
+      }
+      ftok[rr] = plen[rr] > 0
+                     ? __builtin_amdgcn_readfirstlane((n_sub ? a.sub_prefix_ids[SLIMT_SW(rr)] : a.prefix_ids)
+                                                          [(size_t)(bq[rr] - SLIMT_SUB_FIRST(rr)) * SLIMT_SUB_TMAX(rr)])
+                     : 0xffffffffu;
+      const int c = forced_column(fsl, outw.N, ftok[rr], lane);
+      if (row_wave && lane == 0) {
+        fcol_s[16 * rr + wave] = c;
+        ycap[16 * rr + wave] = -__builtin_inff();
+      }
+    }
+  }
   // (a dense tile runs while any of its sentences does: each ends at its own limit below; an aligned one has one limit)
   const int max_steps = n_sub && !a.sub_dense ? a.sub[sj].max_steps : a.max_steps;
   bool all_done = false;
@@ -1740,6 +1771,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
     float bv[RT][4];
     int bi[RT][4];
     [[maybe_unused]] float bs[RT][4];  // SC: sum of exp(logit - bv) over this lane's columns so far
+    [[maybe_unused]] int fc[RT][4];    // FP: the row's forced column (-1: none)
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -1747,6 +1779,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
         bv[rt][r] = -3.402823466e+38f;
         bi[rt][r] = 0x7fffffff;
         if constexpr (SC) bs[rt][r] = 0.0f;
+        if constexpr (FP) fc[rt][r] = fcol_s[16 * rt + lg * 4 + r];
       }
     stream_gemm_from<KSD, NB_OUT, 0, (KSD >= 4), RT>(
         A1, LDA, outw, wave, lane, fl, [&](int tile, int rt, const v4i &acc, int co, float pb) {
@@ -1765,6 +1798,9 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
             // a lane's columns only grow, so strict > keeps its first maximum
             const bool better = in_range && v > bv[rt][r];
             if constexpr (SC) lse_push(v, in_range, better, bv[rt][r], bs[rt][r]);
+            if constexpr (FP) {  // (one lane of one wave per row, once per step)
+              if (col == fc[rt][r]) ycap[16 * rt + lg * 4 + r] = v;
+            }
             bv[rt][r] = better ? v : bv[rt][r];
             bi[rt][r] = better ? col : bi[rt][r];
           }
@@ -1805,7 +1841,15 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
           float sum = lane < NW ? red_s[lane * R + row] : 0.0f;
           row16_argmax_lse(v, ix, sum);
           ix = __builtin_amdgcn_readfirstlane(ix);
-          score = lse_score(sum, ix == 0x7fffffff || nan0);
+          if constexpr (FP) {
+            if (ftok[rr] != 0xffffffffu) {
+              score = forced_score(sum, ycap[row] - v, ix == 0x7fffffff || nan0);
+            } else {
+              score = lse_score(sum, ix == 0x7fffffff || nan0);
+            }
+          } else {
+            score = lse_score(sum, ix == 0x7fffffff || nan0);
+          }
         } else {
           float v = lane < NW ? red_v[lane * R + row] : -3.402823466e+38f;
           ix = lane < NW ? red_i[lane * R + row] : 0x7fffffff;
@@ -1817,6 +1861,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
         ix = (ix == 0x7fffffff || nan0) ? 0 : ix;
         const uint32_t *sl = n_sub ? a.sub[sj].shortlist : a.shortlist;  // (one output layer per tile: the tile's sub-batch's list)
         if (live[rr]) tok = sl ? sl[ix] : (uint32_t)ix;
+        if constexpr (FP) tok = ftok[rr] != 0xffffffffu ? ftok[rr] : tok;  // (only live rows have one)
       }
       if (live[rr] && !finished[rr]) {  // record(), Model.cc:127-137
         const int Tr = SLIMT_SUB_TMAX(rr);
@@ -1829,6 +1874,18 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
         if (tok == a.eos || (n_sub && (int)n_out[rr] >= a.sub[SLIMT_SW(rr)].max_steps)) {
           finished[rr] = true;
           if (lane == 0) atomicAdd(&flags[0], 1);
+        }
+      }
+      if constexpr (FP) {  // the token forced at the next step, and its column for that step's epilogue
+        const uint32_t nt = t + 1 < max_steps && live[rr] && !finished[rr] && n_out[rr] < plen[rr]
+                                ? __builtin_amdgcn_readfirstlane((n_sub ? a.sub_prefix_ids[SLIMT_SW(rr)] : a.prefix_ids)
+                                                                     [(size_t)(bq[rr] - SLIMT_SUB_FIRST(rr)) * SLIMT_SUB_TMAX(rr) + n_out[rr]])
+                                : 0xffffffffu;
+        ftok[rr] = nt;
+        const int c = forced_column(n_sub ? a.sub[sj].shortlist : a.shortlist, outw.N, nt, lane);
+        if (lane == 0) {  // (after this wave's read of ycap[row] above: LDS operations of a wave stay in order)
+          fcol_s[row] = c;
+          ycap[row] = -__builtin_inff();
         }
       }
       if (t + 1 < max_steps) {
@@ -1916,8 +1973,9 @@ int fused_decode_grid(int B, bool tickets, int rows) {
 // D = 256, 16-row, non-MID variants) still fit the 160 KiB; the returned size includes them then.
 // tight: the kernels with the 16-bit cache form inlined (KVI = 16) keep its column terms [Ld][K, V][D] behind everything else.
 // scores: the scored kernels (SC) keep one more [NW][rows] float array beside the arg-max's (red_s)
+// forced: the forced kernels (FP) one float (ycap) and one int (fcol_s) per row
 size_t fused_decode_lds_bytes(int D, int F, int Ld, int rows, bool kv24 = false, int mid = 0,
-                              bool *ln_in_lds = nullptr, bool tight = false, bool scores = false) {
+                              bool *ln_in_lds = nullptr, bool tight = false, bool scores = false, bool forced = false) {
   // D * rows > 256 * 16: two f32 row buffers, SSRU cells in global memory (see the kernel)
   const size_t R = (size_t)rows;
   const bool lean = (size_t)D * R > 256 * 16;
@@ -1926,7 +1984,8 @@ size_t fused_decode_lds_bytes(int D, int F, int Ld, int rows, bool kv24 = false,
   const size_t base = f32rows + 2 * R * (size_t)(D + 32) + R * (size_t)(F + 32) + 2 * NW * R * 4 + 64 +
                       NW * (mid == 2 ? 1024 : mid == 1 ? 512 : 256) * 4 + (kv24 ? (size_t)Ld * (D == 512 ? 4 : 2) * D * 4 : 0) +
                       (tight ? (size_t)Ld * (rows > 16 ? 1 : 2) * D * 4 : 0) +  // (32 sentences: the K centres only)
-                      (scores ? (size_t)NW * R * 4 : 0);
+                      (scores ? (size_t)NW * R * 4 : 0) +
+                      (forced ? 2 * R * 4 : 0);  // (FP: ycap and fcol_s, 128 bytes at 16 rows)
   const size_t ln = (D == 256 && rows == 16 && !mid) ? (size_t)Ld * 6 * D * 4 : 0;
   const bool fits = ln > 0 && base + ln <= 160 * 1024;
   if (ln_in_lds) *ln_in_lds = fits;
@@ -1975,31 +2034,34 @@ bool fused_decode_supported(int D, int F, int H, int Ld) {
 
 // a kernel of the launcher's choice, scored (SC) or not: nullptr where the scored twin does not exist (32-sentence,
 // 8- and 4-sentence tilings, clusters) -- a scored call there fails instead of losing its scores
-template <bool MG, bool SC, int KSD, int KSF, int DH, bool LONG, bool NT, int RT = 1, bool KV24 = false, int MID = 0, int SPW = 16,
-          int CL = 1, int KVI = 20>
+// (FP: the forced twin, likewise; a forced call where it does not exist fails instead of ignoring its prefix)
+template <bool MG, bool SC, bool FP, int KSD, int KSF, int DH, bool LONG, bool NT, int RT = 1, bool KV24 = false, int MID = 0,
+          int SPW = 16, int CL = 1, int KVI = 20>
 static constexpr auto dfk() -> void (*)(FusedDecodeArgs) {
-  if constexpr (SC && (RT != 1 || CL != 1 || SPW != 16))
+  if constexpr ((SC || FP) && (RT != 1 || CL != 1 || SPW != 16))
     return nullptr;
+  else if constexpr (FP)
+    return decode_fused_kernel<MG, KSD, KSF, DH, LONG, NT, RT, KV24, MID, SPW, CL, KVI, true, true>;
   else
     return decode_fused_kernel<MG, KSD, KSF, DH, LONG, NT, RT, KV24, MID, SPW, CL, KVI, SC>;
 }
 
 // the long-sentence instantiation exists for d_head 32 only (attention_row_long), the
 // non-temporal K/V variant for d_head 32 and 64 (the buffer-load paths of attention_row)
-template <bool MG, bool SC, int KSD, int KSF, int DH>
+template <bool MG, bool SC, bool FP, int KSD, int KSF, int DH>
 static auto decode_fused_pick(bool long_sentences, bool nt) -> void (*)(FusedDecodeArgs) {
   if constexpr (DH == 32) {
-    if (long_sentences) return nt ? dfk<MG, SC, KSD, KSF, DH, true, true>() : dfk<MG, SC, KSD, KSF, DH, true, false>();
+    if (long_sentences) return nt ? dfk<MG, SC, FP, KSD, KSF, DH, true, true>() : dfk<MG, SC, FP, KSD, KSF, DH, true, false>();
   }
   if constexpr (DH >= 32) {
-    if (nt) return dfk<MG, SC, KSD, KSF, DH, false, true>();
+    if (nt) return dfk<MG, SC, FP, KSD, KSF, DH, false, true>();
   }
   (void)long_sentences;
   (void)nt;
-  return dfk<MG, SC, KSD, KSF, DH, false, false>();
+  return dfk<MG, SC, FP, KSD, KSF, DH, false, false>();
 }
 
-template <bool MG, bool SC>
+template <bool MG, bool SC, bool FP = false>
 static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int F, int H, hipStream_t st) {
   FusedDecodeArgs a = a_in;
   if (!fused_decode_supported(D, F, H, a.Ld)) return hipErrorInvalidValue;
@@ -2024,29 +2086,29 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
   };
   // the variants over the packed cache: <KSD, KSF, DH, MID> x non-temporal K/V loads x sentences per workgroup
 #define SLIMT_KV24_PICK(KSD_, KSF_, DH_, MID_)                                                                  \
-  (rows == 4   ? (a.kv_nt ? dfk<MG, SC, KSD_, KSF_, DH_, false, true, 1, true, MID_, 4>()                 \
-                          : dfk<MG, SC, KSD_, KSF_, DH_, false, false, 1, true, MID_, 4>())               \
-   : rows == 8 ? (a.kv_nt ? dfk<MG, SC, KSD_, KSF_, DH_, false, true, 1, true, MID_, 8>()                 \
-                          : dfk<MG, SC, KSD_, KSF_, DH_, false, false, 1, true, MID_, 8>())               \
-               : (a.kv_nt ? dfk<MG, SC, KSD_, KSF_, DH_, false, true, 1, true, MID_>()                    \
-                          : dfk<MG, SC, KSD_, KSF_, DH_, false, false, 1, true, MID_>()))
+  (rows == 4   ? (a.kv_nt ? dfk<MG, SC, FP, KSD_, KSF_, DH_, false, true, 1, true, MID_, 4>()                 \
+                          : dfk<MG, SC, FP, KSD_, KSF_, DH_, false, false, 1, true, MID_, 4>())               \
+   : rows == 8 ? (a.kv_nt ? dfk<MG, SC, FP, KSD_, KSF_, DH_, false, true, 1, true, MID_, 8>()                 \
+                          : dfk<MG, SC, FP, KSD_, KSF_, DH_, false, false, 1, true, MID_, 8>())               \
+               : (a.kv_nt ? dfk<MG, SC, FP, KSD_, KSF_, DH_, false, true, 1, true, MID_>()                    \
+                          : dfk<MG, SC, FP, KSD_, KSF_, DH_, false, false, 1, true, MID_>()))
   // every cache of this launch in the 24-bit form (a.kv_fmt == nullptr): the 16-sentence tilings have an instantiation
   // with that form inlined (KVI = 24); the 8- / 4-sentence ones reach it through the fallback call
 #define SLIMT_KV24_ONLY(KSD_, KSF_, DH_, MID_)                                                        \
-  (a.kv_nt ? dfk<MG, SC, KSD_, KSF_, DH_, false, true, 1, true, MID_, 16, 1, 24>()          \
-           : dfk<MG, SC, KSD_, KSF_, DH_, false, false, 1, true, MID_, 16, 1, 24>())
+  (a.kv_nt ? dfk<MG, SC, FP, KSD_, KSF_, DH_, false, true, 1, true, MID_, 16, 1, 24>()          \
+           : dfk<MG, SC, FP, KSD_, KSF_, DH_, false, false, 1, true, MID_, 16, 1, 24>())
   const bool only24 = kv24 && !a.kv_fmt && rows == 16 && a.cluster <= 1;
   if constexpr (MG) {  // (the merged twins: 16-row tilings, sentences of up to 64 tokens, no clusters)
     if (rows > 16 || mid == 2 || a.cluster > 1) return hipErrorInvalidValue;
   }
   if (mid) {
     if (rows > 16 || F != 1536) return hipErrorInvalidValue;
-    const size_t ldsm = fused_decode_lds_bytes(D, F, a.Ld, 16, true, mid, nullptr, a.kv_tight, SC);
+    const size_t ldsm = fused_decode_lds_bytes(D, F, a.Ld, 16, true, mid, nullptr, a.kv_tight, SC, FP);
     if (ldsm > 160 * 1024) return hipErrorInvalidValue;
     if (a.kv_tight) {
 #define SLIMT_KV16_PICK(MID_, SPW_)                                                                \
-  (a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 1, true, MID_, SPW_, 1, 16>()               \
-           : dfk<MG, SC, 4, 24, 32, false, false, 1, true, MID_, SPW_, 1, 16>())
+  (a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 1, true, MID_, SPW_, 1, 16>()               \
+           : dfk<MG, SC, FP, 4, 24, 32, false, false, 1, true, MID_, SPW_, 1, 16>())
       if (mid == 1) return go(rows == 4 ? SLIMT_KV16_PICK(1, 4) : rows == 8 ? SLIMT_KV16_PICK(1, 8) : SLIMT_KV16_PICK(1, 16), ldsm);
       if constexpr (!MG) return go(rows == 4 ? SLIMT_KV16_PICK(2, 4) : rows == 8 ? SLIMT_KV16_PICK(2, 8) : SLIMT_KV16_PICK(2, 16), ldsm);
 #undef SLIMT_KV16_PICK
@@ -2058,14 +2120,14 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
     if (only24) return go(SLIMT_KV24_ONLY(4, 24, 32, 1), ldsm);
     return go(SLIMT_KV24_PICK(4, 24, 32, 1), ldsm);
   }
-  const size_t lds = fused_decode_lds_bytes(D, F, a.Ld, rows <= 16 ? 16 : rows, kv24, 0, &a.ln_in_lds, a.kv_tight, SC);
+  const size_t lds = fused_decode_lds_bytes(D, F, a.Ld, rows <= 16 ? 16 : rows, kv24, 0, &a.ln_in_lds, a.kv_tight, SC, FP);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   if (kv24 && D == 512) {
     if (F != 2048) return hipErrorInvalidValue;
     if (a.kv_tight) {
 #define SLIMT_KV16_PICK(SPW_)                                                                      \
-  (a.kv_nt ? dfk<MG, SC, 8, 32, 64, false, true, 1, true, 0, SPW_, 1, 16>()                  \
-           : dfk<MG, SC, 8, 32, 64, false, false, 1, true, 0, SPW_, 1, 16>())
+  (a.kv_nt ? dfk<MG, SC, FP, 8, 32, 64, false, true, 1, true, 0, SPW_, 1, 16>()                  \
+           : dfk<MG, SC, FP, 8, 32, 64, false, false, 1, true, 0, SPW_, 1, 16>())
       return go(rows == 4 ? SLIMT_KV16_PICK(4) : rows == 8 ? SLIMT_KV16_PICK(8) : SLIMT_KV16_PICK(16), lds);
 #undef SLIMT_KV16_PICK
     }
@@ -2075,15 +2137,15 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
   if constexpr (!MG) {
   if (a.cluster > 1) {  // cluster logits: the 16-sentence tiling of the D = 256 packed-cache shape
     if (!(kv24 && D == 256 && F == 1536 && rows == 16 && a.cluster == 4 && a.cl_act && a.cl_part && a.cl_sync)) return hipErrorInvalidValue;
-    return go(a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 1, true, 0, 16, 4>()
-                      : dfk<MG, SC, 4, 24, 32, false, false, 1, true, 0, 16, 4>(), lds);
+    return go(a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 1, true, 0, 16, 4>()
+                      : dfk<MG, SC, FP, 4, 24, 32, false, false, 1, true, 0, 16, 4>(), lds);
   }
   }
   if (only24) return go(SLIMT_KV24_ONLY(4, 24, 32, 0), lds);
   if (kv24 && rows <= 16 && a.kv_tight) {  // sentences may be in the tight 16-bit form: the kernels with it (and the 20-bit one) inlined
 #define SLIMT_KV16_PICK(SPW_)                                                                      \
-  (a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 1, true, 0, SPW_, 1, 16>()                  \
-           : dfk<MG, SC, 4, 24, 32, false, false, 1, true, 0, SPW_, 1, 16>())
+  (a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 1, true, 0, SPW_, 1, 16>()                  \
+           : dfk<MG, SC, FP, 4, 24, 32, false, false, 1, true, 0, SPW_, 1, 16>())
     return go(rows == 4 ? SLIMT_KV16_PICK(4) : rows == 8 ? SLIMT_KV16_PICK(8) : SLIMT_KV16_PICK(16), lds);
 #undef SLIMT_KV16_PICK
   }
@@ -2093,19 +2155,19 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
   if constexpr (!MG) {
   if (rows == 32) {
     if (kv24 && a.kv_tight)
-      return go(a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 2, true, 0, 16, 1, 16>()
-                        : dfk<MG, SC, 4, 24, 32, false, false, 2, true, 0, 16, 1, 16>(), lds);
+      return go(a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 2, true, 0, 16, 1, 16>()
+                        : dfk<MG, SC, FP, 4, 24, 32, false, false, 2, true, 0, 16, 1, 16>(), lds);
     if (kv24 && !a.kv_fmt)  // every cache in the 24-bit form: that form inlined (KVI = 24), as for the 16-sentence tilings
-      return go(a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 2, true, 0, 16, 1, 24>()
-                        : dfk<MG, SC, 4, 24, 32, false, false, 2, true, 0, 16, 1, 24>(), lds);
-    auto k = kv24 ? (a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 2, true>() : dfk<MG, SC, 4, 24, 32, false, false, 2, true>())
-                  : (a.kv_nt ? dfk<MG, SC, 4, 24, 32, false, true, 2>() : dfk<MG, SC, 4, 24, 32, false, false, 2>());
+      return go(a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 2, true, 0, 16, 1, 24>()
+                        : dfk<MG, SC, FP, 4, 24, 32, false, false, 2, true, 0, 16, 1, 24>(), lds);
+    auto k = kv24 ? (a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 2, true>() : dfk<MG, SC, FP, 4, 24, 32, false, false, 2, true>())
+                  : (a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 2>() : dfk<MG, SC, FP, 4, 24, 32, false, false, 2>());
     return go(k, lds);
   }
   }
 #define SLIMT_FUSED_CASE(KSD_, KSF_, DH_)                                                   \
   if (D == 64 * KSD_ && F == 64 * KSF_ && D / H == DH_) {                                    \
-    auto k = decode_fused_pick<MG, SC, KSD_, KSF_, DH_>(a.S > 32, a.kv_nt);                           \
+    auto k = decode_fused_pick<MG, SC, FP, KSD_, KSF_, DH_>(a.S > 32, a.kv_nt);                           \
     if (!k) return hipErrorInvalidValue;                                                     \
     hipError_t e = set_dynamic_lds_once(reinterpret_cast<const void *>(k), (int)lds); \
     if (e != hipSuccess) return e;                                                           \
@@ -2119,6 +2181,10 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
 }
 
 hipError_t launch_decode_fused(const FusedDecodeArgs &a, int D, int F, int H, hipStream_t st) {
+  if (a.prefix_ids || a.sub_prefix_ids[0]) {  // (forced: scored as well -- the engine gives every batch a destination)
+    if (!(a.n_sub > 0 ? a.sub_scores[0] && a.sub_prefix_len[0] : a.scores && a.prefix_len)) return hipErrorInvalidValue;
+    return a.n_sub > 0 ? launch_decode_fused_t<true, true, true>(a, D, F, H, st) : launch_decode_fused_t<false, true, true>(a, D, F, H, st);
+  }
   if (a.scores || a.sub_scores[0])  // (scored: every sub-batch of a merged launch has its destination; the engine checks)
     return a.n_sub > 0 ? launch_decode_fused_t<true, true>(a, D, F, H, st) : launch_decode_fused_t<false, true>(a, D, F, H, st);
   return a.n_sub > 0 ? launch_decode_fused_t<true, false>(a, D, F, H, st) : launch_decode_fused_t<false, false>(a, D, F, H, st);

@@ -252,18 +252,24 @@ __global__ __launch_bounds__(256) void dgemm_kernel(DGemmArgs a) {
         }
       }
     }
-  } else if constexpr (EPI == EPI_ARGMAX || EPI == EPI_ARGMAX_SC) {
+  } else if constexpr (EPI == EPI_ARGMAX || EPI == EPI_ARGMAX_SC || EPI == EPI_ARGMAX_FP) {
     // SC: beside the first maximum, the sum of exp(logit - maximum) over the same columns (scores.h)
-    constexpr bool SC = EPI == EPI_ARGMAX_SC;
+    // FP (and SC): the logit of the row's forced column (a.fcol) where it is one of this block's, else -inf
+    constexpr bool FP = EPI == EPI_ARGMAX_FP;
+    constexpr bool SC = EPI == EPI_ARGMAX_SC || FP;
     __syncthreads();  // A_lds is reused as the reduction buffer
     float *red_v = reinterpret_cast<float *>(smem);
     int *red_i = reinterpret_cast<int *>(red_v + 64);
     float *red_s = reinterpret_cast<float *>(red_i + 64);  // (SC only)
+    [[maybe_unused]] float *red_y = red_s + 64;  // (FP only)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float bv = -3.402823466e+38f;
       int bi = 0x7fffffff;
       float bs = 0.0f;
+      [[maybe_unused]] float by = -__builtin_inff();
+      [[maybe_unused]] int fc = -1;
+      if constexpr (FP) fc = m0 + lg * 4 + r < a.B ? a.fcol[m0 + lg * 4 + r] : -1;
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         const int ntile = nt0 + nt;
@@ -272,6 +278,7 @@ __global__ __launch_bounds__(256) void dgemm_kernel(DGemmArgs a) {
           float v = (float)(acc[nt][r] + 127 * a.w.colsum[col]) * u;
           v = v + a.w.pb[col];
           if constexpr (SC) lse_push(v, true, v > bv, bv, bs);
+          if constexpr (FP) by = col == fc ? v : by;
           if (v > bv || (v == bv && col < bi)) {
             bv = v;
             bi = col;
@@ -286,6 +293,7 @@ __global__ __launch_bounds__(256) void dgemm_kernel(DGemmArgs a) {
           float mm = bv;
           lse_merge(mm, bs, ov, __shfl_xor(bs, m, 64));
         }
+        if constexpr (FP) by = fmaxf(by, __shfl_xor(by, m, 64));
         if (ov > bv || (ov == bv && oi < bi)) {
           bv = ov;
           bi = oi;
@@ -295,6 +303,7 @@ __global__ __launch_bounds__(256) void dgemm_kernel(DGemmArgs a) {
         red_v[wave * 16 + lg * 4 + r] = bv;
         red_i[wave * 16 + lg * 4 + r] = bi;
         if constexpr (SC) red_s[wave * 16 + lg * 4 + r] = bs;
+        if constexpr (FP) red_y[wave * 16 + lg * 4 + r] = by;
       }
     }
     __syncthreads();
@@ -317,6 +326,9 @@ __global__ __launch_bounds__(256) void dgemm_kernel(DGemmArgs a) {
         a.part_val[(size_t)row * a.n_parts + blockIdx.y] = bv;
         a.part_idx[(size_t)row * a.n_parts + blockIdx.y] = bi;
         if constexpr (SC) a.part_sum[(size_t)row * a.n_parts + blockIdx.y] = bs;
+        if constexpr (FP)
+          a.part_y[(size_t)row * a.n_parts + blockIdx.y] =
+              fmaxf(fmaxf(red_y[tid], red_y[16 + tid]), fmaxf(red_y[32 + tid], red_y[48 + tid]));
       }
     }
   }
@@ -359,6 +371,8 @@ static hipError_t launch_dgemm_t(const DGemmArgs &a, int epi, dim3 grid, size_t 
     hipLaunchKernelGGL((dgemm_kernel<PF, NT, EPI_ARGMAX, false>), grid, dim3(256), lds, st, a);
   else if (epi == EPI_ARGMAX_SC && !i8 && a.part_sum)
     hipLaunchKernelGGL((dgemm_kernel<PF, NT, EPI_ARGMAX_SC, false>), grid, dim3(256), lds, st, a);
+  else if (epi == EPI_ARGMAX_FP && !i8 && a.part_sum && a.fcol && a.part_y)
+    hipLaunchKernelGGL((dgemm_kernel<PF, NT, EPI_ARGMAX_FP, false>), grid, dim3(256), lds, st, a);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
@@ -372,7 +386,7 @@ hipError_t launch_dgemm(const DGemmArgs &a, int epilogue, hipStream_t st) {
   int pf, nt;
   dgemm_config(K, N, a.B, &pf, &nt);
   const int col_blocks = (N + 64 * nt - 1) / (64 * nt);
-  if ((epilogue == EPI_ARGMAX || epilogue == EPI_ARGMAX_SC) && a.n_parts != col_blocks) return hipErrorInvalidValue;
+  if ((epilogue == EPI_ARGMAX || epilogue == EPI_ARGMAX_SC || epilogue == EPI_ARGMAX_FP) && a.n_parts != col_blocks) return hipErrorInvalidValue;
   const dim3 grid((a.B + 15) / 16, col_blocks);
   size_t lds = 16 * (size_t)(K + 16) + 16 * (size_t)(D + 4) * sizeof(float);
   if (lds < 1024) lds = 1024;

@@ -214,6 +214,27 @@ __device__ __forceinline__ void row16_argmax_lse(float &v, int &ix, float &s) {
   argmax_lse_step<8>(v, ix, s);
 }
 
+// The output-layer column of a forced token (slimt_hip_ctx_set_target_prefix), the same on every lane of the wave:
+// with the full vocabulary (sl == nullptr) the token itself, with a shortlist (N sorted unique ids) the index that holds
+// it; -1 where the layer has no such column (tok == 0xffffffff: nothing forced). Every lane calls it. A 64-ary search:
+// each round the lanes probe 64 evenly spaced entries of the range and keep the last one <= tok (the ids are sorted, so
+// those lanes are a prefix) -- two dependent loads for a 4096-entry list. Every load lies inside sl[0 .. N).
+__device__ __forceinline__ int forced_column(const uint32_t *sl, int N, uint32_t tok, int lane) {
+  if (tok == 0xffffffffu) return -1;
+  if (!sl) return tok < (uint32_t)N ? (int)tok : -1;
+  int lo = 0, n = N;  // [lo, lo + n) holds tok if anything does
+  while (n > 64) {
+    const int step = (n + 63) / 64, end = lo + n;
+    const int i = lo + lane * step;
+    const unsigned long long le = __builtin_amdgcn_ballot_w64(i < end && sl[i] <= tok);
+    if (!le) return -1;
+    lo += (63 - __builtin_clzll(le)) * step;
+    n = end - lo < step ? end - lo : step;
+  }
+  const unsigned long long hit = __builtin_amdgcn_ballot_w64(lane < n && sl[lo + lane] == tok);
+  return hit ? lo + __builtin_ctzll(hit) : -1;
+}
+
 // xor butterfly over the 64 lanes, masks ascending; all lanes end equal.
 __device__ __forceinline__ float wave_sum(float v) {
   return bf_add<32>(bf_add<16>(bf_add<8>(bf_add<4>(bf_add<2>(bf_add<1>(v))))));

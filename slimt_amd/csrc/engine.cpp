@@ -1061,7 +1061,7 @@ void sinusoid_table(int S, int D, std::vector<float> &out) {
 void ctx_free(slimt_hip_ctx *c) {
   DevBuf *bufs[] = {&c->pos, &c->ids, &c->lengths, &c->x0, &c->x1, &c->q, &c->k, &c->v, &c->att,
                     &c->h8, &c->a8, &c->ticket, &c->kv, &c->kv_fmt, &c->cl_act, &c->cl_part, &c->cl_sync, &c->dx, &c->dx_pre, &c->dh, &c->datt8, &c->dout, &c->df8,
-                    &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->prev, &c->out_ids, &c->out_len,
+                    &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag};
   for (auto *b : bufs) b->release();
@@ -1251,6 +1251,16 @@ extern "C" int slimt_hip_ctx_set_scores(slimt_hip_ctx *ctx, float *const *scores
   if (!scores && n) return fail(-1, "scores is NULL");
   ctx->sc_next.assign(scores, scores + n);  // (checked by the call that takes them: ScoreCall)
   ctx->sc_armed = n > 0;  // (n = 0: nothing armed)
+  return 0;
+}
+
+extern "C" int slimt_hip_ctx_set_target_prefix(slimt_hip_ctx *ctx, const uint32_t *const *prefix_ids,
+                                               const uint32_t *const *prefix_len, size_t n) {
+  if (!ctx) return fail(-1, "null argument");
+  if ((!prefix_ids || !prefix_len) && n) return fail(-1, "target prefix arrays are NULL");
+  ctx->fp_next_ids.assign(prefix_ids, prefix_ids + n);  // (checked by the call that takes them: PrefixCall)
+  ctx->fp_next_len.assign(prefix_len, prefix_len + n);
+  ctx->fp_armed = n > 0;  // (n = 0: nothing armed)
   return 0;
 }
 
@@ -1452,6 +1462,8 @@ struct MergePlan {
   size_t stride_wp = 0, stride_cs = 0, stride_pb = 0;
   bool dense = false;  // one output layer for all sub-batches: no holes between them (kernels.h, FusedDecodeArgs::sub_dense)
   float *scores[kMaxMerge] = {};  // scored launches: sub-batch j's destination, device-visible (FusedDecodeArgs::sub_scores)
+  const uint32_t *prefix_ids[kMaxMerge] = {};  // forced launches: sub-batch j's prefix in device memory (FusedDecodeArgs)
+  const uint32_t *prefix_len[kMaxMerge] = {};
 };
 
 // The scores armed on a context (slimt_hip_ctx_set_scores) are taken by the translate entry point that comes next, whether
@@ -1484,6 +1496,93 @@ struct ScoreCall {
     c->sc_dev = nullptr;
   }
 };
+
+// The target prefix armed on a context (slimt_hip_ctx_set_target_prefix), taken like the scores (ScoreCall) by the next
+// translate entry point, whether it then succeeds or fails. The entry points point ctx->fp_ids / fp_len at device memory
+// the kernels read: the caller's arrays for the _device calls, else a staged copy (prefix_stage).
+struct PrefixCall {
+  slimt_hip_ctx *c = nullptr;
+  std::vector<const uint32_t *> ids, len;
+  int rc = 0;
+  PrefixCall(slimt_hip_ctx *ctx, size_t n) {
+    if (!ctx || !ctx->fp_armed) return;
+    c = ctx;
+    ids.swap(ctx->fp_next_ids);
+    len.swap(ctx->fp_next_len);
+    ctx->fp_armed = false;
+    ctx->fp_next_ids.clear();
+    ctx->fp_next_len.clear();
+    if (ids.size() != n) {
+      rc = fail(-1, "target prefix: %zu batches armed, the call has %zu", ids.size(), n);
+    } else {
+      for (size_t j = 0; j < n && !rc; ++j)
+        if (!ids[j] || !len[j]) rc = fail(-1, "target prefix: batch %zu has a NULL array", j);
+    }
+    ctx->fp_call = rc == 0;
+    ctx->fp_user_ids = rc == 0 && n == 1 ? ids[0] : nullptr;
+    ctx->fp_user_len = rc == 0 && n == 1 ? len[0] : nullptr;
+    ctx->fp_ids = ctx->fp_len = nullptr;
+  }
+  ~PrefixCall() {
+    if (!c) return;
+    c->fp_call = false;
+    c->fp_user_ids = c->fp_user_len = nullptr;
+    c->fp_ids = c->fp_len = nullptr;
+  }
+};
+
+// A host prefix of B sentences with rows Tmax apart: every length <= Tmax, every id of the prefix < V.
+int prefix_check(const slimt_hip_ctx *c, const uint32_t *ids, const uint32_t *len, size_t B, size_t Tmax) {
+  for (size_t b = 0; b < B; ++b) {
+    if (len[b] > Tmax) return fail(-1, "target prefix: length %u of sentence %zu > Tmax %zu", len[b], b, Tmax);
+    for (size_t t = 0; t < len[b]; ++t)
+      if (ids[b * Tmax + t] >= (uint32_t)c->model->V)
+        return fail(-1, "target prefix: id %u of sentence %zu out of range", ids[b * Tmax + t], b);
+  }
+  return 0;
+}
+
+void *host_device_view(const void *p);  // (below)
+
+// Host prefixes -> addresses the kernels read. Pinned arrays (hipHostMalloc / slimt_hip_host_alloc) are read in place,
+// like the pinned inputs of the asynchronous calls (translate_host: no copy queued behind other streams' kernels); a
+// pageable batch's ids and lengths are staged in device memory with one asynchronous copy each on the context's stream.
+// parts: n batches' (ids, len, B, Tmax); the addresses go to d_ids[j] / d_len[j]. Checked first: nothing is queued for an
+// invalid prefix.
+int prefix_stage(slimt_hip_ctx *c, size_t n, const uint32_t *const *ids, const uint32_t *const *len, const size_t *B,
+                 const size_t *Tmax, const uint32_t **d_ids, const uint32_t **d_len) {
+  size_t words = 0;
+  std::vector<bool> pinned(n);
+  for (size_t j = 0; j < n; ++j) {
+    RCCHK(prefix_check(c, ids[j], len[j], B[j], Tmax[j]));
+    d_ids[j] = static_cast<const uint32_t *>(host_device_view(ids[j]));
+    d_len[j] = static_cast<const uint32_t *>(host_device_view(len[j]));
+    pinned[j] = d_ids[j] && d_len[j];
+    if (!pinned[j]) words += B[j] * Tmax[j] + B[j];
+  }
+  if (words) HIPCHK(c->fp_stage.reserve(words * 4));
+  uint32_t *p = c->fp_stage.as<uint32_t>();
+  for (size_t j = 0; j < n; ++j) {
+    if (pinned[j]) continue;
+    HIPCHK(hipMemcpyAsync(p, ids[j], B[j] * Tmax[j] * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(p + B[j] * Tmax[j], len[j], B[j] * 4, hipMemcpyHostToDevice, c->stream));
+    d_ids[j] = p;
+    d_len[j] = p + B[j] * Tmax[j];
+    p += B[j] * Tmax[j] + B[j];
+  }
+  return 0;
+}
+
+// the host prefixes of a call's batches (PrefixCall) staged at once (prefix_stage): batch j of B_j sentences padded to S_j
+int prefix_stage_batches(slimt_hip_ctx *c, const PrefixCall &pc, const slimt_hip_batch *batches, size_t n, size_t S,
+                         float limit_factor, const uint32_t **d_ids, const uint32_t **d_len) {
+  std::vector<size_t> B(n), T(n);
+  for (size_t j = 0; j < n; ++j) {
+    B[j] = batches[j].B;
+    T[j] = std::max<size_t>(1, (size_t)(limit_factor * (float)(batches[j].S ? batches[j].S : S)));
+  }
+  return prefix_stage(c, n, pc.ids.data(), pc.len.data(), B.data(), T.data(), d_ids, d_len);
+}
 
 // gen (nullable; only where fused_encoder_chosen): the batch's shortlist is generated inside the encoder launch
 // (kernels.h, FusedEncodeArgs::gen) -- its ids / count are pack->idx / pack->n_dev.
@@ -1982,11 +2081,21 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   ds.eos = eos_id;
   // a scored call (ScoreCall): each recorded token's log-probability goes beside it -- to c->sc_dev, or in a merged launch
   // to each sub-batch's mp->scores[j] (the entry points set them to addresses the kernels can write)
-  const bool scored = c->sc_call;
-  float *const d_scores = scored && !mp ? c->sc_dev : nullptr;
+  // a forced call (PrefixCall) takes the scored kernels' forced twins: scored as well, into a context-owned scratch when the
+  // caller did not ask for scores (merged: sub-batch j's rows of it from its first sentence on, Tmax_j <= Tmax)
+  const bool forced = c->fp_call;
+  const bool scored = c->sc_call || forced;
+  if (forced && !c->sc_call) {
+    HIPCHK(c->fp_scratch.reserve(B * Tmax * 4));
+    for (int j = 0; mp && j < mp->n; ++j) mp->scores[j] = c->fp_scratch.as<float>() + (size_t)mp->out[j].first * Tmax;
+  }
+  float *const d_scores = scored && !mp ? (c->sc_call ? c->sc_dev : c->fp_scratch.as<float>()) : nullptr;
   if (scored && !mp && !d_scores) return fail(-1, "scores: no destination for this batch");
   for (int j = 0; scored && mp && j < mp->n; ++j)
     if (!mp->scores[j]) return fail(-1, "scores: no destination for batch %d", j);
+  if (forced && !mp && !(c->fp_ids && c->fp_len)) return fail(-1, "target prefix: none for this batch");
+  for (int j = 0; forced && mp && j < mp->n; ++j)
+    if (!mp->prefix_ids[j] || !mp->prefix_len[j]) return fail(-1, "target prefix: none for batch %d", j);
   if (lean) {
     PackArgs job;
     if (n_sl && mp) {
@@ -2131,11 +2240,19 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
       f.kv_u4096[l][1] = wv.w.u * (1.0f / 4096.0f);
     }
     f.scores = d_scores;
+    if (forced && !mp) {
+      f.prefix_ids = c->fp_ids;
+      f.prefix_len = c->fp_len;
+    }
     if (mp) {
       f.n_sub = mp->n;
       f.sub_dense = mp->dense ? 1 : 0;
       for (int j = 0; j < mp->n; ++j) f.sub[j] = mp->out[j];
       for (int j = 0; scored && j < mp->n; ++j) f.sub_scores[j] = mp->scores[j];
+      for (int j = 0; forced && j < mp->n; ++j) {
+        f.sub_prefix_ids[j] = mp->prefix_ids[j];
+        f.sub_prefix_len[j] = mp->prefix_len[j];
+      }
       f.out_stride_wp = mp->stride_wp;
       f.out_stride_cs = mp->stride_cs;
       f.out_stride_pb = mp->stride_pb;
@@ -2328,13 +2445,25 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   const EmbedArgs e = embed_args(c);
   if (d_scores) HIPCHK(c->part_sum.reserve(B * (size_t)n_parts * 4));
   float *const part_sum = d_scores ? c->part_sum.as<float>() : nullptr;
+  if (forced && mp) return fail(-1, "target prefix: merged launches decode with the persistent kernels only");
+  ForcedStep fs;  // (forced: the prefix's tokens and their columns, kernels.h)
+  if (forced) {
+    HIPCHK(c->fp_col.reserve(B * 4));
+    HIPCHK(c->fp_part_y.reserve(B * (size_t)n_parts * 4));
+    fs.ids = c->fp_ids;
+    fs.len = c->fp_len;
+    fs.sl = ds.shortlist;
+    fs.N = out.w.N;
+    fs.fcol = c->fp_col.as<int>();
+    fs.part_y = c->fp_part_y.as<float>();
+  }
   const size_t max_steps = steps_hint > 0 ? (size_t)steps_hint : (Tmax > 1 ? Tmax : 1);
   int rc = 0;
   size_t t = 0;
   bool all_done = false;
   for (; t < max_steps && !rc; ++t) {
     hipError_t he = launch_decode_begin_step(e, ds, (int)B, t == 0, 1, c->part_val.as<float>(),
-                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores);
+                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs);
     if (he != hipSuccess) { rc = fail((int)he, "decode_begin_step: %s", hipGetErrorString(he)); break; }
     if (steps_hint <= 0 && t > 0 && (t % 8) == 0) {
       // stop as soon as every sentence has emitted EOS (Model.cc:161)
@@ -2354,15 +2483,17 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     g.part_idx = c->part_idx.as<int>();
     g.n_parts = n_parts;
     g.part_sum = part_sum;
+    g.fcol = fs.fcol;
+    g.part_y = fs.ids ? c->fp_part_y.as<float>() : nullptr;
     {
       ProfScope p(c, SLIMT_HIP_K_LOGITS, gemm_macs((int)B, out.w), gemm_bytes(out.w));
-      he = launch_dgemm(g, d_scores ? EPI_ARGMAX_SC : EPI_ARGMAX, st);
+      he = launch_dgemm(g, fs.ids ? EPI_ARGMAX_FP : d_scores ? EPI_ARGMAX_SC : EPI_ARGMAX, st);
     }
     if (he != hipSuccess) { rc = fail((int)he, "logits gemm: %s", hipGetErrorString(he)); break; }
   }
   if (!rc && !all_done) {
     hipError_t he = launch_decode_begin_step(e, ds, (int)B, 0, 0, c->part_val.as<float>(),
-                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores);
+                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs);
     if (he != hipSuccess) rc = fail((int)he, "final record: %s", hipGetErrorString(he));
   }
   return rc;
@@ -2447,13 +2578,19 @@ extern "C" int slimt_hip_translate_device(slimt_hip_ctx *ctx, const uint32_t *d_
                                           uint32_t *d_out_ids, uint32_t *d_out_len,
                                           float *d_align, int steps_hint) {
   ScoreCall sc(ctx, 1);
+  PrefixCall pc(ctx, 1);
   if (sc.rc) return sc.rc;
+  if (pc.rc) return pc.rc;
   if (!ctx || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len) return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
   if (n_shortlist > (size_t)ctx->model->V) return fail(-1, "shortlist larger than the vocabulary");
   if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
   HIPCHK(hipSetDevice(ctx->model->device));
   if (ctx->sc_call) ctx->sc_dev = ctx->sc_user;  // (device memory, like the other outputs)
+  if (ctx->fp_call) {  // (device memory: read where it is)
+    ctx->fp_ids = ctx->fp_user_ids;
+    ctx->fp_len = ctx->fp_user_len;
+  }
   return translate_device(ctx, d_src_ids, d_lengths, d_shortlist, B, S, n_shortlist, limit_factor,
                           eos_id, d_out_ids, d_out_len, d_align, steps_hint);
 }
@@ -2495,6 +2632,10 @@ int translate_host(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *
                           (fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S) ||
                            long_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S));
   hclk.lap(0);
+  if (ctx->fp_call) {  // (a forced call: the caller's host prefix, checked and staged in device memory)
+    const size_t Bs[1] = {B}, Ts[1] = {Tmax};
+    RCCHK(prefix_stage(ctx, 1, &ctx->fp_user_ids, &ctx->fp_user_len, Bs, Ts, &ctx->fp_ids, &ctx->fp_len));
+  }
   float *const scores = ctx->sc_call ? ctx->sc_user : nullptr;  // (a scored call: the caller's [B][Tmax] host array)
   if (!wait && persistent) {
     void *v_ids = host_device_view(src_ids), *v_len = host_device_view(lengths), *v_out = host_device_view(out_ids),
@@ -2544,7 +2685,9 @@ extern "C" int slimt_hip_translate(slimt_hip_ctx *ctx, const uint32_t *src_ids,
                                    float limit_factor, uint32_t eos_id, uint32_t *out_ids,
                                    uint32_t *out_len, float *align) {
   ScoreCall sc(ctx, 1);
+  PrefixCall pc(ctx, 1);
   if (sc.rc) return sc.rc;
+  if (pc.rc) return pc.rc;
   return translate_host(ctx, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, true);
 }
@@ -2555,7 +2698,9 @@ extern "C" int slimt_hip_translate_async(slimt_hip_ctx *ctx, const uint32_t *src
                                          float limit_factor, uint32_t eos_id, uint32_t *out_ids,
                                          uint32_t *out_len, float *align) {
   ScoreCall sc(ctx, 1);
+  PrefixCall pc(ctx, 1);
   if (sc.rc) return sc.rc;
+  if (pc.rc) return pc.rc;
   return translate_host(ctx, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, false);
 }
@@ -2658,7 +2803,9 @@ extern "C" size_t slimt_hip_translate_many_rows(const size_t *B, size_t n_batche
 extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_hip_batch *batches, size_t n_batches, size_t S,
                                                float limit_factor, uint32_t eos_id, int steps_hint) {
   ScoreCall sc(ctx, n_batches);
+  PrefixCall pc(ctx, n_batches);
   if (sc.rc) return sc.rc;
+  if (pc.rc) return pc.rc;
   if (!ctx || !batches || n_batches == 0) return fail(-1, "null argument");
   HIPCHK(hipSetDevice(ctx->model->device));
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
@@ -2670,6 +2817,10 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
   if (mergeable)
     RCCHK(build_merge_plan(ctx, batches, n_batches, S, Tmax, limit_factor, steps_hint, nullptr, mp, rows, merge_tile(ctx, n_cols)));
   for (size_t j = 0; mergeable && ctx->sc_call && j < n_batches; ++j) mp.scores[j] = sc.dst[j];
+  for (size_t j = 0; mergeable && ctx->fp_call && j < n_batches; ++j) {
+    mp.prefix_ids[j] = pc.ids[j];
+    mp.prefix_len[j] = pc.len[j];
+  }
   if (mergeable && rows <= ctx->max_B && rows * S <= ctx->max_M && S <= ctx->max_S && merge_supported(ctx, rows, S))
     return translate_device(ctx, batches[0].src_ids, batches[0].lengths, batches[0].shortlist, rows, S, (size_t)mp.max_N,
                             limit_factor, eos_id, batches[0].out_ids, batches[0].out_len, batches[0].align, steps_hint, nullptr,
@@ -2677,6 +2828,10 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
   for (size_t j = 0; j < n_batches; ++j) {  // batch by batch, in order, on the same stream
     const slimt_hip_batch &b = batches[j];
     if (ctx->sc_call) ctx->sc_user = sc.dst[j];
+    if (ctx->fp_call) {
+      ctx->fp_user_ids = pc.ids[j];
+      ctx->fp_user_len = pc.len[j];
+    }
     RCCHK(slimt_hip_translate_device(ctx, b.src_ids, b.lengths, b.B, b.S ? b.S : S, b.shortlist, b.n_shortlist, limit_factor,
                                      eos_id, b.out_ids, b.out_len, b.align, steps_hint));
   }
@@ -2686,7 +2841,9 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
 extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hip_batch *batches, size_t n_batches, size_t S,
                                               float limit_factor, uint32_t eos_id) {
   ScoreCall sc(ctx, n_batches);
+  PrefixCall pc(ctx, n_batches);
   if (sc.rc) return sc.rc;
+  if (pc.rc) return pc.rc;
   if (!ctx || !batches || n_batches == 0) return fail(-1, "null argument");
   const slimt_hip_model *m = ctx->model;
   HIPCHK(hipSetDevice(m->device));
@@ -2722,6 +2879,10 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
     for (size_t j = 0; j < n_batches; ++j) {
       const slimt_hip_batch &b = batches[j];
       if (ctx->sc_call) ctx->sc_user = sc.dst[j];
+      if (ctx->fp_call) {
+        ctx->fp_user_ids = pc.ids[j];
+        ctx->fp_user_len = pc.len[j];
+      }
       RCCHK(translate_host(ctx, b.src_ids, b.lengths, b.B, b.S ? b.S : S, b.shortlist, b.n_shortlist, limit_factor, eos_id,
                            b.out_ids, b.out_len, b.align, false));
     }
@@ -2748,6 +2909,7 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   MergePlan mp;
   RCCHK(build_merge_plan(ctx, dev, n_batches, S, Tmax, limit_factor, 0, any_align ? ctx->align.as<float>() : nullptr, mp, rows));
   for (size_t j = 0; ctx->sc_call && j < n_batches; ++j) mp.scores[j] = dev_sc[j];
+  if (ctx->fp_call) RCCHK(prefix_stage_batches(ctx, pc, batches, n_batches, S, limit_factor, mp.prefix_ids, mp.prefix_len));
   return translate_device(ctx, dev[0].src_ids, dev[0].lengths, dev[0].shortlist, rows, S, (size_t)mp.max_N, limit_factor, eos_id,
                           dev[0].out_ids, dev[0].out_len, any_align ? ctx->align.as<float>() : nullptr, (int)Tmax, nullptr,
                           any_align ? dev[0].align : nullptr, 0, nullptr, &mp);
@@ -3145,7 +3307,9 @@ extern "C" int slimt_hip_translate_device_generated(slimt_hip_ctx *ctx, slimt_hi
                                                     uint32_t *d_out_ids, uint32_t *d_out_len,
                                                     float *d_align, int steps_hint) {
   ScoreCall sc(ctx, 1);
+  PrefixCall pc(ctx, 1);
   if (sc.rc) return sc.rc;
+  if (pc.rc) return pc.rc;
   if (!ctx || !sl || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len)
     return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
@@ -3155,6 +3319,10 @@ extern "C" int slimt_hip_translate_device_generated(slimt_hip_ctx *ctx, slimt_hi
     return fail(-1, "shortlist target vocabulary %zu != model vocabulary %d", sl->target_vocab, m->V);
   HIPCHK(hipSetDevice(m->device));
   if (ctx->sc_call) ctx->sc_dev = ctx->sc_user;  // (device memory, like the other outputs)
+  if (ctx->fp_call) {  // (device memory: read where it is)
+    ctx->fp_ids = ctx->fp_user_ids;
+    ctx->fp_len = ctx->fp_user_len;
+  }
   return translate_generated(ctx, sl, d_src_ids, d_lengths, B, S, limit_factor, eos_id, d_out_ids, d_out_len,
                              d_align, steps_hint, nullptr);
 }
@@ -3183,6 +3351,10 @@ int translate_host_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
   const bool persistent = fused_decoder_allowed(ctx) && fused_decode_supported(m->D, m->F, m->H, m->Ld) &&
                           (fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S) ||
                            long_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S));
+  if (ctx->fp_call) {  // (translate_host)
+    const size_t Bs[1] = {B}, Ts[1] = {Tmax};
+    RCCHK(prefix_stage(ctx, 1, &ctx->fp_user_ids, &ctx->fp_user_len, Bs, Ts, &ctx->fp_ids, &ctx->fp_len));
+  }
   float *const scores = ctx->sc_call ? ctx->sc_user : nullptr;  // (translate_host)
   if (!wait && persistent) {  // pinned buffers: the kernels read and write host memory themselves (translate_host)
     void *v_ids = host_device_view(src_ids), *v_len = host_device_view(lengths), *v_out = host_device_view(out_ids),
@@ -3224,7 +3396,9 @@ namespace {
 int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const slimt_hip_batch *dev, size_t n, size_t S,
                              float limit_factor, uint32_t eos_id, int steps_hint, bool stage_align,
                              const slimt_hip_batch *host = nullptr, float *const *sc_dev = nullptr,
-                             float *const *sc_host = nullptr) {
+                             float *const *sc_host = nullptr, const uint32_t *const *fp_dev_ids = nullptr,
+                             const uint32_t *const *fp_dev_len = nullptr, const PrefixCall *fp_host = nullptr) {
+  // fp_dev_* / fp_host (a forced call): each batch's prefix in device memory and, with `host`, as the caller gave it
   // sc_dev / sc_host (a scored call): each batch's score destination as the kernels write it (device memory, or the device
   // view of a pinned array) and, with `host`, as the caller gave it
   // host (the asynchronous entry point): the same batches with the caller's HOST pointers -- what the batch-by-batch
@@ -3249,6 +3423,10 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
     for (size_t j = 0; j < n; ++j) {
       const slimt_hip_batch &b = host[j];
       if (ctx->sc_call) ctx->sc_user = sc_host[j];
+      if (ctx->fp_call) {
+        ctx->fp_user_ids = fp_host->ids[j];
+        ctx->fp_user_len = fp_host->len[j];
+      }
       RCCHK(translate_host_generated(ctx, sl, b.src_ids, b.lengths, b.B, b.S ? b.S : S, limit_factor, eos_id, b.out_ids, b.out_len,
                                      b.align, false));
     }
@@ -3265,6 +3443,10 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
       }
       RCCHK(check_batch(ctx, b.B, Sj));
       if (ctx->sc_call) ctx->sc_dev = sc_dev[j];
+      if (ctx->fp_call) {
+        ctx->fp_ids = fp_dev_ids[j];
+        ctx->fp_len = fp_dev_len[j];
+      }
       RCCHK(translate_generated(ctx, sl, b.src_ids, b.lengths, b.B, Sj, limit_factor, eos_id, b.out_ids, b.out_len,
                                 staging ? staging : b.align, steps_hint > 0 ? std::min(steps_hint, (int)Tj) : (stage_align ? (int)Tj : 0),
                                 staging ? b.align : nullptr));
@@ -3285,6 +3467,10 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
   MergePlan mp;
   RCCHK(build_merge_plan(ctx, plan, n, S, Tmax, limit_factor, steps_hint, any_align && stage_align ? ctx->align.as<float>() : nullptr, mp, rows, tile));
   for (size_t j = 0; ctx->sc_call && j < n; ++j) mp.scores[j] = sc_dev[j];
+  for (size_t j = 0; ctx->fp_call && j < n; ++j) {
+    mp.prefix_ids[j] = fp_dev_ids[j];
+    mp.prefix_len[j] = fp_dev_len[j];
+  }
   ShortlistArgs a;
   shortlist_args(sl, plan[0].src_ids, plan[0].lengths, plan[0].B, S, ctx->shortlist.as<uint32_t>(), ctx->n_sl_dev.as<uint32_t>(), a);
   void *hint_dev = nullptr;
@@ -3309,7 +3495,9 @@ extern "C" int slimt_hip_translate_many_device_generated(slimt_hip_ctx *ctx, sli
                                                          size_t n_batches, size_t S, float limit_factor, uint32_t eos_id,
                                                          int steps_hint) {
   ScoreCall sc(ctx, n_batches);
+  PrefixCall pc(ctx, n_batches);
   if (sc.rc) return sc.rc;
+  if (pc.rc) return pc.rc;
   if (!ctx || !sl || !batches || n_batches == 0) return fail(-1, "null argument");
   RCCHK(check_generator(ctx, sl));
   for (size_t j = 0; j < n_batches; ++j) {
@@ -3319,13 +3507,16 @@ extern "C" int slimt_hip_translate_many_device_generated(slimt_hip_ctx *ctx, sli
   }
   HIPCHK(hipSetDevice(ctx->model->device));
   return translate_many_generated(ctx, sl, batches, n_batches, S, limit_factor, eos_id, steps_hint, false, nullptr,
-                                  ctx->sc_call ? sc.dst.data() : nullptr);
+                                  ctx->sc_call ? sc.dst.data() : nullptr, nullptr, ctx->fp_call ? pc.ids.data() : nullptr,
+                                  ctx->fp_call ? pc.len.data() : nullptr);
 }
 
 extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const slimt_hip_batch *batches,
                                                         size_t n_batches, size_t S, float limit_factor, uint32_t eos_id) {
   ScoreCall sc(ctx, n_batches);
+  PrefixCall pc(ctx, n_batches);
   if (sc.rc) return sc.rc;
+  if (pc.rc) return pc.rc;
   if (!ctx || !sl || !batches || n_batches == 0) return fail(-1, "null argument");
   RCCHK(check_generator(ctx, sl));
   const slimt_hip_model *m = ctx->model;
@@ -3353,12 +3544,19 @@ extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slim
     if (!dev[j].src_ids || !dev[j].lengths || !dev[j].out_ids || !dev[j].out_len || (b.align && !dev[j].align)) pinned = false;
     if (ctx->sc_call && !(dev_sc[j] = static_cast<float *>(host_device_view(sc.dst[j])))) pinned = false;
   }
+  const uint32_t *fp_ids[kMaxMerge] = {}, *fp_len[kMaxMerge] = {};  // (forced: the staged prefixes)
+  if (pinned && ctx->fp_call) RCCHK(prefix_stage_batches(ctx, pc, batches, n_batches, S, limit_factor, fp_ids, fp_len));
   if (pinned)
     return translate_many_generated(ctx, sl, dev, n_batches, S, limit_factor, eos_id, 0, true, batches,
-                                    ctx->sc_call ? dev_sc : nullptr, ctx->sc_call ? sc.dst.data() : nullptr);
+                                    ctx->sc_call ? dev_sc : nullptr, ctx->sc_call ? sc.dst.data() : nullptr,
+                                    fp_ids, fp_len, &pc);
   for (size_t j = 0; j < n_batches; ++j) {  // pageable arrays, or too many batches: one by one through the copying path
     const slimt_hip_batch &b = batches[j];
     if (ctx->sc_call) ctx->sc_user = sc.dst[j];
+    if (ctx->fp_call) {
+      ctx->fp_user_ids = pc.ids[j];
+      ctx->fp_user_len = pc.len[j];
+    }
     RCCHK(translate_host_generated(ctx, sl, b.src_ids, b.lengths, b.B, b.S ? b.S : S, limit_factor, eos_id, b.out_ids, b.out_len,
                                    b.align, false));
   }
@@ -3369,7 +3567,9 @@ extern "C" int slimt_hip_translate_generated(slimt_hip_ctx *ctx, slimt_hip_short
                                              const uint32_t *lengths, size_t B, size_t S, float limit_factor,
                                              uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align) {
   ScoreCall sc(ctx, 1);
+  PrefixCall pc(ctx, 1);
   if (sc.rc) return sc.rc;
+  if (pc.rc) return pc.rc;
   return translate_host_generated(ctx, sl, src_ids, lengths, B, S, limit_factor, eos_id, out_ids, out_len, align, true);
 }
 
@@ -3378,6 +3578,8 @@ extern "C" int slimt_hip_translate_async_generated(slimt_hip_ctx *ctx, slimt_hip
                                                    size_t S, float limit_factor, uint32_t eos_id,
                                                    uint32_t *out_ids, uint32_t *out_len, float *align) {
   ScoreCall sc(ctx, 1);
+  PrefixCall pc(ctx, 1);
   if (sc.rc) return sc.rc;
+  if (pc.rc) return pc.rc;
   return translate_host_generated(ctx, sl, src_ids, lengths, B, S, limit_factor, eos_id, out_ids, out_len, align, false);
 }

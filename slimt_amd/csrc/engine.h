@@ -196,6 +196,17 @@ struct slimt_hip_ctx {
   float *sc_user = nullptr;  // the current batch's destination as the caller gave it (host or device memory)
   float *sc_dev = nullptr;   // ... the address the kernels write: sc_user, its pinned view, or sc_stage
   slimt_hip::DevBuf part_sum, sc_stage;  // the step-wise path's partial sums; device staging of a host call's scores
+  // target prefixes (include/slimt_hip.h, slimt_hip_ctx_set_target_prefix): armed for the NEXT translate call, like the scores
+  bool fp_armed = false;
+  std::vector<const uint32_t *> fp_next_ids, fp_next_len;
+  bool fp_call = false;                 // the call in progress is forced (engine.cpp, PrefixCall)
+  const uint32_t *fp_user_ids = nullptr;  // the current batch's prefix as the caller gave it (host or device memory)
+  const uint32_t *fp_user_len = nullptr;
+  const uint32_t *fp_ids = nullptr;     // the current batch's prefix as the kernels read it (device memory)
+  const uint32_t *fp_len = nullptr;
+  slimt_hip::DevBuf fp_stage;           // device staging of host prefixes ([B][Tmax] ids, then [B] lengths, per batch)
+  slimt_hip::DevBuf fp_scratch;         // score destination of forced calls without scores
+  slimt_hip::DevBuf fp_col, fp_part_y;  // the step-wise path's forced columns and captured logits
   slimt_hip::DevBuf prev, out_ids, out_len, finished, n_finished, align;
   slimt_hip::DevBuf shortlist;
   slimt_hip::DevBuf sl_scratch;  // bitmaps of slimt_hip_shortlist_generate_device (kept zeroed)

@@ -79,6 +79,7 @@ enum GemmEpilogue {
   EPI_ARGMAX = 3,  // per-row first-max over this block's columns -> partials
   EPI_ACC = 4,     // raw accS                               -> int32 [M][N]
   EPI_ARGMAX_SC = 5,  // EPI_ARGMAX + each partial's sum of exponentials (DGemmArgs::part_sum; dgemm only)
+  EPI_ARGMAX_FP = 6,  // EPI_ARGMAX_SC + each partial's logit of the row's forced column (DGemmArgs::part_y; dgemm only)
 };
 
 struct GemmArgs {
@@ -171,10 +172,22 @@ struct DecodeState {
 // (Transformer.cc:133-160). with_embed == 0: sample/record only (last step).
 // part_sum / scores (both or neither): the partials' sums of exponentials (EPI_ARGMAX_SC) and the [B][Tmax]
 // destination of each recorded token's log-probability (scores.h), written beside out_ids
+// The forced steps of the step-wise path (slimt_hip_ctx_set_target_prefix): with ids set, a sentence whose recorded
+// count n is below len[b] (<= Tmax) records ids[b][n] instead of the arg-max, scored from part_y (EPI_ARGMAX_FP), and
+// fcol[b] gets the output-layer column of the token forced at the sentence's next step (-1: none) for that step's
+// logits gemm. Forced steps need the scores (part_sum / scores). sl / N: the output layer's shortlist and columns.
+struct ForcedStep {
+  const uint32_t *ids = nullptr;  // [B][Tmax], nullptr: nothing forced
+  const uint32_t *len = nullptr;  // [B]
+  const uint32_t *sl = nullptr;
+  int N = 0;
+  int *fcol = nullptr;            // [B]
+  const float *part_y = nullptr;  // [B][n_parts]
+};
 hipError_t launch_decode_begin_step(const EmbedArgs &e, const DecodeState &s, int B, int first,
                                     int with_embed, const float *part_val, const int *part_idx,
                                     int n_parts, float *x, hipStream_t st, const float *part_sum = nullptr,
-                                    float *scores = nullptr);
+                                    float *scores = nullptr, const ForcedStep *forced = nullptr);
 // set prev tokens explicitly (step-wise parity API) and embed
 hipError_t launch_embed_decoder(const EmbedArgs &e, const uint32_t *prev, int B, int first,
                                 float *x, hipStream_t st);
@@ -225,6 +238,10 @@ struct DGemmArgs {
   float eps = 1e-6f;
   // EPI_ARGMAX_SC: beside each partial's maximum, the sum of its columns' exp(logit - maximum) (scores.h)
   float *part_sum = nullptr;
+  // EPI_ARGMAX_FP: fcol[row] the forced column of each row (-1: none), part_y[row][part] its logit where this
+  // partial holds it, else -inf
+  const int *fcol = nullptr;
+  float *part_y = nullptr;
 };
 int dgemm_col_blocks(int K, int N, int B);
 hipError_t launch_dgemm(const DGemmArgs &a, int epilogue, hipStream_t st);
@@ -433,6 +450,14 @@ struct FusedDecodeArgs {
   // out_ids and written where and when it is; merged launches: sub-batch j's in sub_scores[j] (MergeOut keeps its layout)
   float *scores = nullptr;
   float *sub_scores[kMaxMerge] = {};
+  // the forced kernels (decode_fused_kernel<..., SC = true, FP = true>; slimt_hip_ctx_set_target_prefix): sentence b's
+  // target prefix, prefix_ids [B][Tmax] (the row stride of out_ids) and its length prefix_len [B] (clamped to Tmax);
+  // merged launches: sub-batch j's in sub_prefix_ids[j] / sub_prefix_len[j], rows sub[j].Tmax apart. A forced launch
+  // always scores (the engine points scores at a scratch when the caller did not ask for them).
+  const uint32_t *prefix_ids = nullptr;
+  const uint32_t *prefix_len = nullptr;
+  const uint32_t *sub_prefix_ids[kMaxMerge] = {};
+  const uint32_t *sub_prefix_len[kMaxMerge] = {};
 };
 // hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), but only when
 // `bytes` exceeds what was already set for this kernel on the current device: the call takes

@@ -590,14 +590,24 @@ hipError_t launch_embed_encoder(const EmbedArgs &e, const uint32_t *ids, int B, 
 // (Transformer.cc:160); step 0 embeds zeros (Transformer.cc:138-144).
 // SC: the scored twin -- the partials' sums of exponentials merge with the same order as the arg-max (scores.h) and
 // each recorded token's log-probability goes to scores beside out_ids (the trailing arguments are not read otherwise)
-template <bool SC>
+// FP: the forced twin (kernels.h, ForcedStep; SC as well): a step below the sentence's prefix length records the
+// prefix's token, scored from the maximum of the partials' captured logits (scores.h, forced_score), and the block
+// resolves the token forced at the sentence's next step to its output-layer column for that step's logits gemm.
+template <bool SC, bool FP = false>
 __global__ __launch_bounds__(64) void decode_begin_step_kernel(EmbedArgs e, DecodeState s,
                                                                int first, int with_embed,
                                                                const float *part_val,
                                                                const int *part_idx, int n_parts,
-                                                               float *x, const float *part_sum, float *scores) {
+                                                               float *x, const float *part_sum, float *scores,
+                                                               ForcedStep f) {
+  static_assert(!FP || SC, "forced steps are scored");
   const int b = blockIdx.x;
   __shared__ uint32_t tok_s;
+  [[maybe_unused]] __shared__ uint32_t next_s;  // FP: the token forced at the next step, 0xffffffff: none
+  [[maybe_unused]] const uint32_t plen = FP ? (f.len[b] < (uint32_t)s.Tmax ? f.len[b] : (uint32_t)s.Tmax) : 0u;
+  if constexpr (FP) {
+    if (first && threadIdx.x == 0) next_s = plen > 0 ? f.ids[(size_t)b * s.Tmax] : 0xffffffffu;
+  }
   if (!first && threadIdx.x == 0) {
     // finish the argmax: partials are in ascending column order
     float bv = part_val[(size_t)b * n_parts];
@@ -615,11 +625,22 @@ __global__ __launch_bounds__(64) void decode_begin_step_kernel(EmbedArgs e, Deco
     const bool none = bi == 0x7fffffff || (s.pb0 && (*s.pb0 != *s.pb0 || s.u_out != s.u_out));
     if (bi == 0x7fffffff) bi = 0;  // every logit NaN or -inf: class 0 (Transformer.cc:287-298), never out of range
     if (s.pb0 && (*s.pb0 != *s.pb0 || s.u_out != s.u_out)) bi = 0;  // logit[0] is NaN: the reference's scan never leaves class 0
-    const uint32_t tok = s.shortlist ? s.shortlist[bi] : (uint32_t)bi;
+    [[maybe_unused]] bool forced = false;
+    uint32_t tok = s.shortlist ? s.shortlist[bi] : (uint32_t)bi;
+    if constexpr (FP) {
+      if (!s.finished[b] && s.out_len[b] < plen) {
+        forced = true;
+        tok = f.ids[(size_t)b * s.Tmax + s.out_len[b]];
+      }
+    }
     s.prev[b] = tok;
     if (!s.finished[b]) {  // record(), Model.cc:127-137
       const uint32_t n = s.out_len[b];
-      if constexpr (SC) {
+      if constexpr (FP) {
+        float y = -__builtin_inff();  // the forced column's logit: in at most one partial
+        for (int p = 0; p < n_parts; ++p) y = fmaxf(y, f.part_y[(size_t)b * n_parts + p]);
+        if ((int)n < s.Tmax) scores[(size_t)b * s.Tmax + n] = forced ? forced_score(sum, y - bv, none) : lse_score(sum, none);
+      } else if constexpr (SC) {
         if ((int)n < s.Tmax) scores[(size_t)b * s.Tmax + n] = lse_score(sum, none);
       }
       if ((int)n < s.Tmax) s.out_ids[(size_t)b * s.Tmax + n] = tok;
@@ -630,8 +651,13 @@ __global__ __launch_bounds__(64) void decode_begin_step_kernel(EmbedArgs e, Deco
       }
     }
     tok_s = tok;
+    if constexpr (FP) next_s = !s.finished[b] && s.out_len[b] < plen ? f.ids[(size_t)b * s.Tmax + s.out_len[b]] : 0xffffffffu;
   }
   __syncthreads();
+  if constexpr (FP) {
+    const int col = forced_column(f.sl, f.N, next_s, threadIdx.x);
+    if (threadIdx.x == 0) f.fcol[b] = col;
+  }
   if (!with_embed) return;
   if (first) {
     for (int d = threadIdx.x; d < e.D; d += 64) {
@@ -647,14 +673,19 @@ __global__ __launch_bounds__(64) void decode_begin_step_kernel(EmbedArgs e, Deco
 hipError_t launch_decode_begin_step(const EmbedArgs &e, const DecodeState &s, int B, int first,
                                     int with_embed, const float *part_val, const int *part_idx,
                                     int n_parts, float *x, hipStream_t st, const float *part_sum,
-                                    float *scores) {
+                                    float *scores, const ForcedStep *forced) {
   if ((part_sum != nullptr) != (scores != nullptr)) return hipErrorInvalidValue;
-  if (scores)
+  const ForcedStep fs = forced ? *forced : ForcedStep{};
+  if (fs.ids && (!scores || !fs.len || !fs.fcol || !fs.part_y)) return hipErrorInvalidValue;
+  if (fs.ids)
+    hipLaunchKernelGGL((decode_begin_step_kernel<true, true>), dim3(B), dim3(64), 0, st, e, s, first, with_embed,
+                       part_val, part_idx, n_parts, x, part_sum, scores, fs);
+  else if (scores)
     hipLaunchKernelGGL(decode_begin_step_kernel<true>, dim3(B), dim3(64), 0, st, e, s, first, with_embed,
-                       part_val, part_idx, n_parts, x, part_sum, scores);
+                       part_val, part_idx, n_parts, x, part_sum, scores, fs);
   else
     hipLaunchKernelGGL(decode_begin_step_kernel<false>, dim3(B), dim3(64), 0, st, e, s, first, with_embed,
-                       part_val, part_idx, n_parts, x, part_sum, scores);
+                       part_val, part_idx, n_parts, x, part_sum, scores, fs);
   return hipGetLastError();
 }
 

@@ -56,4 +56,13 @@ SLIMT_SC_HD float lse_score(float s, bool none) {
   return none ? __builtin_nanf("") : -logf(s);
 }
 
+// A forced step (slimt_hip_ctx_set_target_prefix): the recorded token y is the prefix's, not the arg-max. With the row's
+// maximum M and final sum s as above, its log-softmax is l[y] - M - log(s); d = l[y] - M. Written -(log(s) - d) so
+// that d == 0 (the forced token IS a maximum) gives lse_score's bits, -0 at s == 1 included. A token outside the
+// output layer is captured as l[y] = -inf: d = -inf and the score -inf (probability 0 under the shortlisted softmax).
+// none: as for lse_score -- NaN, whatever was forced; a NaN logit elsewhere makes s NaN and the score with it.
+SLIMT_SC_HD float forced_score(float s, float d, bool none) {
+  return none ? __builtin_nanf("") : -(logf(s) - d);
+}
+
 }  // namespace slimt_hip

@@ -192,6 +192,12 @@ void Worker::arm_scores(float *const *scores, size_t n) {
   if (slimt_hip_ctx_set_scores(ctx_, scores, n)) raise("slimt_hip_ctx_set_scores");
 }
 
+#pragma weak slimt_hip_ctx_set_target_prefix
+void Worker::arm_prefix(const uint32_t *const *ids, const uint32_t *const *len, size_t n) {
+  if (!slimt_hip_ctx_set_target_prefix) throw std::runtime_error("this engine has no target prefixes");
+  if (slimt_hip_ctx_set_target_prefix(ctx_, ids, len, n)) raise("slimt_hip_ctx_set_target_prefix");
+}
+
 void Worker::wait() {
   if (slimt_hip_ctx_synchronize(ctx_)) raise("slimt_hip_ctx_synchronize");
 }

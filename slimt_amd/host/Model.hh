@@ -165,6 +165,9 @@ class Worker {
   // the next forward_*async call also writes each token's log-probability: scores[j] = [B_j][T_j] (pinned, like the
   // outputs) of batch j (slimt_hip_ctx_set_scores)
   void arm_scores(float *const *scores, size_t n);
+  // ... forces target prefixes: ids[j] = [B_j][T_j], len[j] = [B_j] of batch j, in pinned memory that the kernels read in
+  // place (slimt_hip_ctx_set_target_prefix)
+  void arm_prefix(const uint32_t *const *ids, const uint32_t *const *len, size_t n);
   void wait();
 
  private:

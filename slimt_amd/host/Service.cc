@@ -13,8 +13,8 @@ namespace slimt {
 
 // ---- Pending -----------------------------------------------------------------
 
-Pending::Pending(std::vector<Words> sentences)
-    : sentences_(std::move(sentences)), results_(sentences_.size()), left_(sentences_.size()) {
+Pending::Pending(std::vector<Words> sentences, std::vector<Words> prefixes)
+    : sentences_(std::move(sentences)), prefixes_(std::move(prefixes)), results_(sentences_.size()), left_(sentences_.size()) {
   if (sentences_.empty()) {
     settled_ = true;
     promise_.set_value({});
@@ -143,6 +143,7 @@ struct Service::Slot {
   std::unique_ptr<Worker> worker;
   Pinned<uint32_t> ids, lengths, out_ids, out_len, shortlist;
   Pinned<float> align, scores;
+  Pinned<uint32_t> prefix_ids, prefix_len;  // forced launches: like out_ids / lengths (read in place by the kernels)
   std::vector<Unit> batch;  // non-empty while a translate is in flight on this slot
   uint64_t serial = 0;
   // `batch` is the concatenation of the launch's batches (one, or several merged: ServiceConfig::merge_batches), each with
@@ -243,14 +244,27 @@ bool Service::set_scores(bool on) {
   return true;
 }
 
-std::future<Histories> Service::translate(std::vector<Words> sentences) {
+std::future<Histories> Service::translate(std::vector<Words> sentences) { return translate(std::move(sentences), {}); }
+
+std::future<Histories> Service::translate(std::vector<Words> sentences, std::vector<Words> prefixes) {
+  if (!prefixes.empty()) {
+    if (prefixes.size() != sentences.size())
+      throw std::invalid_argument(std::to_string(prefixes.size()) + " prefixes for " + std::to_string(sentences.size()) + " sentences");
+    for (size_t i = 0; i < sentences.size(); ++i) {
+      // the row of outputs of the sentence's batch holds at least this many tokens: its padded length is >= its own
+      const size_t limit = std::max<size_t>(1, (size_t)(config_.tgt_length_limit_factor * (float)sentences[i].size()));
+      if (prefixes[i].size() > limit)
+        throw std::invalid_argument("prefix of sentence " + std::to_string(i) + ": " + std::to_string(prefixes[i].size()) +
+                                    " tokens, more than " + std::to_string(limit));
+    }
+  }
   for (const Words &s : sentences) {
     if (s.empty()) throw std::invalid_argument("empty sentence (a sentence holds at least its EOS)");
     if (s.size() > longest_)
       throw std::invalid_argument("sentence of " + std::to_string(s.size()) + " tokens: longer than " +
                                   std::to_string(longest_) + " (wrap it first)");
   }
-  auto pending = std::make_shared<Pending>(std::move(sentences));
+  auto pending = std::make_shared<Pending>(std::move(sentences), std::move(prefixes));
   std::future<Histories> result = pending->future();
   if (pending->size() == 0) return result;
   if (pending->size() >= (1u << 24)) throw std::invalid_argument("request of more than 2^24 sentences");
@@ -381,6 +395,24 @@ void Service::launch(Slot &slot, std::vector<Unit> &batch, slimt_hip_shortlist *
     std::vector<float *> dst(slot.parts.size());
     for (size_t j = 0; j < slot.parts.size(); ++j) dst[j] = scores + slot.parts[j].out_at;
     slot.worker->arm_scores(dst.data(), dst.size());
+  }
+  // forced: a launch holding a sentence of a request with prefixes forces every part (P = 0 for the sentences without one)
+  if (std::any_of(slot.batch.begin(), slot.batch.end(), [](const Unit &u) { return u.owner->has_prefixes(); })) {
+    uint32_t *p_ids = slot.prefix_ids.ensure(n_out), *p_len = slot.prefix_len.ensure(B);
+    std::vector<const uint32_t *> di(slot.parts.size()), dl(slot.parts.size());
+    for (size_t j = 0; j < slot.parts.size(); ++j) {
+      const Slot::Part &p = slot.parts[j];
+      for (size_t b = 0; b < p.B; ++b) {
+        const Unit &u = slot.batch[p.first + b];
+        const Words *w = u.owner->has_prefixes() ? &u.owner->prefix(u.index) : nullptr;
+        const size_t n = w ? std::min(w->size(), p.T) : 0;  // (checked by translate(): n <= T)
+        if (n) std::copy(w->begin(), w->begin() + n, p_ids + p.out_at + b * p.T);
+        p_len[p.first + b] = static_cast<uint32_t>(n);
+      }
+      di[j] = p_ids + p.out_at;
+      dl[j] = p_len + p.first;
+    }
+    slot.worker->arm_prefix(di.data(), dl.data(), di.size());
   }
   if (generator && slot.parts.size() == 1) {  // the batch's own lexical shortlist, generated on the worker's stream (Model.cc:117-120)
     slot.worker->forward_async_generated(generator, ids, lengths, B, p0.S, config_.tgt_length_limit_factor, out_ids,

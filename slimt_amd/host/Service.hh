@@ -40,15 +40,19 @@ namespace slimt {
 // the promise that is fulfilled by whichever worker delivers the last one.
 class Pending {
  public:
-  explicit Pending(std::vector<Words> sentences);
+  explicit Pending(std::vector<Words> sentences, std::vector<Words> prefixes = {});
   size_t size() const { return sentences_.size(); }
   const Words &sentence(size_t i) const { return sentences_[i]; }
+  // sentence i's forced target prefix (empty: none; Service::translate with prefixes)
+  bool has_prefixes() const { return !prefixes_.empty(); }
+  const Words &prefix(size_t i) const { return prefixes_[i]; }
   std::future<Histories> future() { return promise_.get_future(); }
   void deliver(size_t i, History history);   // thread-safe; the last delivery fulfils the promise
   void fail(const std::exception_ptr &error);  // first failure wins; later deliveries are dropped
 
  private:
   std::vector<Words> sentences_;
+  std::vector<Words> prefixes_;  // empty, or one per sentence
   Histories results_;
   std::atomic<size_t> left_;
   std::atomic<bool> settled_{false};
@@ -140,6 +144,10 @@ class Service {
   // Queue one request. Throws std::invalid_argument for an empty sentence or one longer
   // than the service accepts; a failure on a worker arrives through the future.
   std::future<Histories> translate(std::vector<Words> sentences);
+  // ... each sentence forced through its target prefix (include/slimt_hip.h, slimt_hip_ctx_set_target_prefix; an
+  // empty prefix: none). Throws std::invalid_argument for a count that differs from the sentences' or a prefix longer
+  // than max(1, (size_t)(limit factor * the sentence's length)).
+  std::future<Histories> translate(std::vector<Words> sentences, std::vector<Words> prefixes);
   // per-token scores on or off (ServiceConfig::scores): only before the first translate(); false once one has been made
   bool set_scores(bool on);
   // restart the SLIMT_SERVICE_STATS counters (benchmarks: after the warm-up pass)

@@ -10,6 +10,7 @@
 
 #include "Service.hh"
 #include "slimt_hip_service.h"
+#include "slimt_hip_service_prefix.h"
 #include "slimt_hip_service_scores.h"
 
 namespace {
@@ -85,19 +86,25 @@ extern "C" int slimt_hip_service_destroy(slimt_hip_service *service) {
   return 0;
 }
 
-extern "C" int slimt_hip_service_translate(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets,
-                                           size_t n, slimt_hip_result **out) {
-  if (!service || !out || (n && (!tokens || !offsets))) return fail("null argument");
+namespace {
+// slimt_hip_service_translate[_prefixed]: prefix_tokens / prefix_offsets NULL = no prefixes
+int translate(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets, const uint32_t *prefix_tokens,
+              const uint64_t *prefix_offsets, size_t n, slimt_hip_result **out) {
   *out = nullptr;
   try {
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<slimt::Words> sentences(n);
+    std::vector<slimt::Words> sentences(n), prefixes(prefix_offsets ? n : 0);
     for (size_t i = 0; i < n; ++i) {
       if (offsets[i + 1] < offsets[i]) return fail("offsets decrease at sentence %zu", i);
       sentences[i].assign(tokens + offsets[i], tokens + offsets[i + 1]);
+      if (prefix_offsets) {
+        if (prefix_offsets[i + 1] < prefix_offsets[i]) return fail("prefix offsets decrease at sentence %zu", i);
+        if (prefix_offsets[i + 1] > prefix_offsets[i])
+          prefixes[i].assign(prefix_tokens + prefix_offsets[i], prefix_tokens + prefix_offsets[i + 1]);
+      }
     }
     const auto t1 = std::chrono::steady_clock::now();
-    slimt::Histories hs = service->service->translate(std::move(sentences)).get();
+    slimt::Histories hs = service->service->translate(std::move(sentences), std::move(prefixes)).get();
     const auto t2 = std::chrono::steady_clock::now();
     auto r = std::make_unique<slimt_hip_result>();
     r->target_offsets.assign(n + 1, 0);
@@ -137,6 +144,21 @@ extern "C" int slimt_hip_service_translate(slimt_hip_service *service, const uin
   } catch (const std::exception &e) {
     return fail("%s", e.what());
   }
+}
+}  // namespace
+
+extern "C" int slimt_hip_service_translate(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets,
+                                           size_t n, slimt_hip_result **out) {
+  if (!service || !out || (n && (!tokens || !offsets))) return fail("null argument");
+  return translate(service, tokens, offsets, nullptr, nullptr, n, out);
+}
+
+extern "C" int slimt_hip_service_translate_prefixed(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets,
+                                                    const uint32_t *prefix_tokens, const uint64_t *prefix_offsets, size_t n,
+                                                    slimt_hip_result **out) {
+  if (!service || !out || (n && (!tokens || !offsets || !prefix_offsets)) || (n && prefix_offsets[n] > prefix_offsets[0] && !prefix_tokens))
+    return fail("null argument");
+  return translate(service, tokens, offsets, prefix_tokens, prefix_offsets, n, out);
 }
 
 extern "C" int slimt_hip_result_view(const slimt_hip_result *r, size_t *n, const uint32_t **targets,
