@@ -1176,6 +1176,37 @@ extern "C" int slimt_hip_contexts_on_device(int device, int *count) {
   return 0;
 }
 
+// Contexts per hardware queue. The runtime gives a new stream a hardware queue of its own while fewer than
+// GPU_MAX_HW_QUEUES exist, and afterwards the queue that the fewest streams hold -- the null stream counted like any
+// other, although it carries nothing once the model is uploaded, and ties broken the runtime's way. With the default
+// four queues the headline's twenty context streams landed 4 / 5 / 5 / 6 (the null stream's queue four, a tie lost on
+// another six; tools/queue_ledger.py), and kernels that share a queue run one after the other: the step lasted as long
+// as the queue with six, the others ran nothing for 17 % of it. So before a device's first context stream is made,
+// every queue but the null stream's is given one stream that stays idle as well: all queues then start level, and
+// "the fewest streams" spreads the contexts evenly whichever way ties go (20 contexts: 5 / 5 / 5 / 5). Only where
+// sharing is the rule (up to 8 queues: past that a context usually has a queue to itself, and a hardware queue is not
+// free). The streams live as long as the process. SLIMT_IDLE_STREAMS=0: none (A/B).
+static void level_hardware_queues(int device, int queues) {
+  static std::mutex mu;
+  static bool done[kMaxDevices];
+  static std::vector<hipStream_t> idle;  // (never destroyed: a destroyed one would tilt the queues again)
+  static const bool off = std::getenv("SLIMT_IDLE_STREAMS") && std::getenv("SLIMT_IDLE_STREAMS")[0] == '0';
+  if (off || device < 0 || device >= kMaxDevices || queues < 2 || queues > 8) return;
+  std::lock_guard<std::mutex> lock(mu);
+  if (done[device]) return;
+  done[device] = true;
+  if (g_live_ctx[device].load(std::memory_order_relaxed) > 0) return;  // (contexts on streams of the caller's: left alone)
+  (void)hipStreamQuery(nullptr);  // the null stream takes its queue first, if it has none yet
+  for (int q = 1; q < queues; ++q) {
+    hipStream_t s = nullptr;
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
+      (void)hipGetLastError();  // (no harm: the contexts spread as they did before)
+      return;
+    }
+    idle.push_back(s);
+  }
+}
+
 extern "C" int slimt_hip_ctx_create(slimt_hip_model *model, size_t max_batch,
                                     size_t max_source_length, void *stream, slimt_hip_ctx **out) {
   return slimt_hip_ctx_create_budget(model, max_batch, max_source_length,
@@ -1199,6 +1230,7 @@ extern "C" int slimt_hip_ctx_create_budget(slimt_hip_model *model, size_t max_ba
   if (stream) {
     c->stream = reinterpret_cast<hipStream_t>(stream);
   } else {
+    level_hardware_queues(model->device, model->hw_queues);
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
       delete c;
