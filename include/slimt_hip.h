@@ -133,7 +133,14 @@ typedef struct slimt_hip_dims { /* Model::Config (Model.hh:33-51) */
 /* Transformer::Transformer (Transformer.cc:87-94) + load_parameters
  * (:185-225) + the Wemb handling of Io.cc:182-224: uploads and re-tiles the
  * int8 weights for the MFMA B operand, precomputes column sums and prepared
- * biases. Unknown names are ignored, missing ones are an error. */
+ * biases. Unknown names are ignored, missing ones are an error.
+ * Accepted shapes (anything else is refused here, with the offending size in the
+ * message): embedding size 64, 128, 256 or 512; head size (embedding / heads) 16,
+ * 32 or 64, at embedding size 512 only 32 or 64; FFN size a multiple of 64 up to
+ * 2048; any number of encoder / decoder layers, any vocabulary. These are the
+ * shapes the per-stage kernels (decode mode 1, slimt_hip_decode_step) exist for;
+ * the persistent kernels serve a subset of them (slimt_hip_ctx_plan) with the
+ * same results. */
 int slimt_hip_model_create(const slimt_hip_param *params, size_t n_params,
                            const slimt_hip_dims *dims, int device,
                            slimt_hip_model **out);
@@ -171,7 +178,8 @@ int slimt_hip_model_set_xcd_affinity(slimt_hip_model *model, int xcds);
  * sums (the same real numbers as the reference's dequantise-then-attend, other
  * roundings, <= 2.5e-5 apart; every format gives the same floats as every other):
  *   0 (default) = packed integers where the kernels support it (emb 256 / head dim 32 with
- *       sources of up to 128 tokens, emb 512 / head dim 64 up to 32), f32 elsewhere. Packed
+ *       sources of up to 128 tokens, emb 512 / head dim 64 up to 32 tokens and three
+ *       decoder layers), f32 elsewhere. Packed
  *       means, per sentence and decoder layer and decided by the encoder: 16 bits per value
  *       where every accumulator less its column's centre lies in [-2^15, 2^15)
  *       (slimt_hip_model_set_kv_centres; the first batch of >= 1024 rows is cached as f32

@@ -2032,6 +2032,14 @@ bool fused_decode_supported(int D, int F, int H, int Ld) {
   return shape && fused_decode_lds_bytes(D, F, Ld, 16) <= 160 * 1024;
 }
 
+// sources of up to 32 tokens over the packed cache (decode_fused_kernel<..., KV24 = true>): D = 256 / d_head 32, or the
+// D = 512 / F = 2048 / d_head 64 kernel, whose four bias tables per layer no longer fit the 160 KiB with four decoder layers
+bool fused_decode_packed_supported(int D, int F, int H, int Ld) {
+  if (!fused_decode_supported(D, F, H, Ld)) return false;
+  return ((D == 256 && D / H == 32) || (D == 512 && D / H == 64 && F == 2048)) &&
+         fused_decode_lds_bytes(D, F, Ld, 16, true) <= 160 * 1024;
+}
+
 // a kernel of the launcher's choice, scored (SC) or not: nullptr where the scored twin does not exist (32-sentence,
 // 8- and 4-sentence tilings, clusters) -- a scored call there fails instead of losing its scores
 // (FP: the forced twin, likewise; a forced call where it does not exist fails instead of ignoring its prefix)

@@ -1476,7 +1476,7 @@ size_t long16_lds_bytes() {
 
 bool long_encode_supported(int D, int F, int H, int Le, int Ld, int S) {
   if (S < 1 || S > LR || Le < 1 || Le > 6 || Ld < 1 || Ld > 4 || H <= 0 || D % H) return false;
-  return D == 256 && F % 256 == 0 && F <= 4096 && D / H == 32 && long16_lds_bytes() <= 160 * 1024;
+  return D == 256 && F % 256 == 0 && F <= 2048 && D / H == 32 && long16_lds_bytes() <= 160 * 1024;  // (F: model_create's limit)
 }
 
 hipError_t launch_encode_long(const LongEncodeArgs &a, hipStream_t st) {
@@ -1506,8 +1506,11 @@ size_t fused_encode_lds_bytes(int D) {
 
 bool fused_encode_supported(int D, int F, int H, int Le, int Ld, int S) {
   if (S < 1 || S > ER || Le < 1 || Le > 6 || Ld < 1 || Ld > 4) return false;
-  if (H <= 0 || D % H || F % 256) return false;
+  if (H <= 0 || D % H) return false;
   if (wide_encode_supported(D, F, H, Le, Ld, S)) return true;
+  // F: the instantiations launch_encode_fused has (the hidden layer lives in the dead q/k/v buffers, which end at
+  // F = 2048); other multiples of 256 take the per-sentence kernel (long_encode_supported)
+  if (F != 1024 && F != 1536 && F != 2048) return false;
   return D == 256 && D / H == 32 && fused_encode_lds_bytes(D) <= 160 * 1024;
 }
 

@@ -649,12 +649,24 @@ int model_build(slimt_hip_model *m, const slimt_hip_param *params, size_t n,
   m->Le = dims->encoder_layers;
   m->Ld = dims->decoder_layers;
   const int D = m->D, V = m->V;
-  if (D % 64 != 0 || D > 512) return fail(-1, "unsupported embedding size %d", D);
-  if (m->H <= 0 || D % m->H != 0 || D / m->H > 64) return fail(-1, "unsupported head count %d", m->H);
+  // What the per-stage kernels -- the path every model must be able to take (decode mode 1, slimt_hip_decode_step) -- are
+  // instantiated for (the tilings are template arguments: further instantiations would widen the family again):
+  //  D: the encoder's LayerNorm epilogue owns whole rows in 1, 2, 4 or 8 column tiles of 64 (kernels.hip, EPI_RES_LN)
+  if (D != 64 && D != 128 && D != 256 && D != 512)
+    return fail(-1, "unsupported embedding size %d (64, 128, 256 or 512)", D);
+  //  D / H: the decoder's cross-attention exists for 16, 32 and 64, at D = 512 for 32 and 64 (decode_kernels.hip, dqattn_kernel)
+  if (m->H <= 0 || D % m->H != 0) return fail(-1, "unsupported head count %d for embedding size %d", m->H, D);
+  {
+    const int dh = D / m->H;
+    if ((dh != 16 && dh != 32 && dh != 64) || (D == 512 && dh == 16))
+      return fail(-1, "unsupported head count %d: head size %d (16, 32 or 64; 32 or 64 at embedding size 512)", m->H, dh);
+  }
   const slimt_hip_param *w1 = t.get("encoder_l1_ffn_W1");
   if (!w1) return fail(-1, "missing parameter encoder_l1_ffn_W1");
   m->F = w1->cols;
-  if (m->F % 64 != 0 || m->F > 4096) return fail(-1, "unsupported ffn size %d", m->F);
+  //  F: the decoder's FFN2 keeps its 16 int8 input rows in LDS, up to K = 2048 (decode_kernels.hip, launch_dgemm)
+  if (m->F % 64 != 0 || m->F <= 0 || m->F > 2048)
+    return fail(-1, "unsupported ffn size %d (a multiple of 64, at most 2048)", m->F);
   const int F = m->F;
   const size_t VD = (size_t)V * D;
 
@@ -2074,7 +2086,8 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   const bool kv_packed = lean && (m->kv_format == 0 || m->kv_format == 2) &&
                     ((m->D == 256 && m->D / m->H == 32) || (m->D == 512 && m->D / m->H == 64 && m->F == 2048)) &&
                     ((S <= 32 && ((S + 3) & ~(size_t)3) * 3 <= S * 4 &&
-                      fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S)) || kv24_mid || kv24_long);
+                      fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S) &&
+                      fused_decode_packed_supported(m->D, m->F, m->H, m->Ld)) || kv24_mid || kv24_long);
   // The tight form's centres (engine.h, kv_centre): the first batch of enough rows that could take the form is cached as
   // f32 instead, and its column means become the centres (behind the encoder, on this stream).
   bool calibrate = false;

@@ -466,6 +466,9 @@ hipError_t set_dynamic_lds_once(const void *kernel, int bytes);
 int fused_decode_grid(int B, bool tickets, int rows);
 int fused_encode_grid(int B, int S, bool tickets);
 bool fused_decode_supported(int D, int F, int H, int Ld);
+// the packed K/V cache's reader for sources of up to 32 tokens (16 sentences per workgroup or fewer): its per-layer
+// bias tables must fit the LDS beside everything else (D = 512: up to three decoder layers)
+bool fused_decode_packed_supported(int D, int F, int H, int Ld);
 bool fused_decode_mid_supported(int D, int F, int H, int Ld);
 bool fused_decode_tight_supported(int D, int F, int H, int Ld);
 bool fused_decode_tight_rows32_supported(int D, int F, int H, int Ld);

@@ -57,7 +57,11 @@ def test_highway(hip, oracle):
 
 @pytest.mark.parametrize("B,H,Tq,S,dh", [(2, 8, 1, 32, 32), (3, 8, 32, 32, 32), (2, 8, 16, 16, 64),
                                         (1, 8, 1, 128, 32), (2, 8, 70, 70, 8), (2, 8, 1, 5, 16),
-                                        (1, 8, 128, 128, 64)])
+                                        (1, 8, 128, 128, 64)] +
+                         # odd head sizes (the scalar kernel pads its rows to dh + 1 floats) at Tq = S <= 32 -- the other
+                         # side of the MFMA attention's condition (dh 32 / 64 only) --, at Tq = 1 and at S > 64
+                         [(2, 3, tq, s, dh) for dh in (1, 3, 12, 24, 40, 48, 63)
+                          for tq, s in ((min(32, 9 + dh), min(32, 9 + dh)), (1, 29), (70, 70))])
 def test_sdpa(hip, oracle, B, H, Tq, S, dh):
     r = rng(B * 1000 + Tq * 10 + S)
     q = r.normal(0, 1.5, size=(B, H, Tq, dh)).astype(np.float32)

@@ -43,6 +43,10 @@ SHAPES = [
     # many rows: slimt_hip_affine takes the 128-row tiling (gemm_tile.hip): a ragged last row
     # block, K in one / three / four 512-deep chunks, N not a multiple of the 128-column block
     (1100, 512, 512), (1024, 1536, 256), (1300, 2048, 576), (2048, 256, 1536),
+    # K that no model preset has (3, 5, 7, 11, 16 and 64 k-steps of 64), N that is no multiple of 8
+    (19, 192, 40), (70, 320, 517), (5, 448, 7), (33, 704, 1), (130, 1024, 1003), (21, 4096, 72),
+    # the edges of the 128-row tiling's dispatch: M = 1023 / 1024, N = 48 / 64 / 72, K it does not take with M >= 1024
+    (1023, 512, 512), (1024, 512, 48), (1024, 512, 72), (1024, 192, 256), (1024, 320, 256), (1024, 1024, 64),
 ]
 
 
@@ -85,7 +89,7 @@ def test_affine_saturation_and_ties(hip, oracle):
 
 
 @pytest.mark.parametrize("M,K,N,n_idx", [(1, 64, 512, 8), (16, 256, 2048, 256), (64, 256, 32000, 4096),
-                                         (7, 512, 4000, 1000)])
+                                         (7, 512, 4000, 1000), (21, 256, 1003, 200)])
 def test_affine_with_select(hip, oracle, M, K, N, n_idx):
     x, W, bias, aq, bq = make_case(M + n_idx, M, K, N)
     r = rng(n_idx)
@@ -121,6 +125,8 @@ def test_affine_rejects_bad_shapes(hip):
     W = np.zeros((16, 100), dtype=np.int8)
     with pytest.raises(hip.SlimtHipError):
         hip.affine(x, W, None, 1.0, 1.0)  # K % 64 != 0, like intgemm's own constraint
+    with pytest.raises(hip.SlimtHipError, match="4160"):
+        hip.affine(np.zeros((4, 4160), np.float32), np.zeros((16, 4160), np.int8), None, 1.0, 1.0)  # K > 4096
     with pytest.raises(hip.SlimtHipError):
         hip.affine_with_select(np.zeros((4, 64), np.float32), np.zeros((16, 64), np.int8),
                                np.zeros(16, np.float32), 1.0, 1.0, np.array([99], np.uint32))
