@@ -282,6 +282,41 @@ int slimt_hip_ctx_set_scores(slimt_hip_ctx *ctx, float *const *scores, size_t n)
  * other inputs. */
 int slimt_hip_ctx_set_target_prefix(slimt_hip_ctx *ctx, const uint32_t *const *prefix_ids,
                                     const uint32_t *const *prefix_len, size_t n);
+/* Sampled decoding: the key of sentence `index` of a request seeded `seed` (a host
+ * function; what the batching service and the Python frontend use). For a fixed
+ * seed it is a bijection of the index. */
+uint64_t slimt_hip_sampling_key(uint64_t seed, uint64_t index);
+/* Temperature sampling for the NEXT translate call on ctx (any of the
+ * slimt_hip_translate* entry points), which consumes it whether it succeeds or
+ * fails, like the scores and the prefixes; n = 0 arms nothing. temperature must be
+ * finite and > 0, else a negative status. keys[j] is batch j's [B_j] uint64 array of
+ * sentence keys, n = 1 for the single-batch calls and n = n_batches for the _many_
+ * ones (a mismatched n fails that call), in the memory of that call's inputs: host
+ * for the host calls (pinned arrays are read in place by the kernels, pageable ones
+ * are copied asynchronously on the context's stream and must stay valid until the
+ * context is synchronised), device for the _device ones. keys == NULL or
+ * keys[j] == NULL: the key of sentence b of that batch is its row index b.
+ * At step t of sentence b -- t its count of recorded tokens -- the token is the
+ * vocabulary id y_c of the FIRST maximum over the output layer's columns c of
+ *   key_c = fmaf(logit_c, 1.0f / temperature, g(k_b, t, y_c)),
+ * g standard Gumbel noise that is a pure function of the sentence's key, the step
+ * and the vocabulary id (slimt_amd/csrc/sampling.h: the hash, and a logarithm that
+ * gives the same bits on the host): a draw from softmax(logit / temperature) over
+ * the step's output layer (the shortlist, where there is one). The NaN and
+ * start-value rules are the arg-max's, applied to the key. So a sentence's sampled
+ * translation depends on its key and on nothing else: not on its row or its
+ * neighbours in the batch, the decode mode, the entry point, or whether the launch
+ * is merged. EOS, the step limit, alignments and out_len are as for greedy calls.
+ * Sampled calls are scored internally: with slimt_hip_ctx_set_scores the scores are
+ * log softmax(logit / temperature) at the recorded token; without, the engine keeps
+ * them in a scratch of its own. Like scored calls they decode with the 16-sentence
+ * tilings (decode modes 2-6 act as 2), or with the per-stage kernels in mode 1.
+ * With a target prefix (slimt_hip_ctx_set_target_prefix) as well, steps below P_b
+ * are forced and scored at that temperature, and the first sampled step is t = P_b
+ * with the noise of step t. Such calls run the persistent decoder's sampled-and-
+ * forced twin (decode_fused_kernel<..., SC, FP, SM>) or, in mode 1, the per-stage
+ * kernels; the results are the same. */
+int slimt_hip_ctx_set_sampling(slimt_hip_ctx *ctx, float temperature, const uint64_t *const *keys, size_t n);
 /* Which kernels a translate call with source length S would use in the current
  * mode: *encoder_fused / *decoder_fused = 1 for the persistent kernels, 0 for
  * the per-stage ones. */

@@ -39,7 +39,7 @@ SYMBOLS = [
     "slimt_hip_encode_embedded", "slimt_hip_decode_begin_from", "slimt_hip_decode_step_states",
     "slimt_hip_translate_many_rows", "slimt_hip_translate_many_device", "slimt_hip_translate_many_async",
     "slimt_hip_debug_kv_recalibrations", "slimt_hip_translate_many_device_generated", "slimt_hip_translate_many_async_generated",
-    "slimt_hip_ctx_set_scores", "slimt_hip_ctx_set_target_prefix",
+    "slimt_hip_ctx_set_scores", "slimt_hip_ctx_set_target_prefix", "slimt_hip_ctx_set_sampling", "slimt_hip_sampling_key",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -205,6 +205,9 @@ def lib():
     L.slimt_hip_ctx_set_encode_rows.argtypes = [vp, i32]
     L.slimt_hip_ctx_set_scores.argtypes = [vp, vp, sz]
     L.slimt_hip_ctx_set_target_prefix.argtypes = [vp, vp, vp, sz]
+    L.slimt_hip_ctx_set_sampling.argtypes = [vp, f32, vp, sz]
+    L.slimt_hip_sampling_key.argtypes = [C.c_uint64, C.c_uint64]
+    L.slimt_hip_sampling_key.restype = C.c_uint64
     L.slimt_hip_ctx_plan.argtypes = [vp, sz, vp, vp]
     L.slimt_hip_translate.argtypes = [vp, vp, vp, sz, sz, vp, sz, f32, u32, vp, vp, vp]
     L.slimt_hip_translate_async.argtypes = [vp, vp, vp, sz, sz, vp, sz, f32, u32, vp, vp, vp]
@@ -259,6 +262,16 @@ def lib():
             fn.restype = C.c_int
     _lib = L
     return L
+
+
+def sampling_key(seed: int, index: int) -> int:
+    """slimt_hip_sampling_key: the key of sentence `index` of a request seeded `seed`."""
+    return int(lib().slimt_hip_sampling_key(int(seed) & (2 ** 64 - 1), int(index) & (2 ** 64 - 1)))
+
+
+def sampling_keys(seed: int, n: int, first: int = 0) -> np.ndarray:
+    """the keys of sentences first .. first + n - 1 of a request seeded `seed` (uint64 [n])"""
+    return np.array([sampling_key(seed, first + i) for i in range(n)], dtype=np.uint64)
 
 
 def translate_many_rows(sizes) -> int:
@@ -614,6 +627,36 @@ class Context:
         a_len = (C.c_void_p * max(1, n))(*[a or None for a in lens])
         _chk(lib().slimt_hip_ctx_set_target_prefix(self.h, a_ids, a_len, n))
 
+    def set_sampling(self, temperature: float, keys=None):
+        """slimt_hip_ctx_set_sampling: arm temperature sampling for the NEXT translate call. keys: one entry per batch --
+        a numpy uint64 [B_j] array (host calls; kept alive here until synchronize()), an address (int: a device pointer for
+        the device calls) or None (that batch's keys are its row indices); None alone: one batch with row-index keys.
+        The translate wrappers below take `sampling=(temperature, keys)` and do this."""
+        if keys is None:
+            keys = [None]
+        keep, addrs = [], []
+        for k in keys:
+            if isinstance(k, np.ndarray):
+                if k.dtype != np.uint64 or not k.flags.c_contiguous or k.ndim != 1:
+                    raise ValueError("sampling keys: a C-contiguous one-dimensional uint64 array expected")
+                keep.append(k)
+                addrs.append(k.ctypes.data)
+            else:
+                addrs.append(int(k) if k else 0)
+        self._prefix_keep = getattr(self, "_prefix_keep", []) + keep  # (like the prefixes: read until synchronize())
+        arr = (C.c_void_p * max(1, len(addrs)))(*[a or None for a in addrs])
+        _chk(lib().slimt_hip_ctx_set_sampling(self.h, float(temperature), arr, len(addrs)))
+
+    @staticmethod
+    def _sampling_host(sampling, B: int):
+        """(temperature, keys uint64 [B] | None) of a host call's `sampling=` (shape checked)"""
+        T, keys = sampling
+        if keys is not None and not isinstance(keys, int):
+            keys = np.ascontiguousarray(keys, dtype=np.uint64)
+            if keys.shape != (B,):
+                raise ValueError("sampling: keys of shape %s expected" % ((B,),))
+        return float(T), keys
+
     @staticmethod
     def _prefix_host(prefix, B: int, T: int):
         """(ids [B, T], lens [B]) as C-contiguous uint32 arrays (shapes checked)"""
@@ -636,10 +679,13 @@ class Context:
         return bool(e.value), bool(d.value)
 
     def translate(self, ids, lengths, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                  want_align: bool = False, scores: bool = False, prefix=None):
+                  want_align: bool = False, scores: bool = False, prefix=None, sampling=None):
         """Model::forward. Returns out_ids [B,Tmax], out_len [B], align|None (+ scores [B,Tmax] float32 with
         scores=True: the log-probability of each recorded token, include/slimt_hip.h slimt_hip_ctx_set_scores).
-        prefix: (ids [B,Tmax], lens [B]) uint32 -- forced target prefixes (slimt_hip_ctx_set_target_prefix)."""
+        prefix: (ids [B,Tmax], lens [B]) uint32 -- forced target prefixes (slimt_hip_ctx_set_target_prefix).
+        sampling: (temperature, keys uint64 [B] | None) -- temperature sampling under per-sentence keys
+        (slimt_hip_ctx_set_sampling; None: the row indices); the other translate wrappers take it in the same form, the
+        device ones with a device pointer for the keys, the _many_ ones with one entry per batch."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
         B, S = ids.shape
@@ -655,6 +701,9 @@ class Context:
             self.set_scores([sc])
         if pre is not None:
             self.set_target_prefix([pre])
+        if sampling is not None:
+            sm_t, sm_keys = self._sampling_host(sampling, B)
+            self.set_sampling(sm_t, [sm_keys])
         _chk(lib().slimt_hip_translate(self.h, _p(ids), _p(lengths), B, S, _p(sl),
                                        0 if sl is None else sl.size, limit_factor, eos_id,
                                        _p(out_ids), _p(out_len), _p(align)))
@@ -670,7 +719,7 @@ class Context:
                 pin("al").array(np.float32, (B, T, S)) if want_align else None)
 
     def translate_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
-                        scores=None, prefix=None):
+                        scores=None, prefix=None, sampling=None):
         """slimt_hip_translate_async[_generated] on arrays from pinned_buffers() (already filled);
         synchronize() before reading the outputs. `generator`: a ShortlistGenerator -- the batch's
         lexical shortlist is then generated on this context's stream (Model.cc:117-120).
@@ -686,6 +735,9 @@ class Context:
             self.set_scores([scores])
         if pre is not None:
             self.set_target_prefix([pre])
+        if sampling is not None:
+            sm_t, sm_keys = self._sampling_host(sampling, B)
+            self.set_sampling(sm_t, [sm_keys])
         if generator is not None:
             _chk(lib().slimt_hip_translate_async_generated(self.h, generator.h, _p(p_ids), _p(p_len), B, S,
                                                            limit_factor, eos_id, _p(p_out), _p(p_ol), _p(p_al)))
@@ -694,7 +746,7 @@ class Context:
                                              limit_factor, eos_id, _p(p_out), _p(p_ol), _p(p_al)))
 
     def translate_pinned(self, ids, lengths, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                         want_align: bool = False, generator=None, scores: bool = False, prefix=None):
+                         want_align: bool = False, generator=None, scores: bool = False, prefix=None, sampling=None):
         """translate() through this context's pinned staging buffers and slimt_hip_translate_async:
         the persistent kernels then read and write host memory themselves, no copy is queued (host
         pipelines with several contexts: copies of one stream wait behind other streams' kernels).
@@ -705,13 +757,13 @@ class Context:
         bufs[0][...] = ids
         bufs[1][...] = lengths
         sc = self._pinned.setdefault("sc", _Pinned()).array(np.float32, bufs[2].shape) if scores else None
-        self.translate_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix)
+        self.translate_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix, sampling=sampling)
         self.synchronize()
         out = bufs[2].copy(), bufs[3].copy(), (bufs[4].copy() if want_align else None)
         return out + (sc.copy(),) if scores else out
 
     def translate_generated(self, generator, ids, lengths, limit_factor: float = 1.5, eos_id: int = 0,
-                            want_align: bool = False, scores: bool = False, prefix=None):
+                            want_align: bool = False, scores: bool = False, prefix=None, sampling=None):
         """Model::forward with its shortlist step (slimt_hip_translate_generated): host arrays, blocking.
         prefix: as in translate()."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
@@ -727,6 +779,9 @@ class Context:
             self.set_scores([sc])
         if pre is not None:
             self.set_target_prefix([pre])
+        if sampling is not None:
+            sm_t, sm_keys = self._sampling_host(sampling, B)
+            self.set_sampling(sm_t, [sm_keys])
         _chk(lib().slimt_hip_translate_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, limit_factor,
                                                  eos_id, _p(out_ids), _p(out_len), _p(align)))
         self._prefix_keep = []  # (a blocking call: done with its prefix)
@@ -734,7 +789,7 @@ class Context:
 
     def translate_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int,
                          n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int,
-                         d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None):
+                         d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None):
         """Device pointers (ints) in and out; asynchronous when steps_hint > 0. scores: a device pointer to
         [B, Tmax] floats for the tokens' log-probabilities (0 = none). prefix: (d_ids, d_lens) device pointers of a
         forced target prefix ([B, Tmax] and [B] uint32)."""
@@ -746,10 +801,12 @@ class Context:
             self.set_scores([scores])
         if prefix is not None:
             self.set_target_prefix([prefix])
+        if sampling is not None:  # (temperature, device pointer of the [B] uint64 keys or 0 / None)
+            self.set_sampling(sampling[0], [sampling[1]])
         _chk(lib().slimt_hip_translate_device(*args))
 
     def translate_many_device(self, batches, S: int, limit_factor: float, eos_id: int, steps_hint: int = 0, generator=None,
-                              scores=None, prefix=None):
+                              scores=None, prefix=None, sampling=None):
         """slimt_hip_translate_many_device: `batches` = [(d_ids, d_lengths, B, d_shortlist, n_shortlist, d_out_ids,
         d_out_len, d_align[, S_j])] of device pointers (ints; 0 = none) -- ONE encoder and ONE decoder launch for all of them;
         S_j: that batch's own padded length (<= S; default S). scores: one device pointer per batch ([B_j, Tmax_j] floats).
@@ -764,13 +821,15 @@ class Context:
             self.set_scores(list(scores))
         if prefix is not None:
             self.set_target_prefix(list(prefix))
+        if sampling is not None:  # (temperature, one device pointer of keys per batch | None)
+            self.set_sampling(sampling[0], list(sampling[1]) if sampling[1] is not None else [None] * len(batches))
         if generator is not None:
             _chk(lib().slimt_hip_translate_many_device_generated(self.h, generator.h, arr, len(batches), S, limit_factor, eos_id, steps_hint))
             return
         _chk(lib().slimt_hip_translate_many_device(self.h, arr, len(batches), S, limit_factor, eos_id, steps_hint))
 
     def translate_many_async(self, bufs_list, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0, generator=None,
-                             scores=None, prefix=None):
+                             scores=None, prefix=None, sampling=None):
         """slimt_hip_translate_many_async on a list of pinned buffer tuples (ids, lengths, out_ids, out_len, align|None),
         one shortlist (host array) or none for all; synchronize() before reading the outputs.
         scores: one float32 [B_j, Tmax_j] array per batch (pinned: the merged launch writes them in place).
@@ -797,6 +856,11 @@ class Context:
             self.set_scores(list(scores))
         if pre is not None:
             self.set_target_prefix(pre)
+        if sampling is not None:  # (temperature, one uint64 [B_j] host array of keys per batch | None)
+            ks = sampling[1] if sampling[1] is not None else [None] * len(bufs_list)
+            if len(ks) != len(bufs_list):
+                raise ValueError(f"sampling: {len(ks)} key arrays for {len(bufs_list)} batches")
+            self.set_sampling(sampling[0], [self._sampling_host((sampling[0], k), b[2].shape[0])[1] for k, b in zip(ks, bufs_list)])
         if generator is not None:  # every batch's own lexical shortlist, generated inside the encoder launch
             _chk(lib().slimt_hip_translate_many_async_generated(self.h, generator.h, arr, len(bufs_list), S, limit_factor, eos_id))
             return
@@ -804,7 +868,7 @@ class Context:
 
     def translate_device_generated(self, gen: "ShortlistGenerator", d_ids: int, d_lengths: int, B: int,
                                    S: int, limit_factor: float, eos_id: int, d_out_ids: int,
-                                   d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None):
+                                   d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None):
         """Shortlist generation + translate, all on this context's stream. scores, prefix: as in translate_device."""
         vp = C.c_void_p
         args = (self.h, gen.h, vp(d_ids), vp(d_lengths), B, S, limit_factor, eos_id, vp(d_out_ids),
@@ -813,6 +877,8 @@ class Context:
             self.set_scores([scores])
         if prefix is not None:
             self.set_target_prefix([prefix])
+        if sampling is not None:  # (temperature, device pointer of the [B] uint64 keys or 0 / None)
+            self.set_sampling(sampling[0], [sampling[1]])
         _chk(lib().slimt_hip_translate_device_generated(*args))
 
     def encode(self, ids, lengths, want_embed=False, want_layers=False):
@@ -956,6 +1022,8 @@ def host_lib():
     H.slimt_hip_service_set_scores.argtypes = [vp, C.c_int]  # (include/slimt_hip_service_scores.h)
     H.slimt_hip_result_scores.argtypes = [vp, vp]
     H.slimt_hip_service_translate_prefixed.argtypes = [vp, vp, vp, vp, vp, sz, vp]  # (include/slimt_hip_service_prefix.h)
+    H.slimt_hip_service_set_sampling.argtypes = [vp, C.c_float]  # (include/slimt_hip_service_sampling.h)
+    H.slimt_hip_service_translate_sampled.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, sz, vp]
     _host_lib = H
     return H
 
@@ -1035,8 +1103,9 @@ class BatchService:
                  workers_per_device: int = 6, pad_id: int = 0, eos_id: int = 0, alignments: bool = True,
                  lexical_shortlist: bytes = b"", source_vocab: int = 0, target_vocab: int = 0,
                  shared_vocab: bool = False, check: bool = False, shortlist=None, merge_batches: int = 0, merge_words: int = 0,
-                 scores: bool = False):
-        """merge_batches / merge_words: merged launches (0 = the library's defaults: up to 8 consecutive batches of one padded
+                 scores: bool = False, temperature: float = 0.0):
+        """temperature > 0: every request is sampled at that temperature (slimt_hip_service_set_sampling; translate(...,
+        seed=)). merge_batches / merge_words: merged launches (0 = the library's defaults: up to 8 consecutive batches of one padded
         length per launch pair within 8192 words; merge_batches = 1: never). scores: every result carries its target tokens'
         log-probabilities (ServiceResult.scores / token_scores; slimt_hip_service_set_scores)."""
         self._keep = []
@@ -1061,10 +1130,16 @@ class BatchService:
             err = host_lib().slimt_hip_service_last_error().decode()
             self.close()
             raise SlimtHipError(err)
+        self.temperature = float(temperature)
+        if temperature and host_lib().slimt_hip_service_set_sampling(self.h, float(temperature)):
+            err = host_lib().slimt_hip_service_last_error().decode()
+            self.close()
+            raise SlimtHipError(err)
 
-    def translate_flat(self, tokens: np.ndarray, offsets: np.ndarray, prefix_tokens=None, prefix_offsets=None) -> ServiceResult:
+    def translate_flat(self, tokens: np.ndarray, offsets: np.ndarray, prefix_tokens=None, prefix_offsets=None, seed=None) -> ServiceResult:
         """tokens uint32 (flat), offsets uint64 [n + 1]. Blocking; thread-safe. prefix_tokens / prefix_offsets: forced
-        target prefixes in the same form (slimt_hip_service_translate_prefixed; an empty range: not forced)."""
+        target prefixes in the same form (slimt_hip_service_translate_prefixed; an empty range: not forced). seed (a
+        sampling service): sentence i is drawn under sampling_key(seed, i) (slimt_hip_service_translate_sampled)."""
         tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         out = C.c_void_p()
@@ -1073,6 +1148,11 @@ class BatchService:
             prefix_offsets = np.ascontiguousarray(prefix_offsets, dtype=np.uint64)
             if prefix_offsets.size != offsets.size:
                 raise ValueError(f"prefixes: {prefix_offsets.size - 1} for {offsets.size - 1} sentences")
+        if seed is not None:
+            rc = host_lib().slimt_hip_service_translate_sampled(
+                self.h, _p(tokens), _p(offsets), _p(prefix_tokens) if prefix_offsets is not None else None,
+                _p(prefix_offsets) if prefix_offsets is not None else None, int(seed) & (2 ** 64 - 1), offsets.size - 1, C.byref(out))
+        elif prefix_offsets is not None:
             rc = host_lib().slimt_hip_service_translate_prefixed(self.h, _p(tokens), _p(offsets), _p(prefix_tokens),
                                                                 _p(prefix_offsets), offsets.size - 1, C.byref(out))
         else:
@@ -1089,14 +1169,15 @@ class BatchService:
         tokens = np.fromiter(itertools.chain.from_iterable(sentences), dtype=np.uint32, count=int(offsets[-1]))
         return tokens, offsets
 
-    def translate(self, sentences, prefixes=None) -> ServiceResult:
+    def translate(self, sentences, prefixes=None, seed=None) -> ServiceResult:
         """prefixes: one token list per sentence (empty: not forced) -- forced target prefixes; a given translation with
-        its EOS is scored (include/slimt_hip_service_prefix.h)."""
+        its EOS is scored (include/slimt_hip_service_prefix.h). seed: on a sampling service (temperature=), the request's
+        seed (include/slimt_hip_service_sampling.h; None: seed 0)."""
         if prefixes is None:
-            return self.translate_flat(*self._flat(sentences))
+            return self.translate_flat(*self._flat(sentences), seed=seed)
         if len(prefixes) != len(sentences):
             raise ValueError(f"prefixes: {len(prefixes)} for {len(sentences)} sentences")
-        return self.translate_flat(*self._flat(sentences), *self._flat(prefixes))
+        return self.translate_flat(*self._flat(sentences), *self._flat(prefixes), seed=seed)
 
     def close(self):
         if getattr(self, "h", None):

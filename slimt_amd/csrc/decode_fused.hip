@@ -925,12 +925,20 @@ __device__ __forceinline__ void attention_row(AttnRow r, int lane) {
 // token forced at the next step to its output-layer column (device_common.h, forced_column; -1: none) into fcol_s; the
 // output layer's epilogue has the one lane that meets that column store its logit to ycap (no registers held for it
 // through the stream, no reduction), and the owner scores it with the row's maximum and sum (scores.h, forced_score).
+// SM: sampled (slimt_hip_ctx_set_sampling; always scored): the epilogue compares key = fmaf(logit, inv_T, g) with g the
+// Gumbel noise of (sentence key, step, vocabulary id) (sampling.h) instead of the logit, so the first maximum is a draw
+// from softmax(logit / T). The log-sum-exp runs over z = logit * inv_T with a running maximum of its own (mz), the
+// winner's z rides with the key through the reductions (zw), and the score is log softmax(z)[token]. The row's owner
+// hashes (key, step) to two words per row in seed_s at the end of each step (and before the first), where the step is
+// the sentence's count of recorded tokens; the epilogue reads them from LDS for its four rows. With FP, forced steps
+// capture z instead of the logit, so they are scored at the same temperature.
 template <bool MG, int KSD, int KSF, int DH, bool LONG, bool NT, int RT = 1, bool KV24 = false, int MID = 0, int SPW = 16, int CL = 1,
-          int KVI = 20, bool SC = false, bool FP = false>
+          int KVI = 20, bool SC = false, bool FP = false, bool SM = false>
 __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
   static_assert(!MG || (RT == 1 && CL == 1 && MID <= 1), "merged launches: the 16-row tilings, sentences of up to 64 tokens");
   static_assert(!SC || (RT == 1 && CL == 1 && SPW == 16), "scored launches: the 16-sentence tilings without clusters");
   static_assert(!FP || SC, "forced launches are scored");
+  static_assert(!SM || SC, "sampled launches are scored");
   constexpr bool KV20 = KVI != 24;
   static_assert(KVI == 24 || KVI == 20 || (KVI == 16 && KV24 && (KSD == 4 || KSD == 8) && (RT == 1 || (KSD == 4 && MID == 0)) && CL == 1),
                 "16-bit form: sentences of up to 128 tokens at D = 256 (the 32-sentence tiling: up to 32), up to 32 at D = 512");
@@ -982,7 +990,10 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
   float *red_s = reinterpret_cast<float *>(red_i + NW * R);  // SC: [NW][R] the candidates' sums of exponentials
   [[maybe_unused]] float *ycap = red_s + NW * R;  // FP: [R] the logit of the row's forced column (-inf: not met)
   [[maybe_unused]] int *fcol_s = reinterpret_cast<int *>(ycap + R);  // FP: [R] the forced columns of the step
-  int *flags = red_i + NW * R + (SC ? NW * R : 0) + (FP ? 2 * R : 0);  // [0] = number of finished sentences of this tile
+  [[maybe_unused]] float *red_m = red_s + NW * R + (FP ? 2 * R : 0);  // SM: [NW][R] the candidates' maxima of z
+  [[maybe_unused]] float *red_z = red_m + NW * R;                      // SM: [NW][R] the candidates' own z
+  [[maybe_unused]] uint32_t *seed_s = reinterpret_cast<uint32_t *>(red_z + NW * R);  // SM: [2][R] the rows' hash words of the step
+  int *flags = red_i + NW * R + (SC ? NW * R : 0) + (FP ? 2 * R : 0) + (SM ? 2 * NW * R + 2 * R : 0);  // [0] = number of finished sentences of this tile
   float *pbufs = reinterpret_cast<float *>(flags + 16);  // [NW][256] attention scratch
   float *kvpb = pbufs + NW * PBW;  // KV24: [Ld][K pb, V pb][D], or at D = 512 [Ld][K pb, K c127, V pb, V c127][D]
   // LayerNorm scale / bias of every layer in LDS ([Ld][rnn, attn, ffn][scale, bias][D]) where it fits:
@@ -1201,6 +1212,25 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
       if (row_wave && lane == 0) {
         fcol_s[16 * rr + wave] = c;
         ycap[16 * rr + wave] = -__builtin_inff();
+      }
+    }
+  }
+  // SM: each row's key (a.keys == nullptr: its row in its batch) and the hash words of its step 0, like fcol_s above
+  [[maybe_unused]] uint32_t skey[RT][2];
+  if constexpr (SM) {
+#pragma unroll
+    for (int rr = 0; rr < RT; ++rr) {
+      uint64_t k = 0;
+      if (live[rr]) {
+        const uint64_t *const kp = n_sub ? a.sub_keys[SLIMT_SW(rr)] : a.keys;
+        k = kp ? kp[bq[rr] - SLIMT_SUB_FIRST(rr)] : (uint64_t)(bq[rr] - SLIMT_SUB_FIRST(rr));
+      }
+      skey[rr][0] = __builtin_amdgcn_readfirstlane((uint32_t)k);
+      skey[rr][1] = __builtin_amdgcn_readfirstlane((uint32_t)(k >> 32));
+      if (row_wave && lane == 0) {
+        const uint64_t w = sm_step_words(((uint64_t)skey[rr][1] << 32) | skey[rr][0], 0);
+        seed_s[16 * rr + wave] = (uint32_t)w;
+        seed_s[R + 16 * rr + wave] = (uint32_t)(w >> 32);
       }
     }
   }
@@ -1772,6 +1802,8 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
     int bi[RT][4];
     [[maybe_unused]] float bs[RT][4];  // SC: sum of exp(logit - bv) over this lane's columns so far
     [[maybe_unused]] int fc[RT][4];    // FP: the row's forced column (-1: none)
+    [[maybe_unused]] float mz[RT][4];  // SM: bv is the best key; the maximum of z = logit * inv_T that bs is relative to
+    [[maybe_unused]] float zw[RT][4];  // SM: the z of the best key's column
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -1780,12 +1812,36 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
         bi[rt][r] = 0x7fffffff;
         if constexpr (SC) bs[rt][r] = 0.0f;
         if constexpr (FP) fc[rt][r] = fcol_s[16 * rt + lg * 4 + r];
+        if constexpr (SM) {
+          mz[rt][r] = -3.402823466e+38f;
+          zw[rt][r] = 0.0f;
+        }
       }
     stream_gemm_from<KSD, NB_OUT, 0, (KSD >= 4), RT>(
         A1, LDA, outw, wave, lane, fl, [&](int tile, int rt, const v4i &acc, int co, float pb) {
           const int col = tile * 16 + lr;
           const bool in_range = col < outw.N;  // no branch: the streaming loop stays one block
           const Dequant4 l4v = dequant4(acc, co, a.out.u, pb);
+          if constexpr (SM) {  // (the noise goes by vocabulary id: the same draw whatever the shortlist's layout)
+            const uint32_t *const sm_sl = n_sub ? a.sub[sj].shortlist : a.shortlist;  // (the tile's output layer)
+            const uint32_t id = sm_sl ? (in_range ? sm_sl[col] : 0u) : (uint32_t)col;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int row = 16 * rt + lg * 4 + r;
+              const float v = l4v.v[r];
+              const float z = v * a.inv_T;
+              const float key = sm_key(v, a.inv_T, seed_s[row], seed_s[R + row], id);
+              const bool better = in_range && key > bv[rt][r];
+              lse_push_z(z, in_range, mz[rt][r], bs[rt][r]);
+              if constexpr (FP) {
+                if (col == fc[rt][r]) ycap[row] = z;
+              }
+              bv[rt][r] = better ? key : bv[rt][r];
+              bi[rt][r] = better ? col : bi[rt][r];
+              zw[rt][r] = better ? z : zw[rt][r];
+            }
+            return;
+          }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float v = l4v.v[r];
@@ -1810,7 +1866,9 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        if constexpr (SC)
+        if constexpr (SM)
+          row16_argmax_sm(bv[rt][r], bi[rt][r], mz[rt][r], bs[rt][r], zw[rt][r]);
+        else if constexpr (SC)
           row16_argmax_lse(bv[rt][r], bi[rt][r], bs[rt][r]);
         else
           row16_argmax(bv[rt][r], bi[rt][r]);
@@ -1818,6 +1876,10 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
           red_v[wave * R + 16 * rt + lg * 4 + r] = bv[rt][r];
           red_i[wave * R + 16 * rt + lg * 4 + r] = bi[rt][r];
           if constexpr (SC) red_s[wave * R + 16 * rt + lg * 4 + r] = bs[rt][r];
+          if constexpr (SM) {
+            red_m[wave * R + 16 * rt + lg * 4 + r] = mz[rt][r];
+            red_z[wave * R + 16 * rt + lg * 4 + r] = zw[rt][r];
+          }
         }
       }
     SLIMT_STAMP(45);
@@ -1835,6 +1897,18 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
         int ix;
         if constexpr (CL > 1) {
           ix = cl_ix[rr];
+        } else if constexpr (SM) {
+          float k = lane < NW ? red_v[lane * R + row] : -3.402823466e+38f;
+          ix = lane < NW ? red_i[lane * R + row] : 0x7fffffff;
+          float sum = lane < NW ? red_s[lane * R + row] : 0.0f;
+          float m = lane < NW ? red_m[lane * R + row] : -3.402823466e+38f;
+          float zz = lane < NW ? red_z[lane * R + row] : 0.0f;
+          row16_argmax_sm(k, ix, m, sum, zz);
+          ix = __builtin_amdgcn_readfirstlane(ix);
+          score = forced_score(sum, zz - m, ix == 0x7fffffff || nan0);  // log softmax(z) at the drawn column
+          if constexpr (FP) {
+            if (ftok[rr] != 0xffffffffu) score = forced_score(sum, ycap[row] - m, ix == 0x7fffffff || nan0);
+          }
         } else if constexpr (SC) {
           float v = lane < NW ? red_v[lane * R + row] : -3.402823466e+38f;
           ix = lane < NW ? red_i[lane * R + row] : 0x7fffffff;
@@ -1886,6 +1960,13 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
         if (lane == 0) {  // (after this wave's read of ycap[row] above: LDS operations of a wave stay in order)
           fcol_s[row] = c;
           ycap[row] = -__builtin_inff();
+        }
+      }
+      if constexpr (SM) {  // the hash words of the sentence's next step (its count of recorded tokens)
+        if (lane == 0) {
+          const uint64_t w = sm_step_words(((uint64_t)skey[rr][1] << 32) | skey[rr][0], n_out[rr]);
+          seed_s[row] = (uint32_t)w;
+          seed_s[R + row] = (uint32_t)(w >> 32);
         }
       }
       if (t + 1 < max_steps) {
@@ -1974,8 +2055,10 @@ int fused_decode_grid(int B, bool tickets, int rows) {
 // tight: the kernels with the 16-bit cache form inlined (KVI = 16) keep its column terms [Ld][K, V][D] behind everything else.
 // scores: the scored kernels (SC) keep one more [NW][rows] float array beside the arg-max's (red_s)
 // forced: the forced kernels (FP) one float (ycap) and one int (fcol_s) per row
+// sampled: the sampled kernels (SM) two more [NW][rows] float arrays (red_m, red_z) and two words per row (seed_s)
 size_t fused_decode_lds_bytes(int D, int F, int Ld, int rows, bool kv24 = false, int mid = 0,
-                              bool *ln_in_lds = nullptr, bool tight = false, bool scores = false, bool forced = false) {
+                              bool *ln_in_lds = nullptr, bool tight = false, bool scores = false, bool forced = false,
+                              bool sampled = false) {
   // D * rows > 256 * 16: two f32 row buffers, SSRU cells in global memory (see the kernel)
   const size_t R = (size_t)rows;
   const bool lean = (size_t)D * R > 256 * 16;
@@ -1985,7 +2068,8 @@ size_t fused_decode_lds_bytes(int D, int F, int Ld, int rows, bool kv24 = false,
                       NW * (mid == 2 ? 1024 : mid == 1 ? 512 : 256) * 4 + (kv24 ? (size_t)Ld * (D == 512 ? 4 : 2) * D * 4 : 0) +
                       (tight ? (size_t)Ld * (rows > 16 ? 1 : 2) * D * 4 : 0) +  // (32 sentences: the K centres only)
                       (scores ? (size_t)NW * R * 4 : 0) +
-                      (forced ? 2 * R * 4 : 0);  // (FP: ycap and fcol_s, 128 bytes at 16 rows)
+                      (forced ? 2 * R * 4 : 0) +  // (FP: ycap and fcol_s, 128 bytes at 16 rows)
+                      (sampled ? 2 * (size_t)NW * R * 4 + 2 * R * 4 : 0);
   const size_t ln = (D == 256 && rows == 16 && !mid) ? (size_t)Ld * 6 * D * 4 : 0;
   const bool fits = ln > 0 && base + ln <= 160 * 1024;
   if (ln_in_lds) *ln_in_lds = fits;
@@ -2043,11 +2127,14 @@ bool fused_decode_packed_supported(int D, int F, int H, int Ld) {
 // a kernel of the launcher's choice, scored (SC) or not: nullptr where the scored twin does not exist (32-sentence,
 // 8- and 4-sentence tilings, clusters) -- a scored call there fails instead of losing its scores
 // (FP: the forced twin, likewise; a forced call where it does not exist fails instead of ignoring its prefix)
-template <bool MG, bool SC, bool FP, int KSD, int KSF, int DH, bool LONG, bool NT, int RT = 1, bool KV24 = false, int MID = 0,
+// (SM: the sampled twin, with or without FP, likewise; a sampled call where it does not exist fails instead of decoding greedily)
+template <bool MG, bool SC, bool FP, bool SM, int KSD, int KSF, int DH, bool LONG, bool NT, int RT = 1, bool KV24 = false, int MID = 0,
           int SPW = 16, int CL = 1, int KVI = 20>
 static constexpr auto dfk() -> void (*)(FusedDecodeArgs) {
-  if constexpr ((SC || FP) && (RT != 1 || CL != 1 || SPW != 16))
+  if constexpr ((SC || FP || SM) && (RT != 1 || CL != 1 || SPW != 16))
     return nullptr;
+  else if constexpr (SM)
+    return decode_fused_kernel<MG, KSD, KSF, DH, LONG, NT, RT, KV24, MID, SPW, CL, KVI, true, FP, true>;
   else if constexpr (FP)
     return decode_fused_kernel<MG, KSD, KSF, DH, LONG, NT, RT, KV24, MID, SPW, CL, KVI, true, true>;
   else
@@ -2056,20 +2143,20 @@ static constexpr auto dfk() -> void (*)(FusedDecodeArgs) {
 
 // the long-sentence instantiation exists for d_head 32 only (attention_row_long), the
 // non-temporal K/V variant for d_head 32 and 64 (the buffer-load paths of attention_row)
-template <bool MG, bool SC, bool FP, int KSD, int KSF, int DH>
+template <bool MG, bool SC, bool FP, bool SM, int KSD, int KSF, int DH>
 static auto decode_fused_pick(bool long_sentences, bool nt) -> void (*)(FusedDecodeArgs) {
   if constexpr (DH == 32) {
-    if (long_sentences) return nt ? dfk<MG, SC, FP, KSD, KSF, DH, true, true>() : dfk<MG, SC, FP, KSD, KSF, DH, true, false>();
+    if (long_sentences) return nt ? dfk<MG, SC, FP, SM, KSD, KSF, DH, true, true>() : dfk<MG, SC, FP, SM, KSD, KSF, DH, true, false>();
   }
   if constexpr (DH >= 32) {
-    if (nt) return dfk<MG, SC, FP, KSD, KSF, DH, false, true>();
+    if (nt) return dfk<MG, SC, FP, SM, KSD, KSF, DH, false, true>();
   }
   (void)long_sentences;
   (void)nt;
-  return dfk<MG, SC, FP, KSD, KSF, DH, false, false>();
+  return dfk<MG, SC, FP, SM, KSD, KSF, DH, false, false>();
 }
 
-template <bool MG, bool SC, bool FP = false>
+template <bool MG, bool SC, bool FP = false, bool SM = false>
 static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int F, int H, hipStream_t st) {
   FusedDecodeArgs a = a_in;
   if (!fused_decode_supported(D, F, H, a.Ld)) return hipErrorInvalidValue;
@@ -2094,29 +2181,29 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
   };
   // the variants over the packed cache: <KSD, KSF, DH, MID> x non-temporal K/V loads x sentences per workgroup
 #define SLIMT_KV24_PICK(KSD_, KSF_, DH_, MID_)                                                                  \
-  (rows == 4   ? (a.kv_nt ? dfk<MG, SC, FP, KSD_, KSF_, DH_, false, true, 1, true, MID_, 4>()                 \
-                          : dfk<MG, SC, FP, KSD_, KSF_, DH_, false, false, 1, true, MID_, 4>())               \
-   : rows == 8 ? (a.kv_nt ? dfk<MG, SC, FP, KSD_, KSF_, DH_, false, true, 1, true, MID_, 8>()                 \
-                          : dfk<MG, SC, FP, KSD_, KSF_, DH_, false, false, 1, true, MID_, 8>())               \
-               : (a.kv_nt ? dfk<MG, SC, FP, KSD_, KSF_, DH_, false, true, 1, true, MID_>()                    \
-                          : dfk<MG, SC, FP, KSD_, KSF_, DH_, false, false, 1, true, MID_>()))
+  (rows == 4   ? (a.kv_nt ? dfk<MG, SC, FP, SM, KSD_, KSF_, DH_, false, true, 1, true, MID_, 4>()                 \
+                          : dfk<MG, SC, FP, SM, KSD_, KSF_, DH_, false, false, 1, true, MID_, 4>())               \
+   : rows == 8 ? (a.kv_nt ? dfk<MG, SC, FP, SM, KSD_, KSF_, DH_, false, true, 1, true, MID_, 8>()                 \
+                          : dfk<MG, SC, FP, SM, KSD_, KSF_, DH_, false, false, 1, true, MID_, 8>())               \
+               : (a.kv_nt ? dfk<MG, SC, FP, SM, KSD_, KSF_, DH_, false, true, 1, true, MID_>()                    \
+                          : dfk<MG, SC, FP, SM, KSD_, KSF_, DH_, false, false, 1, true, MID_>()))
   // every cache of this launch in the 24-bit form (a.kv_fmt == nullptr): the 16-sentence tilings have an instantiation
   // with that form inlined (KVI = 24); the 8- / 4-sentence ones reach it through the fallback call
 #define SLIMT_KV24_ONLY(KSD_, KSF_, DH_, MID_)                                                        \
-  (a.kv_nt ? dfk<MG, SC, FP, KSD_, KSF_, DH_, false, true, 1, true, MID_, 16, 1, 24>()          \
-           : dfk<MG, SC, FP, KSD_, KSF_, DH_, false, false, 1, true, MID_, 16, 1, 24>())
+  (a.kv_nt ? dfk<MG, SC, FP, SM, KSD_, KSF_, DH_, false, true, 1, true, MID_, 16, 1, 24>()          \
+           : dfk<MG, SC, FP, SM, KSD_, KSF_, DH_, false, false, 1, true, MID_, 16, 1, 24>())
   const bool only24 = kv24 && !a.kv_fmt && rows == 16 && a.cluster <= 1;
   if constexpr (MG) {  // (the merged twins: 16-row tilings, sentences of up to 64 tokens, no clusters)
     if (rows > 16 || mid == 2 || a.cluster > 1) return hipErrorInvalidValue;
   }
   if (mid) {
     if (rows > 16 || F != 1536) return hipErrorInvalidValue;
-    const size_t ldsm = fused_decode_lds_bytes(D, F, a.Ld, 16, true, mid, nullptr, a.kv_tight, SC, FP);
+    const size_t ldsm = fused_decode_lds_bytes(D, F, a.Ld, 16, true, mid, nullptr, a.kv_tight, SC, FP, SM);
     if (ldsm > 160 * 1024) return hipErrorInvalidValue;
     if (a.kv_tight) {
 #define SLIMT_KV16_PICK(MID_, SPW_)                                                                \
-  (a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 1, true, MID_, SPW_, 1, 16>()               \
-           : dfk<MG, SC, FP, 4, 24, 32, false, false, 1, true, MID_, SPW_, 1, 16>())
+  (a.kv_nt ? dfk<MG, SC, FP, SM, 4, 24, 32, false, true, 1, true, MID_, SPW_, 1, 16>()               \
+           : dfk<MG, SC, FP, SM, 4, 24, 32, false, false, 1, true, MID_, SPW_, 1, 16>())
       if (mid == 1) return go(rows == 4 ? SLIMT_KV16_PICK(1, 4) : rows == 8 ? SLIMT_KV16_PICK(1, 8) : SLIMT_KV16_PICK(1, 16), ldsm);
       if constexpr (!MG) return go(rows == 4 ? SLIMT_KV16_PICK(2, 4) : rows == 8 ? SLIMT_KV16_PICK(2, 8) : SLIMT_KV16_PICK(2, 16), ldsm);
 #undef SLIMT_KV16_PICK
@@ -2128,14 +2215,14 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
     if (only24) return go(SLIMT_KV24_ONLY(4, 24, 32, 1), ldsm);
     return go(SLIMT_KV24_PICK(4, 24, 32, 1), ldsm);
   }
-  const size_t lds = fused_decode_lds_bytes(D, F, a.Ld, rows <= 16 ? 16 : rows, kv24, 0, &a.ln_in_lds, a.kv_tight, SC, FP);
+  const size_t lds = fused_decode_lds_bytes(D, F, a.Ld, rows <= 16 ? 16 : rows, kv24, 0, &a.ln_in_lds, a.kv_tight, SC, FP, SM);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   if (kv24 && D == 512) {
     if (F != 2048) return hipErrorInvalidValue;
     if (a.kv_tight) {
 #define SLIMT_KV16_PICK(SPW_)                                                                      \
-  (a.kv_nt ? dfk<MG, SC, FP, 8, 32, 64, false, true, 1, true, 0, SPW_, 1, 16>()                  \
-           : dfk<MG, SC, FP, 8, 32, 64, false, false, 1, true, 0, SPW_, 1, 16>())
+  (a.kv_nt ? dfk<MG, SC, FP, SM, 8, 32, 64, false, true, 1, true, 0, SPW_, 1, 16>()                  \
+           : dfk<MG, SC, FP, SM, 8, 32, 64, false, false, 1, true, 0, SPW_, 1, 16>())
       return go(rows == 4 ? SLIMT_KV16_PICK(4) : rows == 8 ? SLIMT_KV16_PICK(8) : SLIMT_KV16_PICK(16), lds);
 #undef SLIMT_KV16_PICK
     }
@@ -2145,15 +2232,15 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
   if constexpr (!MG) {
   if (a.cluster > 1) {  // cluster logits: the 16-sentence tiling of the D = 256 packed-cache shape
     if (!(kv24 && D == 256 && F == 1536 && rows == 16 && a.cluster == 4 && a.cl_act && a.cl_part && a.cl_sync)) return hipErrorInvalidValue;
-    return go(a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 1, true, 0, 16, 4>()
-                      : dfk<MG, SC, FP, 4, 24, 32, false, false, 1, true, 0, 16, 4>(), lds);
+    return go(a.kv_nt ? dfk<MG, SC, FP, SM, 4, 24, 32, false, true, 1, true, 0, 16, 4>()
+                      : dfk<MG, SC, FP, SM, 4, 24, 32, false, false, 1, true, 0, 16, 4>(), lds);
   }
   }
   if (only24) return go(SLIMT_KV24_ONLY(4, 24, 32, 0), lds);
   if (kv24 && rows <= 16 && a.kv_tight) {  // sentences may be in the tight 16-bit form: the kernels with it (and the 20-bit one) inlined
 #define SLIMT_KV16_PICK(SPW_)                                                                      \
-  (a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 1, true, 0, SPW_, 1, 16>()                  \
-           : dfk<MG, SC, FP, 4, 24, 32, false, false, 1, true, 0, SPW_, 1, 16>())
+  (a.kv_nt ? dfk<MG, SC, FP, SM, 4, 24, 32, false, true, 1, true, 0, SPW_, 1, 16>()                  \
+           : dfk<MG, SC, FP, SM, 4, 24, 32, false, false, 1, true, 0, SPW_, 1, 16>())
     return go(rows == 4 ? SLIMT_KV16_PICK(4) : rows == 8 ? SLIMT_KV16_PICK(8) : SLIMT_KV16_PICK(16), lds);
 #undef SLIMT_KV16_PICK
   }
@@ -2163,19 +2250,19 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
   if constexpr (!MG) {
   if (rows == 32) {
     if (kv24 && a.kv_tight)
-      return go(a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 2, true, 0, 16, 1, 16>()
-                        : dfk<MG, SC, FP, 4, 24, 32, false, false, 2, true, 0, 16, 1, 16>(), lds);
+      return go(a.kv_nt ? dfk<MG, SC, FP, SM, 4, 24, 32, false, true, 2, true, 0, 16, 1, 16>()
+                        : dfk<MG, SC, FP, SM, 4, 24, 32, false, false, 2, true, 0, 16, 1, 16>(), lds);
     if (kv24 && !a.kv_fmt)  // every cache in the 24-bit form: that form inlined (KVI = 24), as for the 16-sentence tilings
-      return go(a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 2, true, 0, 16, 1, 24>()
-                        : dfk<MG, SC, FP, 4, 24, 32, false, false, 2, true, 0, 16, 1, 24>(), lds);
-    auto k = kv24 ? (a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 2, true>() : dfk<MG, SC, FP, 4, 24, 32, false, false, 2, true>())
-                  : (a.kv_nt ? dfk<MG, SC, FP, 4, 24, 32, false, true, 2>() : dfk<MG, SC, FP, 4, 24, 32, false, false, 2>());
+      return go(a.kv_nt ? dfk<MG, SC, FP, SM, 4, 24, 32, false, true, 2, true, 0, 16, 1, 24>()
+                        : dfk<MG, SC, FP, SM, 4, 24, 32, false, false, 2, true, 0, 16, 1, 24>(), lds);
+    auto k = kv24 ? (a.kv_nt ? dfk<MG, SC, FP, SM, 4, 24, 32, false, true, 2, true>() : dfk<MG, SC, FP, SM, 4, 24, 32, false, false, 2, true>())
+                  : (a.kv_nt ? dfk<MG, SC, FP, SM, 4, 24, 32, false, true, 2>() : dfk<MG, SC, FP, SM, 4, 24, 32, false, false, 2>());
     return go(k, lds);
   }
   }
 #define SLIMT_FUSED_CASE(KSD_, KSF_, DH_)                                                   \
   if (D == 64 * KSD_ && F == 64 * KSF_ && D / H == DH_) {                                    \
-    auto k = decode_fused_pick<MG, SC, FP, KSD_, KSF_, DH_>(a.S > 32, a.kv_nt);                           \
+    auto k = decode_fused_pick<MG, SC, FP, SM, KSD_, KSF_, DH_>(a.S > 32, a.kv_nt);                           \
     if (!k) return hipErrorInvalidValue;                                                     \
     hipError_t e = set_dynamic_lds_once(reinterpret_cast<const void *>(k), (int)lds); \
     if (e != hipSuccess) return e;                                                           \
@@ -2189,6 +2276,16 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
 }
 
 hipError_t launch_decode_fused(const FusedDecodeArgs &a, int D, int F, int H, hipStream_t st) {
+  if (a.inv_T != 0.0f) {  // (sampled: scored as well, forced or not)
+    if (!(a.inv_T > 0.0f) || !(a.n_sub > 0 ? a.sub_scores[0] : a.scores)) return hipErrorInvalidValue;
+    if (a.prefix_ids || a.sub_prefix_ids[0]) {
+      if (!(a.n_sub > 0 ? a.sub_prefix_len[0] : a.prefix_len)) return hipErrorInvalidValue;
+      return a.n_sub > 0 ? launch_decode_fused_t<true, true, true, true>(a, D, F, H, st)
+                         : launch_decode_fused_t<false, true, true, true>(a, D, F, H, st);
+    }
+    return a.n_sub > 0 ? launch_decode_fused_t<true, true, false, true>(a, D, F, H, st)
+                       : launch_decode_fused_t<false, true, false, true>(a, D, F, H, st);
+  }
   if (a.prefix_ids || a.sub_prefix_ids[0]) {  // (forced: scored as well -- the engine gives every batch a destination)
     if (!(a.n_sub > 0 ? a.sub_scores[0] && a.sub_prefix_len[0] : a.scores && a.prefix_len)) return hipErrorInvalidValue;
     return a.n_sub > 0 ? launch_decode_fused_t<true, true, true>(a, D, F, H, st) : launch_decode_fused_t<false, true, true>(a, D, F, H, st);

@@ -331,6 +331,91 @@ __global__ __launch_bounds__(256) void dgemm_kernel(DGemmArgs a) {
               fmaxf(fmaxf(red_y[tid], red_y[16 + tid]), fmaxf(red_y[32 + tid], red_y[48 + tid]));
       }
     }
+  } else if constexpr (EPI == EPI_ARGMAX_SM) {
+    // sampled (sampling.h): the first maximum of key = fmaf(logit, inv_T, noise of the column's vocabulary id) with the
+    // merge order of the arg-max above; beside it the log-sum-exp of z = logit * inv_T (its own maximum mz), the z of
+    // the key's column (zw) and, where the row has a forced column (a.fcol, nullable), that column's z
+    __syncthreads();  // A_lds is reused as the reduction buffer
+    float *red_v = reinterpret_cast<float *>(smem);
+    int *red_i = reinterpret_cast<int *>(red_v + 64);
+    float *red_s = reinterpret_cast<float *>(red_i + 64);
+    float *red_y = red_s + 64;
+    float *red_m = red_y + 64;
+    float *red_z = red_m + 64;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = m0 + lg * 4 + r;
+      float bv = -3.402823466e+38f, mz = -3.402823466e+38f;
+      int bi = 0x7fffffff;
+      float bs = 0.0f, zw = 0.0f, by = -__builtin_inff();
+      const int fc = a.fcol && row < a.B ? a.fcol[row] : -1;
+      const uint32_t s0 = row < a.B ? a.seeds[row] : 0u, s1 = row < a.B ? a.seeds[a.B + row] : 0u;
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const int ntile = nt0 + nt;
+        const int col = ntile * 16 + lr;
+        if (ntile < n_tiles && col < a.w.N) {
+          float v = (float)(acc[nt][r] + 127 * a.w.colsum[col]) * u;
+          v = v + a.w.pb[col];
+          const uint32_t id = a.sm_shortlist ? a.sm_shortlist[col] : (uint32_t)col;
+          const float z = v * a.inv_T;
+          const float key = sm_key(v, a.inv_T, s0, s1, id);
+          lse_push_z(z, true, mz, bs);
+          by = col == fc ? z : by;
+          if (key > bv || (key == bv && col < bi)) {
+            bv = key;
+            bi = col;
+            zw = z;
+          }
+        }
+      }
+#pragma unroll
+      for (int m = 1; m < 16; m <<= 1) {
+        const float ov = __shfl_xor(bv, m, 64);
+        const int oi = __shfl_xor(bi, m, 64);
+        const float oz = __shfl_xor(zw, m, 64);
+        lse_merge(mz, bs, __shfl_xor(mz, m, 64), __shfl_xor(bs, m, 64));
+        by = fmaxf(by, __shfl_xor(by, m, 64));
+        if (ov > bv || (ov == bv && oi < bi)) {
+          bv = ov;
+          bi = oi;
+          zw = oz;
+        }
+      }
+      if (lr == 0) {
+        red_v[wave * 16 + lg * 4 + r] = bv;
+        red_i[wave * 16 + lg * 4 + r] = bi;
+        red_s[wave * 16 + lg * 4 + r] = bs;
+        red_y[wave * 16 + lg * 4 + r] = by;
+        red_m[wave * 16 + lg * 4 + r] = mz;
+        red_z[wave * 16 + lg * 4 + r] = zw;
+      }
+    }
+    __syncthreads();
+    if (tid < 16) {
+      float bv = red_v[tid], bs = red_s[tid], mz = red_m[tid], zw = red_z[tid];
+      int bi = red_i[tid];
+      for (int w = 1; w < 4; ++w) {
+        const float ov = red_v[w * 16 + tid];
+        const int oi = red_i[w * 16 + tid];
+        lse_merge(mz, bs, red_m[w * 16 + tid], red_s[w * 16 + tid]);
+        if (ov > bv || (ov == bv && oi < bi)) {
+          bv = ov;
+          bi = oi;
+          zw = red_z[w * 16 + tid];
+        }
+      }
+      const int row = m0 + tid;
+      if (row < a.B) {
+        const size_t at = (size_t)row * a.n_parts + blockIdx.y;
+        a.part_val[at] = bv;
+        a.part_idx[at] = bi;
+        a.part_sum[at] = bs;
+        a.part_mz[at] = mz;
+        a.part_zw[at] = zw;
+        if (a.part_y) a.part_y[at] = fmaxf(fmaxf(red_y[tid], red_y[16 + tid]), fmaxf(red_y[32 + tid], red_y[48 + tid]));
+      }
+    }
   }
 }
 
@@ -373,6 +458,9 @@ static hipError_t launch_dgemm_t(const DGemmArgs &a, int epi, dim3 grid, size_t 
     hipLaunchKernelGGL((dgemm_kernel<PF, NT, EPI_ARGMAX_SC, false>), grid, dim3(256), lds, st, a);
   else if (epi == EPI_ARGMAX_FP && !i8 && a.part_sum && a.fcol && a.part_y)
     hipLaunchKernelGGL((dgemm_kernel<PF, NT, EPI_ARGMAX_FP, false>), grid, dim3(256), lds, st, a);
+  else if (epi == EPI_ARGMAX_SM && !i8 && a.part_sum && a.part_mz && a.part_zw && a.seeds && a.inv_T > 0.0f &&
+           (a.fcol != nullptr) == (a.part_y != nullptr))
+    hipLaunchKernelGGL((dgemm_kernel<PF, NT, EPI_ARGMAX_SM, false>), grid, dim3(256), lds, st, a);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
@@ -386,7 +474,7 @@ hipError_t launch_dgemm(const DGemmArgs &a, int epilogue, hipStream_t st) {
   int pf, nt;
   dgemm_config(K, N, a.B, &pf, &nt);
   const int col_blocks = (N + 64 * nt - 1) / (64 * nt);
-  if ((epilogue == EPI_ARGMAX || epilogue == EPI_ARGMAX_SC || epilogue == EPI_ARGMAX_FP) && a.n_parts != col_blocks) return hipErrorInvalidValue;
+  if ((epilogue == EPI_ARGMAX || epilogue == EPI_ARGMAX_SC || epilogue == EPI_ARGMAX_FP || epilogue == EPI_ARGMAX_SM) && a.n_parts != col_blocks) return hipErrorInvalidValue;
   const dim3 grid((a.B + 15) / 16, col_blocks);
   size_t lds = 16 * (size_t)(K + 16) + 16 * (size_t)(D + 4) * sizeof(float);
   if (lds < 1024) lds = 1024;

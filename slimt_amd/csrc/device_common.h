@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "sampling.h"
 #include "scores.h"
 
 namespace slimt_hip {
@@ -212,6 +213,39 @@ __device__ __forceinline__ void row16_argmax_lse(float &v, int &ix, float &s) {
   argmax_lse_step<2>(v, ix, s);
   argmax_lse_step<4>(v, ix, s);
   argmax_lse_step<8>(v, ix, s);
+}
+
+// ... and the sampled twin (sampling.h): the compared value is a key, so the log-sum-exp of z = logit / T carries its own
+// maximum mz; zw is the winner's z (what the score needs beside mz and s). A running (mz, s) takes one z with lse_push_z.
+__device__ __forceinline__ void lse_push_z(float z, bool in, float &mz, float &s) {
+  const bool up = in && z > mz;
+  lse_push(z, in, up, mz, s);
+  mz = up ? z : mz;
+}
+template <int M>
+__device__ __forceinline__ void argmax_sm_step(float &k, int &ix, float &mz, float &s, float &zw) {
+  float a, ok;
+  butterfly_pair<M>(k, a, ok);
+  float ia, oi;
+  butterfly_pair<M>(__int_as_float(ix), ia, oi);
+  float ma, om;
+  butterfly_pair<M>(mz, ma, om);
+  float sa, os;
+  butterfly_pair<M>(s, sa, os);
+  float za, oz;
+  butterfly_pair<M>(zw, za, oz);
+  const int o = __float_as_int(oi);
+  const bool take = ok > k || (ok == k && o < ix);
+  lse_merge(mz, s, om, os);
+  k = take ? ok : k;
+  ix = take ? o : ix;
+  zw = take ? oz : zw;
+}
+__device__ __forceinline__ void row16_argmax_sm(float &k, int &ix, float &mz, float &s, float &zw) {
+  argmax_sm_step<1>(k, ix, mz, s, zw);
+  argmax_sm_step<2>(k, ix, mz, s, zw);
+  argmax_sm_step<4>(k, ix, mz, s, zw);
+  argmax_sm_step<8>(k, ix, mz, s, zw);
 }
 
 // The output-layer column of a forced token (slimt_hip_ctx_set_target_prefix), the same on every lane of the wave:

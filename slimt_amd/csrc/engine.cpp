@@ -1,6 +1,7 @@
 // C ABI (include/slimt_hip.h) + host-side engine of the MI355X slimt backend.
 #include "engine.h"
 #include "decoder_plan.h"
+#include "sampling.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1073,7 +1074,7 @@ void sinusoid_table(int S, int D, std::vector<float> &out) {
 void ctx_free(slimt_hip_ctx *c) {
   DevBuf *bufs[] = {&c->pos, &c->ids, &c->lengths, &c->x0, &c->x1, &c->q, &c->k, &c->v, &c->att,
                     &c->h8, &c->a8, &c->ticket, &c->kv, &c->kv_fmt, &c->cl_act, &c->cl_part, &c->cl_sync, &c->dx, &c->dx_pre, &c->dh, &c->datt8, &c->dout, &c->df8,
-                    &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->prev, &c->out_ids, &c->out_len,
+                    &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag};
   for (auto *b : bufs) b->release();
@@ -1308,6 +1309,23 @@ extern "C" int slimt_hip_ctx_set_target_prefix(slimt_hip_ctx *ctx, const uint32_
   return 0;
 }
 
+extern "C" uint64_t slimt_hip_sampling_key(uint64_t seed, uint64_t index) { return slimt_hip::sm_sentence_key(seed, index); }
+
+extern "C" int slimt_hip_ctx_set_sampling(slimt_hip_ctx *ctx, float temperature, const uint64_t *const *keys, size_t n) {
+  // (the value first: a bad temperature is refused whatever else is wrong with the call)
+  if (!(temperature > 0.0f) || !std::isfinite(temperature)) return fail(-1, "sampling: temperature %g is not finite and > 0", (double)temperature);
+  const float inv_T = 1.0f / temperature;
+  if (!(inv_T > 0.0f) || !std::isfinite(inv_T)) return fail(-1, "sampling: 1 / temperature %g is not finite and > 0", (double)temperature);
+  if (!ctx) return fail(-1, "null argument");
+  if (keys)
+    ctx->sm_next_keys.assign(keys, keys + n);  // (the count is checked by the call that takes them: SampleCall)
+  else
+    ctx->sm_next_keys.assign(n, nullptr);
+  ctx->sm_next_inv_T = inv_T;
+  ctx->sm_armed = n > 0;  // (n = 0: nothing armed)
+  return 0;
+}
+
 extern "C" int slimt_hip_ctx_set_encode_rows(slimt_hip_ctx *ctx, int rows) {
   if (!ctx) return fail(-1, "ctx is NULL");
   if (rows != 0 && rows != 32 && rows != 64) return fail(-1, "encoder rows per workgroup %d not in {0, 32, 64}", rows);
@@ -1508,6 +1526,7 @@ struct MergePlan {
   float *scores[kMaxMerge] = {};  // scored launches: sub-batch j's destination, device-visible (FusedDecodeArgs::sub_scores)
   const uint32_t *prefix_ids[kMaxMerge] = {};  // forced launches: sub-batch j's prefix in device memory (FusedDecodeArgs)
   const uint32_t *prefix_len[kMaxMerge] = {};
+  const uint64_t *keys[kMaxMerge] = {};  // sampled launches: sub-batch j's keys in device memory (nullptr: the row in the sub-batch)
 };
 
 // The scores armed on a context (slimt_hip_ctx_set_scores) are taken by the translate entry point that comes next, whether
@@ -1575,6 +1594,60 @@ struct PrefixCall {
   }
 };
 
+// The sampling armed on a context (slimt_hip_ctx_set_sampling), taken like the scores and the prefix by the next translate
+// entry point, whether it then succeeds or fails. keys[j] may be NULL (batch j's keys are its row indices). The entry points
+// point ctx->sm_keys at memory the kernels read: the caller's array for the _device calls, else its pinned view or a staged
+// copy (keys_stage).
+struct SampleCall {
+  slimt_hip_ctx *c = nullptr;
+  std::vector<const uint64_t *> keys;
+  int rc = 0;
+  SampleCall(slimt_hip_ctx *ctx, size_t n) {
+    if (!ctx || !ctx->sm_armed) return;
+    c = ctx;
+    keys.swap(ctx->sm_next_keys);
+    ctx->sm_armed = false;
+    ctx->sm_next_keys.clear();
+    if (keys.size() != n) rc = fail(-1, "sampling: %zu batches armed, the call has %zu", keys.size(), n);
+    ctx->sm_call = rc == 0;
+    ctx->sm_inv_T = ctx->sm_next_inv_T;
+    ctx->sm_user_keys = rc == 0 && n == 1 ? keys[0] : nullptr;
+    ctx->sm_keys = nullptr;
+  }
+  ~SampleCall() {
+    if (!c) return;
+    c->sm_call = false;
+    c->sm_user_keys = c->sm_keys = nullptr;
+  }
+};
+
+void *host_device_view(const void *p);  // (below)
+
+// Host keys -> addresses the kernels read, like prefix_stage: pinned arrays in place, a pageable batch's keys staged in
+// device memory with one asynchronous copy on the context's stream; NULL stays NULL.
+int keys_stage(slimt_hip_ctx *c, size_t n, const uint64_t *const *keys, const size_t *B, const uint64_t **d_keys) {
+  size_t words = 0;
+  for (size_t j = 0; j < n; ++j) {
+    d_keys[j] = keys[j] ? static_cast<const uint64_t *>(host_device_view(keys[j])) : nullptr;
+    if (keys[j] && !d_keys[j]) words += B[j];
+  }
+  if (words) HIPCHK(c->sm_stage.reserve(words * 8));
+  uint64_t *p = c->sm_stage.as<uint64_t>();
+  for (size_t j = 0; j < n; ++j) {
+    if (!keys[j] || d_keys[j]) continue;
+    HIPCHK(hipMemcpyAsync(p, keys[j], B[j] * 8, hipMemcpyHostToDevice, c->stream));
+    d_keys[j] = p;
+    p += B[j];
+  }
+  return 0;
+}
+
+int keys_stage_batches(slimt_hip_ctx *c, const SampleCall &sm, const slimt_hip_batch *batches, size_t n, const uint64_t **d_keys) {
+  std::vector<size_t> B(n);
+  for (size_t j = 0; j < n; ++j) B[j] = batches[j].B;
+  return keys_stage(c, n, sm.keys.data(), B.data(), d_keys);
+}
+
 // A host prefix of B sentences with rows Tmax apart: every length <= Tmax, every id of the prefix < V.
 int prefix_check(const slimt_hip_ctx *c, const uint32_t *ids, const uint32_t *len, size_t B, size_t Tmax) {
   for (size_t b = 0; b < B; ++b) {
@@ -1585,8 +1658,6 @@ int prefix_check(const slimt_hip_ctx *c, const uint32_t *ids, const uint32_t *le
   }
   return 0;
 }
-
-void *host_device_view(const void *p);  // (below)
 
 // Host prefixes -> addresses the kernels read. Pinned arrays (hipHostMalloc / slimt_hip_host_alloc) are read in place,
 // like the pinned inputs of the asynchronous calls (translate_host: no copy queued behind other streams' kernels); a
@@ -2128,9 +2199,11 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   // to each sub-batch's mp->scores[j] (the entry points set them to addresses the kernels can write)
   // a forced call (PrefixCall) takes the scored kernels' forced twins: scored as well, into a context-owned scratch when the
   // caller did not ask for scores (merged: sub-batch j's rows of it from its first sentence on, Tmax_j <= Tmax)
+  // a sampled call (SampleCall) takes their sampled twins, with or without a prefix: scored in the same way
   const bool forced = c->fp_call;
-  const bool scored = c->sc_call || forced;
-  if (forced && !c->sc_call) {
+  const bool sampled = c->sm_call;
+  const bool scored = c->sc_call || forced || sampled;
+  if ((forced || sampled) && !c->sc_call) {
     HIPCHK(c->fp_scratch.reserve(B * Tmax * 4));
     for (int j = 0; mp && j < mp->n; ++j) mp->scores[j] = c->fp_scratch.as<float>() + (size_t)mp->out[j].first * Tmax;
   }
@@ -2285,6 +2358,11 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
       f.kv_u4096[l][1] = wv.w.u * (1.0f / 4096.0f);
     }
     f.scores = d_scores;
+    if (sampled) {
+      f.inv_T = c->sm_inv_T;
+      f.keys = mp ? nullptr : c->sm_keys;
+      for (int j = 0; mp && j < mp->n; ++j) f.sub_keys[j] = mp->keys[j];
+    }
     if (forced && !mp) {
       f.prefix_ids = c->fp_ids;
       f.prefix_len = c->fp_len;
@@ -2491,6 +2569,18 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   if (d_scores) HIPCHK(c->part_sum.reserve(B * (size_t)n_parts * 4));
   float *const part_sum = d_scores ? c->part_sum.as<float>() : nullptr;
   if (forced && mp) return fail(-1, "target prefix: merged launches decode with the persistent kernels only");
+  if (sampled && mp) return fail(-1, "sampling: merged launches decode with the persistent kernels only");
+  SampledStep ss;  // (sampled: the keys, the steps' hash words and the partials beside the arg-max's, kernels.h)
+  if (sampled) {
+    HIPCHK(c->sm_seeds.reserve(2 * B * 4));
+    HIPCHK(c->sm_part_mz.reserve(B * (size_t)n_parts * 4));
+    HIPCHK(c->sm_part_zw.reserve(B * (size_t)n_parts * 4));
+    ss.inv_T = c->sm_inv_T;
+    ss.keys = c->sm_keys;
+    ss.seeds = c->sm_seeds.as<uint32_t>();
+    ss.part_mz = c->sm_part_mz.as<float>();
+    ss.part_zw = c->sm_part_zw.as<float>();
+  }
   ForcedStep fs;  // (forced: the prefix's tokens and their columns, kernels.h)
   if (forced) {
     HIPCHK(c->fp_col.reserve(B * 4));
@@ -2508,7 +2598,7 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   bool all_done = false;
   for (; t < max_steps && !rc; ++t) {
     hipError_t he = launch_decode_begin_step(e, ds, (int)B, t == 0, 1, c->part_val.as<float>(),
-                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs);
+                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs, &ss);
     if (he != hipSuccess) { rc = fail((int)he, "decode_begin_step: %s", hipGetErrorString(he)); break; }
     if (steps_hint <= 0 && t > 0 && (t % 8) == 0) {
       // stop as soon as every sentence has emitted EOS (Model.cc:161)
@@ -2530,15 +2620,23 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     g.part_sum = part_sum;
     g.fcol = fs.fcol;
     g.part_y = fs.ids ? c->fp_part_y.as<float>() : nullptr;
+    if (sampled) {
+      g.fcol = fs.ids ? fs.fcol : nullptr;
+      g.inv_T = ss.inv_T;
+      g.seeds = ss.seeds;
+      g.sm_shortlist = ds.shortlist;
+      g.part_mz = c->sm_part_mz.as<float>();
+      g.part_zw = c->sm_part_zw.as<float>();
+    }
     {
       ProfScope p(c, SLIMT_HIP_K_LOGITS, gemm_macs((int)B, out.w), gemm_bytes(out.w));
-      he = launch_dgemm(g, fs.ids ? EPI_ARGMAX_FP : d_scores ? EPI_ARGMAX_SC : EPI_ARGMAX, st);
+      he = launch_dgemm(g, sampled ? EPI_ARGMAX_SM : fs.ids ? EPI_ARGMAX_FP : d_scores ? EPI_ARGMAX_SC : EPI_ARGMAX, st);
     }
     if (he != hipSuccess) { rc = fail((int)he, "logits gemm: %s", hipGetErrorString(he)); break; }
   }
   if (!rc && !all_done) {
     hipError_t he = launch_decode_begin_step(e, ds, (int)B, 0, 0, c->part_val.as<float>(),
-                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs);
+                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs, &ss);
     if (he != hipSuccess) rc = fail((int)he, "final record: %s", hipGetErrorString(he));
   }
   return rc;
@@ -2624,8 +2722,10 @@ extern "C" int slimt_hip_translate_device(slimt_hip_ctx *ctx, const uint32_t *d_
                                           float *d_align, int steps_hint) {
   ScoreCall sc(ctx, 1);
   PrefixCall pc(ctx, 1);
+  SampleCall smc(ctx, 1);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
+  if (smc.rc) return smc.rc;
   if (!ctx || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len) return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
   if (n_shortlist > (size_t)ctx->model->V) return fail(-1, "shortlist larger than the vocabulary");
@@ -2636,6 +2736,7 @@ extern "C" int slimt_hip_translate_device(slimt_hip_ctx *ctx, const uint32_t *d_
     ctx->fp_ids = ctx->fp_user_ids;
     ctx->fp_len = ctx->fp_user_len;
   }
+  if (ctx->sm_call) ctx->sm_keys = ctx->sm_user_keys;  // (device memory, or NULL)
   return translate_device(ctx, d_src_ids, d_lengths, d_shortlist, B, S, n_shortlist, limit_factor,
                           eos_id, d_out_ids, d_out_len, d_align, steps_hint);
 }
@@ -2680,6 +2781,10 @@ int translate_host(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *
   if (ctx->fp_call) {  // (a forced call: the caller's host prefix, checked and staged in device memory)
     const size_t Bs[1] = {B}, Ts[1] = {Tmax};
     RCCHK(prefix_stage(ctx, 1, &ctx->fp_user_ids, &ctx->fp_user_len, Bs, Ts, &ctx->fp_ids, &ctx->fp_len));
+  }
+  if (ctx->sm_call) {  // (a sampled call: the caller's host keys, pinned in place or staged in device memory)
+    const size_t Bk[1] = {B};
+    RCCHK(keys_stage(ctx, 1, &ctx->sm_user_keys, Bk, &ctx->sm_keys));
   }
   float *const scores = ctx->sc_call ? ctx->sc_user : nullptr;  // (a scored call: the caller's [B][Tmax] host array)
   if (!wait && persistent) {
@@ -2731,8 +2836,10 @@ extern "C" int slimt_hip_translate(slimt_hip_ctx *ctx, const uint32_t *src_ids,
                                    uint32_t *out_len, float *align) {
   ScoreCall sc(ctx, 1);
   PrefixCall pc(ctx, 1);
+  SampleCall smc(ctx, 1);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
+  if (smc.rc) return smc.rc;
   return translate_host(ctx, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, true);
 }
@@ -2744,8 +2851,10 @@ extern "C" int slimt_hip_translate_async(slimt_hip_ctx *ctx, const uint32_t *src
                                          uint32_t *out_len, float *align) {
   ScoreCall sc(ctx, 1);
   PrefixCall pc(ctx, 1);
+  SampleCall smc(ctx, 1);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
+  if (smc.rc) return smc.rc;
   return translate_host(ctx, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, false);
 }
@@ -2849,8 +2958,10 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
                                                float limit_factor, uint32_t eos_id, int steps_hint) {
   ScoreCall sc(ctx, n_batches);
   PrefixCall pc(ctx, n_batches);
+  SampleCall smc(ctx, n_batches);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
+  if (smc.rc) return smc.rc;
   if (!ctx || !batches || n_batches == 0) return fail(-1, "null argument");
   HIPCHK(hipSetDevice(ctx->model->device));
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
@@ -2866,6 +2977,7 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
     mp.prefix_ids[j] = pc.ids[j];
     mp.prefix_len[j] = pc.len[j];
   }
+  for (size_t j = 0; mergeable && ctx->sm_call && j < n_batches; ++j) mp.keys[j] = smc.keys[j];
   if (mergeable && rows <= ctx->max_B && rows * S <= ctx->max_M && S <= ctx->max_S && merge_supported(ctx, rows, S))
     return translate_device(ctx, batches[0].src_ids, batches[0].lengths, batches[0].shortlist, rows, S, (size_t)mp.max_N,
                             limit_factor, eos_id, batches[0].out_ids, batches[0].out_len, batches[0].align, steps_hint, nullptr,
@@ -2877,6 +2989,7 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
       ctx->fp_user_ids = pc.ids[j];
       ctx->fp_user_len = pc.len[j];
     }
+    if (ctx->sm_call) ctx->sm_user_keys = smc.keys[j];
     RCCHK(slimt_hip_translate_device(ctx, b.src_ids, b.lengths, b.B, b.S ? b.S : S, b.shortlist, b.n_shortlist, limit_factor,
                                      eos_id, b.out_ids, b.out_len, b.align, steps_hint));
   }
@@ -2887,8 +3000,10 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
                                               float limit_factor, uint32_t eos_id) {
   ScoreCall sc(ctx, n_batches);
   PrefixCall pc(ctx, n_batches);
+  SampleCall smc(ctx, n_batches);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
+  if (smc.rc) return smc.rc;
   if (!ctx || !batches || n_batches == 0) return fail(-1, "null argument");
   const slimt_hip_model *m = ctx->model;
   HIPCHK(hipSetDevice(m->device));
@@ -2928,6 +3043,7 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
         ctx->fp_user_ids = pc.ids[j];
         ctx->fp_user_len = pc.len[j];
       }
+      if (ctx->sm_call) ctx->sm_user_keys = smc.keys[j];
       RCCHK(translate_host(ctx, b.src_ids, b.lengths, b.B, b.S ? b.S : S, b.shortlist, b.n_shortlist, limit_factor, eos_id,
                            b.out_ids, b.out_len, b.align, false));
     }
@@ -2955,6 +3071,7 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   RCCHK(build_merge_plan(ctx, dev, n_batches, S, Tmax, limit_factor, 0, any_align ? ctx->align.as<float>() : nullptr, mp, rows));
   for (size_t j = 0; ctx->sc_call && j < n_batches; ++j) mp.scores[j] = dev_sc[j];
   if (ctx->fp_call) RCCHK(prefix_stage_batches(ctx, pc, batches, n_batches, S, limit_factor, mp.prefix_ids, mp.prefix_len));
+  if (ctx->sm_call) RCCHK(keys_stage_batches(ctx, smc, batches, n_batches, mp.keys));
   return translate_device(ctx, dev[0].src_ids, dev[0].lengths, dev[0].shortlist, rows, S, (size_t)mp.max_N, limit_factor, eos_id,
                           dev[0].out_ids, dev[0].out_len, any_align ? ctx->align.as<float>() : nullptr, (int)Tmax, nullptr,
                           any_align ? dev[0].align : nullptr, 0, nullptr, &mp);
@@ -3353,8 +3470,10 @@ extern "C" int slimt_hip_translate_device_generated(slimt_hip_ctx *ctx, slimt_hi
                                                     float *d_align, int steps_hint) {
   ScoreCall sc(ctx, 1);
   PrefixCall pc(ctx, 1);
+  SampleCall smc(ctx, 1);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
+  if (smc.rc) return smc.rc;
   if (!ctx || !sl || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len)
     return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
@@ -3368,6 +3487,7 @@ extern "C" int slimt_hip_translate_device_generated(slimt_hip_ctx *ctx, slimt_hi
     ctx->fp_ids = ctx->fp_user_ids;
     ctx->fp_len = ctx->fp_user_len;
   }
+  if (ctx->sm_call) ctx->sm_keys = ctx->sm_user_keys;  // (device memory, or NULL)
   return translate_generated(ctx, sl, d_src_ids, d_lengths, B, S, limit_factor, eos_id, d_out_ids, d_out_len,
                              d_align, steps_hint, nullptr);
 }
@@ -3399,6 +3519,10 @@ int translate_host_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
   if (ctx->fp_call) {  // (translate_host)
     const size_t Bs[1] = {B}, Ts[1] = {Tmax};
     RCCHK(prefix_stage(ctx, 1, &ctx->fp_user_ids, &ctx->fp_user_len, Bs, Ts, &ctx->fp_ids, &ctx->fp_len));
+  }
+  if (ctx->sm_call) {  // (a sampled call: the caller's host keys, pinned in place or staged in device memory)
+    const size_t Bk[1] = {B};
+    RCCHK(keys_stage(ctx, 1, &ctx->sm_user_keys, Bk, &ctx->sm_keys));
   }
   float *const scores = ctx->sc_call ? ctx->sc_user : nullptr;  // (translate_host)
   if (!wait && persistent) {  // pinned buffers: the kernels read and write host memory themselves (translate_host)
@@ -3442,7 +3566,9 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
                              float limit_factor, uint32_t eos_id, int steps_hint, bool stage_align,
                              const slimt_hip_batch *host = nullptr, float *const *sc_dev = nullptr,
                              float *const *sc_host = nullptr, const uint32_t *const *fp_dev_ids = nullptr,
-                             const uint32_t *const *fp_dev_len = nullptr, const PrefixCall *fp_host = nullptr) {
+                             const uint32_t *const *fp_dev_len = nullptr, const PrefixCall *fp_host = nullptr,
+                             const uint64_t *const *sm_dev = nullptr, const SampleCall *sm_host = nullptr) {
+  // sm_dev / sm_host (a sampled call): each batch's keys as the kernels read them and, with `host`, as the caller gave them
   // fp_dev_* / fp_host (a forced call): each batch's prefix in device memory and, with `host`, as the caller gave it
   // sc_dev / sc_host (a scored call): each batch's score destination as the kernels write it (device memory, or the device
   // view of a pinned array) and, with `host`, as the caller gave it
@@ -3472,6 +3598,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
         ctx->fp_user_ids = fp_host->ids[j];
         ctx->fp_user_len = fp_host->len[j];
       }
+      if (ctx->sm_call) ctx->sm_user_keys = sm_host->keys[j];
       RCCHK(translate_host_generated(ctx, sl, b.src_ids, b.lengths, b.B, b.S ? b.S : S, limit_factor, eos_id, b.out_ids, b.out_len,
                                      b.align, false));
     }
@@ -3492,6 +3619,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
         ctx->fp_ids = fp_dev_ids[j];
         ctx->fp_len = fp_dev_len[j];
       }
+      if (ctx->sm_call) ctx->sm_keys = sm_dev[j];
       RCCHK(translate_generated(ctx, sl, b.src_ids, b.lengths, b.B, Sj, limit_factor, eos_id, b.out_ids, b.out_len,
                                 staging ? staging : b.align, steps_hint > 0 ? std::min(steps_hint, (int)Tj) : (stage_align ? (int)Tj : 0),
                                 staging ? b.align : nullptr));
@@ -3516,6 +3644,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
     mp.prefix_ids[j] = fp_dev_ids[j];
     mp.prefix_len[j] = fp_dev_len[j];
   }
+  for (size_t j = 0; ctx->sm_call && j < n; ++j) mp.keys[j] = sm_dev[j];
   ShortlistArgs a;
   shortlist_args(sl, plan[0].src_ids, plan[0].lengths, plan[0].B, S, ctx->shortlist.as<uint32_t>(), ctx->n_sl_dev.as<uint32_t>(), a);
   void *hint_dev = nullptr;
@@ -3541,8 +3670,10 @@ extern "C" int slimt_hip_translate_many_device_generated(slimt_hip_ctx *ctx, sli
                                                          int steps_hint) {
   ScoreCall sc(ctx, n_batches);
   PrefixCall pc(ctx, n_batches);
+  SampleCall smc(ctx, n_batches);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
+  if (smc.rc) return smc.rc;
   if (!ctx || !sl || !batches || n_batches == 0) return fail(-1, "null argument");
   RCCHK(check_generator(ctx, sl));
   for (size_t j = 0; j < n_batches; ++j) {
@@ -3553,15 +3684,17 @@ extern "C" int slimt_hip_translate_many_device_generated(slimt_hip_ctx *ctx, sli
   HIPCHK(hipSetDevice(ctx->model->device));
   return translate_many_generated(ctx, sl, batches, n_batches, S, limit_factor, eos_id, steps_hint, false, nullptr,
                                   ctx->sc_call ? sc.dst.data() : nullptr, nullptr, ctx->fp_call ? pc.ids.data() : nullptr,
-                                  ctx->fp_call ? pc.len.data() : nullptr);
+                                  ctx->fp_call ? pc.len.data() : nullptr, nullptr, ctx->sm_call ? smc.keys.data() : nullptr);
 }
 
 extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const slimt_hip_batch *batches,
                                                         size_t n_batches, size_t S, float limit_factor, uint32_t eos_id) {
   ScoreCall sc(ctx, n_batches);
   PrefixCall pc(ctx, n_batches);
+  SampleCall smc(ctx, n_batches);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
+  if (smc.rc) return smc.rc;
   if (!ctx || !sl || !batches || n_batches == 0) return fail(-1, "null argument");
   RCCHK(check_generator(ctx, sl));
   const slimt_hip_model *m = ctx->model;
@@ -3591,10 +3724,12 @@ extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slim
   }
   const uint32_t *fp_ids[kMaxMerge] = {}, *fp_len[kMaxMerge] = {};  // (forced: the staged prefixes)
   if (pinned && ctx->fp_call) RCCHK(prefix_stage_batches(ctx, pc, batches, n_batches, S, limit_factor, fp_ids, fp_len));
+  const uint64_t *sm_keys[kMaxMerge] = {};  // (sampled: the keys' pinned views or staged copies)
+  if (pinned && ctx->sm_call) RCCHK(keys_stage_batches(ctx, smc, batches, n_batches, sm_keys));
   if (pinned)
     return translate_many_generated(ctx, sl, dev, n_batches, S, limit_factor, eos_id, 0, true, batches,
                                     ctx->sc_call ? dev_sc : nullptr, ctx->sc_call ? sc.dst.data() : nullptr,
-                                    fp_ids, fp_len, &pc);
+                                    fp_ids, fp_len, &pc, sm_keys, &smc);
   for (size_t j = 0; j < n_batches; ++j) {  // pageable arrays, or too many batches: one by one through the copying path
     const slimt_hip_batch &b = batches[j];
     if (ctx->sc_call) ctx->sc_user = sc.dst[j];
@@ -3602,6 +3737,7 @@ extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slim
       ctx->fp_user_ids = pc.ids[j];
       ctx->fp_user_len = pc.len[j];
     }
+    if (ctx->sm_call) ctx->sm_user_keys = smc.keys[j];
     RCCHK(translate_host_generated(ctx, sl, b.src_ids, b.lengths, b.B, b.S ? b.S : S, limit_factor, eos_id, b.out_ids, b.out_len,
                                    b.align, false));
   }
@@ -3613,8 +3749,10 @@ extern "C" int slimt_hip_translate_generated(slimt_hip_ctx *ctx, slimt_hip_short
                                              uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align) {
   ScoreCall sc(ctx, 1);
   PrefixCall pc(ctx, 1);
+  SampleCall smc(ctx, 1);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
+  if (smc.rc) return smc.rc;
   return translate_host_generated(ctx, sl, src_ids, lengths, B, S, limit_factor, eos_id, out_ids, out_len, align, true);
 }
 
@@ -3624,7 +3762,9 @@ extern "C" int slimt_hip_translate_async_generated(slimt_hip_ctx *ctx, slimt_hip
                                                    uint32_t *out_ids, uint32_t *out_len, float *align) {
   ScoreCall sc(ctx, 1);
   PrefixCall pc(ctx, 1);
+  SampleCall smc(ctx, 1);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
+  if (smc.rc) return smc.rc;
   return translate_host_generated(ctx, sl, src_ids, lengths, B, S, limit_factor, eos_id, out_ids, out_len, align, false);
 }

@@ -207,6 +207,16 @@ struct slimt_hip_ctx {
   slimt_hip::DevBuf fp_stage;           // device staging of host prefixes ([B][Tmax] ids, then [B] lengths, per batch)
   slimt_hip::DevBuf fp_scratch;         // score destination of forced calls without scores
   slimt_hip::DevBuf fp_col, fp_part_y;  // the step-wise path's forced columns and captured logits
+  // sampling (include/slimt_hip.h, slimt_hip_ctx_set_sampling): armed for the NEXT translate call, like the scores and the prefix
+  bool sm_armed = false;
+  float sm_next_inv_T = 0.0f;
+  std::vector<const uint64_t *> sm_next_keys;  // one per batch, NULL: the batch's keys are its row indices
+  bool sm_call = false;                      // the call in progress is sampled (engine.cpp, SampleCall)
+  float sm_inv_T = 0.0f;                     // ... at 1 / this temperature
+  const uint64_t *sm_user_keys = nullptr;    // the current batch's keys as the caller gave them (host or device memory, or NULL)
+  const uint64_t *sm_keys = nullptr;         // ... as the kernels read them
+  slimt_hip::DevBuf sm_stage;                // device staging of pageable host keys
+  slimt_hip::DevBuf sm_seeds, sm_part_mz, sm_part_zw;  // the step-wise path's hash words and partials (kernels.h, SampledStep)
   slimt_hip::DevBuf prev, out_ids, out_len, finished, n_finished, align;
   slimt_hip::DevBuf shortlist;
   slimt_hip::DevBuf sl_scratch;  // bitmaps of slimt_hip_shortlist_generate_device (kept zeroed)

@@ -80,6 +80,10 @@ enum GemmEpilogue {
   EPI_ACC = 4,     // raw accS                               -> int32 [M][N]
   EPI_ARGMAX_SC = 5,  // EPI_ARGMAX + each partial's sum of exponentials (DGemmArgs::part_sum; dgemm only)
   EPI_ARGMAX_FP = 6,  // EPI_ARGMAX_SC + each partial's logit of the row's forced column (DGemmArgs::part_y; dgemm only)
+  // sampled (sampling.h; dgemm only): the compared value is key = fmaf(logit, inv_T, noise); the partials carry
+  // (key, column, max z, sum of exp(z - max z), z of the key's column) with z = logit * inv_T, and with a forced column
+  // (DGemmArgs::fcol set) its z in part_y
+  EPI_ARGMAX_SM = 7,
 };
 
 struct GemmArgs {
@@ -184,10 +188,23 @@ struct ForcedStep {
   int *fcol = nullptr;            // [B]
   const float *part_y = nullptr;  // [B][n_parts]
 };
+// The sampled steps of the step-wise path (slimt_hip_ctx_set_sampling; EPI_ARGMAX_SM): part_val holds keys, part_mz /
+// part_zw each partial's maximum of z and the z of its key's column; the block that records a sentence's token also
+// writes the hash words of the sentence's next step (sampling.h, sm_step_words) to seeds[b] / seeds[B + b] for that
+// step's logits gemm. keys == nullptr: sentence b's key is b. Sampled steps need the scores (part_sum / scores); with
+// forced steps as well (ForcedStep), part_y holds z.
+struct SampledStep {
+  float inv_T = 0.0f;              // 0: not sampled
+  const uint64_t *keys = nullptr;  // [B]
+  uint32_t *seeds = nullptr;       // [2][B]
+  const float *part_mz = nullptr;  // [B][n_parts]
+  const float *part_zw = nullptr;  // [B][n_parts]
+};
 hipError_t launch_decode_begin_step(const EmbedArgs &e, const DecodeState &s, int B, int first,
                                     int with_embed, const float *part_val, const int *part_idx,
                                     int n_parts, float *x, hipStream_t st, const float *part_sum = nullptr,
-                                    float *scores = nullptr, const ForcedStep *forced = nullptr);
+                                    float *scores = nullptr, const ForcedStep *forced = nullptr,
+                                    const SampledStep *sampled = nullptr);
 // set prev tokens explicitly (step-wise parity API) and embed
 hipError_t launch_embed_decoder(const EmbedArgs &e, const uint32_t *prev, int B, int first,
                                 float *x, hipStream_t st);
@@ -242,6 +259,13 @@ struct DGemmArgs {
   // partial holds it, else -inf
   const int *fcol = nullptr;
   float *part_y = nullptr;
+  // EPI_ARGMAX_SM: 1 / temperature, the rows' hash words of this step ([2][B], SampledStep::seeds), the output layer's
+  // shortlist (nullptr: the column is the vocabulary id) and the partials beside part_val (keys) / part_sum
+  float inv_T = 0.0f;
+  const uint32_t *seeds = nullptr;
+  const uint32_t *sm_shortlist = nullptr;
+  float *part_mz = nullptr;
+  float *part_zw = nullptr;
 };
 int dgemm_col_blocks(int K, int N, int B);
 hipError_t launch_dgemm(const DGemmArgs &a, int epilogue, hipStream_t st);
@@ -458,6 +482,12 @@ struct FusedDecodeArgs {
   const uint32_t *prefix_len = nullptr;
   const uint32_t *sub_prefix_ids[kMaxMerge] = {};
   const uint32_t *sub_prefix_len[kMaxMerge] = {};
+  // the sampled kernels (decode_fused_kernel<..., SC = true, FP, SM = true>; slimt_hip_ctx_set_sampling): inv_T = 1 /
+  // temperature (0: not sampled), keys [B] the sentences' 64-bit keys (nullptr: sentence b's key is b); merged launches:
+  // sub-batch j's in sub_keys[j] (nullptr: the row in the sub-batch). A sampled launch always scores, like a forced one.
+  float inv_T = 0.0f;
+  const uint64_t *keys = nullptr;
+  const uint64_t *sub_keys[kMaxMerge] = {};
 };
 // hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), but only when
 // `bytes` exceeds what was already set for this kernel on the current device: the call takes

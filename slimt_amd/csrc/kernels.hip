@@ -670,13 +670,109 @@ __global__ __launch_bounds__(64) void decode_begin_step_kernel(EmbedArgs e, Deco
   }
 }
 
+// The sampled twin of decode_begin_step_kernel<true, FP> (kernels.h, SampledStep): part_val holds keys, so the partials'
+// log-sum-exp merges over their own maxima (part_mz), the recorded token's score is log softmax(z) at the drawn column
+// (the winning partial's part_zw) or, at a forced step, at the forced column (part_y holds z), and the block writes the
+// hash words of the sentence's next step -- its count of recorded tokens -- for that step's logits gemm.
+template <bool FP>
+__global__ __launch_bounds__(64) void decode_begin_step_sm_kernel(EmbedArgs e, DecodeState s, int B, int first, int with_embed,
+                                                                  const float *part_val, const int *part_idx, int n_parts,
+                                                                  float *x, const float *part_sum, float *scores, ForcedStep f,
+                                                                  SampledStep sm) {
+  const int b = blockIdx.x;
+  __shared__ uint32_t tok_s;
+  [[maybe_unused]] __shared__ uint32_t next_s;  // FP: the token forced at the next step, 0xffffffff: none
+  [[maybe_unused]] const uint32_t plen = FP ? (f.len[b] < (uint32_t)s.Tmax ? f.len[b] : (uint32_t)s.Tmax) : 0u;
+  if constexpr (FP) {
+    if (first && threadIdx.x == 0) next_s = plen > 0 ? f.ids[(size_t)b * s.Tmax] : 0xffffffffu;
+  }
+  if (!first && threadIdx.x == 0) {
+    // finish the first maximum of the keys: partials are in ascending column order
+    const size_t p0 = (size_t)b * n_parts;
+    float bv = part_val[p0], zw = sm.part_zw[p0];
+    int bi = part_idx[p0];
+    float m = sm.part_mz[p0], sum = part_sum[p0];
+    for (int p = 1; p < n_parts; ++p) {
+      const float v = part_val[p0 + p];
+      lse_merge(m, sum, sm.part_mz[p0 + p], part_sum[p0 + p]);
+      if (v > bv) {
+        bv = v;
+        bi = part_idx[p0 + p];
+        zw = sm.part_zw[p0 + p];
+      }
+    }
+    const bool none = bi == 0x7fffffff || (s.pb0 && (*s.pb0 != *s.pb0 || s.u_out != s.u_out));
+    if (bi == 0x7fffffff) bi = 0;  // no key beat the start value: class 0, never out of range
+    if (s.pb0 && (*s.pb0 != *s.pb0 || s.u_out != s.u_out)) bi = 0;  // logit[0] is NaN: class 0
+    [[maybe_unused]] bool forced = false;
+    uint32_t tok = s.shortlist ? s.shortlist[bi] : (uint32_t)bi;
+    if constexpr (FP) {
+      if (!s.finished[b] && s.out_len[b] < plen) {
+        forced = true;
+        tok = f.ids[(size_t)b * s.Tmax + s.out_len[b]];
+      }
+    }
+    s.prev[b] = tok;
+    if (!s.finished[b]) {  // record(), Model.cc:127-137
+      const uint32_t n = s.out_len[b];
+      float d = zw - m;
+      if constexpr (FP) {
+        if (forced) {
+          float y = -__builtin_inff();  // the forced column's z: in at most one partial
+          for (int p = 0; p < n_parts; ++p) y = fmaxf(y, f.part_y[p0 + p]);
+          d = y - m;
+        }
+      }
+      if ((int)n < s.Tmax) scores[(size_t)b * s.Tmax + n] = forced_score(sum, d, none);
+      if ((int)n < s.Tmax) s.out_ids[(size_t)b * s.Tmax + n] = tok;
+      s.out_len[b] = n + 1;
+      if (tok == s.eos) {
+        s.finished[b] = 1;
+        atomicAdd(s.n_finished, 1);
+      }
+    }
+    tok_s = tok;
+    if constexpr (FP) next_s = !s.finished[b] && s.out_len[b] < plen ? f.ids[(size_t)b * s.Tmax + s.out_len[b]] : 0xffffffffu;
+  }
+  if (threadIdx.x == 0) {  // (after the record above: the sentence's count of recorded tokens is its next step)
+    const uint64_t w = sm_step_words(sm.keys ? sm.keys[b] : (uint64_t)b, first ? 0u : s.out_len[b]);
+    sm.seeds[b] = (uint32_t)w;
+    sm.seeds[B + b] = (uint32_t)(w >> 32);
+  }
+  __syncthreads();
+  if constexpr (FP) {
+    const int col = forced_column(f.sl, f.N, next_s, threadIdx.x);
+    if (threadIdx.x == 0) f.fcol[b] = col;
+  }
+  if (!with_embed) return;
+  if (first) {
+    for (int d = threadIdx.x; d < e.D; d += 64) {
+      const float z = 0.0f * e.sqrt_d;
+      x[(size_t)b * e.D + d] = z + e.pos[d];
+    }
+  } else {
+    const uint32_t tok = tok_s;
+    for (int d = threadIdx.x; d < e.D; d += 64) x[(size_t)b * e.D + d] = embed1(e, tok, d, e.pos);
+  }
+}
+
 hipError_t launch_decode_begin_step(const EmbedArgs &e, const DecodeState &s, int B, int first,
                                     int with_embed, const float *part_val, const int *part_idx,
                                     int n_parts, float *x, hipStream_t st, const float *part_sum,
-                                    float *scores, const ForcedStep *forced) {
+                                    float *scores, const ForcedStep *forced, const SampledStep *sampled) {
   if ((part_sum != nullptr) != (scores != nullptr)) return hipErrorInvalidValue;
   const ForcedStep fs = forced ? *forced : ForcedStep{};
   if (fs.ids && (!scores || !fs.len || !fs.fcol || !fs.part_y)) return hipErrorInvalidValue;
+  if (sampled && sampled->inv_T != 0.0f) {
+    if (!scores || !sampled->seeds || !sampled->part_mz || !sampled->part_zw) return hipErrorInvalidValue;
+    if (fs.ids)
+      hipLaunchKernelGGL(decode_begin_step_sm_kernel<true>, dim3(B), dim3(64), 0, st, e, s, B, first, with_embed, part_val,
+                         part_idx, n_parts, x, part_sum, scores, fs, *sampled);
+    else
+      hipLaunchKernelGGL(decode_begin_step_sm_kernel<false>, dim3(B), dim3(64), 0, st, e, s, B, first, with_embed, part_val,
+                         part_idx, n_parts, x, part_sum, scores, fs, *sampled);
+    return hipGetLastError();
+  }
   if (fs.ids)
     hipLaunchKernelGGL((decode_begin_step_kernel<true, true>), dim3(B), dim3(64), 0, st, e, s, first, with_embed,
                        part_val, part_idx, n_parts, x, part_sum, scores, fs);

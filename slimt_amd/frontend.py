@@ -217,14 +217,18 @@ class Service:
         step = self.ENGINE_LIMIT - 1
         return [body[i:i + step] + [eos] for i in range(0, len(body), step)]
 
-    def _engine(self, model: Model, scores: bool = False) -> "capi.BatchService":
+    def _engine(self, model: Model, scores: bool = False, temperature: float = 0.0) -> "capi.BatchService":
         """The C++ batching service for `model` (host/Service.{hh,cc} behind include/slimt_hip_service.h):
         token-budget batches under the rule of _batches, `workers` double-buffered workers with pinned
         staging, the batch's lexical shortlist generated on the device (Model.cc:117-120). Units,
         batches, padding and result routing used to be Python objects; they are C++ now, and one call
-        carries a whole translate(). A scoring service is one of its own (scores are set before its first call)."""
+        carries a whole translate(). A scoring service is one of its own (scores are set before its first call), and so
+        is a sampling one for each temperature: the temperature is a service-wide setting of the C++ service, so every
+        distinct temperature a caller uses keeps its own service -- workers, contexts and pinned staging -- until close().
+        None is evicted before that (another thread's call may be in flight on it): a caller that sweeps temperatures
+        closes the Service between them, or uses capi.Context.set_sampling, where the temperature is per call."""
         with self._lock:
-            eng = self._engines.get((model.id, scores))
+            eng = self._engines.get((model.id, scores, float(temperature)))
             if eng is None:
                 V = model.dims[2]
                 eng = capi.BatchService([model.engine], max_words=max(self.max_words, 1),
@@ -233,12 +237,13 @@ class Service:
                                         eos_id=model.vocabulary.eos_id(), alignments=True,
                                         lexical_shortlist=model.shortlist_blob, source_vocab=V, target_vocab=V,
                                         shared_vocab=False, check=False,  # as Model.cc:73-80 constructs it
-                                        scores=scores)
-                self._engines[(model.id, scores)] = eng
+                                        scores=scores, temperature=float(temperature))
+                self._engines[(model.id, scores, float(temperature))] = eng
         return eng
 
-    def _translate_segments(self, model: Model, per_request: List[List[List[int]]], scores: bool = False):
-        """per request, per segment: (target ids, alignment, token scores | None)"""
+    def _translate_segments(self, model: Model, per_request: List[List[List[int]]], scores: bool = False, sampling=None):
+        """per request, per segment: (target ids, alignment, token scores | None). sampling: (temperature, seed) -- one
+        draw per segment under capi.sampling_key(seed, the segment's index in this call's flat list)"""
         eos = model.vocabulary.eos_id()
         flat, owner = [], []  # the sentences of the one request the C++ service gets; (request, index, piece)
         pieces_of = {}
@@ -260,7 +265,10 @@ class Service:
         histories = [[None] * len(segs) for segs in per_request]
         if not flat:
             return histories
-        res = self._engine(model, scores).translate(flat)
+        if sampling is not None:
+            res = self._engine(model, scores, sampling[0]).translate(flat, seed=int(sampling[1]))
+        else:
+            res = self._engine(model, scores).translate(flat)
         targets, t_off = res.targets.copy(), res.target_offsets.astype(np.int64)
         tok_sc = res.scores.copy() if scores else None
         align, a_off = res.alignments.copy(), res.align_offsets.astype(np.int64)
@@ -348,9 +356,14 @@ class Service:
         return out
 
     def translate(self, model: Model, texts: Sequence[str], html: bool = False,
-                  encoding: Encoding = Encoding.UTF8, scores: bool = False) -> List[Response]:
+                  encoding: Encoding = Encoding.UTF8, scores: bool = False, sampling=None) -> List[Response]:
         """scores: every Response also carries token_scores (per target sentence, each target token's log-probability,
-        EOS included; a wrapped segment's pieces concatenated) and sentence_scores (their sums)."""
+        EOS included; a wrapped segment's pieces concatenated) and sentence_scores (their sums).
+        sampling: (temperature, seed) -- each sentence is one draw from the model at that temperature instead of the
+        greedy translation, reproducible for a seed: the key of a segment is capi.sampling_key(seed, its index among the
+        call's segments), so the same call gives the same text whatever the batcher does; with scores=True the scores are
+        the draws' log-probabilities at that temperature. A sampled call goes to the engine as one request. Every
+        distinct temperature keeps a batching service of its own until close() (_engine)."""
         if html:
             raise NotImplementedError("HTML markup transfer is outside the ported path (SURVEY.md §2)")
         # Large calls go through in chunks of documents, pipelined: while the engine translates chunk k
@@ -358,9 +371,9 @@ class Service:
         # assembles the responses of chunk k - 1. Batches are formed per chunk (as they are per
         # arrival window in the reference's Async service).
         chunk = self.pipeline_documents
-        if len(texts) <= chunk:
+        if len(texts) <= chunk or sampling is not None:  # (sampled: one request, so that the segments' indices are the call's)
             processed = model.processor.process_many(texts, self.wrap_length, self.workers)
-            histories = self._translate_segments(model, [segs for _, segs in processed], scores)
+            histories = self._translate_segments(model, [segs for _, segs in processed], scores, sampling)
             out = self._respond_many(model, [src for src, _ in processed], histories)
         else:
             from concurrent.futures import ThreadPoolExecutor
@@ -382,15 +395,17 @@ class Service:
         return out
 
     def pivot(self, first: Model, second: Model, texts: Sequence[str], html: bool = False,
-              scores: bool = False) -> List[Response]:
-        """source -> pivot with `first`, pivot -> target with `second`, sentence for sentence;
+              scores: bool = False, sampling=None) -> List[Response]:
+        """sampling: (temperature, seed) -- both hops sample, the first under seed and the second under seed + 1.
+        source -> pivot with `first`, pivot -> target with `second`, sentence for sentence;
         alignments are marginalised over the pivot tokens (Response.cc:13-195). scores: the SECOND hop's scores --
         those of the final target tokens given the pivot text (the pivot's own probability is not in them)."""
         if html:
             raise NotImplementedError("HTML markup transfer is outside the ported path (SURVEY.md §2)")
-        firsts = self.translate(first, texts, encoding=Encoding.Byte)
+        firsts = self.translate(first, texts, encoding=Encoding.Byte, sampling=sampling)
         second_in = [second.processor.process_annotated(r.target) for r in firsts]
-        histories = self._translate_segments(second, [segs for _, segs in second_in], scores)
+        histories = self._translate_segments(second, [segs for _, segs in second_in], scores,
+                                             None if sampling is None else (sampling[0], int(sampling[1]) + 1))
         seconds = self._respond_many(second, [src for src, _ in second_in], histories)
         return [combine(r1, r2) for r1, r2 in zip(firsts, seconds)]
 

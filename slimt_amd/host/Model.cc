@@ -198,6 +198,18 @@ void Worker::arm_prefix(const uint32_t *const *ids, const uint32_t *const *len, 
   if (slimt_hip_ctx_set_target_prefix(ctx_, ids, len, n)) raise("slimt_hip_ctx_set_target_prefix");
 }
 
+#pragma weak slimt_hip_ctx_set_sampling
+#pragma weak slimt_hip_sampling_key
+void Worker::arm_sampling(float temperature, const uint64_t *const *keys, size_t n) {
+  if (!slimt_hip_ctx_set_sampling) throw std::runtime_error("this engine has no sampling");
+  if (slimt_hip_ctx_set_sampling(ctx_, temperature, keys, n)) raise("slimt_hip_ctx_set_sampling");
+}
+
+uint64_t Worker::sampling_key(uint64_t seed, uint64_t index) {
+  if (!slimt_hip_sampling_key) throw std::runtime_error("this engine has no sampling");
+  return slimt_hip_sampling_key(seed, index);
+}
+
 void Worker::wait() {
   if (slimt_hip_ctx_synchronize(ctx_)) raise("slimt_hip_ctx_synchronize");
 }

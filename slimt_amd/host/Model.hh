@@ -168,6 +168,10 @@ class Worker {
   // ... forces target prefixes: ids[j] = [B_j][T_j], len[j] = [B_j] of batch j, in pinned memory that the kernels read in
   // place (slimt_hip_ctx_set_target_prefix)
   void arm_prefix(const uint32_t *const *ids, const uint32_t *const *len, size_t n);
+  // ... samples at `temperature` under keys[j] = [B_j] per-sentence keys of batch j, in pinned memory
+  // (slimt_hip_ctx_set_sampling); sampling_key: slimt_hip_sampling_key
+  void arm_sampling(float temperature, const uint64_t *const *keys, size_t n);
+  static uint64_t sampling_key(uint64_t seed, uint64_t index);
   void wait();
 
  private:

@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <future>
@@ -13,8 +14,8 @@ namespace slimt {
 
 // ---- Pending -----------------------------------------------------------------
 
-Pending::Pending(std::vector<Words> sentences, std::vector<Words> prefixes)
-    : sentences_(std::move(sentences)), prefixes_(std::move(prefixes)), results_(sentences_.size()), left_(sentences_.size()) {
+Pending::Pending(std::vector<Words> sentences, std::vector<Words> prefixes, uint64_t seed)
+    : sentences_(std::move(sentences)), prefixes_(std::move(prefixes)), seed_(seed), results_(sentences_.size()), left_(sentences_.size()) {
   if (sentences_.empty()) {
     settled_ = true;
     promise_.set_value({});
@@ -144,6 +145,7 @@ struct Service::Slot {
   Pinned<uint32_t> ids, lengths, out_ids, out_len, shortlist;
   Pinned<float> align, scores;
   Pinned<uint32_t> prefix_ids, prefix_len;  // forced launches: like out_ids / lengths (read in place by the kernels)
+  Pinned<uint64_t> keys;                    // sampled launches: one key per sentence, like lengths
   std::vector<Unit> batch;  // non-empty while a translate is in flight on this slot
   uint64_t serial = 0;
   // `batch` is the concatenation of the launch's batches (one, or several merged: ServiceConfig::merge_batches), each with
@@ -244,9 +246,20 @@ bool Service::set_scores(bool on) {
   return true;
 }
 
-std::future<Histories> Service::translate(std::vector<Words> sentences) { return translate(std::move(sentences), {}); }
+bool Service::set_sampling(float temperature) {
+  std::lock_guard<std::mutex> lock(mutex_);  // (like set_scores)
+  if (sequence_ > 0 || !(temperature >= 0.0f) || !std::isfinite(temperature)) return false;
+  config_.temperature = temperature;
+  return true;
+}
+
+std::future<Histories> Service::translate(std::vector<Words> sentences) { return translate(std::move(sentences), {}, 0); }
 
 std::future<Histories> Service::translate(std::vector<Words> sentences, std::vector<Words> prefixes) {
+  return translate(std::move(sentences), std::move(prefixes), 0);
+}
+
+std::future<Histories> Service::translate(std::vector<Words> sentences, std::vector<Words> prefixes, uint64_t seed) {
   if (!prefixes.empty()) {
     if (prefixes.size() != sentences.size())
       throw std::invalid_argument(std::to_string(prefixes.size()) + " prefixes for " + std::to_string(sentences.size()) + " sentences");
@@ -264,7 +277,7 @@ std::future<Histories> Service::translate(std::vector<Words> sentences, std::vec
       throw std::invalid_argument("sentence of " + std::to_string(s.size()) + " tokens: longer than " +
                                   std::to_string(longest_) + " (wrap it first)");
   }
-  auto pending = std::make_shared<Pending>(std::move(sentences), std::move(prefixes));
+  auto pending = std::make_shared<Pending>(std::move(sentences), std::move(prefixes), seed);
   std::future<Histories> result = pending->future();
   if (pending->size() == 0) return result;
   if (pending->size() >= (1u << 24)) throw std::invalid_argument("request of more than 2^24 sentences");
@@ -413,6 +426,19 @@ void Service::launch(Slot &slot, std::vector<Unit> &batch, slimt_hip_shortlist *
       dl[j] = p_len + p.first;
     }
     slot.worker->arm_prefix(di.data(), dl.data(), di.size());
+  }
+  if (config_.temperature > 0.0f) {  // sampled: every sentence under the key of its place in its own request
+    uint64_t *keys = slot.keys.ensure(B);
+    std::vector<const uint64_t *> dk(slot.parts.size());
+    for (size_t j = 0; j < slot.parts.size(); ++j) {
+      const Slot::Part &p = slot.parts[j];
+      for (size_t b = 0; b < p.B; ++b) {
+        const Unit &u = slot.batch[p.first + b];
+        keys[p.first + b] = Worker::sampling_key(u.owner->seed(), u.index);
+      }
+      dk[j] = keys + p.first;
+    }
+    slot.worker->arm_sampling(config_.temperature, dk.data(), dk.size());
   }
   if (generator && slot.parts.size() == 1) {  // the batch's own lexical shortlist, generated on the worker's stream (Model.cc:117-120)
     slot.worker->forward_async_generated(generator, ids, lengths, B, p0.S, config_.tgt_length_limit_factor, out_ids,

@@ -40,12 +40,14 @@ namespace slimt {
 // the promise that is fulfilled by whichever worker delivers the last one.
 class Pending {
  public:
-  explicit Pending(std::vector<Words> sentences, std::vector<Words> prefixes = {});
+  explicit Pending(std::vector<Words> sentences, std::vector<Words> prefixes = {}, uint64_t seed = 0);
   size_t size() const { return sentences_.size(); }
   const Words &sentence(size_t i) const { return sentences_[i]; }
   // sentence i's forced target prefix (empty: none; Service::translate with prefixes)
   bool has_prefixes() const { return !prefixes_.empty(); }
   const Words &prefix(size_t i) const { return prefixes_[i]; }
+  // the request's sampling seed (a sampling service: sentence i's key is slimt_hip_sampling_key(seed, i))
+  uint64_t seed() const { return seed_; }
   std::future<Histories> future() { return promise_.get_future(); }
   void deliver(size_t i, History history);   // thread-safe; the last delivery fulfils the promise
   void fail(const std::exception_ptr &error);  // first failure wins; later deliveries are dropped
@@ -53,6 +55,7 @@ class Pending {
  private:
   std::vector<Words> sentences_;
   std::vector<Words> prefixes_;  // empty, or one per sentence
+  uint64_t seed_ = 0;
   Histories results_;
   std::atomic<size_t> left_;
   std::atomic<bool> settled_{false};
@@ -117,6 +120,7 @@ struct ServiceConfig {
   bool alignments = true;
   bool flat_alignments = false;  // Hypothesis::alignment_flat instead of ::alignment (one block per sentence)
   bool scores = false;           // Hypothesis::scores: every target token's log-probability (Service::set_scores)
+  float temperature = 0.0f;      // > 0: every launch samples at this temperature (Service::set_sampling); 0: greedy
   // Output vocabulary of a batch, one policy for the service's lifetime:
   //  * lexical_shortlist set: the reference's own -- ShortlistGenerator::generate on every batch's
   //    source words (Model.cc:60-82,117-120; Shortlist.cc:115-175) -- run on the device, on the
@@ -148,8 +152,14 @@ class Service {
   // empty prefix: none). Throws std::invalid_argument for a count that differs from the sentences' or a prefix longer
   // than max(1, (size_t)(limit factor * the sentence's length)).
   std::future<Histories> translate(std::vector<Words> sentences, std::vector<Words> prefixes);
+  // ... on a sampling service (set_sampling) under this seed: sentence i is drawn under slimt_hip_sampling_key(seed, i),
+  // wherever the batcher puts it (the other overloads use seed 0); prefixes may be empty
+  std::future<Histories> translate(std::vector<Words> sentences, std::vector<Words> prefixes, uint64_t seed);
   // per-token scores on or off (ServiceConfig::scores): only before the first translate(); false once one has been made
   bool set_scores(bool on);
+  // temperature sampling for every request (include/slimt_hip.h, slimt_hip_ctx_set_sampling; 0: greedy again): only before
+  // the first translate(); false once one has been made, or for a temperature that is not finite and >= 0
+  bool set_sampling(float temperature);
   // restart the SLIMT_SERVICE_STATS counters (benchmarks: after the warm-up pass)
   void stats_reset() {
     stats_base_ = batches_.load();

@@ -1,5 +1,6 @@
 // extern "C" face of host/Service (include/slimt_hip_service.h).
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +12,7 @@
 #include "Service.hh"
 #include "slimt_hip_service.h"
 #include "slimt_hip_service_prefix.h"
+#include "slimt_hip_service_sampling.h"
 #include "slimt_hip_service_scores.h"
 
 namespace {
@@ -28,6 +30,7 @@ struct slimt_hip_service {
   std::vector<std::unique_ptr<slimt::Model>> models;  // non-owning views of the caller's replicas
   std::unique_ptr<slimt::Service> service;
   bool scores = false;  // slimt_hip_service_set_scores
+  float temperature = 0.0f;  // slimt_hip_service_set_sampling
 };
 
 struct slimt_hip_result {
@@ -89,7 +92,7 @@ extern "C" int slimt_hip_service_destroy(slimt_hip_service *service) {
 namespace {
 // slimt_hip_service_translate[_prefixed]: prefix_tokens / prefix_offsets NULL = no prefixes
 int translate(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets, const uint32_t *prefix_tokens,
-              const uint64_t *prefix_offsets, size_t n, slimt_hip_result **out) {
+              const uint64_t *prefix_offsets, size_t n, slimt_hip_result **out, uint64_t seed = 0) {
   *out = nullptr;
   try {
     const auto t0 = std::chrono::steady_clock::now();
@@ -104,7 +107,7 @@ int translate(slimt_hip_service *service, const uint32_t *tokens, const uint64_t
       }
     }
     const auto t1 = std::chrono::steady_clock::now();
-    slimt::Histories hs = service->service->translate(std::move(sentences), std::move(prefixes)).get();
+    slimt::Histories hs = service->service->translate(std::move(sentences), std::move(prefixes), seed).get();
     const auto t2 = std::chrono::steady_clock::now();
     auto r = std::make_unique<slimt_hip_result>();
     r->target_offsets.assign(n + 1, 0);
@@ -185,6 +188,25 @@ extern "C" int slimt_hip_service_set_scores(slimt_hip_service *service, int on) 
   if (!service->service->set_scores(on != 0)) return fail("set_scores: only before the first slimt_hip_service_translate");
   service->scores = on != 0;
   return 0;
+}
+
+extern "C" int slimt_hip_service_set_sampling(slimt_hip_service *service, float temperature) {
+  if (!service) return fail("null argument");
+  if (!(temperature > 0.0f) || !std::isfinite(temperature)) return fail("set_sampling: temperature %g is not finite and > 0", (double)temperature);
+  if (!service->service->set_sampling(temperature)) return fail("set_sampling: only before the first slimt_hip_service_translate");
+  service->temperature = temperature;
+  return 0;
+}
+
+extern "C" int slimt_hip_service_translate_sampled(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets,
+                                                   const uint32_t *prefix_tokens, const uint64_t *prefix_offsets, uint64_t seed,
+                                                   size_t n, slimt_hip_result **out) {
+  if (!service || !out || (n && (!tokens || !offsets)) ||
+      (n && prefix_offsets && prefix_offsets[n] > prefix_offsets[0] && !prefix_tokens))
+    return fail("null argument");
+  if (!(service->temperature > 0.0f))
+    return fail("translate_sampled: the service does not sample (slimt_hip_service_set_sampling)");
+  return translate(service, tokens, offsets, prefix_tokens, prefix_offsets, n, out, seed);
 }
 
 extern "C" int slimt_hip_result_scores(const slimt_hip_result *r, const float **scores) {
