@@ -540,6 +540,51 @@ int slimt_hip_translate_many_device_generated(slimt_hip_ctx *ctx, slimt_hip_shor
 int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const slimt_hip_batch *batches,
                                              size_t n_batches, size_t S, float limit_factor, uint32_t eos_id);
 
+/* ---- teacher-forced scoring: every target position in one pass ------------- */
+/* Scores GIVEN targets tgt_ids [B][T] with lengths tgt_len [B] (n_b = tgt_len[b] <= T) against a source batch, and
+ * optionally aligns them. With the targets known the decoder is position-parallel: the B x T rows go through the
+ * decoder weights as one tall batch (the SSRU is an elementwise scan over t; everything else is row-wise), where the
+ * forced-prefix path (slimt_hip_ctx_set_target_prefix) runs the persistent decoder step by step. For every t < n_b:
+ *   - row (b, t)'s decoder input is the zero embedding at t = 0, else tgt_ids[b][t - 1] at position 0;
+ *   - scores[b][t] is the natural-log softmax probability of tgt_ids[b][t] over the output layer (the shortlist's
+ *     columns, or the full vocabulary when n_shortlist == 0), as slimt_hip_ctx_set_scores defines it: -inf for a token
+ *     the layer does not hold (it is still fed to row t + 1), NaN for a row whose logits hold a NaN;
+ *   - align[b][t][j], j < lengths[b] (align nullable, [B][T][S]), is head 0 of the last decoder layer (Model.cc:84-108).
+ * Nothing stops at EOS: an EOS inside the target is a token like any other. Through the first EOS, and for n_b <=
+ * max(1, limit_factor * S), the results are those of the forced-prefix call with the same prefix. There is no such cap
+ * here: T is the caller's. Entries with t >= n_b and alignment columns j >= lengths[b] are NOT written.
+ * Arithmetic: the PORTABLE contract; every hidden row and alignment row equals the step-wise decoder's bit for bit, and
+ * a sentence's results do not depend on its place in the batch or on the batch around it.
+ * The K/V cache format (slimt_hip_model_set_kv_cache_format) concerns the persistent decoder's packed cache only: these
+ * calls always attend over the f32 float(accS) cache in the hoisted order. A model set to format 3 (the literal order)
+ * is REFUSED with a message, not scored in another order.
+ * Score calls are not translate calls: options armed with slimt_hip_ctx_set_scores / _set_target_prefix / _set_sampling
+ * are neither used nor consumed by them.
+ * Limits: B <= max_batch, S <= max_source_length, 1 <= T <= 65536, B * T <= 2^24. The workspace for the rows (18 D + F
+ * + 4 bytes each) is allocated on a context's first scoring call and grows when a later call needs more (the
+ * context is synchronised before the old block is freed); rows are processed in chunks of whole sentences of at most
+ * max(T, 8192) rows, and results do not depend on the chunking.
+ * slimt_hip_score waits for the result. slimt_hip_score_async queues the work on ctx's stream: pinned ids / lengths /
+ * targets are read in place and pinned scores written in place; other arrays are bracketed by copies on the stream (the
+ * copies back restore what the call does not write) and must stay valid until slimt_hip_ctx_synchronize. Host entry points
+ * check lengths[b] <= S, tgt_len[b] <= T and every id (source, target below tgt_len, shortlist) against the vocabulary.
+ * slimt_hip_score_device takes device pointers and is asynchronous on ctx's stream; device arrays cannot be checked: a
+ * tgt_len[b] > T is taken as T, a lengths[b] > S as S, and an id past the embedding table reads its last row (that
+ * sentence alone is undefined). slimt_hip_score_async_generated generates the batch's lexical shortlist on the device
+ * first (one 4-byte read-back sizes the output layer, as with the stage kernels of _translate_generated). */
+int slimt_hip_score(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                    const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids, const uint32_t *tgt_len,
+                    size_t T, float *scores, float *align);
+int slimt_hip_score_async(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                          const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids,
+                          const uint32_t *tgt_len, size_t T, float *scores, float *align);
+int slimt_hip_score_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids, const uint32_t *d_lengths, size_t B, size_t S,
+                           const uint32_t *d_shortlist, size_t n_shortlist, const uint32_t *d_tgt_ids,
+                           const uint32_t *d_tgt_len, size_t T, float *d_scores, float *d_align);
+int slimt_hip_score_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *shortlist, const uint32_t *src_ids,
+                                    const uint32_t *lengths, size_t B, size_t S, const uint32_t *tgt_ids,
+                                    const uint32_t *tgt_len, size_t T, float *scores, float *align);
+
 
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, HIP events bracket every launch of kernel family `kernel_id`

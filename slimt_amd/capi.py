@@ -40,6 +40,7 @@ SYMBOLS = [
     "slimt_hip_translate_many_rows", "slimt_hip_translate_many_device", "slimt_hip_translate_many_async",
     "slimt_hip_debug_kv_recalibrations", "slimt_hip_translate_many_device_generated", "slimt_hip_translate_many_async_generated",
     "slimt_hip_ctx_set_scores", "slimt_hip_ctx_set_target_prefix", "slimt_hip_ctx_set_sampling", "slimt_hip_sampling_key",
+    "slimt_hip_score", "slimt_hip_score_async", "slimt_hip_score_device", "slimt_hip_score_async_generated",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -256,6 +257,10 @@ def lib():
     L.slimt_hip_translate_many_async.argtypes = [vp, vp, sz, sz, f32, u32]
     L.slimt_hip_translate_many_device_generated.argtypes = [vp, vp, vp, sz, sz, f32, u32, i32]
     L.slimt_hip_translate_many_async_generated.argtypes = [vp, vp, vp, sz, sz, f32, u32]
+    L.slimt_hip_score.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp]
+    L.slimt_hip_score_async.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp]
+    L.slimt_hip_score_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp]
+    L.slimt_hip_score_async_generated.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, sz, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("slimt_hip_abi_version",):
@@ -787,6 +792,75 @@ class Context:
         self._prefix_keep = []  # (a blocking call: done with its prefix)
         return (out_ids, out_len, align, sc) if scores else (out_ids, out_len, align)
 
+    @staticmethod
+    def _score_host(ids, lengths, tgt_ids, tgt_len):
+        """(ids [B,S], lengths [B], tgt_ids [B,T], tgt_len [B]) as C-contiguous uint32 arrays (shapes checked)"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        tgt_ids = np.ascontiguousarray(tgt_ids, dtype=np.uint32)
+        tgt_len = np.ascontiguousarray(tgt_len, dtype=np.uint32)
+        if ids.ndim != 2 or tgt_ids.ndim != 2:
+            raise ValueError("score: ids [B, S] and tgt_ids [B, T] expected")
+        B = ids.shape[0]
+        if lengths.shape != (B,) or tgt_ids.shape[0] != B or tgt_len.shape != (B,):
+            raise ValueError("score: %d sentences, but lengths %s, tgt_ids %s, tgt_len %s"
+                             % (B, lengths.shape, tgt_ids.shape, tgt_len.shape))
+        return ids, lengths, tgt_ids, tgt_len
+
+    def score(self, ids, lengths, shortlist, tgt_ids, tgt_len, want_align: bool = False, fill=np.nan):
+        """slimt_hip_score: teacher-forced scoring of given targets in one pass over all target positions. tgt_ids [B,T],
+        tgt_len [B] (<= T; T is the caller's, there is no limit_factor cap). Returns scores [B,T] float32 -- the natural-log
+        softmax probability of tgt_ids[b,t] for t < tgt_len[b], -inf for a token outside the shortlist -- and align [B,T,S]
+        (head 0 of the last decoder layer) or None. Entries the call does not write (t >= tgt_len[b], alignment columns
+        j >= lengths[b]) keep `fill`. Blocking; nothing armed on the context is used or consumed."""
+        ids, lengths, tgt_ids, tgt_len = self._score_host(ids, lengths, tgt_ids, tgt_len)
+        (B, S), T = ids.shape, tgt_ids.shape[1]
+        sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
+        sc = np.full((B, T), fill, dtype=np.float32)
+        align = np.full((B, T, S), fill, dtype=np.float32) if want_align else None
+        _chk(lib().slimt_hip_score(self.h, _p(ids), _p(lengths), B, S, _p(sl), 0 if sl is None else sl.size,
+                                   _p(tgt_ids), _p(tgt_len), T, _p(sc), _p(align)))
+        return sc, align
+
+    def score_buffers(self, B: int, S: int, T: int, want_align: bool = False):
+        """This context's pinned arrays for score_async: (ids [B,S], lengths [B], tgt_ids [B,T], tgt_len [B],
+        scores [B,T], align [B,T,S] | None)."""
+        pin = lambda name: self._pinned.setdefault(name, _Pinned())
+        return (pin("ids").array(np.uint32, (B, S)), pin("len").array(np.uint32, (B,)),
+                pin("tg").array(np.uint32, (B, T)), pin("tl").array(np.uint32, (B,)),
+                pin("sc").array(np.float32, (B, T)), pin("al").array(np.float32, (B, T, S)) if want_align else None)
+
+    def score_async(self, bufs, shortlist=None, generator=None):
+        """slimt_hip_score_async[_generated] on (ids, lengths, tgt_ids, tgt_len, scores, align | None) host arrays (already
+        filled; those of score_buffers() are pinned: read and, the scores, written in place); synchronize() before reading
+        the outputs, and keep the arrays alive until then. generator: a ShortlistGenerator -- the batch's lexical shortlist."""
+        ids, lengths, tgt_ids, tgt_len, sc, align = bufs
+        for a, dt in ((ids, np.uint32), (lengths, np.uint32), (tgt_ids, np.uint32), (tgt_len, np.uint32), (sc, np.float32)):
+            if a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError("score_async: C-contiguous uint32 inputs and float32 scores expected")
+        if ids.ndim != 2 or tgt_ids.ndim != 2:
+            raise ValueError("score_async: ids [B, S] and tgt_ids [B, T] expected")
+        (B, S), T = ids.shape, tgt_ids.shape[1]
+        if lengths.shape != (B,) or tgt_ids.shape[0] != B or tgt_len.shape != (B,) or sc.shape != (B, T):
+            raise ValueError("score_async: mismatched shapes")
+        if align is not None and (align.dtype != np.float32 or align.shape != (B, T, S) or not align.flags.c_contiguous):
+            raise ValueError("score_async: a C-contiguous float32 align of shape %s expected" % ((B, T, S),))
+        if generator is not None:
+            _chk(lib().slimt_hip_score_async_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, _p(tgt_ids),
+                                                       _p(tgt_len), T, _p(sc), _p(align)))
+            return
+        sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
+        _chk(lib().slimt_hip_score_async(self.h, _p(ids), _p(lengths), B, S, _p(sl), 0 if sl is None else sl.size,
+                                         _p(tgt_ids), _p(tgt_len), T, _p(sc), _p(align)))
+
+    def score_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int, n_shortlist: int,
+                     d_tgt_ids: int, d_tgt_len: int, T: int, d_scores: int, d_align: int = 0):
+        """slimt_hip_score_device: device pointers (ints) in and out, asynchronous on this context's stream."""
+        vp = C.c_void_p
+        _chk(lib().slimt_hip_score_device(self.h, vp(d_ids), vp(d_lengths), B, S, vp(d_shortlist) if n_shortlist else None,
+                                          n_shortlist, vp(d_tgt_ids), vp(d_tgt_len), T, vp(d_scores),
+                                          vp(d_align) if d_align else None))
+
     def translate_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int,
                          n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int,
                          d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None):
@@ -1024,6 +1098,7 @@ def host_lib():
     H.slimt_hip_service_translate_prefixed.argtypes = [vp, vp, vp, vp, vp, sz, vp]  # (include/slimt_hip_service_prefix.h)
     H.slimt_hip_service_set_sampling.argtypes = [vp, C.c_float]  # (include/slimt_hip_service_sampling.h)
     H.slimt_hip_service_translate_sampled.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, sz, vp]
+    H.slimt_hip_service_score.argtypes = [vp, vp, vp, vp, vp, sz, vp]  # (include/slimt_hip_service_score.h)
     _host_lib = H
     return H
 
@@ -1178,6 +1253,21 @@ class BatchService:
         if len(prefixes) != len(sentences):
             raise ValueError(f"prefixes: {len(prefixes)} for {len(sentences)} sentences")
         return self.translate_flat(*self._flat(sentences), *self._flat(prefixes), seed=seed)
+
+    def score(self, sentences, targets) -> ServiceResult:
+        """slimt_hip_service_score: teacher-forced scoring of targets[i] (a token list, with its EOS when that is to be
+        scored; any length) against sentences[i] in one pass over all target positions. The result's target(i) is the given
+        tokens, token_scores(i) their log-probabilities (whether or not the service scores its translations),
+        alignment(i) the [target tokens, source tokens] rows. Blocking; thread-safe."""
+        if len(targets) != len(sentences):
+            raise ValueError(f"targets: {len(targets)} for {len(sentences)} sentences")
+        tokens, offsets = self._flat(sentences)
+        t_tokens, t_offsets = self._flat(targets)
+        out = C.c_void_p()
+        if host_lib().slimt_hip_service_score(self.h, _p(tokens), _p(offsets), _p(t_tokens), _p(t_offsets), offsets.size - 1,
+                                              C.byref(out)):
+            raise SlimtHipError(host_lib().slimt_hip_service_last_error().decode())
+        return ServiceResult(out, np.diff(offsets).astype(np.int64))
 
     def close(self):
         if getattr(self, "h", None):

@@ -1076,7 +1076,8 @@ void ctx_free(slimt_hip_ctx *c) {
                     &c->h8, &c->a8, &c->ticket, &c->kv, &c->kv_fmt, &c->cl_act, &c->cl_part, &c->cl_sync, &c->dx, &c->dx_pre, &c->dh, &c->datt8, &c->dout, &c->df8,
                     &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
-                    &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag};
+                    &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag,
+                    &c->score_ws, &c->score_io};
   for (auto *b : bufs) b->release();
   free_affine(c->out_sl);
   if (c->n_finished_host) (void)hipHostFree(c->n_finished_host);
@@ -3767,4 +3768,257 @@ extern "C" int slimt_hip_translate_async_generated(slimt_hip_ctx *ctx, slimt_hip
   if (pc.rc) return pc.rc;
   if (smc.rc) return smc.rc;
   return translate_host_generated(ctx, sl, src_ids, lengths, B, S, limit_factor, eos_id, out_ids, out_len, align, false);
+}
+
+// ---- teacher-forced scoring: every target position in one tall pass (include/slimt_hip.h, slimt_hip_score*) -----------
+// score_tall.hip has the kernels and the reasoning. Here: the context's encoder for the batch with the f32 float(accS) K/V
+// cache of the stage path (encode_device / decode_setup), then per chunk of whole sentences the decoder layers as tall
+// GEMMs (launch_gemm: 128-row tiles from 1024 rows on, bit-identical to the step-wise dgemm) around the scan, the
+// attention and the scoring output layer. None of it reads or consumes what set_scores / set_target_prefix / set_sampling
+// armed: these entry points construct no ScoreCall / PrefixCall / SampleCall.
+namespace {
+constexpr size_t kScoreChunkRows = 8192;         // rows of a chunk (whole sentences; a single sentence may exceed it)
+constexpr size_t kScoreMaxT = 65536;             // longest target
+constexpr size_t kScoreMaxRows = (size_t)1 << 24;  // largest B * T of a call
+
+// a buffer a queued kernel may still read: the context is synchronised before the old block is freed
+int score_reserve(slimt_hip_ctx *c, DevBuf &buf, size_t bytes) {
+  if (bytes <= buf.bytes && buf.p) return 0;
+  if (buf.p) HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(buf.reserve(bytes));
+  return 0;
+}
+
+int score_check(const slimt_hip_ctx *c, size_t B, size_t S, size_t n_sl, size_t T) {
+  RCCHK(check_batch(c, B, S));
+  const slimt_hip_model *m = c->model;
+  if (T == 0) return fail(-1, "score: T is 0 (a target row needs at least one column)");
+  if (T > kScoreMaxT || B * T > kScoreMaxRows)
+    return fail(-1, "score: %zu x %zu target positions exceed the limits (T <= %zu, B * T <= %zu)", B, T, kScoreMaxT, kScoreMaxRows);
+  if (n_sl > (size_t)m->V) return fail(-1, "shortlist larger than the vocabulary");
+  if (m->kv_format == 3)
+    return fail(-1, "score: the model is set to K/V cache format 3 (the literal cross-attention order); the scoring pass "
+                    "has the hoisted order only");
+  if (!score_supported(m->D, m->H) || S > 128)
+    return fail(-1, "score: no scoring kernels for D = %d with %d heads, S = %zu", m->D, m->H, S);
+  return 0;
+}
+
+int score_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_lengths, size_t B, size_t S,
+                 const uint32_t *d_shortlist, size_t n_sl, const uint32_t *d_tgt, const uint32_t *d_tlen, size_t T,
+                 float *d_scores, float *d_align) {
+  const slimt_hip_model *m = c->model;
+  hipStream_t st = c->stream;
+  const size_t D = (size_t)m->D, F = (size_t)m->F;
+  // the batch through the context's encoder; K / V as the stage path caches them (decode_setup), the output layer packed
+  if (d_ids != c->ids.as<uint32_t>()) HIPCHK(hipMemcpyAsync(c->ids.p, d_ids, B * S * 4, hipMemcpyDefault, st));
+  if (d_lengths != c->lengths.as<uint32_t>())
+    HIPCHK(hipMemcpyAsync(c->lengths.p, d_lengths, B * 4, hipMemcpyDefault, st));
+  if (n_sl && d_shortlist != c->shortlist.as<uint32_t>()) {
+    c->sl_host.clear();  // ctx->shortlist no longer holds what a host call uploaded last
+    HIPCHK(hipMemcpyAsync(c->shortlist.p, d_shortlist, n_sl * 4, hipMemcpyDefault, st));
+  }
+  RCCHK(encode_device(c, (int)B, (int)S, nullptr, nullptr));
+  RCCHK(decode_setup(c, n_sl));
+  c->decode_ready = false;  // (the step-wise API starts from its own decode_begin)
+  const AffineW &out = output_layer(c);
+  // workspace of one chunk: four f32 row buffers, two int8 ones, FFN1's int8 output, the target columns
+  const size_t spc = std::max<size_t>(1, kScoreChunkRows / T);  // sentences per chunk
+  const size_t ws_rows = std::min(B, spc) * T;
+  auto up = [](size_t n) { return (n + 255) / 256 * 256; };
+  const size_t b_f32 = up(ws_rows * D * 4), b_i8 = up(ws_rows * D), b_f8 = up(ws_rows * F), b_col = up(ws_rows * 4);
+  RCCHK(score_reserve(c, c->score_ws, 4 * b_f32 + 2 * b_i8 + b_f8 + b_col));
+  char *p = c->score_ws.as<char>();
+  float *x = reinterpret_cast<float *>(p);
+  float *f = reinterpret_cast<float *>(p + b_f32);
+  float *wx = reinterpret_cast<float *>(p + 2 * b_f32);
+  float *h = reinterpret_cast<float *>(p + 3 * b_f32);
+  int8_t *att8 = reinterpret_cast<int8_t *>(p + 4 * b_f32);
+  int8_t *y8 = att8 + b_i8;
+  int8_t *f8 = y8 + b_i8;
+  int *tcol = reinterpret_cast<int *>(f8 + b_f8);
+  const float *kv = c->kv.as<float>();
+  const size_t M = B * S;
+  for (size_t b0 = 0; b0 < B; b0 += spc) {
+    ScoreRows rows;
+    rows.b0 = (int)b0;
+    rows.nb = (int)std::min(spc, B - b0);
+    rows.T = (int)T;
+    rows.tgt_ids = d_tgt;
+    rows.tgt_len = d_tlen;
+    const int R = rows.nb * rows.T;
+    HIPCHK(launch_score_embed(embed_args(c), rows, n_sl ? c->shortlist.as<uint32_t>() : nullptr, out.w.N, x, tcol, st));
+    for (int l = 0; l < m->Ld; ++l) {
+      const DecLayerW &L = m->dec[(size_t)l];
+      // SSRU (Modules.cc:190-235): both gate GEMMs over all rows, then the scan
+      RCCHK(run_affine_f32(c, SLIMT_HIP_K_GEMM_DEC, L.rnn_f, x, R, f, 0));
+      RCCHK(run_affine_f32(c, SLIMT_HIP_K_GEMM_DEC, L.rnn_w, x, R, wx, 0));
+      {
+        ProfScope ps(c, SLIMT_HIP_K_SSRU, 0, 0);
+        HIPCHK(launch_score_scan(rows, m->D, x, f, wx, L.rnn_ln.scale.as<float>(), L.rnn_ln.bias.as<float>(), 1e-6f, h, st));
+      }
+      // Attention::forward (Modules.cc:287-319): Q projection, then every query row of a sentence over its cached K / V
+      RCCHK(run_affine_f32(c, SLIMT_HIP_K_GEMM_DEC, L.attn.q, h, R, f, 0));
+      ScoreAttnArgs a;
+      a.rows = rows;
+      a.D = m->D; a.H = m->H; a.S = (int)S;
+      a.q = f;
+      a.k = kv + (size_t)(2 * l) * M * D;
+      a.v = kv + (size_t)(2 * l + 1) * M * D;
+      a.ldv = m->D;
+      a.uk = L.attn.k.w.u;
+      a.uv = L.attn.v.w.u;
+      a.pbk = L.attn.k.w.pb;
+      a.pbv = L.attn.v.w.pb;
+      a.lengths = c->lengths.as<uint32_t>();
+      a.alpha = 1.0f / std::sqrt(static_cast<float>(m->D / m->H));
+      a.out_i8 = att8;
+      a.a_quant_out = L.attn.o.w.a_quant;
+      a.align = l + 1 == m->Ld ? d_align : nullptr;  // alignment = last layer (Transformer.cc:165-174)
+      {
+        ProfScope ps(c, SLIMT_HIP_K_ATTN_DEC, 0, 0);
+        HIPCHK(launch_score_attention(a, st));
+      }
+      // O projection + residual, LayerNorm (Modules.cc:308-316); FFN (Modules.cc:251-257)
+      RCCHK(run_affine_res(c, SLIMT_HIP_K_GEMM_DEC, L.attn.o, nullptr, att8, R, h, wx, 0));
+      HIPCHK(launch_layer_norm_q(wx, L.attn.ln.scale.as<float>(), L.attn.ln.bias.as<float>(), 1e-6f, R, m->D, wx, y8,
+                                 L.ffn1.w.a_quant, st));
+      RCCHK(run_affine_relu_q(c, SLIMT_HIP_K_GEMM_DEC, L.ffn1, nullptr, y8, R, L.ffn2.w.a_quant, f8, 0));
+      RCCHK(run_affine_res(c, SLIMT_HIP_K_GEMM_DEC, L.ffn2, nullptr, f8, R, wx, x, 0));
+      const bool last = l + 1 == m->Ld;  // the last layer's rows leave quantised for the output layer as well
+      HIPCHK(launch_layer_norm_q(x, L.ffn_ln.scale.as<float>(), L.ffn_ln.bias.as<float>(), 1e-6f, R, m->D, x,
+                                 last ? y8 : nullptr, last ? out.w.a_quant : 0.0f, st));
+    }
+    ScoreOutArgs o;
+    o.rows = rows;
+    o.a_i8 = y8;
+    o.w = out.w;
+    o.tcol = tcol;
+    o.scores = d_scores;
+    {
+      ProfScope ps(c, SLIMT_HIP_K_LOGITS, (double)R * out.w.K * out.w.N, gemm_bytes(out.w));
+      HIPCHK(launch_score_output(o, st));
+    }
+  }
+  return 0;
+}
+
+// Host buffers: validated, then read / written in place where pinned, else bracketed by copies on the context's stream.
+// gen (nullable): the batch's lexical shortlist is generated on the device first (shortlist / n_sl are then not used).
+int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
+               size_t S, const uint32_t *shortlist, size_t n_sl, const uint32_t *tgt_ids, const uint32_t *tgt_len, size_t T,
+               float *scores, float *align, bool wait) {
+  if (ctx && T == 0) return fail(-1, "score: T is 0 (a target row needs at least one column)");
+  if (!ctx || !src_ids || !lengths || !tgt_ids || !tgt_len || !scores) return fail(-1, "null argument");
+  RCCHK(score_check(ctx, B, S, n_sl, T));
+  const slimt_hip_model *m = ctx->model;
+  uint32_t vmax = (uint32_t)m->V;
+  if (gen) {
+    RCCHK(check_generator(ctx, gen));
+    vmax = (uint32_t)std::min((size_t)m->V, gen->source_vocab);
+  } else if (n_sl && !shortlist) {
+    return fail(-1, "shortlist is NULL");
+  }
+  for (size_t i = 0; i < B * S; ++i)
+    if (src_ids[i] >= vmax) return fail(-1, "token id %u out of range", src_ids[i]);
+  for (size_t i = 0; !gen && i < n_sl; ++i)
+    if (shortlist[i] >= (uint32_t)m->V) return fail(-1, "shortlist id %u out of range", shortlist[i]);
+  for (size_t b = 0; b < B; ++b) {
+    if (lengths[b] > S) return fail(-1, "length %u > S", lengths[b]);
+    if (tgt_len[b] > T) return fail(-1, "score: target length %u of sentence %zu > T %zu", tgt_len[b], b, T);
+    for (size_t t = 0; t < tgt_len[b]; ++t)
+      if (tgt_ids[b * T + t] >= (uint32_t)m->V)
+        return fail(-1, "score: target id %u of sentence %zu out of range", tgt_ids[b * T + t], b);
+  }
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t st = ctx->stream;
+  if (!gen && n_sl && (ctx->sl_host.size() != n_sl || std::memcmp(ctx->sl_host.data(), shortlist, n_sl * 4) != 0)) {
+    ctx->sl_host.clear();  // (translate_host: the shortlist stays on the device, uploaded when it changes)
+    HIPCHK(hipMemcpyAsync(ctx->shortlist.p, shortlist, n_sl * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    ctx->sl_host.assign(shortlist, shortlist + n_sl);
+  }
+  // inputs: pinned arrays in place, others staged; [tgt_ids B T][tgt_len B][scores B T] in score_io
+  const uint32_t *d_ids = static_cast<const uint32_t *>(host_device_view(src_ids));
+  const uint32_t *d_len = static_cast<const uint32_t *>(host_device_view(lengths));
+  const uint32_t *d_tgt = static_cast<const uint32_t *>(host_device_view(tgt_ids));
+  const uint32_t *d_tlen = static_cast<const uint32_t *>(host_device_view(tgt_len));
+  float *d_scores = static_cast<float *>(host_device_view(scores));
+  RCCHK(score_reserve(ctx, ctx->score_io, (2 * B * T + B) * 4));
+  if (align) RCCHK(score_reserve(ctx, ctx->align, B * T * S * 4));
+  if (!d_ids) {
+    HIPCHK(hipMemcpyAsync(ctx->ids.p, src_ids, B * S * 4, hipMemcpyHostToDevice, st));
+    d_ids = ctx->ids.as<uint32_t>();
+  }
+  if (!d_len) {
+    HIPCHK(hipMemcpyAsync(ctx->lengths.p, lengths, B * 4, hipMemcpyHostToDevice, st));
+    d_len = ctx->lengths.as<uint32_t>();
+  }
+  uint32_t *io = ctx->score_io.as<uint32_t>();
+  if (!d_tgt) {
+    HIPCHK(hipMemcpyAsync(io, tgt_ids, B * T * 4, hipMemcpyHostToDevice, st));
+    d_tgt = io;
+  }
+  if (!d_tlen) {
+    HIPCHK(hipMemcpyAsync(io + B * T, tgt_len, B * 4, hipMemcpyHostToDevice, st));
+    d_tlen = io + B * T;
+  }
+  // outputs that are copied back go down first: the copy back then restores every entry the pass does not write
+  float *stage_sc = nullptr;
+  if (!d_scores) {
+    stage_sc = reinterpret_cast<float *>(io + B * T + B);
+    HIPCHK(hipMemcpyAsync(stage_sc, scores, B * T * 4, hipMemcpyHostToDevice, st));
+    d_scores = stage_sc;
+  }
+  if (align) HIPCHK(hipMemcpyAsync(ctx->align.p, align, B * T * S * 4, hipMemcpyHostToDevice, st));
+  const uint32_t *d_sl = ctx->shortlist.as<uint32_t>();
+  if (gen) {  // Model.cc:117-120: the batch's shortlist, generated on this stream into ctx->shortlist
+    ctx->sl_host.clear();
+    HIPCHK(ctx->n_sl_dev.reserve(4));
+    RCCHK(shortlist_scratch(ctx->sl_scratch, gen, st));
+    ShortlistArgs a;
+    shortlist_args(gen, d_ids, d_len, B, S, ctx->shortlist.as<uint32_t>(), ctx->n_sl_dev.as<uint32_t>(), a);
+    a.scratch = ctx->sl_scratch.as<uint32_t>();
+    HIPCHK(launch_shortlist_generate(a, st));
+    uint32_t n = 0;  // the tall kernels are sized on the host: one 4-byte read-back
+    HIPCHK(hipMemcpyAsync(&n, ctx->n_sl_dev.p, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    n_sl = n;
+  }
+  RCCHK(score_device(ctx, d_ids, d_len, B, S, d_sl, n_sl, d_tgt, d_tlen, T, d_scores, align ? ctx->align.as<float>() : nullptr));
+  if (stage_sc) HIPCHK(hipMemcpyAsync(scores, stage_sc, B * T * 4, hipMemcpyDeviceToHost, st));
+  if (align) HIPCHK(hipMemcpyAsync(align, ctx->align.p, B * T * S * 4, hipMemcpyDeviceToHost, st));
+  if (wait) RCCHK(slimt_hip_ctx_synchronize(ctx));
+  return 0;
+}
+}  // namespace
+
+extern "C" int slimt_hip_score(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                               const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids,
+                               const uint32_t *tgt_len, size_t T, float *scores, float *align) {
+  return score_host(ctx, nullptr, src_ids, lengths, B, S, shortlist, n_shortlist, tgt_ids, tgt_len, T, scores, align, true);
+}
+
+extern "C" int slimt_hip_score_async(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                                     const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids,
+                                     const uint32_t *tgt_len, size_t T, float *scores, float *align) {
+  return score_host(ctx, nullptr, src_ids, lengths, B, S, shortlist, n_shortlist, tgt_ids, tgt_len, T, scores, align, false);
+}
+
+extern "C" int slimt_hip_score_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *shortlist, const uint32_t *src_ids,
+                                               const uint32_t *lengths, size_t B, size_t S, const uint32_t *tgt_ids,
+                                               const uint32_t *tgt_len, size_t T, float *scores, float *align) {
+  if (!shortlist) return fail(-1, "null argument");
+  return score_host(ctx, shortlist, src_ids, lengths, B, S, nullptr, 0, tgt_ids, tgt_len, T, scores, align, false);
+}
+
+extern "C" int slimt_hip_score_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids, const uint32_t *d_lengths, size_t B,
+                                      size_t S, const uint32_t *d_shortlist, size_t n_shortlist, const uint32_t *d_tgt_ids,
+                                      const uint32_t *d_tgt_len, size_t T, float *d_scores, float *d_align) {
+  if (ctx && T == 0) return fail(-1, "score: T is 0 (a target row needs at least one column)");
+  if (!ctx || !d_src_ids || !d_lengths || !d_tgt_ids || !d_tgt_len || !d_scores) return fail(-1, "null argument");
+  RCCHK(score_check(ctx, B, S, n_shortlist, T));
+  if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
+  HIPCHK(hipSetDevice(ctx->model->device));
+  return score_device(ctx, d_src_ids, d_lengths, B, S, d_shortlist, n_shortlist, d_tgt_ids, d_tgt_len, T, d_scores, d_align);
 }

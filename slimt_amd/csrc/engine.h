@@ -223,6 +223,9 @@ struct slimt_hip_ctx {
   slimt_hip::DevBuf n_sl_dev;    // [1] size of a shortlist generated on this context's stream
   slimt_hip::AffineW out_sl;  // shortlisted output layer (per batch)
   slimt_hip::DevBuf logits, attn_dbg;
+  // teacher-forced scoring (include/slimt_hip.h, slimt_hip_score*): allocated on the first scoring call, grown when a later
+  // one needs more. score_ws: one chunk's rows (engine.cpp, score_device); score_io: staging of a host call's targets and scores
+  slimt_hip::DevBuf score_ws, score_io;
   int *n_finished_host = nullptr;  // pinned
   // profiling
   int prof_kernel = 0;

@@ -631,6 +631,51 @@ struct LongEncodeArgs {
 };
 bool long_encode_supported(int D, int F, int H, int Le, int Ld, int S);
 hipError_t launch_encode_long(const LongEncodeArgs &a, hipStream_t st);
+// ---- teacher-forced scoring: all target positions as one tall pass (score_tall.hip) ---------------------------------------
+// A chunk of whole sentences b0 .. b0 + nb - 1 of a call with targets tgt_ids [B][T] / tgt_len [B]; the chunk's local
+// row r = (b - b0) T + t. n_b = min(tgt_len[b], T); rows with t >= n_b are dead (computed where that is cheaper than a
+// branch, never stored).
+struct ScoreRows {
+  int b0 = 0, nb = 0, T = 0;
+  const uint32_t *tgt_ids = nullptr;
+  const uint32_t *tgt_len = nullptr;
+};
+// x [R][D]: the decoder input of every row (zero embedding at t = 0, else tgt_ids[b][t - 1] at position 0);
+// tcol [R]: the output-layer column of tgt_ids[b][t] (sl: the N sorted shortlist ids, nullptr: the full vocabulary of N
+// entries), -1 where the layer has no such column or the row is dead
+hipError_t launch_score_embed(const EmbedArgs &e, const ScoreRows &rows, const uint32_t *sl, int N, float *x, int *tcol,
+                              hipStream_t st);
+// the SSRU scan of each sentence over t ascending from a zero cell: f / wx [R][D] are the rows' gate pre-activations
+// affine(Wf, bf)(x) and W x; h [R][D] = LayerNorm(x + relu(c_t)), c_t = highway(c_{t-1}, wx_t, f_t)
+hipError_t launch_score_scan(const ScoreRows &rows, int D, const float *x, const float *f, const float *wx,
+                             const float *ln_scale, const float *ln_bias, float eps, float *h, hipStream_t st);
+struct ScoreAttnArgs {
+  ScoreRows rows;
+  int D = 0, H = 0, S = 0;
+  const float *q = nullptr;  // [R][D] projected queries
+  const float *k = nullptr;  // the call's cached K [B][H][dh/4][S][4], values float(accS) (DQAttnArgs)
+  const float *v = nullptr;  // ... and V [B*S][ldv]
+  int ldv = 0;
+  float uk = 0.f, uv = 0.f;
+  const float *pbk = nullptr, *pbv = nullptr;
+  const uint32_t *lengths = nullptr;  // [B] source lengths (clamped to S)
+  float alpha = 0.f;
+  int8_t *out_i8 = nullptr;  // [R][D] joined heads, quantised for the O projection
+  float a_quant_out = 0.f;
+  float *align = nullptr;  // nullable [B][T][S]: head 0's row of (b, t), columns j < lengths[b]
+};
+size_t score_attention_lds_bytes(int S, int dh);  // 8 S dh: one head's K and V of one sentence, f32
+hipError_t launch_score_attention(const ScoreAttnArgs &a, hipStream_t st);
+struct ScoreOutArgs {
+  ScoreRows rows;
+  const int8_t *a_i8 = nullptr;  // [R][K] final decoder rows, quantised with the output layer's a_quant
+  PreparedWeight w;              // the (shortlisted) output layer
+  const int *tcol = nullptr;     // [R]
+  float *scores = nullptr;       // [B][T]: log softmax at the target column (scores.h, forced_score), live rows only
+};
+hipError_t launch_score_output(const ScoreOutArgs &a, hipStream_t st);
+bool score_supported(int D, int H);  // D in {64, 128, 256, 512}, d_head in {16, 32, 64}
+
 // the column means (rounded) of an f32 K/V cache [Ld][K, V][B * S][D]: centre[(2 l + p) * D + d] (FusedDecodeArgs::kv_centre)
 hipError_t launch_kv_centres(const float *kv, int Ld, int B, int S, int D, unsigned long long *sums, int *centre, hipStream_t st);
 

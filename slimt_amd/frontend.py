@@ -92,6 +92,15 @@ def _blob(x) -> bytes:
         return f.read()
 
 
+@dataclass
+class PairScore:  # Service.score: one (source, given target) pair
+    source_ids: List[int]         # the source as tokenised, EOS included
+    target_ids: List[int]         # the target as tokenised, EOS included
+    token_scores: np.ndarray      # float32 [len(target_ids)]: log-probability of each target token given those before it
+    score: float                  # their sum: the log-probability of the target given the source
+    alignment: np.ndarray         # float32 [len(target_ids), len(source_ids)]
+
+
 class Model:
     """slimt::Model (Model.hh:31-83): vocabulary + text processor + the transformer's weights on
     `device` + the optional lexical shortlist generator."""
@@ -392,6 +401,34 @@ class Service:
                     finish(pending.pop(0))
         for r in out:
             r.to(encoding)
+        return out
+
+    def score(self, model: Model, sources: Sequence[str], targets: Sequence[str]) -> List["PairScore"]:
+        """Teacher-forced scoring of given translations (include/slimt_hip_service_score.h): targets[i] against
+        sources[i], each text ONE sentence as the model's vocabulary tokenises it, EOS appended -- no sentence splitting,
+        no wrapping: a source of more than ENGINE_LIMIT tokens is refused, a target may be any length. Every target
+        position goes through the decoder in one pass; the output layer is the one translate() uses (the model's lexical
+        shortlist per batch, else the full vocabulary), so a target token outside it scores -inf. Returns one PairScore
+        per pair: the token ids of both sides, each target token's log-probability, their sum, and the
+        [target tokens, source tokens] alignment (head 0 of the last decoder layer)."""
+        if len(sources) != len(targets):
+            raise ValueError(f"score: {len(targets)} targets for {len(sources)} sources")
+        v = model.vocabulary
+        eos = v.eos_id()
+        src = [ids + [eos] for ids in v.encode_ids_batch(list(sources), self.workers)] if sources else []
+        tgt = [ids + [eos] for ids in v.encode_ids_batch(list(targets), self.workers)] if targets else []
+        for i, ids in enumerate(src):
+            if len(ids) > self.ENGINE_LIMIT:
+                raise ValueError(f"score: source {i} has {len(ids)} tokens, more than {self.ENGINE_LIMIT}")
+        if not src:
+            return []
+        res = self._engine(model).score(src, tgt)
+        out = []
+        for i in range(len(src)):
+            sc = res.token_scores(i).copy()
+            out.append(PairScore(source_ids=src[i], target_ids=tgt[i], token_scores=sc,
+                                 score=float(np.sum(sc, dtype=np.float64)), alignment=res.alignment(i).copy()))
+        res.close()
         return out
 
     def pivot(self, first: Model, second: Model, texts: Sequence[str], html: bool = False,

@@ -210,6 +210,22 @@ uint64_t Worker::sampling_key(uint64_t seed, uint64_t index) {
   return slimt_hip_sampling_key(seed, index);
 }
 
+// (weak, like the scores: the Service's sanitizer builds link a test double of the engine that predates these calls)
+#pragma weak slimt_hip_score
+#pragma weak slimt_hip_score_async_generated
+void Worker::score(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
+                   const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids, const uint32_t *tgt_len, size_t T,
+                   float *scores, float *align) {
+  if (!slimt_hip_score || !slimt_hip_score_async_generated) throw std::runtime_error("this engine has no teacher-forced scoring");
+  if (generator) {
+    if (slimt_hip_score_async_generated(ctx_, generator, ids, lengths, B, S, tgt_ids, tgt_len, T, scores, align))
+      raise("slimt_hip_score_async_generated");
+    wait();
+  } else if (slimt_hip_score(ctx_, ids, lengths, B, S, shortlist, n_shortlist, tgt_ids, tgt_len, T, scores, align)) {
+    raise("slimt_hip_score");
+  }
+}
+
 void Worker::wait() {
   if (slimt_hip_ctx_synchronize(ctx_)) raise("slimt_hip_ctx_synchronize");
 }

@@ -172,6 +172,14 @@ class Worker {
   // (slimt_hip_ctx_set_sampling); sampling_key: slimt_hip_sampling_key
   void arm_sampling(float temperature, const uint64_t *const *keys, size_t n);
   static uint64_t sampling_key(uint64_t seed, uint64_t index);
+  // Teacher-forced scoring of given targets in one pass over all target positions (include/slimt_hip.h, slimt_hip_score):
+  // tgt_ids [B][T], tgt_len [B] (T is the caller's: no limit-factor cap), scores [B][T], align nullable [B][T][S]; entries
+  // with t >= tgt_len[b] and alignment columns j >= lengths[b] are not written. Waits for the result; nothing armed on
+  // the worker is used or consumed. generator (nullable): the batch's lexical shortlist, generated on the device
+  // (slimt_hip_score_async_generated) -- shortlist / n_shortlist are then not used.
+  void score(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
+             const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids, const uint32_t *tgt_len, size_t T,
+             float *scores, float *align);
   void wait();
 
  private:

@@ -213,6 +213,8 @@ Service::Service(const ServiceConfig &config, std::vector<const Model *> replica
                      n, config.workers_per_device, contexts, device, kContextsPerDeviceCliff, kContextsPerDeviceCliff / 2);
     }
   }
+  score_model_ = replicas[0];
+  score_generator_ = generator_of[0];
   live_workers_ = replicas.size() * config.workers_per_device;
   for (size_t r = 0; r < replicas.size(); ++r)
     for (size_t w = 0; w < config.workers_per_device; ++w)
@@ -237,6 +239,75 @@ Service::~Service() {
                  static_cast<unsigned long long>(merged_launches_.load() - merged_base_),
                  static_cast<unsigned long long>(launches_.load() - launches_base_), n);
   }
+}
+
+Histories Service::score(std::vector<Words> sentences, std::vector<Words> targets) {
+  constexpr size_t kLongestTarget = 65536;  // include/slimt_hip.h, slimt_hip_score
+  if (targets.size() != sentences.size())
+    throw std::invalid_argument(std::to_string(targets.size()) + " targets for " + std::to_string(sentences.size()) + " sentences");
+  for (size_t i = 0; i < sentences.size(); ++i) {
+    const Words &s = sentences[i];
+    if (s.empty()) throw std::invalid_argument("empty sentence (a sentence holds at least its EOS)");
+    if (s.size() > longest_)
+      throw std::invalid_argument("sentence of " + std::to_string(s.size()) + " tokens: longer than " +
+                                  std::to_string(longest_) + " (wrap it first)");
+    if (targets[i].size() > kLongestTarget)
+      throw std::invalid_argument("target of sentence " + std::to_string(i) + ": " + std::to_string(targets[i].size()) +
+                                  " tokens, more than " + std::to_string(kLongestTarget));
+  }
+  const size_t n = sentences.size();
+  Histories results(n);
+  if (n == 0) return results;
+  if (n >= (1u << 24)) throw std::invalid_argument("request of more than 2^24 sentences");
+  LengthQueue queue(config_.max_words, longest_);  // the batch-forming rule of translate()
+  for (size_t i = 0; i < n; ++i) {
+    Unit u;
+    u.order = i;
+    u.index = static_cast<uint32_t>(i);
+    u.length = static_cast<uint32_t>(sentences[i].size());
+    queue.push(std::move(u));
+  }
+  std::lock_guard<std::mutex> lock(score_mu_);
+  if (!score_worker_) score_worker_ = std::make_unique<Worker>(*score_model_, config_.max_words, longest_, config_.max_words);
+  std::vector<uint32_t> ids, lengths, tgt, tlen;
+  std::vector<float> sc, al;
+  for (;;) {
+    const std::vector<Unit> batch = queue.take();
+    if (batch.empty()) break;
+    const size_t B = batch.size();
+    size_t S = 1, T = 1;
+    for (const Unit &u : batch) {
+      S = std::max<size_t>(S, u.length);
+      T = std::max(T, targets[u.index].size());
+    }
+    ids.assign(B * S, config_.pad_id);
+    lengths.resize(B);
+    tgt.assign(B * T, 0);
+    tlen.resize(B);
+    sc.assign(B * T, 0.0f);
+    if (config_.alignments) al.assign(B * T * S, 0.0f);
+    for (size_t b = 0; b < B; ++b) {
+      const Words &s = sentences[batch[b].index], &t = targets[batch[b].index];
+      std::copy(s.begin(), s.end(), ids.begin() + static_cast<std::ptrdiff_t>(b * S));
+      std::copy(t.begin(), t.end(), tgt.begin() + static_cast<std::ptrdiff_t>(b * T));
+      lengths[b] = static_cast<uint32_t>(s.size());
+      tlen[b] = static_cast<uint32_t>(t.size());
+    }
+    const bool fixed = config_.shortlist && !score_generator_;
+    score_worker_->score(score_generator_, ids.data(), lengths.data(), B, S, fixed ? config_.shortlist->data() : nullptr,
+                         fixed ? config_.shortlist->size() : 0, tgt.data(), tlen.data(), T, sc.data(),
+                         config_.alignments ? al.data() : nullptr);
+    const uint64_t serial = batches_.fetch_add(1);
+    // the given tokens as the recorded ones: collect() cuts rows at tgt_len and alignment rows at the sentence's length
+    Histories hs = collect(tgt.data(), tlen.data(), config_.alignments ? al.data() : nullptr, lengths.data(), B, S, T,
+                           config_.flat_alignments);
+    for (size_t b = 0; b < B; ++b) {
+      hs[b]->scores.assign(sc.begin() + static_cast<std::ptrdiff_t>(b * T), sc.begin() + static_cast<std::ptrdiff_t>(b * T + tlen[b]));
+      hs[b]->batch = serial;
+      results[batch[b].index] = std::move(hs[b]);
+    }
+  }
+  return results;
 }
 
 bool Service::set_scores(bool on) {

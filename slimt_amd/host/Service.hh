@@ -155,6 +155,16 @@ class Service {
   // ... on a sampling service (set_sampling) under this seed: sentence i is drawn under slimt_hip_sampling_key(seed, i),
   // wherever the batcher puts it (the other overloads use seed 0); prefixes may be empty
   std::future<Histories> translate(std::vector<Words> sentences, std::vector<Words> prefixes, uint64_t seed);
+  // Teacher-forced scoring (include/slimt_hip.h, slimt_hip_score): targets[i] is the given translation of sentences[i]
+  // (with its EOS when that is to be scored), of ANY length -- there is no limit-factor cap. Batches are formed by the
+  // source-length rule of translate(); each batch's target rows are as long as its longest target; the output layer is
+  // the one the service translates with (its lexical shortlist per batch, its fixed list, or the full vocabulary). One
+  // Hypothesis per sentence: target = the given tokens, scores = their log-probabilities (always filled, whatever
+  // set_scores says), the alignment rows as translate() returns them. Synchronous, on the caller's thread and a context
+  // of its own (built on the first call, on the first replica): it neither queues behind translate requests nor is
+  // merged with them; concurrent callers take turns. Throws std::invalid_argument for counts that differ, an empty
+  // sentence or one longer than the service accepts, or a target of more than 65536 tokens.
+  Histories score(std::vector<Words> sentences, std::vector<Words> targets);
   // per-token scores on or off (ServiceConfig::scores): only before the first translate(); false once one has been made
   bool set_scores(bool on);
   // temperature sampling for every request (include/slimt_hip.h, slimt_hip_ctx_set_sampling; 0: greedy again): only before
@@ -192,6 +202,11 @@ class Service {
   std::mutex mutex_;
   std::condition_variable wake_;
   std::vector<std::thread> threads_;
+  // score(): the first replica, its generator (nullable), and the context the calls share (built by the first one)
+  const Model *score_model_ = nullptr;
+  slimt_hip_shortlist *score_generator_ = nullptr;
+  std::mutex score_mu_;
+  std::unique_ptr<Worker> score_worker_;
 };
 
 }  // namespace slimt

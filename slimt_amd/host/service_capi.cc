@@ -12,6 +12,7 @@
 #include "Service.hh"
 #include "slimt_hip_service.h"
 #include "slimt_hip_service_prefix.h"
+#include "slimt_hip_service_score.h"
 #include "slimt_hip_service_sampling.h"
 #include "slimt_hip_service_scores.h"
 
@@ -90,6 +91,39 @@ extern "C" int slimt_hip_service_destroy(slimt_hip_service *service) {
 }
 
 namespace {
+// Histories -> the arrays of a result (scored: with every token's log-probability)
+int flatten(const slimt::Histories &hs, size_t n, bool scored, std::unique_ptr<slimt_hip_result> &out) {
+  auto r = std::make_unique<slimt_hip_result>();
+  r->target_offsets.assign(n + 1, 0);
+  r->align_offsets.assign(n + 1, 0);
+  r->padded.resize(n);
+  r->batch.resize(n);
+  size_t n_tok = 0, n_al = 0;
+  for (size_t i = 0; i < n; ++i) {
+    n_tok += hs[i]->target.size();
+    n_al += hs[i]->alignment_flat.size();
+  }
+  r->targets.reserve(n_tok);
+  r->alignments.reserve(n_al);
+  r->scored = scored;
+  if (r->scored) r->scores.reserve(n_tok);
+  for (size_t i = 0; i < n; ++i) {
+    const slimt::Hypothesis &h = *hs[i];
+    r->targets.insert(r->targets.end(), h.target.begin(), h.target.end());
+    r->alignments.insert(r->alignments.end(), h.alignment_flat.begin(), h.alignment_flat.end());
+    if (r->scored) {
+      if (h.scores.size() != h.target.size()) return fail("sentence %zu: %zu scores for %zu tokens", i, h.scores.size(), h.target.size());
+      r->scores.insert(r->scores.end(), h.scores.begin(), h.scores.end());
+    }
+    r->target_offsets[i + 1] = r->targets.size();
+    r->align_offsets[i + 1] = r->alignments.size();
+    r->padded[i] = static_cast<uint32_t>(h.padded_length);
+    r->batch[i] = h.batch;
+  }
+  out = std::move(r);
+  return 0;
+}
+
 // slimt_hip_service_translate[_prefixed]: prefix_tokens / prefix_offsets NULL = no prefixes
 int translate(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets, const uint32_t *prefix_tokens,
               const uint64_t *prefix_offsets, size_t n, slimt_hip_result **out, uint64_t seed = 0) {
@@ -109,33 +143,8 @@ int translate(slimt_hip_service *service, const uint32_t *tokens, const uint64_t
     const auto t1 = std::chrono::steady_clock::now();
     slimt::Histories hs = service->service->translate(std::move(sentences), std::move(prefixes), seed).get();
     const auto t2 = std::chrono::steady_clock::now();
-    auto r = std::make_unique<slimt_hip_result>();
-    r->target_offsets.assign(n + 1, 0);
-    r->align_offsets.assign(n + 1, 0);
-    r->padded.resize(n);
-    r->batch.resize(n);
-    size_t n_tok = 0, n_al = 0;
-    for (size_t i = 0; i < n; ++i) {
-      n_tok += hs[i]->target.size();
-      n_al += hs[i]->alignment_flat.size();
-    }
-    r->targets.reserve(n_tok);
-    r->alignments.reserve(n_al);
-    r->scored = service->scores;
-    if (r->scored) r->scores.reserve(n_tok);
-    for (size_t i = 0; i < n; ++i) {
-      const slimt::Hypothesis &h = *hs[i];
-      r->targets.insert(r->targets.end(), h.target.begin(), h.target.end());
-      r->alignments.insert(r->alignments.end(), h.alignment_flat.begin(), h.alignment_flat.end());
-      if (r->scored) {
-        if (h.scores.size() != h.target.size()) return fail("sentence %zu: %zu scores for %zu tokens", i, h.scores.size(), h.target.size());
-        r->scores.insert(r->scores.end(), h.scores.begin(), h.scores.end());
-      }
-      r->target_offsets[i + 1] = r->targets.size();
-      r->align_offsets[i + 1] = r->alignments.size();
-      r->padded[i] = static_cast<uint32_t>(h.padded_length);
-      r->batch[i] = h.batch;
-    }
+    std::unique_ptr<slimt_hip_result> r;
+    if (const int rc = flatten(hs, n, service->scores, r)) return rc;
     *out = r.release();
     if (std::getenv("SLIMT_SERVICE_STATS")) {
       const auto t3 = std::chrono::steady_clock::now();
@@ -162,6 +171,29 @@ extern "C" int slimt_hip_service_translate_prefixed(slimt_hip_service *service, 
   if (!service || !out || (n && (!tokens || !offsets || !prefix_offsets)) || (n && prefix_offsets[n] > prefix_offsets[0] && !prefix_tokens))
     return fail("null argument");
   return translate(service, tokens, offsets, prefix_tokens, prefix_offsets, n, out);
+}
+
+extern "C" int slimt_hip_service_score(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets,
+                                       const uint32_t *tgt_tokens, const uint64_t *tgt_offsets, size_t n, slimt_hip_result **out) {
+  if (!service || !out || (n && (!tokens || !offsets || !tgt_offsets)) || (n && tgt_offsets[n] > tgt_offsets[0] && !tgt_tokens))
+    return fail("null argument");
+  *out = nullptr;
+  try {
+    std::vector<slimt::Words> sentences(n), targets(n);
+    for (size_t i = 0; i < n; ++i) {
+      if (offsets[i + 1] < offsets[i]) return fail("offsets decrease at sentence %zu", i);
+      if (tgt_offsets[i + 1] < tgt_offsets[i]) return fail("target offsets decrease at sentence %zu", i);
+      sentences[i].assign(tokens + offsets[i], tokens + offsets[i + 1]);
+      if (tgt_offsets[i + 1] > tgt_offsets[i]) targets[i].assign(tgt_tokens + tgt_offsets[i], tgt_tokens + tgt_offsets[i + 1]);
+    }
+    const slimt::Histories hs = service->service->score(std::move(sentences), std::move(targets));
+    std::unique_ptr<slimt_hip_result> r;
+    if (const int rc = flatten(hs, n, true, r)) return rc;
+    *out = r.release();
+    return 0;
+  } catch (const std::exception &e) {
+    return fail("%s", e.what());
+  }
 }
 
 extern "C" int slimt_hip_result_view(const slimt_hip_result *r, size_t *n, const uint32_t **targets,

@@ -21,6 +21,7 @@ for line in out.splitlines():
 print(f"{'kernel':100s} VGPR AGPR SGPR scratch vspill sspill LDS occ")
 for r in rows:
     name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
-    name = re.sub(r"slimt_hip::|\(.*\)|void ", "", name)
+    name = re.sub(r"slimt_hip::|\(anonymous namespace\)::", "", name)  # (before the argument list goes: its pattern is greedy)
+    name = re.sub(r"\(.*\)|void ", "", name)
     print(f"{name[:100]:100s} {r.get('VGPRs','?'):>4} {r.get('AGPRs','?'):>4} {r.get('SGPRs','?'):>4} "
           f"{r.get('ScratchSize [bytes/lane]','?'):>7} {r.get('VGPRs Spill','?'):>6} {r.get('SGPRs Spill','?'):>6} {r.get('LDS Size [bytes/block]','?'):>5} {r.get('Occupancy [waves/SIMD]','?'):>3}")
