@@ -146,3 +146,67 @@ def test_linearity_property_full_size(hip):
     sa, sb, sab, s0 = (hip.affine_acc_i32(v, W, 1.0) for v in (a, b, a + b, z))
     assert np.array_equal(sa.astype(np.int64) + sb - sab, s0.astype(np.int64))
     assert np.array_equal(s0[0], 127 * W.astype(np.int64).sum(axis=1))
+
+
+# ---- the extremes of the int8 formats (tests/support/qmm_extremes.py; the oracle's side is pinned in tests/test_oracle.py) ----
+
+def _extreme_shapes():
+    from support import qmm_extremes as X
+    return [(M, K, N) for K in X.KS for M in X.MS for N in X.NS]
+
+
+@pytest.fixture(scope="module")
+def extreme_cases(oracle):
+    """(x, W, bias, aq, bq, the oracle's accumulators) per shape, computed once and never written to"""
+    from support import qmm_extremes as X
+    cache = {}
+
+    def get(M, K, N):
+        if (M, K, N) not in cache:
+            x, W, bias, aq, bq = X.make(M, K, N)
+            acc = oracle.affine_acc(x, W, aq)
+            for a in (x, W, bias, acc):
+                a.setflags(write=False)
+            cache[(M, K, N)] = (x, W, bias, aq, bq, acc)
+        return cache[(M, K, N)]
+
+    return get
+
+
+@pytest.mark.parametrize("M,K,N", _extreme_shapes())
+def test_extremes_accumulators_bit_exact_and_closed_forms(hip, extreme_cases, M, K, N):
+    """Weights of -128 and rows of one sign against activations that saturate, tie and vanish: int32 accumulators equal
+    to the oracle's and to the closed forms (accS == -254 * 128 * K for a saturated-positive row against an all -128
+    column; 0 for a saturated-negative row, which a clamp to -128 would turn into -colsum), K up to 4096 (|accS| up to
+    133,169,152 < 2^31), M at and past the 128-row tiling's threshold, N that is no multiple of 8."""
+    from support import qmm_extremes as X
+    x, W, _, aq, _, want = extreme_cases(M, K, N)
+    got = hip.affine_acc_i32(x, W, aq)
+    assert got.dtype == np.int32 and np.array_equal(got, want)
+    X.check_closed_forms(got, M, K)
+
+
+@pytest.mark.parametrize("M,K,N", _extreme_shapes())
+def test_extremes_affine_dot_and_select_bit_exact(hip, oracle, extreme_cases, M, K, N):
+    """The floats of the same case: affine, dot (no bias) and affine_with_select (the four extreme columns and every
+    third of the others) equal to the oracle's bit for bit. From K = 1536 on the one-signed columns' accumulators pass 2^24,
+    where float(accS) rounds: a kernel that converts the signed accumulator and 127 colsum separately differs there. M >=
+    1024 takes the 128-row tiling (gemm_tile.hip), which the suite's other extremes (M = 32) never reach."""
+    x, W, bias, aq, bq, acc = extreme_cases(M, K, N)
+    if K >= 1536:
+        a = acc.astype(np.int64)
+        assert (a.astype(np.float32).astype(np.int64) != a).any()  # this case does exercise the rounding conversion
+        shift = 127 * W.astype(np.int64).sum(axis=1)[None, :]  # ... and the split conversion is another float somewhere in it
+        assert ((a - shift).astype(np.float32) + shift.astype(np.float32) != a.astype(np.float32)).any()
+    oracle.set_mode(oracle.PORTABLE)
+    try:
+        for b in (bias, None):
+            got = hip.affine(x, W, b, aq, bq) if b is not None else hip.dot(x, W, aq, bq)
+            want = oracle.affine(x, W, b, aq, bq)
+            assert np.array_equal(got, want), (b is None, np.abs(got - want).max())
+        idx = np.unique(np.concatenate([np.arange(min(4, N)), np.arange(4, N, 3)])).astype(np.uint32)
+        got = hip.affine_with_select(x, W, bias, aq, bq, idx)
+        want = oracle.affine_select(x, W, bias, aq, bq, idx)
+        assert got.shape == (M, idx.size) and np.array_equal(got, want), np.abs(got - want).max()
+    finally:
+        oracle.set_mode(oracle.FAITHFUL)

@@ -364,3 +364,36 @@ def test_end_to_end_agreement_of_the_two_orders_on_a_larger_sample(oracle, synth
               f"({same_sentences / sentences:.3f}), identical tokens {tok_same}/{tok_total} ({tok_same / tok_total:.4f})")
     assert same_sentences / sentences >= 0.80
     assert tok_same / tok_total >= 0.95
+
+
+@pytest.mark.parametrize("M,K,N", [(5, 64, 7), (5, 4096, 72), (1100, 1536, 7), (1024, 2048, 72), (5, 256, 517)])
+def test_affine_at_the_extremes_of_the_formats_against_an_int64_sum(oracle, M, K, N):
+    """tests/support/qmm_extremes.py (weights of -128, rows of one sign, saturating activations, exact ties, zeros): the
+    oracle's accumulators against an int64 numpy sum and the closed forms, its floats against the float32 re-derivation
+    above -- ONE int -> float conversion of accS, which rounds past 2^24 (K >= 1536 here). This pins the reference the GPU
+    test of the same case (tests/test_gpu_qmm.py) compares with."""
+    from support import qmm_extremes as X
+    x, W, bias, aq, bq = X.make(M, K, N)
+    q = oracle.quantize(x, aq)
+    assert np.array_equal(q.astype(np.int64), X.quantised(x)) and q.min() == -127 and q.max() == 127
+    ties = q[2].astype(np.int64)
+    assert (ties % 2 == 0).all() and np.array_equal(np.abs(ties * 2 - 2 * x[2].astype(np.float64) * aq), np.ones(K))  # to even
+    acc = oracle.affine_acc(x, W, aq)
+    want = X.accumulators_int64(x, W)
+    assert np.abs(want).max() < 2 ** 31 and np.array_equal(acc.astype(np.int64), want)
+    X.check_closed_forms(acc, M, K)
+    if K >= 1536:
+        assert np.abs(want).max() > 2 ** 24
+        assert (want.astype(np.float32).astype(np.int64) != want).any()  # the conversion does round in this case
+        # ... and converting the signed accumulator and 127 colsum separately gives ANOTHER float somewhere: a kernel doing
+        # that cannot pass the bit-exact comparison of this case
+        shift = 127 * W.astype(np.int64).sum(axis=1)[None, :]
+        assert ((want - shift).astype(np.float32) + shift.astype(np.float32) != want.astype(np.float32)).any()
+    for b in (bias, None):
+        for mode in (oracle.PORTABLE, oracle.FAITHFUL):
+            oracle.set_mode(mode)
+            try:
+                y = oracle.affine(x, W, b, aq, bq)
+            finally:
+                oracle.set_mode(oracle.FAITHFUL)
+            assert np.array_equal(y, _affine_numpy(x, W, b, np.float32(aq), np.float32(bq)))
