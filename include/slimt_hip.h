@@ -560,8 +560,9 @@ int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slimt_hip_short
  * is REFUSED with a message, not scored in another order.
  * Score calls are not translate calls: options armed with slimt_hip_ctx_set_scores / _set_target_prefix / _set_sampling
  * are neither used nor consumed by them.
- * Limits: B <= max_batch, S <= max_source_length, 1 <= T <= 65536, B * T <= 2^24. The workspace for the rows (18 D + F
- * + 4 bytes each) is allocated on a context's first scoring call and grows when a later call needs more (the
+ * Limits: B <= max_batch, S <= max_source_length, which is itself at most 128 (slimt_hip_ctx_create; the scoring attention
+ * keeps two keys per lane, so S <= 128 is also the scoring kernels' own limit), 1 <= T <= 65536, B * T <= 2^24. The
+ * workspace for the rows (18 D + F + 4 bytes each) is allocated on a context's first scoring call and grows when a later call needs more (the
  * context is synchronised before the old block is freed); rows are processed in chunks of whole sentences of at most
  * max(T, 8192) rows, and results do not depend on the chunking.
  * slimt_hip_score waits for the result. slimt_hip_score_async queues the work on ctx's stream: pinned ids / lengths /
