@@ -95,6 +95,18 @@ int slimt_hip_layer_norm(const float *x, const float *scale, const float *bias,
                          float eps, size_t rows, size_t cols, float *y);
 /* softmax (TensorOps.cc:282-315) */
 int slimt_hip_softmax(const float *x, size_t rows, size_t cols, float *y);
+/* One truncated sampled step over the caller's logits [M][N] (host pointers; the
+ * kernel of slimt_hip_ctx_set_sampling_truncation alone, which states the rule).
+ * N at most 2^31 - 257. ids: the columns' vocabulary ids [N] (NULL: the column); keys: the rows' sentence
+ * keys [M] (NULL: the row index); steps: the rows' step t [M] (NULL: 0).
+ * columns[r]: the drawn column, or 0 with scores[r] NaN when nothing is kept or
+ * logit 0 of the row is NaN; thresholds[r] = max(tau_k, tau_p) as a value (-inf
+ * where nothing is cut; compare with ==, +-0 are the same threshold); kept[r] = |K|;
+ * scores[r]: the step's score. */
+int slimt_hip_sample_truncated(const float *logits, size_t M, size_t N, const uint32_t *ids,
+                               float temperature, uint32_t top_k, float top_p,
+                               const uint64_t *keys, const uint32_t *steps,
+                               uint32_t *columns, float *thresholds, uint32_t *kept, float *scores);
 /* highway (TensorOps.cc:662-682): out = sigmoid(g)*x + (1-sigmoid(g))*y */
 int slimt_hip_highway(const float *x, const float *y, const float *g, size_t n,
                       float *out);
@@ -317,6 +329,60 @@ uint64_t slimt_hip_sampling_key(uint64_t seed, uint64_t index);
  * forced twin (decode_fused_kernel<..., SC, FP, SM>) or, in mode 1, the per-stage
  * kernels; the results are the same. */
 int slimt_hip_ctx_set_sampling(slimt_hip_ctx *ctx, float temperature, const uint64_t *const *keys, size_t n);
+/* Top-k and nucleus (top-p) truncation of the NEXT translate call on ctx, which must
+ * be a sampled one (slimt_hip_ctx_set_sampling): armed for that call, which consumes
+ * it whether it succeeds or fails, like the scores, the prefix and the sampling.
+ * top_k == 0: no top-k; top_p == 1.0f: no top-p; with both off nothing is armed and
+ * the call is the plain sampled call, same kernels included. top_p must be finite
+ * with 0 < top_p <= 1, else a negative status at once. A translate call that finds
+ * truncation armed but no sampling armed fails with a negative status and a
+ * message; it still consumes the setting.
+ *
+ * One drawn step: a step of a sentence that is NOT forced at that step. l_c are the
+ * output layer's logits over its N columns, inv_T = 1.0f / temperature and
+ * z_c = l_c * inv_T one float32 product.
+ *  1. A column is valid if z_c is not NaN; n_valid is their count. With
+ *     n_valid == 0 nothing is kept: class 0 and score NaN, the arg-max's "none" rule.
+ *  2. Top-k. top_k == 0 or top_k >= n_valid: tau_k = -inf. Otherwise tau_k is the
+ *     top_k-th largest valid z. K1 = {valid c : z_c >= tau_k} by float comparison:
+ *     ties at the threshold are all kept (K1 may hold more than top_k columns), and
+ *     the set depends on values alone, never on column order.
+ *  3. Top-p (skipped when top_p == 1). M is the maximum valid z and
+ *     w_c = tr_weight(z_c, M) for c in K1 (slimt_amd/csrc/truncation.h), an integer
+ *     in [0, 2^24]: 2^24 if z_c == M (tested first, so M = +-inf never evaluates
+ *     inf - inf), else 0 if d = z_c - M <= -17.0f, else
+ *     (uint32_t)(tr_exp(d) * 16777216.0f), tr_exp an exponential with the same bits
+ *     on host and device. Q = sum over K1 of w_c as uint64. tau_p is the largest
+ *     value v among {z_c : c in K1} such that
+ *       (double)(sum of w_c over c in K1 with z_c >= v) >= (double)top_p * (double)Q
+ *     (one IEEE double product; both sides exact integers below 2^53).
+ *     K = {c in K1 : z_c >= tau_p}: ties at the boundary are kept, and K always
+ *     holds the maximal columns. Without top-p, K = K1.
+ *  4. The token is the vocabulary id of the FIRST maximum over c in K of
+ *     key_c = fmaf(l_c, inv_T, g(k_b, t, y_c)) as in slimt_hip_ctx_set_sampling:
+ *     start value -FLT_MAX, strict >, the lowest column wins a tie, and "logit 0 is
+ *     NaN -> class 0" holds.
+ *  5. The score is log softmax of z over K at the drawn column:
+ *     forced_score(sum over K of exp(z_c - M), z_token - M, none)
+ *     (slimt_amd/csrc/scores.h). A row whose logits hold a NaN anywhere, kept or
+ *     not, scores NaN.
+ * Forced steps (slimt_hip_ctx_set_target_prefix) draw nothing, so nothing is
+ * truncated: they are recorded, fed and scored over the WHOLE layer at the
+ * temperature, as in an untruncated sampled call. A forced token outside the layer
+ * scores -inf (or NaN) either way.
+ * A sentence's truncated translation depends on its key, the temperature, top_k and
+ * top_p and on nothing else: not on its row, its neighbours, the decode mode, the
+ * entry point or the shortlist's layout.
+ * Execution: the threshold needs the whole row before the draw, and the persistent
+ * decoder never stores logits. A truncated call therefore DECODES with the per-stage
+ * kernels (as decode mode 1 does, K/V cache format 3 included) whatever mode the
+ * context is in, with the logits gemm storing the row and one selection kernel
+ * (slimt_amd/csrc/sample_truncate.hip) per step; its encoder is the one the
+ * context's mode chooses. The context's mode itself is not changed, and
+ * slimt_hip_ctx_plan, which does not know about armed settings, keeps reporting it.
+ * The _many_ entry points do not merge a truncated call: it is translated batch by
+ * batch, in order, on the same stream, each batch within its own step limit. */
+int slimt_hip_ctx_set_sampling_truncation(slimt_hip_ctx *ctx, uint32_t top_k, float top_p);
 /* Which kernels a translate call with source length S would use in the current
  * mode: *encoder_fused / *decoder_fused = 1 for the persistent kernels, 0 for
  * the per-stage ones. */

@@ -14,6 +14,12 @@ extern "C" {
  * results' scores are log softmax(logit / temperature) at the drawn tokens. */
 int slimt_hip_service_set_sampling(slimt_hip_service *service, float temperature);
 
+/* Every sampled request is truncated to the top_k largest columns (0: no top-k) and the nucleus of mass top_p (finite,
+ * 0 < top_p <= 1; 1: no top-p): include/slimt_hip.h, slimt_hip_ctx_set_sampling_truncation. Service-wide, only after
+ * slimt_hip_service_set_sampling and before the first request. The engine does not merge truncated calls, so such a
+ * service sends every batch as a launch of its own. */
+int slimt_hip_service_set_sampling_truncation(slimt_hip_service *service, uint32_t top_k, float top_p);
+
 /* slimt_hip_service_translate on a sampling service, seeded: sentence i is drawn under the key
  * slimt_hip_sampling_key(seed, i), wherever the batcher puts it and whatever shares its launch, so a request's
  * translations depend on its sentences and its seed alone. prefix_tokens / prefix_offsets (both NULL: none): forced

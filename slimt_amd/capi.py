@@ -40,6 +40,7 @@ SYMBOLS = [
     "slimt_hip_translate_many_rows", "slimt_hip_translate_many_device", "slimt_hip_translate_many_async",
     "slimt_hip_debug_kv_recalibrations", "slimt_hip_translate_many_device_generated", "slimt_hip_translate_many_async_generated",
     "slimt_hip_ctx_set_scores", "slimt_hip_ctx_set_target_prefix", "slimt_hip_ctx_set_sampling", "slimt_hip_sampling_key",
+    "slimt_hip_ctx_set_sampling_truncation", "slimt_hip_sample_truncated",
     "slimt_hip_score", "slimt_hip_score_async", "slimt_hip_score_device", "slimt_hip_score_async_generated",
 ]
 
@@ -209,6 +210,8 @@ def lib():
     L.slimt_hip_ctx_set_sampling.argtypes = [vp, f32, vp, sz]
     L.slimt_hip_sampling_key.argtypes = [C.c_uint64, C.c_uint64]
     L.slimt_hip_sampling_key.restype = C.c_uint64
+    L.slimt_hip_ctx_set_sampling_truncation.argtypes = [vp, u32, f32]
+    L.slimt_hip_sample_truncated.argtypes = [vp, sz, sz, vp, f32, u32, f32, vp, vp, vp, vp, vp, vp]
     L.slimt_hip_ctx_plan.argtypes = [vp, sz, vp, vp]
     L.slimt_hip_translate.argtypes = [vp, vp, vp, sz, sz, vp, sz, f32, u32, vp, vp, vp]
     L.slimt_hip_translate_async.argtypes = [vp, vp, vp, sz, sz, vp, sz, f32, u32, vp, vp, vp]
@@ -277,6 +280,24 @@ def sampling_key(seed: int, index: int) -> int:
 def sampling_keys(seed: int, n: int, first: int = 0) -> np.ndarray:
     """the keys of sentences first .. first + n - 1 of a request seeded `seed` (uint64 [n])"""
     return np.array([sampling_key(seed, first + i) for i in range(n)], dtype=np.uint64)
+
+
+def sample_truncated(logits, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, ids=None, keys=None, steps=None):
+    """slimt_hip_sample_truncated: one truncated sampled step over logits [M, N] (float32). ids: the columns' vocabulary
+    ids (uint32 [N]; None: the column), keys: the rows' sentence keys (uint64 [M]; None: the row index), steps: the rows'
+    step (uint32 [M]; None: 0). Returns (columns uint32 [M], thresholds float32 [M], kept uint32 [M], scores float32 [M])."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    M, N = logits.shape
+    ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32)
+    keys = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint64)
+    steps = None if steps is None else np.ascontiguousarray(steps, dtype=np.uint32)
+    if (ids is not None and ids.shape != (N,)) or (keys is not None and keys.shape != (M,)) or (steps is not None and steps.shape != (M,)):
+        raise ValueError("sample_truncated: ids [N], keys [M] and steps [M] expected")
+    cols, thr = np.zeros(M, np.uint32), np.zeros(M, np.float32)
+    kept, sc = np.zeros(M, np.uint32), np.zeros(M, np.float32)
+    _chk(lib().slimt_hip_sample_truncated(_p(logits), M, N, _p(ids), float(temperature), int(top_k), float(top_p), _p(keys),
+                                          _p(steps), _p(cols), _p(thr), _p(kept), _p(sc)))
+    return cols, thr, kept, sc
 
 
 def translate_many_rows(sizes) -> int:
@@ -652,6 +673,12 @@ class Context:
         arr = (C.c_void_p * max(1, len(addrs)))(*[a or None for a in addrs])
         _chk(lib().slimt_hip_ctx_set_sampling(self.h, float(temperature), arr, len(addrs)))
 
+    def set_sampling_truncation(self, top_k: int = 0, top_p: float = 1.0):
+        """slimt_hip_ctx_set_sampling_truncation: truncate the NEXT translate call's sampling (armed with set_sampling) to
+        the top_k largest columns (0: no top-k) and the nucleus of mass top_p (1.0: no top-p). The translate wrappers take
+        `truncation=(top_k, top_p)` beside `sampling=` and do this."""
+        _chk(lib().slimt_hip_ctx_set_sampling_truncation(self.h, int(top_k), float(top_p)))
+
     @staticmethod
     def _sampling_host(sampling, B: int):
         """(temperature, keys uint64 [B] | None) of a host call's `sampling=` (shape checked)"""
@@ -684,7 +711,7 @@ class Context:
         return bool(e.value), bool(d.value)
 
     def translate(self, ids, lengths, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                  want_align: bool = False, scores: bool = False, prefix=None, sampling=None):
+                  want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None):
         """Model::forward. Returns out_ids [B,Tmax], out_len [B], align|None (+ scores [B,Tmax] float32 with
         scores=True: the log-probability of each recorded token, include/slimt_hip.h slimt_hip_ctx_set_scores).
         prefix: (ids [B,Tmax], lens [B]) uint32 -- forced target prefixes (slimt_hip_ctx_set_target_prefix).
@@ -709,6 +736,8 @@ class Context:
         if sampling is not None:
             sm_t, sm_keys = self._sampling_host(sampling, B)
             self.set_sampling(sm_t, [sm_keys])
+        if truncation is not None:
+            self.set_sampling_truncation(*truncation)
         _chk(lib().slimt_hip_translate(self.h, _p(ids), _p(lengths), B, S, _p(sl),
                                        0 if sl is None else sl.size, limit_factor, eos_id,
                                        _p(out_ids), _p(out_len), _p(align)))
@@ -724,7 +753,7 @@ class Context:
                 pin("al").array(np.float32, (B, T, S)) if want_align else None)
 
     def translate_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
-                        scores=None, prefix=None, sampling=None):
+                        scores=None, prefix=None, sampling=None, truncation=None):
         """slimt_hip_translate_async[_generated] on arrays from pinned_buffers() (already filled);
         synchronize() before reading the outputs. `generator`: a ShortlistGenerator -- the batch's
         lexical shortlist is then generated on this context's stream (Model.cc:117-120).
@@ -743,6 +772,8 @@ class Context:
         if sampling is not None:
             sm_t, sm_keys = self._sampling_host(sampling, B)
             self.set_sampling(sm_t, [sm_keys])
+        if truncation is not None:
+            self.set_sampling_truncation(*truncation)
         if generator is not None:
             _chk(lib().slimt_hip_translate_async_generated(self.h, generator.h, _p(p_ids), _p(p_len), B, S,
                                                            limit_factor, eos_id, _p(p_out), _p(p_ol), _p(p_al)))
@@ -751,7 +782,7 @@ class Context:
                                              limit_factor, eos_id, _p(p_out), _p(p_ol), _p(p_al)))
 
     def translate_pinned(self, ids, lengths, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                         want_align: bool = False, generator=None, scores: bool = False, prefix=None, sampling=None):
+                         want_align: bool = False, generator=None, scores: bool = False, prefix=None, sampling=None, truncation=None):
         """translate() through this context's pinned staging buffers and slimt_hip_translate_async:
         the persistent kernels then read and write host memory themselves, no copy is queued (host
         pipelines with several contexts: copies of one stream wait behind other streams' kernels).
@@ -762,13 +793,14 @@ class Context:
         bufs[0][...] = ids
         bufs[1][...] = lengths
         sc = self._pinned.setdefault("sc", _Pinned()).array(np.float32, bufs[2].shape) if scores else None
-        self.translate_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix, sampling=sampling)
+        self.translate_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix, sampling=sampling,
+                             truncation=truncation)
         self.synchronize()
         out = bufs[2].copy(), bufs[3].copy(), (bufs[4].copy() if want_align else None)
         return out + (sc.copy(),) if scores else out
 
     def translate_generated(self, generator, ids, lengths, limit_factor: float = 1.5, eos_id: int = 0,
-                            want_align: bool = False, scores: bool = False, prefix=None, sampling=None):
+                            want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None):
         """Model::forward with its shortlist step (slimt_hip_translate_generated): host arrays, blocking.
         prefix: as in translate()."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
@@ -787,6 +819,8 @@ class Context:
         if sampling is not None:
             sm_t, sm_keys = self._sampling_host(sampling, B)
             self.set_sampling(sm_t, [sm_keys])
+        if truncation is not None:
+            self.set_sampling_truncation(*truncation)
         _chk(lib().slimt_hip_translate_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, limit_factor,
                                                  eos_id, _p(out_ids), _p(out_len), _p(align)))
         self._prefix_keep = []  # (a blocking call: done with its prefix)
@@ -863,7 +897,7 @@ class Context:
 
     def translate_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int,
                          n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int,
-                         d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None):
+                         d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None, truncation=None):
         """Device pointers (ints) in and out; asynchronous when steps_hint > 0. scores: a device pointer to
         [B, Tmax] floats for the tokens' log-probabilities (0 = none). prefix: (d_ids, d_lens) device pointers of a
         forced target prefix ([B, Tmax] and [B] uint32)."""
@@ -877,10 +911,12 @@ class Context:
             self.set_target_prefix([prefix])
         if sampling is not None:  # (temperature, device pointer of the [B] uint64 keys or 0 / None)
             self.set_sampling(sampling[0], [sampling[1]])
+        if truncation is not None:
+            self.set_sampling_truncation(*truncation)
         _chk(lib().slimt_hip_translate_device(*args))
 
     def translate_many_device(self, batches, S: int, limit_factor: float, eos_id: int, steps_hint: int = 0, generator=None,
-                              scores=None, prefix=None, sampling=None):
+                              scores=None, prefix=None, sampling=None, truncation=None):
         """slimt_hip_translate_many_device: `batches` = [(d_ids, d_lengths, B, d_shortlist, n_shortlist, d_out_ids,
         d_out_len, d_align[, S_j])] of device pointers (ints; 0 = none) -- ONE encoder and ONE decoder launch for all of them;
         S_j: that batch's own padded length (<= S; default S). scores: one device pointer per batch ([B_j, Tmax_j] floats).
@@ -897,13 +933,15 @@ class Context:
             self.set_target_prefix(list(prefix))
         if sampling is not None:  # (temperature, one device pointer of keys per batch | None)
             self.set_sampling(sampling[0], list(sampling[1]) if sampling[1] is not None else [None] * len(batches))
+        if truncation is not None:
+            self.set_sampling_truncation(*truncation)
         if generator is not None:
             _chk(lib().slimt_hip_translate_many_device_generated(self.h, generator.h, arr, len(batches), S, limit_factor, eos_id, steps_hint))
             return
         _chk(lib().slimt_hip_translate_many_device(self.h, arr, len(batches), S, limit_factor, eos_id, steps_hint))
 
     def translate_many_async(self, bufs_list, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0, generator=None,
-                             scores=None, prefix=None, sampling=None):
+                             scores=None, prefix=None, sampling=None, truncation=None):
         """slimt_hip_translate_many_async on a list of pinned buffer tuples (ids, lengths, out_ids, out_len, align|None),
         one shortlist (host array) or none for all; synchronize() before reading the outputs.
         scores: one float32 [B_j, Tmax_j] array per batch (pinned: the merged launch writes them in place).
@@ -935,6 +973,8 @@ class Context:
             if len(ks) != len(bufs_list):
                 raise ValueError(f"sampling: {len(ks)} key arrays for {len(bufs_list)} batches")
             self.set_sampling(sampling[0], [self._sampling_host((sampling[0], k), b[2].shape[0])[1] for k, b in zip(ks, bufs_list)])
+        if truncation is not None:
+            self.set_sampling_truncation(*truncation)
         if generator is not None:  # every batch's own lexical shortlist, generated inside the encoder launch
             _chk(lib().slimt_hip_translate_many_async_generated(self.h, generator.h, arr, len(bufs_list), S, limit_factor, eos_id))
             return
@@ -942,7 +982,7 @@ class Context:
 
     def translate_device_generated(self, gen: "ShortlistGenerator", d_ids: int, d_lengths: int, B: int,
                                    S: int, limit_factor: float, eos_id: int, d_out_ids: int,
-                                   d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None):
+                                   d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None, truncation=None):
         """Shortlist generation + translate, all on this context's stream. scores, prefix: as in translate_device."""
         vp = C.c_void_p
         args = (self.h, gen.h, vp(d_ids), vp(d_lengths), B, S, limit_factor, eos_id, vp(d_out_ids),
@@ -953,6 +993,8 @@ class Context:
             self.set_target_prefix([prefix])
         if sampling is not None:  # (temperature, device pointer of the [B] uint64 keys or 0 / None)
             self.set_sampling(sampling[0], [sampling[1]])
+        if truncation is not None:
+            self.set_sampling_truncation(*truncation)
         _chk(lib().slimt_hip_translate_device_generated(*args))
 
     def encode(self, ids, lengths, want_embed=False, want_layers=False):
@@ -1098,6 +1140,7 @@ def host_lib():
     H.slimt_hip_service_translate_prefixed.argtypes = [vp, vp, vp, vp, vp, sz, vp]  # (include/slimt_hip_service_prefix.h)
     H.slimt_hip_service_set_sampling.argtypes = [vp, C.c_float]  # (include/slimt_hip_service_sampling.h)
     H.slimt_hip_service_translate_sampled.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, sz, vp]
+    H.slimt_hip_service_set_sampling_truncation.argtypes = [vp, C.c_uint32, C.c_float]
     H.slimt_hip_service_score.argtypes = [vp, vp, vp, vp, vp, sz, vp]  # (include/slimt_hip_service_score.h)
     _host_lib = H
     return H
@@ -1178,9 +1221,10 @@ class BatchService:
                  workers_per_device: int = 6, pad_id: int = 0, eos_id: int = 0, alignments: bool = True,
                  lexical_shortlist: bytes = b"", source_vocab: int = 0, target_vocab: int = 0,
                  shared_vocab: bool = False, check: bool = False, shortlist=None, merge_batches: int = 0, merge_words: int = 0,
-                 scores: bool = False, temperature: float = 0.0):
+                 scores: bool = False, temperature: float = 0.0, truncation=None):
         """temperature > 0: every request is sampled at that temperature (slimt_hip_service_set_sampling; translate(...,
-        seed=)). merge_batches / merge_words: merged launches (0 = the library's defaults: up to 8 consecutive batches of one padded
+        seed=)); truncation=(top_k, top_p): ... from the top_k largest columns and the nucleus of mass top_p
+        (slimt_hip_service_set_sampling_truncation; such a service never merges batches). merge_batches / merge_words: merged launches (0 = the library's defaults: up to 8 consecutive batches of one padded
         length per launch pair within 8192 words; merge_batches = 1: never). scores: every result carries its target tokens'
         log-probabilities (ServiceResult.scores / token_scores; slimt_hip_service_set_scores)."""
         self._keep = []
@@ -1207,6 +1251,11 @@ class BatchService:
             raise SlimtHipError(err)
         self.temperature = float(temperature)
         if temperature and host_lib().slimt_hip_service_set_sampling(self.h, float(temperature)):
+            err = host_lib().slimt_hip_service_last_error().decode()
+            self.close()
+            raise SlimtHipError(err)
+        if truncation is not None and host_lib().slimt_hip_service_set_sampling_truncation(
+                self.h, int(truncation[0]), float(truncation[1])):
             err = host_lib().slimt_hip_service_last_error().decode()
             self.close()
             raise SlimtHipError(err)

@@ -2,6 +2,8 @@
 #include "engine.h"
 #include "decoder_plan.h"
 #include "sampling.h"
+#include "scores.h"
+#include "truncation.h"
 
 #include <algorithm>
 #include <atomic>
@@ -50,7 +52,10 @@ static std::atomic<bool> g_hip_called{false};
 
 // The persistent decoder runs the hoisted cross-attention order over a cache of accumulators; the reference's literal
 // sequence (K/V cache format 3) exists in the stage-wise attention kernel only (decode_kernels.hip, DQAttnArgs::literal)
-static bool fused_decoder_allowed(const slimt_hip_ctx *c) { return c->decode_mode != 1 && c->model->kv_format != 3; }
+// ... and a truncated sampled call (TruncationCall) needs each step's whole row of logits, which only the stage-wise decoder
+// stores. Every decision that hangs on the persistent decoder -- the lean path, pinned arrays read in place, merged launches --
+// asks here; the encoder is chosen as the context's mode says.
+static bool fused_decoder_allowed(const slimt_hip_ctx *c) { return c->decode_mode != 1 && c->model->kv_format != 3 && !c->tr_call; }
 
 // The narrow K/V form for this model's next batch (engine.h, kv_auto_wide): format 0, and the sentences so far mostly fit.
 // Called under the model's submit / gate discipline by encode_device; the counter lags the device by a few batches.
@@ -460,6 +465,64 @@ extern "C" int slimt_hip_softmax(const float *x, size_t rows, size_t cols, float
   HIPCHK(launch_softmax(t.a.as<float>(), (int)rows, (int)cols, t.b.as<float>(), st));
   HIPCHK(hipMemcpyAsync(y, t.b.p, rows * cols * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+extern "C" int slimt_hip_sample_truncated(const float *logits, size_t M, size_t N, const uint32_t *ids, float temperature,
+                                          uint32_t top_k, float top_p, const uint64_t *keys, const uint32_t *steps,
+                                          uint32_t *columns, float *thresholds, uint32_t *kept, float *scores) {
+  if (!(temperature > 0.0f) || !std::isfinite(temperature)) return fail(-1, "sampling: temperature %g is not finite and > 0", (double)temperature);
+  const float inv_T = 1.0f / temperature;
+  if (!(inv_T > 0.0f) || !std::isfinite(inv_T)) return fail(-1, "sampling: 1 / temperature %g is not finite and > 0", (double)temperature);
+  if (!(top_p > 0.0f && top_p <= 1.0f)) return fail(-1, "sampling truncation: top_p %g is not in (0, 1]", (double)top_p);
+  if (!logits || !columns || !thresholds || !kept || !scores || !M || !N) return fail(-1, "bad argument");
+  if (M > 0x7fffffffu || N > (size_t)kSampleTruncMaxN) return fail(-1, "sample_truncated: more than %d rows or %d columns", 0x7fffffff, kSampleTruncMaxN);
+  std::vector<uint32_t> seeds(2 * M);  // the rows' hash words (sampling.h), as decode_begin_step_sm_kernel writes them
+  for (size_t r = 0; r < M; ++r) {
+    const uint64_t w = slimt_hip::sm_step_words(keys ? keys[r] : (uint64_t)r, steps ? steps[r] : 0u);
+    seeds[r] = (uint32_t)w;
+    seeds[M + r] = (uint32_t)(w >> 32);
+  }
+  Tmp3 t;
+  hipStream_t st = nullptr;
+  HIPCHK(t.a.reserve(M * N * 4));
+  HIPCHK(t.b.reserve(N * 4));
+  HIPCHK(t.c.reserve(2 * M * 4));
+  HIPCHK(t.d.reserve(7 * M * 4));
+  HIPCHK(hipMemcpyAsync(t.a.p, logits, M * N * 4, hipMemcpyHostToDevice, st));
+  if (ids) HIPCHK(hipMemcpyAsync(t.b.p, ids, N * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.p, seeds.data(), 2 * M * 4, hipMemcpyHostToDevice, st));
+  SampleTruncArgs a;
+  a.logits = t.a.as<float>();
+  a.B = (int)M;
+  a.N = (int)N;
+  a.inv_T = inv_T;
+  a.top_k = top_k;
+  a.top_p = top_p;
+  a.seeds = t.c.as<uint32_t>();
+  a.shortlist = ids ? t.b.as<uint32_t>() : nullptr;
+  float *o = t.d.as<float>();
+  a.part_val = o;
+  a.part_idx = reinterpret_cast<int *>(o + M);
+  a.part_sum = o + 2 * M;
+  a.part_mz = o + 3 * M;
+  a.part_zw = o + 4 * M;
+  a.thresholds = o + 5 * M;
+  a.kept = reinterpret_cast<uint32_t *>(o + 6 * M);
+  HIPCHK(launch_sample_truncated(a, st));
+  std::vector<float> h(7 * M);
+  HIPCHK(hipMemcpyAsync(h.data(), t.d.p, 7 * M * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (size_t r = 0; r < M; ++r) {
+    int col;
+    memcpy(&col, &h[M + r], 4);
+    // the "none" rule of decode_begin_step_sm_kernel: no key beat the start value, or logit 0 is NaN -- class 0, score NaN
+    const bool none = col == 0x7fffffff || logits[r * N] != logits[r * N];
+    columns[r] = none ? 0u : (uint32_t)col;
+    scores[r] = slimt_hip::forced_score(h[2 * M + r], h[4 * M + r] - h[3 * M + r], none);
+    thresholds[r] = h[5 * M + r];
+    memcpy(&kept[r], &h[6 * M + r], 4);
+  }
   return 0;
 }
 
@@ -1074,7 +1137,7 @@ void sinusoid_table(int S, int D, std::vector<float> &out) {
 void ctx_free(slimt_hip_ctx *c) {
   DevBuf *bufs[] = {&c->pos, &c->ids, &c->lengths, &c->x0, &c->x1, &c->q, &c->k, &c->v, &c->att,
                     &c->h8, &c->a8, &c->ticket, &c->kv, &c->kv_fmt, &c->cl_act, &c->cl_part, &c->cl_sync, &c->dx, &c->dx_pre, &c->dh, &c->datt8, &c->dout, &c->df8,
-                    &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->prev, &c->out_ids, &c->out_len,
+                    &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->tr_logits, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag,
                     &c->score_ws, &c->score_io};
@@ -1324,6 +1387,16 @@ extern "C" int slimt_hip_ctx_set_sampling(slimt_hip_ctx *ctx, float temperature,
     ctx->sm_next_keys.assign(n, nullptr);
   ctx->sm_next_inv_T = inv_T;
   ctx->sm_armed = n > 0;  // (n = 0: nothing armed)
+  return 0;
+}
+
+extern "C" int slimt_hip_ctx_set_sampling_truncation(slimt_hip_ctx *ctx, uint32_t top_k, float top_p) {
+  // (the value first, like the temperature)
+  if (!(top_p > 0.0f && top_p <= 1.0f)) return fail(-1, "sampling truncation: top_p %g is not in (0, 1]", (double)top_p);
+  if (!ctx) return fail(-1, "null argument");
+  ctx->tr_next_k = top_k;
+  ctx->tr_next_p = top_p;
+  ctx->tr_armed = top_k != 0 || top_p != 1.0f;  // (both off: nothing armed, the call is today's sampled call)
   return 0;
 }
 
@@ -1619,6 +1692,30 @@ struct SampleCall {
     if (!c) return;
     c->sm_call = false;
     c->sm_user_keys = c->sm_keys = nullptr;
+  }
+};
+
+// The truncation armed on a context (slimt_hip_ctx_set_sampling_truncation), taken by the next translate entry point behind
+// its SampleCall, whether it then succeeds or fails; without sampling armed that call fails. A truncated call needs the
+// whole row of logits before it draws: while tr_call is set fused_decoder_allowed() is false, so the call decodes with the
+// per-stage kernels and is never merged; the context's decode mode is not touched and still chooses the encoder.
+struct TruncationCall {
+  slimt_hip_ctx *c = nullptr;
+  int rc = 0;
+  explicit TruncationCall(slimt_hip_ctx *ctx) {
+    if (!ctx || !ctx->tr_armed) return;
+    ctx->tr_armed = false;
+    if (!ctx->sm_call) {
+      rc = fail(-1, "sampling truncation: armed without sampling (slimt_hip_ctx_set_sampling)");
+      return;
+    }
+    c = ctx;
+    ctx->tr_call = true;
+    ctx->tr_k = ctx->tr_next_k;
+    ctx->tr_p = ctx->tr_next_p;
+  }
+  ~TruncationCall() {
+    if (c) c->tr_call = false;
   }
 };
 
@@ -2565,7 +2662,11 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     c->ticket_base += tickets;
     return 0;
   }
-  const int n_parts = dgemm_col_blocks(out.w.K, out.w.N, (int)B);
+  // a truncated call (TruncationCall) stores each step's logits and selects over them: one partial per row (sample_truncate.hip)
+  const bool truncated = sampled && c->tr_call;
+  if (c->tr_call && !truncated) return fail(-1, "sampling truncation: the call is not sampled");
+  const int n_parts = truncated ? 1 : dgemm_col_blocks(out.w.K, out.w.N, (int)B);
+  if (truncated) HIPCHK(c->tr_logits.reserve(B * (size_t)out.w.N * 4));
   const EmbedArgs e = embed_args(c);
   if (d_scores) HIPCHK(c->part_sum.reserve(B * (size_t)n_parts * 4));
   float *const part_sum = d_scores ? c->part_sum.as<float>() : nullptr;
@@ -2629,11 +2730,35 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
       g.part_mz = c->sm_part_mz.as<float>();
       g.part_zw = c->sm_part_zw.as<float>();
     }
+    if (truncated) {
+      g.y = c->tr_logits.as<float>();
+      g.ldy = out.w.N;
+    }
     {
       ProfScope p(c, SLIMT_HIP_K_LOGITS, gemm_macs((int)B, out.w), gemm_bytes(out.w));
-      he = launch_dgemm(g, sampled ? EPI_ARGMAX_SM : fs.ids ? EPI_ARGMAX_FP : d_scores ? EPI_ARGMAX_SC : EPI_ARGMAX, st);
+      he = launch_dgemm(g, truncated ? EPI_PLAIN : sampled ? EPI_ARGMAX_SM : fs.ids ? EPI_ARGMAX_FP : d_scores ? EPI_ARGMAX_SC : EPI_ARGMAX, st);
     }
     if (he != hipSuccess) { rc = fail((int)he, "logits gemm: %s", hipGetErrorString(he)); break; }
+    if (truncated) {
+      SampleTruncArgs ta;
+      ta.logits = c->tr_logits.as<float>();
+      ta.B = (int)B;
+      ta.N = out.w.N;
+      ta.inv_T = ss.inv_T;
+      ta.top_k = c->tr_k;
+      ta.top_p = c->tr_p;
+      ta.seeds = ss.seeds;
+      ta.shortlist = ds.shortlist;
+      ta.fcol = g.fcol;
+      ta.part_val = g.part_val;
+      ta.part_idx = g.part_idx;
+      ta.part_sum = g.part_sum;
+      ta.part_mz = g.part_mz;
+      ta.part_zw = g.part_zw;
+      ta.part_y = g.part_y;
+      he = launch_sample_truncated(ta, st);
+      if (he != hipSuccess) { rc = fail((int)he, "truncated sampling: %s", hipGetErrorString(he)); break; }
+    }
   }
   if (!rc && !all_done) {
     hipError_t he = launch_decode_begin_step(e, ds, (int)B, 0, 0, c->part_val.as<float>(),
@@ -2724,9 +2849,11 @@ extern "C" int slimt_hip_translate_device(slimt_hip_ctx *ctx, const uint32_t *d_
   ScoreCall sc(ctx, 1);
   PrefixCall pc(ctx, 1);
   SampleCall smc(ctx, 1);
+  TruncationCall trc(ctx);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
   if (smc.rc) return smc.rc;
+  if (trc.rc) return trc.rc;
   if (!ctx || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len) return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
   if (n_shortlist > (size_t)ctx->model->V) return fail(-1, "shortlist larger than the vocabulary");
@@ -2838,9 +2965,11 @@ extern "C" int slimt_hip_translate(slimt_hip_ctx *ctx, const uint32_t *src_ids,
   ScoreCall sc(ctx, 1);
   PrefixCall pc(ctx, 1);
   SampleCall smc(ctx, 1);
+  TruncationCall trc(ctx);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
   if (smc.rc) return smc.rc;
+  if (trc.rc) return trc.rc;
   return translate_host(ctx, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, true);
 }
@@ -2853,9 +2982,11 @@ extern "C" int slimt_hip_translate_async(slimt_hip_ctx *ctx, const uint32_t *src
   ScoreCall sc(ctx, 1);
   PrefixCall pc(ctx, 1);
   SampleCall smc(ctx, 1);
+  TruncationCall trc(ctx);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
   if (smc.rc) return smc.rc;
+  if (trc.rc) return trc.rc;
   return translate_host(ctx, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, false);
 }
@@ -2960,15 +3091,17 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
   ScoreCall sc(ctx, n_batches);
   PrefixCall pc(ctx, n_batches);
   SampleCall smc(ctx, n_batches);
+  TruncationCall trc(ctx);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
   if (smc.rc) return smc.rc;
+  if (trc.rc) return trc.rc;
   if (!ctx || !batches || n_batches == 0) return fail(-1, "null argument");
   HIPCHK(hipSetDevice(ctx->model->device));
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
   MergePlan mp;
   size_t rows = 0;
-  const bool mergeable = n_batches > 1 && n_batches <= (size_t)kMaxMerge;
+  const bool mergeable = n_batches > 1 && n_batches <= (size_t)kMaxMerge && !ctx->tr_call;  // (truncated: batch by batch)
   size_t n_cols = 0;  // the widest output layer of the launch
   for (size_t j = 0; j < n_batches; ++j) n_cols = std::max(n_cols, batches[j].n_shortlist ? batches[j].n_shortlist : (size_t)ctx->model->V);
   if (mergeable)
@@ -2991,8 +3124,13 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
       ctx->fp_user_len = pc.len[j];
     }
     if (ctx->sm_call) ctx->sm_user_keys = smc.keys[j];
-    RCCHK(slimt_hip_translate_device(ctx, b.src_ids, b.lengths, b.B, b.S ? b.S : S, b.shortlist, b.n_shortlist, limit_factor,
-                                     eos_id, b.out_ids, b.out_len, b.align, steps_hint));
+    // (a truncated call is never merged, so it must give here what a merged launch gives: the launch's step budget is the
+    // longest batch's, and a shorter batch takes at most its own Tmax_j -- build_merge_plan's rule. Other calls that come
+    // this way keep the budget as given, as before.)
+    const size_t Sj = b.S ? b.S : S, Tj = std::max<size_t>(1, (size_t)(limit_factor * (float)Sj));
+    const int hint = ctx->tr_call && steps_hint > 0 ? std::min(steps_hint, (int)Tj) : steps_hint;
+    RCCHK(slimt_hip_translate_device(ctx, b.src_ids, b.lengths, b.B, Sj, b.shortlist, b.n_shortlist, limit_factor,
+                                     eos_id, b.out_ids, b.out_len, b.align, hint));
   }
   return 0;
 }
@@ -3002,14 +3140,16 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   ScoreCall sc(ctx, n_batches);
   PrefixCall pc(ctx, n_batches);
   SampleCall smc(ctx, n_batches);
+  TruncationCall trc(ctx);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
   if (smc.rc) return smc.rc;
+  if (trc.rc) return trc.rc;
   if (!ctx || !batches || n_batches == 0) return fail(-1, "null argument");
   const slimt_hip_model *m = ctx->model;
   HIPCHK(hipSetDevice(m->device));
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
-  bool merged = n_batches > 1 && n_batches <= (size_t)kMaxMerge && S <= ctx->max_S;
+  bool merged = n_batches > 1 && n_batches <= (size_t)kMaxMerge && S <= ctx->max_S && !ctx->tr_call;
   slimt_hip_batch dev[kMaxMerge];
   float *dev_sc[kMaxMerge] = {};  // (scored: the device views of the pinned score arrays)
   bool any_align = false;
@@ -3472,9 +3612,11 @@ extern "C" int slimt_hip_translate_device_generated(slimt_hip_ctx *ctx, slimt_hi
   ScoreCall sc(ctx, 1);
   PrefixCall pc(ctx, 1);
   SampleCall smc(ctx, 1);
+  TruncationCall trc(ctx);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
   if (smc.rc) return smc.rc;
+  if (trc.rc) return trc.rc;
   if (!ctx || !sl || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len)
     return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
@@ -3588,7 +3730,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
     any_align = any_align || dev[j].align != nullptr;
   }
   static const bool fold = !(std::getenv("SLIMT_SHORTLIST_FOLD") && std::getenv("SLIMT_SHORTLIST_FOLD")[0] == '0');
-  const bool merged = n > 1 && n <= (size_t)kMaxMerge && S <= ctx->max_S && rows <= ctx->max_B && rows * S <= ctx->max_M &&
+  const bool merged = n > 1 && n <= (size_t)kMaxMerge && !ctx->tr_call && S <= ctx->max_S && rows <= ctx->max_B && rows * S <= ctx->max_M &&
                       merge_supported(ctx, rows, S) && fold &&
                       shortlist_in_launch_lds_bytes((int)sl->source_vocab, (int)sl->target_vocab) <= 64 * 1024;
   if (!merged && host) {
@@ -3672,9 +3814,11 @@ extern "C" int slimt_hip_translate_many_device_generated(slimt_hip_ctx *ctx, sli
   ScoreCall sc(ctx, n_batches);
   PrefixCall pc(ctx, n_batches);
   SampleCall smc(ctx, n_batches);
+  TruncationCall trc(ctx);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
   if (smc.rc) return smc.rc;
+  if (trc.rc) return trc.rc;
   if (!ctx || !sl || !batches || n_batches == 0) return fail(-1, "null argument");
   RCCHK(check_generator(ctx, sl));
   for (size_t j = 0; j < n_batches; ++j) {
@@ -3693,9 +3837,11 @@ extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slim
   ScoreCall sc(ctx, n_batches);
   PrefixCall pc(ctx, n_batches);
   SampleCall smc(ctx, n_batches);
+  TruncationCall trc(ctx);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
   if (smc.rc) return smc.rc;
+  if (trc.rc) return trc.rc;
   if (!ctx || !sl || !batches || n_batches == 0) return fail(-1, "null argument");
   RCCHK(check_generator(ctx, sl));
   const slimt_hip_model *m = ctx->model;
@@ -3751,9 +3897,11 @@ extern "C" int slimt_hip_translate_generated(slimt_hip_ctx *ctx, slimt_hip_short
   ScoreCall sc(ctx, 1);
   PrefixCall pc(ctx, 1);
   SampleCall smc(ctx, 1);
+  TruncationCall trc(ctx);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
   if (smc.rc) return smc.rc;
+  if (trc.rc) return trc.rc;
   return translate_host_generated(ctx, sl, src_ids, lengths, B, S, limit_factor, eos_id, out_ids, out_len, align, true);
 }
 
@@ -3764,9 +3912,11 @@ extern "C" int slimt_hip_translate_async_generated(slimt_hip_ctx *ctx, slimt_hip
   ScoreCall sc(ctx, 1);
   PrefixCall pc(ctx, 1);
   SampleCall smc(ctx, 1);
+  TruncationCall trc(ctx);
   if (sc.rc) return sc.rc;
   if (pc.rc) return pc.rc;
   if (smc.rc) return smc.rc;
+  if (trc.rc) return trc.rc;
   return translate_host_generated(ctx, sl, src_ids, lengths, B, S, limit_factor, eos_id, out_ids, out_len, align, false);
 }
 

@@ -217,6 +217,14 @@ struct slimt_hip_ctx {
   const uint64_t *sm_keys = nullptr;         // ... as the kernels read them
   slimt_hip::DevBuf sm_stage;                // device staging of pageable host keys
   slimt_hip::DevBuf sm_seeds, sm_part_mz, sm_part_zw;  // the step-wise path's hash words and partials (kernels.h, SampledStep)
+  // truncation of sampled calls (slimt_hip_ctx_set_sampling_truncation): armed for the NEXT translate call beside the sampling
+  bool tr_armed = false;
+  uint32_t tr_next_k = 0;
+  float tr_next_p = 1.0f;
+  bool tr_call = false;         // the call in progress is truncated (engine.cpp, TruncationCall): per-stage decoder, never merged
+  uint32_t tr_k = 0;            // ... to the top_k largest (0: no top-k)
+  float tr_p = 1.0f;            // ... and the nucleus of mass top_p (1: no top-p)
+  slimt_hip::DevBuf tr_logits;  // [B][N] f32: the step's logits, reserved by the first truncated call
   slimt_hip::DevBuf prev, out_ids, out_len, finished, n_finished, align;
   slimt_hip::DevBuf shortlist;
   slimt_hip::DevBuf sl_scratch;  // bitmaps of slimt_hip_shortlist_generate_device (kept zeroed)

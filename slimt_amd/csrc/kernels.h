@@ -676,6 +676,32 @@ struct ScoreOutArgs {
 hipError_t launch_score_output(const ScoreOutArgs &a, hipStream_t st);
 bool score_supported(int D, int H);  // D in {64, 128, 256, 512}, d_head in {16, 32, 64}
 
+// ---- truncated sampling: top-k / nucleus selection over stored logits (sample_truncate.hip) -------------------------------
+// One sampled step of B rows whose output-layer logits [B][N] are in memory (the logits gemm with EPI_PLAIN): the kept set
+// of include/slimt_hip.h (slimt_hip_ctx_set_sampling_truncation; truncation.h) and, over it, one partial per row in
+// EPI_ARGMAX_SM's format (n_parts = 1), which decode_begin_step_sm_kernel consumes unchanged. A row with fcol[b] >= 0 (a
+// forced step) keeps every valid column.
+struct SampleTruncArgs {
+  const float *logits = nullptr;  // [B][N]
+  int B = 0, N = 0;
+  float inv_T = 0.0f;
+  uint32_t top_k = 0;  // 0: none
+  float top_p = 1.0f;  // 1: none
+  const uint32_t *seeds = nullptr;      // [2][B] the rows' hash words of this step (SampledStep::seeds)
+  const uint32_t *shortlist = nullptr;  // [N] the columns' vocabulary ids (nullptr: the column)
+  const int *fcol = nullptr;            // nullable [B]
+  float *part_val = nullptr;            // [B] best key over the kept set (-FLT_MAX: none)
+  int *part_idx = nullptr;              // [B] ... its column (0x7fffffff: none)
+  float *part_sum = nullptr;            // [B] sum of exp(z - M) over the kept set; NaN where the row holds a NaN
+  float *part_mz = nullptr;             // [B] M, the maximum valid z
+  float *part_zw = nullptr;             // [B] z of the best key's column
+  float *part_y = nullptr;              // nullable [B] z at fcol[b], -inf where there is none
+  float *thresholds = nullptr;          // nullable [B] max(tau_k, tau_p), -inf where nothing is cut
+  uint32_t *kept = nullptr;             // nullable [B] the size of the kept set
+};
+constexpr int kSampleTruncMaxN = 0x7fffffff - 256;  // the column loops step an int by the workgroup's 256 threads
+hipError_t launch_sample_truncated(const SampleTruncArgs &a, hipStream_t st);
+
 // the column means (rounded) of an f32 K/V cache [Ld][K, V][B * S][D]: centre[(2 l + p) * D + d] (FusedDecodeArgs::kv_centre)
 hipError_t launch_kv_centres(const float *kv, int Ld, int B, int S, int D, unsigned long long *sums, int *centre, hipStream_t st);
 

@@ -226,7 +226,7 @@ class Service:
         step = self.ENGINE_LIMIT - 1
         return [body[i:i + step] + [eos] for i in range(0, len(body), step)]
 
-    def _engine(self, model: Model, scores: bool = False, temperature: float = 0.0) -> "capi.BatchService":
+    def _engine(self, model: Model, scores: bool = False, temperature: float = 0.0, truncation=None) -> "capi.BatchService":
         """The C++ batching service for `model` (host/Service.{hh,cc} behind include/slimt_hip_service.h):
         token-budget batches under the rule of _batches, `workers` double-buffered workers with pinned
         staging, the batch's lexical shortlist generated on the device (Model.cc:117-120). Units,
@@ -235,9 +235,11 @@ class Service:
         is a sampling one for each temperature: the temperature is a service-wide setting of the C++ service, so every
         distinct temperature a caller uses keeps its own service -- workers, contexts and pinned staging -- until close().
         None is evicted before that (another thread's call may be in flight on it): a caller that sweeps temperatures
-        closes the Service between them, or uses capi.Context.set_sampling, where the temperature is per call."""
+        closes the Service between them, or uses capi.Context.set_sampling, where the temperature is per call. The same
+        holds for each truncation (top_k, top_p) of a sampling service."""
+        trunc = None if truncation is None else (int(truncation[0]), float(truncation[1]))
         with self._lock:
-            eng = self._engines.get((model.id, scores, float(temperature)))
+            eng = self._engines.get((model.id, scores, float(temperature), trunc))
             if eng is None:
                 V = model.dims[2]
                 eng = capi.BatchService([model.engine], max_words=max(self.max_words, 1),
@@ -246,13 +248,15 @@ class Service:
                                         eos_id=model.vocabulary.eos_id(), alignments=True,
                                         lexical_shortlist=model.shortlist_blob, source_vocab=V, target_vocab=V,
                                         shared_vocab=False, check=False,  # as Model.cc:73-80 constructs it
-                                        scores=scores, temperature=float(temperature))
-                self._engines[(model.id, scores, float(temperature))] = eng
+                                        scores=scores, temperature=float(temperature), truncation=trunc)
+                self._engines[(model.id, scores, float(temperature), trunc)] = eng
         return eng
 
-    def _translate_segments(self, model: Model, per_request: List[List[List[int]]], scores: bool = False, sampling=None):
+    def _translate_segments(self, model: Model, per_request: List[List[List[int]]], scores: bool = False, sampling=None,
+                            truncation=None):
         """per request, per segment: (target ids, alignment, token scores | None). sampling: (temperature, seed) -- one
-        draw per segment under capi.sampling_key(seed, the segment's index in this call's flat list)"""
+        draw per segment under capi.sampling_key(seed, the segment's index in this call's flat list); truncation:
+        (top_k, top_p) of those draws"""
         eos = model.vocabulary.eos_id()
         flat, owner = [], []  # the sentences of the one request the C++ service gets; (request, index, piece)
         pieces_of = {}
@@ -275,7 +279,9 @@ class Service:
         if not flat:
             return histories
         if sampling is not None:
-            res = self._engine(model, scores, sampling[0]).translate(flat, seed=int(sampling[1]))
+            res = self._engine(model, scores, sampling[0], truncation).translate(flat, seed=int(sampling[1]))
+        elif truncation is not None:
+            raise ValueError("truncation: only with sampling=(temperature, seed)")
         else:
             res = self._engine(model, scores).translate(flat)
         targets, t_off = res.targets.copy(), res.target_offsets.astype(np.int64)
@@ -365,14 +371,16 @@ class Service:
         return out
 
     def translate(self, model: Model, texts: Sequence[str], html: bool = False,
-                  encoding: Encoding = Encoding.UTF8, scores: bool = False, sampling=None) -> List[Response]:
+                  encoding: Encoding = Encoding.UTF8, scores: bool = False, sampling=None, truncation=None) -> List[Response]:
         """scores: every Response also carries token_scores (per target sentence, each target token's log-probability,
         EOS included; a wrapped segment's pieces concatenated) and sentence_scores (their sums).
         sampling: (temperature, seed) -- each sentence is one draw from the model at that temperature instead of the
         greedy translation, reproducible for a seed: the key of a segment is capi.sampling_key(seed, its index among the
         call's segments), so the same call gives the same text whatever the batcher does; with scores=True the scores are
         the draws' log-probabilities at that temperature. A sampled call goes to the engine as one request. Every
-        distinct temperature keeps a batching service of its own until close() (_engine)."""
+        distinct temperature keeps a batching service of its own until close() (_engine).
+        truncation: (top_k, top_p) with sampling -- the draws come from the top_k most probable tokens (0: all) and the
+        nucleus of mass top_p (1.0: all) of each step (include/slimt_hip.h, slimt_hip_ctx_set_sampling_truncation)."""
         if html:
             raise NotImplementedError("HTML markup transfer is outside the ported path (SURVEY.md §2)")
         # Large calls go through in chunks of documents, pipelined: while the engine translates chunk k
@@ -380,9 +388,11 @@ class Service:
         # assembles the responses of chunk k - 1. Batches are formed per chunk (as they are per
         # arrival window in the reference's Async service).
         chunk = self.pipeline_documents
+        if truncation is not None and sampling is None:
+            raise ValueError("truncation: only with sampling=(temperature, seed)")
         if len(texts) <= chunk or sampling is not None:  # (sampled: one request, so that the segments' indices are the call's)
             processed = model.processor.process_many(texts, self.wrap_length, self.workers)
-            histories = self._translate_segments(model, [segs for _, segs in processed], scores, sampling)
+            histories = self._translate_segments(model, [segs for _, segs in processed], scores, sampling, truncation)
             out = self._respond_many(model, [src for src, _ in processed], histories)
         else:
             from concurrent.futures import ThreadPoolExecutor
@@ -432,17 +442,18 @@ class Service:
         return out
 
     def pivot(self, first: Model, second: Model, texts: Sequence[str], html: bool = False,
-              scores: bool = False, sampling=None) -> List[Response]:
-        """sampling: (temperature, seed) -- both hops sample, the first under seed and the second under seed + 1.
+              scores: bool = False, sampling=None, truncation=None) -> List[Response]:
+        """sampling: (temperature, seed) -- both hops sample, the first under seed and the second under seed + 1;
+        truncation: (top_k, top_p) of both hops' draws.
         source -> pivot with `first`, pivot -> target with `second`, sentence for sentence;
         alignments are marginalised over the pivot tokens (Response.cc:13-195). scores: the SECOND hop's scores --
         those of the final target tokens given the pivot text (the pivot's own probability is not in them)."""
         if html:
             raise NotImplementedError("HTML markup transfer is outside the ported path (SURVEY.md §2)")
-        firsts = self.translate(first, texts, encoding=Encoding.Byte, sampling=sampling)
+        firsts = self.translate(first, texts, encoding=Encoding.Byte, sampling=sampling, truncation=truncation)
         second_in = [second.processor.process_annotated(r.target) for r in firsts]
         histories = self._translate_segments(second, [segs for _, segs in second_in], scores,
-                                             None if sampling is None else (sampling[0], int(sampling[1]) + 1))
+                                             None if sampling is None else (sampling[0], int(sampling[1]) + 1), truncation)
         seconds = self._respond_many(second, [src for src, _ in second_in], histories)
         return [combine(r1, r2) for r1, r2 in zip(firsts, seconds)]
 

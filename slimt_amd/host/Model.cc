@@ -226,6 +226,12 @@ void Worker::score(slimt_hip_shortlist *generator, const uint32_t *ids, const ui
   }
 }
 
+#pragma weak slimt_hip_ctx_set_sampling_truncation
+void Worker::arm_sampling_truncation(uint32_t top_k, float top_p) {
+  if (!slimt_hip_ctx_set_sampling_truncation) throw std::runtime_error("this engine has no sampling truncation");
+  if (slimt_hip_ctx_set_sampling_truncation(ctx_, top_k, top_p)) raise("slimt_hip_ctx_set_sampling_truncation");
+}
+
 void Worker::wait() {
   if (slimt_hip_ctx_synchronize(ctx_)) raise("slimt_hip_ctx_synchronize");
 }

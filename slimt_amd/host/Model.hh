@@ -172,6 +172,8 @@ class Worker {
   // (slimt_hip_ctx_set_sampling); sampling_key: slimt_hip_sampling_key
   void arm_sampling(float temperature, const uint64_t *const *keys, size_t n);
   static uint64_t sampling_key(uint64_t seed, uint64_t index);
+  // ... truncates that sampling to the top_k largest and the nucleus of mass top_p (slimt_hip_ctx_set_sampling_truncation)
+  void arm_sampling_truncation(uint32_t top_k, float top_p);
   // Teacher-forced scoring of given targets in one pass over all target positions (include/slimt_hip.h, slimt_hip_score):
   // tgt_ids [B][T], tgt_len [B] (T is the caller's: no limit-factor cap), scores [B][T], align nullable [B][T][S]; entries
   // with t >= tgt_len[b] and alignment columns j >= lengths[b] are not written. Waits for the result; nothing armed on

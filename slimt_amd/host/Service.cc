@@ -324,6 +324,14 @@ bool Service::set_sampling(float temperature) {
   return true;
 }
 
+bool Service::set_sampling_truncation(uint32_t top_k, float top_p) {
+  std::lock_guard<std::mutex> lock(mutex_);  // (like set_scores)
+  if (sequence_ > 0 || !(top_p > 0.0f && top_p <= 1.0f)) return false;
+  config_.top_k = top_k;
+  config_.top_p = top_p;
+  return true;
+}
+
 std::future<Histories> Service::translate(std::vector<Words> sentences) { return translate(std::move(sentences), {}, 0); }
 
 std::future<Histories> Service::translate(std::vector<Words> sentences, std::vector<Words> prefixes) {
@@ -397,7 +405,8 @@ std::vector<Unit> Service::next_batch(bool may_block, std::vector<size_t> *parts
   part.to(ns_starved_);  // ... and an empty queue)
   std::vector<Unit> batch = queue_.take();
   if (parts) parts->clear();
-  if (parts && !batch.empty() && config_.merge_batches > 1) {
+  const bool truncating = config_.top_k != 0 || config_.top_p != 1.0f;  // (the engine does not merge truncated calls)
+  if (parts && !batch.empty() && config_.merge_batches > 1 && !truncating) {
     auto rows_of = [](size_t n) { return (n + 31) / 32 * 32; };  // slimt_hip_translate_many_rows
     size_t lo = batch.back().length, hi = lo;  // shortest / longest padded length of the launch
     size_t rows = rows_of(batch.size()), n = 1;
@@ -510,6 +519,7 @@ void Service::launch(Slot &slot, std::vector<Unit> &batch, slimt_hip_shortlist *
       dk[j] = keys + p.first;
     }
     slot.worker->arm_sampling(config_.temperature, dk.data(), dk.size());
+    if (config_.top_k != 0 || config_.top_p != 1.0f) slot.worker->arm_sampling_truncation(config_.top_k, config_.top_p);
   }
   if (generator && slot.parts.size() == 1) {  // the batch's own lexical shortlist, generated on the worker's stream (Model.cc:117-120)
     slot.worker->forward_async_generated(generator, ids, lengths, B, p0.S, config_.tgt_length_limit_factor, out_ids,

@@ -121,6 +121,8 @@ struct ServiceConfig {
   bool flat_alignments = false;  // Hypothesis::alignment_flat instead of ::alignment (one block per sentence)
   bool scores = false;           // Hypothesis::scores: every target token's log-probability (Service::set_scores)
   float temperature = 0.0f;      // > 0: every launch samples at this temperature (Service::set_sampling); 0: greedy
+  uint32_t top_k = 0;            // sampled launches keep the top_k largest (0: all) ...
+  float top_p = 1.0f;            // ... and the nucleus of this mass (1: all): Service::set_sampling_truncation
   // Output vocabulary of a batch, one policy for the service's lifetime:
   //  * lexical_shortlist set: the reference's own -- ShortlistGenerator::generate on every batch's
   //    source words (Model.cc:60-82,117-120; Shortlist.cc:115-175) -- run on the device, on the
@@ -170,6 +172,10 @@ class Service {
   // temperature sampling for every request (include/slimt_hip.h, slimt_hip_ctx_set_sampling; 0: greedy again): only before
   // the first translate(); false once one has been made, or for a temperature that is not finite and >= 0
   bool set_sampling(float temperature);
+  // top-k / nucleus truncation of every sampled launch (slimt_hip_ctx_set_sampling_truncation; (0, 1): none): only before
+  // the first translate(); false once one has been made, or for a top_p outside (0, 1]. The engine does not merge
+  // truncated calls, so a truncating service sends every batch as a launch of its own, whatever merge_batches says.
+  bool set_sampling_truncation(uint32_t top_k, float top_p);
   // restart the SLIMT_SERVICE_STATS counters (benchmarks: after the warm-up pass)
   void stats_reset() {
     stats_base_ = batches_.load();

@@ -230,6 +230,16 @@ extern "C" int slimt_hip_service_set_sampling(slimt_hip_service *service, float 
   return 0;
 }
 
+extern "C" int slimt_hip_service_set_sampling_truncation(slimt_hip_service *service, uint32_t top_k, float top_p) {
+  if (!service) return fail("null argument");
+  if (!(top_p > 0.0f && top_p <= 1.0f)) return fail("set_sampling_truncation: top_p %g is not in (0, 1]", (double)top_p);
+  if (!(service->temperature > 0.0f))
+    return fail("set_sampling_truncation: the service does not sample (slimt_hip_service_set_sampling first)");
+  if (!service->service->set_sampling_truncation(top_k, top_p))
+    return fail("set_sampling_truncation: only before the first slimt_hip_service_translate");
+  return 0;
+}
+
 extern "C" int slimt_hip_service_translate_sampled(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets,
                                                    const uint32_t *prefix_tokens, const uint64_t *prefix_offsets, uint64_t seed,
                                                    size_t n, slimt_hip_result **out) {
