@@ -652,6 +652,39 @@ int slimt_hip_score_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sho
                                     const uint32_t *lengths, size_t B, size_t S, const uint32_t *tgt_ids,
                                     const uint32_t *tgt_len, size_t T, float *scores, float *align);
 
+/* ---- alternatives of a score call: the k best tokens and the target's rank at every position ---- */
+/* Arms the NEXT score call of ctx (slimt_hip_score, _score_async, _score_device or _score_async_generated) to report, for
+ * every row (b, t) with t < n_b, what the model would have said instead and how far down its list the given token is.
+ * k = 0 disarms. k > SLIMT_HIP_MAX_ALTERNATIVES is refused at once, and so is alt_ids == NULL with k > 0. The next score
+ * call takes the setting, WHATEVER ITS OUTCOME (a refused call included), and disarms it. Translate calls neither take
+ * nor clear it, and what slimt_hip_ctx_set_scores / _set_target_prefix / _set_sampling armed stays armed, as for every
+ * score call. alt_ids [B][T][k], alt_scores [B][T][k] (nullable) and rank [B][T] (nullable) are of the SAME KIND as that
+ * call's scores: host memory for slimt_hip_score, pinned or pageable host memory -- all three like scores -- for the
+ * asynchronous host calls (pinned arrays are written in place; pageable ones are bracketed by copies on the stream, the
+ * copy down first, so that entries the pass does not write survive), device memory for slimt_hip_score_device. A call
+ * whose arrays are of another kind is refused with a message. A context's first armed call with pageable arrays
+ * allocates their device staging ((2 k + 1) B T words, grown when a later call needs more); no other context pays it.
+ *
+ * For a row (b, t), t < n_b, take the output layer's N columns (the shortlist's, or the vocabulary's) with the logits l_c
+ * the scorer forms, float(acc + 127 colsum) * u + pb:
+ *   - the VALID columns are those with a non-NaN logit;
+ *   - the ORDER is descending l_c compared as floats (+0 equals -0, infinities order like any value), ties to the
+ *     ascending column: the greedy arg-max's first-maximum rule continued;
+ *   - alt_ids[b][t][i] is the vocabulary id of the i-th valid column in that order; positions i >= the number of valid
+ *     columns hold 0xFFFFFFFF. Padding columns of the layer's last 16-column tile never appear;
+ *   - alt_scores[b][t][i] = forced_score(s, l_c - m, none) with the row's own final (m, s), the pair behind scores[b][t]
+ *     in the same merge order: the natural-log softmax probability of that column. A row holding a NaN logit gives NaN
+ *     scores while its ids are still the order of its valid columns; positions past the valid columns hold -inf;
+ *   - rank[b][t] is the number of valid columns ordered strictly before the target's column, 0xFFFFFFFF when the target
+ *     is not in the layer or its logit is NaN. Hence rank < k  <=>  alt_ids[b][t][rank] == tgt_ids[b][t], and then
+ *     alt_scores[b][t][rank] has the BITS of scores[b][t].
+ * Entries with t >= n_b are NOT written. scores and align of an armed call are bit-identical to the unarmed call's, and
+ * no result depends on where a sentence sits in the batch or on the row chunking. A model set to K/V cache format 3 is
+ * refused, as by every score call. */
+#define SLIMT_HIP_MAX_ALTERNATIVES 8
+int slimt_hip_ctx_set_score_alternatives(slimt_hip_ctx *ctx, uint32_t k, uint32_t *alt_ids, float *alt_scores,
+                                         uint32_t *rank);
+
 
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, HIP events bracket every launch of kernel family `kernel_id`

@@ -15,6 +15,8 @@ import numpy as np
 
 from . import build as _build
 
+MAX_ALTERNATIVES = 8  # SLIMT_HIP_MAX_ALTERNATIVES
+
 SYMBOLS = [
     "slimt_hip_abi_version", "slimt_hip_last_error", "slimt_hip_device_count",
     "slimt_hip_set_device", "slimt_hip_affine", "slimt_hip_affine_select",
@@ -42,6 +44,7 @@ SYMBOLS = [
     "slimt_hip_ctx_set_scores", "slimt_hip_ctx_set_target_prefix", "slimt_hip_ctx_set_sampling", "slimt_hip_sampling_key",
     "slimt_hip_ctx_set_sampling_truncation", "slimt_hip_sample_truncated",
     "slimt_hip_score", "slimt_hip_score_async", "slimt_hip_score_device", "slimt_hip_score_async_generated",
+    "slimt_hip_ctx_set_score_alternatives",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -264,6 +267,7 @@ def lib():
     L.slimt_hip_score_async.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp]
     L.slimt_hip_score_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp]
     L.slimt_hip_score_async_generated.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, sz, vp, vp]
+    L.slimt_hip_ctx_set_score_alternatives.argtypes = [vp, u32, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("slimt_hip_abi_version",):
@@ -841,20 +845,60 @@ class Context:
                              % (B, lengths.shape, tgt_ids.shape, tgt_len.shape))
         return ids, lengths, tgt_ids, tgt_len
 
-    def score(self, ids, lengths, shortlist, tgt_ids, tgt_len, want_align: bool = False, fill=np.nan):
+    def set_score_alternatives(self, k: int, alt_ids=None, alt_scores=None, rank=None):
+        """slimt_hip_ctx_set_score_alternatives: arm the NEXT score call to report the k (<= MAX_ALTERNATIVES) best tokens of
+        every target position and the target's rank. alt_ids [B,T,k] uint32, alt_scores [B,T,k] float32 | None, rank [B,T]
+        uint32 | None: numpy arrays of the kind of that call's scores, or device pointers (ints) for score_device. k = 0
+        disarms. The caller keeps the arrays alive until the call has finished."""
+        ptr = lambda a: None if a is None else (C.c_void_p(a) if isinstance(a, int) else _p(a))
+        _chk(lib().slimt_hip_ctx_set_score_alternatives(self.h, int(k), ptr(alt_ids), ptr(alt_scores), ptr(rank)))
+
+    @staticmethod
+    def _alternatives_arrays(arrays, B: int, T: int):
+        """(alt_ids, alt_scores | None, rank | None) checked against [B, T, k] / [B, T]; returns k"""
+        alt_ids, alt_scores, rank = arrays
+        if alt_ids is None or alt_ids.dtype != np.uint32 or alt_ids.ndim != 3 or alt_ids.shape[:2] != (B, T) \
+                or not alt_ids.flags.c_contiguous:
+            raise ValueError("score alternatives: a C-contiguous uint32 alt_ids of shape (%d, %d, k) expected" % (B, T))
+        k = alt_ids.shape[2]
+        if not 1 <= k <= MAX_ALTERNATIVES:
+            raise ValueError("score alternatives: k = %d is not in 1..%d" % (k, MAX_ALTERNATIVES))
+        if alt_scores is not None and (alt_scores.dtype != np.float32 or alt_scores.shape != (B, T, k)
+                                       or not alt_scores.flags.c_contiguous):
+            raise ValueError("score alternatives: a C-contiguous float32 alt_scores of shape %s expected" % ((B, T, k),))
+        if rank is not None and (rank.dtype != np.uint32 or rank.shape != (B, T) or not rank.flags.c_contiguous):
+            raise ValueError("score alternatives: a C-contiguous uint32 rank of shape %s expected" % ((B, T),))
+        return k
+
+    @staticmethod
+    def _alternatives_k(k):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_ALTERNATIVES:
+            raise ValueError("score alternatives: k = %r is not an integer in 1..%d" % (k, MAX_ALTERNATIVES))
+        return int(k)
+
+    def score(self, ids, lengths, shortlist, tgt_ids, tgt_len, want_align: bool = False, fill=np.nan, alternatives=None):
         """slimt_hip_score: teacher-forced scoring of given targets in one pass over all target positions. tgt_ids [B,T],
         tgt_len [B] (<= T; T is the caller's, there is no limit_factor cap). Returns scores [B,T] float32 -- the natural-log
         softmax probability of tgt_ids[b,t] for t < tgt_len[b], -inf for a token outside the shortlist -- and align [B,T,S]
         (head 0 of the last decoder layer) or None. Entries the call does not write (t >= tgt_len[b], alignment columns
-        j >= lengths[b]) keep `fill`. Blocking; nothing armed on the context is used or consumed."""
+        j >= lengths[b]) keep `fill`. Blocking; nothing armed on the context for translate calls is used or consumed.
+        alternatives = k (1..MAX_ALTERNATIVES): additionally returns alt_ids [B,T,k] uint32 (the k most probable ids,
+        0xFFFFFFFF past the layer's valid columns), alt_scores [B,T,k] float32 (their log-probabilities) and rank [B,T] uint32
+        (the target's place in that order, 0xFFFFFFFF outside the layer); unwritten entries hold 0xFFFFFFFF / `fill`."""
         ids, lengths, tgt_ids, tgt_len = self._score_host(ids, lengths, tgt_ids, tgt_len)
         (B, S), T = ids.shape, tgt_ids.shape[1]
         sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
         sc = np.full((B, T), fill, dtype=np.float32)
         align = np.full((B, T, S), fill, dtype=np.float32) if want_align else None
+        alt = None
+        if alternatives:
+            k = self._alternatives_k(alternatives)
+            alt = (np.full((B, T, k), 0xFFFFFFFF, dtype=np.uint32), np.full((B, T, k), fill, dtype=np.float32),
+                   np.full((B, T), 0xFFFFFFFF, dtype=np.uint32))
+            self.set_score_alternatives(k, *alt)
         _chk(lib().slimt_hip_score(self.h, _p(ids), _p(lengths), B, S, _p(sl), 0 if sl is None else sl.size,
                                    _p(tgt_ids), _p(tgt_len), T, _p(sc), _p(align)))
-        return sc, align
+        return (sc, align) + alt if alt else (sc, align)
 
     def score_buffers(self, B: int, S: int, T: int, want_align: bool = False):
         """This context's pinned arrays for score_async: (ids [B,S], lengths [B], tgt_ids [B,T], tgt_len [B],
@@ -864,10 +908,18 @@ class Context:
                 pin("tg").array(np.uint32, (B, T)), pin("tl").array(np.uint32, (B,)),
                 pin("sc").array(np.float32, (B, T)), pin("al").array(np.float32, (B, T, S)) if want_align else None)
 
-    def score_async(self, bufs, shortlist=None, generator=None):
+    def score_alternatives_buffers(self, B: int, T: int, k: int):
+        """This context's pinned arrays for score_async(..., alternatives=): (alt_ids [B,T,k], alt_scores [B,T,k], rank [B,T])."""
+        pin = lambda name: self._pinned.setdefault(name, _Pinned())
+        return (pin("ai").array(np.uint32, (B, T, k)), pin("as").array(np.float32, (B, T, k)),
+                pin("ar").array(np.uint32, (B, T)))
+
+    def score_async(self, bufs, shortlist=None, generator=None, alternatives=None):
         """slimt_hip_score_async[_generated] on (ids, lengths, tgt_ids, tgt_len, scores, align | None) host arrays (already
         filled; those of score_buffers() are pinned: read and, the scores, written in place); synchronize() before reading
-        the outputs, and keep the arrays alive until then. generator: a ShortlistGenerator -- the batch's lexical shortlist."""
+        the outputs, and keep the arrays alive until then. generator: a ShortlistGenerator -- the batch's lexical shortlist.
+        alternatives: k -- this context's pinned arrays of score_alternatives_buffers(), filled with 0xFFFFFFFF / NaN -- or
+        the caller's (alt_ids, alt_scores | None, rank | None), of the kind of scores; the three arrays are returned."""
         ids, lengths, tgt_ids, tgt_len, sc, align = bufs
         for a, dt in ((ids, np.uint32), (lengths, np.uint32), (tgt_ids, np.uint32), (tgt_len, np.uint32), (sc, np.float32)):
             if a.dtype != dt or not a.flags.c_contiguous:
@@ -879,21 +931,46 @@ class Context:
             raise ValueError("score_async: mismatched shapes")
         if align is not None and (align.dtype != np.float32 or align.shape != (B, T, S) or not align.flags.c_contiguous):
             raise ValueError("score_async: a C-contiguous float32 align of shape %s expected" % ((B, T, S),))
+        alt = None
+        if alternatives is not None and not (isinstance(alternatives, (int, np.integer)) and not alternatives):
+            if isinstance(alternatives, (tuple, list)):
+                alt = tuple(alternatives)
+                if len(alt) != 3:
+                    raise ValueError("score alternatives: (alt_ids, alt_scores | None, rank | None) expected")
+                k = self._alternatives_arrays(alt, B, T)
+            else:
+                k = self._alternatives_k(alternatives)
+                alt = self.score_alternatives_buffers(B, T, k)
+                alt[0][...] = 0xFFFFFFFF
+                alt[1][...] = np.nan
+                alt[2][...] = 0xFFFFFFFF
+            self.set_score_alternatives(k, *alt)
         if generator is not None:
             _chk(lib().slimt_hip_score_async_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, _p(tgt_ids),
                                                        _p(tgt_len), T, _p(sc), _p(align)))
-            return
+            return alt
         sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
         _chk(lib().slimt_hip_score_async(self.h, _p(ids), _p(lengths), B, S, _p(sl), 0 if sl is None else sl.size,
                                          _p(tgt_ids), _p(tgt_len), T, _p(sc), _p(align)))
+        return alt
 
     def score_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int, n_shortlist: int,
-                     d_tgt_ids: int, d_tgt_len: int, T: int, d_scores: int, d_align: int = 0):
-        """slimt_hip_score_device: device pointers (ints) in and out, asynchronous on this context's stream."""
+                     d_tgt_ids: int, d_tgt_len: int, T: int, d_scores: int, d_align: int = 0, alternatives=None):
+        """slimt_hip_score_device: device pointers (ints) in and out, asynchronous on this context's stream.
+        alternatives: (k, d_alt_ids, d_alt_scores | 0, d_rank | 0), device pointers to [B,T,k] / [B,T]; returned as given."""
         vp = C.c_void_p
+        if alternatives is not None:
+            if len(alternatives) != 4:
+                raise ValueError("score alternatives: (k, d_alt_ids, d_alt_scores | 0, d_rank | 0) expected")
+            k, d_ai, d_as, d_ar = alternatives
+            k = self._alternatives_k(k)
+            if not d_ai:
+                raise ValueError("score alternatives: d_alt_ids is 0")
+            self.set_score_alternatives(k, int(d_ai), int(d_as) if d_as else None, int(d_ar) if d_ar else None)
         _chk(lib().slimt_hip_score_device(self.h, vp(d_ids), vp(d_lengths), B, S, vp(d_shortlist) if n_shortlist else None,
                                           n_shortlist, vp(d_tgt_ids), vp(d_tgt_len), T, vp(d_scores),
                                           vp(d_align) if d_align else None))
+        return alternatives
 
     def translate_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int,
                          n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int,
@@ -1142,6 +1219,8 @@ def host_lib():
     H.slimt_hip_service_translate_sampled.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, sz, vp]
     H.slimt_hip_service_set_sampling_truncation.argtypes = [vp, C.c_uint32, C.c_float]
     H.slimt_hip_service_score.argtypes = [vp, vp, vp, vp, vp, sz, vp]  # (include/slimt_hip_service_score.h)
+    H.slimt_hip_service_score_alternatives.argtypes = [vp, vp, vp, vp, vp, sz, C.c_uint32, vp]  # (include/slimt_hip_service_alternatives.h)
+    H.slimt_hip_result_alternatives.argtypes = [vp, sz, vp, vp, vp, vp]
     _host_lib = H
     return H
 
@@ -1189,6 +1268,22 @@ class ServiceResult:
 
     def target(self, i: int) -> np.ndarray:
         return self.targets[int(self.target_offsets[i]):int(self.target_offsets[i + 1])]
+
+    def alternatives(self, i: int):
+        """sentence i of a BatchService.score(..., alternatives=k) result (slimt_hip_result_alternatives): alt_ids [n_i, k]
+        uint32, alt_scores [n_i, k] float32 and ranks [n_i] uint32 over its n_i target tokens; views valid while this object
+        lives"""
+        k, pi, ps, pr = C.c_uint32(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        if host_lib().slimt_hip_result_alternatives(self.h, i, C.byref(k), C.byref(pi), C.byref(ps), C.byref(pr)):
+            raise SlimtHipError(host_lib().slimt_hip_service_last_error().decode())
+        n = int(self.target_offsets[i + 1]) - int(self.target_offsets[i])
+
+        def arr(p, dtype, shape):
+            if not n or not p.value:
+                return np.zeros(shape, dtype)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=shape)
+
+        return arr(pi, np.uint32, (n, k.value)), arr(ps, np.float32, (n, k.value)), arr(pr, np.uint32, (n,))
 
     def token_scores(self, i: int) -> np.ndarray:
         """sentence i's per-token log-probabilities (EOS included); the service must score"""
@@ -1303,18 +1398,27 @@ class BatchService:
             raise ValueError(f"prefixes: {len(prefixes)} for {len(sentences)} sentences")
         return self.translate_flat(*self._flat(sentences), *self._flat(prefixes), seed=seed)
 
-    def score(self, sentences, targets) -> ServiceResult:
+    def score(self, sentences, targets, alternatives: int = 0) -> ServiceResult:
         """slimt_hip_service_score: teacher-forced scoring of targets[i] (a token list, with its EOS when that is to be
         scored; any length) against sentences[i] in one pass over all target positions. The result's target(i) is the given
         tokens, token_scores(i) their log-probabilities (whether or not the service scores its translations),
-        alignment(i) the [target tokens, source tokens] rows. Blocking; thread-safe."""
+        alignment(i) the [target tokens, source tokens] rows. Blocking; thread-safe.
+        alternatives = k (1..MAX_ALTERNATIVES; slimt_hip_service_score_alternatives): the result's alternatives(i) are the
+        k most probable ids of every target position, their log-probabilities and the given tokens' ranks."""
         if len(targets) != len(sentences):
             raise ValueError(f"targets: {len(targets)} for {len(sentences)} sentences")
+        if alternatives:
+            alternatives = Context._alternatives_k(alternatives)
         tokens, offsets = self._flat(sentences)
         t_tokens, t_offsets = self._flat(targets)
         out = C.c_void_p()
-        if host_lib().slimt_hip_service_score(self.h, _p(tokens), _p(offsets), _p(t_tokens), _p(t_offsets), offsets.size - 1,
-                                              C.byref(out)):
+        if alternatives:
+            rc = host_lib().slimt_hip_service_score_alternatives(self.h, _p(tokens), _p(offsets), _p(t_tokens), _p(t_offsets),
+                                                                 offsets.size - 1, alternatives, C.byref(out))
+        else:
+            rc = host_lib().slimt_hip_service_score(self.h, _p(tokens), _p(offsets), _p(t_tokens), _p(t_offsets),
+                                                    offsets.size - 1, C.byref(out))
+        if rc:
             raise SlimtHipError(host_lib().slimt_hip_service_last_error().decode())
         return ServiceResult(out, np.diff(offsets).astype(np.int64))
 

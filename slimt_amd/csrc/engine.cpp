@@ -1140,7 +1140,7 @@ void ctx_free(slimt_hip_ctx *c) {
                     &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->tr_logits, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag,
-                    &c->score_ws, &c->score_io};
+                    &c->score_ws, &c->score_io, &c->alt_stage};
   for (auto *b : bufs) b->release();
   free_affine(c->out_sl);
   if (c->n_finished_host) (void)hipHostFree(c->n_finished_host);
@@ -1397,6 +1397,20 @@ extern "C" int slimt_hip_ctx_set_sampling_truncation(slimt_hip_ctx *ctx, uint32_
   ctx->tr_next_k = top_k;
   ctx->tr_next_p = top_p;
   ctx->tr_armed = top_k != 0 || top_p != 1.0f;  // (both off: nothing armed, the call is today's sampled call)
+  return 0;
+}
+
+extern "C" int slimt_hip_ctx_set_score_alternatives(slimt_hip_ctx *ctx, uint32_t k, uint32_t *alt_ids, float *alt_scores,
+                                                    uint32_t *rank) {
+  // (the value first, like the temperature)
+  if (k > SLIMT_HIP_MAX_ALTERNATIVES)
+    return fail(-1, "score alternatives: k %u exceeds SLIMT_HIP_MAX_ALTERNATIVES (%d)", k, SLIMT_HIP_MAX_ALTERNATIVES);
+  if (!ctx) return fail(-1, "null argument");
+  if (k && !alt_ids) return fail(-1, "score alternatives: alt_ids is NULL");
+  ctx->alt_next_k = k;  // (k = 0: nothing armed)
+  ctx->alt_next_ids = k ? alt_ids : nullptr;
+  ctx->alt_next_scores = k ? alt_scores : nullptr;
+  ctx->alt_next_rank = k ? rank : nullptr;
   return 0;
 }
 
@@ -3954,9 +3968,37 @@ int score_check(const slimt_hip_ctx *c, size_t B, size_t S, size_t n_sl, size_t 
   return 0;
 }
 
+// The alternatives armed on a context (slimt_hip_ctx_set_score_alternatives) are taken by the score entry point that comes
+// next, whether it succeeds or not; translate calls construct none of these.
+struct AltCall {
+  ScoreAltArgs a;  // k = 0: the call is not armed
+  explicit AltCall(slimt_hip_ctx *ctx) {
+    if (!ctx || !ctx->alt_next_k) return;
+    a.k = (int)ctx->alt_next_k;
+    a.ids = ctx->alt_next_ids;
+    a.scores = ctx->alt_next_scores;
+    a.rank = ctx->alt_next_rank;
+    ctx->alt_next_k = 0;
+    ctx->alt_next_ids = nullptr;
+    ctx->alt_next_scores = nullptr;
+    ctx->alt_next_rank = nullptr;
+  }
+};
+
+// memory a kernel can write: device, managed or pinned host memory as the runtime knows it
+bool device_visible(const void *p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged;
+}
+
+// alt (k = 0: unarmed): ids / scores / rank are addresses the kernels write
 int score_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_lengths, size_t B, size_t S,
                  const uint32_t *d_shortlist, size_t n_sl, const uint32_t *d_tgt, const uint32_t *d_tlen, size_t T,
-                 float *d_scores, float *d_align) {
+                 float *d_scores, float *d_align, const ScoreAltArgs &alt) {
   const slimt_hip_model *m = c->model;
   hipStream_t st = c->stream;
   const size_t D = (size_t)m->D, F = (size_t)m->F;
@@ -4047,7 +4089,13 @@ int score_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_leng
     o.scores = d_scores;
     {
       ProfScope ps(c, SLIMT_HIP_K_LOGITS, (double)R * out.w.K * out.w.N, gemm_bytes(out.w));
-      HIPCHK(launch_score_output(o, st));
+      if (alt.k) {
+        ScoreAltArgs al = alt;
+        al.sl = n_sl ? c->shortlist.as<uint32_t>() : nullptr;
+        HIPCHK(launch_score_alternatives(o, al, st));
+      } else {
+        HIPCHK(launch_score_output(o, st));
+      }
     }
   }
   return 0;
@@ -4058,9 +4106,20 @@ int score_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_leng
 int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
                size_t S, const uint32_t *shortlist, size_t n_sl, const uint32_t *tgt_ids, const uint32_t *tgt_len, size_t T,
                float *scores, float *align, bool wait) {
+  AltCall ac(ctx);
   if (ctx && T == 0) return fail(-1, "score: T is 0 (a target row needs at least one column)");
   if (!ctx || !src_ids || !lengths || !tgt_ids || !tgt_len || !scores) return fail(-1, "null argument");
   RCCHK(score_check(ctx, B, S, n_sl, T));
+  ScoreAltArgs alt = ac.a;
+  if (alt.k) {  // the three arrays are of the kind of scores: all pinned (written in place) or all pageable (staged)
+    const bool pinned = host_device_view(scores) != nullptr;
+    const void *arr[3] = {alt.ids, alt.scores, alt.rank};
+    const char *name[3] = {"alt_ids", "alt_scores", "rank"};
+    for (int i = 0; i < 3; ++i)
+      if (arr[i] && (host_device_view(arr[i]) != nullptr) != pinned)
+        return fail(-1, "score alternatives: %s is %s memory, scores is %s: the arrays are of the kind of scores", name[i],
+                    pinned ? "pageable" : "pinned", pinned ? "pinned" : "pageable");
+  }
   const slimt_hip_model *m = ctx->model;
   uint32_t vmax = (uint32_t)m->V;
   if (gen) {
@@ -4121,6 +4180,31 @@ int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src
     d_scores = stage_sc;
   }
   if (align) HIPCHK(hipMemcpyAsync(ctx->align.p, align, B * T * S * 4, hipMemcpyHostToDevice, st));
+  // the alternatives likewise: pinned arrays in place, pageable ones as [ids B T k][scores B T k][rank B T] in alt_stage
+  ScoreAltArgs user_alt = alt;
+  const size_t n_alt = B * T * (size_t)alt.k;
+  bool stage_alt = false;
+  if (alt.k) {
+    if (void *v = host_device_view(alt.ids)) {
+      alt.ids = static_cast<uint32_t *>(v);
+      alt.scores = alt.scores ? static_cast<float *>(host_device_view(alt.scores)) : nullptr;
+      alt.rank = alt.rank ? static_cast<uint32_t *>(host_device_view(alt.rank)) : nullptr;
+    } else {
+      stage_alt = true;
+      RCCHK(score_reserve(ctx, ctx->alt_stage, (2 * n_alt + B * T) * 4));
+      uint32_t *sa = ctx->alt_stage.as<uint32_t>();
+      alt.ids = sa;
+      HIPCHK(hipMemcpyAsync(alt.ids, user_alt.ids, n_alt * 4, hipMemcpyHostToDevice, st));
+      if (user_alt.scores) {
+        alt.scores = reinterpret_cast<float *>(sa + n_alt);
+        HIPCHK(hipMemcpyAsync(alt.scores, user_alt.scores, n_alt * 4, hipMemcpyHostToDevice, st));
+      }
+      if (user_alt.rank) {
+        alt.rank = sa + 2 * n_alt;
+        HIPCHK(hipMemcpyAsync(alt.rank, user_alt.rank, B * T * 4, hipMemcpyHostToDevice, st));
+      }
+    }
+  }
   const uint32_t *d_sl = ctx->shortlist.as<uint32_t>();
   if (gen) {  // Model.cc:117-120: the batch's shortlist, generated on this stream into ctx->shortlist
     ctx->sl_host.clear();
@@ -4135,8 +4219,14 @@ int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src
     HIPCHK(hipStreamSynchronize(st));
     n_sl = n;
   }
-  RCCHK(score_device(ctx, d_ids, d_len, B, S, d_sl, n_sl, d_tgt, d_tlen, T, d_scores, align ? ctx->align.as<float>() : nullptr));
+  RCCHK(score_device(ctx, d_ids, d_len, B, S, d_sl, n_sl, d_tgt, d_tlen, T, d_scores, align ? ctx->align.as<float>() : nullptr,
+                     alt));
   if (stage_sc) HIPCHK(hipMemcpyAsync(scores, stage_sc, B * T * 4, hipMemcpyDeviceToHost, st));
+  if (stage_alt) {
+    HIPCHK(hipMemcpyAsync(user_alt.ids, alt.ids, n_alt * 4, hipMemcpyDeviceToHost, st));
+    if (user_alt.scores) HIPCHK(hipMemcpyAsync(user_alt.scores, alt.scores, n_alt * 4, hipMemcpyDeviceToHost, st));
+    if (user_alt.rank) HIPCHK(hipMemcpyAsync(user_alt.rank, alt.rank, B * T * 4, hipMemcpyDeviceToHost, st));
+  }
   if (align) HIPCHK(hipMemcpyAsync(align, ctx->align.p, B * T * S * 4, hipMemcpyDeviceToHost, st));
   if (wait) RCCHK(slimt_hip_ctx_synchronize(ctx));
   return 0;
@@ -4158,17 +4248,29 @@ extern "C" int slimt_hip_score_async(slimt_hip_ctx *ctx, const uint32_t *src_ids
 extern "C" int slimt_hip_score_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *shortlist, const uint32_t *src_ids,
                                                const uint32_t *lengths, size_t B, size_t S, const uint32_t *tgt_ids,
                                                const uint32_t *tgt_len, size_t T, float *scores, float *align) {
-  if (!shortlist) return fail(-1, "null argument");
+  if (!shortlist) {
+    AltCall ac(ctx);  // (taken whatever the outcome)
+    return fail(-1, "null argument");
+  }
   return score_host(ctx, shortlist, src_ids, lengths, B, S, nullptr, 0, tgt_ids, tgt_len, T, scores, align, false);
 }
 
 extern "C" int slimt_hip_score_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids, const uint32_t *d_lengths, size_t B,
                                       size_t S, const uint32_t *d_shortlist, size_t n_shortlist, const uint32_t *d_tgt_ids,
                                       const uint32_t *d_tgt_len, size_t T, float *d_scores, float *d_align) {
+  AltCall ac(ctx);
   if (ctx && T == 0) return fail(-1, "score: T is 0 (a target row needs at least one column)");
   if (!ctx || !d_src_ids || !d_lengths || !d_tgt_ids || !d_tgt_len || !d_scores) return fail(-1, "null argument");
   RCCHK(score_check(ctx, B, S, n_shortlist, T));
   if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
   HIPCHK(hipSetDevice(ctx->model->device));
-  return score_device(ctx, d_src_ids, d_lengths, B, S, d_shortlist, n_shortlist, d_tgt_ids, d_tgt_len, T, d_scores, d_align);
+  if (ac.a.k) {
+    const void *arr[3] = {ac.a.ids, ac.a.scores, ac.a.rank};
+    const char *name[3] = {"alt_ids", "alt_scores", "rank"};
+    for (int i = 0; i < 3; ++i)
+      if (arr[i] && !device_visible(arr[i]))
+        return fail(-1, "score alternatives: %s is not memory the device can write (the arrays are of the kind of scores)", name[i]);
+  }
+  return score_device(ctx, d_src_ids, d_lengths, B, S, d_shortlist, n_shortlist, d_tgt_ids, d_tgt_len, T, d_scores, d_align,
+                      ac.a);
 }

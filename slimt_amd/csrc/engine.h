@@ -234,6 +234,14 @@ struct slimt_hip_ctx {
   // teacher-forced scoring (include/slimt_hip.h, slimt_hip_score*): allocated on the first scoring call, grown when a later
   // one needs more. score_ws: one chunk's rows (engine.cpp, score_device); score_io: staging of a host call's targets and scores
   slimt_hip::DevBuf score_ws, score_io;
+  // alternatives (include/slimt_hip.h, slimt_hip_ctx_set_score_alternatives): armed for the NEXT score call, which takes them
+  // whatever its outcome (engine.cpp, AltCall). alt_stage: device staging of pageable destinations, allocated by the first
+  // armed call that needs it
+  uint32_t alt_next_k = 0;  // 0: nothing armed
+  uint32_t *alt_next_ids = nullptr;
+  float *alt_next_scores = nullptr;
+  uint32_t *alt_next_rank = nullptr;
+  slimt_hip::DevBuf alt_stage;
   int *n_finished_host = nullptr;  // pinned
   // profiling
   int prof_kernel = 0;

@@ -674,6 +674,17 @@ struct ScoreOutArgs {
   float *scores = nullptr;       // [B][T]: log softmax at the target column (scores.h, forced_score), live rows only
 };
 hipError_t launch_score_output(const ScoreOutArgs &a, hipStream_t st);
+// the armed twin (score_alternatives.hip; slimt_hip_ctx_set_score_alternatives): the same scores, and per live row the k
+// best (logit, column) pairs and the number of valid columns ordered before the target's
+struct ScoreAltArgs {
+  int k = 0;                     // 1 .. 8
+  const uint32_t *sl = nullptr;  // [N] the columns' vocabulary ids (nullptr: the column)
+  uint32_t *ids = nullptr;       // [B][T][k]
+  float *scores = nullptr;       // nullable [B][T][k]
+  uint32_t *rank = nullptr;      // nullable [B][T]
+};
+size_t score_alternatives_lds_bytes(int K);
+hipError_t launch_score_alternatives(const ScoreOutArgs &a, const ScoreAltArgs &alt, hipStream_t st);
 bool score_supported(int D, int H);  // D in {64, 128, 256, 512}, d_head in {16, 32, 64}
 
 // ---- truncated sampling: top-k / nucleus selection over stored logits (sample_truncate.hip) -------------------------------

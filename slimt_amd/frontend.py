@@ -23,7 +23,7 @@ from __future__ import annotations
 import functools
 import threading
 from dataclasses import dataclass, field
-from typing import List, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -99,6 +99,11 @@ class PairScore:  # Service.score: one (source, given target) pair
     token_scores: np.ndarray      # float32 [len(target_ids)]: log-probability of each target token given those before it
     score: float                  # their sum: the log-probability of the target given the source
     alignment: np.ndarray         # float32 [len(target_ids), len(source_ids)]
+    # Service.score(..., alternatives=k) only (else None):
+    ranks: Optional[List[int]] = None   # per target token: how many tokens of the output layer the model preferred to it
+    #                                     (0: it is the model's choice; None: the token is outside the layer)
+    alternatives: Optional[List[List[Tuple[str, float]]]] = None  # per target token: the (up to) k most probable
+    #                                     (piece string, log-probability) pairs of its position, best first
 
 
 class Model:
@@ -413,14 +418,17 @@ class Service:
             r.to(encoding)
         return out
 
-    def score(self, model: Model, sources: Sequence[str], targets: Sequence[str]) -> List["PairScore"]:
+    def score(self, model: Model, sources: Sequence[str], targets: Sequence[str], alternatives: int = 0) -> List["PairScore"]:
         """Teacher-forced scoring of given translations (include/slimt_hip_service_score.h): targets[i] against
         sources[i], each text ONE sentence as the model's vocabulary tokenises it, EOS appended -- no sentence splitting,
         no wrapping: a source of more than ENGINE_LIMIT tokens is refused, a target may be any length. Every target
         position goes through the decoder in one pass; the output layer is the one translate() uses (the model's lexical
         shortlist per batch, else the full vocabulary), so a target token outside it scores -inf. Returns one PairScore
         per pair: the token ids of both sides, each target token's log-probability, their sum, and the
-        [target tokens, source tokens] alignment (head 0 of the last decoder layer)."""
+        [target tokens, source tokens] alignment (head 0 of the last decoder layer).
+        alternatives = k (1..8; include/slimt_hip_service_alternatives.h): each PairScore also carries `alternatives` -- per
+        target token the k most probable pieces of its position with their log-probabilities -- and `ranks`, each given
+        token's place in that order (rank r < k means alternatives[t][r] is the token itself)."""
         if len(sources) != len(targets):
             raise ValueError(f"score: {len(targets)} targets for {len(sources)} sources")
         v = model.vocabulary
@@ -432,12 +440,17 @@ class Service:
                 raise ValueError(f"score: source {i} has {len(ids)} tokens, more than {self.ENGINE_LIMIT}")
         if not src:
             return []
-        res = self._engine(model).score(src, tgt)
+        res = self._engine(model).score(src, tgt, alternatives) if alternatives else self._engine(model).score(src, tgt)
         out = []
         for i in range(len(src)):
             sc = res.token_scores(i).copy()
             out.append(PairScore(source_ids=src[i], target_ids=tgt[i], token_scores=sc,
                                  score=float(np.sum(sc, dtype=np.float64)), alignment=res.alignment(i).copy()))
+            if alternatives:
+                a_ids, a_sc, a_rank = res.alternatives(i)
+                out[-1].ranks = [None if r == 0xFFFFFFFF else int(r) for r in a_rank]
+                out[-1].alternatives = [[(v.piece(w), float(s)) for w, s in zip(row_ids, row_sc) if w != 0xFFFFFFFF]
+                                        for row_ids, row_sc in zip(a_ids, a_sc)]
         res.close()
         return out
 

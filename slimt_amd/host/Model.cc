@@ -213,10 +213,16 @@ uint64_t Worker::sampling_key(uint64_t seed, uint64_t index) {
 // (weak, like the scores: the Service's sanitizer builds link a test double of the engine that predates these calls)
 #pragma weak slimt_hip_score
 #pragma weak slimt_hip_score_async_generated
+#pragma weak slimt_hip_ctx_set_score_alternatives
 void Worker::score(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
                    const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids, const uint32_t *tgt_len, size_t T,
-                   float *scores, float *align) {
+                   float *scores, float *align, const ScoreAlternatives *alternatives) {
   if (!slimt_hip_score || !slimt_hip_score_async_generated) throw std::runtime_error("this engine has no teacher-forced scoring");
+  if (alternatives && alternatives->k) {  // taken by the score call below, whatever its outcome
+    if (!slimt_hip_ctx_set_score_alternatives) throw std::runtime_error("this engine has no score alternatives");
+    if (slimt_hip_ctx_set_score_alternatives(ctx_, alternatives->k, alternatives->alt_ids, alternatives->alt_scores, alternatives->rank))
+      raise("slimt_hip_ctx_set_score_alternatives");
+  }
   if (generator) {
     if (slimt_hip_score_async_generated(ctx_, generator, ids, lengths, B, S, tgt_ids, tgt_len, T, scores, align))
       raise("slimt_hip_score_async_generated");

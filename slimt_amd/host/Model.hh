@@ -33,6 +33,13 @@ struct Hypothesis {  // slimt/Types.hh:55-61
   // per-token log-probabilities of `target` (one per token, EOS included) when the producer was asked for them
   // (ServiceConfig::scores; include/slimt_hip.h, slimt_hip_ctx_set_scores); empty otherwise
   std::vector<float> scores;
+  // Service::score(..., alternatives = k): per target token the k most probable ids of its position and their
+  // log-probabilities ([target.size()][k]; 0xFFFFFFFF / -inf past the layer's valid columns), and the token's own place in
+  // that order (0xFFFFFFFF outside the layer): include/slimt_hip.h, slimt_hip_ctx_set_score_alternatives. Empty otherwise
+  uint32_t alternatives = 0;  // k
+  std::vector<uint32_t> alt_ids;
+  std::vector<float> alt_scores;
+  std::vector<uint32_t> ranks;
   size_t padded_length = 0;  // diagnostic: the S of the batch this sentence was translated in
   uint64_t batch = 0;        // diagnostic: serial number of that batch (Service: batches in launch order)
 };
@@ -40,6 +47,15 @@ using History = std::shared_ptr<Hypothesis>;
 // alignment_flat -> alignment: target.size() rows of equal length (the sentence's source tokens), then the block is released
 void expand_alignment(Hypothesis &hypothesis);
 using Histories = std::vector<History>;
+
+// Destinations of a scoring call's alternatives (slimt_hip_ctx_set_score_alternatives): host arrays of the kind of the call's
+// scores; alt_ids [B][T][k], alt_scores [B][T][k] (nullable), rank [B][T] (nullable). Entries with t >= tgt_len[b] are not written
+struct ScoreAlternatives {
+  uint32_t k = 0;
+  uint32_t *alt_ids = nullptr;
+  float *alt_scores = nullptr;
+  uint32_t *rank = nullptr;
+};
 
 // Padded batch (slimt/Input.cc:20-63): indices [B,S], lengths, limit factor.
 class Input {
@@ -181,7 +197,7 @@ class Worker {
   // (slimt_hip_score_async_generated) -- shortlist / n_shortlist are then not used.
   void score(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
              const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids, const uint32_t *tgt_len, size_t T,
-             float *scores, float *align);
+             float *scores, float *align, const ScoreAlternatives *alternatives = nullptr);
   void wait();
 
  private:

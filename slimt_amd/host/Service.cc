@@ -241,8 +241,11 @@ Service::~Service() {
   }
 }
 
-Histories Service::score(std::vector<Words> sentences, std::vector<Words> targets) {
+Histories Service::score(std::vector<Words> sentences, std::vector<Words> targets, size_t alternatives) {
   constexpr size_t kLongestTarget = 65536;  // include/slimt_hip.h, slimt_hip_score
+  if (alternatives > SLIMT_HIP_MAX_ALTERNATIVES)
+    throw std::invalid_argument(std::to_string(alternatives) + " alternatives: more than " + std::to_string(SLIMT_HIP_MAX_ALTERNATIVES));
+  const size_t k = alternatives;
   if (targets.size() != sentences.size())
     throw std::invalid_argument(std::to_string(targets.size()) + " targets for " + std::to_string(sentences.size()) + " sentences");
   for (size_t i = 0; i < sentences.size(); ++i) {
@@ -270,7 +273,8 @@ Histories Service::score(std::vector<Words> sentences, std::vector<Words> target
   std::lock_guard<std::mutex> lock(score_mu_);
   if (!score_worker_) score_worker_ = std::make_unique<Worker>(*score_model_, config_.max_words, longest_, config_.max_words);
   std::vector<uint32_t> ids, lengths, tgt, tlen;
-  std::vector<float> sc, al;
+  std::vector<float> sc, al, alt_sc;
+  std::vector<uint32_t> alt_id, rank;
   for (;;) {
     const std::vector<Unit> batch = queue.take();
     if (batch.empty()) break;
@@ -294,9 +298,19 @@ Histories Service::score(std::vector<Words> sentences, std::vector<Words> target
       tlen[b] = static_cast<uint32_t>(t.size());
     }
     const bool fixed = config_.shortlist && !score_generator_;
+    ScoreAlternatives alt;
+    if (k) {
+      alt_id.assign(B * T * k, 0xFFFFFFFFu);
+      alt_sc.assign(B * T * k, 0.0f);
+      rank.assign(B * T, 0xFFFFFFFFu);
+      alt.k = static_cast<uint32_t>(k);
+      alt.alt_ids = alt_id.data();
+      alt.alt_scores = alt_sc.data();
+      alt.rank = rank.data();
+    }
     score_worker_->score(score_generator_, ids.data(), lengths.data(), B, S, fixed ? config_.shortlist->data() : nullptr,
                          fixed ? config_.shortlist->size() : 0, tgt.data(), tlen.data(), T, sc.data(),
-                         config_.alignments ? al.data() : nullptr);
+                         config_.alignments ? al.data() : nullptr, k ? &alt : nullptr);
     const uint64_t serial = batches_.fetch_add(1);
     // the given tokens as the recorded ones: collect() cuts rows at tgt_len and alignment rows at the sentence's length
     Histories hs = collect(tgt.data(), tlen.data(), config_.alignments ? al.data() : nullptr, lengths.data(), B, S, T,
@@ -304,6 +318,13 @@ Histories Service::score(std::vector<Words> sentences, std::vector<Words> target
     for (size_t b = 0; b < B; ++b) {
       hs[b]->scores.assign(sc.begin() + static_cast<std::ptrdiff_t>(b * T), sc.begin() + static_cast<std::ptrdiff_t>(b * T + tlen[b]));
       hs[b]->batch = serial;
+      if (k) {
+        const auto at = [](size_t i) { return static_cast<std::ptrdiff_t>(i); };
+        hs[b]->alternatives = static_cast<uint32_t>(k);
+        hs[b]->alt_ids.assign(alt_id.begin() + at(b * T * k), alt_id.begin() + at((b * T + tlen[b]) * k));
+        hs[b]->alt_scores.assign(alt_sc.begin() + at(b * T * k), alt_sc.begin() + at((b * T + tlen[b]) * k));
+        hs[b]->ranks.assign(rank.begin() + at(b * T), rank.begin() + at(b * T + tlen[b]));
+      }
       results[batch[b].index] = std::move(hs[b]);
     }
   }

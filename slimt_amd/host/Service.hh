@@ -166,7 +166,10 @@ class Service {
   // of its own (built on the first call, on the first replica): it neither queues behind translate requests nor is
   // merged with them; concurrent callers take turns. Throws std::invalid_argument for counts that differ, an empty
   // sentence or one longer than the service accepts, or a target of more than 65536 tokens.
-  Histories score(std::vector<Words> sentences, std::vector<Words> targets);
+  // alternatives = k (1 .. 8): each Hypothesis also carries, per target token, the k most probable ids of its position with
+  // their log-probabilities and the token's rank among the layer's columns (Hypothesis::alt_ids / alt_scores / ranks;
+  // include/slimt_hip.h, slimt_hip_ctx_set_score_alternatives). More than 8 is refused.
+  Histories score(std::vector<Words> sentences, std::vector<Words> targets, size_t alternatives = 0);
   // per-token scores on or off (ServiceConfig::scores): only before the first translate(); false once one has been made
   bool set_scores(bool on);
   // temperature sampling for every request (include/slimt_hip.h, slimt_hip_ctx_set_sampling; 0: greedy again): only before

@@ -15,6 +15,7 @@
 #include "slimt_hip_service_score.h"
 #include "slimt_hip_service_sampling.h"
 #include "slimt_hip_service_scores.h"
+#include "slimt_hip_service_alternatives.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -40,6 +41,10 @@ struct slimt_hip_result {
   std::vector<float> alignments;
   std::vector<float> scores;  // per target token, by target_offsets (a scoring service only)
   bool scored = false;
+  // slimt_hip_service_score_alternatives: per target token, by target_offsets ([k] ids and scores, one rank)
+  uint32_t alternatives = 0;
+  std::vector<uint32_t> alt_ids, ranks;
+  std::vector<float> alt_scores;
 };
 
 extern "C" const char *slimt_hip_service_last_error(void) { return g_err; }
@@ -92,8 +97,9 @@ extern "C" int slimt_hip_service_destroy(slimt_hip_service *service) {
 
 namespace {
 // Histories -> the arrays of a result (scored: with every token's log-probability)
-int flatten(const slimt::Histories &hs, size_t n, bool scored, std::unique_ptr<slimt_hip_result> &out) {
+int flatten(const slimt::Histories &hs, size_t n, bool scored, std::unique_ptr<slimt_hip_result> &out, uint32_t alternatives = 0) {
   auto r = std::make_unique<slimt_hip_result>();
+  r->alternatives = alternatives;
   r->target_offsets.assign(n + 1, 0);
   r->align_offsets.assign(n + 1, 0);
   r->padded.resize(n);
@@ -114,6 +120,15 @@ int flatten(const slimt::Histories &hs, size_t n, bool scored, std::unique_ptr<s
     if (r->scored) {
       if (h.scores.size() != h.target.size()) return fail("sentence %zu: %zu scores for %zu tokens", i, h.scores.size(), h.target.size());
       r->scores.insert(r->scores.end(), h.scores.begin(), h.scores.end());
+    }
+    if (alternatives) {
+      const size_t nt = h.target.size();
+      if (h.alternatives != alternatives || h.alt_ids.size() != nt * alternatives || h.alt_scores.size() != nt * alternatives ||
+          h.ranks.size() != nt)
+        return fail("sentence %zu: alternatives of %zu tokens do not match k = %u", i, nt, alternatives);
+      r->alt_ids.insert(r->alt_ids.end(), h.alt_ids.begin(), h.alt_ids.end());
+      r->alt_scores.insert(r->alt_scores.end(), h.alt_scores.begin(), h.alt_scores.end());
+      r->ranks.insert(r->ranks.end(), h.ranks.begin(), h.ranks.end());
     }
     r->target_offsets[i + 1] = r->targets.size();
     r->align_offsets[i + 1] = r->alignments.size();
@@ -173,8 +188,9 @@ extern "C" int slimt_hip_service_translate_prefixed(slimt_hip_service *service, 
   return translate(service, tokens, offsets, prefix_tokens, prefix_offsets, n, out);
 }
 
-extern "C" int slimt_hip_service_score(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets,
-                                       const uint32_t *tgt_tokens, const uint64_t *tgt_offsets, size_t n, slimt_hip_result **out) {
+namespace {
+int score(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets, const uint32_t *tgt_tokens,
+          const uint64_t *tgt_offsets, size_t n, uint32_t alternatives, slimt_hip_result **out) {
   if (!service || !out || (n && (!tokens || !offsets || !tgt_offsets)) || (n && tgt_offsets[n] > tgt_offsets[0] && !tgt_tokens))
     return fail("null argument");
   *out = nullptr;
@@ -186,14 +202,41 @@ extern "C" int slimt_hip_service_score(slimt_hip_service *service, const uint32_
       sentences[i].assign(tokens + offsets[i], tokens + offsets[i + 1]);
       if (tgt_offsets[i + 1] > tgt_offsets[i]) targets[i].assign(tgt_tokens + tgt_offsets[i], tgt_tokens + tgt_offsets[i + 1]);
     }
-    const slimt::Histories hs = service->service->score(std::move(sentences), std::move(targets));
+    const slimt::Histories hs = service->service->score(std::move(sentences), std::move(targets), alternatives);
     std::unique_ptr<slimt_hip_result> r;
-    if (const int rc = flatten(hs, n, true, r)) return rc;
+    if (const int rc = flatten(hs, n, true, r, alternatives)) return rc;
     *out = r.release();
     return 0;
   } catch (const std::exception &e) {
     return fail("%s", e.what());
   }
+}
+}  // namespace
+
+extern "C" int slimt_hip_service_score(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets,
+                                       const uint32_t *tgt_tokens, const uint64_t *tgt_offsets, size_t n, slimt_hip_result **out) {
+  return score(service, tokens, offsets, tgt_tokens, tgt_offsets, n, 0, out);
+}
+
+extern "C" int slimt_hip_service_score_alternatives(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets,
+                                                    const uint32_t *tgt_tokens, const uint64_t *tgt_offsets, size_t n, uint32_t k,
+                                                    slimt_hip_result **out) {
+  if (k < 1 || k > SLIMT_HIP_MAX_ALTERNATIVES)
+    return fail("score_alternatives: k %u is not in 1..%d", k, SLIMT_HIP_MAX_ALTERNATIVES);
+  return score(service, tokens, offsets, tgt_tokens, tgt_offsets, n, k, out);
+}
+
+extern "C" int slimt_hip_result_alternatives(const slimt_hip_result *r, size_t i, uint32_t *k, const uint32_t **ids,
+                                             const float **scores, const uint32_t **ranks) {
+  if (!r) return fail("result is NULL");
+  if (!r->alternatives) return fail("result_alternatives: not a result of slimt_hip_service_score_alternatives");
+  if (i >= r->padded.size()) return fail("result_alternatives: sentence %zu of %zu", i, r->padded.size());
+  const size_t at = r->target_offsets[i];
+  if (k) *k = r->alternatives;
+  if (ids) *ids = r->alt_ids.data() + at * r->alternatives;
+  if (scores) *scores = r->alt_scores.data() + at * r->alternatives;
+  if (ranks) *ranks = r->ranks.data() + at;
+  return 0;
 }
 
 extern "C" int slimt_hip_result_view(const slimt_hip_result *r, size_t *n, const uint32_t **targets,

@@ -231,6 +231,11 @@ class Vocabulary:
     def pad_id(self) -> int:
         return self.sp.pad_id()
 
+    def piece(self, word: int) -> str:
+        """the piece string of one id ("" for an id past the vocabulary: a padding row of the model's embedding)"""
+        word = int(word)
+        return self.sp.id_to_piece(word) if 0 <= word < self.size() else ""
+
     def encode(self, line: bytes | str, add_eos: bool = False) -> Tuple[List[int], List[Tuple[int, int]]]:
         """ids and, per id, the (begin, end) byte range of its surface in `line`
         (Vocabulary.cc:34-75; the appended EOS has no range, as there)."""
