@@ -728,6 +728,12 @@ int slimt_hip_debug_cross_attention(slimt_hip_ctx *ctx, int layer, int literal, 
  * slimt_hip_ctx_synchronize, or the blocking translate calls -- FAILS: the batch's results are
  * not to be used. Tests use it to reach that path. */
 int slimt_hip_debug_break_shortlist_handoff(slimt_hip_ctx *ctx, int broken, unsigned poll_limit);
+/* Diagnostic: what ctx's shortlist buffer holds after a *_generated call: waits for ctx's stream, then for j < n_batches writes
+ * counts[j] (the device's count of sub-batch j; j = 0 for an unmerged call) and the first min(counts[j], capacity) ids
+ * of that list to ids + j * capacity. Reads only what the context has reserved; fails otherwise (n_batches not in 1..8,
+ * or a context that has generated fewer lists). A count above the vocabulary is reported as it is and never followed.
+ * Tests compare the lists generated inside an encoder launch with the reference's, id for id. */
+int slimt_hip_debug_ctx_shortlists(slimt_hip_ctx *ctx, size_t n_batches, uint32_t *ids, size_t capacity, uint32_t *counts);
 /* Diagnostic: which form each sentence-layer of ctx's last batch was cached in -- out[l * B + b],
  * 0 = 20-bit, 1 = 24-bit, 2 = 16-bit (the tight form); *batch = B, or 0 when the batch's caches
  * are all in one form (f32 or 24-bit: formats 1 / 2, a shape without the narrow form, or the

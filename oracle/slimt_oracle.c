@@ -1206,7 +1206,9 @@ size_t so_shortlist_generate(const so_shortlist *sl, int shared, size_t source_v
   /* unique source words -> their aligned target words, :131-145 */
   for (size_t k = 0; k < n_words; ++k) {
     uint32_t word = words[k];
-    if (shared) target_table[word] = 1;
+    /* a shared-vocabulary word at or above the target vocabulary: Shortlist.cc:133 writes past its table there
+     * (undefined); no id exists for it, so it selects nothing of its own -- its list still counts */
+    if (shared && word < target_vocab) target_table[word] = 1;
     if (!source_table[word]) {
       uint64_t begin = sl->word_to_offset[word], end = sl->word_to_offset[word + 1];
       for (uint64_t j = begin; j < end; ++j) target_table[sl->shortlist[j]] = 1;

@@ -44,7 +44,7 @@ SYMBOLS = [
     "slimt_hip_ctx_set_scores", "slimt_hip_ctx_set_target_prefix", "slimt_hip_ctx_set_sampling", "slimt_hip_sampling_key",
     "slimt_hip_ctx_set_sampling_truncation", "slimt_hip_sample_truncated",
     "slimt_hip_score", "slimt_hip_score_async", "slimt_hip_score_device", "slimt_hip_score_async_generated",
-    "slimt_hip_ctx_set_score_alternatives",
+    "slimt_hip_ctx_set_score_alternatives", "slimt_hip_debug_ctx_shortlists",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -242,6 +242,7 @@ def lib():
     L.slimt_hip_debug_kv_centres.argtypes = [vp, vp, sz, vp]
     L.slimt_hip_model_set_kv_centres.argtypes = [vp, vp, sz]
     L.slimt_hip_debug_break_shortlist_handoff.argtypes = [vp, i32, u32]
+    L.slimt_hip_debug_ctx_shortlists.argtypes = [vp, sz, vp, sz, vp]
     L.slimt_hip_debug_cross_attention.argtypes = [vp, i32, i32, vp, vp, vp]
     L.slimt_hip_model_set_decoder_budget.argtypes = [vp, i32]
     L.slimt_hip_model_set_kv_cache_policy.argtypes = [vp, i32]
@@ -1119,6 +1120,17 @@ class Context:
     def debug_break_shortlist_handoff(self, broken: bool, poll_limit: int = 1 << 24):
         """The waiters of an in-launch shortlist look for a publication that never comes (tests: the timeout path)."""
         _chk(lib().slimt_hip_debug_break_shortlist_handoff(self.h, 1 if broken else 0, int(poll_limit)))
+
+    def debug_shortlists(self, n_batches: int = 1, capacity: Optional[int] = None, with_counts: bool = False):
+        """slimt_hip_debug_ctx_shortlists: the lists the last *_generated call left in this context, one uint32 array per
+        sub-batch (one for an unmerged call) -- the first min(count, capacity) ids; capacity defaults to the vocabulary.
+        with_counts: also the device's counts (uint32 [n_batches]), reported in full whatever the capacity."""
+        cap = self.model.V if capacity is None else int(capacity)
+        ids = np.zeros((max(n_batches, 1), max(cap, 1)), dtype=np.uint32)
+        counts = np.zeros(max(n_batches, 1), dtype=np.uint32)
+        _chk(lib().slimt_hip_debug_ctx_shortlists(self.h, n_batches, _p(ids), cap, _p(counts)))
+        lists = [ids[j, : min(int(counts[j]), cap)].copy() for j in range(n_batches)]
+        return (lists, counts) if with_counts else lists
 
     def debug_decoder_plan(self) -> dict:
         """The plan of this context's last fused decoder launch under the decoder admission (decoder_plan.h)."""

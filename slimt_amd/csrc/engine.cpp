@@ -995,6 +995,25 @@ extern "C" int slimt_hip_debug_break_shortlist_handoff(slimt_hip_ctx *ctx, int b
   return 0;
 }
 
+extern "C" int slimt_hip_debug_ctx_shortlists(slimt_hip_ctx *ctx, size_t n_batches, uint32_t *ids, size_t capacity, uint32_t *counts) {
+  if (!ctx || !ids || !counts) return fail(-1, "null argument");
+  if (n_batches == 0 || n_batches > (size_t)kMaxMerge) return fail(-1, "%zu shortlists not in 1..%d", n_batches, kMaxMerge);
+  const size_t V = (size_t)ctx->model->V;
+  // sub-batch j's ids at j * V, its count at n_sl_dev[j] (translate_many_generated); only what the context has reserved
+  if (!ctx->n_sl_dev.p || ctx->n_sl_dev.bytes < n_batches * 4)
+    return fail(-1, "shortlists: the context holds %zu counts, %zu asked for (no *_generated call yet?)", ctx->n_sl_dev.bytes / 4, n_batches);
+  if (!ctx->shortlist.p || ctx->shortlist.bytes < n_batches * V * 4)
+    return fail(-1, "shortlists: the context holds room for %zu lists of %zu ids, %zu asked for", ctx->shortlist.bytes / (V * 4), V, n_batches);
+  HIPCHK(hipSetDevice(ctx->model->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(counts, ctx->n_sl_dev.p, n_batches * 4, hipMemcpyDeviceToHost));
+  for (size_t j = 0; j < n_batches; ++j) {
+    const size_t n = std::min(std::min((size_t)counts[j], capacity), V);  // (a count above V is reported as it is, never followed)
+    if (n) HIPCHK(hipMemcpy(ids + j * capacity, ctx->shortlist.as<uint32_t>() + j * V, n * 4, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
 extern "C" int slimt_hip_debug_kv_narrow_limit(slimt_hip_model *model, int limit) {
   if (!model) return fail(-1, "model is NULL");
   if (limit < 1 || limit > (1 << 19)) return fail(-1, "narrow-form limit %d not in 1..2^19 (20 bits hold [-2^19, 2^19))", limit);
