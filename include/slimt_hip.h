@@ -686,6 +686,63 @@ int slimt_hip_ctx_set_score_alternatives(slimt_hip_ctx *ctx, uint32_t k, uint32_
                                          uint32_t *rank);
 
 
+/* ---- candidates: several target rows per source from one encoding ---------- */
+/* The score calls above with N candidate targets tgt_ids [N][T] / tgt_len [N] over a source batch src_ids [B][S] /
+ * lengths [B]: cand_src [N] names each candidate's source, cand_src[c] < B. The B sources are encoded ONCE and the N
+ * candidates go through the tall pass; scores [N][T] and the nullable align [N][T][S] are indexed by candidate.
+ * THE CONTRACT: for candidate c and t < n_c = min(tgt_len[c], T), every value written is bit for bit what slimt_hip_score
+ * writes for row c when called on the duplicated batch src_ids[cand_src], lengths[cand_src] with the same targets and
+ * output layer (alignment columns j < lengths[cand_src[c]]); nothing else is written. It holds because every row's
+ * arithmetic is independent of its neighbours.
+ * cand_src may be in ANY order; a source may have no candidate and a candidate may be empty (n_c = 0). The order affects
+ * speed only: the attention keeps one source's K / V staged for a run of SLIMT_HIP_CANDIDATE_RUN consecutive candidates
+ * and restages when the next live candidate names another source, so candidates sorted by source cost least.
+ * The context bounds B (max_batch), S and B * S only; N is bounded by 1 <= T <= 65536 and N * T <= 2^24, and everything
+ * sized by N (the row workspace, the staging of pageable targets, scores, alignments and alternatives) grows on demand.
+ * N = 0 is a successful call that writes nothing. Rows are chunked in whole candidates of at most max(T, 8192) rows.
+ * Host calls check cand_src[c] < B, tgt_len[c] <= T and every id, and refuse with a message; pinned arrays are read and
+ * written in place, pageable ones bracketed by copies (the copy down first), as for slimt_hip_score_async. Device
+ * arrays cannot be checked: a cand_src[c] >= B is taken as B - 1 and a length past T as T (that candidate alone is
+ * undefined; nothing is read or written out of bounds).
+ * A candidate call IS a score call: it takes and disarms slimt_hip_ctx_set_score_alternatives (the arrays are then
+ * [N][T][k], [N][T][k] and [N][T]), leaves translate options armed, and refuses K/V cache format 3. */
+#define SLIMT_HIP_CANDIDATE_RUN 2
+int slimt_hip_score_candidates(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                               const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids,
+                               const uint32_t *tgt_len, size_t T, const uint32_t *cand_src, size_t N, float *scores,
+                               float *align);
+int slimt_hip_score_candidates_async(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
+                                     size_t S, const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids,
+                                     const uint32_t *tgt_len, size_t T, const uint32_t *cand_src, size_t N,
+                                     float *scores, float *align);
+int slimt_hip_score_candidates_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids, const uint32_t *d_lengths, size_t B,
+                                      size_t S, const uint32_t *d_shortlist, size_t n_shortlist,
+                                      const uint32_t *d_tgt_ids, const uint32_t *d_tgt_len, size_t T,
+                                      const uint32_t *d_cand_src, size_t N, float *d_scores, float *d_align);
+int slimt_hip_score_candidates_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *shortlist,
+                                               const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                                               const uint32_t *tgt_ids, const uint32_t *tgt_len, size_t T,
+                                               const uint32_t *cand_src, size_t N, float *scores, float *align);
+
+/* Ranks the candidates of each source by their scores [N][T] (as a candidate call wrote them):
+ *   - totals[c] is the f32 sum of scores[c][t] over t < n_c = min(tgt_len[c], T), accumulated in ascending t from +0.0f
+ *     with one f32 add per term (a host loop reproduces the bits; -inf and NaN propagate); n_c = 0 gives 0.0f;
+ *   - key_c = totals[c] (mode 0, sum) or totals[c] / (float)n_c (mode 1, mean per token: one IEEE division); any other
+ *     mode is refused;
+ *   - best[b] is the lowest c with cand_src[c] == b, n_c > 0 and key_c not NaN whose key is >= every other such key,
+ *     keys compared as floats (+0 equals -0; -inf competes and loses to anything finite); 0xFFFFFFFF when the source has
+ *     no such candidate.
+ * The result does not depend on the order of cand_src or on scheduling. totals [N] f32, best [B] u32; B >= 1, T >= 1,
+ * N * T <= 2^24; N = 0 writes best only. slimt_hip_candidates_rank takes host pointers, is stateless and waits (it
+ * refuses a cand_src[c] >= B and a tgt_len[c] > T); slimt_hip_candidates_rank_device runs on ctx's stream over device
+ * arrays, e.g. behind slimt_hip_score_candidates_device without a host round trip (values it cannot check are clamped
+ * as by that call). */
+int slimt_hip_candidates_rank(const float *scores, const uint32_t *tgt_len, const uint32_t *cand_src, size_t N, size_t T,
+                              size_t B, int mode, float *totals, uint32_t *best);
+int slimt_hip_candidates_rank_device(slimt_hip_ctx *ctx, const float *d_scores, const uint32_t *d_tgt_len,
+                                     const uint32_t *d_cand_src, size_t N, size_t T, size_t B, int mode, float *d_totals,
+                                     uint32_t *d_best);
+
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, HIP events bracket every launch of kernel family `kernel_id`
  * on the ctx stream; slimt_hip_profile_read returns the number of launches

@@ -16,6 +16,7 @@ import numpy as np
 from . import build as _build
 
 MAX_ALTERNATIVES = 8  # SLIMT_HIP_MAX_ALTERNATIVES
+CANDIDATE_RUN = 2  # SLIMT_HIP_CANDIDATE_RUN: consecutive candidates one attention workgroup walks (score_candidates.hip)
 
 SYMBOLS = [
     "slimt_hip_abi_version", "slimt_hip_last_error", "slimt_hip_device_count",
@@ -45,6 +46,8 @@ SYMBOLS = [
     "slimt_hip_ctx_set_sampling_truncation", "slimt_hip_sample_truncated",
     "slimt_hip_score", "slimt_hip_score_async", "slimt_hip_score_device", "slimt_hip_score_async_generated",
     "slimt_hip_ctx_set_score_alternatives", "slimt_hip_debug_ctx_shortlists",
+    "slimt_hip_score_candidates", "slimt_hip_score_candidates_async", "slimt_hip_score_candidates_device",
+    "slimt_hip_score_candidates_async_generated", "slimt_hip_candidates_rank", "slimt_hip_candidates_rank_device",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -269,6 +272,12 @@ def lib():
     L.slimt_hip_score_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp]
     L.slimt_hip_score_async_generated.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, sz, vp, vp]
     L.slimt_hip_ctx_set_score_alternatives.argtypes = [vp, u32, vp, vp, vp]
+    L.slimt_hip_score_candidates.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp]
+    L.slimt_hip_score_candidates_async.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp]
+    L.slimt_hip_score_candidates_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp]
+    L.slimt_hip_score_candidates_async_generated.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, sz, vp, sz, vp, vp]
+    L.slimt_hip_candidates_rank.argtypes = [vp, vp, vp, sz, sz, sz, i32, vp, vp]
+    L.slimt_hip_candidates_rank_device.argtypes = [vp, vp, vp, vp, sz, sz, sz, i32, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("slimt_hip_abi_version",):
@@ -303,6 +312,24 @@ def sample_truncated(logits, temperature: float = 1.0, top_k: int = 0, top_p: fl
     _chk(lib().slimt_hip_sample_truncated(_p(logits), M, N, _p(ids), float(temperature), int(top_k), float(top_p), _p(keys),
                                           _p(steps), _p(cols), _p(thr), _p(kept), _p(sc)))
     return cols, thr, kept, sc
+
+
+def candidates_rank(scores, tgt_len, cand_src, B: int, mean: bool = False, mode=None):
+    """slimt_hip_candidates_rank: scores [N, T] float32, tgt_len [N], cand_src [N] (< B). Returns (totals float32 [N] -- each
+    candidate's f32 sum over t < tgt_len[c], ascending t from +0 -- and best uint32 [B] -- per source the lowest index among
+    the candidates of the largest key, 0xFFFFFFFF where none competes; the key is the total, or with mean=True the total
+    divided by the length). mode: the C call's integer, where that is what is tested (overrides mean)."""
+    scores = np.ascontiguousarray(scores, dtype=np.float32)
+    tgt_len = np.ascontiguousarray(tgt_len, dtype=np.uint32)
+    cand_src = np.ascontiguousarray(cand_src, dtype=np.uint32)
+    if scores.ndim != 2 or tgt_len.shape != scores.shape[:1] or cand_src.shape != scores.shape[:1]:
+        raise ValueError("candidates_rank: scores [N, T], tgt_len [N] and cand_src [N] expected, got %s, %s, %s"
+                         % (scores.shape, tgt_len.shape, cand_src.shape))
+    N, T = scores.shape
+    totals, best = np.zeros(N, np.float32), np.zeros(int(B), np.uint32)
+    _chk(lib().slimt_hip_candidates_rank(_p(scores), _p(tgt_len), _p(cand_src), N, T, int(B),
+                                         int(bool(mean)) if mode is None else int(mode), _p(totals), _p(best)))
+    return totals, best
 
 
 def translate_many_rows(sizes) -> int:
@@ -973,6 +1000,110 @@ class Context:
                                           vp(d_align) if d_align else None))
         return alternatives
 
+    @staticmethod
+    def _candidates_host(ids, lengths, tgt_ids, tgt_len, cand_src):
+        """(ids [B,S], lengths [B], tgt_ids [N,T], tgt_len [N], cand_src [N]) as C-contiguous uint32 arrays (shapes checked)"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        tgt_ids = np.ascontiguousarray(tgt_ids, dtype=np.uint32)
+        tgt_len = np.ascontiguousarray(tgt_len, dtype=np.uint32)
+        cand_src = np.ascontiguousarray(cand_src, dtype=np.uint32)
+        if ids.ndim != 2 or tgt_ids.ndim != 2:
+            raise ValueError("score_candidates: ids [B, S] and tgt_ids [N, T] expected")
+        B, N = ids.shape[0], tgt_ids.shape[0]
+        if lengths.shape != (B,) or tgt_len.shape != (N,) or cand_src.shape != (N,):
+            raise ValueError("score_candidates: %d sources and %d candidates, but lengths %s, tgt_len %s, cand_src %s"
+                             % (B, N, lengths.shape, tgt_len.shape, cand_src.shape))
+        return ids, lengths, tgt_ids, tgt_len, cand_src
+
+    def score_candidates(self, ids, lengths, shortlist, tgt_ids, tgt_len, cand_src, want_align: bool = False, fill=np.nan,
+                         alternatives=None):
+        """slimt_hip_score_candidates: score() for N candidate targets tgt_ids [N,T] / tgt_len [N] over B sources encoded once;
+        cand_src [N] (< B, any order) names each candidate's source. Returns scores [N,T] and align [N,T,S] | None (+ the
+        alternatives' alt_ids [N,T,k], alt_scores [N,T,k], rank [N,T]), bit for bit what score() returns on ids[cand_src]."""
+        ids, lengths, tgt_ids, tgt_len, cand_src = self._candidates_host(ids, lengths, tgt_ids, tgt_len, cand_src)
+        (B, S), (N, T) = ids.shape, tgt_ids.shape
+        sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
+        sc = np.full((N, T), fill, dtype=np.float32)
+        align = np.full((N, T, S), fill, dtype=np.float32) if want_align else None
+        alt = None
+        if alternatives:
+            k = self._alternatives_k(alternatives)
+            alt = (np.full((N, T, k), 0xFFFFFFFF, dtype=np.uint32), np.full((N, T, k), fill, dtype=np.float32),
+                   np.full((N, T), 0xFFFFFFFF, dtype=np.uint32))
+            self.set_score_alternatives(k, *alt)
+        _chk(lib().slimt_hip_score_candidates(self.h, _p(ids), _p(lengths), B, S, _p(sl), 0 if sl is None else sl.size,
+                                              _p(tgt_ids), _p(tgt_len), T, _p(cand_src), N, _p(sc), _p(align)))
+        return (sc, align) + alt if alt else (sc, align)
+
+    def score_candidates_buffers(self, B: int, S: int, N: int, T: int, want_align: bool = False):
+        """This context's pinned arrays for score_candidates_async: (ids [B,S], lengths [B], tgt_ids [N,T], tgt_len [N],
+        cand_src [N], scores [N,T], align [N,T,S] | None)."""
+        pin = lambda name: self._pinned.setdefault(name, _Pinned())
+        return (pin("ids").array(np.uint32, (B, S)), pin("len").array(np.uint32, (B,)),
+                pin("tg").array(np.uint32, (N, T)), pin("tl").array(np.uint32, (N,)), pin("cs").array(np.uint32, (N,)),
+                pin("sc").array(np.float32, (N, T)), pin("al").array(np.float32, (N, T, S)) if want_align else None)
+
+    def score_candidates_async(self, bufs, shortlist=None, generator=None, alternatives=None):
+        """slimt_hip_score_candidates_async[_generated] on (ids, lengths, tgt_ids, tgt_len, cand_src, scores, align | None) host
+        arrays (already filled; those of score_candidates_buffers() are pinned: read and written in place); synchronize()
+        before reading the outputs. alternatives: the caller's (alt_ids [N,T,k], alt_scores | None, rank | None), of the
+        kind of scores; returned as given."""
+        ids, lengths, tgt_ids, tgt_len, cand_src, sc, align = bufs
+        for a, dt in ((ids, np.uint32), (lengths, np.uint32), (tgt_ids, np.uint32), (tgt_len, np.uint32),
+                      (cand_src, np.uint32), (sc, np.float32)):
+            if a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError("score_candidates_async: C-contiguous uint32 inputs and float32 scores expected")
+        if ids.ndim != 2 or tgt_ids.ndim != 2:
+            raise ValueError("score_candidates_async: ids [B, S] and tgt_ids [N, T] expected")
+        (B, S), (N, T) = ids.shape, tgt_ids.shape
+        if lengths.shape != (B,) or tgt_len.shape != (N,) or cand_src.shape != (N,) or sc.shape != (N, T):
+            raise ValueError("score_candidates_async: mismatched shapes")
+        if align is not None and (align.dtype != np.float32 or align.shape != (N, T, S) or not align.flags.c_contiguous):
+            raise ValueError("score_candidates_async: a C-contiguous float32 align of shape %s expected" % ((N, T, S),))
+        alt = None
+        if alternatives is not None:
+            alt = tuple(alternatives)
+            if len(alt) != 3:
+                raise ValueError("score alternatives: (alt_ids, alt_scores | None, rank | None) expected")
+            self.set_score_alternatives(self._alternatives_arrays(alt, N, T), *alt)
+        if generator is not None:
+            _chk(lib().slimt_hip_score_candidates_async_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, _p(tgt_ids),
+                                                                  _p(tgt_len), T, _p(cand_src), N, _p(sc), _p(align)))
+            return alt
+        sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
+        _chk(lib().slimt_hip_score_candidates_async(self.h, _p(ids), _p(lengths), B, S, _p(sl), 0 if sl is None else sl.size,
+                                                    _p(tgt_ids), _p(tgt_len), T, _p(cand_src), N, _p(sc), _p(align)))
+        return alt
+
+    def score_candidates_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int, n_shortlist: int,
+                                d_tgt_ids: int, d_tgt_len: int, T: int, d_cand_src: int, N: int, d_scores: int,
+                                d_align: int = 0, alternatives=None):
+        """slimt_hip_score_candidates_device: device pointers (ints) in and out, asynchronous on this context's stream.
+        alternatives: (k, d_alt_ids, d_alt_scores | 0, d_rank | 0), device pointers to [N,T,k] / [N,T]; returned as given."""
+        vp = C.c_void_p
+        if alternatives is not None:
+            if len(alternatives) != 4:
+                raise ValueError("score alternatives: (k, d_alt_ids, d_alt_scores | 0, d_rank | 0) expected")
+            k, d_ai, d_as, d_ar = alternatives
+            k = self._alternatives_k(k)
+            if not d_ai:
+                raise ValueError("score alternatives: d_alt_ids is 0")
+            self.set_score_alternatives(k, int(d_ai), int(d_as) if d_as else None, int(d_ar) if d_ar else None)
+        _chk(lib().slimt_hip_score_candidates_device(self.h, vp(d_ids), vp(d_lengths), B, S,
+                                                     vp(d_shortlist) if n_shortlist else None, n_shortlist, vp(d_tgt_ids),
+                                                     vp(d_tgt_len), T, vp(d_cand_src), N, vp(d_scores),
+                                                     vp(d_align) if d_align else None))
+        return alternatives
+
+    def candidates_rank_device(self, d_scores: int, d_tgt_len: int, d_cand_src: int, N: int, T: int, B: int, d_totals: int,
+                               d_best: int, mean: bool = False):
+        """slimt_hip_candidates_rank_device: candidates_rank over device arrays on this context's stream (totals [N] float32,
+        best [B] uint32), e.g. behind score_candidates_device."""
+        vp = C.c_void_p
+        _chk(lib().slimt_hip_candidates_rank_device(self.h, vp(d_scores), vp(d_tgt_len), vp(d_cand_src), N, T, B,
+                                                    int(bool(mean)), vp(d_totals), vp(d_best)))
+
     def translate_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int,
                          n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int,
                          d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None, truncation=None):
@@ -1233,6 +1364,8 @@ def host_lib():
     H.slimt_hip_service_score.argtypes = [vp, vp, vp, vp, vp, sz, vp]  # (include/slimt_hip_service_score.h)
     H.slimt_hip_service_score_alternatives.argtypes = [vp, vp, vp, vp, vp, sz, C.c_uint32, vp]  # (include/slimt_hip_service_alternatives.h)
     H.slimt_hip_result_alternatives.argtypes = [vp, sz, vp, vp, vp, vp]
+    H.slimt_hip_service_score_candidates.argtypes = [vp, vp, vp, sz, vp, vp, vp, C.c_int, vp]  # (include/slimt_hip_service_candidates.h)
+    H.slimt_hip_result_candidates.argtypes = [vp, vp, vp]
     _host_lib = H
     return H
 
@@ -1296,6 +1429,21 @@ class ServiceResult:
             return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=shape)
 
         return arr(pi, np.uint32, (n, k.value)), arr(ps, np.float32, (n, k.value)), arr(pr, np.uint32, (n,))
+
+    def candidates(self, n_sources: int):
+        """of a BatchService.score_candidates result (slimt_hip_result_candidates): (totals float32 [entries] -- each
+        candidate's summed score --, best uint32 [n_sources] -- per source the index among its own candidates of the best
+        one, 0xFFFFFFFF: none); views valid while this object lives"""
+        pt, pb = C.c_void_p(), C.c_void_p()
+        if host_lib().slimt_hip_result_candidates(self.h, C.byref(pt), C.byref(pb)):
+            raise SlimtHipError(host_lib().slimt_hip_service_last_error().decode())
+
+        def arr(p, dtype, count):
+            if not count or not p.value:
+                return np.zeros(0, dtype)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=(count,))
+
+        return arr(pt, np.float32, self.n), arr(pb, np.uint32, int(n_sources))
 
     def token_scores(self, i: int) -> np.ndarray:
         """sentence i's per-token log-probabilities (EOS included); the service must score"""
@@ -1433,6 +1581,27 @@ class BatchService:
         if rc:
             raise SlimtHipError(host_lib().slimt_hip_service_last_error().decode())
         return ServiceResult(out, np.diff(offsets).astype(np.int64))
+
+    def score_candidates(self, sentences, candidates, mean: bool = False):
+        """slimt_hip_service_score_candidates: candidates[i] is a list of token lists, the candidate translations of
+        sentences[i] (any number, each with its EOS when that is to be scored); each sentence is encoded once. Returns
+        (result, cand_offsets, totals, best): the ServiceResult has ONE ENTRY PER CANDIDATE in the order given -- sentence i's
+        are entries cand_offsets[i] .. cand_offsets[i + 1] - 1, token_scores(e) / alignment(e) as score() gives them for the
+        pair --, totals float32 [entries] their summed scores and best uint32 [len(sentences)] the index among a sentence's
+        own candidates of the best one by the sum (mean=True: by the sum per token), 0xFFFFFFFF where none competes."""
+        if len(candidates) != len(sentences):
+            raise ValueError(f"candidates: {len(candidates)} lists for {len(sentences)} sentences")
+        tokens, offsets = self._flat(sentences)
+        t_tokens, t_offsets = self._flat([c for cs in candidates for c in cs])
+        c_offsets = np.zeros(len(sentences) + 1, np.uint64)
+        np.cumsum([len(cs) for cs in candidates], out=c_offsets[1:])
+        out = C.c_void_p()
+        if host_lib().slimt_hip_service_score_candidates(self.h, _p(tokens), _p(offsets), offsets.size - 1, _p(t_tokens),
+                                                         _p(t_offsets), _p(c_offsets), int(bool(mean)), C.byref(out)):
+            raise SlimtHipError(host_lib().slimt_hip_service_last_error().decode())
+        res = ServiceResult(out, np.repeat(np.diff(offsets).astype(np.int64), np.diff(c_offsets).astype(np.int64)))
+        totals, best = res.candidates(len(sentences))
+        return res, c_offsets, totals, best
 
     def close(self):
         if getattr(self, "h", None):

@@ -1159,7 +1159,7 @@ void ctx_free(slimt_hip_ctx *c) {
                     &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->tr_logits, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag,
-                    &c->score_ws, &c->score_io, &c->alt_stage};
+                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank};
   for (auto *b : bufs) b->release();
   free_affine(c->out_sl);
   if (c->n_finished_host) (void)hipHostFree(c->n_finished_host);
@@ -3972,12 +3972,13 @@ int score_reserve(slimt_hip_ctx *c, DevBuf &buf, size_t bytes) {
   return 0;
 }
 
-int score_check(const slimt_hip_ctx *c, size_t B, size_t S, size_t n_sl, size_t T) {
+// NR: the target rows of the call -- its B sentences, or the N candidates of a candidate call
+int score_check(const slimt_hip_ctx *c, size_t B, size_t S, size_t n_sl, size_t T, size_t NR) {
   RCCHK(check_batch(c, B, S));
   const slimt_hip_model *m = c->model;
   if (T == 0) return fail(-1, "score: T is 0 (a target row needs at least one column)");
-  if (T > kScoreMaxT || B * T > kScoreMaxRows)
-    return fail(-1, "score: %zu x %zu target positions exceed the limits (T <= %zu, B * T <= %zu)", B, T, kScoreMaxT, kScoreMaxRows);
+  if (T > kScoreMaxT || NR > kScoreMaxRows || NR * T > kScoreMaxRows)
+    return fail(-1, "score: %zu x %zu target positions exceed the limits (T <= %zu, B * T <= %zu)", NR, T, kScoreMaxT, kScoreMaxRows);
   if (n_sl > (size_t)m->V) return fail(-1, "shortlist larger than the vocabulary");
   if (m->kv_format == 3)
     return fail(-1, "score: the model is set to K/V cache format 3 (the literal cross-attention order); the scoring pass "
@@ -4015,9 +4016,12 @@ bool device_visible(const void *p) {
 }
 
 // alt (k = 0: unarmed): ids / scores / rank are addresses the kernels write
+// d_cand (nullable): a candidate call -- the targets, scores, alignment and alternatives are those of N candidates, candidate
+// c over source d_cand[c]; the B sources are encoded once. nullptr: target row b belongs to source b (N is not read)
 int score_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_lengths, size_t B, size_t S,
                  const uint32_t *d_shortlist, size_t n_sl, const uint32_t *d_tgt, const uint32_t *d_tlen, size_t T,
-                 float *d_scores, float *d_align, const ScoreAltArgs &alt) {
+                 float *d_scores, float *d_align, const ScoreAltArgs &alt, const uint32_t *d_cand = nullptr, size_t N = 0) {
+  const size_t NR = d_cand ? N : B;  // target sentences
   const slimt_hip_model *m = c->model;
   hipStream_t st = c->stream;
   const size_t D = (size_t)m->D, F = (size_t)m->F;
@@ -4035,7 +4039,7 @@ int score_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_leng
   const AffineW &out = output_layer(c);
   // workspace of one chunk: four f32 row buffers, two int8 ones, FFN1's int8 output, the target columns
   const size_t spc = std::max<size_t>(1, kScoreChunkRows / T);  // sentences per chunk
-  const size_t ws_rows = std::min(B, spc) * T;
+  const size_t ws_rows = std::min(NR, spc) * T;
   auto up = [](size_t n) { return (n + 255) / 256 * 256; };
   const size_t b_f32 = up(ws_rows * D * 4), b_i8 = up(ws_rows * D), b_f8 = up(ws_rows * F), b_col = up(ws_rows * 4);
   RCCHK(score_reserve(c, c->score_ws, 4 * b_f32 + 2 * b_i8 + b_f8 + b_col));
@@ -4050,10 +4054,10 @@ int score_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_leng
   int *tcol = reinterpret_cast<int *>(f8 + b_f8);
   const float *kv = c->kv.as<float>();
   const size_t M = B * S;
-  for (size_t b0 = 0; b0 < B; b0 += spc) {
+  for (size_t b0 = 0; b0 < NR; b0 += spc) {
     ScoreRows rows;
     rows.b0 = (int)b0;
-    rows.nb = (int)std::min(spc, B - b0);
+    rows.nb = (int)std::min(spc, NR - b0);
     rows.T = (int)T;
     rows.tgt_ids = d_tgt;
     rows.tgt_len = d_tlen;
@@ -4088,7 +4092,15 @@ int score_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_leng
       a.align = l + 1 == m->Ld ? d_align : nullptr;  // alignment = last layer (Transformer.cc:165-174)
       {
         ProfScope ps(c, SLIMT_HIP_K_ATTN_DEC, 0, 0);
-        HIPCHK(launch_score_attention(a, st));
+        if (d_cand) {
+          ScoreCandAttnArgs ca;
+          ca.a = a;
+          ca.cand_src = d_cand;
+          ca.B = (int)B;
+          HIPCHK(launch_score_candidates_attention(ca, st));
+        } else {
+          HIPCHK(launch_score_attention(a, st));
+        }
       }
       // O projection + residual, LayerNorm (Modules.cc:308-316); FFN (Modules.cc:251-257)
       RCCHK(run_affine_res(c, SLIMT_HIP_K_GEMM_DEC, L.attn.o, nullptr, att8, R, h, wx, 0));
@@ -4122,13 +4134,18 @@ int score_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_leng
 
 // Host buffers: validated, then read / written in place where pinned, else bracketed by copies on the context's stream.
 // gen (nullable): the batch's lexical shortlist is generated on the device first (shortlist / n_sl are then not used).
+// candidates: a candidate call (slimt_hip_score_candidates*) -- tgt_ids, tgt_len, scores, align and the alternatives are
+// those of N candidates, cand_src [N] their sources. Otherwise target row b belongs to source b (cand_src / N are not read).
 int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
                size_t S, const uint32_t *shortlist, size_t n_sl, const uint32_t *tgt_ids, const uint32_t *tgt_len, size_t T,
-               float *scores, float *align, bool wait) {
+               float *scores, float *align, bool wait, bool candidates = false, const uint32_t *cand_src = nullptr,
+               size_t N = 0) {
   AltCall ac(ctx);
   if (ctx && T == 0) return fail(-1, "score: T is 0 (a target row needs at least one column)");
-  if (!ctx || !src_ids || !lengths || !tgt_ids || !tgt_len || !scores) return fail(-1, "null argument");
-  RCCHK(score_check(ctx, B, S, n_sl, T));
+  if (!ctx || !src_ids || !lengths || !tgt_ids || !tgt_len || !scores || (candidates && !cand_src))
+    return fail(-1, "null argument");
+  const size_t NR = candidates ? N : B;  // target sentences
+  RCCHK(score_check(ctx, B, S, n_sl, T, NR));
   ScoreAltArgs alt = ac.a;
   if (alt.k) {  // the three arrays are of the kind of scores: all pinned (written in place) or all pageable (staged)
     const bool pinned = host_device_view(scores) != nullptr;
@@ -4151,13 +4168,17 @@ int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src
     if (src_ids[i] >= vmax) return fail(-1, "token id %u out of range", src_ids[i]);
   for (size_t i = 0; !gen && i < n_sl; ++i)
     if (shortlist[i] >= (uint32_t)m->V) return fail(-1, "shortlist id %u out of range", shortlist[i]);
-  for (size_t b = 0; b < B; ++b) {
+  for (size_t b = 0; b < B; ++b)
     if (lengths[b] > S) return fail(-1, "length %u > S", lengths[b]);
+  for (size_t b = 0; b < NR; ++b) {
+    if (candidates && cand_src[b] >= B)
+      return fail(-1, "score: candidate %zu names source %u, the batch has %zu", b, cand_src[b], B);
     if (tgt_len[b] > T) return fail(-1, "score: target length %u of sentence %zu > T %zu", tgt_len[b], b, T);
     for (size_t t = 0; t < tgt_len[b]; ++t)
       if (tgt_ids[b * T + t] >= (uint32_t)m->V)
         return fail(-1, "score: target id %u of sentence %zu out of range", tgt_ids[b * T + t], b);
   }
+  if (NR == 0) return 0;  // (a candidate call without candidates: nothing to write)
   HIPCHK(hipSetDevice(m->device));
   hipStream_t st = ctx->stream;
   if (!gen && n_sl && (ctx->sl_host.size() != n_sl || std::memcmp(ctx->sl_host.data(), shortlist, n_sl * 4) != 0)) {
@@ -4166,14 +4187,16 @@ int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src
     HIPCHK(hipStreamSynchronize(st));
     ctx->sl_host.assign(shortlist, shortlist + n_sl);
   }
-  // inputs: pinned arrays in place, others staged; [tgt_ids B T][tgt_len B][scores B T] in score_io
+  // inputs: pinned arrays in place, others staged; [tgt_ids NR T][tgt_len NR][cand_src NR][scores NR T] in score_io
   const uint32_t *d_ids = static_cast<const uint32_t *>(host_device_view(src_ids));
   const uint32_t *d_len = static_cast<const uint32_t *>(host_device_view(lengths));
   const uint32_t *d_tgt = static_cast<const uint32_t *>(host_device_view(tgt_ids));
   const uint32_t *d_tlen = static_cast<const uint32_t *>(host_device_view(tgt_len));
   float *d_scores = static_cast<float *>(host_device_view(scores));
-  RCCHK(score_reserve(ctx, ctx->score_io, (2 * B * T + B) * 4));
-  if (align) RCCHK(score_reserve(ctx, ctx->align, B * T * S * 4));
+  const uint32_t *d_cand = candidates ? static_cast<const uint32_t *>(host_device_view(cand_src)) : nullptr;
+  RCCHK(score_reserve(ctx, ctx->score_io, (2 * NR * T + 2 * NR) * 4));
+  DevBuf &al_stage = candidates ? ctx->cand_align : ctx->align;  // (ctx->align is the context's, sized for max_batch)
+  if (align) RCCHK(score_reserve(ctx, al_stage, NR * T * S * 4));
   if (!d_ids) {
     HIPCHK(hipMemcpyAsync(ctx->ids.p, src_ids, B * S * 4, hipMemcpyHostToDevice, st));
     d_ids = ctx->ids.as<uint32_t>();
@@ -4184,24 +4207,28 @@ int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src
   }
   uint32_t *io = ctx->score_io.as<uint32_t>();
   if (!d_tgt) {
-    HIPCHK(hipMemcpyAsync(io, tgt_ids, B * T * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(io, tgt_ids, NR * T * 4, hipMemcpyHostToDevice, st));
     d_tgt = io;
   }
   if (!d_tlen) {
-    HIPCHK(hipMemcpyAsync(io + B * T, tgt_len, B * 4, hipMemcpyHostToDevice, st));
-    d_tlen = io + B * T;
+    HIPCHK(hipMemcpyAsync(io + NR * T, tgt_len, NR * 4, hipMemcpyHostToDevice, st));
+    d_tlen = io + NR * T;
+  }
+  if (candidates && !d_cand) {
+    HIPCHK(hipMemcpyAsync(io + NR * T + NR, cand_src, NR * 4, hipMemcpyHostToDevice, st));
+    d_cand = io + NR * T + NR;
   }
   // outputs that are copied back go down first: the copy back then restores every entry the pass does not write
   float *stage_sc = nullptr;
   if (!d_scores) {
-    stage_sc = reinterpret_cast<float *>(io + B * T + B);
-    HIPCHK(hipMemcpyAsync(stage_sc, scores, B * T * 4, hipMemcpyHostToDevice, st));
+    stage_sc = reinterpret_cast<float *>(io + NR * T + 2 * NR);
+    HIPCHK(hipMemcpyAsync(stage_sc, scores, NR * T * 4, hipMemcpyHostToDevice, st));
     d_scores = stage_sc;
   }
-  if (align) HIPCHK(hipMemcpyAsync(ctx->align.p, align, B * T * S * 4, hipMemcpyHostToDevice, st));
+  if (align) HIPCHK(hipMemcpyAsync(al_stage.p, align, NR * T * S * 4, hipMemcpyHostToDevice, st));
   // the alternatives likewise: pinned arrays in place, pageable ones as [ids B T k][scores B T k][rank B T] in alt_stage
   ScoreAltArgs user_alt = alt;
-  const size_t n_alt = B * T * (size_t)alt.k;
+  const size_t n_alt = NR * T * (size_t)alt.k;
   bool stage_alt = false;
   if (alt.k) {
     if (void *v = host_device_view(alt.ids)) {
@@ -4210,7 +4237,7 @@ int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src
       alt.rank = alt.rank ? static_cast<uint32_t *>(host_device_view(alt.rank)) : nullptr;
     } else {
       stage_alt = true;
-      RCCHK(score_reserve(ctx, ctx->alt_stage, (2 * n_alt + B * T) * 4));
+      RCCHK(score_reserve(ctx, ctx->alt_stage, (2 * n_alt + NR * T) * 4));
       uint32_t *sa = ctx->alt_stage.as<uint32_t>();
       alt.ids = sa;
       HIPCHK(hipMemcpyAsync(alt.ids, user_alt.ids, n_alt * 4, hipMemcpyHostToDevice, st));
@@ -4220,7 +4247,7 @@ int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src
       }
       if (user_alt.rank) {
         alt.rank = sa + 2 * n_alt;
-        HIPCHK(hipMemcpyAsync(alt.rank, user_alt.rank, B * T * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(alt.rank, user_alt.rank, NR * T * 4, hipMemcpyHostToDevice, st));
       }
     }
   }
@@ -4238,15 +4265,15 @@ int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src
     HIPCHK(hipStreamSynchronize(st));
     n_sl = n;
   }
-  RCCHK(score_device(ctx, d_ids, d_len, B, S, d_sl, n_sl, d_tgt, d_tlen, T, d_scores, align ? ctx->align.as<float>() : nullptr,
-                     alt));
-  if (stage_sc) HIPCHK(hipMemcpyAsync(scores, stage_sc, B * T * 4, hipMemcpyDeviceToHost, st));
+  RCCHK(score_device(ctx, d_ids, d_len, B, S, d_sl, n_sl, d_tgt, d_tlen, T, d_scores, align ? al_stage.as<float>() : nullptr,
+                     alt, d_cand, NR));
+  if (stage_sc) HIPCHK(hipMemcpyAsync(scores, stage_sc, NR * T * 4, hipMemcpyDeviceToHost, st));
   if (stage_alt) {
     HIPCHK(hipMemcpyAsync(user_alt.ids, alt.ids, n_alt * 4, hipMemcpyDeviceToHost, st));
     if (user_alt.scores) HIPCHK(hipMemcpyAsync(user_alt.scores, alt.scores, n_alt * 4, hipMemcpyDeviceToHost, st));
-    if (user_alt.rank) HIPCHK(hipMemcpyAsync(user_alt.rank, alt.rank, B * T * 4, hipMemcpyDeviceToHost, st));
+    if (user_alt.rank) HIPCHK(hipMemcpyAsync(user_alt.rank, alt.rank, NR * T * 4, hipMemcpyDeviceToHost, st));
   }
-  if (align) HIPCHK(hipMemcpyAsync(align, ctx->align.p, B * T * S * 4, hipMemcpyDeviceToHost, st));
+  if (align) HIPCHK(hipMemcpyAsync(align, al_stage.p, NR * T * S * 4, hipMemcpyDeviceToHost, st));
   if (wait) RCCHK(slimt_hip_ctx_synchronize(ctx));
   return 0;
 }
@@ -4280,7 +4307,7 @@ extern "C" int slimt_hip_score_device(slimt_hip_ctx *ctx, const uint32_t *d_src_
   AltCall ac(ctx);
   if (ctx && T == 0) return fail(-1, "score: T is 0 (a target row needs at least one column)");
   if (!ctx || !d_src_ids || !d_lengths || !d_tgt_ids || !d_tgt_len || !d_scores) return fail(-1, "null argument");
-  RCCHK(score_check(ctx, B, S, n_shortlist, T));
+  RCCHK(score_check(ctx, B, S, n_shortlist, T, B));
   if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
   HIPCHK(hipSetDevice(ctx->model->device));
   if (ac.a.k) {
@@ -4292,4 +4319,132 @@ extern "C" int slimt_hip_score_device(slimt_hip_ctx *ctx, const uint32_t *d_src_
   }
   return score_device(ctx, d_src_ids, d_lengths, B, S, d_shortlist, n_shortlist, d_tgt_ids, d_tgt_len, T, d_scores, d_align,
                       ac.a);
+}
+
+// ---- candidates: N target rows over B sources encoded once (include/slimt_hip.h, slimt_hip_score_candidates*) ----------
+// score_host / score_device above with the targets counted by candidate; score_candidates.hip has the attention that
+// knows each candidate's source, and the ranking.
+static_assert(slimt_hip::kScoreCandidateRun == SLIMT_HIP_CANDIDATE_RUN, "the run length the header documents");
+
+extern "C" int slimt_hip_score_candidates(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                                          const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids,
+                                          const uint32_t *tgt_len, size_t T, const uint32_t *cand_src, size_t N, float *scores,
+                                          float *align) {
+  return score_host(ctx, nullptr, src_ids, lengths, B, S, shortlist, n_shortlist, tgt_ids, tgt_len, T, scores, align, true, true,
+                    cand_src, N);
+}
+
+extern "C" int slimt_hip_score_candidates_async(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
+                                                size_t S, const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids,
+                                                const uint32_t *tgt_len, size_t T, const uint32_t *cand_src, size_t N,
+                                                float *scores, float *align) {
+  return score_host(ctx, nullptr, src_ids, lengths, B, S, shortlist, n_shortlist, tgt_ids, tgt_len, T, scores, align, false, true,
+                    cand_src, N);
+}
+
+extern "C" int slimt_hip_score_candidates_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *shortlist,
+                                                          const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                                                          const uint32_t *tgt_ids, const uint32_t *tgt_len, size_t T,
+                                                          const uint32_t *cand_src, size_t N, float *scores, float *align) {
+  if (!shortlist) {
+    AltCall ac(ctx);  // (taken whatever the outcome)
+    return fail(-1, "null argument");
+  }
+  return score_host(ctx, shortlist, src_ids, lengths, B, S, nullptr, 0, tgt_ids, tgt_len, T, scores, align, false, true, cand_src,
+                    N);
+}
+
+extern "C" int slimt_hip_score_candidates_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids, const uint32_t *d_lengths,
+                                                 size_t B, size_t S, const uint32_t *d_shortlist, size_t n_shortlist,
+                                                 const uint32_t *d_tgt_ids, const uint32_t *d_tgt_len, size_t T,
+                                                 const uint32_t *d_cand_src, size_t N, float *d_scores, float *d_align) {
+  AltCall ac(ctx);
+  if (ctx && T == 0) return fail(-1, "score: T is 0 (a target row needs at least one column)");
+  if (!ctx || !d_src_ids || !d_lengths || !d_tgt_ids || !d_tgt_len || !d_cand_src || !d_scores) return fail(-1, "null argument");
+  RCCHK(score_check(ctx, B, S, n_shortlist, T, N));
+  if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
+  if (N == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->model->device));
+  if (ac.a.k) {
+    const void *arr[3] = {ac.a.ids, ac.a.scores, ac.a.rank};
+    const char *name[3] = {"alt_ids", "alt_scores", "rank"};
+    for (int i = 0; i < 3; ++i)
+      if (arr[i] && !device_visible(arr[i]))
+        return fail(-1, "score alternatives: %s is not memory the device can write (the arrays are of the kind of scores)", name[i]);
+  }
+  return score_device(ctx, d_src_ids, d_lengths, B, S, d_shortlist, n_shortlist, d_tgt_ids, d_tgt_len, T, d_scores, d_align, ac.a,
+                      d_cand_src, N);
+}
+
+namespace {
+int candidates_rank_check(const void *scores, const void *tgt_len, const void *cand_src, size_t N, size_t T, size_t B, int mode,
+                          const void *totals, const void *best) {
+  if (!scores || !tgt_len || !cand_src || !totals || !best) return fail(-1, "null argument");
+  if (mode != 0 && mode != 1) return fail(-1, "candidates rank: mode %d is neither 0 (sum) nor 1 (mean per token)", mode);
+  if (B == 0 || B > 0xffffffffu) return fail(-1, "candidates rank: %zu sources", B);
+  if (T == 0 || T > kScoreMaxT || N > kScoreMaxRows || N * T > kScoreMaxRows)
+    return fail(-1, "candidates rank: %zu x %zu scores exceed the limits (1 <= T <= %zu, N * T <= %zu)", N, T, kScoreMaxT,
+                kScoreMaxRows);
+  return 0;
+}
+}  // namespace
+
+extern "C" int slimt_hip_candidates_rank(const float *scores, const uint32_t *tgt_len, const uint32_t *cand_src, size_t N, size_t T,
+                                         size_t B, int mode, float *totals, uint32_t *best) {
+  RCCHK(candidates_rank_check(scores, tgt_len, cand_src, N, T, B, mode, totals, best));
+  for (size_t c = 0; c < N; ++c) {
+    if (cand_src[c] >= B) return fail(-1, "candidates rank: candidate %zu names source %u of %zu", c, cand_src[c], B);
+    if (tgt_len[c] > T) return fail(-1, "candidates rank: length %u of candidate %zu > T %zu", tgt_len[c], c, T);
+  }
+  Tmp3 t;
+  hipStream_t st = nullptr;
+  HIPCHK(t.a.reserve(std::max<size_t>(1, N * T) * 4));
+  HIPCHK(t.b.reserve(std::max<size_t>(1, N) * 4));
+  HIPCHK(t.c.reserve(std::max<size_t>(1, N) * 4));
+  HIPCHK(t.d.reserve(std::max<size_t>(1, N) * 4));
+  HIPCHK(t.e.reserve(B * 4));
+  HIPCHK(t.f.reserve(B * 8));
+  if (N) {
+    HIPCHK(hipMemcpyAsync(t.a.p, scores, N * T * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(t.b.p, tgt_len, N * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(t.c.p, cand_src, N * 4, hipMemcpyHostToDevice, st));
+  }
+  CandRankArgs a;
+  a.scores = t.a.as<float>();
+  a.tgt_len = t.b.as<uint32_t>();
+  a.cand_src = t.c.as<uint32_t>();
+  a.N = N;
+  a.T = (uint32_t)T;
+  a.B = (uint32_t)B;
+  a.mode = mode;
+  a.totals = t.d.as<float>();
+  a.best = t.e.as<uint32_t>();
+  a.entries = t.f.as<unsigned long long>();
+  HIPCHK(launch_candidates_rank(a, st));
+  if (N) HIPCHK(hipMemcpyAsync(totals, t.d.p, N * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(best, t.e.p, B * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+extern "C" int slimt_hip_candidates_rank_device(slimt_hip_ctx *ctx, const float *d_scores, const uint32_t *d_tgt_len,
+                                                const uint32_t *d_cand_src, size_t N, size_t T, size_t B, int mode,
+                                                float *d_totals, uint32_t *d_best) {
+  if (!ctx) return fail(-1, "null argument");
+  RCCHK(candidates_rank_check(d_scores, d_tgt_len, d_cand_src, N, T, B, mode, d_totals, d_best));
+  HIPCHK(hipSetDevice(ctx->model->device));
+  RCCHK(score_reserve(ctx, ctx->cand_rank, B * 8));
+  CandRankArgs a;
+  a.scores = d_scores;
+  a.tgt_len = d_tgt_len;
+  a.cand_src = d_cand_src;
+  a.N = N;
+  a.T = (uint32_t)T;
+  a.B = (uint32_t)B;
+  a.mode = mode;
+  a.totals = d_totals;
+  a.best = d_best;
+  a.entries = ctx->cand_rank.as<unsigned long long>();
+  HIPCHK(launch_candidates_rank(a, ctx->stream));
+  return 0;
 }

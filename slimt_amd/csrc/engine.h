@@ -234,6 +234,9 @@ struct slimt_hip_ctx {
   // teacher-forced scoring (include/slimt_hip.h, slimt_hip_score*): allocated on the first scoring call, grown when a later
   // one needs more. score_ws: one chunk's rows (engine.cpp, score_device); score_io: staging of a host call's targets and scores
   slimt_hip::DevBuf score_ws, score_io;
+  // candidate calls (slimt_hip_score_candidates*): the staging of a pageable alignment [N][T][S] (sized by N, so not
+  // ctx->align, which a context sizes for max_batch), and the ranking's per-source maxima (slimt_hip_candidates_rank_device)
+  slimt_hip::DevBuf cand_align, cand_rank;
   // alternatives (include/slimt_hip.h, slimt_hip_ctx_set_score_alternatives): armed for the NEXT score call, which takes them
   // whatever its outcome (engine.cpp, AltCall). alt_stage: device staging of pageable destinations, allocated by the first
   // armed call that needs it

@@ -687,6 +687,35 @@ size_t score_alternatives_lds_bytes(int K);
 hipError_t launch_score_alternatives(const ScoreOutArgs &a, const ScoreAltArgs &alt, hipStream_t st);
 bool score_supported(int D, int H);  // D in {64, 128, 256, 512}, d_head in {16, 32, 64}
 
+// ---- candidate scoring: N target rows over B encoded sources (score_candidates.hip; slimt_hip_score_candidates*) ----------
+// The tall pass above with rows.b0 / nb / tgt_ids / tgt_len counting CANDIDATES; only the attention knows the sources.
+// A workgroup walks a run of kScoreCandidateRun consecutive candidates of the chunk for one head and restages K / V only
+// when the next live candidate names another source. 2: at the measured shape (32 sources x 8 candidates of 48 rows, 8
+// heads of 32) the chunk offers 1024 workgroups = 4096 waves, what 256 compute units hold at once at this kernel's four
+// waves per SIMD, so a wave walks 24 rows -- as it does when score_attn_kernel's 2048 workgroups of 12 rows a wave pass in
+// two rounds. Measured: 4 left half the machine idle (48 rows a wave) and cost a single stream 14 % of the call; sorted
+// candidates are staged once per two.
+constexpr int kScoreCandidateRun = 2;  // == SLIMT_HIP_CANDIDATE_RUN (include/slimt_hip.h; engine.cpp asserts it)
+struct ScoreCandAttnArgs {
+  ScoreAttnArgs a;  // rows, q, out_i8, align: by candidate; k, v, lengths: by source
+  const uint32_t *cand_src = nullptr;  // [N]: candidate c's source; a value >= B is taken as B - 1
+  int B = 0;                           // sources
+};
+hipError_t launch_score_candidates_attention(const ScoreCandAttnArgs &a, hipStream_t st);
+// totals [N] / best [B] as include/slimt_hip.h defines them (slimt_hip_candidates_rank); entries [B]: scratch
+struct CandRankArgs {
+  const float *scores = nullptr;       // [N][T]
+  const uint32_t *tgt_len = nullptr;   // [N], clamped to T
+  const uint32_t *cand_src = nullptr;  // [N], clamped to B - 1
+  size_t N = 0;
+  uint32_t T = 0, B = 0;
+  int mode = 0;  // 0: sum, 1: mean per token
+  float *totals = nullptr;
+  uint32_t *best = nullptr;
+  unsigned long long *entries = nullptr;
+};
+hipError_t launch_candidates_rank(const CandRankArgs &a, hipStream_t st);
+
 // ---- truncated sampling: top-k / nucleus selection over stored logits (sample_truncate.hip) -------------------------------
 // One sampled step of B rows whose output-layer logits [B][N] are in memory (the logits gemm with EPI_PLAIN): the kept set
 // of include/slimt_hip.h (slimt_hip_ctx_set_sampling_truncation; truncation.h) and, over it, one partial per row in

@@ -454,6 +454,40 @@ class Service:
         res.close()
         return out
 
+    def rerank(self, model: Model, sources: Sequence[str], candidates: Sequence[Sequence[str]],
+               mean: bool = False) -> List[Tuple[List["PairScore"], Optional[int]]]:
+        """Ranks candidates[i], the candidate translations of sources[i], from ONE encoding of each source
+        (include/slimt_hip_service_candidates.h); texts are tokenised as score() tokenises them. Returns per source the
+        candidates' PairScores in the given order and the index of the best one -- the largest summed log-probability, with
+        mean=True the largest sum per token; the first of equals -- or None for a source without candidates."""
+        if len(sources) != len(candidates):
+            raise ValueError(f"rerank: {len(candidates)} candidate lists for {len(sources)} sources")
+        v = model.vocabulary
+        eos = v.eos_id()
+        src = [ids + [eos] for ids in v.encode_ids_batch(list(sources), self.workers)] if sources else []
+        for i, ids in enumerate(src):
+            if len(ids) > self.ENGINE_LIMIT:
+                raise ValueError(f"rerank: source {i} has {len(ids)} tokens, more than {self.ENGINE_LIMIT}")
+        if not src:
+            return []
+        flat = [t for cs in candidates for t in cs]
+        enc = [ids + [eos] for ids in v.encode_ids_batch(flat, self.workers)] if flat else []
+        at, tgt = 0, []
+        for cs in candidates:
+            tgt.append(enc[at:at + len(cs)])
+            at += len(cs)
+        res, c_off, _, best = self._engine(model).score_candidates(src, tgt, mean=mean)
+        out = []
+        for i in range(len(src)):
+            pairs = []
+            for j, e in enumerate(range(int(c_off[i]), int(c_off[i + 1]))):
+                sc = res.token_scores(e).copy()
+                pairs.append(PairScore(source_ids=src[i], target_ids=tgt[i][j], token_scores=sc,
+                                       score=float(np.sum(sc, dtype=np.float64)), alignment=res.alignment(e).copy()))
+            out.append((pairs, None if best[i] == 0xFFFFFFFF else int(best[i])))
+        res.close()
+        return out
+
     def pivot(self, first: Model, second: Model, texts: Sequence[str], html: bool = False,
               scores: bool = False, sampling=None, truncation=None) -> List[Response]:
         """sampling: (temperature, seed) -- both hops sample, the first under seed and the second under seed + 1;

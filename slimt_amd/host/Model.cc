@@ -232,6 +232,24 @@ void Worker::score(slimt_hip_shortlist *generator, const uint32_t *ids, const ui
   }
 }
 
+#pragma weak slimt_hip_score_candidates
+#pragma weak slimt_hip_score_candidates_async_generated
+void Worker::score_candidates(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
+                              const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids, const uint32_t *tgt_len,
+                              size_t T, const uint32_t *cand_src, size_t N, float *scores, float *align) {
+  if (!slimt_hip_score_candidates || !slimt_hip_score_candidates_async_generated)
+    throw std::runtime_error("this engine has no candidate scoring");
+  if (generator) {
+    if (slimt_hip_score_candidates_async_generated(ctx_, generator, ids, lengths, B, S, tgt_ids, tgt_len, T, cand_src, N, scores,
+                                                   align))
+      raise("slimt_hip_score_candidates_async_generated");
+    wait();
+  } else if (slimt_hip_score_candidates(ctx_, ids, lengths, B, S, shortlist, n_shortlist, tgt_ids, tgt_len, T, cand_src, N, scores,
+                                        align)) {
+    raise("slimt_hip_score_candidates");
+  }
+}
+
 #pragma weak slimt_hip_ctx_set_sampling_truncation
 void Worker::arm_sampling_truncation(uint32_t top_k, float top_p) {
   if (!slimt_hip_ctx_set_sampling_truncation) throw std::runtime_error("this engine has no sampling truncation");

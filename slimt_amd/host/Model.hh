@@ -198,6 +198,11 @@ class Worker {
   void score(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
              const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids, const uint32_t *tgt_len, size_t T,
              float *scores, float *align, const ScoreAlternatives *alternatives = nullptr);
+  // The same for N candidate targets over the B sources, encoded once (include/slimt_hip.h, slimt_hip_score_candidates):
+  // tgt_ids [N][T], tgt_len [N], cand_src [N] (< B: candidate c's source), scores [N][T], align nullable [N][T][S]. Blocking.
+  void score_candidates(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
+                        const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids, const uint32_t *tgt_len,
+                        size_t T, const uint32_t *cand_src, size_t N, float *scores, float *align);
   void wait();
 
  private:

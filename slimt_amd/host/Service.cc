@@ -331,6 +331,111 @@ Histories Service::score(std::vector<Words> sentences, std::vector<Words> target
   return results;
 }
 
+Service::CandidateScores Service::score_candidates(std::vector<Words> sentences, std::vector<std::vector<Words>> candidates,
+                                                   int mode) {
+  constexpr size_t kLongestTarget = 65536;  // include/slimt_hip.h, slimt_hip_score
+  if (mode != 0 && mode != 1) throw std::invalid_argument("mode " + std::to_string(mode) + ": neither 0 (sum) nor 1 (mean per token)");
+  if (candidates.size() != sentences.size())
+    throw std::invalid_argument(std::to_string(candidates.size()) + " candidate lists for " + std::to_string(sentences.size()) +
+                                " sentences");
+  const size_t n = sentences.size();
+  std::vector<size_t> first(n + 1, 0);  // sentence i's candidates in the result
+  for (size_t i = 0; i < n; ++i) {
+    const Words &s = sentences[i];
+    if (s.empty()) throw std::invalid_argument("empty sentence (a sentence holds at least its EOS)");
+    if (s.size() > longest_)
+      throw std::invalid_argument("sentence of " + std::to_string(s.size()) + " tokens: longer than " +
+                                  std::to_string(longest_) + " (wrap it first)");
+    for (const Words &t : candidates[i])
+      if (t.size() > kLongestTarget)
+        throw std::invalid_argument("candidate of sentence " + std::to_string(i) + ": " + std::to_string(t.size()) +
+                                    " tokens, more than " + std::to_string(kLongestTarget));
+    first[i + 1] = first[i] + candidates[i].size();
+  }
+  CandidateScores out;
+  out.candidates.resize(first[n]);
+  out.totals.assign(first[n], 0.0f);
+  out.best.assign(n, 0xFFFFFFFFu);
+  if (n == 0) return out;
+  if (n >= (1u << 24)) throw std::invalid_argument("request of more than 2^24 sentences");
+  LengthQueue queue(config_.max_words, longest_);  // the batch-forming rule of translate()
+  for (size_t i = 0; i < n; ++i) {
+    Unit u;
+    u.order = i;
+    u.index = static_cast<uint32_t>(i);
+    u.length = static_cast<uint32_t>(sentences[i].size());
+    queue.push(std::move(u));
+  }
+  std::lock_guard<std::mutex> lock(score_mu_);
+  if (!score_worker_) score_worker_ = std::make_unique<Worker>(*score_model_, config_.max_words, longest_, config_.max_words);
+  std::vector<uint32_t> ids, lengths, tgt, tlen, src, clen;
+  std::vector<float> sc, al;
+  for (;;) {
+    const std::vector<Unit> batch = queue.take();
+    if (batch.empty()) break;
+    const size_t B = batch.size();
+    size_t S = 1, T = 1, N = 0;
+    for (const Unit &u : batch) {
+      S = std::max<size_t>(S, u.length);
+      N += candidates[u.index].size();
+      for (const Words &t : candidates[u.index]) T = std::max(T, t.size());
+    }
+    if (N == 0) continue;  // (sentences without candidates: nothing to encode for)
+    ids.assign(B * S, config_.pad_id);
+    lengths.resize(B);
+    tgt.assign(N * T, 0);
+    tlen.resize(N);
+    src.resize(N);
+    clen.resize(N);
+    sc.assign(N * T, 0.0f);
+    if (config_.alignments) al.assign(N * T * S, 0.0f);
+    size_t c = 0;
+    for (size_t b = 0; b < B; ++b) {
+      const Words &s = sentences[batch[b].index];
+      std::copy(s.begin(), s.end(), ids.begin() + static_cast<std::ptrdiff_t>(b * S));
+      lengths[b] = static_cast<uint32_t>(s.size());
+      for (const Words &t : candidates[batch[b].index]) {  // sorted by source
+        std::copy(t.begin(), t.end(), tgt.begin() + static_cast<std::ptrdiff_t>(c * T));
+        tlen[c] = static_cast<uint32_t>(t.size());
+        src[c] = static_cast<uint32_t>(b);
+        clen[c] = lengths[b];
+        ++c;
+      }
+    }
+    const bool fixed = config_.shortlist && !score_generator_;
+    score_worker_->score_candidates(score_generator_, ids.data(), lengths.data(), B, S, fixed ? config_.shortlist->data() : nullptr,
+                                    fixed ? config_.shortlist->size() : 0, tgt.data(), tlen.data(), T, src.data(), N, sc.data(),
+                                    config_.alignments ? al.data() : nullptr);
+    const uint64_t serial = batches_.fetch_add(1);
+    Histories hs = collect(tgt.data(), tlen.data(), config_.alignments ? al.data() : nullptr, clen.data(), N, S, T,
+                           config_.flat_alignments);
+    c = 0;
+    for (size_t b = 0; b < B; ++b) {
+      const size_t i = batch[b].index;
+      float top = 0.0f;
+      for (size_t j = 0; j < candidates[i].size(); ++j, ++c) {
+        const float *row = sc.data() + c * T;
+        float total = 0.0f;  // ascending t from +0, one f32 add per term
+        for (size_t t = 0; t < tlen[c]; ++t) total = total + row[t];
+        hs[c]->scores.assign(row, row + tlen[c]);
+        hs[c]->batch = serial;
+        out.totals[first[i] + j] = total;
+        out.candidates[first[i] + j] = std::move(hs[c]);
+        if (tlen[c] == 0) continue;
+        const float key = mode == 1 ? total / static_cast<float>(tlen[c]) : total;
+        if (key != key) continue;
+        if (out.best[i] == 0xFFFFFFFFu || key > top) {
+          top = key;
+          out.best[i] = static_cast<uint32_t>(j);
+        }
+      }
+    }
+  }
+  for (size_t c = 0; c < out.candidates.size(); ++c)  // (cannot happen: every candidate travels with its sentence)
+    if (!out.candidates[c]) throw std::runtime_error("candidate " + std::to_string(c) + " was not scored");
+  return out;
+}
+
 bool Service::set_scores(bool on) {
   std::lock_guard<std::mutex> lock(mutex_);  // (the workers read config_.scores only for batches queued after this)
   if (sequence_ > 0) return false;
@@ -634,6 +739,9 @@ void Service::work(const Model *model, slimt_hip_shortlist *generator) {
   };
   try {
     if (config_.fail_worker_setup) config_.fail_worker_setup(model);  // tests: a worker that cannot be built
+    // one worker at a time: when memory runs out, the workers built so far are whole, instead of every worker holding
+    // one context and failing on its second, which would leave a service with none
+    std::lock_guard<std::mutex> setup(setup_mu_);
     for (Slot &s : slots) {
       // (B + 1) * S <= max_words: at most max_words - 1 rows, at most max_words padded tokens; a merged launch: up to
       // merge_words of its 32-aligned rows x length (next_batch)

@@ -170,6 +170,20 @@ class Service {
   // their log-probabilities and the token's rank among the layer's columns (Hypothesis::alt_ids / alt_scores / ranks;
   // include/slimt_hip.h, slimt_hip_ctx_set_score_alternatives). More than 8 is refused.
   Histories score(std::vector<Words> sentences, std::vector<Words> targets, size_t alternatives = 0);
+  // Several candidate translations per sentence, scored from ONE encoding of each sentence (include/slimt_hip.h,
+  // slimt_hip_score_candidates): candidates[i] are sentence i's (any number, 0 included; each of any length). Batches are
+  // formed by the source-length rule of translate(); all candidates of a sentence travel in its batch, sorted by source,
+  // and a batch's T is its longest candidate. The output layer, the context and the mutex are those of score(). Returns one
+  // Hypothesis per candidate in the order given (sentence 0's first), as score() fills them; totals: per candidate the f32
+  // sum of its scores in ascending order from +0; best: per SENTENCE the index among its own candidates of the lowest
+  // one whose key -- the total (mode 0) or the total / tokens (mode 1) -- is >= every other's, candidates without tokens
+  // or with a NaN key aside; 0xFFFFFFFF when none is left (slimt_hip_candidates_rank's rule). Another mode is refused.
+  struct CandidateScores {
+    Histories candidates;
+    std::vector<float> totals;
+    std::vector<uint32_t> best;
+  };
+  CandidateScores score_candidates(std::vector<Words> sentences, std::vector<std::vector<Words>> candidates, int mode = 0);
   // per-token scores on or off (ServiceConfig::scores): only before the first translate(); false once one has been made
   bool set_scores(bool on);
   // temperature sampling for every request (include/slimt_hip.h, slimt_hip_ctx_set_sampling; 0: greedy again): only before
@@ -209,6 +223,7 @@ class Service {
   size_t live_workers_ = 0;          // workers that can take batches
   std::exception_ptr dead_error_;    // set once the last of them has failed: requests fail with it
   std::mutex mutex_;
+  std::mutex setup_mu_;              // one worker at a time builds its two contexts (work())
   std::condition_variable wake_;
   std::vector<std::thread> threads_;
   // score(): the first replica, its generator (nullable), and the context the calls share (built by the first one)

@@ -12,6 +12,7 @@
 #include "Service.hh"
 #include "slimt_hip_service.h"
 #include "slimt_hip_service_prefix.h"
+#include "slimt_hip_service_candidates.h"
 #include "slimt_hip_service_score.h"
 #include "slimt_hip_service_sampling.h"
 #include "slimt_hip_service_scores.h"
@@ -45,6 +46,10 @@ struct slimt_hip_result {
   uint32_t alternatives = 0;
   std::vector<uint32_t> alt_ids, ranks;
   std::vector<float> alt_scores;
+  // slimt_hip_service_score_candidates: one total per entry (candidate), one best index per source sentence
+  bool ranked = false;
+  std::vector<float> totals;
+  std::vector<uint32_t> best;
 };
 
 extern "C" const char *slimt_hip_service_last_error(void) { return g_err; }
@@ -224,6 +229,47 @@ extern "C" int slimt_hip_service_score_alternatives(slimt_hip_service *service, 
   if (k < 1 || k > SLIMT_HIP_MAX_ALTERNATIVES)
     return fail("score_alternatives: k %u is not in 1..%d", k, SLIMT_HIP_MAX_ALTERNATIVES);
   return score(service, tokens, offsets, tgt_tokens, tgt_offsets, n, k, out);
+}
+
+extern "C" int slimt_hip_service_score_candidates(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets, size_t n,
+                                                  const uint32_t *tgt_tokens, const uint64_t *tgt_offsets,
+                                                  const uint64_t *cand_offsets, int mode, slimt_hip_result **out) {
+  if (!service || !out || (n && (!tokens || !offsets || !cand_offsets))) return fail("null argument");
+  const size_t N = n ? cand_offsets[n] : 0;
+  if (n && cand_offsets[0] != 0) return fail("candidate offsets start at %llu, not 0", (unsigned long long)cand_offsets[0]);
+  if (N && (!tgt_offsets || (tgt_offsets[N] > tgt_offsets[0] && !tgt_tokens))) return fail("null argument");
+  *out = nullptr;
+  try {
+    std::vector<slimt::Words> sentences(n);
+    std::vector<std::vector<slimt::Words>> candidates(n);
+    for (size_t i = 0; i < n; ++i) {
+      if (offsets[i + 1] < offsets[i]) return fail("offsets decrease at sentence %zu", i);
+      if (cand_offsets[i + 1] < cand_offsets[i]) return fail("candidate offsets decrease at sentence %zu", i);
+      sentences[i].assign(tokens + offsets[i], tokens + offsets[i + 1]);
+      for (uint64_t c = cand_offsets[i]; c < cand_offsets[i + 1]; ++c) {
+        if (tgt_offsets[c + 1] < tgt_offsets[c]) return fail("target offsets decrease at candidate %llu", (unsigned long long)c);
+        candidates[i].emplace_back(tgt_tokens + tgt_offsets[c], tgt_tokens + tgt_offsets[c + 1]);
+      }
+    }
+    slimt::Service::CandidateScores cs = service->service->score_candidates(std::move(sentences), std::move(candidates), mode);
+    std::unique_ptr<slimt_hip_result> r;
+    if (const int rc = flatten(cs.candidates, cs.candidates.size(), true, r)) return rc;
+    r->ranked = true;
+    r->totals = std::move(cs.totals);
+    r->best = std::move(cs.best);
+    *out = r.release();
+    return 0;
+  } catch (const std::exception &e) {
+    return fail("%s", e.what());
+  }
+}
+
+extern "C" int slimt_hip_result_candidates(const slimt_hip_result *r, const float **totals, const uint32_t **best) {
+  if (!r) return fail("null argument");
+  if (!r->ranked) return fail("result_candidates: not a result of slimt_hip_service_score_candidates");
+  if (totals) *totals = r->totals.data();
+  if (best) *best = r->best.data();
+  return 0;
 }
 
 extern "C" int slimt_hip_result_alternatives(const slimt_hip_result *r, size_t i, uint32_t *k, const uint32_t **ids,
