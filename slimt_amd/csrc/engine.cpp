@@ -57,6 +57,15 @@ static std::atomic<bool> g_hip_called{false};
 // asks here; the encoder is chosen as the context's mode says.
 static bool fused_decoder_allowed(const slimt_hip_ctx *c) { return c->decode_mode != 1 && c->model->kv_format != 3 && !c->tr_call; }
 
+// The lean path for sources padded to S tokens: the persistent decoder, allowed and compiled for the model, behind a
+// persistent encoder (the fused one, or the per-sentence one of 65..128 tokens).
+static bool persistent_path(const slimt_hip_ctx *c, size_t S) {
+  const slimt_hip_model *m = c->model;
+  return fused_decoder_allowed(c) && fused_decode_supported(m->D, m->F, m->H, m->Ld) &&
+         (fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S) ||
+          long_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S));
+}
+
 // The narrow K/V form for this model's next batch (engine.h, kv_auto_wide): format 0, and the sentences so far mostly fit.
 // Called under the model's submit / gate discipline by encode_device; the counter lags the device by a few batches.
 static bool kv_narrow_wanted(slimt_hip_model *m, unsigned long long **count_dev) {
@@ -1752,6 +1761,29 @@ struct TruncationCall {
   }
 };
 
+// What a translate entry point opens with: the four guards, constructed in this order (TruncationCall reads sm_call, which
+// SampleCall sets) and all of them whatever the earlier ones found -- what was armed is consumed whether or not the call
+// succeeds. n: the batches of the call. rc(): the first guard's that refused.
+struct CallOptions {
+  ScoreCall sc;
+  PrefixCall pc;
+  SampleCall smc;
+  TruncationCall trc;
+  CallOptions(slimt_hip_ctx *ctx, size_t n) : sc(ctx, n), pc(ctx, n), smc(ctx, n), trc(ctx) {}
+  int rc() const { return sc.rc ? sc.rc : pc.rc ? pc.rc : smc.rc ? smc.rc : trc.rc; }
+};
+
+// Batch j of a call that goes batch by batch through a single-batch path: its own destination, prefix and keys where that
+// path looks for the caller's (the *_user fields).
+void arm_batch(slimt_hip_ctx *ctx, float *const *scores, const PrefixCall &pc, const SampleCall &smc, size_t j) {
+  if (ctx->sc_call) ctx->sc_user = scores[j];
+  if (ctx->fp_call) {
+    ctx->fp_user_ids = pc.ids[j];
+    ctx->fp_user_len = pc.len[j];
+  }
+  if (ctx->sm_call) ctx->sm_user_keys = smc.keys[j];
+}
+
 void *host_device_view(const void *p);  // (below)
 
 // Host keys -> addresses the kernels read, like prefix_stage: pinned arrays in place, a pageable batch's keys staged in
@@ -2273,9 +2305,7 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   // Model.cc:144-161: the first step is unconditional (one token is always recorded), the
   // loop then runs while i < (size_t)(limit_factor * S): at least one output column
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
-  const bool fused_dec = fused_decoder_allowed(c) && fused_decode_supported(m->D, m->F, m->H, m->Ld);
-  const bool lean = fused_dec && (fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S) ||
-                                  long_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S));
+  const bool lean = persistent_path(c, S);
   // packed 24-bit K/V cache: fused encoder -> fused decoder, D = 256 / d_head 32 or D = 512 / d_head 64, S <= 32
   // (V is cached in groups of four keys: S = 1, 2, 5 would not fit the f32 form's plane)
   // ... and for 33..64-token sentences of the D = 256 / F = 1536 shape (64-row encoder, one sentence per workgroup)
@@ -2823,9 +2853,18 @@ void *host_device_view(const void *p) {
   return a.type == hipMemoryTypeHost ? a.devicePointer : nullptr;
 }
 
-void shortlist_args(const slimt_hip_shortlist *sl, const uint32_t *d_ids, const uint32_t *d_len,
-                    size_t B, size_t S, uint32_t *d_out, uint32_t *d_n, ShortlistArgs &a);
-int shortlist_scratch(DevBuf &buf, const slimt_hip_shortlist *sl, hipStream_t st);
+// (below, with the lexical shortlist)
+int upload_shortlist_if_changed(slimt_hip_ctx *ctx, const uint32_t *ids, size_t n);
+int generated_shortlist_args(slimt_hip_ctx *ctx, const slimt_hip_shortlist *sl, const uint32_t *d_ids, const uint32_t *d_len,
+                             size_t B, size_t S, ShortlistArgs &a, size_t n_lists = 1);
+
+int check_generator(const slimt_hip_ctx *ctx, const slimt_hip_shortlist *sl) {
+  const slimt_hip_model *m = ctx->model;
+  if (sl->device != m->device) return fail(-1, "shortlist and context are on different devices");
+  if (sl->target_vocab != (size_t)m->V)
+    return fail(-1, "shortlist target vocabulary %zu != model vocabulary %d", sl->target_vocab, m->V);
+  return 0;
+}
 
 // Model::forward's order (Model.cc:117-120): the batch's shortlist first -- generated on ctx's
 // stream into ctx->shortlist -- then translate_device with it. Arrays the device can read.
@@ -2835,13 +2874,8 @@ int translate_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const uint3
                         float *align_out) {
   const slimt_hip_model *m = ctx->model;
   hipStream_t st = ctx->stream;
-  ctx->sl_host.clear();  // ctx->shortlist no longer holds what translate_host uploaded last
-  HIPCHK(ctx->n_sl_dev.reserve(4));
-  RCCHK(shortlist_scratch(ctx->sl_scratch, sl, st));
   ShortlistArgs a;
-  shortlist_args(sl, d_src_ids, d_lengths, B, S, ctx->shortlist.as<uint32_t>(),
-                 ctx->n_sl_dev.as<uint32_t>(), a);
-  a.scratch = ctx->sl_scratch.as<uint32_t>();
+  RCCHK(generated_shortlist_args(ctx, sl, d_src_ids, d_lengths, B, S, a));
   // the count also goes to a pinned word: what this context's PREVIOUS shortlist held is the host's
   // estimate of this one's size (a batch's shortlist is sized on the device; the host only picks
   // the decoder variant by it)
@@ -2849,9 +2883,7 @@ int translate_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const uint3
   const size_t n_hint = *hint;
   void *hint_dev = nullptr;
   if (hipHostGetDevicePointer(&hint_dev, hint, 0) == hipSuccess) a.n_out_host = static_cast<uint32_t *>(hint_dev);
-  const bool lean = fused_decoder_allowed(ctx) && fused_decode_supported(m->D, m->F, m->H, m->Ld) &&
-                    (fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S) ||
-                     long_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S));
+  const bool lean = persistent_path(ctx, S);
   // With the 64-row encoder the generator runs INSIDE the encoder launch, by the workgroup that starts first
   // (encode_tall.hip): as a launch of its own -- one workgroup -- it waited ~0.5 ms for a CU behind the
   // other batches' persistent kernels (47 us alone). Same ids, same count, same consumers.
@@ -2879,14 +2911,8 @@ extern "C" int slimt_hip_translate_device(slimt_hip_ctx *ctx, const uint32_t *d_
                                           float limit_factor, uint32_t eos_id,
                                           uint32_t *d_out_ids, uint32_t *d_out_len,
                                           float *d_align, int steps_hint) {
-  ScoreCall sc(ctx, 1);
-  PrefixCall pc(ctx, 1);
-  SampleCall smc(ctx, 1);
-  TruncationCall trc(ctx);
-  if (sc.rc) return sc.rc;
-  if (pc.rc) return pc.rc;
-  if (smc.rc) return smc.rc;
-  if (trc.rc) return trc.rc;
+  CallOptions opt(ctx, 1);
+  RCCHK(opt.rc());
   if (!ctx || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len) return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
   if (n_shortlist > (size_t)ctx->model->V) return fail(-1, "shortlist larger than the vocabulary");
@@ -2904,18 +2930,26 @@ extern "C" int slimt_hip_translate_device(slimt_hip_ctx *ctx, const uint32_t *d_
 
 namespace {
 // Model::forward on host buffers: validate, queue H2D + kernels + D2H on the ctx stream.
-int translate_host(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
+// gen (nullable): the batch's lexical shortlist is generated on the device (Model.cc:117-120; shortlist / n_shortlist are
+// then not used): no host shortlist, no upload, no synchronisation in the asynchronous form.
+int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
                    size_t S, const uint32_t *shortlist, size_t n_shortlist, float limit_factor,
                    uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align, bool wait) {
   if (!ctx || !src_ids || !lengths || !out_ids || !out_len) return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
   StageClock hclk;
   const slimt_hip_model *m = ctx->model;
-  if (n_shortlist > (size_t)m->V) return fail(-1, "shortlist larger than the vocabulary");
-  if (n_shortlist && !shortlist) return fail(-1, "shortlist is NULL");
+  uint32_t vmax = (uint32_t)m->V;
+  if (gen) {
+    RCCHK(check_generator(ctx, gen));
+    vmax = (uint32_t)std::min((size_t)m->V, gen->source_vocab);
+  } else {
+    if (n_shortlist > (size_t)m->V) return fail(-1, "shortlist larger than the vocabulary");
+    if (n_shortlist && !shortlist) return fail(-1, "shortlist is NULL");
+  }
   for (size_t i = 0; i < B * S; ++i)
-    if (src_ids[i] >= (uint32_t)m->V) return fail(-1, "token id %u out of range", src_ids[i]);
-  for (size_t i = 0; i < n_shortlist; ++i)
+    if (src_ids[i] >= vmax) return fail(-1, "token id %u out of range", src_ids[i]);
+  for (size_t i = 0; !gen && i < n_shortlist; ++i)
     if (shortlist[i] >= (uint32_t)m->V) return fail(-1, "shortlist id %u out of range", shortlist[i]);
   for (size_t i = 0; i < B; ++i)
     if (lengths[i] > S) return fail(-1, "length %u > S", lengths[i]);
@@ -2923,21 +2957,24 @@ int translate_host(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *
   hipStream_t st = ctx->stream;
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
   // the shortlist is read at random every step: it stays on the device, uploaded when it changes
-  if (n_shortlist && (ctx->sl_host.size() != n_shortlist ||
-                      std::memcmp(ctx->sl_host.data(), shortlist, n_shortlist * 4) != 0)) {
-    ctx->sl_host.clear();  // until the upload has succeeded the device copy is nobody's
-    HIPCHK(hipMemcpyAsync(ctx->shortlist.p, shortlist, n_shortlist * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));  // (the caller's array may be pageable: the copy is staged; done once per shortlist)
-    ctx->sl_host.assign(shortlist, shortlist + n_shortlist);
-  }
+  if (!gen) RCCHK(upload_shortlist_if_changed(ctx, shortlist, n_shortlist));
+  // the kernels for either shortlist, on arrays the device can read; the alignment rows go to ctx->align and, where
+  // align_out is given, from there to the caller's pinned array
+  auto run = [&](const uint32_t *d_ids, const uint32_t *d_len, uint32_t *d_out, uint32_t *d_ol, int steps_hint,
+                 float *align_out) {
+    float *d_align = align ? ctx->align.as<float>() : nullptr;
+    if (gen)
+      return translate_generated(ctx, gen, d_ids, d_len, B, S, limit_factor, eos_id, d_out, d_ol, d_align, steps_hint,
+                                 align_out);
+    return translate_device(ctx, d_ids, d_len, ctx->shortlist.as<uint32_t>(), B, S, n_shortlist, limit_factor, eos_id, d_out,
+                            d_ol, d_align, steps_hint, nullptr, align_out);
+  };
   // Asynchronous callers with PINNED buffers (hipHostMalloc / slimt_hip_host_alloc): the persistent
   // kernels read the ids / lengths and write tokens, lengths and alignments in host memory themselves
   // -- no copy on either side. Copies are what a host pipeline stalls on: an asynchronous copy
   // of stream A sits in a DMA queue behind copies that wait for stream B's kernels (measured with the
   // Service: 12 contexts of equal batches ran strictly one after the other, 3.7 M tok/s).
-  const bool persistent = fused_decoder_allowed(ctx) && fused_decode_supported(m->D, m->F, m->H, m->Ld) &&
-                          (fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S) ||
-                           long_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S));
+  const bool persistent = persistent_path(ctx, S);
   hclk.lap(0);
   if (ctx->fp_call) {  // (a forced call: the caller's host prefix, checked and staged in device memory)
     const size_t Bs[1] = {B}, Ts[1] = {Tmax};
@@ -2959,12 +2996,8 @@ int translate_host(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *
       // sentence, as whole 16-byte stores when its loop ends: written row by row across PCIe from
       // inside the step loop they cost the Service 28 % (12.9 against 17.9 M tok/s)
       if (align) HIPCHK(ctx->align.reserve(align_staging_bytes(ctx, B, S, Tmax, limit_factor)));
-      RCCHK(translate_device(ctx, static_cast<const uint32_t *>(v_ids), static_cast<const uint32_t *>(v_len),
-                             ctx->shortlist.as<uint32_t>(), B, S, n_shortlist, limit_factor, eos_id,
-                             static_cast<uint32_t *>(v_out), static_cast<uint32_t *>(v_ol),
-                             align ? ctx->align.as<float>() : nullptr, (int)Tmax, nullptr,
-                             static_cast<float *>(v_al)));
-      return 0;
+      return run(static_cast<const uint32_t *>(v_ids), static_cast<const uint32_t *>(v_len), static_cast<uint32_t *>(v_out),
+                 static_cast<uint32_t *>(v_ol), (int)Tmax, static_cast<float *>(v_al));
     }
   }
   HIPCHK(ctx->out_ids.reserve(B * Tmax * 4));
@@ -2977,10 +3010,8 @@ int translate_host(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *
   HIPCHK(hipMemcpyAsync(ctx->lengths.p, lengths, B * 4, hipMemcpyHostToDevice, st));
   // asynchronous callers never read back inside the loop: a fixed step budget (the persistent
   // decoder still leaves its loop as soon as every sentence has emitted EOS)
-  RCCHK(translate_device(ctx, ctx->ids.as<uint32_t>(), ctx->lengths.as<uint32_t>(),
-                         ctx->shortlist.as<uint32_t>(), B, S, n_shortlist, limit_factor, eos_id,
-                         ctx->out_ids.as<uint32_t>(), ctx->out_len.as<uint32_t>(),
-                         align ? ctx->align.as<float>() : nullptr, wait ? 0 : (int)Tmax));
+  RCCHK(run(ctx->ids.as<uint32_t>(), ctx->lengths.as<uint32_t>(), ctx->out_ids.as<uint32_t>(), ctx->out_len.as<uint32_t>(),
+            wait ? 0 : (int)Tmax, nullptr));
   HIPCHK(hipMemcpyAsync(out_ids, ctx->out_ids.p, B * Tmax * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(out_len, ctx->out_len.p, B * 4, hipMemcpyDeviceToHost, st));
   if (align) HIPCHK(hipMemcpyAsync(align, ctx->align.p, B * Tmax * S * 4, hipMemcpyDeviceToHost, st));
@@ -2995,15 +3026,9 @@ extern "C" int slimt_hip_translate(slimt_hip_ctx *ctx, const uint32_t *src_ids,
                                    const uint32_t *shortlist, size_t n_shortlist,
                                    float limit_factor, uint32_t eos_id, uint32_t *out_ids,
                                    uint32_t *out_len, float *align) {
-  ScoreCall sc(ctx, 1);
-  PrefixCall pc(ctx, 1);
-  SampleCall smc(ctx, 1);
-  TruncationCall trc(ctx);
-  if (sc.rc) return sc.rc;
-  if (pc.rc) return pc.rc;
-  if (smc.rc) return smc.rc;
-  if (trc.rc) return trc.rc;
-  return translate_host(ctx, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
+  CallOptions opt(ctx, 1);
+  RCCHK(opt.rc());
+  return translate_host(ctx, nullptr, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, true);
 }
 
@@ -3012,15 +3037,9 @@ extern "C" int slimt_hip_translate_async(slimt_hip_ctx *ctx, const uint32_t *src
                                          const uint32_t *shortlist, size_t n_shortlist,
                                          float limit_factor, uint32_t eos_id, uint32_t *out_ids,
                                          uint32_t *out_len, float *align) {
-  ScoreCall sc(ctx, 1);
-  PrefixCall pc(ctx, 1);
-  SampleCall smc(ctx, 1);
-  TruncationCall trc(ctx);
-  if (sc.rc) return sc.rc;
-  if (pc.rc) return pc.rc;
-  if (smc.rc) return smc.rc;
-  if (trc.rc) return trc.rc;
-  return translate_host(ctx, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
+  CallOptions opt(ctx, 1);
+  RCCHK(opt.rc());
+  return translate_host(ctx, nullptr, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, false);
 }
 
@@ -3106,10 +3125,31 @@ int build_merge_plan(const slimt_hip_ctx *c, const slimt_hip_batch *b, size_t n,
 // the decoder tile of a merged launch: always 16 sentences -- where an unmerged call would take the 32-sentence tiling (decode
 // mode 3, or mode 0 with an output layer of more than 16k columns) a merged one runs the 16-sentence tiling instead
 // (translate_device; decode_fused.hip compiles the merged paths into the 16-row tilings only)
-size_t merge_tile(const slimt_hip_ctx *c, size_t n_columns) {
-  (void)c;
-  (void)n_columns;
-  return 16;  // (merged launches never take the 32-sentence tiling: translate_device)
+constexpr size_t kMergeTile = 16;
+
+// Batch j of a host _many_ call as its front checks it: the arrays, B, and the batch's padded length against the launch's;
+// with `values` every id (< vmax) and every length as well.
+int check_host_batch(const slimt_hip_batch &b, size_t j, size_t S, uint32_t vmax, bool values) {
+  if (!b.src_ids || !b.lengths || !b.out_ids || !b.out_len || b.B == 0) return fail(-1, "batch %zu: null array or empty", j);
+  const size_t Sj = b.S ? b.S : S;
+  if (Sj > S) return fail(-1, "batch %zu is padded to %zu tokens, the launch to %zu", j, Sj, S);
+  for (size_t i = 0; values && i < b.B * Sj; ++i)
+    if (b.src_ids[i] >= vmax) return fail(-1, "batch %zu: token id %u out of range", j, b.src_ids[i]);
+  for (size_t i = 0; values && i < b.B; ++i)
+    if (b.lengths[i] > Sj) return fail(-1, "batch %zu: length %u > S", j, b.lengths[i]);
+  return 0;
+}
+
+// A host batch as the kernels read and write it: dev = b with the device views of its pinned arrays (the shortlist stays
+// the caller's). false: one of the arrays is pageable.
+bool pinned_batch_view(const slimt_hip_batch &b, slimt_hip_batch &dev) {
+  dev = b;
+  dev.src_ids = static_cast<const uint32_t *>(host_device_view(b.src_ids));
+  dev.lengths = static_cast<const uint32_t *>(host_device_view(b.lengths));
+  dev.out_ids = static_cast<uint32_t *>(host_device_view(b.out_ids));
+  dev.out_len = static_cast<uint32_t *>(host_device_view(b.out_len));
+  dev.align = b.align ? static_cast<float *>(host_device_view(b.align)) : nullptr;
+  return dev.src_ids && dev.lengths && dev.out_ids && dev.out_len && (!b.align || dev.align);
 }
 }  // namespace
 
@@ -3121,42 +3161,29 @@ extern "C" size_t slimt_hip_translate_many_rows(const size_t *B, size_t n_batche
 
 extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_hip_batch *batches, size_t n_batches, size_t S,
                                                float limit_factor, uint32_t eos_id, int steps_hint) {
-  ScoreCall sc(ctx, n_batches);
-  PrefixCall pc(ctx, n_batches);
-  SampleCall smc(ctx, n_batches);
-  TruncationCall trc(ctx);
-  if (sc.rc) return sc.rc;
-  if (pc.rc) return pc.rc;
-  if (smc.rc) return smc.rc;
-  if (trc.rc) return trc.rc;
+  CallOptions opt(ctx, n_batches);
+  RCCHK(opt.rc());
   if (!ctx || !batches || n_batches == 0) return fail(-1, "null argument");
   HIPCHK(hipSetDevice(ctx->model->device));
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
   MergePlan mp;
   size_t rows = 0;
   const bool mergeable = n_batches > 1 && n_batches <= (size_t)kMaxMerge && !ctx->tr_call;  // (truncated: batch by batch)
-  size_t n_cols = 0;  // the widest output layer of the launch
-  for (size_t j = 0; j < n_batches; ++j) n_cols = std::max(n_cols, batches[j].n_shortlist ? batches[j].n_shortlist : (size_t)ctx->model->V);
   if (mergeable)
-    RCCHK(build_merge_plan(ctx, batches, n_batches, S, Tmax, limit_factor, steps_hint, nullptr, mp, rows, merge_tile(ctx, n_cols)));
-  for (size_t j = 0; mergeable && ctx->sc_call && j < n_batches; ++j) mp.scores[j] = sc.dst[j];
+    RCCHK(build_merge_plan(ctx, batches, n_batches, S, Tmax, limit_factor, steps_hint, nullptr, mp, rows, kMergeTile));
+  for (size_t j = 0; mergeable && ctx->sc_call && j < n_batches; ++j) mp.scores[j] = opt.sc.dst[j];
   for (size_t j = 0; mergeable && ctx->fp_call && j < n_batches; ++j) {
-    mp.prefix_ids[j] = pc.ids[j];
-    mp.prefix_len[j] = pc.len[j];
+    mp.prefix_ids[j] = opt.pc.ids[j];
+    mp.prefix_len[j] = opt.pc.len[j];
   }
-  for (size_t j = 0; mergeable && ctx->sm_call && j < n_batches; ++j) mp.keys[j] = smc.keys[j];
+  for (size_t j = 0; mergeable && ctx->sm_call && j < n_batches; ++j) mp.keys[j] = opt.smc.keys[j];
   if (mergeable && rows <= ctx->max_B && rows * S <= ctx->max_M && S <= ctx->max_S && merge_supported(ctx, rows, S))
     return translate_device(ctx, batches[0].src_ids, batches[0].lengths, batches[0].shortlist, rows, S, (size_t)mp.max_N,
                             limit_factor, eos_id, batches[0].out_ids, batches[0].out_len, batches[0].align, steps_hint, nullptr,
                             nullptr, 0, nullptr, &mp);
   for (size_t j = 0; j < n_batches; ++j) {  // batch by batch, in order, on the same stream
     const slimt_hip_batch &b = batches[j];
-    if (ctx->sc_call) ctx->sc_user = sc.dst[j];
-    if (ctx->fp_call) {
-      ctx->fp_user_ids = pc.ids[j];
-      ctx->fp_user_len = pc.len[j];
-    }
-    if (ctx->sm_call) ctx->sm_user_keys = smc.keys[j];
+    arm_batch(ctx, opt.sc.dst.data(), opt.pc, opt.smc, j);
     // (a truncated call is never merged, so it must give here what a merged launch gives: the launch's step budget is the
     // longest batch's, and a shorter batch takes at most its own Tmax_j -- build_merge_plan's rule. Other calls that come
     // this way keep the budget as given, as before.)
@@ -3170,14 +3197,8 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
 
 extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hip_batch *batches, size_t n_batches, size_t S,
                                               float limit_factor, uint32_t eos_id) {
-  ScoreCall sc(ctx, n_batches);
-  PrefixCall pc(ctx, n_batches);
-  SampleCall smc(ctx, n_batches);
-  TruncationCall trc(ctx);
-  if (sc.rc) return sc.rc;
-  if (pc.rc) return pc.rc;
-  if (smc.rc) return smc.rc;
-  if (trc.rc) return trc.rc;
+  CallOptions opt(ctx, n_batches);
+  RCCHK(opt.rc());
   if (!ctx || !batches || n_batches == 0) return fail(-1, "null argument");
   const slimt_hip_model *m = ctx->model;
   HIPCHK(hipSetDevice(m->device));
@@ -3189,22 +3210,11 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   size_t rows = 0;
   for (size_t j = 0; merged && j < n_batches; ++j) {
     const slimt_hip_batch &b = batches[j];
-    if (!b.src_ids || !b.lengths || !b.out_ids || !b.out_len || b.B == 0) return fail(-1, "batch %zu: null array or empty", j);
     if (b.shortlist != batches[0].shortlist || b.n_shortlist != batches[0].n_shortlist) merged = false;  // one host shortlist
-    const size_t Sj = b.S ? b.S : S;
-    if (Sj > S) return fail(-1, "batch %zu is padded to %zu tokens, the launch to %zu", j, Sj, S);
-    for (size_t i = 0; merged && i < b.B * Sj; ++i)
-      if (b.src_ids[i] >= (uint32_t)m->V) return fail(-1, "batch %zu: token id %u out of range", j, b.src_ids[i]);
-    for (size_t i = 0; merged && i < b.B; ++i)
-      if (b.lengths[i] > Sj) return fail(-1, "batch %zu: length %u > S", j, b.lengths[i]);
-    dev[j] = b;
-    dev[j].src_ids = static_cast<const uint32_t *>(host_device_view(b.src_ids));
-    dev[j].lengths = static_cast<const uint32_t *>(host_device_view(b.lengths));
-    dev[j].out_ids = static_cast<uint32_t *>(host_device_view(b.out_ids));
-    dev[j].out_len = static_cast<uint32_t *>(host_device_view(b.out_len));
-    dev[j].align = b.align ? static_cast<float *>(host_device_view(b.align)) : nullptr;
-    if (!dev[j].src_ids || !dev[j].lengths || !dev[j].out_ids || !dev[j].out_len || (b.align && !dev[j].align)) merged = false;
-    if (ctx->sc_call && !(dev_sc[j] = static_cast<float *>(host_device_view(sc.dst[j])))) merged = false;
+    // (ids and lengths only while a merged launch is still possible: else each batch's translate_host checks its own)
+    RCCHK(check_host_batch(b, j, S, (uint32_t)m->V, merged));
+    if (!pinned_batch_view(b, dev[j])) merged = false;
+    if (ctx->sc_call && !(dev_sc[j] = static_cast<float *>(host_device_view(opt.sc.dst[j])))) merged = false;
     any_align = any_align || b.align != nullptr;
     rows += b.B;  // (one shortlist for all: the sub-batches follow each other densely)
   }
@@ -3212,13 +3222,8 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   if (!merged) {
     for (size_t j = 0; j < n_batches; ++j) {
       const slimt_hip_batch &b = batches[j];
-      if (ctx->sc_call) ctx->sc_user = sc.dst[j];
-      if (ctx->fp_call) {
-        ctx->fp_user_ids = pc.ids[j];
-        ctx->fp_user_len = pc.len[j];
-      }
-      if (ctx->sm_call) ctx->sm_user_keys = smc.keys[j];
-      RCCHK(translate_host(ctx, b.src_ids, b.lengths, b.B, b.S ? b.S : S, b.shortlist, b.n_shortlist, limit_factor, eos_id,
+      arm_batch(ctx, opt.sc.dst.data(), opt.pc, opt.smc, j);
+      RCCHK(translate_host(ctx, nullptr, b.src_ids, b.lengths, b.B, b.S ? b.S : S, b.shortlist, b.n_shortlist, limit_factor, eos_id,
                            b.out_ids, b.out_len, b.align, false));
     }
     return 0;
@@ -3229,13 +3234,7 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   if (n_sl && !shortlist) return fail(-1, "shortlist is NULL");
   for (size_t i = 0; i < n_sl; ++i)
     if (shortlist[i] >= (uint32_t)m->V) return fail(-1, "shortlist id %u out of range", shortlist[i]);
-  hipStream_t st = ctx->stream;
-  if (n_sl && (ctx->sl_host.size() != n_sl || std::memcmp(ctx->sl_host.data(), shortlist, n_sl * 4) != 0)) {
-    ctx->sl_host.clear();  // (translate_host: uploaded when it changes)
-    HIPCHK(hipMemcpyAsync(ctx->shortlist.p, shortlist, n_sl * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    ctx->sl_host.assign(shortlist, shortlist + n_sl);
-  }
+  RCCHK(upload_shortlist_if_changed(ctx, shortlist, n_sl));  // (translate_host: uploaded when it changes)
   if (any_align) HIPCHK(ctx->align.reserve(align_staging_bytes(ctx, rows, S, Tmax, limit_factor)));
   for (size_t j = 0; j < n_batches; ++j) {
     dev[j].shortlist = n_sl ? ctx->shortlist.as<uint32_t>() : nullptr;
@@ -3244,8 +3243,8 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   MergePlan mp;
   RCCHK(build_merge_plan(ctx, dev, n_batches, S, Tmax, limit_factor, 0, any_align ? ctx->align.as<float>() : nullptr, mp, rows));
   for (size_t j = 0; ctx->sc_call && j < n_batches; ++j) mp.scores[j] = dev_sc[j];
-  if (ctx->fp_call) RCCHK(prefix_stage_batches(ctx, pc, batches, n_batches, S, limit_factor, mp.prefix_ids, mp.prefix_len));
-  if (ctx->sm_call) RCCHK(keys_stage_batches(ctx, smc, batches, n_batches, mp.keys));
+  if (ctx->fp_call) RCCHK(prefix_stage_batches(ctx, opt.pc, batches, n_batches, S, limit_factor, mp.prefix_ids, mp.prefix_len));
+  if (ctx->sm_call) RCCHK(keys_stage_batches(ctx, opt.smc, batches, n_batches, mp.keys));
   return translate_device(ctx, dev[0].src_ids, dev[0].lengths, dev[0].shortlist, rows, S, (size_t)mp.max_N, limit_factor, eos_id,
                           dev[0].out_ids, dev[0].out_len, any_align ? ctx->align.as<float>() : nullptr, (int)Tmax, nullptr,
                           any_align ? dev[0].align : nullptr, 0, nullptr, &mp);
@@ -3501,6 +3500,30 @@ void shortlist_args(const slimt_hip_shortlist *sl, const uint32_t *d_ids, const 
   a.n_out = d_n;
 }
 
+// A caller's host shortlist of n ids in ctx->shortlist, where the kernels read it.
+int upload_shortlist_if_changed(slimt_hip_ctx *ctx, const uint32_t *ids, size_t n) {
+  if (!n || (ctx->sl_host.size() == n && std::memcmp(ctx->sl_host.data(), ids, n * 4) == 0)) return 0;
+  hipStream_t st = ctx->stream;
+  ctx->sl_host.clear();  // until the upload has succeeded the device copy is nobody's
+  HIPCHK(hipMemcpyAsync(ctx->shortlist.p, ids, n * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));  // (the caller's array may be pageable: the copy is staged; done once per shortlist)
+  ctx->sl_host.assign(ids, ids + n);
+  return 0;
+}
+
+// The generator's arguments for the batch's list in ctx->shortlist, its count in ctx->n_sl_dev, on the context's scratch.
+// n_lists > 1 (a merged launch, one list per sub-batch inside the encoder launch): that many counts, and no scratch -- the
+// bitmaps in global memory are the two-kernel generator's. Launching and reading the count back are the caller's.
+int generated_shortlist_args(slimt_hip_ctx *ctx, const slimt_hip_shortlist *sl, const uint32_t *d_ids, const uint32_t *d_len,
+                             size_t B, size_t S, ShortlistArgs &a, size_t n_lists) {
+  ctx->sl_host.clear();  // ctx->shortlist no longer holds what translate_host uploaded last
+  HIPCHK(ctx->n_sl_dev.reserve(4 * n_lists));
+  if (n_lists == 1) RCCHK(shortlist_scratch(ctx->sl_scratch, sl, ctx->stream));
+  shortlist_args(sl, d_ids, d_len, B, S, ctx->shortlist.as<uint32_t>(), ctx->n_sl_dev.as<uint32_t>(), a);
+  if (n_lists == 1) a.scratch = ctx->sl_scratch.as<uint32_t>();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int slimt_hip_shortlist_create(const void *blob, size_t blob_size, size_t source_vocab,
@@ -3642,22 +3665,13 @@ extern "C" int slimt_hip_translate_device_generated(slimt_hip_ctx *ctx, slimt_hi
                                                     float limit_factor, uint32_t eos_id,
                                                     uint32_t *d_out_ids, uint32_t *d_out_len,
                                                     float *d_align, int steps_hint) {
-  ScoreCall sc(ctx, 1);
-  PrefixCall pc(ctx, 1);
-  SampleCall smc(ctx, 1);
-  TruncationCall trc(ctx);
-  if (sc.rc) return sc.rc;
-  if (pc.rc) return pc.rc;
-  if (smc.rc) return smc.rc;
-  if (trc.rc) return trc.rc;
+  CallOptions opt(ctx, 1);
+  RCCHK(opt.rc());
   if (!ctx || !sl || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len)
     return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
-  const slimt_hip_model *m = ctx->model;
-  if (sl->device != m->device) return fail(-1, "shortlist and context are on different devices");
-  if (sl->target_vocab != (size_t)m->V)
-    return fail(-1, "shortlist target vocabulary %zu != model vocabulary %d", sl->target_vocab, m->V);
-  HIPCHK(hipSetDevice(m->device));
+  RCCHK(check_generator(ctx, sl));
+  HIPCHK(hipSetDevice(ctx->model->device));
   if (ctx->sc_call) ctx->sc_dev = ctx->sc_user;  // (device memory, like the other outputs)
   if (ctx->fp_call) {  // (device memory: read where it is)
     ctx->fp_ids = ctx->fp_user_ids;
@@ -3668,115 +3682,53 @@ extern "C" int slimt_hip_translate_device_generated(slimt_hip_ctx *ctx, slimt_hi
                              d_align, steps_hint, nullptr);
 }
 
-namespace {
-// Model::forward (Model.cc:111-204) on HOST buffers with the batch's lexical shortlist generated on
-// the device (Model.cc:117-120): no host shortlist, no upload, no synchronisation in the
-// asynchronous form.
-int translate_host_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const uint32_t *src_ids,
-                             const uint32_t *lengths, size_t B, size_t S, float limit_factor,
-                             uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align, bool wait) {
-  if (!ctx || !sl || !src_ids || !lengths || !out_ids || !out_len) return fail(-1, "null argument");
-  RCCHK(check_batch(ctx, B, S));
-  const slimt_hip_model *m = ctx->model;
-  if (sl->device != m->device) return fail(-1, "shortlist and context are on different devices");
-  if (sl->target_vocab != (size_t)m->V)
-    return fail(-1, "shortlist target vocabulary %zu != model vocabulary %d", sl->target_vocab, m->V);
-  const uint32_t vmax = (uint32_t)std::min((size_t)m->V, sl->source_vocab);
-  for (size_t i = 0; i < B * S; ++i)
-    if (src_ids[i] >= vmax) return fail(-1, "token id %u out of range", src_ids[i]);
-  for (size_t i = 0; i < B; ++i)
-    if (lengths[i] > S) return fail(-1, "length %u > S", lengths[i]);
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t st = ctx->stream;
-  const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
-  const bool persistent = fused_decoder_allowed(ctx) && fused_decode_supported(m->D, m->F, m->H, m->Ld) &&
-                          (fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S) ||
-                           long_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S));
-  if (ctx->fp_call) {  // (translate_host)
-    const size_t Bs[1] = {B}, Ts[1] = {Tmax};
-    RCCHK(prefix_stage(ctx, 1, &ctx->fp_user_ids, &ctx->fp_user_len, Bs, Ts, &ctx->fp_ids, &ctx->fp_len));
-  }
-  if (ctx->sm_call) {  // (a sampled call: the caller's host keys, pinned in place or staged in device memory)
-    const size_t Bk[1] = {B};
-    RCCHK(keys_stage(ctx, 1, &ctx->sm_user_keys, Bk, &ctx->sm_keys));
-  }
-  float *const scores = ctx->sc_call ? ctx->sc_user : nullptr;  // (translate_host)
-  if (!wait && persistent) {  // pinned buffers: the kernels read and write host memory themselves (translate_host)
-    void *v_ids = host_device_view(src_ids), *v_len = host_device_view(lengths), *v_out = host_device_view(out_ids),
-         *v_ol = host_device_view(out_len), *v_al = align ? host_device_view(align) : nullptr;
-    void *v_sc = scores ? host_device_view(scores) : nullptr;
-    if (v_ids && v_len && v_out && v_ol && (!align || v_al) && (!scores || v_sc)) {
-      ctx->sc_dev = static_cast<float *>(v_sc);
-      if (align) HIPCHK(ctx->align.reserve(align_staging_bytes(ctx, B, S, Tmax, limit_factor)));
-      return translate_generated(ctx, sl, static_cast<const uint32_t *>(v_ids), static_cast<const uint32_t *>(v_len),
-                                 B, S, limit_factor, eos_id, static_cast<uint32_t *>(v_out),
-                                 static_cast<uint32_t *>(v_ol), align ? ctx->align.as<float>() : nullptr,
-                                 (int)Tmax, static_cast<float *>(v_al));
-    }
-  }
-  HIPCHK(ctx->out_ids.reserve(B * Tmax * 4));
-  if (align) HIPCHK(ctx->align.reserve(B * Tmax * S * 4));
-  if (scores) {
-    HIPCHK(ctx->sc_stage.reserve(B * Tmax * 4));
-    ctx->sc_dev = ctx->sc_stage.as<float>();
-  }
-  HIPCHK(hipMemcpyAsync(ctx->ids.p, src_ids, B * S * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(ctx->lengths.p, lengths, B * 4, hipMemcpyHostToDevice, st));
-  RCCHK(translate_generated(ctx, sl, ctx->ids.as<uint32_t>(), ctx->lengths.as<uint32_t>(), B, S, limit_factor,
-                            eos_id, ctx->out_ids.as<uint32_t>(), ctx->out_len.as<uint32_t>(),
-                            align ? ctx->align.as<float>() : nullptr, wait ? 0 : (int)Tmax, nullptr));
-  HIPCHK(hipMemcpyAsync(out_ids, ctx->out_ids.p, B * Tmax * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(out_len, ctx->out_len.p, B * 4, hipMemcpyDeviceToHost, st));
-  if (align) HIPCHK(hipMemcpyAsync(align, ctx->align.p, B * Tmax * S * 4, hipMemcpyDeviceToHost, st));
-  if (scores) HIPCHK(hipMemcpyAsync(scores, ctx->sc_stage.p, B * Tmax * 4, hipMemcpyDeviceToHost, st));
-  if (wait) RCCHK(slimt_hip_ctx_synchronize(ctx));  // sleeps on a blocking-sync event (a worker per context: no spinning)
-  return 0;
-}
-}  // namespace
-
 // ---- merged launches whose batches each get THEIR lexical shortlist, generated inside the encoder launch ---------------
 namespace {
+// The per-batch options of a translate_many_generated call, one entry per batch where a pointer is set. The *_dev arrays hold
+// what the kernels read and write (device memory, or the device views of pinned arrays; for the prefixes and keys also
+// staged copies); the *_host members what the caller gave, for the fallback through translate_host.
+struct ManyGenerated {
+  float *const *sc_dev = nullptr;   // a scored call: each batch's score destination ...
+  float *const *sc_host = nullptr;  // ... and, with `host`, as the caller gave it
+  const uint32_t *const *fp_dev_ids = nullptr;  // a forced call: each batch's prefix in device memory ...
+  const uint32_t *const *fp_dev_len = nullptr;
+  const PrefixCall *fp_host = nullptr;  // ... and, with `host`, as the caller gave it
+  const uint64_t *const *sm_dev = nullptr;  // a sampled call: each batch's keys as the kernels read them ...
+  const SampleCall *sm_host = nullptr;      // ... and, with `host`, as the caller gave them
+  // the asynchronous entry point: the same batches with the caller's HOST pointers -- what the batch-by-batch fallback hands
+  // to translate_host, which knows when the kernels can use pinned arrays in place
+  const slimt_hip_batch *host = nullptr;
+  bool stage_align = false;  // the alignment rows are staged in ctx->align (the batches' `align` are pinned views)
+  int steps_hint = 0;
+};
+
 // dev: the batches with arrays the device can read (device memory, or the device views of pinned arrays); the merged launch
 // when it is possible, else batch by batch through translate_generated
 int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const slimt_hip_batch *dev, size_t n, size_t S,
-                             float limit_factor, uint32_t eos_id, int steps_hint, bool stage_align,
-                             const slimt_hip_batch *host = nullptr, float *const *sc_dev = nullptr,
-                             float *const *sc_host = nullptr, const uint32_t *const *fp_dev_ids = nullptr,
-                             const uint32_t *const *fp_dev_len = nullptr, const PrefixCall *fp_host = nullptr,
-                             const uint64_t *const *sm_dev = nullptr, const SampleCall *sm_host = nullptr) {
-  // sm_dev / sm_host (a sampled call): each batch's keys as the kernels read them and, with `host`, as the caller gave them
-  // fp_dev_* / fp_host (a forced call): each batch's prefix in device memory and, with `host`, as the caller gave it
-  // sc_dev / sc_host (a scored call): each batch's score destination as the kernels write it (device memory, or the device
-  // view of a pinned array) and, with `host`, as the caller gave it
-  // host (the asynchronous entry point): the same batches with the caller's HOST pointers -- what the batch-by-batch
-  // fallback hands to translate_host_generated, which knows when the kernels can use pinned arrays in place
+                             float limit_factor, uint32_t eos_id, const ManyGenerated &o) {
   const slimt_hip_model *m = ctx->model;
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
   const size_t V = (size_t)m->V;
+  const int steps_hint = o.steps_hint;
+  const bool stage_align = o.stage_align;
   size_t rows = 0;
   bool any_align = false;
   uint32_t *hint = reinterpret_cast<uint32_t *>(ctx->n_finished_host) + 1;  // (translate_generated: the previous shortlist's size)
   const size_t n_hint = *hint;
-  const size_t tile = merge_tile(ctx, n_hint ? n_hint : V);  // (translate_device picks the decoder tiling from the same number)
   for (size_t j = 0; j < n; ++j) {
-    rows += (dev[j].B + tile - 1) / tile * tile;
+    rows += (dev[j].B + kMergeTile - 1) / kMergeTile * kMergeTile;
     any_align = any_align || dev[j].align != nullptr;
   }
   static const bool fold = !(std::getenv("SLIMT_SHORTLIST_FOLD") && std::getenv("SLIMT_SHORTLIST_FOLD")[0] == '0');
   const bool merged = n > 1 && n <= (size_t)kMaxMerge && !ctx->tr_call && S <= ctx->max_S && rows <= ctx->max_B && rows * S <= ctx->max_M &&
                       merge_supported(ctx, rows, S) && fold &&
                       shortlist_in_launch_lds_bytes((int)sl->source_vocab, (int)sl->target_vocab) <= 64 * 1024;
-  if (!merged && host) {
+  if (!merged && o.host) {
     for (size_t j = 0; j < n; ++j) {
-      const slimt_hip_batch &b = host[j];
-      if (ctx->sc_call) ctx->sc_user = sc_host[j];
-      if (ctx->fp_call) {
-        ctx->fp_user_ids = fp_host->ids[j];
-        ctx->fp_user_len = fp_host->len[j];
-      }
-      if (ctx->sm_call) ctx->sm_user_keys = sm_host->keys[j];
-      RCCHK(translate_host_generated(ctx, sl, b.src_ids, b.lengths, b.B, b.S ? b.S : S, limit_factor, eos_id, b.out_ids, b.out_len,
-                                     b.align, false));
+      const slimt_hip_batch &b = o.host[j];
+      arm_batch(ctx, o.sc_host, *o.fp_host, *o.sm_host, j);
+      RCCHK(translate_host(ctx, sl, b.src_ids, b.lengths, b.B, b.S ? b.S : S, nullptr, 0, limit_factor, eos_id, b.out_ids,
+                           b.out_len, b.align, false));
     }
     return 0;
   }
@@ -3790,22 +3742,22 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
         staging = ctx->align.as<float>();
       }
       RCCHK(check_batch(ctx, b.B, Sj));
-      if (ctx->sc_call) ctx->sc_dev = sc_dev[j];
+      if (ctx->sc_call) ctx->sc_dev = o.sc_dev[j];
       if (ctx->fp_call) {
-        ctx->fp_ids = fp_dev_ids[j];
-        ctx->fp_len = fp_dev_len[j];
+        ctx->fp_ids = o.fp_dev_ids[j];
+        ctx->fp_len = o.fp_dev_len[j];
       }
-      if (ctx->sm_call) ctx->sm_keys = sm_dev[j];
+      if (ctx->sm_call) ctx->sm_keys = o.sm_dev[j];
       RCCHK(translate_generated(ctx, sl, b.src_ids, b.lengths, b.B, Sj, limit_factor, eos_id, b.out_ids, b.out_len,
                                 staging ? staging : b.align, steps_hint > 0 ? std::min(steps_hint, (int)Tj) : (stage_align ? (int)Tj : 0),
                                 staging ? b.align : nullptr));
     }
     return 0;
   }
-  hipStream_t st = ctx->stream;
   ctx->sl_host.clear();  // ctx->shortlist no longer holds what translate_host uploaded last
   HIPCHK(ctx->shortlist.reserve(n * V * 4));  // job j's ids at j * V, its count at n_sl_dev[j]
-  HIPCHK(ctx->n_sl_dev.reserve(4 * (size_t)kMaxMerge));
+  ShortlistArgs a;
+  RCCHK(generated_shortlist_args(ctx, sl, dev[0].src_ids, dev[0].lengths, dev[0].B, S, a, (size_t)kMaxMerge));
   slimt_hip_batch plan[kMaxMerge];
   for (size_t j = 0; j < n; ++j) {
     plan[j] = dev[j];
@@ -3814,44 +3766,27 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
   }
   if (any_align && stage_align) HIPCHK(ctx->align.reserve(align_staging_bytes(ctx, rows, S, Tmax, limit_factor)));
   MergePlan mp;
-  RCCHK(build_merge_plan(ctx, plan, n, S, Tmax, limit_factor, steps_hint, any_align && stage_align ? ctx->align.as<float>() : nullptr, mp, rows, tile));
-  for (size_t j = 0; ctx->sc_call && j < n; ++j) mp.scores[j] = sc_dev[j];
+  RCCHK(build_merge_plan(ctx, plan, n, S, Tmax, limit_factor, steps_hint, any_align && stage_align ? ctx->align.as<float>() : nullptr, mp, rows, kMergeTile));
+  for (size_t j = 0; ctx->sc_call && j < n; ++j) mp.scores[j] = o.sc_dev[j];
   for (size_t j = 0; ctx->fp_call && j < n; ++j) {
-    mp.prefix_ids[j] = fp_dev_ids[j];
-    mp.prefix_len[j] = fp_dev_len[j];
+    mp.prefix_ids[j] = o.fp_dev_ids[j];
+    mp.prefix_len[j] = o.fp_dev_len[j];
   }
-  for (size_t j = 0; ctx->sm_call && j < n; ++j) mp.keys[j] = sm_dev[j];
-  ShortlistArgs a;
-  shortlist_args(sl, plan[0].src_ids, plan[0].lengths, plan[0].B, S, ctx->shortlist.as<uint32_t>(), ctx->n_sl_dev.as<uint32_t>(), a);
+  for (size_t j = 0; ctx->sm_call && j < n; ++j) mp.keys[j] = o.sm_dev[j];
   void *hint_dev = nullptr;
   if (hipHostGetDevicePointer(&hint_dev, hint, 0) == hipSuccess) a.n_out_host = static_cast<uint32_t *>(hint_dev);
-  (void)st;
   return translate_device(ctx, plan[0].src_ids, plan[0].lengths, ctx->shortlist.as<uint32_t>(), rows, S, V, limit_factor, eos_id,
                           plan[0].out_ids, plan[0].out_len, any_align ? (stage_align ? ctx->align.as<float>() : plan[0].align) : nullptr,
                           steps_hint > 0 ? steps_hint : (int)Tmax, ctx->n_sl_dev.as<uint32_t>(),
                           any_align && stage_align ? plan[0].align : nullptr, n_hint, &a, &mp);
-}
-
-int check_generator(const slimt_hip_ctx *ctx, const slimt_hip_shortlist *sl) {
-  const slimt_hip_model *m = ctx->model;
-  if (sl->device != m->device) return fail(-1, "shortlist and context are on different devices");
-  if (sl->target_vocab != (size_t)m->V)
-    return fail(-1, "shortlist target vocabulary %zu != model vocabulary %d", sl->target_vocab, m->V);
-  return 0;
 }
 }  // namespace
 
 extern "C" int slimt_hip_translate_many_device_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const slimt_hip_batch *batches,
                                                          size_t n_batches, size_t S, float limit_factor, uint32_t eos_id,
                                                          int steps_hint) {
-  ScoreCall sc(ctx, n_batches);
-  PrefixCall pc(ctx, n_batches);
-  SampleCall smc(ctx, n_batches);
-  TruncationCall trc(ctx);
-  if (sc.rc) return sc.rc;
-  if (pc.rc) return pc.rc;
-  if (smc.rc) return smc.rc;
-  if (trc.rc) return trc.rc;
+  CallOptions opt(ctx, n_batches);
+  RCCHK(opt.rc());
   if (!ctx || !sl || !batches || n_batches == 0) return fail(-1, "null argument");
   RCCHK(check_generator(ctx, sl));
   for (size_t j = 0; j < n_batches; ++j) {
@@ -3860,21 +3795,21 @@ extern "C" int slimt_hip_translate_many_device_generated(slimt_hip_ctx *ctx, sli
     if ((b.S ? b.S : S) > S) return fail(-1, "batch %zu is padded to %zu tokens, the launch to %zu", j, b.S, S);
   }
   HIPCHK(hipSetDevice(ctx->model->device));
-  return translate_many_generated(ctx, sl, batches, n_batches, S, limit_factor, eos_id, steps_hint, false, nullptr,
-                                  ctx->sc_call ? sc.dst.data() : nullptr, nullptr, ctx->fp_call ? pc.ids.data() : nullptr,
-                                  ctx->fp_call ? pc.len.data() : nullptr, nullptr, ctx->sm_call ? smc.keys.data() : nullptr);
+  ManyGenerated o;
+  o.steps_hint = steps_hint;
+  if (ctx->sc_call) o.sc_dev = opt.sc.dst.data();
+  if (ctx->fp_call) {
+    o.fp_dev_ids = opt.pc.ids.data();
+    o.fp_dev_len = opt.pc.len.data();
+  }
+  if (ctx->sm_call) o.sm_dev = opt.smc.keys.data();
+  return translate_many_generated(ctx, sl, batches, n_batches, S, limit_factor, eos_id, o);
 }
 
 extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const slimt_hip_batch *batches,
                                                         size_t n_batches, size_t S, float limit_factor, uint32_t eos_id) {
-  ScoreCall sc(ctx, n_batches);
-  PrefixCall pc(ctx, n_batches);
-  SampleCall smc(ctx, n_batches);
-  TruncationCall trc(ctx);
-  if (sc.rc) return sc.rc;
-  if (pc.rc) return pc.rc;
-  if (smc.rc) return smc.rc;
-  if (trc.rc) return trc.rc;
+  CallOptions opt(ctx, n_batches);
+  RCCHK(opt.rc());
   if (!ctx || !sl || !batches || n_batches == 0) return fail(-1, "null argument");
   RCCHK(check_generator(ctx, sl));
   const slimt_hip_model *m = ctx->model;
@@ -3883,43 +3818,36 @@ extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slim
   slimt_hip_batch dev[kMaxMerge];
   float *dev_sc[kMaxMerge] = {};  // (scored: the device views of the pinned score arrays)
   bool pinned = n_batches <= (size_t)kMaxMerge;
-  for (size_t j = 0; j < n_batches; ++j) {
-    const slimt_hip_batch &b = batches[j];
-    if (!b.src_ids || !b.lengths || !b.out_ids || !b.out_len || b.B == 0) return fail(-1, "batch %zu: null array or empty", j);
-    const size_t Sj = b.S ? b.S : S;
-    if (Sj > S) return fail(-1, "batch %zu is padded to %zu tokens, the launch to %zu", j, Sj, S);
-    for (size_t i = 0; i < b.B * Sj; ++i)
-      if (b.src_ids[i] >= vmax) return fail(-1, "batch %zu: token id %u out of range", j, b.src_ids[i]);
-    for (size_t i = 0; i < b.B; ++i)
-      if (b.lengths[i] > Sj) return fail(-1, "batch %zu: length %u > S", j, b.lengths[i]);
+  for (size_t j = 0; j < n_batches; ++j) {  // (every batch in full before anything is queued)
+    RCCHK(check_host_batch(batches[j], j, S, vmax, true));
     if (!pinned) continue;
-    dev[j] = b;
-    dev[j].src_ids = static_cast<const uint32_t *>(host_device_view(b.src_ids));
-    dev[j].lengths = static_cast<const uint32_t *>(host_device_view(b.lengths));
-    dev[j].out_ids = static_cast<uint32_t *>(host_device_view(b.out_ids));
-    dev[j].out_len = static_cast<uint32_t *>(host_device_view(b.out_len));
-    dev[j].align = b.align ? static_cast<float *>(host_device_view(b.align)) : nullptr;
-    if (!dev[j].src_ids || !dev[j].lengths || !dev[j].out_ids || !dev[j].out_len || (b.align && !dev[j].align)) pinned = false;
-    if (ctx->sc_call && !(dev_sc[j] = static_cast<float *>(host_device_view(sc.dst[j])))) pinned = false;
+    if (!pinned_batch_view(batches[j], dev[j])) pinned = false;
+    if (ctx->sc_call && !(dev_sc[j] = static_cast<float *>(host_device_view(opt.sc.dst[j])))) pinned = false;
   }
   const uint32_t *fp_ids[kMaxMerge] = {}, *fp_len[kMaxMerge] = {};  // (forced: the staged prefixes)
-  if (pinned && ctx->fp_call) RCCHK(prefix_stage_batches(ctx, pc, batches, n_batches, S, limit_factor, fp_ids, fp_len));
+  if (pinned && ctx->fp_call) RCCHK(prefix_stage_batches(ctx, opt.pc, batches, n_batches, S, limit_factor, fp_ids, fp_len));
   const uint64_t *sm_keys[kMaxMerge] = {};  // (sampled: the keys' pinned views or staged copies)
-  if (pinned && ctx->sm_call) RCCHK(keys_stage_batches(ctx, smc, batches, n_batches, sm_keys));
-  if (pinned)
-    return translate_many_generated(ctx, sl, dev, n_batches, S, limit_factor, eos_id, 0, true, batches,
-                                    ctx->sc_call ? dev_sc : nullptr, ctx->sc_call ? sc.dst.data() : nullptr,
-                                    fp_ids, fp_len, &pc, sm_keys, &smc);
+  if (pinned && ctx->sm_call) RCCHK(keys_stage_batches(ctx, opt.smc, batches, n_batches, sm_keys));
+  if (pinned) {
+    ManyGenerated o;
+    o.host = batches;
+    o.stage_align = true;
+    if (ctx->sc_call) {
+      o.sc_dev = dev_sc;
+      o.sc_host = opt.sc.dst.data();
+    }
+    o.fp_dev_ids = fp_ids;
+    o.fp_dev_len = fp_len;
+    o.fp_host = &opt.pc;
+    o.sm_dev = sm_keys;
+    o.sm_host = &opt.smc;
+    return translate_many_generated(ctx, sl, dev, n_batches, S, limit_factor, eos_id, o);
+  }
   for (size_t j = 0; j < n_batches; ++j) {  // pageable arrays, or too many batches: one by one through the copying path
     const slimt_hip_batch &b = batches[j];
-    if (ctx->sc_call) ctx->sc_user = sc.dst[j];
-    if (ctx->fp_call) {
-      ctx->fp_user_ids = pc.ids[j];
-      ctx->fp_user_len = pc.len[j];
-    }
-    if (ctx->sm_call) ctx->sm_user_keys = smc.keys[j];
-    RCCHK(translate_host_generated(ctx, sl, b.src_ids, b.lengths, b.B, b.S ? b.S : S, limit_factor, eos_id, b.out_ids, b.out_len,
-                                   b.align, false));
+    arm_batch(ctx, opt.sc.dst.data(), opt.pc, opt.smc, j);
+    RCCHK(translate_host(ctx, sl, b.src_ids, b.lengths, b.B, b.S ? b.S : S, nullptr, 0, limit_factor, eos_id, b.out_ids, b.out_len,
+                         b.align, false));
   }
   return 0;
 }
@@ -3927,30 +3855,20 @@ extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slim
 extern "C" int slimt_hip_translate_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const uint32_t *src_ids,
                                              const uint32_t *lengths, size_t B, size_t S, float limit_factor,
                                              uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align) {
-  ScoreCall sc(ctx, 1);
-  PrefixCall pc(ctx, 1);
-  SampleCall smc(ctx, 1);
-  TruncationCall trc(ctx);
-  if (sc.rc) return sc.rc;
-  if (pc.rc) return pc.rc;
-  if (smc.rc) return smc.rc;
-  if (trc.rc) return trc.rc;
-  return translate_host_generated(ctx, sl, src_ids, lengths, B, S, limit_factor, eos_id, out_ids, out_len, align, true);
+  CallOptions opt(ctx, 1);
+  RCCHK(opt.rc());
+  if (!sl) return fail(-1, "null argument");
+  return translate_host(ctx, sl, src_ids, lengths, B, S, nullptr, 0, limit_factor, eos_id, out_ids, out_len, align, true);
 }
 
 extern "C" int slimt_hip_translate_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl,
                                                    const uint32_t *src_ids, const uint32_t *lengths, size_t B,
                                                    size_t S, float limit_factor, uint32_t eos_id,
                                                    uint32_t *out_ids, uint32_t *out_len, float *align) {
-  ScoreCall sc(ctx, 1);
-  PrefixCall pc(ctx, 1);
-  SampleCall smc(ctx, 1);
-  TruncationCall trc(ctx);
-  if (sc.rc) return sc.rc;
-  if (pc.rc) return pc.rc;
-  if (smc.rc) return smc.rc;
-  if (trc.rc) return trc.rc;
-  return translate_host_generated(ctx, sl, src_ids, lengths, B, S, limit_factor, eos_id, out_ids, out_len, align, false);
+  CallOptions opt(ctx, 1);
+  RCCHK(opt.rc());
+  if (!sl) return fail(-1, "null argument");
+  return translate_host(ctx, sl, src_ids, lengths, B, S, nullptr, 0, limit_factor, eos_id, out_ids, out_len, align, false);
 }
 
 // ---- teacher-forced scoring: every target position in one tall pass (include/slimt_hip.h, slimt_hip_score*) -----------
@@ -4013,6 +3931,17 @@ bool device_visible(const void *p) {
     return false;
   }
   return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged;
+}
+
+// the alternatives of a _device call (k = 0: unarmed): each array given is memory the kernels can write
+int alternatives_device_visible(const ScoreAltArgs &alt) {
+  if (!alt.k) return 0;
+  const void *arr[3] = {alt.ids, alt.scores, alt.rank};
+  const char *name[3] = {"alt_ids", "alt_scores", "rank"};
+  for (int i = 0; i < 3; ++i)
+    if (arr[i] && !device_visible(arr[i]))
+      return fail(-1, "score alternatives: %s is not memory the device can write (the arrays are of the kind of scores)", name[i]);
+  return 0;
 }
 
 // alt (k = 0: unarmed): ids / scores / rank are addresses the kernels write
@@ -4181,12 +4110,8 @@ int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src
   if (NR == 0) return 0;  // (a candidate call without candidates: nothing to write)
   HIPCHK(hipSetDevice(m->device));
   hipStream_t st = ctx->stream;
-  if (!gen && n_sl && (ctx->sl_host.size() != n_sl || std::memcmp(ctx->sl_host.data(), shortlist, n_sl * 4) != 0)) {
-    ctx->sl_host.clear();  // (translate_host: the shortlist stays on the device, uploaded when it changes)
-    HIPCHK(hipMemcpyAsync(ctx->shortlist.p, shortlist, n_sl * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    ctx->sl_host.assign(shortlist, shortlist + n_sl);
-  }
+  // (translate_host: the shortlist stays on the device, uploaded when it changes)
+  if (!gen) RCCHK(upload_shortlist_if_changed(ctx, shortlist, n_sl));
   // inputs: pinned arrays in place, others staged; [tgt_ids NR T][tgt_len NR][cand_src NR][scores NR T] in score_io
   const uint32_t *d_ids = static_cast<const uint32_t *>(host_device_view(src_ids));
   const uint32_t *d_len = static_cast<const uint32_t *>(host_device_view(lengths));
@@ -4253,12 +4178,8 @@ int score_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src
   }
   const uint32_t *d_sl = ctx->shortlist.as<uint32_t>();
   if (gen) {  // Model.cc:117-120: the batch's shortlist, generated on this stream into ctx->shortlist
-    ctx->sl_host.clear();
-    HIPCHK(ctx->n_sl_dev.reserve(4));
-    RCCHK(shortlist_scratch(ctx->sl_scratch, gen, st));
     ShortlistArgs a;
-    shortlist_args(gen, d_ids, d_len, B, S, ctx->shortlist.as<uint32_t>(), ctx->n_sl_dev.as<uint32_t>(), a);
-    a.scratch = ctx->sl_scratch.as<uint32_t>();
+    RCCHK(generated_shortlist_args(ctx, gen, d_ids, d_len, B, S, a));
     HIPCHK(launch_shortlist_generate(a, st));
     uint32_t n = 0;  // the tall kernels are sized on the host: one 4-byte read-back
     HIPCHK(hipMemcpyAsync(&n, ctx->n_sl_dev.p, 4, hipMemcpyDeviceToHost, st));
@@ -4310,13 +4231,7 @@ extern "C" int slimt_hip_score_device(slimt_hip_ctx *ctx, const uint32_t *d_src_
   RCCHK(score_check(ctx, B, S, n_shortlist, T, B));
   if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
   HIPCHK(hipSetDevice(ctx->model->device));
-  if (ac.a.k) {
-    const void *arr[3] = {ac.a.ids, ac.a.scores, ac.a.rank};
-    const char *name[3] = {"alt_ids", "alt_scores", "rank"};
-    for (int i = 0; i < 3; ++i)
-      if (arr[i] && !device_visible(arr[i]))
-        return fail(-1, "score alternatives: %s is not memory the device can write (the arrays are of the kind of scores)", name[i]);
-  }
+  RCCHK(alternatives_device_visible(ac.a));
   return score_device(ctx, d_src_ids, d_lengths, B, S, d_shortlist, n_shortlist, d_tgt_ids, d_tgt_len, T, d_scores, d_align,
                       ac.a);
 }
@@ -4365,13 +4280,7 @@ extern "C" int slimt_hip_score_candidates_device(slimt_hip_ctx *ctx, const uint3
   if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
   if (N == 0) return 0;
   HIPCHK(hipSetDevice(ctx->model->device));
-  if (ac.a.k) {
-    const void *arr[3] = {ac.a.ids, ac.a.scores, ac.a.rank};
-    const char *name[3] = {"alt_ids", "alt_scores", "rank"};
-    for (int i = 0; i < 3; ++i)
-      if (arr[i] && !device_visible(arr[i]))
-        return fail(-1, "score alternatives: %s is not memory the device can write (the arrays are of the kind of scores)", name[i]);
-  }
+  RCCHK(alternatives_device_visible(ac.a));
   return score_device(ctx, d_src_ids, d_lengths, B, S, d_shortlist, n_shortlist, d_tgt_ids, d_tgt_len, T, d_scores, d_align, ac.a,
                       d_cand_src, N);
 }
@@ -4386,6 +4295,22 @@ int candidates_rank_check(const void *scores, const void *tgt_len, const void *c
     return fail(-1, "candidates rank: %zu x %zu scores exceed the limits (1 <= T <= %zu, N * T <= %zu)", N, T, kScoreMaxT,
                 kScoreMaxRows);
   return 0;
+}
+
+CandRankArgs candidates_rank_args(const float *scores, const uint32_t *tgt_len, const uint32_t *cand_src, size_t N, size_t T,
+                                  size_t B, int mode, float *totals, uint32_t *best, unsigned long long *entries) {
+  CandRankArgs a;
+  a.scores = scores;
+  a.tgt_len = tgt_len;
+  a.cand_src = cand_src;
+  a.N = N;
+  a.T = (uint32_t)T;
+  a.B = (uint32_t)B;
+  a.mode = mode;
+  a.totals = totals;
+  a.best = best;
+  a.entries = entries;
+  return a;
 }
 }  // namespace
 
@@ -4409,18 +4334,8 @@ extern "C" int slimt_hip_candidates_rank(const float *scores, const uint32_t *tg
     HIPCHK(hipMemcpyAsync(t.b.p, tgt_len, N * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(t.c.p, cand_src, N * 4, hipMemcpyHostToDevice, st));
   }
-  CandRankArgs a;
-  a.scores = t.a.as<float>();
-  a.tgt_len = t.b.as<uint32_t>();
-  a.cand_src = t.c.as<uint32_t>();
-  a.N = N;
-  a.T = (uint32_t)T;
-  a.B = (uint32_t)B;
-  a.mode = mode;
-  a.totals = t.d.as<float>();
-  a.best = t.e.as<uint32_t>();
-  a.entries = t.f.as<unsigned long long>();
-  HIPCHK(launch_candidates_rank(a, st));
+  HIPCHK(launch_candidates_rank(candidates_rank_args(t.a.as<float>(), t.b.as<uint32_t>(), t.c.as<uint32_t>(), N, T, B, mode,
+                                                     t.d.as<float>(), t.e.as<uint32_t>(), t.f.as<unsigned long long>()), st));
   if (N) HIPCHK(hipMemcpyAsync(totals, t.d.p, N * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(best, t.e.p, B * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -4434,17 +4349,7 @@ extern "C" int slimt_hip_candidates_rank_device(slimt_hip_ctx *ctx, const float 
   RCCHK(candidates_rank_check(d_scores, d_tgt_len, d_cand_src, N, T, B, mode, d_totals, d_best));
   HIPCHK(hipSetDevice(ctx->model->device));
   RCCHK(score_reserve(ctx, ctx->cand_rank, B * 8));
-  CandRankArgs a;
-  a.scores = d_scores;
-  a.tgt_len = d_tgt_len;
-  a.cand_src = d_cand_src;
-  a.N = N;
-  a.T = (uint32_t)T;
-  a.B = (uint32_t)B;
-  a.mode = mode;
-  a.totals = d_totals;
-  a.best = d_best;
-  a.entries = ctx->cand_rank.as<unsigned long long>();
-  HIPCHK(launch_candidates_rank(a, ctx->stream));
+  HIPCHK(launch_candidates_rank(candidates_rank_args(d_scores, d_tgt_len, d_cand_src, N, T, B, mode, d_totals, d_best,
+                                                     ctx->cand_rank.as<unsigned long long>()), ctx->stream));
   return 0;
 }

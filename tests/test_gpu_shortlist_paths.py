@@ -326,3 +326,140 @@ def test_accessor_refusals(hip, oracle, engines):
     finally:
         gen.close()
         ctx.close()
+
+
+# ---- the batch-by-batch fallbacks of slimt_hip_translate_many_async_generated --------------------------------------------------
+# Batches of 3 and 5 sentences padded to 4 and 7 tokens (two of them, pinned, are one merged launch: _assert_merged). One
+# pageable array among the pinned ones, or more than eight batches, and every batch goes through the host path of a single
+# call instead -- with the options armed for the whole call handed on batch by batch.
+FALLBACK_SHAPES = [(3, 4), (5, 7)]
+FALLBACK_S = 7
+
+
+def _fallback_inputs(hip, oracle, n, options):
+    """n Cases of FALLBACK_SHAPES in turn; with options per batch a forced prefix of 0..2 words of ITS list and sampling keys"""
+    from slimt_amd import synth
+    blob, Vs = T.generator_blob(T.MERGED_MODEL, T.MERGED_GENERATOR)
+    V = T.model_V(T.MERGED_MODEL)
+    cases, prefixes, keys = [], [], []
+    rng = np.random.default_rng(6)
+    for j in range(n):
+        B, Sj = FALLBACK_SHAPES[j % 2]
+        ids, lens = synth.make_batch(V, B, Sj, seed=640 + j, ragged=True)
+        c = T.Case("fallback-%d" % j, blob, Vs, V, T.padded(blob, V, ids, lens, V), lens, False, (), None)
+        cases.append(c)
+        words = T.reference(oracle, c)
+        words = words[words != 0]
+        prefixes.append((rng.choice(words, size=(B, _tmax(Sj))).astype(np.uint32), rng.integers(0, 3, size=B).astype(np.uint32)))
+        keys.append(hip.sampling_keys(78, B, first=100 * j))
+    return cases, (prefixes if options else None), (keys if options else None)
+
+
+def _fallback_buffers(hip, cases, pageable):
+    """per batch (ids, lens, out, out_len, align) and a scores array, pinned; pageable: the last batch's out_len is not"""
+    pins, bufs, scs = [], [], []
+    for j, c in enumerate(cases):
+        B, Sj = c.ids.shape
+        ps = [hip._Pinned() for _ in range(6)]
+        pins += ps
+        b = [ps[0].array(np.uint32, (B, Sj)), ps[1].array(np.uint32, (B,)), ps[2].array(np.uint32, (B, _tmax(Sj))),
+             ps[3].array(np.uint32, (B,)), ps[4].array(np.float32, (B, _tmax(Sj), Sj))]
+        if pageable and j == len(cases) - 1:
+            b[3] = np.zeros((B,), np.uint32)
+        b[0][...] = c.ids
+        b[1][...] = c.lens
+        b[2][...] = SENTINEL
+        b[3][...] = SENTINEL
+        b[4][...] = np.float32(7.25)
+        sc = ps[5].array(np.float32, (B, _tmax(Sj)))
+        sc[...] = np.float32(7.5)
+        bufs.append(tuple(b))
+        scs.append(sc)
+    return pins, bufs, scs
+
+
+def _same_scores(sc, want_sc, ln):
+    for r in range(len(ln)):
+        assert np.array_equal(sc[r, :ln[r]].view(np.uint32), want_sc[r, :ln[r]].view(np.uint32)), r
+
+
+@pytest.mark.parametrize("n,pageable,options", [(2, True, False), (9, False, False), (2, True, True), (9, False, True)],
+                         ids=["pageable-array", "nine-batches", "pageable-array-options", "nine-batches-options"])
+def test_async_fallbacks_equal_the_blocking_calls(hip, oracle, engines, n, pageable, options):
+    """slimt_hip_translate_many_async_generated batch by batch == slimt_hip_translate_generated of each batch on the same
+    context; with scores, a forced prefix and sampling keys armed together each batch gets its own."""
+    cases, prefixes, keys = _fallback_inputs(hip, oracle, n, options)
+    gm = engines(T.MERGED_MODEL)
+    gen = hip.ShortlistGenerator(cases[0].blob, cases[0].Vs, cases[0].Vt)
+    ctx = hip.Context(gm, hip.translate_many_rows([c.ids.shape[0] for c in cases]), FALLBACK_S)
+    pins, bufs, scs = _fallback_buffers(hip, cases, pageable)
+    try:
+        _assert_merged(ctx, FALLBACK_S, 2)
+        if options:
+            wants = [ctx.translate_generated(gen, c.ids, c.lens, want_align=True, scores=True, prefix=p, sampling=(0.8, k))
+                     for c, p, k in zip(cases, prefixes, keys)]
+            ctx.translate_many_async(bufs, generator=gen, scores=scs, prefix=prefixes, sampling=(0.8, keys))
+        else:
+            wants = [ctx.translate_generated(gen, c.ids, c.lens, want_align=True) for c in cases]
+            ctx.translate_many_async(bufs, generator=gen)
+        ctx.synchronize()
+        for b, sc, c, want in zip(bufs, scs, cases, wants):
+            _same_translation((b[2], b[3], b[4]), want[:3], c.lens)
+            if options:
+                _same_scores(sc, want[3], want[1])
+    finally:
+        gen.close()
+        ctx.close()
+        for p in pins:
+            p.free()
+
+
+def test_async_failed_guard_consumes_every_armed_option(hip, oracle, engines):
+    """Scores armed for three batches, a prefix and sampling for two, a call of two batches: it fails at the scores, and the
+    next plain call is an ordinary greedy one -- the prefix and the sampling were taken with the scores."""
+    cases, prefixes, keys = _fallback_inputs(hip, oracle, 2, True)
+    for _, p_len in prefixes:
+        p_len[...] = 2  # (every sentence forced: a prefix left armed would show)
+    gm = engines(T.MERGED_MODEL)
+    gen = hip.ShortlistGenerator(cases[0].blob, cases[0].Vs, cases[0].Vt)
+    ctx = hip.Context(gm, hip.translate_many_rows([c.ids.shape[0] for c in cases]), FALLBACK_S)
+    pins, bufs, scs = _fallback_buffers(hip, cases, True)
+    try:
+        wants = [ctx.translate_generated(gen, c.ids, c.lens, want_align=True) for c in cases]
+        ctx.set_scores(scs + [scs[0]])
+        ctx.set_target_prefix(prefixes)
+        ctx.set_sampling(0.8, keys)
+        with pytest.raises(hip.SlimtHipError, match="scores: 3 destinations armed, the call has 2 batches"):
+            ctx.translate_many_async(bufs, generator=gen)
+        ctx.translate_many_async(bufs, generator=gen)
+        ctx.synchronize()
+        for b, sc, c, want in zip(bufs, scs, cases, wants):
+            _same_translation((b[2], b[3], b[4]), want, c.lens)
+            assert (sc == np.float32(7.5)).all()
+    finally:
+        gen.close()
+        ctx.close()
+        for p in pins:
+            p.free()
+
+
+def test_device_call_refuses_a_generator_of_another_target_vocabulary(hip, engines):
+    """slimt_hip_translate_device_generated checks the generator against the model like the host calls do: refused with their
+    message, nothing written."""
+    V = T.model_V(T.MERGED_MODEL)
+    Vt = V - 3
+    gen = hip.ShortlistGenerator(T.lexical(V, Vt, 24, 4, 45), V, Vt)
+    B, S = FALLBACK_SHAPES[0]
+    ctx = hip.Context(engines(T.MERGED_MODEL), B, S)
+    try:
+        d_ids = torch.ones((B, S), dtype=torch.int32, device="cuda")
+        d_len = torch.full((B,), S, dtype=torch.int32, device="cuda")
+        d_out = torch.full((B, _tmax(S)), SENTINEL, dtype=torch.int32, device="cuda")
+        d_ol = torch.full((B,), SENTINEL, dtype=torch.int32, device="cuda")
+        with pytest.raises(hip.SlimtHipError, match="shortlist target vocabulary %d != model vocabulary %d" % (Vt, V)):
+            ctx.translate_device_generated(gen, d_ids.data_ptr(), d_len.data_ptr(), B, S, 1.5, 0, d_out.data_ptr(), d_ol.data_ptr())
+        ctx.synchronize()
+        assert (d_out.cpu().numpy() == SENTINEL).all() and (d_ol.cpu().numpy() == SENTINEL).all()
+    finally:
+        gen.close()
+        ctx.close()

@@ -262,3 +262,121 @@ def test_merged_batches_generate_their_own_lexical_shortlists(hip, oracle, engin
         _check(oracle, om, batches, sls, res)
     ctx.close()
     gen.close()
+
+
+# ---- the batch-by-batch fallbacks of slimt_hip_translate_many_async -------------------------------------------------------
+# Batches of 3 and 5 sentences padded to 4 and 7 tokens (two of them, pinned, are one merged launch: the tests above). One
+# pageable array among the pinned ones, or more than eight batches, and every batch goes through the host path of a single
+# call instead -- with the options armed for the whole call handed on batch by batch.
+FALLBACK_SHAPES = [(3, 4), (5, 7)]
+FALLBACK_S = 7
+
+
+def _fallback_inputs(V, n, sl, options):
+    """n batches of FALLBACK_SHAPES in turn; with options per batch a forced prefix of 0..2 listed words and sampling keys"""
+    from slimt_amd import capi, synth
+    shapes = [FALLBACK_SHAPES[j % 2] for j in range(n)]
+    batches = [synth.make_batch(V, B, Sj, seed=600 + j, ragged=True) for j, (B, Sj) in enumerate(shapes)]
+    if not options:
+        return batches, None, None
+    rng = np.random.default_rng(5)
+    words = sl[sl != 0]
+    prefixes, keys = [], []
+    for j, (B, Sj) in enumerate(shapes):
+        T = max(int(np.float32(1.5) * np.float32(Sj)), 1)
+        prefixes.append((rng.choice(words, size=(B, T)).astype(np.uint32), rng.integers(0, 3, size=B).astype(np.uint32)))
+        keys.append(capi.sampling_keys(77, B, first=100 * j))
+    return batches, prefixes, keys
+
+
+def _fallback_buffers(hip, batches, pageable):
+    """per batch (ids, lens, out, out_len, align) and a scores array, pinned; pageable: the last batch's out_len is not"""
+    pins, bufs, scs = [], [], []
+    for j, (ids, lens) in enumerate(batches):
+        B, Sj = ids.shape
+        T = max(int(np.float32(1.5) * np.float32(Sj)), 1)
+        ps = [hip._Pinned() for _ in range(6)]
+        pins += ps
+        b = [ps[0].array(np.uint32, (B, Sj)), ps[1].array(np.uint32, (B,)), ps[2].array(np.uint32, (B, T)),
+             ps[3].array(np.uint32, (B,)), ps[4].array(np.float32, (B, T, Sj))]
+        if pageable and j == len(batches) - 1:
+            b[3] = np.zeros((B,), np.uint32)
+        b[0][...] = ids
+        b[1][...] = lens
+        b[2][...] = 0x5a5a5a5a
+        b[3][...] = 0x5a5a5a5a
+        b[4][...] = np.float32(7.25)
+        sc = ps[5].array(np.float32, (B, T))
+        sc[...] = np.float32(7.5)
+        bufs.append(tuple(b))
+        scs.append(sc)
+    return pins, bufs, scs
+
+
+def _same_as_own_call(b, sc, lens, want):
+    """ids and lengths, the alignment over each sentence's own columns and rows, the scores of its tokens: bit for bit"""
+    assert np.array_equal(b[3], want[1]), (b[3], want[1])
+    assert np.array_equal(b[2], want[0])
+    for r in range(len(lens)):
+        n, L = int(want[1][r]), int(lens[r])
+        assert np.array_equal(b[4][r, :n, :L].view(np.uint32), want[2][r, :n, :L].view(np.uint32)), r
+        if sc is not None:
+            assert np.array_equal(sc[r, :n].view(np.uint32), want[3][r, :n].view(np.uint32)), r
+
+
+@pytest.mark.parametrize("n,pageable,options", [(2, True, False), (9, False, False), (2, True, True), (9, False, True)],
+                         ids=["pageable-array", "nine-batches", "pageable-array-options", "nine-batches-options"])
+def test_async_fallbacks_equal_the_blocking_calls(hip, engines, n, pageable, options):
+    """slimt_hip_translate_many_async batch by batch == slimt_hip_translate of each batch on the same context; with scores, a
+    forced prefix and sampling keys armed together each batch gets its own."""
+    from slimt_amd import synth
+    m, gm, _ = engines("tiny11", 6.0)
+    sl = synth.make_shortlist(m.V, 1024)
+    batches, prefixes, keys = _fallback_inputs(m.V, n, sl, options)
+    ctx = hip.Context(gm, hip.translate_many_rows([ids.shape[0] for ids, _ in batches]), FALLBACK_S)
+    pins, bufs, scs = _fallback_buffers(hip, batches, pageable)
+    try:
+        assert ctx.plan(FALLBACK_S) == (True, True)
+        if options:
+            wants = [ctx.translate(ids, lens, sl, want_align=True, scores=True, prefix=p, sampling=(0.8, k))
+                     for (ids, lens), p, k in zip(batches, prefixes, keys)]
+            ctx.translate_many_async(bufs, sl, scores=scs, prefix=prefixes, sampling=(0.8, keys))
+        else:
+            wants = [ctx.translate(ids, lens, sl, want_align=True) for ids, lens in batches]
+            ctx.translate_many_async(bufs, sl)
+        ctx.synchronize()
+        for b, sc, (_, lens), want in zip(bufs, scs, batches, wants):
+            _same_as_own_call(b, sc if options else None, lens, want)
+    finally:
+        ctx.close()
+        for p in pins:
+            p.free()
+
+
+def test_async_failed_guard_consumes_every_armed_option(hip, engines):
+    """Scores armed for three batches, a prefix and sampling for two, a call of two batches: it fails at the scores, and the
+    next plain call is an ordinary greedy one -- the prefix and the sampling were taken with the scores."""
+    from slimt_amd import synth
+    m, gm, _ = engines("tiny11", 6.0)
+    sl = synth.make_shortlist(m.V, 1024)
+    batches, prefixes, keys = _fallback_inputs(m.V, 2, sl, True)
+    for _, p_len in prefixes:
+        p_len[...] = 2  # (every sentence forced: a prefix left armed would show)
+    ctx = hip.Context(gm, hip.translate_many_rows([ids.shape[0] for ids, _ in batches]), FALLBACK_S)
+    pins, bufs, scs = _fallback_buffers(hip, batches, True)
+    try:
+        wants = [ctx.translate(ids, lens, sl, want_align=True) for ids, lens in batches]
+        ctx.set_scores(scs + [scs[0]])
+        ctx.set_target_prefix(prefixes)
+        ctx.set_sampling(0.8, keys)
+        with pytest.raises(hip.SlimtHipError, match="scores: 3 destinations armed, the call has 2 batches"):
+            ctx.translate_many_async(bufs, sl)
+        ctx.translate_many_async(bufs, sl)
+        ctx.synchronize()
+        for b, sc, (_, lens), want in zip(bufs, scs, batches, wants):
+            _same_as_own_call(b, None, lens, want)
+            assert (sc == np.float32(7.5)).all()
+    finally:
+        ctx.close()
+        for p in pins:
+            p.free()
