@@ -438,7 +438,9 @@ int slimt_hip_host_free(void *p);
  * either), the other sentences' results are not affected. A target prefix
  * (slimt_hip_ctx_set_target_prefix) in device memory is not checked either: a length
  * past Tmax is taken as Tmax, and a prefix id >= the vocabulary leaves that
- * sentence's result undefined and no other sentence's. */
+ * sentence's result undefined and no other sentence's. The row_src of
+ * slimt_hip_translate_fanout_device is not checked either: a value >= B is taken
+ * as B - 1, which leaves that row's result undefined and no other row's. */
 int slimt_hip_translate_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids,
                                const uint32_t *d_lengths, size_t B, size_t S,
                                const uint32_t *d_shortlist, size_t n_shortlist,
@@ -742,6 +744,48 @@ int slimt_hip_candidates_rank(const float *scores, const uint32_t *tgt_len, cons
 int slimt_hip_candidates_rank_device(slimt_hip_ctx *ctx, const float *d_scores, const uint32_t *d_tgt_len,
                                      const uint32_t *d_cand_src, size_t N, size_t T, size_t B, int mode, float *d_totals,
                                      uint32_t *d_best);
+
+/* ---- fan-out: several decoder rows per source from one encoding ------------ */
+/* slimt_hip_translate with N decoder rows over a source batch src_ids [B][S] / lengths [B]: row_src [N] names each
+ * row's source, row_src[r] < B. The B sources are encoded ONCE, their cross-attention K / V are projected and cached
+ * once, and the N rows decode step by step over them -- n samples of a sentence (slimt_hip_ctx_set_sampling) without
+ * repeating its row n times. out_ids [N][Tmax], out_len [N] and the nullable align [N][Tmax][S] are indexed by row; Tmax
+ * follows slimt_hip_translate's rule from S.
+ * The options armed on the context apply as to a call of one batch of N rows: scores [N][Tmax], prefix ids [N][Tmax] and
+ * lengths [N], keys [N] (NULL: row r's key is r); truncation applies as to any sampled call. A fan-out call consumes
+ * what was armed whether it succeeds or fails, like every translate call.
+ * THE CONTRACT: for every row r, every value written -- tokens, out_len, alignment rows, scores -- is bit for bit what
+ * slimt_hip_translate in decode mode 1 writes for row r of the duplicated batch src_ids[row_src], lengths[row_src] with
+ * the same shortlist ids and the same per-row options: greedy, scored, forced, sampled, truncated, sampled + forced. It
+ * holds because every row's arithmetic is independent of its neighbours.
+ * row_src may be in ANY order and a source may have no row. The order affects speed only: the attention stages a
+ * source's K / V once per run of consecutive rows that name it (within 16 rows), so rows sorted by source cost least.
+ * A fan-out call decodes with the per-stage kernels whatever the context's decode mode, which is not changed
+ * (slimt_hip_ctx_plan keeps reporting it; the mode still chooses the encoder); K/V cache format 3 works. Merged launches
+ * (slimt_hip_translate_many_*) of fan-out calls do not exist.
+ * Bounds: B <= max_batch, B * S within the context's padded tokens, and 1 <= N <= max_batch -- the per-row decoder
+ * workspaces (states, step rows, partials) are sized by max_batch when the context is created.
+ * Host calls check every id and length as slimt_hip_translate does, and refuse N = 0 and a row_src[r] >= B with a
+ * message; _async queues the work like slimt_hip_translate_async (pinned or pageable buffers; copies bracket the kernels).
+ * _device takes device pointers like slimt_hip_translate_device (steps_hint as there); device arrays cannot be checked:
+ * a row_src[r] >= B is taken as B - 1 (that row alone is undefined; nothing is read or written out of bounds).
+ * _async_generated generates the lexical shortlist from the B sources GIVEN: a source without rows still contributes its
+ * words to it. */
+int slimt_hip_translate_fanout(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                               const uint32_t *row_src, size_t N, const uint32_t *shortlist, size_t n_shortlist,
+                               float limit_factor, uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align);
+int slimt_hip_translate_fanout_async(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
+                                     size_t S, const uint32_t *row_src, size_t N, const uint32_t *shortlist,
+                                     size_t n_shortlist, float limit_factor, uint32_t eos_id, uint32_t *out_ids,
+                                     uint32_t *out_len, float *align);
+int slimt_hip_translate_fanout_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids, const uint32_t *d_lengths, size_t B,
+                                      size_t S, const uint32_t *d_row_src, size_t N, const uint32_t *d_shortlist,
+                                      size_t n_shortlist, float limit_factor, uint32_t eos_id, uint32_t *d_out_ids,
+                                      uint32_t *d_out_len, float *d_align, int steps_hint);
+int slimt_hip_translate_fanout_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *shortlist,
+                                               const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                                               const uint32_t *row_src, size_t N, float limit_factor, uint32_t eos_id,
+                                               uint32_t *out_ids, uint32_t *out_len, float *align);
 
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, HIP events bracket every launch of kernel family `kernel_id`

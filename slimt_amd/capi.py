@@ -48,6 +48,8 @@ SYMBOLS = [
     "slimt_hip_ctx_set_score_alternatives", "slimt_hip_debug_ctx_shortlists",
     "slimt_hip_score_candidates", "slimt_hip_score_candidates_async", "slimt_hip_score_candidates_device",
     "slimt_hip_score_candidates_async_generated", "slimt_hip_candidates_rank", "slimt_hip_candidates_rank_device",
+    "slimt_hip_translate_fanout", "slimt_hip_translate_fanout_async", "slimt_hip_translate_fanout_device",
+    "slimt_hip_translate_fanout_async_generated",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -278,6 +280,10 @@ def lib():
     L.slimt_hip_score_candidates_async_generated.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, sz, vp, sz, vp, vp]
     L.slimt_hip_candidates_rank.argtypes = [vp, vp, vp, sz, sz, sz, i32, vp, vp]
     L.slimt_hip_candidates_rank_device.argtypes = [vp, vp, vp, vp, sz, sz, sz, i32, vp, vp]
+    L.slimt_hip_translate_fanout.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, sz, f32, u32, vp, vp, vp]
+    L.slimt_hip_translate_fanout_async.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, sz, f32, u32, vp, vp, vp]
+    L.slimt_hip_translate_fanout_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, sz, f32, u32, vp, vp, vp, i32]
+    L.slimt_hip_translate_fanout_async_generated.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, f32, u32, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("slimt_hip_abi_version",):
@@ -858,6 +864,116 @@ class Context:
         self._prefix_keep = []  # (a blocking call: done with its prefix)
         return (out_ids, out_len, align, sc) if scores else (out_ids, out_len, align)
 
+    # ---- fan-out: N decoder rows over B sources encoded once (include/slimt_hip.h, slimt_hip_translate_fanout*) ----
+    def _arm(self, N: int, scores, prefix, sampling, truncation, T: int):
+        """arms a one-batch call's options, shaped by its N rows (right before the call that takes them)"""
+        pre = self._prefix_host(prefix, N, T) if prefix is not None else None
+        if scores is not None:
+            self.set_scores([self._scores_array(scores, N, T)])
+        if pre is not None:
+            self.set_target_prefix([pre])
+        if sampling is not None:
+            sm_t, sm_keys = self._sampling_host(sampling, N)
+            self.set_sampling(sm_t, [sm_keys])
+        if truncation is not None:
+            self.set_sampling_truncation(*truncation)
+
+    def translate_fanout(self, ids, lengths, row_src, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
+                         want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None):
+        """slimt_hip_translate_fanout: translate() with N decoder rows over the B sources ids [B,S] / lengths [B], encoded
+        once; row_src [N] uint32 names each row's source. Returns out_ids [N,Tmax], out_len [N], align [N,Tmax,S] | None
+        (+ scores [N,Tmax]). prefix, sampling, truncation: as in translate(), shaped by N. Every row is bit for bit its row
+        of translate() on ids[row_src], lengths[row_src] in decode mode 1."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        row_src = np.ascontiguousarray(row_src, dtype=np.uint32)
+        if ids.ndim != 2 or lengths.shape != (ids.shape[0],) or row_src.ndim != 1:
+            raise ValueError("translate_fanout: ids [B, S], lengths [B] and row_src [N] expected")
+        (B, S), N = ids.shape, row_src.size
+        T = max(int(np.float32(limit_factor) * np.float32(S)), 1)
+        sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
+        out_ids = np.zeros((N, T), dtype=np.uint32)
+        out_len = np.zeros(N, dtype=np.uint32)
+        align = np.zeros((N, T, S), dtype=np.float32) if want_align else None
+        sc = np.full((N, T), np.nan, dtype=np.float32) if scores else None
+        self._arm(N, sc, prefix, sampling, truncation, T)
+        _chk(lib().slimt_hip_translate_fanout(self.h, _p(ids), _p(lengths), B, S, _p(row_src), N, _p(sl),
+                                              0 if sl is None else sl.size, limit_factor, eos_id, _p(out_ids), _p(out_len),
+                                              _p(align)))
+        self._prefix_keep = []  # (a blocking call: done with its prefix)
+        return (out_ids, out_len, align, sc) if scores else (out_ids, out_len, align)
+
+    def fanout_buffers(self, B: int, S: int, N: int, limit_factor: float = 1.5, want_align: bool = False):
+        """This context's pinned arrays for translate_fanout_async: (ids [B,S], lengths [B], row_src [N], out_ids [N,Tmax],
+        out_len [N], align [N,Tmax,S] | None)."""
+        T = max(int(np.float32(limit_factor) * np.float32(S)), 1)
+        pin = lambda name: self._pinned.setdefault(name, _Pinned())
+        return (pin("fo_ids").array(np.uint32, (B, S)), pin("fo_len").array(np.uint32, (B,)),
+                pin("fo_src").array(np.uint32, (N,)), pin("fo_out").array(np.uint32, (N, T)),
+                pin("fo_ol").array(np.uint32, (N,)), pin("fo_al").array(np.float32, (N, T, S)) if want_align else None)
+
+    def translate_fanout_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
+                               scores=None, prefix=None, sampling=None, truncation=None):
+        """slimt_hip_translate_fanout_async[_generated] on (ids, lengths, row_src, out_ids, out_len, align | None) host arrays
+        (already filled; those of fanout_buffers() are pinned); synchronize() before reading the outputs. scores: a float32
+        [N, Tmax] array; prefix, sampling, truncation: as in translate_async(), shaped by N."""
+        ids, lengths, row_src, out_ids, out_len, align = bufs
+        for a in (ids, lengths, row_src, out_ids, out_len):
+            if a.dtype != np.uint32 or not a.flags.c_contiguous:
+                raise ValueError("translate_fanout_async: C-contiguous uint32 arrays expected")
+        (B, S), N = ids.shape, row_src.size
+        T = max(int(np.float32(limit_factor) * np.float32(S)), 1)
+        if lengths.shape != (B,) or out_ids.shape != (N, T) or out_len.shape != (N,):
+            raise ValueError("translate_fanout_async: mismatched shapes")
+        if align is not None and (align.dtype != np.float32 or align.shape != (N, T, S) or not align.flags.c_contiguous):
+            raise ValueError("translate_fanout_async: a C-contiguous float32 align of shape %s expected" % ((N, T, S),))
+        sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
+        self._arm(N, scores, prefix, sampling, truncation, T)
+        if generator is not None:
+            _chk(lib().slimt_hip_translate_fanout_async_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, _p(row_src),
+                                                                  N, limit_factor, eos_id, _p(out_ids), _p(out_len), _p(align)))
+            return
+        _chk(lib().slimt_hip_translate_fanout_async(self.h, _p(ids), _p(lengths), B, S, _p(row_src), N, _p(sl),
+                                                    0 if sl is None else sl.size, limit_factor, eos_id, _p(out_ids),
+                                                    _p(out_len), _p(align)))
+
+    def translate_fanout_pinned(self, ids, lengths, row_src, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
+                                want_align: bool = False, generator=None, scores: bool = False, prefix=None, sampling=None,
+                                truncation=None):
+        """translate_fanout() through this context's pinned arrays and slimt_hip_translate_fanout_async; returns copies."""
+        ids, row_src = np.asarray(ids), np.asarray(row_src)
+        B, S = ids.shape
+        bufs = self.fanout_buffers(B, S, row_src.size, limit_factor, want_align)
+        bufs[0][...] = ids
+        bufs[1][...] = lengths
+        bufs[2][...] = row_src
+        sc = self._pinned.setdefault("fo_sc", _Pinned()).array(np.float32, bufs[3].shape) if scores else None
+        self.translate_fanout_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix,
+                                    sampling=sampling, truncation=truncation)
+        self.synchronize()
+        out = bufs[3].copy(), bufs[4].copy(), (bufs[5].copy() if want_align else None)
+        return out + (sc.copy(),) if scores else out
+
+    def translate_fanout_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_row_src: int, N: int, d_shortlist: int,
+                                n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int, d_out_len: int,
+                                d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None,
+                                truncation=None):
+        """slimt_hip_translate_fanout_device: device pointers (ints) in and out, like translate_device(); d_row_src [N]
+        uint32 (a value >= B is taken as B - 1), outputs and options shaped by N."""
+        vp = C.c_void_p
+        if scores:  # (armed right before the call that takes it)
+            self.set_scores([scores])
+        if prefix is not None:
+            self.set_target_prefix([prefix])
+        if sampling is not None:  # (temperature, device pointer of the [N] uint64 keys or 0 / None)
+            self.set_sampling(sampling[0], [sampling[1]])
+        if truncation is not None:
+            self.set_sampling_truncation(*truncation)
+        _chk(lib().slimt_hip_translate_fanout_device(self.h, vp(d_ids), vp(d_lengths), B, S, vp(d_row_src), N,
+                                                     vp(d_shortlist) if n_shortlist else None, n_shortlist, limit_factor,
+                                                     eos_id, vp(d_out_ids), vp(d_out_len), vp(d_align) if d_align else None,
+                                                     steps_hint))
+
     @staticmethod
     def _score_host(ids, lengths, tgt_ids, tgt_len):
         """(ids [B,S], lengths [B], tgt_ids [B,T], tgt_len [B]) as C-contiguous uint32 arrays (shapes checked)"""
@@ -1366,6 +1482,8 @@ def host_lib():
     H.slimt_hip_result_alternatives.argtypes = [vp, sz, vp, vp, vp, vp]
     H.slimt_hip_service_score_candidates.argtypes = [vp, vp, vp, sz, vp, vp, vp, C.c_int, vp]  # (include/slimt_hip_service_candidates.h)
     H.slimt_hip_result_candidates.argtypes = [vp, vp, vp]
+    H.slimt_hip_service_translate_samples.argtypes = [vp, vp, vp, sz, sz, C.c_uint64, vp]  # (include/slimt_hip_service_samples.h)
+    H.slimt_hip_result_samples.argtypes = [vp, vp]
     _host_lib = H
     return H
 
@@ -1602,6 +1720,22 @@ class BatchService:
         res = ServiceResult(out, np.repeat(np.diff(offsets).astype(np.int64), np.diff(c_offsets).astype(np.int64)))
         totals, best = res.candidates(len(sentences))
         return res, c_offsets, totals, best
+
+    def translate_samples(self, sentences, n: int, seed: int = 0) -> ServiceResult:
+        """slimt_hip_service_translate_samples: n sampled translations of every sentence from one encoding of it, on a
+        sampling service (temperature=; truncation= applies). The ServiceResult has ONE ENTRY PER SAMPLE -- sample j of
+        sentence i is entry i * n + j, drawn under sampling_key(seed, i * n + j) --, token_scores(e) always filled.
+        Blocking; thread-safe."""
+        tokens, offsets = self._flat(sentences)
+        out = C.c_void_p()
+        if host_lib().slimt_hip_service_translate_samples(self.h, _p(tokens), _p(offsets), offsets.size - 1, int(n),
+                                                          int(seed) & (2 ** 64 - 1), C.byref(out)):
+            raise SlimtHipError(host_lib().slimt_hip_service_last_error().decode())
+        res = ServiceResult(out, np.repeat(np.diff(offsets).astype(np.int64), int(n)))
+        got = C.c_size_t(0)
+        if host_lib().slimt_hip_result_samples(res.h, C.byref(got)) or got.value != int(n):
+            raise SlimtHipError("translate_samples: the result holds %d samples per sentence, not %d" % (got.value, int(n)))
+        return res
 
     def close(self):
         if getattr(self, "h", None):

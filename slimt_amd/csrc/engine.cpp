@@ -55,7 +55,11 @@ static std::atomic<bool> g_hip_called{false};
 // ... and a truncated sampled call (TruncationCall) needs each step's whole row of logits, which only the stage-wise decoder
 // stores. Every decision that hangs on the persistent decoder -- the lean path, pinned arrays read in place, merged launches --
 // asks here; the encoder is chosen as the context's mode says.
-static bool fused_decoder_allowed(const slimt_hip_ctx *c) { return c->decode_mode != 1 && c->model->kv_format != 3 && !c->tr_call; }
+static bool fused_decoder_allowed(const slimt_hip_ctx *c) {
+  return c->decode_mode != 1 && c->model->kv_format != 3 && !c->tr_call && !c->fo_call;
+}
+// The decoder rows of the call in progress: a fan-out call's N (FanoutCall), else one per source.
+static int decoder_rows(const slimt_hip_ctx *c) { return c->fo_call ? c->fo_rows : c->B; }
 
 // The lean path for sources padded to S tokens: the persistent decoder, allowed and compiled for the model, behind a
 // persistent encoder (the fused one, or the per-sentence one of 65..128 tokens).
@@ -1168,7 +1172,7 @@ void ctx_free(slimt_hip_ctx *c) {
                     &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->tr_logits, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag,
-                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank};
+                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage};
   for (auto *b : bufs) b->release();
   free_affine(c->out_sl);
   if (c->n_finished_host) (void)hipHostFree(c->n_finished_host);
@@ -1773,6 +1777,37 @@ struct CallOptions {
   int rc() const { return sc.rc ? sc.rc : pc.rc ? pc.rc : smc.rc ? smc.rc : trc.rc; }
 };
 
+// A fan-out call (slimt_hip_translate_fanout*): N decoder rows over the call's B sources, opened behind the call's
+// CallOptions, whose arrays then count N rows. While fo_call is set fused_decoder_allowed() is false -- the call decodes with
+// the per-stage kernels, whose cross-attention alone looks a row's source up (decode_fanout.hip), and is never merged --
+// and decoder_rows() is N; the context's decode mode is not touched and still chooses the encoder. The entry points point
+// ctx->fo_row_src at memory the kernels read. N is bounded by max_batch: the per-row decoder workspaces are sized by it.
+struct FanoutCall {
+  slimt_hip_ctx *c = nullptr;
+  int rc = 0;
+  FanoutCall(slimt_hip_ctx *ctx, size_t N) {
+    if (!ctx) return;
+    if (N == 0) {
+      rc = fail(-1, "fan-out: no rows (N = 0)");
+      return;
+    }
+    if (N > ctx->max_B) {
+      rc = fail(-1, "fan-out: %zu rows exceed the context's max_batch %zu", N, ctx->max_B);
+      return;
+    }
+    c = ctx;
+    ctx->fo_call = true;
+    ctx->fo_rows = (int)N;
+    ctx->fo_row_src = nullptr;
+  }
+  ~FanoutCall() {
+    if (!c) return;
+    c->fo_call = false;
+    c->fo_rows = 0;
+    c->fo_row_src = nullptr;
+  }
+};
+
 // Batch j of a call that goes batch by batch through a single-batch path: its own destination, prefix and keys where that
 // path looks for the caller's (the *_user fields).
 void arm_batch(slimt_hip_ctx *ctx, float *const *scores, const PrefixCall &pc, const SampleCall &smc, size_t j) {
@@ -2152,7 +2187,7 @@ int decode_setup(slimt_hip_ctx *c, size_t n_sl) {
                          c->shortlist.as<uint32_t>(), m->out_bias.as<float>(), m->out_a_quant,
                          m->wemb_mult, st));
   }
-  HIPCHK(hipMemsetAsync(c->state.p, 0, (size_t)m->Ld * B * D * 4, st));
+  HIPCHK(hipMemsetAsync(c->state.p, 0, (size_t)m->Ld * decoder_rows(c) * D * 4, st));  // (one state per decoder row)
   c->decode_ready = true;
   return 0;
 }
@@ -2178,7 +2213,9 @@ int decoder_layers(slimt_hip_ctx *c, float *d_align, int Tmax, const uint32_t *d
                    float *d_attn_dbg) {
   const slimt_hip_model *m = c->model;
   hipStream_t st = c->stream;
-  const int B = c->B, S = c->S, M = B * S, D = m->D;
+  // B sources, N decoder rows (N = B but in a fan-out call): the K / V planes are M = B S positions apart and, with the
+  // lengths, indexed by the source -- in the cross-attention only; everything else is row-wise
+  const int B = c->B, N = decoder_rows(c), S = c->S, M = B * S, D = m->D;
   float *kv = c->kv.as<float>();
   for (int l = 0; l < m->Ld; ++l) {
     const DecLayerW &L = m->dec[(size_t)l];
@@ -2193,13 +2230,13 @@ int decoder_layers(slimt_hip_ctx *c, float *d_align, int Tmax, const uint32_t *d
       xin.ln_bias = P.ffn_ln.bias.as<float>();
     }
     DSsruArgs s;
-    s.B = B; s.D = D;
+    s.B = N; s.D = D;
     s.x = xin;
     s.wf = L.rnn_f.w; s.w = L.rnn_w.w;
-    s.state = c->state.as<float>() + (size_t)l * B * D;
+    s.state = c->state.as<float>() + (size_t)l * N * D;
     s.h_pre = c->dh.as<float>();
     {
-      ProfScope p(c, SLIMT_HIP_K_SSRU, 2.0 * B * D * D, 2.0 * D * D);
+      ProfScope p(c, SLIMT_HIP_K_SSRU, 2.0 * N * D * D, 2.0 * D * D);
       HIPCHK(launch_dssru(s, st));
     }
     RowSrc h;  // LN(x + relu(c')), Modules.cc:230
@@ -2233,19 +2270,25 @@ int decoder_layers(slimt_hip_ctx *c, float *d_align, int Tmax, const uint32_t *d
       }
     }
     {
-      ProfScope p(c, SLIMT_HIP_K_ATTN_DEC, (double)B * D * D, (double)D * D);
-      HIPCHK(launch_dqattn(a, st));
+      ProfScope p(c, SLIMT_HIP_K_ATTN_DEC, (double)N * D * D, (double)D * D);
+      if (c->fo_call) {  // rows that share sources: a source's K / V staged once per run of its rows (decode_fanout.hip)
+        a.rows = N;
+        a.row_src = c->fo_row_src;
+        HIPCHK(launch_dqattn_fanout(a, st));
+      } else {
+        HIPCHK(launch_dqattn(a, st));
+      }
     }
     // O projection + residual h (Modules.cc:308-314) -> pre-LN rows
     DGemmArgs o;
-    o.B = B; o.D = D;
+    o.B = N; o.D = D;
     o.a_i8 = c->datt8.as<int8_t>();
     o.w = L.attn.o.w;
     o.res = h;
     o.y = c->dout.as<float>();
     o.ldy = D;
     {
-      ProfScope p(c, SLIMT_HIP_K_GEMM_DEC, gemm_macs(B, o.w), gemm_bytes(o.w));
+      ProfScope p(c, SLIMT_HIP_K_GEMM_DEC, gemm_macs(N, o.w), gemm_bytes(o.w));
       HIPCHK(launch_dgemm(o, EPI_PLAIN, st));
     }
     RowSrc ao;  // LN(h + O(...)), Modules.cc:316
@@ -2254,25 +2297,25 @@ int decoder_layers(slimt_hip_ctx *c, float *d_align, int Tmax, const uint32_t *d
     ao.ln_bias = L.attn.ln.bias.as<float>();
     // FFN (Modules.cc:251-257)
     DGemmArgs f1;
-    f1.B = B; f1.D = D;
+    f1.B = N; f1.D = D;
     f1.a = ao;
     f1.w = L.ffn1.w;
     f1.y_i8 = c->df8.as<int8_t>();
     f1.ldy8 = m->F;
     f1.a_quant_out = L.ffn2.w.a_quant;
     {
-      ProfScope p(c, SLIMT_HIP_K_GEMM_DEC, gemm_macs(B, f1.w), gemm_bytes(f1.w));
+      ProfScope p(c, SLIMT_HIP_K_GEMM_DEC, gemm_macs(N, f1.w), gemm_bytes(f1.w));
       HIPCHK(launch_dgemm(f1, EPI_RELU_Q, st));
     }
     DGemmArgs f2;
-    f2.B = B; f2.D = D;
+    f2.B = N; f2.D = D;
     f2.a_i8 = c->df8.as<int8_t>();
     f2.w = L.ffn2.w;
     f2.res = ao;
     f2.y = c->dx_pre.as<float>();
     f2.ldy = D;
     {
-      ProfScope p(c, SLIMT_HIP_K_GEMM_DEC, gemm_macs(B, f2.w), gemm_bytes(f2.w));
+      ProfScope p(c, SLIMT_HIP_K_GEMM_DEC, gemm_macs(N, f2.w), gemm_bytes(f2.w));
       HIPCHK(launch_dgemm(f2, EPI_PLAIN, st));
     }
   }
@@ -2306,6 +2349,9 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   // loop then runs while i < (size_t)(limit_factor * S): at least one output column
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
   const bool lean = persistent_path(c, S);
+  // R decoder rows over the B sources: B, but in a fan-out call (FanoutCall; never lean, never merged). The caller's
+  // outputs, the per-call options and every decoder workspace are per row; ids, lengths, the encoder and the K / V per source.
+  const size_t R = c->fo_call ? (size_t)c->fo_rows : B;
   // packed 24-bit K/V cache: fused encoder -> fused decoder, D = 256 / d_head 32 or D = 512 / d_head 64, S <= 32
   // (V is cached in groups of four keys: S = 1, 2, 5 would not fit the f32 form's plane)
   // ... and for 33..64-token sentences of the D = 256 / F = 1536 shape (64-row encoder, one sentence per workgroup)
@@ -2365,7 +2411,7 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   const bool sampled = c->sm_call;
   const bool scored = c->sc_call || forced || sampled;
   if ((forced || sampled) && !c->sc_call) {
-    HIPCHK(c->fp_scratch.reserve(B * Tmax * 4));
+    HIPCHK(c->fp_scratch.reserve(R * Tmax * 4));
     for (int j = 0; mp && j < mp->n; ++j) mp->scores[j] = c->fp_scratch.as<float>() + (size_t)mp->out[j].first * Tmax;
   }
   float *const d_scores = scored && !mp ? (c->sc_call ? c->sc_dev : c->fp_scratch.as<float>()) : nullptr;
@@ -2428,11 +2474,11 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     d_shortlist = c->shortlist.as<uint32_t>();
     RCCHK(encode_device(c, (int)B, (int)S, nullptr, nullptr));
     RCCHK(decode_setup(c, n_sl));
-    HIPCHK(hipMemsetAsync(d_out_ids, 0, B * (Tmax ? Tmax : 1) * 4, st));
-    HIPCHK(hipMemsetAsync(d_out_len, 0, B * 4, st));
-    HIPCHK(hipMemsetAsync(c->finished.p, 0, B, st));
+    HIPCHK(hipMemsetAsync(d_out_ids, 0, R * (Tmax ? Tmax : 1) * 4, st));
+    HIPCHK(hipMemsetAsync(d_out_len, 0, R * 4, st));
+    HIPCHK(hipMemsetAsync(c->finished.p, 0, R, st));
     HIPCHK(hipMemsetAsync(c->n_finished.p, 0, 16, st));
-    if (d_align) HIPCHK(hipMemsetAsync(d_align, 0, B * Tmax * S * 4, st));
+    if (d_align) HIPCHK(hipMemsetAsync(d_align, 0, R * Tmax * S * 4, st));
   }
   ds.shortlist = n_sl ? d_shortlist : nullptr;
   const AffineW &out = output_layer(c);
@@ -2728,18 +2774,18 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   // a truncated call (TruncationCall) stores each step's logits and selects over them: one partial per row (sample_truncate.hip)
   const bool truncated = sampled && c->tr_call;
   if (c->tr_call && !truncated) return fail(-1, "sampling truncation: the call is not sampled");
-  const int n_parts = truncated ? 1 : dgemm_col_blocks(out.w.K, out.w.N, (int)B);
-  if (truncated) HIPCHK(c->tr_logits.reserve(B * (size_t)out.w.N * 4));
+  const int n_parts = truncated ? 1 : dgemm_col_blocks(out.w.K, out.w.N, (int)R);
+  if (truncated) HIPCHK(c->tr_logits.reserve(R * (size_t)out.w.N * 4));
   const EmbedArgs e = embed_args(c);
-  if (d_scores) HIPCHK(c->part_sum.reserve(B * (size_t)n_parts * 4));
+  if (d_scores) HIPCHK(c->part_sum.reserve(R * (size_t)n_parts * 4));
   float *const part_sum = d_scores ? c->part_sum.as<float>() : nullptr;
   if (forced && mp) return fail(-1, "target prefix: merged launches decode with the persistent kernels only");
   if (sampled && mp) return fail(-1, "sampling: merged launches decode with the persistent kernels only");
   SampledStep ss;  // (sampled: the keys, the steps' hash words and the partials beside the arg-max's, kernels.h)
   if (sampled) {
-    HIPCHK(c->sm_seeds.reserve(2 * B * 4));
-    HIPCHK(c->sm_part_mz.reserve(B * (size_t)n_parts * 4));
-    HIPCHK(c->sm_part_zw.reserve(B * (size_t)n_parts * 4));
+    HIPCHK(c->sm_seeds.reserve(2 * R * 4));
+    HIPCHK(c->sm_part_mz.reserve(R * (size_t)n_parts * 4));
+    HIPCHK(c->sm_part_zw.reserve(R * (size_t)n_parts * 4));
     ss.inv_T = c->sm_inv_T;
     ss.keys = c->sm_keys;
     ss.seeds = c->sm_seeds.as<uint32_t>();
@@ -2748,8 +2794,8 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   }
   ForcedStep fs;  // (forced: the prefix's tokens and their columns, kernels.h)
   if (forced) {
-    HIPCHK(c->fp_col.reserve(B * 4));
-    HIPCHK(c->fp_part_y.reserve(B * (size_t)n_parts * 4));
+    HIPCHK(c->fp_col.reserve(R * 4));
+    HIPCHK(c->fp_part_y.reserve(R * (size_t)n_parts * 4));
     fs.ids = c->fp_ids;
     fs.len = c->fp_len;
     fs.sl = ds.shortlist;
@@ -2762,7 +2808,7 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   size_t t = 0;
   bool all_done = false;
   for (; t < max_steps && !rc; ++t) {
-    hipError_t he = launch_decode_begin_step(e, ds, (int)B, t == 0, 1, c->part_val.as<float>(),
+    hipError_t he = launch_decode_begin_step(e, ds, (int)R, t == 0, 1, c->part_val.as<float>(),
                                              c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs, &ss);
     if (he != hipSuccess) { rc = fail((int)he, "decode_begin_step: %s", hipGetErrorString(he)); break; }
     if (steps_hint <= 0 && t > 0 && (t % 8) == 0) {
@@ -2770,12 +2816,12 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
       he = hipMemcpyAsync(c->n_finished_host, c->n_finished.p, sizeof(int), hipMemcpyDeviceToHost, st);
       if (he == hipSuccess) he = hipStreamSynchronize(st);
       if (he != hipSuccess) { rc = fail((int)he, "early-exit readback: %s", hipGetErrorString(he)); break; }
-      if (*c->n_finished_host >= (int)B) { all_done = true; break; }
+      if (*c->n_finished_host >= (int)R) { all_done = true; break; }
     }
     rc = decoder_layers(c, d_align, (int)Tmax, d_out_len, nullptr);
     if (rc) break;
     DGemmArgs g;
-    g.B = (int)B;
+    g.B = (int)R;
     g.D = m->D;
     g.a = decoder_out_rows(c);
     g.w = out.w;
@@ -2798,14 +2844,14 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
       g.ldy = out.w.N;
     }
     {
-      ProfScope p(c, SLIMT_HIP_K_LOGITS, gemm_macs((int)B, out.w), gemm_bytes(out.w));
+      ProfScope p(c, SLIMT_HIP_K_LOGITS, gemm_macs((int)R, out.w), gemm_bytes(out.w));
       he = launch_dgemm(g, truncated ? EPI_PLAIN : sampled ? EPI_ARGMAX_SM : fs.ids ? EPI_ARGMAX_FP : d_scores ? EPI_ARGMAX_SC : EPI_ARGMAX, st);
     }
     if (he != hipSuccess) { rc = fail((int)he, "logits gemm: %s", hipGetErrorString(he)); break; }
     if (truncated) {
       SampleTruncArgs ta;
       ta.logits = c->tr_logits.as<float>();
-      ta.B = (int)B;
+      ta.B = (int)R;
       ta.N = out.w.N;
       ta.inv_T = ss.inv_T;
       ta.top_k = c->tr_k;
@@ -2824,7 +2870,7 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     }
   }
   if (!rc && !all_done) {
-    hipError_t he = launch_decode_begin_step(e, ds, (int)B, 0, 0, c->part_val.as<float>(),
+    hipError_t he = launch_decode_begin_step(e, ds, (int)R, 0, 0, c->part_val.as<float>(),
                                              c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs, &ss);
     if (he != hipSuccess) rc = fail((int)he, "final record: %s", hipGetErrorString(he));
   }
@@ -2934,9 +2980,15 @@ namespace {
 // then not used): no host shortlist, no upload, no synchronisation in the asynchronous form.
 int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
                    size_t S, const uint32_t *shortlist, size_t n_shortlist, float limit_factor,
-                   uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align, bool wait) {
+                   uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align, bool wait,
+                   const uint32_t *row_src = nullptr) {
   if (!ctx || !src_ids || !lengths || !out_ids || !out_len) return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
+  // a fan-out call (FanoutCall, opened by the entry point): R = N rows named by row_src; every output, option and staging
+  // below is per row, the ids and lengths per source
+  const bool fanout = ctx->fo_call;
+  if (fanout && !row_src) return fail(-1, "null argument");
+  const size_t R = fanout ? (size_t)ctx->fo_rows : B;
   StageClock hclk;
   const slimt_hip_model *m = ctx->model;
   uint32_t vmax = (uint32_t)m->V;
@@ -2977,12 +3029,20 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t 
   const bool persistent = persistent_path(ctx, S);
   hclk.lap(0);
   if (ctx->fp_call) {  // (a forced call: the caller's host prefix, checked and staged in device memory)
-    const size_t Bs[1] = {B}, Ts[1] = {Tmax};
+    const size_t Bs[1] = {R}, Ts[1] = {Tmax};
     RCCHK(prefix_stage(ctx, 1, &ctx->fp_user_ids, &ctx->fp_user_len, Bs, Ts, &ctx->fp_ids, &ctx->fp_len));
   }
   if (ctx->sm_call) {  // (a sampled call: the caller's host keys, pinned in place or staged in device memory)
-    const size_t Bk[1] = {B};
+    const size_t Bk[1] = {R};
     RCCHK(keys_stage(ctx, 1, &ctx->sm_user_keys, Bk, &ctx->sm_keys));
+  }
+  if (fanout) {  // (the rows' sources: a pinned array in place, a pageable one staged in device memory)
+    ctx->fo_row_src = static_cast<const uint32_t *>(host_device_view(row_src));
+    if (!ctx->fo_row_src) {
+      HIPCHK(ctx->fo_stage.reserve(R * 4));
+      HIPCHK(hipMemcpyAsync(ctx->fo_stage.p, row_src, R * 4, hipMemcpyHostToDevice, st));
+      ctx->fo_row_src = ctx->fo_stage.as<uint32_t>();
+    }
   }
   float *const scores = ctx->sc_call ? ctx->sc_user : nullptr;  // (a scored call: the caller's [B][Tmax] host array)
   if (!wait && persistent) {
@@ -3000,10 +3060,10 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t 
                  static_cast<uint32_t *>(v_ol), (int)Tmax, static_cast<float *>(v_al));
     }
   }
-  HIPCHK(ctx->out_ids.reserve(B * Tmax * 4));
-  if (align) HIPCHK(ctx->align.reserve(B * Tmax * S * 4));
+  HIPCHK(ctx->out_ids.reserve(R * Tmax * 4));
+  if (align) HIPCHK(ctx->align.reserve(R * Tmax * S * 4));
   if (scores) {
-    HIPCHK(ctx->sc_stage.reserve(B * Tmax * 4));
+    HIPCHK(ctx->sc_stage.reserve(R * Tmax * 4));
     ctx->sc_dev = ctx->sc_stage.as<float>();
   }
   HIPCHK(hipMemcpyAsync(ctx->ids.p, src_ids, B * S * 4, hipMemcpyHostToDevice, st));
@@ -3012,10 +3072,10 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t 
   // decoder still leaves its loop as soon as every sentence has emitted EOS)
   RCCHK(run(ctx->ids.as<uint32_t>(), ctx->lengths.as<uint32_t>(), ctx->out_ids.as<uint32_t>(), ctx->out_len.as<uint32_t>(),
             wait ? 0 : (int)Tmax, nullptr));
-  HIPCHK(hipMemcpyAsync(out_ids, ctx->out_ids.p, B * Tmax * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(out_len, ctx->out_len.p, B * 4, hipMemcpyDeviceToHost, st));
-  if (align) HIPCHK(hipMemcpyAsync(align, ctx->align.p, B * Tmax * S * 4, hipMemcpyDeviceToHost, st));
-  if (scores) HIPCHK(hipMemcpyAsync(scores, ctx->sc_stage.p, B * Tmax * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(out_ids, ctx->out_ids.p, R * Tmax * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(out_len, ctx->out_len.p, R * 4, hipMemcpyDeviceToHost, st));
+  if (align) HIPCHK(hipMemcpyAsync(align, ctx->align.p, R * Tmax * S * 4, hipMemcpyDeviceToHost, st));
+  if (scores) HIPCHK(hipMemcpyAsync(scores, ctx->sc_stage.p, R * Tmax * 4, hipMemcpyDeviceToHost, st));
   if (wait) RCCHK(slimt_hip_ctx_synchronize(ctx));  // sleeps on a blocking-sync event (a worker per context: no spinning)
   return 0;
 }
@@ -3041,6 +3101,77 @@ extern "C" int slimt_hip_translate_async(slimt_hip_ctx *ctx, const uint32_t *src
   RCCHK(opt.rc());
   return translate_host(ctx, nullptr, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, false);
+}
+
+// ---- fan-out: N decoder rows over B sources encoded once (include/slimt_hip.h, slimt_hip_translate_fanout*) ------------
+// translate_host / translate_device above with the outputs and options counted by row (FanoutCall); decode_fanout.hip has
+// the attention that looks a row's source up.
+namespace {
+int translate_fanout_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
+                          size_t S, const uint32_t *row_src, size_t N, const uint32_t *shortlist, size_t n_shortlist,
+                          float limit_factor, uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align, bool wait) {
+  CallOptions opt(ctx, 1);
+  // (what needs no context is checked first: these refusals say what is wrong with the arguments, context or not)
+  if (N == 0) return fail(-1, "fan-out: no rows (N = 0)");
+  if (!row_src) return fail(-1, "null argument");
+  for (size_t r = 0; r < N; ++r)
+    if (row_src[r] >= B) return fail(-1, "fan-out: row %zu names source %u, the call has %zu", r, row_src[r], B);
+  if (!ctx) return fail(-1, "null argument");
+  RCCHK(opt.rc());
+  FanoutCall fo(ctx, N);
+  RCCHK(fo.rc);
+  return translate_host(ctx, gen, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id, out_ids, out_len, align,
+                        wait, row_src);
+}
+}  // namespace
+
+extern "C" int slimt_hip_translate_fanout(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                                          const uint32_t *row_src, size_t N, const uint32_t *shortlist, size_t n_shortlist,
+                                          float limit_factor, uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align) {
+  return translate_fanout_host(ctx, nullptr, src_ids, lengths, B, S, row_src, N, shortlist, n_shortlist, limit_factor, eos_id,
+                               out_ids, out_len, align, true);
+}
+
+extern "C" int slimt_hip_translate_fanout_async(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
+                                                size_t S, const uint32_t *row_src, size_t N, const uint32_t *shortlist,
+                                                size_t n_shortlist, float limit_factor, uint32_t eos_id, uint32_t *out_ids,
+                                                uint32_t *out_len, float *align) {
+  return translate_fanout_host(ctx, nullptr, src_ids, lengths, B, S, row_src, N, shortlist, n_shortlist, limit_factor, eos_id,
+                               out_ids, out_len, align, false);
+}
+
+extern "C" int slimt_hip_translate_fanout_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *shortlist,
+                                                          const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                                                          const uint32_t *row_src, size_t N, float limit_factor, uint32_t eos_id,
+                                                          uint32_t *out_ids, uint32_t *out_len, float *align) {
+  if (!shortlist) return fail(-1, "null argument");
+  return translate_fanout_host(ctx, shortlist, src_ids, lengths, B, S, row_src, N, nullptr, 0, limit_factor, eos_id, out_ids,
+                               out_len, align, false);
+}
+
+extern "C" int slimt_hip_translate_fanout_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids, const uint32_t *d_lengths,
+                                                 size_t B, size_t S, const uint32_t *d_row_src, size_t N,
+                                                 const uint32_t *d_shortlist, size_t n_shortlist, float limit_factor,
+                                                 uint32_t eos_id, uint32_t *d_out_ids, uint32_t *d_out_len, float *d_align,
+                                                 int steps_hint) {
+  CallOptions opt(ctx, 1);
+  RCCHK(opt.rc());
+  FanoutCall fo(ctx, N);
+  RCCHK(fo.rc);
+  if (!ctx || !d_src_ids || !d_lengths || !d_row_src || !d_out_ids || !d_out_len) return fail(-1, "null argument");
+  RCCHK(check_batch(ctx, B, S));
+  if (n_shortlist > (size_t)ctx->model->V) return fail(-1, "shortlist larger than the vocabulary");
+  if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
+  HIPCHK(hipSetDevice(ctx->model->device));
+  ctx->fo_row_src = d_row_src;
+  if (ctx->sc_call) ctx->sc_dev = ctx->sc_user;  // (device memory, like the other outputs; [N][Tmax])
+  if (ctx->fp_call) {
+    ctx->fp_ids = ctx->fp_user_ids;
+    ctx->fp_len = ctx->fp_user_len;
+  }
+  if (ctx->sm_call) ctx->sm_keys = ctx->sm_user_keys;
+  return translate_device(ctx, d_src_ids, d_lengths, d_shortlist, B, S, n_shortlist, limit_factor, eos_id, d_out_ids, d_out_len,
+                          d_align, steps_hint);
 }
 
 // ---- several batches in one launch pair (include/slimt_hip.h, slimt_hip_translate_many*) ----------------------------

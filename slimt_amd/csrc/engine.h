@@ -225,6 +225,12 @@ struct slimt_hip_ctx {
   uint32_t tr_k = 0;            // ... to the top_k largest (0: no top-k)
   float tr_p = 1.0f;            // ... and the nucleus of mass top_p (1: no top-p)
   slimt_hip::DevBuf tr_logits;  // [B][N] f32: the step's logits, reserved by the first truncated call
+  // fan-out (include/slimt_hip.h, slimt_hip_translate_fanout*): the call in progress decodes fo_rows rows over its B sources
+  // (engine.cpp, FanoutCall): per-stage decoder, never merged, like a truncated call
+  bool fo_call = false;
+  int fo_rows = 0;                      // N <= max_B: the per-row decoder workspaces are sized by max_B
+  const uint32_t *fo_row_src = nullptr;  // [fo_rows] as the kernels read it (device memory)
+  slimt_hip::DevBuf fo_stage;           // device staging of a host call's row_src
   slimt_hip::DevBuf prev, out_ids, out_len, finished, n_finished, align;
   slimt_hip::DevBuf shortlist;
   slimt_hip::DevBuf sl_scratch;  // bitmaps of slimt_hip_shortlist_generate_device (kept zeroed)

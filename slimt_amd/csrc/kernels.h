@@ -306,8 +306,18 @@ struct DQAttnArgs {
   const uint32_t *out_len = nullptr;
   const uint8_t *finished = nullptr;
   int Tmax = 0;
+  // fan-out (launch_dqattn_fanout only): `rows` decoder rows over the B sources. Row r attends over the K / V and the
+  // length of source row_src[r] (device memory, [rows]; a value >= B reads source B - 1); x, out_*, attn, align, out_len
+  // and finished are indexed by the row, k, v and lengths by the source.
+  const uint32_t *row_src = nullptr;
+  int rows = 0;
 };
 hipError_t launch_dqattn(const DQAttnArgs &a, hipStream_t st);
+// The same attention for a translate call whose rows share sources (decode_fanout.hip): each row's float sequence is
+// launch_dqattn's on the duplicated batch; a source's K / V head slice is staged in LDS once per run of consecutive rows
+// that name it. q_given is not supported.
+size_t dqattn_fanout_lds_bytes(int D, int dh, int S);
+hipError_t launch_dqattn_fanout(const DQAttnArgs &a, hipStream_t st);
 
 // ---- merged launches (slimt_hip_translate_many*) -------------------------------
 // Several batches of ONE padded source length share an encoder and a decoder launch: what k concurrent Model::forward

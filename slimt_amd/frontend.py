@@ -74,10 +74,16 @@ class Response:  # Response.hh: source / target with sentence + token ranges, so
     # and their sum (no length normalisation); empty otherwise
     token_scores: List[np.ndarray] = field(default_factory=list)
     sentence_scores: List[float] = field(default_factory=list)
+    # translate(..., samples=n): the n alternatives of this text, each a Response of its own (alternative j holds sample j of
+    # every sentence); this Response is alternative 0. Empty otherwise
+    samples: List["Response"] = field(default_factory=list)
 
     def to(self, encoding: Encoding) -> None:
         self.source.to(encoding)
         self.target.to(encoding)
+        for r in self.samples:
+            if r is not self:
+                r.to(encoding)
 
 
 def _target_boundaries(vocabulary, begin: int, words) -> List[int]:
@@ -257,6 +263,26 @@ class Service:
                 self._engines[(model.id, scores, float(temperature), trunc)] = eng
         return eng
 
+    def _translate_samples(self, model: Model, per_request: List[List[List[int]]], samples: int, sampling, truncation=None):
+        """`samples` histories lists shaped like _translate_segments': list j holds sample j of every segment, drawn from
+        one encoding of the segment under capi.sampling_key(seed, its index in this call's flat list * samples + j)
+        (include/slimt_hip_service_samples.h). Always scored. A segment above ENGINE_LIMIT tokens is refused."""
+        flat = [seg for segs in per_request for seg in segs]
+        if any(len(seg) > self.ENGINE_LIMIT for seg in flat):
+            raise ValueError(f"samples: a segment has more than {self.ENGINE_LIMIT} tokens")
+        out = [[[None] * len(segs) for segs in per_request] for _ in range(samples)]
+        if not flat:
+            return out
+        res = self._engine(model, False, sampling[0], truncation).translate_samples(flat, samples, seed=int(sampling[1]))
+        e = 0
+        for r, segs in enumerate(per_request):
+            for i in range(len(segs)):
+                for j in range(samples):
+                    out[j][r][i] = (res.target(e).tolist(), res.alignment(e).copy(), res.token_scores(e).copy())
+                    e += 1
+        res.close()
+        return out
+
     def _translate_segments(self, model: Model, per_request: List[List[List[int]]], scores: bool = False, sampling=None,
                             truncation=None):
         """per request, per segment: (target ids, alignment, token scores | None). sampling: (temperature, seed) -- one
@@ -376,7 +402,8 @@ class Service:
         return out
 
     def translate(self, model: Model, texts: Sequence[str], html: bool = False,
-                  encoding: Encoding = Encoding.UTF8, scores: bool = False, sampling=None, truncation=None) -> List[Response]:
+                  encoding: Encoding = Encoding.UTF8, scores: bool = False, sampling=None, truncation=None,
+                  samples: Optional[int] = None) -> List[Response]:
         """scores: every Response also carries token_scores (per target sentence, each target token's log-probability,
         EOS included; a wrapped segment's pieces concatenated) and sentence_scores (their sums).
         sampling: (temperature, seed) -- each sentence is one draw from the model at that temperature instead of the
@@ -385,9 +412,24 @@ class Service:
         the draws' log-probabilities at that temperature. A sampled call goes to the engine as one request. Every
         distinct temperature keeps a batching service of its own until close() (_engine).
         truncation: (top_k, top_p) with sampling -- the draws come from the top_k most probable tokens (0: all) and the
-        nucleus of mass top_p (1.0: all) of each step (include/slimt_hip.h, slimt_hip_ctx_set_sampling_truncation)."""
+        nucleus of mass top_p (1.0: all) of each step (include/slimt_hip.h, slimt_hip_ctx_set_sampling_truncation).
+        samples: n >= 1 with sampling -- n draws of every sentence from ONE encoding of it (include/slimt_hip.h,
+        slimt_hip_translate_fanout): each Response carries `samples`, its n alternatives as Responses (alternative j holds
+        sample j of every sentence, always with scores; the Response returned is alternative 0). Sample j of the call's
+        segment i is drawn under capi.sampling_key(seed, i * n + j)."""
         if html:
             raise NotImplementedError("HTML markup transfer is outside the ported path (SURVEY.md §2)")
+        if samples is not None:
+            if sampling is None or int(samples) < 1:
+                raise ValueError("samples: n >= 1, and only with sampling=(temperature, seed)")
+            processed = model.processor.process_many(texts, self.wrap_length, self.workers)
+            per_sample = self._translate_samples(model, [segs for _, segs in processed], int(samples), sampling, truncation)
+            alts = [self._respond_many(model, [src for src, _ in processed], h) for h in per_sample]
+            out = alts[0]
+            for r, resp in enumerate(out):
+                resp.samples = [a[r] for a in alts]
+                resp.to(encoding)
+            return out
         # Large calls go through in chunks of documents, pipelined: while the engine translates chunk k
         # (a C call: no interpreter lock held), this thread splits and tokenises chunk k + 1 and
         # assembles the responses of chunk k - 1. Batches are formed per chunk (as they are per
@@ -487,6 +529,15 @@ class Service:
             out.append((pairs, None if best[i] == 0xFFFFFFFF else int(best[i])))
         res.close()
         return out
+
+    def sample_and_rerank(self, model: Model, sources: Sequence[str], n: int, sampling, truncation=None, mean: bool = False):
+        """translate(samples=n) followed by rerank() of each source's n samples: draws n translations of every source from
+        one encoding of it, then scores them teacher-forced from one encoding again (greedy log-probabilities: the model's
+        own, not the draws' at the sampling temperature). sources: each ONE sentence, as for rerank(). Returns (responses,
+        ranked): translate()'s Responses with their `samples`, and rerank()'s list over the samples' target texts."""
+        responses = self.translate(model, sources, sampling=sampling, truncation=truncation, samples=n)
+        ranked = self.rerank(model, sources, [[a.target.text for a in r.samples] for r in responses], mean=mean)
+        return responses, ranked
 
     def pivot(self, first: Model, second: Model, texts: Sequence[str], html: bool = False,
               scores: bool = False, sampling=None, truncation=None) -> List[Response]:

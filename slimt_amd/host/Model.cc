@@ -256,6 +256,25 @@ void Worker::arm_sampling_truncation(uint32_t top_k, float top_p) {
   if (slimt_hip_ctx_set_sampling_truncation(ctx_, top_k, top_p)) raise("slimt_hip_ctx_set_sampling_truncation");
 }
 
+// (weak, like the scores)
+#pragma weak slimt_hip_translate_fanout
+#pragma weak slimt_hip_translate_fanout_async_generated
+void Worker::translate_fanout(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
+                              const uint32_t *row_src, size_t N, const uint32_t *shortlist, size_t n_shortlist,
+                              float limit_factor, uint32_t *out_ids, uint32_t *out_len, float *align) {
+  if (!slimt_hip_translate_fanout || !slimt_hip_translate_fanout_async_generated)
+    throw std::runtime_error("this engine has no fan-out translate calls");
+  if (generator) {
+    if (slimt_hip_translate_fanout_async_generated(ctx_, generator, ids, lengths, B, S, row_src, N, limit_factor,
+                                                   model_.config().eos_id, out_ids, out_len, align))
+      raise("slimt_hip_translate_fanout_async_generated");
+    wait();
+  } else if (slimt_hip_translate_fanout(ctx_, ids, lengths, B, S, row_src, N, shortlist, n_shortlist, limit_factor,
+                                        model_.config().eos_id, out_ids, out_len, align)) {
+    raise("slimt_hip_translate_fanout");
+  }
+}
+
 void Worker::wait() {
   if (slimt_hip_ctx_synchronize(ctx_)) raise("slimt_hip_ctx_synchronize");
 }

@@ -203,6 +203,14 @@ class Worker {
   void score_candidates(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
                         const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids, const uint32_t *tgt_len,
                         size_t T, const uint32_t *cand_src, size_t N, float *scores, float *align);
+  // slimt_hip_translate_fanout: N decoder rows over the B sources, encoded once -- row_src [N] (< B: row r's source),
+  // out_ids [N][T], out_len [N], align nullable [N][T][S] with T = max(1, (size_t)(limit_factor * S)). What was armed on
+  // the worker applies with arrays of N rows (arm_scores, arm_prefix, arm_sampling, arm_sampling_truncation). Blocking.
+  // generator (nullable): the lexical shortlist of the B sources, generated on the device -- shortlist / n_shortlist are
+  // then not used.
+  void translate_fanout(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
+                        const uint32_t *row_src, size_t N, const uint32_t *shortlist, size_t n_shortlist, float limit_factor,
+                        uint32_t *out_ids, uint32_t *out_len, float *align);
   void wait();
 
  private:

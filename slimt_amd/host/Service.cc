@@ -436,6 +436,96 @@ Service::CandidateScores Service::score_candidates(std::vector<Words> sentences,
   return out;
 }
 
+Histories Service::translate_samples(std::vector<Words> sentences, size_t n, uint64_t seed) {
+  float temperature, top_p;
+  uint32_t top_k;
+  {
+    std::lock_guard<std::mutex> lock(mutex_);  // (set_sampling* write these under it)
+    temperature = config_.temperature;
+    top_k = config_.top_k;
+    top_p = config_.top_p;
+  }
+  if (!(temperature > 0.0f)) throw std::invalid_argument("translate_samples: the service does not sample (set_sampling first)");
+  const size_t max_rows = config_.max_words;  // max_batch of the context below: a batch's rows must fit it
+  if (n == 0 || n > max_rows)
+    throw std::invalid_argument(std::to_string(n) + " samples per sentence: not in 1.." + std::to_string(max_rows));
+  for (const Words &s : sentences) {
+    if (s.empty()) throw std::invalid_argument("empty sentence (a sentence holds at least its EOS)");
+    if (s.size() > longest_)
+      throw std::invalid_argument("sentence of " + std::to_string(s.size()) + " tokens: longer than " +
+                                  std::to_string(longest_) + " (wrap it first)");
+  }
+  const size_t count = sentences.size();
+  Histories results(count * n);
+  if (count == 0) return results;
+  if (count >= (1u << 24)) throw std::invalid_argument("request of more than 2^24 sentences");
+  LengthQueue queue(config_.max_words, longest_);  // the batch-forming rule of translate()
+  for (size_t i = 0; i < count; ++i) {
+    Unit u;
+    u.order = i;
+    u.index = static_cast<uint32_t>(i);
+    u.length = static_cast<uint32_t>(sentences[i].size());
+    queue.push(std::move(u));
+  }
+  std::lock_guard<std::mutex> lock(score_mu_);
+  if (!score_worker_) score_worker_ = std::make_unique<Worker>(*score_model_, config_.max_words, longest_, config_.max_words);
+  const size_t per_call = max_rows / n;  // sentences of one fan-out call: n rows each, at most max_batch rows
+  std::vector<uint32_t> ids, lengths, src, rlen, out_ids, out_len;
+  std::vector<uint64_t> keys;
+  std::vector<float> sc, al;
+  for (;;) {
+    const std::vector<Unit> batch = queue.take();
+    if (batch.empty()) break;
+    size_t S = 1;
+    for (const Unit &u : batch) S = std::max<size_t>(S, u.length);  // (the batch's padded length, however it is split below)
+    const size_t Tmax = static_cast<size_t>(config_.tgt_length_limit_factor * static_cast<float>(S));
+    const size_t T = Tmax ? Tmax : 1;
+    for (size_t b0 = 0; b0 < batch.size(); b0 += per_call) {
+      const size_t B = std::min(per_call, batch.size() - b0), N = B * n;
+      ids.assign(B * S, config_.pad_id);
+      lengths.resize(B);
+      src.resize(N);
+      rlen.resize(N);
+      keys.resize(N);
+      out_ids.assign(N * T, 0);
+      out_len.assign(N, 0);
+      sc.assign(N * T, 0.0f);
+      if (config_.alignments) al.assign(N * T * S, 0.0f);
+      for (size_t b = 0; b < B; ++b) {
+        const size_t i = batch[b0 + b].index;
+        const Words &s = sentences[i];
+        std::copy(s.begin(), s.end(), ids.begin() + static_cast<std::ptrdiff_t>(b * S));
+        lengths[b] = static_cast<uint32_t>(s.size());
+        for (size_t j = 0; j < n; ++j) {  // sorted by source; the key goes by the request's numbering, not by the row
+          src[b * n + j] = static_cast<uint32_t>(b);
+          rlen[b * n + j] = lengths[b];
+          keys[b * n + j] = Worker::sampling_key(seed, static_cast<uint64_t>(i) * n + j);
+        }
+      }
+      const uint64_t *kp = keys.data();
+      float *sp = sc.data();
+      score_worker_->arm_sampling(temperature, &kp, 1);
+      if (top_k != 0 || top_p != 1.0f) score_worker_->arm_sampling_truncation(top_k, top_p);
+      score_worker_->arm_scores(&sp, 1);
+      const bool fixed = config_.shortlist && !score_generator_;
+      score_worker_->translate_fanout(score_generator_, ids.data(), lengths.data(), B, S, src.data(), N,
+                                      fixed ? config_.shortlist->data() : nullptr, fixed ? config_.shortlist->size() : 0,
+                                      config_.tgt_length_limit_factor, out_ids.data(), out_len.data(),
+                                      config_.alignments ? al.data() : nullptr);
+      const uint64_t serial = batches_.fetch_add(1);
+      Histories hs = collect(out_ids.data(), out_len.data(), config_.alignments ? al.data() : nullptr, rlen.data(), N, S, T,
+                             config_.flat_alignments);
+      for (size_t r = 0; r < N; ++r) {
+        const float *row = sc.data() + r * T;
+        hs[r]->scores.assign(row, row + out_len[r]);
+        hs[r]->batch = serial;
+        results[static_cast<size_t>(batch[b0 + r / n].index) * n + r % n] = std::move(hs[r]);
+      }
+    }
+  }
+  return results;
+}
+
 bool Service::set_scores(bool on) {
   std::lock_guard<std::mutex> lock(mutex_);  // (the workers read config_.scores only for batches queued after this)
   if (sequence_ > 0) return false;

@@ -184,6 +184,15 @@ class Service {
     std::vector<uint32_t> best;
   };
   CandidateScores score_candidates(std::vector<Words> sentences, std::vector<std::vector<Words>> candidates, int mode = 0);
+  // n sampled translations of every sentence from ONE encoding of it (include/slimt_hip.h, slimt_hip_translate_fanout), on a
+  // sampling service (set_sampling; set_sampling_truncation applies). Batches are formed by the source-length rule of
+  // translate(); all n rows of a sentence travel in its batch, sorted by source, and a batch of more than max_words / n
+  // sentences goes as several calls at the batch's padded length (n * sentences of a call <= the context's max_batch).
+  // Sample j of sentence i is drawn under slimt_hip_sampling_key(seed, i * n + j), wherever the batcher puts it. Returns
+  // n Hypotheses per sentence, sample j of sentence i at i * n + j, each with its scores (always filled) and alignment rows
+  // as translate() returns them. The context and the mutex are those of score(): synchronous, on the caller's thread.
+  // Throws std::invalid_argument on a greedy service, for n = 0 or n > max_words, an empty sentence or one too long.
+  Histories translate_samples(std::vector<Words> sentences, size_t n, uint64_t seed = 0);
   // per-token scores on or off (ServiceConfig::scores): only before the first translate(); false once one has been made
   bool set_scores(bool on);
   // temperature sampling for every request (include/slimt_hip.h, slimt_hip_ctx_set_sampling; 0: greedy again): only before

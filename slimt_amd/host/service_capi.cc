@@ -13,6 +13,7 @@
 #include "slimt_hip_service.h"
 #include "slimt_hip_service_prefix.h"
 #include "slimt_hip_service_candidates.h"
+#include "slimt_hip_service_samples.h"
 #include "slimt_hip_service_score.h"
 #include "slimt_hip_service_sampling.h"
 #include "slimt_hip_service_scores.h"
@@ -50,6 +51,8 @@ struct slimt_hip_result {
   bool ranked = false;
   std::vector<float> totals;
   std::vector<uint32_t> best;
+  // slimt_hip_service_translate_samples: entries per sentence (0: another kind of result)
+  size_t samples = 0;
 };
 
 extern "C" const char *slimt_hip_service_last_error(void) { return g_err; }
@@ -269,6 +272,34 @@ extern "C" int slimt_hip_result_candidates(const slimt_hip_result *r, const floa
   if (!r->ranked) return fail("result_candidates: not a result of slimt_hip_service_score_candidates");
   if (totals) *totals = r->totals.data();
   if (best) *best = r->best.data();
+  return 0;
+}
+
+extern "C" int slimt_hip_service_translate_samples(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets,
+                                                   size_t n, size_t samples, uint64_t seed, slimt_hip_result **out) {
+  if (!service || !out || (n && (!tokens || !offsets))) return fail("null argument");
+  *out = nullptr;
+  try {
+    std::vector<slimt::Words> sentences(n);
+    for (size_t i = 0; i < n; ++i) {
+      if (offsets[i + 1] < offsets[i]) return fail("offsets decrease at sentence %zu", i);
+      sentences[i].assign(tokens + offsets[i], tokens + offsets[i + 1]);
+    }
+    const slimt::Histories hs = service->service->translate_samples(std::move(sentences), samples, seed);
+    std::unique_ptr<slimt_hip_result> r;
+    if (const int rc = flatten(hs, hs.size(), true, r)) return rc;
+    r->samples = samples;
+    *out = r.release();
+    return 0;
+  } catch (const std::exception &e) {
+    return fail("%s", e.what());
+  }
+}
+
+extern "C" int slimt_hip_result_samples(const slimt_hip_result *r, size_t *samples) {
+  if (!r || !samples) return fail("null argument");
+  if (!r->samples) return fail("result_samples: not a result of slimt_hip_service_translate_samples");
+  *samples = r->samples;
   return 0;
 }
 
