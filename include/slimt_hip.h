@@ -787,6 +787,51 @@ int slimt_hip_translate_fanout_async_generated(slimt_hip_ctx *ctx, slimt_hip_sho
                                                const uint32_t *row_src, size_t N, float limit_factor, uint32_t eos_id,
                                                uint32_t *out_ids, uint32_t *out_len, float *align);
 
+/* ---- consensus: minimum-Bayes-risk pick among each source's rows ---------- */
+/* Of the rows ids [N][T] u32 with lengths len [N] that row_src [N] assigns to B sources (n samples of a sentence, as a
+ * fan-out call returns them), keeps for each source the row that agrees most with the source's other rows: the token
+ * n-gram F score (chrF's formula over token ids). Integer counts and IEEE doubles in a fixed order: host and device agree
+ * bit for bit. With n_c = min(len[c], T), G = max_order in 1..SLIMT_HIP_CONSENSUS_MAX_ORDER and the integer
+ * beta2 = beta^2 in 1..SLIMT_HIP_CONSENSUS_MAX_BETA2 (4: chrF's beta = 2; 1: the balanced F):
+ *   - the g-grams of row c are the sequences ids[c][p .. p + g) for p <= n_c - g; there are c_g(c) = max(n_c - g + 1, 0);
+ *   - M_g(h, r) = the sum over the distinct g-grams x of min(count of x in h, count of x in r): clipped counts, symmetric.
+ *     Tokens are compared as full 32-bit ids;
+ *   - F_g(h, r) = ((1 + beta2) * M_g) / (beta2 * c_g(r) + c_g(h)): both sides exact integers converted to double, one IEEE
+ *     division; an order with c_g(h) = c_g(r) = 0 is skipped;
+ *   - U(h, r) = (F_1 + F_2 + ... over the counted orders, added in ascending g from +0.0) / (the number of counted orders),
+ *     0.0 when no order counts;
+ *   - a row COMPETES when n_c > 0; the references of a competing row h are the other competing rows of its source;
+ *   - utility[h] = (the sum of U(h, r) over h's references in ascending row index, added from +0.0) / (their number); 0.0
+ *     when h has no reference and for a row that does not compete. No NaN arises;
+ *   - best[b] is the lowest competing row h of source b whose utility is >= every other competing row's; 0xFFFFFFFF when the
+ *     source has no competing row.
+ * Rows may name sources in any order: the result depends on the row order only through the two "ascending / lowest row
+ * index" rules. utility [N] f64, best [B] u32. Bounds: B >= 1, 1 <= T <= SLIMT_HIP_CONSENSUS_MAX_T, N <= 65536, at most
+ * SLIMT_HIP_CONSENSUS_MAX_ROWS rows per source (a source's tokens then fit 64 KiB of LDS). N = 0 writes best only.
+ * slimt_hip_consensus_select takes host pointers, is stateless and waits; it refuses, with a message, a source with more
+ * than SLIMT_HIP_CONSENSUS_MAX_ROWS rows, a row_src[c] >= B, a len[c] > T and a max_order or beta2 out of range.
+ * slimt_hip_consensus_select_device runs on ctx's stream over device arrays, which it cannot check: a row_src[c] >= B is
+ * taken as B - 1, a len[c] > T as T, and a source with more than SLIMT_HIP_CONSENSUS_MAX_ROWS rows gets best 0xFFFFFFFF and
+ * utility 0.0 for its rows; nothing is read or written out of bounds. */
+#define SLIMT_HIP_CONSENSUS_MAX_ORDER 4
+#define SLIMT_HIP_CONSENSUS_MAX_BETA2 16
+#define SLIMT_HIP_CONSENSUS_MAX_ROWS 64
+#define SLIMT_HIP_CONSENSUS_MAX_T 256
+int slimt_hip_consensus_select(const uint32_t *ids, const uint32_t *len, const uint32_t *row_src, size_t N, size_t T, size_t B,
+                               int max_order, int beta2, double *utility, uint32_t *best);
+int slimt_hip_consensus_select_device(slimt_hip_ctx *ctx, const uint32_t *d_ids, const uint32_t *d_len,
+                                      const uint32_t *d_row_src, size_t N, size_t T, size_t B, int max_order, int beta2,
+                                      double *d_utility, uint32_t *d_best);
+/* A per-call option in the style of slimt_hip_ctx_set_scores: the NEXT fan-out call (slimt_hip_translate_fanout, _async,
+ * _device, _async_generated) runs the selection over its own out_ids / out_len / row_src (T = its Tmax) on the device,
+ * behind its last decode step, and writes best [B] and utility [N] beside its outputs -- arrays of the same kind as the
+ * call's own outputs (host for the host calls, read after the call or slimt_hip_ctx_synchronize; device for _device).
+ * Every other output of the call is bit for bit what the call writes without the option. The option is consumed by the next
+ * translate call whatever its outcome; a translate call that is not a fan-out call fails with a message when it is armed.
+ * max_order = 0 with both arrays NULL disarms (beta2 is then not looked at). Refused at once: max_order = 0 with an array
+ * given, max_order or beta2 out of range, a NULL array. An armed fan-out call whose Tmax exceeds SLIMT_HIP_CONSENSUS_MAX_T is refused with a message. */
+int slimt_hip_ctx_set_fanout_consensus(slimt_hip_ctx *ctx, int max_order, int beta2, uint32_t *best, double *utility);
+
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, HIP events bracket every launch of kernel family `kernel_id`
  * on the ctx stream; slimt_hip_profile_read returns the number of launches
@@ -801,7 +846,8 @@ enum {
   SLIMT_HIP_K_SSRU = 6,
   SLIMT_HIP_K_DECODE_FUSED = 7, /* persistent whole-loop decoder           */
   SLIMT_HIP_K_ENCODE_FUSED = 8, /* persistent whole-stack encoder          */
-  SLIMT_HIP_K_COUNT = 9
+  SLIMT_HIP_K_CONSENSUS = 9,    /* consensus selection (one launch per call) */
+  SLIMT_HIP_K_COUNT = 10
 };
 int slimt_hip_profile_enable(slimt_hip_ctx *ctx, int kernel_id);
 int slimt_hip_profile_read(slimt_hip_ctx *ctx, uint64_t *launches,

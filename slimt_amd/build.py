@@ -18,7 +18,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 # SLIMT_HIP_LIB: build/load an alternative library file (kernel experiments only)
 LIB_PATH = os.environ.get("SLIMT_HIP_LIB") or os.path.join(LIB_DIR, "libslimt_hip.so")
 
-SOURCES = ["kernels.hip", "gemm_tile.hip", "decode_kernels.hip", "decode_fused.hip", "encode_fused.hip", "encode_wide.hip", "encode_tall.hip", "shortlist.hip", "score_tall.hip", "score_alternatives.hip", "score_candidates.hip", "decode_fanout.hip", "sample_truncate.hip",
+SOURCES = ["kernels.hip", "gemm_tile.hip", "decode_kernels.hip", "decode_fused.hip", "encode_fused.hip", "encode_wide.hip", "encode_tall.hip", "shortlist.hip", "score_tall.hip", "score_alternatives.hip", "score_candidates.hip", "decode_fanout.hip", "consensus.hip", "sample_truncate.hip",
            "engine.cpp"]
 HEADERS = ["kernels.h", "engine.h", "decoder_plan.h", "device_common.h", "scores.h", "sampling.h", "truncation.h", "shortlist_device.h", "decode_attention_packed.inl.h", "decode_rows.h",
            os.path.join(ROOT, "include", "slimt_hip.h")]
@@ -138,7 +138,8 @@ def build_host_lib(force: bool = False) -> str:
         os.path.join(ROOT, "include", "slimt_hip_service_score.h"),
         os.path.join(ROOT, "include", "slimt_hip_service_alternatives.h"),
         os.path.join(ROOT, "include", "slimt_hip_service_candidates.h"),
-        os.path.join(ROOT, "include", "slimt_hip_service_samples.h")]
+        os.path.join(ROOT, "include", "slimt_hip_service_samples.h"),
+        os.path.join(ROOT, "include", "slimt_hip_service_consensus.h")]
     if not force and os.path.exists(HOST_LIB) and all(
             os.path.getmtime(d) <= os.path.getmtime(HOST_LIB) for d in deps):
         return HOST_LIB

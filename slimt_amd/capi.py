@@ -50,9 +50,13 @@ SYMBOLS = [
     "slimt_hip_score_candidates_async_generated", "slimt_hip_candidates_rank", "slimt_hip_candidates_rank_device",
     "slimt_hip_translate_fanout", "slimt_hip_translate_fanout_async", "slimt_hip_translate_fanout_device",
     "slimt_hip_translate_fanout_async_generated",
+    "slimt_hip_consensus_select", "slimt_hip_consensus_select_device", "slimt_hip_ctx_set_fanout_consensus",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
+K_CONSENSUS = 9  # (consensus selection: slimt_hip_consensus_select_device and armed fan-out calls)
+CONSENSUS_MAX_ORDER, CONSENSUS_MAX_BETA2, CONSENSUS_MAX_ROWS, CONSENSUS_MAX_T = 4, 16, 64, 256  # (include/slimt_hip.h)
+NO_ROW = 0xFFFFFFFF  # best[b] of a source without a competing row
 KERNEL_NAMES = {K_GEMM_ENC: "gemm_enc", K_GEMM_DEC: "gemm_dec", K_LOGITS: "logits_argmax",
                 K_ATTN_ENC: "attn_enc", K_ATTN_DEC: "attn_dec", K_SSRU: "ssru"}
 
@@ -284,6 +288,9 @@ def lib():
     L.slimt_hip_translate_fanout_async.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, sz, f32, u32, vp, vp, vp]
     L.slimt_hip_translate_fanout_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, sz, f32, u32, vp, vp, vp, i32]
     L.slimt_hip_translate_fanout_async_generated.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, f32, u32, vp, vp, vp]
+    L.slimt_hip_consensus_select.argtypes = [vp, vp, vp, sz, sz, sz, i32, i32, vp, vp]
+    L.slimt_hip_consensus_select_device.argtypes = [vp, vp, vp, vp, sz, sz, sz, i32, i32, vp, vp]
+    L.slimt_hip_ctx_set_fanout_consensus.argtypes = [vp, i32, i32, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("slimt_hip_abi_version",):
@@ -336,6 +343,23 @@ def candidates_rank(scores, tgt_len, cand_src, B: int, mean: bool = False, mode=
     _chk(lib().slimt_hip_candidates_rank(_p(scores), _p(tgt_len), _p(cand_src), N, T, int(B),
                                          int(bool(mean)) if mode is None else int(mode), _p(totals), _p(best)))
     return totals, best
+
+
+def consensus_select(ids, lengths, row_src, B: int, max_order: int = 4, beta2: int = 4):
+    """slimt_hip_consensus_select: ids [N, T] uint32, lengths [N], row_src [N] (< B). Returns (utility float64 [N] -- each
+    row's mean token n-gram F (orders 1..max_order, integer beta2 = beta^2) against the other non-empty rows of its source --
+    and best uint32 [B] -- per source the lowest row of the largest utility, NO_ROW where no row competes)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    row_src = np.ascontiguousarray(row_src, dtype=np.uint32)
+    if ids.ndim != 2 or lengths.shape != ids.shape[:1] or row_src.shape != ids.shape[:1]:
+        raise ValueError("consensus_select: ids [N, T], lengths [N] and row_src [N] expected, got %s, %s, %s"
+                         % (ids.shape, lengths.shape, row_src.shape))
+    N, T = ids.shape
+    utility, best = np.zeros(N, np.float64), np.zeros(int(B), np.uint32)
+    _chk(lib().slimt_hip_consensus_select(_p(ids), _p(lengths), _p(row_src), N, T, int(B), int(max_order), int(beta2),
+                                          _p(utility), _p(best)))
+    return utility, best
 
 
 def translate_many_rows(sizes) -> int:
@@ -717,6 +741,30 @@ class Context:
         `truncation=(top_k, top_p)` beside `sampling=` and do this."""
         _chk(lib().slimt_hip_ctx_set_sampling_truncation(self.h, int(top_k), float(top_p)))
 
+    def set_fanout_consensus(self, max_order: int, beta2: int, best, utility):
+        """slimt_hip_ctx_set_fanout_consensus: arm the consensus selection for the NEXT fan-out call -- best [B] uint32 and
+        utility [N] float64, as numpy arrays (host calls; kept alive here until the next arming) or addresses (ints: device
+        pointers for the device call). max_order = 0 with no arrays disarms. The translate_fanout* wrappers take
+        `consensus=` and do this."""
+        keep, addr = [], []
+        for a, dt in ((best, np.uint32), (utility, np.float64)):
+            if isinstance(a, np.ndarray):
+                if a.dtype != dt or not a.flags.c_contiguous:
+                    raise ValueError("consensus: C-contiguous uint32 best and float64 utility expected")
+                keep.append(a)
+                addr.append(a.ctypes.data)
+            else:
+                addr.append(int(a) if a else 0)
+        self._consensus_keep = keep
+        _chk(lib().slimt_hip_ctx_set_fanout_consensus(self.h, int(max_order), int(beta2), C.c_void_p(addr[0] or None),
+                                                      C.c_void_p(addr[1] or None)))
+
+    def _arm_consensus(self, consensus, B: int, N: int):
+        """arms a host fan-out call's consensus=(max_order, beta2); returns its (best [B], utility [N]) arrays"""
+        best, utility = np.full(B, NO_ROW, np.uint32), np.zeros(N, np.float64)
+        self.set_fanout_consensus(int(consensus[0]), int(consensus[1]), best, utility)
+        return best, utility
+
     @staticmethod
     def _sampling_host(sampling, B: int):
         """(temperature, keys uint64 [B] | None) of a host call's `sampling=` (shape checked)"""
@@ -879,11 +927,14 @@ class Context:
             self.set_sampling_truncation(*truncation)
 
     def translate_fanout(self, ids, lengths, row_src, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                         want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None):
+                         want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None,
+                         consensus=None):
         """slimt_hip_translate_fanout: translate() with N decoder rows over the B sources ids [B,S] / lengths [B], encoded
         once; row_src [N] uint32 names each row's source. Returns out_ids [N,Tmax], out_len [N], align [N,Tmax,S] | None
         (+ scores [N,Tmax]). prefix, sampling, truncation: as in translate(), shaped by N. Every row is bit for bit its row
-        of translate() on ids[row_src], lengths[row_src] in decode mode 1."""
+        of translate() on ids[row_src], lengths[row_src] in decode mode 1.
+        consensus: (max_order, beta2) -- the call also selects each source's consensus row on the device
+        (slimt_hip_ctx_set_fanout_consensus) and returns, last, best [B] uint32 and utility [N] float64."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
         row_src = np.ascontiguousarray(row_src, dtype=np.uint32)
@@ -897,11 +948,12 @@ class Context:
         align = np.zeros((N, T, S), dtype=np.float32) if want_align else None
         sc = np.full((N, T), np.nan, dtype=np.float32) if scores else None
         self._arm(N, sc, prefix, sampling, truncation, T)
+        cs = self._arm_consensus(consensus, B, N) if consensus is not None else ()
         _chk(lib().slimt_hip_translate_fanout(self.h, _p(ids), _p(lengths), B, S, _p(row_src), N, _p(sl),
                                               0 if sl is None else sl.size, limit_factor, eos_id, _p(out_ids), _p(out_len),
                                               _p(align)))
         self._prefix_keep = []  # (a blocking call: done with its prefix)
-        return (out_ids, out_len, align, sc) if scores else (out_ids, out_len, align)
+        return ((out_ids, out_len, align, sc) if scores else (out_ids, out_len, align)) + tuple(cs)
 
     def fanout_buffers(self, B: int, S: int, N: int, limit_factor: float = 1.5, want_align: bool = False):
         """This context's pinned arrays for translate_fanout_async: (ids [B,S], lengths [B], row_src [N], out_ids [N,Tmax],
@@ -913,10 +965,11 @@ class Context:
                 pin("fo_ol").array(np.uint32, (N,)), pin("fo_al").array(np.float32, (N, T, S)) if want_align else None)
 
     def translate_fanout_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
-                               scores=None, prefix=None, sampling=None, truncation=None):
+                               scores=None, prefix=None, sampling=None, truncation=None, consensus=None):
         """slimt_hip_translate_fanout_async[_generated] on (ids, lengths, row_src, out_ids, out_len, align | None) host arrays
         (already filled; those of fanout_buffers() are pinned); synchronize() before reading the outputs. scores: a float32
-        [N, Tmax] array; prefix, sampling, truncation: as in translate_async(), shaped by N."""
+        [N, Tmax] array; prefix, sampling, truncation: as in translate_async(), shaped by N.
+        consensus: (max_order, beta2) -- returns (best [B] uint32, utility [N] float64), filled like the other outputs."""
         ids, lengths, row_src, out_ids, out_len, align = bufs
         for a in (ids, lengths, row_src, out_ids, out_len):
             if a.dtype != np.uint32 or not a.flags.c_contiguous:
@@ -929,17 +982,19 @@ class Context:
             raise ValueError("translate_fanout_async: a C-contiguous float32 align of shape %s expected" % ((N, T, S),))
         sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
         self._arm(N, scores, prefix, sampling, truncation, T)
+        cs = self._arm_consensus(consensus, B, N) if consensus is not None else None
         if generator is not None:
             _chk(lib().slimt_hip_translate_fanout_async_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, _p(row_src),
                                                                   N, limit_factor, eos_id, _p(out_ids), _p(out_len), _p(align)))
-            return
+            return cs
         _chk(lib().slimt_hip_translate_fanout_async(self.h, _p(ids), _p(lengths), B, S, _p(row_src), N, _p(sl),
                                                     0 if sl is None else sl.size, limit_factor, eos_id, _p(out_ids),
                                                     _p(out_len), _p(align)))
+        return cs
 
     def translate_fanout_pinned(self, ids, lengths, row_src, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
                                 want_align: bool = False, generator=None, scores: bool = False, prefix=None, sampling=None,
-                                truncation=None):
+                                truncation=None, consensus=None):
         """translate_fanout() through this context's pinned arrays and slimt_hip_translate_fanout_async; returns copies."""
         ids, row_src = np.asarray(ids), np.asarray(row_src)
         B, S = ids.shape
@@ -948,18 +1003,19 @@ class Context:
         bufs[1][...] = lengths
         bufs[2][...] = row_src
         sc = self._pinned.setdefault("fo_sc", _Pinned()).array(np.float32, bufs[3].shape) if scores else None
-        self.translate_fanout_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix,
-                                    sampling=sampling, truncation=truncation)
+        cs = self.translate_fanout_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix,
+                                         sampling=sampling, truncation=truncation, consensus=consensus)
         self.synchronize()
         out = bufs[3].copy(), bufs[4].copy(), (bufs[5].copy() if want_align else None)
-        return out + (sc.copy(),) if scores else out
+        return (out + (sc.copy(),) if scores else out) + tuple(cs or ())
 
     def translate_fanout_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_row_src: int, N: int, d_shortlist: int,
                                 n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int, d_out_len: int,
                                 d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None,
-                                truncation=None):
+                                truncation=None, consensus=None):
         """slimt_hip_translate_fanout_device: device pointers (ints) in and out, like translate_device(); d_row_src [N]
-        uint32 (a value >= B is taken as B - 1), outputs and options shaped by N."""
+        uint32 (a value >= B is taken as B - 1), outputs and options shaped by N. consensus: (max_order, beta2, d_best,
+        d_utility) with the device pointers of best [B] uint32 and utility [N] float64."""
         vp = C.c_void_p
         if scores:  # (armed right before the call that takes it)
             self.set_scores([scores])
@@ -969,6 +1025,8 @@ class Context:
             self.set_sampling(sampling[0], [sampling[1]])
         if truncation is not None:
             self.set_sampling_truncation(*truncation)
+        if consensus is not None:
+            self.set_fanout_consensus(*consensus)
         _chk(lib().slimt_hip_translate_fanout_device(self.h, vp(d_ids), vp(d_lengths), B, S, vp(d_row_src), N,
                                                      vp(d_shortlist) if n_shortlist else None, n_shortlist, limit_factor,
                                                      eos_id, vp(d_out_ids), vp(d_out_len), vp(d_align) if d_align else None,
@@ -1219,6 +1277,14 @@ class Context:
         vp = C.c_void_p
         _chk(lib().slimt_hip_candidates_rank_device(self.h, vp(d_scores), vp(d_tgt_len), vp(d_cand_src), N, T, B,
                                                     int(bool(mean)), vp(d_totals), vp(d_best)))
+
+    def consensus_select_device(self, d_ids: int, d_len: int, d_row_src: int, N: int, T: int, B: int, max_order: int,
+                                beta2: int, d_utility: int, d_best: int):
+        """slimt_hip_consensus_select_device: consensus_select over device arrays on this context's stream (utility [N]
+        float64, best [B] uint32), e.g. behind translate_fanout_device."""
+        vp = C.c_void_p
+        _chk(lib().slimt_hip_consensus_select_device(self.h, vp(d_ids), vp(d_len), vp(d_row_src), N, T, B, int(max_order),
+                                                     int(beta2), vp(d_utility), vp(d_best)))
 
     def translate_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int,
                          n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int,
@@ -1484,6 +1550,8 @@ def host_lib():
     H.slimt_hip_result_candidates.argtypes = [vp, vp, vp]
     H.slimt_hip_service_translate_samples.argtypes = [vp, vp, vp, sz, sz, C.c_uint64, vp]  # (include/slimt_hip_service_samples.h)
     H.slimt_hip_result_samples.argtypes = [vp, vp]
+    H.slimt_hip_service_translate_consensus.argtypes = [vp, vp, vp, sz, sz, C.c_uint64, C.c_int, C.c_int, vp]  # (include/slimt_hip_service_consensus.h)
+    H.slimt_hip_result_consensus.argtypes = [vp, vp, vp]
     _host_lib = H
     return H
 
@@ -1562,6 +1630,21 @@ class ServiceResult:
             return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=(count,))
 
         return arr(pt, np.float32, self.n), arr(pb, np.uint32, int(n_sources))
+
+    def consensus(self):
+        """of a BatchService.translate_consensus result (slimt_hip_result_consensus): (utility float64 [entries] -- the
+        winner's utility among its sentence's samples --, sample_index uint32 [entries] -- its index j among them); views
+        valid while this object lives"""
+        pu, pj = C.c_void_p(), C.c_void_p()
+        if host_lib().slimt_hip_result_consensus(self.h, C.byref(pu), C.byref(pj)):
+            raise SlimtHipError(host_lib().slimt_hip_service_last_error().decode())
+
+        def arr(p, dtype):
+            if not self.n or not p.value:
+                return np.zeros(0, dtype)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=(self.n,))
+
+        return arr(pu, np.float64), arr(pj, np.uint32)
 
     def token_scores(self, i: int) -> np.ndarray:
         """sentence i's per-token log-probabilities (EOS included); the service must score"""
@@ -1736,6 +1819,21 @@ class BatchService:
         if host_lib().slimt_hip_result_samples(res.h, C.byref(got)) or got.value != int(n):
             raise SlimtHipError("translate_samples: the result holds %d samples per sentence, not %d" % (got.value, int(n)))
         return res
+
+    def translate_consensus(self, sentences, n: int, seed: int = 0, max_order: int = 4, beta2: int = 4):
+        """slimt_hip_service_translate_consensus: translate_samples(sentences, n, seed) followed by the consensus pick among
+        each sentence's n samples, made on the device behind the fan-out call (no second encoding, no scorer pass). Returns
+        (ServiceResult with ONE ENTRY PER SENTENCE -- the winning sample, token_scores(i) filled --, utility float64
+        [sentences], sample_index uint32 [sentences]): entry i is entry i * n + sample_index[i] of translate_samples with the
+        same seed. n <= 64. Blocking; thread-safe."""
+        tokens, offsets = self._flat(sentences)
+        out = C.c_void_p()
+        if host_lib().slimt_hip_service_translate_consensus(self.h, _p(tokens), _p(offsets), offsets.size - 1, int(n),
+                                                            int(seed) & (2 ** 64 - 1), int(max_order), int(beta2), C.byref(out)):
+            raise SlimtHipError(host_lib().slimt_hip_service_last_error().decode())
+        res = ServiceResult(out, np.diff(offsets).astype(np.int64))
+        utility, index = res.consensus()
+        return res, utility, index
 
     def close(self):
         if getattr(self, "h", None):

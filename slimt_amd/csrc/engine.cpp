@@ -1172,7 +1172,7 @@ void ctx_free(slimt_hip_ctx *c) {
                     &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->tr_logits, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag,
-                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage};
+                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage, &c->cs_stage};
   for (auto *b : bufs) b->release();
   free_affine(c->out_sl);
   if (c->n_finished_host) (void)hipHostFree(c->n_finished_host);
@@ -1429,6 +1429,23 @@ extern "C" int slimt_hip_ctx_set_sampling_truncation(slimt_hip_ctx *ctx, uint32_
   ctx->tr_next_k = top_k;
   ctx->tr_next_p = top_p;
   ctx->tr_armed = top_k != 0 || top_p != 1.0f;  // (both off: nothing armed, the call is today's sampled call)
+  return 0;
+}
+
+extern "C" int slimt_hip_ctx_set_fanout_consensus(slimt_hip_ctx *ctx, int max_order, int beta2, uint32_t *best, double *utility) {
+  // (the values first, like the temperature)
+  if (max_order == 0 && (best || utility)) return fail(-1, "consensus: max_order 0 disarms and takes no arrays");
+  if (max_order < 0 || max_order > SLIMT_HIP_CONSENSUS_MAX_ORDER)
+    return fail(-1, "consensus: max_order %d is not in 1..%d", max_order, SLIMT_HIP_CONSENSUS_MAX_ORDER);
+  if (max_order && (beta2 < 1 || beta2 > SLIMT_HIP_CONSENSUS_MAX_BETA2))
+    return fail(-1, "consensus: beta2 %d is not in 1..%d", beta2, SLIMT_HIP_CONSENSUS_MAX_BETA2);
+  if (max_order && (!best || !utility)) return fail(-1, "consensus: best or utility is NULL");
+  if (!ctx) return fail(-1, "null argument");
+  ctx->cs_next_order = max_order;
+  ctx->cs_next_beta2 = beta2;
+  ctx->cs_next_best = best;
+  ctx->cs_next_util = utility;
+  ctx->cs_armed = max_order > 0;  // (0: nothing armed)
   return 0;
 }
 
@@ -1765,16 +1782,48 @@ struct TruncationCall {
   }
 };
 
-// What a translate entry point opens with: the four guards, constructed in this order (TruncationCall reads sm_call, which
+// The consensus selection armed on a context (slimt_hip_ctx_set_fanout_consensus), taken by the next translate entry point,
+// whether it then succeeds or fails; only a fan-out call can use it, any other call that finds it armed fails. The entry
+// points point ctx->cs_dev_best / cs_dev_util at memory the kernel writes: the caller's arrays for the _device call, else
+// the context's staging (translate_host copies it out behind the kernels).
+struct ConsensusCall {
+  slimt_hip_ctx *c = nullptr;
+  int rc = 0;
+  ConsensusCall(slimt_hip_ctx *ctx, bool fanout) {
+    if (!ctx || !ctx->cs_armed) return;
+    ctx->cs_armed = false;
+    if (!fanout) {
+      rc = fail(-1, "consensus: armed on a translate call that is not a fan-out call (slimt_hip_translate_fanout*)");
+      return;
+    }
+    c = ctx;
+    ctx->cs_call = true;
+    ctx->cs_order = ctx->cs_next_order;
+    ctx->cs_beta2 = ctx->cs_next_beta2;
+    ctx->cs_user_best = ctx->cs_next_best;
+    ctx->cs_user_util = ctx->cs_next_util;
+    ctx->cs_dev_best = nullptr;
+    ctx->cs_dev_util = nullptr;
+  }
+  ~ConsensusCall() {
+    if (!c) return;
+    c->cs_call = false;
+    c->cs_user_best = c->cs_dev_best = nullptr;
+    c->cs_user_util = c->cs_dev_util = nullptr;
+  }
+};
+
+// What a translate entry point opens with: the five guards, constructed in this order (TruncationCall reads sm_call, which
 // SampleCall sets) and all of them whatever the earlier ones found -- what was armed is consumed whether or not the call
-// succeeds. n: the batches of the call. rc(): the first guard's that refused.
+// succeeds. n: the batches of the call; fanout: a fan-out entry point. rc(): the first guard's that refused.
 struct CallOptions {
   ScoreCall sc;
   PrefixCall pc;
   SampleCall smc;
   TruncationCall trc;
-  CallOptions(slimt_hip_ctx *ctx, size_t n) : sc(ctx, n), pc(ctx, n), smc(ctx, n), trc(ctx) {}
-  int rc() const { return sc.rc ? sc.rc : pc.rc ? pc.rc : smc.rc ? smc.rc : trc.rc; }
+  ConsensusCall csc;
+  CallOptions(slimt_hip_ctx *ctx, size_t n, bool fanout = false) : sc(ctx, n), pc(ctx, n), smc(ctx, n), trc(ctx), csc(ctx, fanout) {}
+  int rc() const { return sc.rc ? sc.rc : pc.rc ? pc.rc : smc.rc ? smc.rc : trc.rc ? trc.rc : csc.rc; }
 };
 
 // A fan-out call (slimt_hip_translate_fanout*): N decoder rows over the call's B sources, opened behind the call's
@@ -2352,6 +2401,11 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   // R decoder rows over the B sources: B, but in a fan-out call (FanoutCall; never lean, never merged). The caller's
   // outputs, the per-call options and every decoder workspace are per row; ids, lengths, the encoder and the K / V per source.
   const size_t R = c->fo_call ? (size_t)c->fo_rows : B;
+  if (c->cs_call) {  // (ConsensusCall: a fan-out call; the selection runs behind the last step, below)
+    if (!c->fo_call || !c->cs_dev_best || !c->cs_dev_util) return fail(-1, "consensus: not a fan-out call");
+    if (Tmax > (size_t)SLIMT_HIP_CONSENSUS_MAX_T)
+      return fail(-1, "consensus: the call's Tmax %zu exceeds %d", Tmax, SLIMT_HIP_CONSENSUS_MAX_T);
+  }
   // packed 24-bit K/V cache: fused encoder -> fused decoder, D = 256 / d_head 32 or D = 512 / d_head 64, S <= 32
   // (V is cached in groups of four keys: S = 1, 2, 5 would not fit the f32 form's plane)
   // ... and for 33..64-token sentences of the D = 256 / F = 1536 shape (64-row encoder, one sentence per workgroup)
@@ -2874,6 +2928,22 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
                                              c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs, &ss);
     if (he != hipSuccess) rc = fail((int)he, "final record: %s", hipGetErrorString(he));
   }
+  if (!rc && c->cs_call) {  // the selection over the rows just written (consensus.hip): one launch behind the last step
+    ConsensusArgs ca;
+    ca.ids = d_out_ids;
+    ca.len = d_out_len;
+    ca.row_src = c->fo_row_src;
+    ca.N = (uint32_t)R;
+    ca.T = (uint32_t)Tmax;
+    ca.B = (uint32_t)B;
+    ca.max_order = c->cs_order;
+    ca.beta2 = c->cs_beta2;
+    ca.utility = c->cs_dev_util;
+    ca.best = c->cs_dev_best;
+    ProfScope p(c, SLIMT_HIP_K_CONSENSUS, 0, 0);
+    const hipError_t he = launch_consensus(ca, st);
+    if (he != hipSuccess) rc = fail((int)he, "consensus: %s", hipGetErrorString(he));
+  }
   return rc;
 }
 
@@ -3044,6 +3114,11 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t 
       ctx->fo_row_src = ctx->fo_stage.as<uint32_t>();
     }
   }
+  if (ctx->cs_call) {  // (a fan-out call with the selection armed: utility [R] f64, then best [B] u32, staged on the device)
+    HIPCHK(ctx->cs_stage.reserve(R * 8 + B * 4));
+    ctx->cs_dev_util = ctx->cs_stage.as<double>();
+    ctx->cs_dev_best = reinterpret_cast<uint32_t *>(ctx->cs_stage.as<char>() + R * 8);
+  }
   float *const scores = ctx->sc_call ? ctx->sc_user : nullptr;  // (a scored call: the caller's [B][Tmax] host array)
   if (!wait && persistent) {
     void *v_ids = host_device_view(src_ids), *v_len = host_device_view(lengths), *v_out = host_device_view(out_ids),
@@ -3076,6 +3151,10 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t 
   HIPCHK(hipMemcpyAsync(out_len, ctx->out_len.p, R * 4, hipMemcpyDeviceToHost, st));
   if (align) HIPCHK(hipMemcpyAsync(align, ctx->align.p, R * Tmax * S * 4, hipMemcpyDeviceToHost, st));
   if (scores) HIPCHK(hipMemcpyAsync(scores, ctx->sc_stage.p, R * Tmax * 4, hipMemcpyDeviceToHost, st));
+  if (ctx->cs_call) {
+    HIPCHK(hipMemcpyAsync(ctx->cs_user_util, ctx->cs_dev_util, R * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ctx->cs_user_best, ctx->cs_dev_best, B * 4, hipMemcpyDeviceToHost, st));
+  }
   if (wait) RCCHK(slimt_hip_ctx_synchronize(ctx));  // sleeps on a blocking-sync event (a worker per context: no spinning)
   return 0;
 }
@@ -3110,7 +3189,7 @@ namespace {
 int translate_fanout_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
                           size_t S, const uint32_t *row_src, size_t N, const uint32_t *shortlist, size_t n_shortlist,
                           float limit_factor, uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align, bool wait) {
-  CallOptions opt(ctx, 1);
+  CallOptions opt(ctx, 1, true);
   // (what needs no context is checked first: these refusals say what is wrong with the arguments, context or not)
   if (N == 0) return fail(-1, "fan-out: no rows (N = 0)");
   if (!row_src) return fail(-1, "null argument");
@@ -3154,7 +3233,7 @@ extern "C" int slimt_hip_translate_fanout_device(slimt_hip_ctx *ctx, const uint3
                                                  const uint32_t *d_shortlist, size_t n_shortlist, float limit_factor,
                                                  uint32_t eos_id, uint32_t *d_out_ids, uint32_t *d_out_len, float *d_align,
                                                  int steps_hint) {
-  CallOptions opt(ctx, 1);
+  CallOptions opt(ctx, 1, true);
   RCCHK(opt.rc());
   FanoutCall fo(ctx, N);
   RCCHK(fo.rc);
@@ -3164,6 +3243,10 @@ extern "C" int slimt_hip_translate_fanout_device(slimt_hip_ctx *ctx, const uint3
   if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
   HIPCHK(hipSetDevice(ctx->model->device));
   ctx->fo_row_src = d_row_src;
+  if (ctx->cs_call) {  // (device memory, like the other outputs: best [B], utility [N])
+    ctx->cs_dev_best = ctx->cs_user_best;
+    ctx->cs_dev_util = ctx->cs_user_util;
+  }
   if (ctx->sc_call) ctx->sc_dev = ctx->sc_user;  // (device memory, like the other outputs; [N][Tmax])
   if (ctx->fp_call) {
     ctx->fp_ids = ctx->fp_user_ids;
@@ -4482,5 +4565,84 @@ extern "C" int slimt_hip_candidates_rank_device(slimt_hip_ctx *ctx, const float 
   RCCHK(score_reserve(ctx, ctx->cand_rank, B * 8));
   HIPCHK(launch_candidates_rank(candidates_rank_args(d_scores, d_tgt_len, d_cand_src, N, T, B, mode, d_totals, d_best,
                                                      ctx->cand_rank.as<unsigned long long>()), ctx->stream));
+  return 0;
+}
+
+// ---- consensus selection among each source's rows (include/slimt_hip.h, slimt_hip_consensus_select*; consensus.hip) --------
+static_assert(kConsensusMaxOrder == SLIMT_HIP_CONSENSUS_MAX_ORDER && kConsensusMaxRows == SLIMT_HIP_CONSENSUS_MAX_ROWS &&
+                  kConsensusMaxT == SLIMT_HIP_CONSENSUS_MAX_T && kConsensusMaxBeta2 == SLIMT_HIP_CONSENSUS_MAX_BETA2,
+              "include/slimt_hip.h and kernels.h disagree on the consensus limits");
+namespace {
+int consensus_check(const void *ids, const void *len, const void *row_src, size_t N, size_t T, size_t B, int max_order, int beta2,
+                    const void *utility, const void *best) {
+  if (max_order < 1 || max_order > SLIMT_HIP_CONSENSUS_MAX_ORDER)
+    return fail(-1, "consensus: max_order %d is not in 1..%d", max_order, SLIMT_HIP_CONSENSUS_MAX_ORDER);
+  if (beta2 < 1 || beta2 > SLIMT_HIP_CONSENSUS_MAX_BETA2)
+    return fail(-1, "consensus: beta2 %d is not in 1..%d", beta2, SLIMT_HIP_CONSENSUS_MAX_BETA2);
+  if (!best || (N && (!ids || !len || !row_src || !utility))) return fail(-1, "null argument");
+  if (B == 0 || B > 0x7fffffffu) return fail(-1, "consensus: %zu sources", B);
+  if (T == 0 || T > (size_t)SLIMT_HIP_CONSENSUS_MAX_T || N > kConsensusMaxN)
+    return fail(-1, "consensus: %zu rows of %zu tokens exceed the limits (1 <= T <= %d, N <= %u)", N, T,
+                SLIMT_HIP_CONSENSUS_MAX_T, kConsensusMaxN);
+  return 0;
+}
+
+ConsensusArgs consensus_args(const uint32_t *ids, const uint32_t *len, const uint32_t *row_src, size_t N, size_t T, size_t B,
+                             int max_order, int beta2, double *utility, uint32_t *best) {
+  ConsensusArgs a;
+  a.ids = ids;
+  a.len = len;
+  a.row_src = row_src;
+  a.N = (uint32_t)N;
+  a.T = (uint32_t)T;
+  a.B = (uint32_t)B;
+  a.max_order = max_order;
+  a.beta2 = beta2;
+  a.utility = utility;
+  a.best = best;
+  return a;
+}
+}  // namespace
+
+extern "C" int slimt_hip_consensus_select(const uint32_t *ids, const uint32_t *len, const uint32_t *row_src, size_t N, size_t T,
+                                          size_t B, int max_order, int beta2, double *utility, uint32_t *best) {
+  RCCHK(consensus_check(ids, len, row_src, N, T, B, max_order, beta2, utility, best));
+  {
+    std::map<uint32_t, uint32_t> rows;  // (N <= 65536 entries, whatever B)
+    for (size_t c = 0; c < N; ++c) {
+      if (row_src[c] >= B) return fail(-1, "consensus: row %zu names source %u of %zu", c, row_src[c], B);
+      if (len[c] > T) return fail(-1, "consensus: length %u of row %zu > T %zu", len[c], c, T);
+      if (++rows[row_src[c]] > (uint32_t)SLIMT_HIP_CONSENSUS_MAX_ROWS)
+        return fail(-1, "consensus: source %u has more than %d rows", row_src[c], SLIMT_HIP_CONSENSUS_MAX_ROWS);
+    }
+  }
+  Tmp3 t;
+  hipStream_t st = nullptr;
+  HIPCHK(t.a.reserve(std::max<size_t>(1, N * T) * 4));
+  HIPCHK(t.b.reserve(std::max<size_t>(1, N) * 4));
+  HIPCHK(t.c.reserve(std::max<size_t>(1, N) * 4));
+  HIPCHK(t.d.reserve(std::max<size_t>(1, N) * 8));
+  HIPCHK(t.e.reserve(B * 4));
+  if (N) {
+    HIPCHK(hipMemcpyAsync(t.a.p, ids, N * T * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(t.b.p, len, N * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(t.c.p, row_src, N * 4, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(launch_consensus(consensus_args(t.a.as<uint32_t>(), t.b.as<uint32_t>(), t.c.as<uint32_t>(), N, T, B, max_order, beta2,
+                                         t.d.as<double>(), t.e.as<uint32_t>()), st));
+  if (N) HIPCHK(hipMemcpyAsync(utility, t.d.p, N * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(best, t.e.p, B * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+extern "C" int slimt_hip_consensus_select_device(slimt_hip_ctx *ctx, const uint32_t *d_ids, const uint32_t *d_len,
+                                                 const uint32_t *d_row_src, size_t N, size_t T, size_t B, int max_order,
+                                                 int beta2, double *d_utility, uint32_t *d_best) {
+  RCCHK(consensus_check(d_ids, d_len, d_row_src, N, T, B, max_order, beta2, d_utility, d_best));
+  if (!ctx) return fail(-1, "null argument");
+  HIPCHK(hipSetDevice(ctx->model->device));
+  ProfScope p(ctx, SLIMT_HIP_K_CONSENSUS, 0, 0);
+  HIPCHK(launch_consensus(consensus_args(d_ids, d_len, d_row_src, N, T, B, max_order, beta2, d_utility, d_best), ctx->stream));
   return 0;
 }

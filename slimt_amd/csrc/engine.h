@@ -231,6 +231,13 @@ struct slimt_hip_ctx {
   int fo_rows = 0;                      // N <= max_B: the per-row decoder workspaces are sized by max_B
   const uint32_t *fo_row_src = nullptr;  // [fo_rows] as the kernels read it (device memory)
   slimt_hip::DevBuf fo_stage;           // device staging of a host call's row_src
+  // consensus (include/slimt_hip.h, slimt_hip_ctx_set_fanout_consensus): armed for the next fan-out call, taken by its
+  // ConsensusCall (engine.cpp) like the scores; cs_dev_* are the arrays the kernel writes (the caller's, or cs_stage)
+  bool cs_armed = false, cs_call = false;
+  int cs_next_order = 0, cs_next_beta2 = 0, cs_order = 0, cs_beta2 = 0;
+  uint32_t *cs_next_best = nullptr, *cs_user_best = nullptr, *cs_dev_best = nullptr;
+  double *cs_next_util = nullptr, *cs_user_util = nullptr, *cs_dev_util = nullptr;
+  slimt_hip::DevBuf cs_stage;  // device staging of a host call's utility [N] f64 + best [B] u32
   slimt_hip::DevBuf prev, out_ids, out_len, finished, n_finished, align;
   slimt_hip::DevBuf shortlist;
   slimt_hip::DevBuf sl_scratch;  // bitmaps of slimt_hip_shortlist_generate_device (kept zeroed)

@@ -726,6 +726,28 @@ struct CandRankArgs {
 };
 hipError_t launch_candidates_rank(const CandRankArgs &a, hipStream_t st);
 
+// ---- consensus selection among each source's rows (consensus.hip; slimt_hip_consensus_select*) -----------------------------
+// utility [N] / best [B] as include/slimt_hip.h defines them: one workgroup per source finds its rows in row_src, stages
+// their tokens in LDS and counts the clipped n-gram matches of every unordered pair once. Device arrays are not checked:
+// row_src is clamped to B - 1, len to T; a source with more than kConsensusMaxRows rows gets best 0xFFFFFFFF, utility 0.
+constexpr int kConsensusMaxOrder = 4;   // == SLIMT_HIP_CONSENSUS_MAX_ORDER (engine.cpp asserts these)
+constexpr int kConsensusMaxRows = 64;   // == SLIMT_HIP_CONSENSUS_MAX_ROWS
+constexpr int kConsensusMaxT = 256;     // == SLIMT_HIP_CONSENSUS_MAX_T
+constexpr int kConsensusMaxBeta2 = 16;  // == SLIMT_HIP_CONSENSUS_MAX_BETA2
+constexpr uint32_t kConsensusMaxN = 65536;
+struct ConsensusArgs {
+  const uint32_t *ids = nullptr;      // [N][T]
+  const uint32_t *len = nullptr;      // [N], clamped to T
+  const uint32_t *row_src = nullptr;  // [N], clamped to B - 1
+  uint32_t N = 0, T = 0, B = 0;
+  int max_order = 0, beta2 = 0;
+  int lds_rows = 0;  // (set by launch_consensus) rows the LDS image holds: min(N, kConsensusMaxRows)
+  double *utility = nullptr;  // [N]; may be NULL when N = 0
+  uint32_t *best = nullptr;   // [B]
+};
+size_t consensus_lds_bytes(int rows, int T);
+hipError_t launch_consensus(const ConsensusArgs &a, hipStream_t st);
+
 // ---- truncated sampling: top-k / nucleus selection over stored logits (sample_truncate.hip) -------------------------------
 // One sampled step of B rows whose output-layer logits [B][N] are in memory (the logits gemm with EPI_PLAIN): the kept set
 // of include/slimt_hip.h (slimt_hip_ctx_set_sampling_truncation; truncation.h) and, over it, one partial per row in

@@ -77,6 +77,10 @@ class Response:  # Response.hh: source / target with sentence + token ranges, so
     # translate(..., samples=n): the n alternatives of this text, each a Response of its own (alternative j holds sample j of
     # every sentence); this Response is alternative 0. Empty otherwise
     samples: List["Response"] = field(default_factory=list)
+    # sample_and_select(): per sentence (segment) of this text, the winning sample's utility among the segment's samples and
+    # its index j among them; empty otherwise
+    utility: List[float] = field(default_factory=list)
+    sample_index: List[int] = field(default_factory=list)
 
     def to(self, encoding: Encoding) -> None:
         self.source.to(encoding)
@@ -538,6 +542,39 @@ class Service:
         responses = self.translate(model, sources, sampling=sampling, truncation=truncation, samples=n)
         ranked = self.rerank(model, sources, [[a.target.text for a in r.samples] for r in responses], mean=mean)
         return responses, ranked
+
+    def sample_and_select(self, model: Model, sources: Sequence[str], n: int, sampling, truncation=None, max_order: int = 4,
+                          beta2: int = 4, encoding: Encoding = Encoding.UTF8) -> List[Response]:
+        """translate(samples=n) followed by the consensus (minimum-Bayes-risk) pick: of the n draws of every sentence, the one
+        that agrees most with the others -- the mean token n-gram F (orders 1..max_order, integer beta2 = beta^2; 4 is chrF's)
+        against the sentence's other draws (include/slimt_hip.h, slimt_hip_consensus_select). The pick is made on the device
+        behind the fan-out call that drew the samples: no second encoding and no scorer pass (sample_and_rerank makes both).
+        Returns one Response per source, built from the winners (always with scores), carrying `utility` and `sample_index`
+        per sentence: sentence i's winner is sample sample_index[i] of translate(samples=n) under the same sampling. n <= 64."""
+        if sampling is None or int(n) < 1:
+            raise ValueError("sample_and_select: n >= 1 and sampling=(temperature, seed)")
+        processed = model.processor.process_many(sources, self.wrap_length, self.workers)
+        per_request = [segs for _, segs in processed]
+        flat = [seg for segs in per_request for seg in segs]
+        if any(len(seg) > self.ENGINE_LIMIT for seg in flat):
+            raise ValueError(f"samples: a segment has more than {self.ENGINE_LIMIT} tokens")
+        histories = [[None] * len(segs) for segs in per_request]
+        picked = [([0.0] * len(segs), [0] * len(segs)) for segs in per_request]
+        if flat:
+            res, utility, index = self._engine(model, False, sampling[0], truncation).translate_consensus(
+                flat, int(n), seed=int(sampling[1]), max_order=max_order, beta2=beta2)
+            e = 0
+            for r, segs in enumerate(per_request):
+                for i in range(len(segs)):
+                    histories[r][i] = (res.target(e).tolist(), res.alignment(e).copy(), res.token_scores(e).copy())
+                    picked[r][0][i], picked[r][1][i] = float(utility[e]), int(index[e])
+                    e += 1
+            res.close()
+        out = self._respond_many(model, [src for src, _ in processed], histories)
+        for resp, (u, j) in zip(out, picked):
+            resp.utility, resp.sample_index = u, j
+            resp.to(encoding)
+        return out
 
     def pivot(self, first: Model, second: Model, texts: Sequence[str], html: bool = False,
               scores: bool = False, sampling=None, truncation=None) -> List[Response]:

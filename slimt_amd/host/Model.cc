@@ -259,11 +259,18 @@ void Worker::arm_sampling_truncation(uint32_t top_k, float top_p) {
 // (weak, like the scores)
 #pragma weak slimt_hip_translate_fanout
 #pragma weak slimt_hip_translate_fanout_async_generated
+#pragma weak slimt_hip_ctx_set_fanout_consensus
 void Worker::translate_fanout(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
                               const uint32_t *row_src, size_t N, const uint32_t *shortlist, size_t n_shortlist,
-                              float limit_factor, uint32_t *out_ids, uint32_t *out_len, float *align) {
+                              float limit_factor, uint32_t *out_ids, uint32_t *out_len, float *align,
+                              const FanoutConsensus *consensus) {
   if (!slimt_hip_translate_fanout || !slimt_hip_translate_fanout_async_generated)
     throw std::runtime_error("this engine has no fan-out translate calls");
+  if (consensus) {  // (armed right before the call that takes it)
+    if (!slimt_hip_ctx_set_fanout_consensus) throw std::runtime_error("this engine has no consensus selection");
+    if (slimt_hip_ctx_set_fanout_consensus(ctx_, consensus->max_order, consensus->beta2, consensus->best, consensus->utility))
+      raise("slimt_hip_ctx_set_fanout_consensus");
+  }
   if (generator) {
     if (slimt_hip_translate_fanout_async_generated(ctx_, generator, ids, lengths, B, S, row_src, N, limit_factor,
                                                    model_.config().eos_id, out_ids, out_len, align))

@@ -40,6 +40,10 @@ struct Hypothesis {  // slimt/Types.hh:55-61
   std::vector<uint32_t> alt_ids;
   std::vector<float> alt_scores;
   std::vector<uint32_t> ranks;
+  // Service::translate_consensus: the winner's utility among its sentence's samples and its index j among them
+  // (include/slimt_hip.h, slimt_hip_consensus_select); 0 otherwise
+  double utility = 0.0;
+  uint32_t sample_index = 0;
   size_t padded_length = 0;  // diagnostic: the S of the batch this sentence was translated in
   uint64_t batch = 0;        // diagnostic: serial number of that batch (Service: batches in launch order)
 };
@@ -208,9 +212,16 @@ class Worker {
   // the worker applies with arrays of N rows (arm_scores, arm_prefix, arm_sampling, arm_sampling_truncation). Blocking.
   // generator (nullable): the lexical shortlist of the B sources, generated on the device -- shortlist / n_shortlist are
   // then not used.
+  // consensus (nullable): the call also selects each source's consensus row on the device
+  // (slimt_hip_ctx_set_fanout_consensus) and fills consensus->best [B] and consensus->utility [N].
+  struct FanoutConsensus {
+    int max_order = 4, beta2 = 4;
+    uint32_t *best = nullptr;
+    double *utility = nullptr;
+  };
   void translate_fanout(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
                         const uint32_t *row_src, size_t N, const uint32_t *shortlist, size_t n_shortlist, float limit_factor,
-                        uint32_t *out_ids, uint32_t *out_len, float *align);
+                        uint32_t *out_ids, uint32_t *out_len, float *align, const FanoutConsensus *consensus = nullptr);
   void wait();
 
  private:

@@ -437,6 +437,20 @@ Service::CandidateScores Service::score_candidates(std::vector<Words> sentences,
 }
 
 Histories Service::translate_samples(std::vector<Words> sentences, size_t n, uint64_t seed) {
+  return fanout_samples(std::move(sentences), n, seed, false, 0, 0);
+}
+
+Histories Service::translate_consensus(std::vector<Words> sentences, size_t n, uint64_t seed, int max_order, int beta2) {
+  if (n > SLIMT_HIP_CONSENSUS_MAX_ROWS)
+    throw std::invalid_argument(std::to_string(n) + " samples per sentence: the consensus selection takes at most " +
+                                std::to_string(SLIMT_HIP_CONSENSUS_MAX_ROWS));
+  if (max_order < 1 || max_order > SLIMT_HIP_CONSENSUS_MAX_ORDER || beta2 < 1 || beta2 > SLIMT_HIP_CONSENSUS_MAX_BETA2)
+    throw std::invalid_argument("consensus: max_order " + std::to_string(max_order) + " or beta2 " + std::to_string(beta2) +
+                                " out of range");
+  return fanout_samples(std::move(sentences), n, seed, true, max_order, beta2);
+}
+
+Histories Service::fanout_samples(std::vector<Words> sentences, size_t n, uint64_t seed, bool select, int max_order, int beta2) {
   float temperature, top_p;
   uint32_t top_k;
   {
@@ -456,9 +470,11 @@ Histories Service::translate_samples(std::vector<Words> sentences, size_t n, uin
                                   std::to_string(longest_) + " (wrap it first)");
   }
   const size_t count = sentences.size();
-  Histories results(count * n);
+  Histories results(select ? count : count * n);
   if (count == 0) return results;
   if (count >= (1u << 24)) throw std::invalid_argument("request of more than 2^24 sentences");
+  std::vector<uint32_t> best;    // (select) per source of a call: its consensus row
+  std::vector<double> utility;   // (select) per row of a call
   LengthQueue queue(config_.max_words, longest_);  // the batch-forming rule of translate()
   for (size_t i = 0; i < count; ++i) {
     Unit u;
@@ -508,10 +524,19 @@ Histories Service::translate_samples(std::vector<Words> sentences, size_t n, uin
       if (top_k != 0 || top_p != 1.0f) score_worker_->arm_sampling_truncation(top_k, top_p);
       score_worker_->arm_scores(&sp, 1);
       const bool fixed = config_.shortlist && !score_generator_;
+      Worker::FanoutConsensus cs;
+      if (select) {  // the pick among each sentence's rows, on the device behind the last step
+        best.assign(B, 0xFFFFFFFFu);
+        utility.assign(N, 0.0);
+        cs.max_order = max_order;
+        cs.beta2 = beta2;
+        cs.best = best.data();
+        cs.utility = utility.data();
+      }
       score_worker_->translate_fanout(score_generator_, ids.data(), lengths.data(), B, S, src.data(), N,
                                       fixed ? config_.shortlist->data() : nullptr, fixed ? config_.shortlist->size() : 0,
                                       config_.tgt_length_limit_factor, out_ids.data(), out_len.data(),
-                                      config_.alignments ? al.data() : nullptr);
+                                      config_.alignments ? al.data() : nullptr, select ? &cs : nullptr);
       const uint64_t serial = batches_.fetch_add(1);
       Histories hs = collect(out_ids.data(), out_len.data(), config_.alignments ? al.data() : nullptr, rlen.data(), N, S, T,
                              config_.flat_alignments);
@@ -519,7 +544,13 @@ Histories Service::translate_samples(std::vector<Words> sentences, size_t n, uin
         const float *row = sc.data() + r * T;
         hs[r]->scores.assign(row, row + out_len[r]);
         hs[r]->batch = serial;
-        results[static_cast<size_t>(batch[b0 + r / n].index) * n + r % n] = std::move(hs[r]);
+        if (!select) results[static_cast<size_t>(batch[b0 + r / n].index) * n + r % n] = std::move(hs[r]);
+      }
+      for (size_t b = 0; select && b < B; ++b) {  // (rows b n .. b n + n are sentence b's; no competing row: sample 0)
+        const size_t r = best[b] >= b * n && best[b] < (b + 1) * n ? best[b] : b * n;
+        hs[r]->utility = best[b] == r ? utility[r] : 0.0;
+        hs[r]->sample_index = static_cast<uint32_t>(r - b * n);
+        results[batch[b0 + b].index] = std::move(hs[r]);
       }
     }
   }

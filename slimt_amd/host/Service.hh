@@ -193,6 +193,14 @@ class Service {
   // as translate() returns them. The context and the mutex are those of score(): synchronous, on the caller's thread.
   // Throws std::invalid_argument on a greedy service, for n = 0 or n > max_words, an empty sentence or one too long.
   Histories translate_samples(std::vector<Words> sentences, size_t n, uint64_t seed = 0);
+  // translate_samples followed by the consensus (minimum-Bayes-risk) pick among each sentence's n samples, made on the device
+  // behind the fan-out call's last step (include/slimt_hip.h, slimt_hip_ctx_set_fanout_consensus): no second encoding, no
+  // scorer pass. The same batching and the same keys as translate_samples -- the winner of sentence i is bit for bit entry
+  // i * n + sample_index of that call with this seed. Returns ONE Hypothesis per sentence: the winning sample with its
+  // tokens, scores and alignment, plus its utility and its index j among the samples (Hypothesis::utility, sample_index);
+  // n = 1 returns the lone sample with utility 0. Throws as translate_samples does, and for n > 64
+  // (SLIMT_HIP_CONSENSUS_MAX_ROWS) or max_order / beta2 out of range.
+  Histories translate_consensus(std::vector<Words> sentences, size_t n, uint64_t seed = 0, int max_order = 4, int beta2 = 4);
   // per-token scores on or off (ServiceConfig::scores): only before the first translate(); false once one has been made
   bool set_scores(bool on);
   // temperature sampling for every request (include/slimt_hip.h, slimt_hip_ctx_set_sampling; 0: greedy again): only before
@@ -211,6 +219,8 @@ class Service {
   }
 
  private:
+  // translate_samples (select = false: n entries per sentence) and translate_consensus (select = true: the winner alone)
+  Histories fanout_samples(std::vector<Words> sentences, size_t n, uint64_t seed, bool select, int max_order, int beta2);
   struct Slot;
   void work(const Model *model, slimt_hip_shortlist *generator);
   std::vector<Unit> next_batch(bool may_block, std::vector<size_t> *parts = nullptr);

@@ -14,6 +14,7 @@
 #include "slimt_hip_service_prefix.h"
 #include "slimt_hip_service_candidates.h"
 #include "slimt_hip_service_samples.h"
+#include "slimt_hip_service_consensus.h"
 #include "slimt_hip_service_score.h"
 #include "slimt_hip_service_sampling.h"
 #include "slimt_hip_service_scores.h"
@@ -53,6 +54,10 @@ struct slimt_hip_result {
   std::vector<uint32_t> best;
   // slimt_hip_service_translate_samples: entries per sentence (0: another kind of result)
   size_t samples = 0;
+  // slimt_hip_service_translate_consensus: per entry (sentence) the winner's utility and its index among the samples
+  bool selected = false;
+  std::vector<double> utility;
+  std::vector<uint32_t> sample_index;
 };
 
 extern "C" const char *slimt_hip_service_last_error(void) { return g_err; }
@@ -300,6 +305,42 @@ extern "C" int slimt_hip_result_samples(const slimt_hip_result *r, size_t *sampl
   if (!r || !samples) return fail("null argument");
   if (!r->samples) return fail("result_samples: not a result of slimt_hip_service_translate_samples");
   *samples = r->samples;
+  return 0;
+}
+
+extern "C" int slimt_hip_service_translate_consensus(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets,
+                                                     size_t n, size_t samples, uint64_t seed, int max_order, int beta2,
+                                                     slimt_hip_result **out) {
+  if (!service || !out || (n && (!tokens || !offsets))) return fail("null argument");
+  *out = nullptr;
+  try {
+    std::vector<slimt::Words> sentences(n);
+    for (size_t i = 0; i < n; ++i) {
+      if (offsets[i + 1] < offsets[i]) return fail("offsets decrease at sentence %zu", i);
+      sentences[i].assign(tokens + offsets[i], tokens + offsets[i + 1]);
+    }
+    const slimt::Histories hs = service->service->translate_consensus(std::move(sentences), samples, seed, max_order, beta2);
+    std::unique_ptr<slimt_hip_result> r;
+    if (const int rc = flatten(hs, hs.size(), true, r)) return rc;
+    r->selected = true;
+    r->utility.reserve(hs.size());
+    r->sample_index.reserve(hs.size());
+    for (const slimt::History &h : hs) {
+      r->utility.push_back(h->utility);
+      r->sample_index.push_back(h->sample_index);
+    }
+    *out = r.release();
+    return 0;
+  } catch (const std::exception &e) {
+    return fail("%s", e.what());
+  }
+}
+
+extern "C" int slimt_hip_result_consensus(const slimt_hip_result *r, const double **utility, const uint32_t **sample_index) {
+  if (!r || !utility || !sample_index) return fail("null argument");
+  if (!r->selected) return fail("result_consensus: not a result of slimt_hip_service_translate_consensus");
+  *utility = r->utility.data();
+  *sample_index = r->sample_index.data();
   return 0;
 }
 
