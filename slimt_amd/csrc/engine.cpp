@@ -52,14 +52,15 @@ static std::atomic<bool> g_hip_called{false};
 
 // The persistent decoder runs the hoisted cross-attention order over a cache of accumulators; the reference's literal
 // sequence (K/V cache format 3) exists in the stage-wise attention kernel only (decode_kernels.hip, DQAttnArgs::literal)
-// ... and a truncated sampled call (TruncationCall) needs each step's whole row of logits, which only the stage-wise decoder
-// stores. Every decision that hangs on the persistent decoder -- the lean path, pinned arrays read in place, merged launches --
-// asks here; the encoder is chosen as the context's mode says.
+// ... and a truncated sampled call needs each step's whole row of logits, which only the stage-wise decoder stores; a
+// fan-out call's cross-attention looks a row's source up, which only the stage-wise one does (decode_fanout.hip). Every
+// decision that hangs on the persistent decoder -- the lean path, pinned arrays read in place, merged launches -- asks here;
+// the encoder is chosen as the context's mode says.
 static bool fused_decoder_allowed(const slimt_hip_ctx *c) {
-  return c->decode_mode != 1 && c->model->kv_format != 3 && !c->tr_call && !c->fo_call;
+  return c->decode_mode != 1 && c->model->kv_format != 3 && !c->call.truncated && !c->call.fanout;
 }
-// The decoder rows of the call in progress: a fan-out call's N (FanoutCall), else one per source.
-static int decoder_rows(const slimt_hip_ctx *c) { return c->fo_call ? c->fo_rows : c->B; }
+// The decoder rows of the call in progress: a fan-out call's N, else one per source.
+static int decoder_rows(const slimt_hip_ctx *c) { return c->call.fanout ? c->call.rows : c->B; }
 
 // The lean path for sources padded to S tokens: the persistent decoder, allowed and compiled for the model, behind a
 // persistent encoder (the fused one, or the per-sentence one of 65..128 tokens).
@@ -1390,8 +1391,7 @@ extern "C" int slimt_hip_ctx_set_decode_mode(slimt_hip_ctx *ctx, int mode) {
 extern "C" int slimt_hip_ctx_set_scores(slimt_hip_ctx *ctx, float *const *scores, size_t n) {
   if (!ctx) return fail(-1, "null argument");
   if (!scores && n) return fail(-1, "scores is NULL");
-  ctx->sc_next.assign(scores, scores + n);  // (checked by the call that takes them: ScoreCall)
-  ctx->sc_armed = n > 0;  // (n = 0: nothing armed)
+  ctx->armed.scores.assign(scores, scores + n);  // (checked by the call that takes them, CallOptions; n = 0: nothing armed)
   return 0;
 }
 
@@ -1399,9 +1399,8 @@ extern "C" int slimt_hip_ctx_set_target_prefix(slimt_hip_ctx *ctx, const uint32_
                                                const uint32_t *const *prefix_len, size_t n) {
   if (!ctx) return fail(-1, "null argument");
   if ((!prefix_ids || !prefix_len) && n) return fail(-1, "target prefix arrays are NULL");
-  ctx->fp_next_ids.assign(prefix_ids, prefix_ids + n);  // (checked by the call that takes them: PrefixCall)
-  ctx->fp_next_len.assign(prefix_len, prefix_len + n);
-  ctx->fp_armed = n > 0;  // (n = 0: nothing armed)
+  ctx->armed.prefix_ids.assign(prefix_ids, prefix_ids + n);  // (checked by the call that takes them; n = 0: nothing armed)
+  ctx->armed.prefix_len.assign(prefix_len, prefix_len + n);
   return 0;
 }
 
@@ -1414,11 +1413,10 @@ extern "C" int slimt_hip_ctx_set_sampling(slimt_hip_ctx *ctx, float temperature,
   if (!(inv_T > 0.0f) || !std::isfinite(inv_T)) return fail(-1, "sampling: 1 / temperature %g is not finite and > 0", (double)temperature);
   if (!ctx) return fail(-1, "null argument");
   if (keys)
-    ctx->sm_next_keys.assign(keys, keys + n);  // (the count is checked by the call that takes them: SampleCall)
+    ctx->armed.keys.assign(keys, keys + n);  // (the count is checked by the call that takes them; n = 0: nothing armed)
   else
-    ctx->sm_next_keys.assign(n, nullptr);
-  ctx->sm_next_inv_T = inv_T;
-  ctx->sm_armed = n > 0;  // (n = 0: nothing armed)
+    ctx->armed.keys.assign(n, nullptr);
+  ctx->armed.inv_T = inv_T;
   return 0;
 }
 
@@ -1426,9 +1424,8 @@ extern "C" int slimt_hip_ctx_set_sampling_truncation(slimt_hip_ctx *ctx, uint32_
   // (the value first, like the temperature)
   if (!(top_p > 0.0f && top_p <= 1.0f)) return fail(-1, "sampling truncation: top_p %g is not in (0, 1]", (double)top_p);
   if (!ctx) return fail(-1, "null argument");
-  ctx->tr_next_k = top_k;
-  ctx->tr_next_p = top_p;
-  ctx->tr_armed = top_k != 0 || top_p != 1.0f;  // (both off: nothing armed, the call is today's sampled call)
+  ctx->armed.top_k = top_k;  // (both off: nothing armed, the call is a plain sampled call)
+  ctx->armed.top_p = top_p;
   return 0;
 }
 
@@ -1441,11 +1438,10 @@ extern "C" int slimt_hip_ctx_set_fanout_consensus(slimt_hip_ctx *ctx, int max_or
     return fail(-1, "consensus: beta2 %d is not in 1..%d", beta2, SLIMT_HIP_CONSENSUS_MAX_BETA2);
   if (max_order && (!best || !utility)) return fail(-1, "consensus: best or utility is NULL");
   if (!ctx) return fail(-1, "null argument");
-  ctx->cs_next_order = max_order;
-  ctx->cs_next_beta2 = beta2;
-  ctx->cs_next_best = best;
-  ctx->cs_next_util = utility;
-  ctx->cs_armed = max_order > 0;  // (0: nothing armed)
+  ctx->armed.cs_order = max_order;  // (0: nothing armed)
+  ctx->armed.cs_beta2 = beta2;
+  ctx->armed.cs_best = best;
+  ctx->armed.cs_util = utility;
   return 0;
 }
 
@@ -1660,240 +1656,93 @@ struct MergePlan {
   int max_N = 0;  // columns of the widest job
   size_t stride_wp = 0, stride_cs = 0, stride_pb = 0;
   bool dense = false;  // one output layer for all sub-batches: no holes between them (kernels.h, FusedDecodeArgs::sub_dense)
-  float *scores[kMaxMerge] = {};  // scored launches: sub-batch j's destination, device-visible (FusedDecodeArgs::sub_scores)
-  const uint32_t *prefix_ids[kMaxMerge] = {};  // forced launches: sub-batch j's prefix in device memory (FusedDecodeArgs)
-  const uint32_t *prefix_len[kMaxMerge] = {};
-  const uint64_t *keys[kMaxMerge] = {};  // sampled launches: sub-batch j's keys in device memory (nullptr: the row in the sub-batch)
+  BatchOptions opt[kMaxMerge];  // sub-batch j's options as the kernels address them (FusedDecodeArgs::sub_scores / sub_prefix_* / sub_keys)
 };
 
-// The scores armed on a context (slimt_hip_ctx_set_scores) are taken by the translate entry point that comes next, whether
-// that call then succeeds or fails. n: the destinations the call needs (1, or its number of batches). An entry point that
-// another one calls for a batch of its own (the batch-by-batch fallbacks) finds nothing armed and keeps what its caller set.
-struct ScoreCall {
-  slimt_hip_ctx *c = nullptr;
-  std::vector<float *> dst;
-  int rc = 0;
-  ScoreCall(slimt_hip_ctx *ctx, size_t n) {
-    if (!ctx || !ctx->sc_armed) return;
-    c = ctx;
-    dst.swap(ctx->sc_next);
-    ctx->sc_armed = false;
-    ctx->sc_next.clear();
-    if (dst.size() != n) {
-      rc = fail(-1, "scores: %zu destinations armed, the call has %zu batches", dst.size(), n);
-    } else {
-      for (size_t j = 0; j < n && !rc; ++j)
-        if (!dst[j]) rc = fail(-1, "scores: destination %zu is NULL", j);
-    }
-    ctx->sc_call = rc == 0;
-    ctx->sc_user = rc == 0 && n == 1 ? dst[0] : nullptr;
-    ctx->sc_dev = nullptr;
-  }
-  ~ScoreCall() {
-    if (!c) return;
-    c->sc_call = false;
-    c->sc_user = nullptr;
-    c->sc_dev = nullptr;
-  }
-};
-
-// The target prefix armed on a context (slimt_hip_ctx_set_target_prefix), taken like the scores (ScoreCall) by the next
-// translate entry point, whether it then succeeds or fails. The entry points point ctx->fp_ids / fp_len at device memory
-// the kernels read: the caller's arrays for the _device calls, else a staged copy (prefix_stage).
-struct PrefixCall {
-  slimt_hip_ctx *c = nullptr;
-  std::vector<const uint32_t *> ids, len;
-  int rc = 0;
-  PrefixCall(slimt_hip_ctx *ctx, size_t n) {
-    if (!ctx || !ctx->fp_armed) return;
-    c = ctx;
-    ids.swap(ctx->fp_next_ids);
-    len.swap(ctx->fp_next_len);
-    ctx->fp_armed = false;
-    ctx->fp_next_ids.clear();
-    ctx->fp_next_len.clear();
-    if (ids.size() != n) {
-      rc = fail(-1, "target prefix: %zu batches armed, the call has %zu", ids.size(), n);
-    } else {
-      for (size_t j = 0; j < n && !rc; ++j)
-        if (!ids[j] || !len[j]) rc = fail(-1, "target prefix: batch %zu has a NULL array", j);
-    }
-    ctx->fp_call = rc == 0;
-    ctx->fp_user_ids = rc == 0 && n == 1 ? ids[0] : nullptr;
-    ctx->fp_user_len = rc == 0 && n == 1 ? len[0] : nullptr;
-    ctx->fp_ids = ctx->fp_len = nullptr;
-  }
-  ~PrefixCall() {
-    if (!c) return;
-    c->fp_call = false;
-    c->fp_user_ids = c->fp_user_len = nullptr;
-    c->fp_ids = c->fp_len = nullptr;
-  }
-};
-
-// The sampling armed on a context (slimt_hip_ctx_set_sampling), taken like the scores and the prefix by the next translate
-// entry point, whether it then succeeds or fails. keys[j] may be NULL (batch j's keys are its row indices). The entry points
-// point ctx->sm_keys at memory the kernels read: the caller's array for the _device calls, else its pinned view or a staged
-// copy (keys_stage).
-struct SampleCall {
-  slimt_hip_ctx *c = nullptr;
-  std::vector<const uint64_t *> keys;
-  int rc = 0;
-  SampleCall(slimt_hip_ctx *ctx, size_t n) {
-    if (!ctx || !ctx->sm_armed) return;
-    c = ctx;
-    keys.swap(ctx->sm_next_keys);
-    ctx->sm_armed = false;
-    ctx->sm_next_keys.clear();
-    if (keys.size() != n) rc = fail(-1, "sampling: %zu batches armed, the call has %zu", keys.size(), n);
-    ctx->sm_call = rc == 0;
-    ctx->sm_inv_T = ctx->sm_next_inv_T;
-    ctx->sm_user_keys = rc == 0 && n == 1 ? keys[0] : nullptr;
-    ctx->sm_keys = nullptr;
-  }
-  ~SampleCall() {
-    if (!c) return;
-    c->sm_call = false;
-    c->sm_user_keys = c->sm_keys = nullptr;
-  }
-};
-
-// The truncation armed on a context (slimt_hip_ctx_set_sampling_truncation), taken by the next translate entry point behind
-// its SampleCall, whether it then succeeds or fails; without sampling armed that call fails. A truncated call needs the
-// whole row of logits before it draws: while tr_call is set fused_decoder_allowed() is false, so the call decodes with the
-// per-stage kernels and is never merged; the context's decode mode is not touched and still chooses the encoder.
-struct TruncationCall {
-  slimt_hip_ctx *c = nullptr;
-  int rc = 0;
-  explicit TruncationCall(slimt_hip_ctx *ctx) {
-    if (!ctx || !ctx->tr_armed) return;
-    ctx->tr_armed = false;
-    if (!ctx->sm_call) {
-      rc = fail(-1, "sampling truncation: armed without sampling (slimt_hip_ctx_set_sampling)");
-      return;
-    }
-    c = ctx;
-    ctx->tr_call = true;
-    ctx->tr_k = ctx->tr_next_k;
-    ctx->tr_p = ctx->tr_next_p;
-  }
-  ~TruncationCall() {
-    if (c) c->tr_call = false;
-  }
-};
-
-// The consensus selection armed on a context (slimt_hip_ctx_set_fanout_consensus), taken by the next translate entry point,
-// whether it then succeeds or fails; only a fan-out call can use it, any other call that finds it armed fails. The entry
-// points point ctx->cs_dev_best / cs_dev_util at memory the kernel writes: the caller's arrays for the _device call, else
-// the context's staging (translate_host copies it out behind the kernels).
-struct ConsensusCall {
-  slimt_hip_ctx *c = nullptr;
-  int rc = 0;
-  ConsensusCall(slimt_hip_ctx *ctx, bool fanout) {
-    if (!ctx || !ctx->cs_armed) return;
-    ctx->cs_armed = false;
-    if (!fanout) {
-      rc = fail(-1, "consensus: armed on a translate call that is not a fan-out call (slimt_hip_translate_fanout*)");
-      return;
-    }
-    c = ctx;
-    ctx->cs_call = true;
-    ctx->cs_order = ctx->cs_next_order;
-    ctx->cs_beta2 = ctx->cs_next_beta2;
-    ctx->cs_user_best = ctx->cs_next_best;
-    ctx->cs_user_util = ctx->cs_next_util;
-    ctx->cs_dev_best = nullptr;
-    ctx->cs_dev_util = nullptr;
-  }
-  ~ConsensusCall() {
-    if (!c) return;
-    c->cs_call = false;
-    c->cs_user_best = c->cs_dev_best = nullptr;
-    c->cs_user_util = c->cs_dev_util = nullptr;
-  }
-};
-
-// What a translate entry point opens with: the five guards, constructed in this order (TruncationCall reads sm_call, which
-// SampleCall sets) and all of them whatever the earlier ones found -- what was armed is consumed whether or not the call
-// succeeds. n: the batches of the call; fanout: a fan-out entry point. rc(): the first guard's that refused.
+// What a translate entry point opens with. Whatever the slimt_hip_ctx_set_* functions armed on the context is moved out of
+// ctx->armed here -- consumed whether or not the call then succeeds -- checked against the call's n batches, and becomes
+// ctx->call, the record every inner function reads; `user` holds the per-batch arrays as the caller gave them, one entry per
+// batch, for the entry point to hand on: as they are where they are device memory (options_in_place), through
+// stage_options where they are host memory. The checks run scores -> prefix -> sampling -> truncation -> consensus and the
+// first refusal is the call's (rc); a truncated call must be sampled, so the truncation is looked at behind the sampling.
+// While call.truncated or call.fanout is set fused_decoder_allowed() is false: the call decodes with the per-stage kernels
+// and is never merged; the context's decode mode is not touched and still chooses the encoder. Consensus is for the
+// fan-out entry points (fanout) only: any other call that finds it armed is refused. The destructor empties ctx->call.
+// The score entry points (slimt_hip_score*) open no CallOptions: they neither read nor consume what was armed.
 struct CallOptions {
-  ScoreCall sc;
-  PrefixCall pc;
-  SampleCall smc;
-  TruncationCall trc;
-  ConsensusCall csc;
-  CallOptions(slimt_hip_ctx *ctx, size_t n, bool fanout = false) : sc(ctx, n), pc(ctx, n), smc(ctx, n), trc(ctx), csc(ctx, fanout) {}
-  int rc() const { return sc.rc ? sc.rc : pc.rc ? pc.rc : smc.rc ? smc.rc : trc.rc ? trc.rc : csc.rc; }
-};
-
-// A fan-out call (slimt_hip_translate_fanout*): N decoder rows over the call's B sources, opened behind the call's
-// CallOptions, whose arrays then count N rows. While fo_call is set fused_decoder_allowed() is false -- the call decodes with
-// the per-stage kernels, whose cross-attention alone looks a row's source up (decode_fanout.hip), and is never merged --
-// and decoder_rows() is N; the context's decode mode is not touched and still chooses the encoder. The entry points point
-// ctx->fo_row_src at memory the kernels read. N is bounded by max_batch: the per-row decoder workspaces are sized by it.
-struct FanoutCall {
-  slimt_hip_ctx *c = nullptr;
+  slimt_hip_ctx *c;
+  std::vector<BatchOptions> user;
   int rc = 0;
-  FanoutCall(slimt_hip_ctx *ctx, size_t N) {
-    if (!ctx) return;
-    if (N == 0) {
-      rc = fail(-1, "fan-out: no rows (N = 0)");
-      return;
-    }
-    if (N > ctx->max_B) {
-      rc = fail(-1, "fan-out: %zu rows exceed the context's max_batch %zu", N, ctx->max_B);
-      return;
-    }
-    c = ctx;
-    ctx->fo_call = true;
-    ctx->fo_rows = (int)N;
-    ctx->fo_row_src = nullptr;
-  }
-  ~FanoutCall() {
+  CallOptions(slimt_hip_ctx *ctx, size_t n, bool fanout = false) : c(ctx), user(n) {
     if (!c) return;
-    c->fo_call = false;
-    c->fo_rows = 0;
-    c->fo_row_src = nullptr;
+    const ArmedOptions a = std::move(c->armed);
+    c->armed = {};
+    c->call = {};
+    rc = take(a, n, fanout);
+    if (rc) c->call = {};
+  }
+  ~CallOptions() {
+    if (c) c->call = {};
+  }
+  // A fan-out call (slimt_hip_translate_fanout*): N decoder rows over the call's B sources, opened behind the options, whose
+  // arrays then count N rows; decoder_rows() is N from here on. N is bounded by max_batch, which sizes the per-row workspaces.
+  int open_fanout(size_t N) {
+    if (!c) return 0;
+    if (N == 0) return fail(-1, "fan-out: no rows (N = 0)");
+    if (N > c->max_B) return fail(-1, "fan-out: %zu rows exceed the context's max_batch %zu", N, c->max_B);
+    c->call.fanout = true;
+    c->call.rows = (int)N;
+    return 0;
+  }
+
+ private:
+  int take(const ArmedOptions &a, size_t n, bool fanout) {
+    CallState &call = c->call;
+    if (!a.scores.empty()) {
+      if (a.scores.size() != n) return fail(-1, "scores: %zu destinations armed, the call has %zu batches", a.scores.size(), n);
+      for (size_t j = 0; j < n; ++j) {
+        if (!a.scores[j]) return fail(-1, "scores: destination %zu is NULL", j);
+        user[j].scores = a.scores[j];
+      }
+      call.scored = true;
+    }
+    if (!a.prefix_ids.empty()) {
+      if (a.prefix_ids.size() != n) return fail(-1, "target prefix: %zu batches armed, the call has %zu", a.prefix_ids.size(), n);
+      for (size_t j = 0; j < n; ++j) {
+        if (!a.prefix_ids[j] || !a.prefix_len[j]) return fail(-1, "target prefix: batch %zu has a NULL array", j);
+        user[j].prefix_ids = a.prefix_ids[j];
+        user[j].prefix_len = a.prefix_len[j];
+      }
+      call.forced = true;
+    }
+    if (!a.keys.empty()) {  // (keys[j] may be NULL: batch j's keys are its row indices)
+      if (a.keys.size() != n) return fail(-1, "sampling: %zu batches armed, the call has %zu", a.keys.size(), n);
+      for (size_t j = 0; j < n; ++j) user[j].keys = a.keys[j];
+      call.sampled = true;
+      call.inv_T = a.inv_T;
+    }
+    if (a.top_k != 0 || a.top_p != 1.0f) {
+      if (!call.sampled) return fail(-1, "sampling truncation: armed without sampling (slimt_hip_ctx_set_sampling)");
+      call.truncated = true;
+      call.top_k = a.top_k;
+      call.top_p = a.top_p;
+    }
+    if (a.cs_order > 0) {
+      if (!fanout) return fail(-1, "consensus: armed on a translate call that is not a fan-out call (slimt_hip_translate_fanout*)");
+      call.consensus = true;
+      call.cs_order = a.cs_order;
+      call.cs_beta2 = a.cs_beta2;
+      call.cs_best = a.cs_best;
+      call.cs_util = a.cs_util;
+    }
+    return 0;
   }
 };
 
-// Batch j of a call that goes batch by batch through a single-batch path: its own destination, prefix and keys where that
-// path looks for the caller's (the *_user fields).
-void arm_batch(slimt_hip_ctx *ctx, float *const *scores, const PrefixCall &pc, const SampleCall &smc, size_t j) {
-  if (ctx->sc_call) ctx->sc_user = scores[j];
-  if (ctx->fp_call) {
-    ctx->fp_user_ids = pc.ids[j];
-    ctx->fp_user_len = pc.len[j];
-  }
-  if (ctx->sm_call) ctx->sm_user_keys = smc.keys[j];
-}
+// A batch whose options are device memory (the _device entry points): the kernels address them where they are.
+void options_in_place(slimt_hip_ctx *c, const BatchOptions &user) { c->call.dev = user; }
 
 void *host_device_view(const void *p);  // (below)
-
-// Host keys -> addresses the kernels read, like prefix_stage: pinned arrays in place, a pageable batch's keys staged in
-// device memory with one asynchronous copy on the context's stream; NULL stays NULL.
-int keys_stage(slimt_hip_ctx *c, size_t n, const uint64_t *const *keys, const size_t *B, const uint64_t **d_keys) {
-  size_t words = 0;
-  for (size_t j = 0; j < n; ++j) {
-    d_keys[j] = keys[j] ? static_cast<const uint64_t *>(host_device_view(keys[j])) : nullptr;
-    if (keys[j] && !d_keys[j]) words += B[j];
-  }
-  if (words) HIPCHK(c->sm_stage.reserve(words * 8));
-  uint64_t *p = c->sm_stage.as<uint64_t>();
-  for (size_t j = 0; j < n; ++j) {
-    if (!keys[j] || d_keys[j]) continue;
-    HIPCHK(hipMemcpyAsync(p, keys[j], B[j] * 8, hipMemcpyHostToDevice, c->stream));
-    d_keys[j] = p;
-    p += B[j];
-  }
-  return 0;
-}
-
-int keys_stage_batches(slimt_hip_ctx *c, const SampleCall &sm, const slimt_hip_batch *batches, size_t n, const uint64_t **d_keys) {
-  std::vector<size_t> B(n);
-  for (size_t j = 0; j < n; ++j) B[j] = batches[j].B;
-  return keys_stage(c, n, sm.keys.data(), B.data(), d_keys);
-}
 
 // A host prefix of B sentences with rows Tmax apart: every length <= Tmax, every id of the prefix < V.
 int prefix_check(const slimt_hip_ctx *c, const uint32_t *ids, const uint32_t *len, size_t B, size_t Tmax) {
@@ -1906,44 +1755,59 @@ int prefix_check(const slimt_hip_ctx *c, const uint32_t *ids, const uint32_t *le
   return 0;
 }
 
-// Host prefixes -> addresses the kernels read. Pinned arrays (hipHostMalloc / slimt_hip_host_alloc) are read in place,
-// like the pinned inputs of the asynchronous calls (translate_host: no copy queued behind other streams' kernels); a
-// pageable batch's ids and lengths are staged in device memory with one asynchronous copy each on the context's stream.
-// parts: n batches' (ids, len, B, Tmax); the addresses go to d_ids[j] / d_len[j]. Checked first: nothing is queued for an
-// invalid prefix.
-int prefix_stage(slimt_hip_ctx *c, size_t n, const uint32_t *const *ids, const uint32_t *const *len, const size_t *B,
-                 const size_t *Tmax, const uint32_t **d_ids, const uint32_t **d_len) {
-  size_t words = 0;
-  std::vector<bool> pinned(n);
+// Host prefixes and keys -> addresses the kernels read: n batches' user[j] of rows[j] rows with prefix rows Tmax[j] apart, to
+// dev[j].prefix_* / dev[j].keys (dev[j].scores is not touched: a host call's scores have a copy-back, translate_host). Pinned
+// arrays (hipHostMalloc / slimt_hip_host_alloc) are read in place, like the pinned inputs of the asynchronous calls
+// (translate_host: no copy queued behind other streams' kernels); a pageable batch's prefix (ids, then lengths) and keys
+// are staged in device memory with one asynchronous copy each on the context's stream; NULL keys stay NULL. Every prefix is
+// checked first: nothing is queued for an invalid one.
+int stage_options(slimt_hip_ctx *c, size_t n, const BatchOptions *user, const size_t *rows, const size_t *Tmax, BatchOptions *dev) {
+  for (size_t j = 0; j < n; ++j)
+    if (user[j].prefix_ids) RCCHK(prefix_check(c, user[j].prefix_ids, user[j].prefix_len, rows[j], Tmax[j]));
+  size_t fp_words = 0, sm_words = 0;
   for (size_t j = 0; j < n; ++j) {
-    RCCHK(prefix_check(c, ids[j], len[j], B[j], Tmax[j]));
-    d_ids[j] = static_cast<const uint32_t *>(host_device_view(ids[j]));
-    d_len[j] = static_cast<const uint32_t *>(host_device_view(len[j]));
-    pinned[j] = d_ids[j] && d_len[j];
-    if (!pinned[j]) words += B[j] * Tmax[j] + B[j];
+    const BatchOptions &u = user[j];
+    BatchOptions &d = dev[j];
+    d.prefix_ids = u.prefix_ids ? static_cast<const uint32_t *>(host_device_view(u.prefix_ids)) : nullptr;
+    d.prefix_len = u.prefix_ids ? static_cast<const uint32_t *>(host_device_view(u.prefix_len)) : nullptr;
+    if (!d.prefix_ids || !d.prefix_len) d.prefix_ids = d.prefix_len = nullptr;  // (both in place, or both staged)
+    d.keys = u.keys ? static_cast<const uint64_t *>(host_device_view(u.keys)) : nullptr;
+    if (u.prefix_ids && !d.prefix_ids) fp_words += rows[j] * Tmax[j] + rows[j];
+    if (u.keys && !d.keys) sm_words += rows[j];
   }
-  if (words) HIPCHK(c->fp_stage.reserve(words * 4));
+  if (fp_words) HIPCHK(c->fp_stage.reserve(fp_words * 4));
+  if (sm_words) HIPCHK(c->sm_stage.reserve(sm_words * 8));
   uint32_t *p = c->fp_stage.as<uint32_t>();
+  uint64_t *q = c->sm_stage.as<uint64_t>();
   for (size_t j = 0; j < n; ++j) {
-    if (pinned[j]) continue;
-    HIPCHK(hipMemcpyAsync(p, ids[j], B[j] * Tmax[j] * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(p + B[j] * Tmax[j], len[j], B[j] * 4, hipMemcpyHostToDevice, c->stream));
-    d_ids[j] = p;
-    d_len[j] = p + B[j] * Tmax[j];
-    p += B[j] * Tmax[j] + B[j];
+    const BatchOptions &u = user[j];
+    BatchOptions &d = dev[j];
+    const size_t ids = rows[j] * Tmax[j];
+    if (u.prefix_ids && !d.prefix_ids) {
+      HIPCHK(hipMemcpyAsync(p, u.prefix_ids, ids * 4, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(p + ids, u.prefix_len, rows[j] * 4, hipMemcpyHostToDevice, c->stream));
+      d.prefix_ids = p;
+      d.prefix_len = p + ids;
+      p += ids + rows[j];
+    }
+    if (u.keys && !d.keys) {
+      HIPCHK(hipMemcpyAsync(q, u.keys, rows[j] * 8, hipMemcpyHostToDevice, c->stream));
+      d.keys = q;
+      q += rows[j];
+    }
   }
   return 0;
 }
 
-// the host prefixes of a call's batches (PrefixCall) staged at once (prefix_stage): batch j of B_j sentences padded to S_j
-int prefix_stage_batches(slimt_hip_ctx *c, const PrefixCall &pc, const slimt_hip_batch *batches, size_t n, size_t S,
-                         float limit_factor, const uint32_t **d_ids, const uint32_t **d_len) {
-  std::vector<size_t> B(n), T(n);
+// ... for the batches of a host _many_ call (n <= kMaxMerge): batch j of B_j sentences padded to S_j tokens
+int stage_options(slimt_hip_ctx *c, const slimt_hip_batch *batches, size_t n, size_t S, float limit_factor, const BatchOptions *user,
+                  BatchOptions *dev) {
+  size_t rows[kMaxMerge], Tmax[kMaxMerge];
   for (size_t j = 0; j < n; ++j) {
-    B[j] = batches[j].B;
-    T[j] = std::max<size_t>(1, (size_t)(limit_factor * (float)(batches[j].S ? batches[j].S : S)));
+    rows[j] = batches[j].B;
+    Tmax[j] = std::max<size_t>(1, (size_t)(limit_factor * (float)(batches[j].S ? batches[j].S : S)));
   }
-  return prefix_stage(c, n, pc.ids.data(), pc.len.data(), B.data(), T.data(), d_ids, d_len);
+  return stage_options(c, n, user, rows, Tmax, dev);
 }
 
 // gen (nullable; only where fused_encoder_chosen): the batch's shortlist is generated inside the encoder launch
@@ -2320,9 +2184,9 @@ int decoder_layers(slimt_hip_ctx *c, float *d_align, int Tmax, const uint32_t *d
     }
     {
       ProfScope p(c, SLIMT_HIP_K_ATTN_DEC, (double)N * D * D, (double)D * D);
-      if (c->fo_call) {  // rows that share sources: a source's K / V staged once per run of its rows (decode_fanout.hip)
+      if (c->call.fanout) {  // rows that share sources: a source's K / V staged once per run of its rows (decode_fanout.hip)
         a.rows = N;
-        a.row_src = c->fo_row_src;
+        a.row_src = c->call.row_src;
         HIPCHK(launch_dqattn_fanout(a, st));
       } else {
         HIPCHK(launch_dqattn(a, st));
@@ -2398,11 +2262,12 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   // loop then runs while i < (size_t)(limit_factor * S): at least one output column
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
   const bool lean = persistent_path(c, S);
-  // R decoder rows over the B sources: B, but in a fan-out call (FanoutCall; never lean, never merged). The caller's
-  // outputs, the per-call options and every decoder workspace are per row; ids, lengths, the encoder and the K / V per source.
-  const size_t R = c->fo_call ? (size_t)c->fo_rows : B;
-  if (c->cs_call) {  // (ConsensusCall: a fan-out call; the selection runs behind the last step, below)
-    if (!c->fo_call || !c->cs_dev_best || !c->cs_dev_util) return fail(-1, "consensus: not a fan-out call");
+  // R decoder rows over the B sources: B, but in a fan-out call (never lean, never merged). The caller's outputs, the
+  // per-call options and every decoder workspace are per row; ids, lengths, the encoder and the K / V per source.
+  const CallState &call = c->call;
+  const size_t R = call.fanout ? (size_t)call.rows : B;
+  if (call.consensus) {  // (a fan-out call; the selection runs behind the last step, below)
+    if (!call.fanout || !call.cs_dev_best || !call.cs_dev_util) return fail(-1, "consensus: not a fan-out call");
     if (Tmax > (size_t)SLIMT_HIP_CONSENSUS_MAX_T)
       return fail(-1, "consensus: the call's Tmax %zu exceeds %d", Tmax, SLIMT_HIP_CONSENSUS_MAX_T);
   }
@@ -2456,25 +2321,26 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   ds.n_finished = c->n_finished.as<int>();
   ds.Tmax = (int)Tmax;
   ds.eos = eos_id;
-  // a scored call (ScoreCall): each recorded token's log-probability goes beside it -- to c->sc_dev, or in a merged launch
-  // to each sub-batch's mp->scores[j] (the entry points set them to addresses the kernels can write)
-  // a forced call (PrefixCall) takes the scored kernels' forced twins: scored as well, into a context-owned scratch when the
-  // caller did not ask for scores (merged: sub-batch j's rows of it from its first sentence on, Tmax_j <= Tmax)
-  // a sampled call (SampleCall) takes their sampled twins, with or without a prefix: scored in the same way
-  const bool forced = c->fp_call;
-  const bool sampled = c->sm_call;
-  const bool scored = c->sc_call || forced || sampled;
-  if ((forced || sampled) && !c->sc_call) {
+  // The batch's options as the kernels address them (the entry points set them): call.dev, or in a merged launch each
+  // sub-batch's mp->opt[j].
+  // a scored call: each recorded token's log-probability goes beside it
+  // a forced call takes the scored kernels' forced twins: scored as well, into a context-owned scratch when the caller did
+  // not ask for scores (merged: sub-batch j's rows of it from its first sentence on, Tmax_j <= Tmax)
+  // a sampled call takes their sampled twins, with or without a prefix: scored in the same way
+  const bool forced = call.forced;
+  const bool sampled = call.sampled;
+  const bool scored = call.scored || forced || sampled;
+  if ((forced || sampled) && !call.scored) {
     HIPCHK(c->fp_scratch.reserve(R * Tmax * 4));
-    for (int j = 0; mp && j < mp->n; ++j) mp->scores[j] = c->fp_scratch.as<float>() + (size_t)mp->out[j].first * Tmax;
+    for (int j = 0; mp && j < mp->n; ++j) mp->opt[j].scores = c->fp_scratch.as<float>() + (size_t)mp->out[j].first * Tmax;
   }
-  float *const d_scores = scored && !mp ? (c->sc_call ? c->sc_dev : c->fp_scratch.as<float>()) : nullptr;
+  float *const d_scores = scored && !mp ? (call.scored ? call.dev.scores : c->fp_scratch.as<float>()) : nullptr;
   if (scored && !mp && !d_scores) return fail(-1, "scores: no destination for this batch");
   for (int j = 0; scored && mp && j < mp->n; ++j)
-    if (!mp->scores[j]) return fail(-1, "scores: no destination for batch %d", j);
-  if (forced && !mp && !(c->fp_ids && c->fp_len)) return fail(-1, "target prefix: none for this batch");
+    if (!mp->opt[j].scores) return fail(-1, "scores: no destination for batch %d", j);
+  if (forced && !mp && !(call.dev.prefix_ids && call.dev.prefix_len)) return fail(-1, "target prefix: none for this batch");
   for (int j = 0; forced && mp && j < mp->n; ++j)
-    if (!mp->prefix_ids[j] || !mp->prefix_len[j]) return fail(-1, "target prefix: none for batch %d", j);
+    if (!mp->opt[j].prefix_ids || !mp->opt[j].prefix_len) return fail(-1, "target prefix: none for batch %d", j);
   if (lean) {
     PackArgs job;
     if (n_sl && mp) {
@@ -2620,22 +2486,22 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     }
     f.scores = d_scores;
     if (sampled) {
-      f.inv_T = c->sm_inv_T;
-      f.keys = mp ? nullptr : c->sm_keys;
-      for (int j = 0; mp && j < mp->n; ++j) f.sub_keys[j] = mp->keys[j];
+      f.inv_T = call.inv_T;
+      f.keys = mp ? nullptr : call.dev.keys;
+      for (int j = 0; mp && j < mp->n; ++j) f.sub_keys[j] = mp->opt[j].keys;
     }
     if (forced && !mp) {
-      f.prefix_ids = c->fp_ids;
-      f.prefix_len = c->fp_len;
+      f.prefix_ids = call.dev.prefix_ids;
+      f.prefix_len = call.dev.prefix_len;
     }
     if (mp) {
       f.n_sub = mp->n;
       f.sub_dense = mp->dense ? 1 : 0;
       for (int j = 0; j < mp->n; ++j) f.sub[j] = mp->out[j];
-      for (int j = 0; scored && j < mp->n; ++j) f.sub_scores[j] = mp->scores[j];
+      for (int j = 0; scored && j < mp->n; ++j) f.sub_scores[j] = mp->opt[j].scores;
       for (int j = 0; forced && j < mp->n; ++j) {
-        f.sub_prefix_ids[j] = mp->prefix_ids[j];
-        f.sub_prefix_len[j] = mp->prefix_len[j];
+        f.sub_prefix_ids[j] = mp->opt[j].prefix_ids;
+        f.sub_prefix_len[j] = mp->opt[j].prefix_len;
       }
       f.out_stride_wp = mp->stride_wp;
       f.out_stride_cs = mp->stride_cs;
@@ -2825,9 +2691,9 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     c->ticket_base += tickets;
     return 0;
   }
-  // a truncated call (TruncationCall) stores each step's logits and selects over them: one partial per row (sample_truncate.hip)
-  const bool truncated = sampled && c->tr_call;
-  if (c->tr_call && !truncated) return fail(-1, "sampling truncation: the call is not sampled");
+  // a truncated call stores each step's logits and selects over them: one partial per row (sample_truncate.hip)
+  const bool truncated = sampled && call.truncated;
+  if (call.truncated && !truncated) return fail(-1, "sampling truncation: the call is not sampled");
   const int n_parts = truncated ? 1 : dgemm_col_blocks(out.w.K, out.w.N, (int)R);
   if (truncated) HIPCHK(c->tr_logits.reserve(R * (size_t)out.w.N * 4));
   const EmbedArgs e = embed_args(c);
@@ -2840,8 +2706,8 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     HIPCHK(c->sm_seeds.reserve(2 * R * 4));
     HIPCHK(c->sm_part_mz.reserve(R * (size_t)n_parts * 4));
     HIPCHK(c->sm_part_zw.reserve(R * (size_t)n_parts * 4));
-    ss.inv_T = c->sm_inv_T;
-    ss.keys = c->sm_keys;
+    ss.inv_T = call.inv_T;
+    ss.keys = call.dev.keys;
     ss.seeds = c->sm_seeds.as<uint32_t>();
     ss.part_mz = c->sm_part_mz.as<float>();
     ss.part_zw = c->sm_part_zw.as<float>();
@@ -2850,8 +2716,8 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   if (forced) {
     HIPCHK(c->fp_col.reserve(R * 4));
     HIPCHK(c->fp_part_y.reserve(R * (size_t)n_parts * 4));
-    fs.ids = c->fp_ids;
-    fs.len = c->fp_len;
+    fs.ids = call.dev.prefix_ids;
+    fs.len = call.dev.prefix_len;
     fs.sl = ds.shortlist;
     fs.N = out.w.N;
     fs.fcol = c->fp_col.as<int>();
@@ -2908,8 +2774,8 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
       ta.B = (int)R;
       ta.N = out.w.N;
       ta.inv_T = ss.inv_T;
-      ta.top_k = c->tr_k;
-      ta.top_p = c->tr_p;
+      ta.top_k = call.top_k;
+      ta.top_p = call.top_p;
       ta.seeds = ss.seeds;
       ta.shortlist = ds.shortlist;
       ta.fcol = g.fcol;
@@ -2928,18 +2794,18 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
                                              c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs, &ss);
     if (he != hipSuccess) rc = fail((int)he, "final record: %s", hipGetErrorString(he));
   }
-  if (!rc && c->cs_call) {  // the selection over the rows just written (consensus.hip): one launch behind the last step
+  if (!rc && call.consensus) {  // the selection over the rows just written (consensus.hip): one launch behind the last step
     ConsensusArgs ca;
     ca.ids = d_out_ids;
     ca.len = d_out_len;
-    ca.row_src = c->fo_row_src;
+    ca.row_src = c->call.row_src;
     ca.N = (uint32_t)R;
     ca.T = (uint32_t)Tmax;
     ca.B = (uint32_t)B;
-    ca.max_order = c->cs_order;
-    ca.beta2 = c->cs_beta2;
-    ca.utility = c->cs_dev_util;
-    ca.best = c->cs_dev_best;
+    ca.max_order = call.cs_order;
+    ca.beta2 = call.cs_beta2;
+    ca.utility = call.cs_dev_util;
+    ca.best = call.cs_dev_best;
     ProfScope p(c, SLIMT_HIP_K_CONSENSUS, 0, 0);
     const hipError_t he = launch_consensus(ca, st);
     if (he != hipSuccess) rc = fail((int)he, "consensus: %s", hipGetErrorString(he));
@@ -3019,6 +2885,21 @@ int translate_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const uint3
   return translate_device(ctx, d_src_ids, d_lengths, ctx->shortlist.as<uint32_t>(), B, S, n,
                           limit_factor, eos_id, d_out_ids, d_out_len, d_align, steps_hint);
 }
+
+// One batch with a listed shortlist, every array and option in device memory: slimt_hip_translate_device behind its guard,
+// and a batch of slimt_hip_translate_many_device that goes on its own.
+int translate_device_batch(slimt_hip_ctx *ctx, const BatchOptions &user, const uint32_t *d_src_ids, const uint32_t *d_lengths,
+                           size_t B, size_t S, const uint32_t *d_shortlist, size_t n_shortlist, float limit_factor,
+                           uint32_t eos_id, uint32_t *d_out_ids, uint32_t *d_out_len, float *d_align, int steps_hint) {
+  if (!ctx || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len) return fail(-1, "null argument");
+  RCCHK(check_batch(ctx, B, S));
+  if (n_shortlist > (size_t)ctx->model->V) return fail(-1, "shortlist larger than the vocabulary");
+  if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
+  HIPCHK(hipSetDevice(ctx->model->device));
+  options_in_place(ctx, user);
+  return translate_device(ctx, d_src_ids, d_lengths, d_shortlist, B, S, n_shortlist, limit_factor,
+                          eos_id, d_out_ids, d_out_len, d_align, steps_hint);
+}
 }  // namespace
 
 extern "C" int slimt_hip_translate_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids,
@@ -3028,37 +2909,28 @@ extern "C" int slimt_hip_translate_device(slimt_hip_ctx *ctx, const uint32_t *d_
                                           uint32_t *d_out_ids, uint32_t *d_out_len,
                                           float *d_align, int steps_hint) {
   CallOptions opt(ctx, 1);
-  RCCHK(opt.rc());
-  if (!ctx || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len) return fail(-1, "null argument");
-  RCCHK(check_batch(ctx, B, S));
-  if (n_shortlist > (size_t)ctx->model->V) return fail(-1, "shortlist larger than the vocabulary");
-  if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
-  HIPCHK(hipSetDevice(ctx->model->device));
-  if (ctx->sc_call) ctx->sc_dev = ctx->sc_user;  // (device memory, like the other outputs)
-  if (ctx->fp_call) {  // (device memory: read where it is)
-    ctx->fp_ids = ctx->fp_user_ids;
-    ctx->fp_len = ctx->fp_user_len;
-  }
-  if (ctx->sm_call) ctx->sm_keys = ctx->sm_user_keys;  // (device memory, or NULL)
-  return translate_device(ctx, d_src_ids, d_lengths, d_shortlist, B, S, n_shortlist, limit_factor,
-                          eos_id, d_out_ids, d_out_len, d_align, steps_hint);
+  RCCHK(opt.rc);
+  return translate_device_batch(ctx, opt.user[0], d_src_ids, d_lengths, B, S, d_shortlist, n_shortlist, limit_factor, eos_id,
+                                d_out_ids, d_out_len, d_align, steps_hint);
 }
 
 namespace {
 // Model::forward on host buffers: validate, queue H2D + kernels + D2H on the ctx stream.
 // gen (nullable): the batch's lexical shortlist is generated on the device (Model.cc:117-120; shortlist / n_shortlist are
 // then not used): no host shortlist, no upload, no synchronisation in the asynchronous form.
-int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
-                   size_t S, const uint32_t *shortlist, size_t n_shortlist, float limit_factor,
+// user: the batch's options as the caller gave them, host memory: staged here into ctx->call.dev.
+int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const BatchOptions &user, const uint32_t *src_ids,
+                   const uint32_t *lengths, size_t B, size_t S, const uint32_t *shortlist, size_t n_shortlist, float limit_factor,
                    uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align, bool wait,
                    const uint32_t *row_src = nullptr) {
   if (!ctx || !src_ids || !lengths || !out_ids || !out_len) return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
-  // a fan-out call (FanoutCall, opened by the entry point): R = N rows named by row_src; every output, option and staging
-  // below is per row, the ids and lengths per source
-  const bool fanout = ctx->fo_call;
+  // a fan-out call (opened by the entry point): R = N rows named by row_src; every output, option and staging below is per
+  // row, the ids and lengths per source
+  CallState &call = ctx->call;
+  const bool fanout = call.fanout;
   if (fanout && !row_src) return fail(-1, "null argument");
-  const size_t R = fanout ? (size_t)ctx->fo_rows : B;
+  const size_t R = fanout ? (size_t)call.rows : B;
   StageClock hclk;
   const slimt_hip_model *m = ctx->model;
   uint32_t vmax = (uint32_t)m->V;
@@ -3098,35 +2970,30 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t 
   // Service: 12 contexts of equal batches ran strictly one after the other, 3.7 M tok/s).
   const bool persistent = persistent_path(ctx, S);
   hclk.lap(0);
-  if (ctx->fp_call) {  // (a forced call: the caller's host prefix, checked and staged in device memory)
-    const size_t Bs[1] = {R}, Ts[1] = {Tmax};
-    RCCHK(prefix_stage(ctx, 1, &ctx->fp_user_ids, &ctx->fp_user_len, Bs, Ts, &ctx->fp_ids, &ctx->fp_len));
-  }
-  if (ctx->sm_call) {  // (a sampled call: the caller's host keys, pinned in place or staged in device memory)
-    const size_t Bk[1] = {R};
-    RCCHK(keys_stage(ctx, 1, &ctx->sm_user_keys, Bk, &ctx->sm_keys));
-  }
+  // (a forced call: the caller's host prefix, checked; it and a sampled call's host keys pinned in place or staged)
+  call.dev = {};
+  RCCHK(stage_options(ctx, 1, &user, &R, &Tmax, &call.dev));
   if (fanout) {  // (the rows' sources: a pinned array in place, a pageable one staged in device memory)
-    ctx->fo_row_src = static_cast<const uint32_t *>(host_device_view(row_src));
-    if (!ctx->fo_row_src) {
+    call.row_src = static_cast<const uint32_t *>(host_device_view(row_src));
+    if (!call.row_src) {
       HIPCHK(ctx->fo_stage.reserve(R * 4));
       HIPCHK(hipMemcpyAsync(ctx->fo_stage.p, row_src, R * 4, hipMemcpyHostToDevice, st));
-      ctx->fo_row_src = ctx->fo_stage.as<uint32_t>();
+      call.row_src = ctx->fo_stage.as<uint32_t>();
     }
   }
-  if (ctx->cs_call) {  // (a fan-out call with the selection armed: utility [R] f64, then best [B] u32, staged on the device)
+  if (call.consensus) {  // (a fan-out call with the selection armed: utility [R] f64, then best [B] u32, staged on the device)
     HIPCHK(ctx->cs_stage.reserve(R * 8 + B * 4));
-    ctx->cs_dev_util = ctx->cs_stage.as<double>();
-    ctx->cs_dev_best = reinterpret_cast<uint32_t *>(ctx->cs_stage.as<char>() + R * 8);
+    call.cs_dev_util = ctx->cs_stage.as<double>();
+    call.cs_dev_best = reinterpret_cast<uint32_t *>(ctx->cs_stage.as<char>() + R * 8);
   }
-  float *const scores = ctx->sc_call ? ctx->sc_user : nullptr;  // (a scored call: the caller's [B][Tmax] host array)
+  float *const scores = user.scores;  // (a scored call: the caller's [B][Tmax] host array)
   if (!wait && persistent) {
     void *v_ids = host_device_view(src_ids), *v_len = host_device_view(lengths), *v_out = host_device_view(out_ids),
          *v_ol = host_device_view(out_len), *v_al = align ? host_device_view(align) : nullptr;
     void *v_sc = scores ? host_device_view(scores) : nullptr;
     hclk.lap(6);
     if (v_ids && v_len && v_out && v_ol && (!align || v_al) && (!scores || v_sc)) {
-      ctx->sc_dev = static_cast<float *>(v_sc);
+      call.dev.scores = static_cast<float *>(v_sc);
       // alignment rows (Model.cc:84-108) are staged in device memory and leave for the host once per
       // sentence, as whole 16-byte stores when its loop ends: written row by row across PCIe from
       // inside the step loop they cost the Service 28 % (12.9 against 17.9 M tok/s)
@@ -3139,7 +3006,7 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t 
   if (align) HIPCHK(ctx->align.reserve(R * Tmax * S * 4));
   if (scores) {
     HIPCHK(ctx->sc_stage.reserve(R * Tmax * 4));
-    ctx->sc_dev = ctx->sc_stage.as<float>();
+    call.dev.scores = ctx->sc_stage.as<float>();
   }
   HIPCHK(hipMemcpyAsync(ctx->ids.p, src_ids, B * S * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(ctx->lengths.p, lengths, B * 4, hipMemcpyHostToDevice, st));
@@ -3151,9 +3018,9 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t 
   HIPCHK(hipMemcpyAsync(out_len, ctx->out_len.p, R * 4, hipMemcpyDeviceToHost, st));
   if (align) HIPCHK(hipMemcpyAsync(align, ctx->align.p, R * Tmax * S * 4, hipMemcpyDeviceToHost, st));
   if (scores) HIPCHK(hipMemcpyAsync(scores, ctx->sc_stage.p, R * Tmax * 4, hipMemcpyDeviceToHost, st));
-  if (ctx->cs_call) {
-    HIPCHK(hipMemcpyAsync(ctx->cs_user_util, ctx->cs_dev_util, R * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(ctx->cs_user_best, ctx->cs_dev_best, B * 4, hipMemcpyDeviceToHost, st));
+  if (call.consensus) {
+    HIPCHK(hipMemcpyAsync(call.cs_util, call.cs_dev_util, R * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(call.cs_best, call.cs_dev_best, B * 4, hipMemcpyDeviceToHost, st));
   }
   if (wait) RCCHK(slimt_hip_ctx_synchronize(ctx));  // sleeps on a blocking-sync event (a worker per context: no spinning)
   return 0;
@@ -3166,8 +3033,8 @@ extern "C" int slimt_hip_translate(slimt_hip_ctx *ctx, const uint32_t *src_ids,
                                    float limit_factor, uint32_t eos_id, uint32_t *out_ids,
                                    uint32_t *out_len, float *align) {
   CallOptions opt(ctx, 1);
-  RCCHK(opt.rc());
-  return translate_host(ctx, nullptr, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
+  RCCHK(opt.rc);
+  return translate_host(ctx, nullptr, opt.user[0], src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, true);
 }
 
@@ -3177,14 +3044,14 @@ extern "C" int slimt_hip_translate_async(slimt_hip_ctx *ctx, const uint32_t *src
                                          float limit_factor, uint32_t eos_id, uint32_t *out_ids,
                                          uint32_t *out_len, float *align) {
   CallOptions opt(ctx, 1);
-  RCCHK(opt.rc());
-  return translate_host(ctx, nullptr, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
+  RCCHK(opt.rc);
+  return translate_host(ctx, nullptr, opt.user[0], src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id,
                         out_ids, out_len, align, false);
 }
 
 // ---- fan-out: N decoder rows over B sources encoded once (include/slimt_hip.h, slimt_hip_translate_fanout*) ------------
-// translate_host / translate_device above with the outputs and options counted by row (FanoutCall); decode_fanout.hip has
-// the attention that looks a row's source up.
+// translate_host / translate_device above with the outputs and options counted by row (CallOptions::open_fanout);
+// decode_fanout.hip has the attention that looks a row's source up.
 namespace {
 int translate_fanout_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
                           size_t S, const uint32_t *row_src, size_t N, const uint32_t *shortlist, size_t n_shortlist,
@@ -3196,11 +3063,10 @@ int translate_fanout_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const ui
   for (size_t r = 0; r < N; ++r)
     if (row_src[r] >= B) return fail(-1, "fan-out: row %zu names source %u, the call has %zu", r, row_src[r], B);
   if (!ctx) return fail(-1, "null argument");
-  RCCHK(opt.rc());
-  FanoutCall fo(ctx, N);
-  RCCHK(fo.rc);
-  return translate_host(ctx, gen, src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id, out_ids, out_len, align,
-                        wait, row_src);
+  RCCHK(opt.rc);
+  RCCHK(opt.open_fanout(N));
+  return translate_host(ctx, gen, opt.user[0], src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id, out_ids,
+                        out_len, align, wait, row_src);
 }
 }  // namespace
 
@@ -3234,25 +3100,17 @@ extern "C" int slimt_hip_translate_fanout_device(slimt_hip_ctx *ctx, const uint3
                                                  uint32_t eos_id, uint32_t *d_out_ids, uint32_t *d_out_len, float *d_align,
                                                  int steps_hint) {
   CallOptions opt(ctx, 1, true);
-  RCCHK(opt.rc());
-  FanoutCall fo(ctx, N);
-  RCCHK(fo.rc);
+  RCCHK(opt.rc);
+  RCCHK(opt.open_fanout(N));
   if (!ctx || !d_src_ids || !d_lengths || !d_row_src || !d_out_ids || !d_out_len) return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
   if (n_shortlist > (size_t)ctx->model->V) return fail(-1, "shortlist larger than the vocabulary");
   if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
   HIPCHK(hipSetDevice(ctx->model->device));
-  ctx->fo_row_src = d_row_src;
-  if (ctx->cs_call) {  // (device memory, like the other outputs: best [B], utility [N])
-    ctx->cs_dev_best = ctx->cs_user_best;
-    ctx->cs_dev_util = ctx->cs_user_util;
-  }
-  if (ctx->sc_call) ctx->sc_dev = ctx->sc_user;  // (device memory, like the other outputs; [N][Tmax])
-  if (ctx->fp_call) {
-    ctx->fp_ids = ctx->fp_user_ids;
-    ctx->fp_len = ctx->fp_user_len;
-  }
-  if (ctx->sm_call) ctx->sm_keys = ctx->sm_user_keys;
+  ctx->call.row_src = d_row_src;
+  ctx->call.cs_dev_best = ctx->call.cs_best;  // (device memory, like the other outputs: best [B], utility [N])
+  ctx->call.cs_dev_util = ctx->call.cs_util;
+  options_in_place(ctx, opt.user[0]);  // (scores [N][Tmax], prefix and keys by row)
   return translate_device(ctx, d_src_ids, d_lengths, d_shortlist, B, S, n_shortlist, limit_factor, eos_id, d_out_ids, d_out_len,
                           d_align, steps_hint);
 }
@@ -3376,35 +3234,29 @@ extern "C" size_t slimt_hip_translate_many_rows(const size_t *B, size_t n_batche
 extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_hip_batch *batches, size_t n_batches, size_t S,
                                                float limit_factor, uint32_t eos_id, int steps_hint) {
   CallOptions opt(ctx, n_batches);
-  RCCHK(opt.rc());
+  RCCHK(opt.rc);
   if (!ctx || !batches || n_batches == 0) return fail(-1, "null argument");
   HIPCHK(hipSetDevice(ctx->model->device));
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
   MergePlan mp;
   size_t rows = 0;
-  const bool mergeable = n_batches > 1 && n_batches <= (size_t)kMaxMerge && !ctx->tr_call;  // (truncated: batch by batch)
+  const bool mergeable = n_batches > 1 && n_batches <= (size_t)kMaxMerge && !ctx->call.truncated;  // (truncated: batch by batch)
   if (mergeable)
     RCCHK(build_merge_plan(ctx, batches, n_batches, S, Tmax, limit_factor, steps_hint, nullptr, mp, rows, kMergeTile));
-  for (size_t j = 0; mergeable && ctx->sc_call && j < n_batches; ++j) mp.scores[j] = opt.sc.dst[j];
-  for (size_t j = 0; mergeable && ctx->fp_call && j < n_batches; ++j) {
-    mp.prefix_ids[j] = opt.pc.ids[j];
-    mp.prefix_len[j] = opt.pc.len[j];
-  }
-  for (size_t j = 0; mergeable && ctx->sm_call && j < n_batches; ++j) mp.keys[j] = opt.smc.keys[j];
+  for (size_t j = 0; mergeable && j < n_batches; ++j) mp.opt[j] = opt.user[j];  // (device memory: addressed where it is)
   if (mergeable && rows <= ctx->max_B && rows * S <= ctx->max_M && S <= ctx->max_S && merge_supported(ctx, rows, S))
     return translate_device(ctx, batches[0].src_ids, batches[0].lengths, batches[0].shortlist, rows, S, (size_t)mp.max_N,
                             limit_factor, eos_id, batches[0].out_ids, batches[0].out_len, batches[0].align, steps_hint, nullptr,
                             nullptr, 0, nullptr, &mp);
   for (size_t j = 0; j < n_batches; ++j) {  // batch by batch, in order, on the same stream
     const slimt_hip_batch &b = batches[j];
-    arm_batch(ctx, opt.sc.dst.data(), opt.pc, opt.smc, j);
     // (a truncated call is never merged, so it must give here what a merged launch gives: the launch's step budget is the
     // longest batch's, and a shorter batch takes at most its own Tmax_j -- build_merge_plan's rule. Other calls that come
     // this way keep the budget as given, as before.)
     const size_t Sj = b.S ? b.S : S, Tj = std::max<size_t>(1, (size_t)(limit_factor * (float)Sj));
-    const int hint = ctx->tr_call && steps_hint > 0 ? std::min(steps_hint, (int)Tj) : steps_hint;
-    RCCHK(slimt_hip_translate_device(ctx, b.src_ids, b.lengths, b.B, Sj, b.shortlist, b.n_shortlist, limit_factor,
-                                     eos_id, b.out_ids, b.out_len, b.align, hint));
+    const int hint = ctx->call.truncated && steps_hint > 0 ? std::min(steps_hint, (int)Tj) : steps_hint;
+    RCCHK(translate_device_batch(ctx, opt.user[j], b.src_ids, b.lengths, b.B, Sj, b.shortlist, b.n_shortlist, limit_factor,
+                                 eos_id, b.out_ids, b.out_len, b.align, hint));
   }
   return 0;
 }
@@ -3412,14 +3264,14 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
 extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hip_batch *batches, size_t n_batches, size_t S,
                                               float limit_factor, uint32_t eos_id) {
   CallOptions opt(ctx, n_batches);
-  RCCHK(opt.rc());
+  RCCHK(opt.rc);
   if (!ctx || !batches || n_batches == 0) return fail(-1, "null argument");
   const slimt_hip_model *m = ctx->model;
   HIPCHK(hipSetDevice(m->device));
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
-  bool merged = n_batches > 1 && n_batches <= (size_t)kMaxMerge && S <= ctx->max_S && !ctx->tr_call;
+  bool merged = n_batches > 1 && n_batches <= (size_t)kMaxMerge && S <= ctx->max_S && !ctx->call.truncated;
   slimt_hip_batch dev[kMaxMerge];
-  float *dev_sc[kMaxMerge] = {};  // (scored: the device views of the pinned score arrays)
+  MergePlan mp;  // (its opt[j].scores: the device views of the pinned score arrays)
   bool any_align = false;
   size_t rows = 0;
   for (size_t j = 0; merged && j < n_batches; ++j) {
@@ -3428,7 +3280,8 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
     // (ids and lengths only while a merged launch is still possible: else each batch's translate_host checks its own)
     RCCHK(check_host_batch(b, j, S, (uint32_t)m->V, merged));
     if (!pinned_batch_view(b, dev[j])) merged = false;
-    if (ctx->sc_call && !(dev_sc[j] = static_cast<float *>(host_device_view(opt.sc.dst[j])))) merged = false;
+    float *const sc = opt.user[j].scores;
+    if (sc && !(mp.opt[j].scores = static_cast<float *>(host_device_view(sc)))) merged = false;
     any_align = any_align || b.align != nullptr;
     rows += b.B;  // (one shortlist for all: the sub-batches follow each other densely)
   }
@@ -3436,9 +3289,8 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   if (!merged) {
     for (size_t j = 0; j < n_batches; ++j) {
       const slimt_hip_batch &b = batches[j];
-      arm_batch(ctx, opt.sc.dst.data(), opt.pc, opt.smc, j);
-      RCCHK(translate_host(ctx, nullptr, b.src_ids, b.lengths, b.B, b.S ? b.S : S, b.shortlist, b.n_shortlist, limit_factor, eos_id,
-                           b.out_ids, b.out_len, b.align, false));
+      RCCHK(translate_host(ctx, nullptr, opt.user[j], b.src_ids, b.lengths, b.B, b.S ? b.S : S, b.shortlist, b.n_shortlist,
+                           limit_factor, eos_id, b.out_ids, b.out_len, b.align, false));
     }
     return 0;
   }
@@ -3454,11 +3306,8 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
     dev[j].shortlist = n_sl ? ctx->shortlist.as<uint32_t>() : nullptr;
     dev[j].n_shortlist = n_sl;
   }
-  MergePlan mp;
   RCCHK(build_merge_plan(ctx, dev, n_batches, S, Tmax, limit_factor, 0, any_align ? ctx->align.as<float>() : nullptr, mp, rows));
-  for (size_t j = 0; ctx->sc_call && j < n_batches; ++j) mp.scores[j] = dev_sc[j];
-  if (ctx->fp_call) RCCHK(prefix_stage_batches(ctx, opt.pc, batches, n_batches, S, limit_factor, mp.prefix_ids, mp.prefix_len));
-  if (ctx->sm_call) RCCHK(keys_stage_batches(ctx, opt.smc, batches, n_batches, mp.keys));
+  RCCHK(stage_options(ctx, batches, n_batches, S, limit_factor, opt.user.data(), mp.opt));
   return translate_device(ctx, dev[0].src_ids, dev[0].lengths, dev[0].shortlist, rows, S, (size_t)mp.max_N, limit_factor, eos_id,
                           dev[0].out_ids, dev[0].out_len, any_align ? ctx->align.as<float>() : nullptr, (int)Tmax, nullptr,
                           any_align ? dev[0].align : nullptr, 0, nullptr, &mp);
@@ -3880,38 +3729,28 @@ extern "C" int slimt_hip_translate_device_generated(slimt_hip_ctx *ctx, slimt_hi
                                                     uint32_t *d_out_ids, uint32_t *d_out_len,
                                                     float *d_align, int steps_hint) {
   CallOptions opt(ctx, 1);
-  RCCHK(opt.rc());
+  RCCHK(opt.rc);
   if (!ctx || !sl || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len)
     return fail(-1, "null argument");
   RCCHK(check_batch(ctx, B, S));
   RCCHK(check_generator(ctx, sl));
   HIPCHK(hipSetDevice(ctx->model->device));
-  if (ctx->sc_call) ctx->sc_dev = ctx->sc_user;  // (device memory, like the other outputs)
-  if (ctx->fp_call) {  // (device memory: read where it is)
-    ctx->fp_ids = ctx->fp_user_ids;
-    ctx->fp_len = ctx->fp_user_len;
-  }
-  if (ctx->sm_call) ctx->sm_keys = ctx->sm_user_keys;  // (device memory, or NULL)
+  options_in_place(ctx, opt.user[0]);
   return translate_generated(ctx, sl, d_src_ids, d_lengths, B, S, limit_factor, eos_id, d_out_ids, d_out_len,
                              d_align, steps_hint, nullptr);
 }
 
 // ---- merged launches whose batches each get THEIR lexical shortlist, generated inside the encoder launch ---------------
 namespace {
-// The per-batch options of a translate_many_generated call, one entry per batch where a pointer is set. The *_dev arrays hold
-// what the kernels read and write (device memory, or the device views of pinned arrays; for the prefixes and keys also
-// staged copies); the *_host members what the caller gave, for the fallback through translate_host.
+// What a translate_many_generated call has beside its batches. dev[j]: batch j's options as the kernels address them (device
+// memory, or the device views of pinned arrays; for the prefixes and keys also staged copies).
 struct ManyGenerated {
-  float *const *sc_dev = nullptr;   // a scored call: each batch's score destination ...
-  float *const *sc_host = nullptr;  // ... and, with `host`, as the caller gave it
-  const uint32_t *const *fp_dev_ids = nullptr;  // a forced call: each batch's prefix in device memory ...
-  const uint32_t *const *fp_dev_len = nullptr;
-  const PrefixCall *fp_host = nullptr;  // ... and, with `host`, as the caller gave it
-  const uint64_t *const *sm_dev = nullptr;  // a sampled call: each batch's keys as the kernels read them ...
-  const SampleCall *sm_host = nullptr;      // ... and, with `host`, as the caller gave them
-  // the asynchronous entry point: the same batches with the caller's HOST pointers -- what the batch-by-batch fallback hands
-  // to translate_host, which knows when the kernels can use pinned arrays in place
-  const slimt_hip_batch *host = nullptr;
+  const BatchOptions *dev = nullptr;
+  // the asynchronous entry point: the same batches with the caller's HOST pointers, and host[j], their options as the caller
+  // gave them -- what the batch-by-batch fallback hands to translate_host, which knows when the kernels can use pinned
+  // arrays in place
+  const slimt_hip_batch *host_batches = nullptr;
+  const BatchOptions *host = nullptr;
   bool stage_align = false;  // the alignment rows are staged in ctx->align (the batches' `align` are pinned views)
   int steps_hint = 0;
 };
@@ -3934,15 +3773,14 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
     any_align = any_align || dev[j].align != nullptr;
   }
   static const bool fold = !(std::getenv("SLIMT_SHORTLIST_FOLD") && std::getenv("SLIMT_SHORTLIST_FOLD")[0] == '0');
-  const bool merged = n > 1 && n <= (size_t)kMaxMerge && !ctx->tr_call && S <= ctx->max_S && rows <= ctx->max_B && rows * S <= ctx->max_M &&
+  const bool merged = n > 1 && n <= (size_t)kMaxMerge && !ctx->call.truncated && S <= ctx->max_S && rows <= ctx->max_B && rows * S <= ctx->max_M &&
                       merge_supported(ctx, rows, S) && fold &&
                       shortlist_in_launch_lds_bytes((int)sl->source_vocab, (int)sl->target_vocab) <= 64 * 1024;
-  if (!merged && o.host) {
+  if (!merged && o.host_batches) {
     for (size_t j = 0; j < n; ++j) {
-      const slimt_hip_batch &b = o.host[j];
-      arm_batch(ctx, o.sc_host, *o.fp_host, *o.sm_host, j);
-      RCCHK(translate_host(ctx, sl, b.src_ids, b.lengths, b.B, b.S ? b.S : S, nullptr, 0, limit_factor, eos_id, b.out_ids,
-                           b.out_len, b.align, false));
+      const slimt_hip_batch &b = o.host_batches[j];
+      RCCHK(translate_host(ctx, sl, o.host[j], b.src_ids, b.lengths, b.B, b.S ? b.S : S, nullptr, 0, limit_factor, eos_id,
+                           b.out_ids, b.out_len, b.align, false));
     }
     return 0;
   }
@@ -3956,12 +3794,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
         staging = ctx->align.as<float>();
       }
       RCCHK(check_batch(ctx, b.B, Sj));
-      if (ctx->sc_call) ctx->sc_dev = o.sc_dev[j];
-      if (ctx->fp_call) {
-        ctx->fp_ids = o.fp_dev_ids[j];
-        ctx->fp_len = o.fp_dev_len[j];
-      }
-      if (ctx->sm_call) ctx->sm_keys = o.sm_dev[j];
+      options_in_place(ctx, o.dev[j]);
       RCCHK(translate_generated(ctx, sl, b.src_ids, b.lengths, b.B, Sj, limit_factor, eos_id, b.out_ids, b.out_len,
                                 staging ? staging : b.align, steps_hint > 0 ? std::min(steps_hint, (int)Tj) : (stage_align ? (int)Tj : 0),
                                 staging ? b.align : nullptr));
@@ -3981,12 +3814,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
   if (any_align && stage_align) HIPCHK(ctx->align.reserve(align_staging_bytes(ctx, rows, S, Tmax, limit_factor)));
   MergePlan mp;
   RCCHK(build_merge_plan(ctx, plan, n, S, Tmax, limit_factor, steps_hint, any_align && stage_align ? ctx->align.as<float>() : nullptr, mp, rows, kMergeTile));
-  for (size_t j = 0; ctx->sc_call && j < n; ++j) mp.scores[j] = o.sc_dev[j];
-  for (size_t j = 0; ctx->fp_call && j < n; ++j) {
-    mp.prefix_ids[j] = o.fp_dev_ids[j];
-    mp.prefix_len[j] = o.fp_dev_len[j];
-  }
-  for (size_t j = 0; ctx->sm_call && j < n; ++j) mp.keys[j] = o.sm_dev[j];
+  for (size_t j = 0; j < n; ++j) mp.opt[j] = o.dev[j];
   void *hint_dev = nullptr;
   if (hipHostGetDevicePointer(&hint_dev, hint, 0) == hipSuccess) a.n_out_host = static_cast<uint32_t *>(hint_dev);
   return translate_device(ctx, plan[0].src_ids, plan[0].lengths, ctx->shortlist.as<uint32_t>(), rows, S, V, limit_factor, eos_id,
@@ -4000,7 +3828,7 @@ extern "C" int slimt_hip_translate_many_device_generated(slimt_hip_ctx *ctx, sli
                                                          size_t n_batches, size_t S, float limit_factor, uint32_t eos_id,
                                                          int steps_hint) {
   CallOptions opt(ctx, n_batches);
-  RCCHK(opt.rc());
+  RCCHK(opt.rc);
   if (!ctx || !sl || !batches || n_batches == 0) return fail(-1, "null argument");
   RCCHK(check_generator(ctx, sl));
   for (size_t j = 0; j < n_batches; ++j) {
@@ -4011,57 +3839,42 @@ extern "C" int slimt_hip_translate_many_device_generated(slimt_hip_ctx *ctx, sli
   HIPCHK(hipSetDevice(ctx->model->device));
   ManyGenerated o;
   o.steps_hint = steps_hint;
-  if (ctx->sc_call) o.sc_dev = opt.sc.dst.data();
-  if (ctx->fp_call) {
-    o.fp_dev_ids = opt.pc.ids.data();
-    o.fp_dev_len = opt.pc.len.data();
-  }
-  if (ctx->sm_call) o.sm_dev = opt.smc.keys.data();
+  o.dev = opt.user.data();  // (device memory: addressed where it is)
   return translate_many_generated(ctx, sl, batches, n_batches, S, limit_factor, eos_id, o);
 }
 
 extern "C" int slimt_hip_translate_many_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const slimt_hip_batch *batches,
                                                         size_t n_batches, size_t S, float limit_factor, uint32_t eos_id) {
   CallOptions opt(ctx, n_batches);
-  RCCHK(opt.rc());
+  RCCHK(opt.rc);
   if (!ctx || !sl || !batches || n_batches == 0) return fail(-1, "null argument");
   RCCHK(check_generator(ctx, sl));
   const slimt_hip_model *m = ctx->model;
   HIPCHK(hipSetDevice(m->device));
   const uint32_t vmax = (uint32_t)std::min((size_t)m->V, sl->source_vocab);
   slimt_hip_batch dev[kMaxMerge];
-  float *dev_sc[kMaxMerge] = {};  // (scored: the device views of the pinned score arrays)
+  BatchOptions dev_opt[kMaxMerge];  // (scores: the device views of the pinned arrays; prefixes and keys: those, or staged copies)
   bool pinned = n_batches <= (size_t)kMaxMerge;
   for (size_t j = 0; j < n_batches; ++j) {  // (every batch in full before anything is queued)
     RCCHK(check_host_batch(batches[j], j, S, vmax, true));
     if (!pinned) continue;
     if (!pinned_batch_view(batches[j], dev[j])) pinned = false;
-    if (ctx->sc_call && !(dev_sc[j] = static_cast<float *>(host_device_view(opt.sc.dst[j])))) pinned = false;
+    float *const sc = opt.user[j].scores;
+    if (sc && !(dev_opt[j].scores = static_cast<float *>(host_device_view(sc)))) pinned = false;
   }
-  const uint32_t *fp_ids[kMaxMerge] = {}, *fp_len[kMaxMerge] = {};  // (forced: the staged prefixes)
-  if (pinned && ctx->fp_call) RCCHK(prefix_stage_batches(ctx, opt.pc, batches, n_batches, S, limit_factor, fp_ids, fp_len));
-  const uint64_t *sm_keys[kMaxMerge] = {};  // (sampled: the keys' pinned views or staged copies)
-  if (pinned && ctx->sm_call) RCCHK(keys_stage_batches(ctx, opt.smc, batches, n_batches, sm_keys));
   if (pinned) {
+    RCCHK(stage_options(ctx, batches, n_batches, S, limit_factor, opt.user.data(), dev_opt));
     ManyGenerated o;
-    o.host = batches;
+    o.host_batches = batches;
+    o.host = opt.user.data();
+    o.dev = dev_opt;
     o.stage_align = true;
-    if (ctx->sc_call) {
-      o.sc_dev = dev_sc;
-      o.sc_host = opt.sc.dst.data();
-    }
-    o.fp_dev_ids = fp_ids;
-    o.fp_dev_len = fp_len;
-    o.fp_host = &opt.pc;
-    o.sm_dev = sm_keys;
-    o.sm_host = &opt.smc;
     return translate_many_generated(ctx, sl, dev, n_batches, S, limit_factor, eos_id, o);
   }
   for (size_t j = 0; j < n_batches; ++j) {  // pageable arrays, or too many batches: one by one through the copying path
     const slimt_hip_batch &b = batches[j];
-    arm_batch(ctx, opt.sc.dst.data(), opt.pc, opt.smc, j);
-    RCCHK(translate_host(ctx, sl, b.src_ids, b.lengths, b.B, b.S ? b.S : S, nullptr, 0, limit_factor, eos_id, b.out_ids, b.out_len,
-                         b.align, false));
+    RCCHK(translate_host(ctx, sl, opt.user[j], b.src_ids, b.lengths, b.B, b.S ? b.S : S, nullptr, 0, limit_factor, eos_id,
+                         b.out_ids, b.out_len, b.align, false));
   }
   return 0;
 }
@@ -4070,9 +3883,10 @@ extern "C" int slimt_hip_translate_generated(slimt_hip_ctx *ctx, slimt_hip_short
                                              const uint32_t *lengths, size_t B, size_t S, float limit_factor,
                                              uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *align) {
   CallOptions opt(ctx, 1);
-  RCCHK(opt.rc());
+  RCCHK(opt.rc);
   if (!sl) return fail(-1, "null argument");
-  return translate_host(ctx, sl, src_ids, lengths, B, S, nullptr, 0, limit_factor, eos_id, out_ids, out_len, align, true);
+  return translate_host(ctx, sl, opt.user[0], src_ids, lengths, B, S, nullptr, 0, limit_factor, eos_id, out_ids, out_len, align,
+                        true);
 }
 
 extern "C" int slimt_hip_translate_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl,
@@ -4080,9 +3894,10 @@ extern "C" int slimt_hip_translate_async_generated(slimt_hip_ctx *ctx, slimt_hip
                                                    size_t S, float limit_factor, uint32_t eos_id,
                                                    uint32_t *out_ids, uint32_t *out_len, float *align) {
   CallOptions opt(ctx, 1);
-  RCCHK(opt.rc());
+  RCCHK(opt.rc);
   if (!sl) return fail(-1, "null argument");
-  return translate_host(ctx, sl, src_ids, lengths, B, S, nullptr, 0, limit_factor, eos_id, out_ids, out_len, align, false);
+  return translate_host(ctx, sl, opt.user[0], src_ids, lengths, B, S, nullptr, 0, limit_factor, eos_id, out_ids, out_len, align,
+                        false);
 }
 
 // ---- teacher-forced scoring: every target position in one tall pass (include/slimt_hip.h, slimt_hip_score*) -----------
@@ -4090,7 +3905,7 @@ extern "C" int slimt_hip_translate_async_generated(slimt_hip_ctx *ctx, slimt_hip
 // cache of the stage path (encode_device / decode_setup), then per chunk of whole sentences the decoder layers as tall
 // GEMMs (launch_gemm: 128-row tiles from 1024 rows on, bit-identical to the step-wise dgemm) around the scan, the
 // attention and the scoring output layer. None of it reads or consumes what set_scores / set_target_prefix / set_sampling
-// armed: these entry points construct no ScoreCall / PrefixCall / SampleCall.
+// armed: these entry points open no CallOptions.
 namespace {
 constexpr size_t kScoreChunkRows = 8192;         // rows of a chunk (whole sentences; a single sentence may exceed it)
 constexpr size_t kScoreMaxT = 65536;             // longest target

@@ -54,6 +54,46 @@ struct DecLayerW {
   LnW ffn_ln;
 };
 
+// One batch's arrays for the per-batch options of a translate call (slimt_hip_ctx_set_scores / _target_prefix / _sampling),
+// each nullptr when not given. The same type holds them as the caller gave them (host or device memory, by entry point) and
+// as the kernels address them (device memory, or the device view of a pinned array): an instance's name and place say which.
+struct BatchOptions {
+  float *scores = nullptr;                                      // [rows][Tmax]
+  const uint32_t *prefix_ids = nullptr, *prefix_len = nullptr;  // [rows][Tmax], [rows]
+  const uint64_t *keys = nullptr;                               // [rows]; a sampled call without: the rows' indices
+};
+
+// What the slimt_hip_ctx_set_* functions armed for the next translate call. A vector's size is the number of batches it was
+// armed for (0: not armed); truncation is armed by a top_k or top_p that truncates, consensus by an order above 0.
+struct ArmedOptions {
+  std::vector<float *> scores;
+  std::vector<const uint32_t *> prefix_ids, prefix_len;
+  std::vector<const uint64_t *> keys;  // (an entry may be NULL)
+  float inv_T = 0.0f;                  // 1 / the sampling temperature
+  uint32_t top_k = 0;
+  float top_p = 1.0f;
+  int cs_order = 0, cs_beta2 = 0;
+  uint32_t *cs_best = nullptr;
+  double *cs_util = nullptr;
+};
+
+// The translate call in progress: filled by its CallOptions (engine.cpp), reset as a whole when the entry point returns.
+struct CallState {
+  bool scored = false, forced = false, sampled = false;
+  bool truncated = false;  // sampled, to the top_k largest and the nucleus of mass top_p: per-stage decoder, never merged
+  bool fanout = false;     // `rows` decoder rows over the B sources: per-stage decoder, never merged, like a truncated call
+  bool consensus = false;  // a fan-out call that selects among each source's rows
+  float inv_T = 0.0f;
+  uint32_t top_k = 0;
+  float top_p = 1.0f;
+  int cs_order = 0, cs_beta2 = 0;
+  int rows = 0;                       // fan-out: N <= max_B (the per-row decoder workspaces are sized by max_B)
+  const uint32_t *row_src = nullptr;  // ... [rows] as the kernels read it (device memory)
+  uint32_t *cs_best = nullptr, *cs_dev_best = nullptr;  // consensus: best [B] and utility [rows] as the caller gave
+  double *cs_util = nullptr, *cs_dev_util = nullptr;    // them, and as the kernel writes them (the caller's, or cs_stage)
+  BatchOptions dev;  // the current unmerged batch's options as the kernels address them (a merged launch: MergePlan::opt)
+};
+
 }  // namespace slimt_hip
 
 struct slimt_hip_ctx;
@@ -189,55 +229,21 @@ struct slimt_hip_ctx {
   // decoder workspace
   slimt_hip::DevBuf dx, dx_pre, dh, datt8, dout, df8, state;
   slimt_hip::DevBuf part_val, part_idx;
-  // per-token scores (include/slimt_hip.h, slimt_hip_ctx_set_scores): armed for the NEXT translate call, which consumes them
-  bool sc_armed = false;
-  std::vector<float *> sc_next;
-  bool sc_call = false;      // the call in progress scores (engine.cpp, ScoreCall)
-  float *sc_user = nullptr;  // the current batch's destination as the caller gave it (host or device memory)
-  float *sc_dev = nullptr;   // ... the address the kernels write: sc_user, its pinned view, or sc_stage
-  slimt_hip::DevBuf part_sum, sc_stage;  // the step-wise path's partial sums; device staging of a host call's scores
-  // target prefixes (include/slimt_hip.h, slimt_hip_ctx_set_target_prefix): armed for the NEXT translate call, like the scores
-  bool fp_armed = false;
-  std::vector<const uint32_t *> fp_next_ids, fp_next_len;
-  bool fp_call = false;                 // the call in progress is forced (engine.cpp, PrefixCall)
-  const uint32_t *fp_user_ids = nullptr;  // the current batch's prefix as the caller gave it (host or device memory)
-  const uint32_t *fp_user_len = nullptr;
-  const uint32_t *fp_ids = nullptr;     // the current batch's prefix as the kernels read it (device memory)
-  const uint32_t *fp_len = nullptr;
-  slimt_hip::DevBuf fp_stage;           // device staging of host prefixes ([B][Tmax] ids, then [B] lengths, per batch)
-  slimt_hip::DevBuf fp_scratch;         // score destination of forced calls without scores
-  slimt_hip::DevBuf fp_col, fp_part_y;  // the step-wise path's forced columns and captured logits
-  // sampling (include/slimt_hip.h, slimt_hip_ctx_set_sampling): armed for the NEXT translate call, like the scores and the prefix
-  bool sm_armed = false;
-  float sm_next_inv_T = 0.0f;
-  std::vector<const uint64_t *> sm_next_keys;  // one per batch, NULL: the batch's keys are its row indices
-  bool sm_call = false;                      // the call in progress is sampled (engine.cpp, SampleCall)
-  float sm_inv_T = 0.0f;                     // ... at 1 / this temperature
-  const uint64_t *sm_user_keys = nullptr;    // the current batch's keys as the caller gave them (host or device memory, or NULL)
-  const uint64_t *sm_keys = nullptr;         // ... as the kernels read them
-  slimt_hip::DevBuf sm_stage;                // device staging of pageable host keys
-  slimt_hip::DevBuf sm_seeds, sm_part_mz, sm_part_zw;  // the step-wise path's hash words and partials (kernels.h, SampledStep)
-  // truncation of sampled calls (slimt_hip_ctx_set_sampling_truncation): armed for the NEXT translate call beside the sampling
-  bool tr_armed = false;
-  uint32_t tr_next_k = 0;
-  float tr_next_p = 1.0f;
-  bool tr_call = false;         // the call in progress is truncated (engine.cpp, TruncationCall): per-stage decoder, never merged
-  uint32_t tr_k = 0;            // ... to the top_k largest (0: no top-k)
-  float tr_p = 1.0f;            // ... and the nucleus of mass top_p (1: no top-p)
-  slimt_hip::DevBuf tr_logits;  // [B][N] f32: the step's logits, reserved by the first truncated call
-  // fan-out (include/slimt_hip.h, slimt_hip_translate_fanout*): the call in progress decodes fo_rows rows over its B sources
-  // (engine.cpp, FanoutCall): per-stage decoder, never merged, like a truncated call
-  bool fo_call = false;
-  int fo_rows = 0;                      // N <= max_B: the per-row decoder workspaces are sized by max_B
-  const uint32_t *fo_row_src = nullptr;  // [fo_rows] as the kernels read it (device memory)
-  slimt_hip::DevBuf fo_stage;           // device staging of a host call's row_src
-  // consensus (include/slimt_hip.h, slimt_hip_ctx_set_fanout_consensus): armed for the next fan-out call, taken by its
-  // ConsensusCall (engine.cpp) like the scores; cs_dev_* are the arrays the kernel writes (the caller's, or cs_stage)
-  bool cs_armed = false, cs_call = false;
-  int cs_next_order = 0, cs_next_beta2 = 0, cs_order = 0, cs_beta2 = 0;
-  uint32_t *cs_next_best = nullptr, *cs_user_best = nullptr, *cs_dev_best = nullptr;
-  double *cs_next_util = nullptr, *cs_user_util = nullptr, *cs_dev_util = nullptr;
-  slimt_hip::DevBuf cs_stage;  // device staging of a host call's utility [N] f64 + best [B] u32
+  // The per-call options (include/slimt_hip.h, slimt_hip_ctx_set_*): `armed` is what the set functions wrote and nothing else
+  // writes; the next translate entry point moves it out into `call` (engine.cpp, CallOptions), whatever its outcome, and
+  // `call` is empty again when that entry point returns. Nothing else of the context says anything about the call in progress.
+  slimt_hip::ArmedOptions armed;
+  slimt_hip::CallState call;
+  // ... and their workspace, which outlives the calls:
+  slimt_hip::DevBuf part_sum, sc_stage;  // scores: the step-wise path's partial sums; device staging of a host call's scores
+  slimt_hip::DevBuf fp_stage;            // prefixes: device staging of host prefixes ([B][Tmax] ids, then [B] lengths, per batch)
+  slimt_hip::DevBuf fp_scratch;          // ... score destination of forced and sampled calls without scores
+  slimt_hip::DevBuf fp_col, fp_part_y;   // ... the step-wise path's forced columns and captured logits
+  slimt_hip::DevBuf sm_stage;            // sampling: device staging of pageable host keys
+  slimt_hip::DevBuf sm_seeds, sm_part_mz, sm_part_zw;  // ... the step-wise path's hash words and partials (kernels.h, SampledStep)
+  slimt_hip::DevBuf tr_logits;           // truncation: [B][N] f32, the step's logits, reserved by the first truncated call
+  slimt_hip::DevBuf fo_stage;            // fan-out: device staging of a host call's row_src
+  slimt_hip::DevBuf cs_stage;            // consensus: device staging of a host call's utility [N] f64 + best [B] u32
   slimt_hip::DevBuf prev, out_ids, out_len, finished, n_finished, align;
   slimt_hip::DevBuf shortlist;
   slimt_hip::DevBuf sl_scratch;  // bitmaps of slimt_hip_shortlist_generate_device (kept zeroed)

@@ -353,6 +353,86 @@ def test_async_fallbacks_equal_the_blocking_calls(hip, engines, n, pageable, opt
             p.free()
 
 
+def _many_device_with_options(ctx, batches, sls, prefixes, keys, steps_hint, generator=None):
+    """slimt_hip_translate_many_device[_generated] with scores, a forced prefix and sampling keys armed together, every
+    array in device memory; per batch (None, None, out, out_len, align) as _same_as_own_call reads them, and the scores"""
+    keep, args, outs, d_scs, d_pre, d_keys = [], [], [], [], [], []
+    for (ids, lens), sl, (p_ids, p_len), k in zip(batches, sls, prefixes, keys):
+        B, Sj = ids.shape
+        T = max(int(np.float32(1.5) * np.float32(Sj)), 1)
+        d_ids, d_len, d_sl = _dev(ids), _dev(lens), None if sl is None else _dev(sl)
+        d_out = torch.full((B, T), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
+        d_ol = torch.full((B,), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
+        d_al = torch.full((B, T, Sj), 7.25, dtype=torch.float32, device="cuda")
+        d_sc = torch.full((B, T), 7.5, dtype=torch.float32, device="cuda")
+        d_pi, d_pl = _dev(p_ids), _dev(p_len)
+        d_k = torch.from_numpy(np.ascontiguousarray(k).view(np.int64)).cuda()
+        keep.append((d_ids, d_len, d_sl, d_pi, d_pl, d_k))
+        outs.append((d_out, d_ol, d_al, d_sc))
+        d_scs.append(d_sc.data_ptr())
+        d_pre.append((d_pi.data_ptr(), d_pl.data_ptr()))
+        d_keys.append(d_k.data_ptr())
+        args.append((d_ids.data_ptr(), d_len.data_ptr(), B, 0 if d_sl is None else d_sl.data_ptr(), 0 if sl is None else sl.size,
+                     d_out.data_ptr(), d_ol.data_ptr(), d_al.data_ptr(), Sj))
+    ctx.translate_many_device(args, FALLBACK_S, 1.5, 0, steps_hint=steps_hint, generator=generator, scores=d_scs, prefix=d_pre,
+                              sampling=(0.8, d_keys))
+    ctx.synchronize()
+    return [((None, None, o.cpu().numpy().view(np.uint32), l.cpu().numpy().view(np.uint32), a.cpu().numpy()), s.cpu().numpy())
+            for o, l, a, s in outs]
+
+
+def test_device_fallback_hands_each_batch_its_options(hip, engines):
+    """slimt_hip_translate_many_device with a listed shortlist, nine batches (batch by batch): with scores, a forced prefix
+    and sampling keys armed together in device memory, each batch == slimt_hip_translate of it on the same context."""
+    from slimt_amd import synth
+    m, gm, _ = engines("tiny11", 6.0)
+    sl = synth.make_shortlist(m.V, 1024)
+    batches, prefixes, keys = _fallback_inputs(m.V, 9, sl, True)
+    ctx = hip.Context(gm, hip.translate_many_rows([ids.shape[0] for ids, _ in batches]), FALLBACK_S)
+    try:
+        assert ctx.plan(FALLBACK_S) == (True, True)
+        wants = [ctx.translate(ids, lens, sl, want_align=True, scores=True, prefix=p, sampling=(0.8, k))
+                 for (ids, lens), p, k in zip(batches, prefixes, keys)]
+        res = _many_device_with_options(ctx, batches, [sl] * 9, prefixes, keys, 0)
+        for (b, sc), (_, lens), want in zip(res, batches, wants):
+            _same_as_own_call(b, sc, lens, want)
+    finally:
+        ctx.close()
+
+
+def test_device_generated_unmerged_hands_each_batch_its_options(hip, oracle, engines):
+    """slimt_hip_translate_many_device_generated, nine batches (its unmerged device branch), with the same three options in
+    device memory: each batch == slimt_hip_translate_generated of it on the same context. A prefix holds words of ITS list."""
+    from slimt_amd import synth
+    from support import shortlist_cases as T
+    m, gm, _ = engines("tiny11", 6.0)
+    blob = T.lexical(m.V, m.V, *T.GENERATORS[T.MERGED_GENERATOR][1:])
+    osl = oracle.OracleShortlist(blob, m.V, m.V)
+    gen = hip.ShortlistGenerator(blob, m.V, m.V)
+    shapes = [FALLBACK_SHAPES[j % 2] for j in range(9)]
+    batches = [synth.make_batch(m.V, B, Sj, seed=600 + j, ragged=True) for j, (B, Sj) in enumerate(shapes)]
+    rng = np.random.default_rng(5)
+    prefixes, keys = [], []
+    for j, ((ids, lens), (B, Sj)) in enumerate(zip(batches, shapes)):
+        words = osl.generate(ids, lens)
+        words = words[words != 0]
+        T_j = max(int(np.float32(1.5) * np.float32(Sj)), 1)
+        prefixes.append((rng.choice(words, size=(B, T_j)).astype(np.uint32), rng.integers(0, 3, size=B).astype(np.uint32)))
+        keys.append(hip.sampling_keys(77, B, first=100 * j))
+    ctx = hip.Context(gm, hip.translate_many_rows([B for B, _ in shapes]), FALLBACK_S)
+    try:
+        assert ctx.plan(FALLBACK_S) == (True, True)
+        wants = [ctx.translate_generated(gen, ids, lens, want_align=True, scores=True, prefix=p, sampling=(0.8, k))
+                 for (ids, lens), p, k in zip(batches, prefixes, keys)]
+        res = _many_device_with_options(ctx, batches, [None] * 9, prefixes, keys, max(int(np.float32(1.5) * np.float32(FALLBACK_S)), 1),
+                                        generator=gen)
+        for (b, sc), (_, lens), want in zip(res, batches, wants):
+            _same_as_own_call(b, sc, lens, want)
+    finally:
+        gen.close()
+        ctx.close()
+
+
 def test_async_failed_guard_consumes_every_armed_option(hip, engines):
     """Scores armed for three batches, a prefix and sampling for two, a call of two batches: it fails at the scores, and the
     next plain call is an ordinary greedy one -- the prefix and the sampling were taken with the scores."""
