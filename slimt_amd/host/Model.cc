@@ -184,42 +184,24 @@ void Worker::forward_many_async_generated(slimt_hip_shortlist *generator, const 
     raise("slimt_hip_translate_many_async_generated");
 }
 
-// (weak: the Service's sanitizer builds link a test double of the engine that predates scores; a Worker asked to score
-// there fails instead of leaving the link unresolved)
-#pragma weak slimt_hip_ctx_set_scores
 void Worker::arm_scores(float *const *scores, size_t n) {
-  if (!slimt_hip_ctx_set_scores) throw std::runtime_error("this engine has no per-token scores");
   if (slimt_hip_ctx_set_scores(ctx_, scores, n)) raise("slimt_hip_ctx_set_scores");
 }
 
-#pragma weak slimt_hip_ctx_set_target_prefix
 void Worker::arm_prefix(const uint32_t *const *ids, const uint32_t *const *len, size_t n) {
-  if (!slimt_hip_ctx_set_target_prefix) throw std::runtime_error("this engine has no target prefixes");
   if (slimt_hip_ctx_set_target_prefix(ctx_, ids, len, n)) raise("slimt_hip_ctx_set_target_prefix");
 }
 
-#pragma weak slimt_hip_ctx_set_sampling
-#pragma weak slimt_hip_sampling_key
 void Worker::arm_sampling(float temperature, const uint64_t *const *keys, size_t n) {
-  if (!slimt_hip_ctx_set_sampling) throw std::runtime_error("this engine has no sampling");
   if (slimt_hip_ctx_set_sampling(ctx_, temperature, keys, n)) raise("slimt_hip_ctx_set_sampling");
 }
 
-uint64_t Worker::sampling_key(uint64_t seed, uint64_t index) {
-  if (!slimt_hip_sampling_key) throw std::runtime_error("this engine has no sampling");
-  return slimt_hip_sampling_key(seed, index);
-}
+uint64_t Worker::sampling_key(uint64_t seed, uint64_t index) { return slimt_hip_sampling_key(seed, index); }
 
-// (weak, like the scores: the Service's sanitizer builds link a test double of the engine that predates these calls)
-#pragma weak slimt_hip_score
-#pragma weak slimt_hip_score_async_generated
-#pragma weak slimt_hip_ctx_set_score_alternatives
 void Worker::score(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
                    const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids, const uint32_t *tgt_len, size_t T,
                    float *scores, float *align, const ScoreAlternatives *alternatives) {
-  if (!slimt_hip_score || !slimt_hip_score_async_generated) throw std::runtime_error("this engine has no teacher-forced scoring");
   if (alternatives && alternatives->k) {  // taken by the score call below, whatever its outcome
-    if (!slimt_hip_ctx_set_score_alternatives) throw std::runtime_error("this engine has no score alternatives");
     if (slimt_hip_ctx_set_score_alternatives(ctx_, alternatives->k, alternatives->alt_ids, alternatives->alt_scores, alternatives->rank))
       raise("slimt_hip_ctx_set_score_alternatives");
   }
@@ -232,13 +214,9 @@ void Worker::score(slimt_hip_shortlist *generator, const uint32_t *ids, const ui
   }
 }
 
-#pragma weak slimt_hip_score_candidates
-#pragma weak slimt_hip_score_candidates_async_generated
 void Worker::score_candidates(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
                               const uint32_t *shortlist, size_t n_shortlist, const uint32_t *tgt_ids, const uint32_t *tgt_len,
                               size_t T, const uint32_t *cand_src, size_t N, float *scores, float *align) {
-  if (!slimt_hip_score_candidates || !slimt_hip_score_candidates_async_generated)
-    throw std::runtime_error("this engine has no candidate scoring");
   if (generator) {
     if (slimt_hip_score_candidates_async_generated(ctx_, generator, ids, lengths, B, S, tgt_ids, tgt_len, T, cand_src, N, scores,
                                                    align))
@@ -250,24 +228,15 @@ void Worker::score_candidates(slimt_hip_shortlist *generator, const uint32_t *id
   }
 }
 
-#pragma weak slimt_hip_ctx_set_sampling_truncation
 void Worker::arm_sampling_truncation(uint32_t top_k, float top_p) {
-  if (!slimt_hip_ctx_set_sampling_truncation) throw std::runtime_error("this engine has no sampling truncation");
   if (slimt_hip_ctx_set_sampling_truncation(ctx_, top_k, top_p)) raise("slimt_hip_ctx_set_sampling_truncation");
 }
 
-// (weak, like the scores)
-#pragma weak slimt_hip_translate_fanout
-#pragma weak slimt_hip_translate_fanout_async_generated
-#pragma weak slimt_hip_ctx_set_fanout_consensus
 void Worker::translate_fanout(slimt_hip_shortlist *generator, const uint32_t *ids, const uint32_t *lengths, size_t B, size_t S,
                               const uint32_t *row_src, size_t N, const uint32_t *shortlist, size_t n_shortlist,
                               float limit_factor, uint32_t *out_ids, uint32_t *out_len, float *align,
                               const FanoutConsensus *consensus) {
-  if (!slimt_hip_translate_fanout || !slimt_hip_translate_fanout_async_generated)
-    throw std::runtime_error("this engine has no fan-out translate calls");
   if (consensus) {  // (armed right before the call that takes it)
-    if (!slimt_hip_ctx_set_fanout_consensus) throw std::runtime_error("this engine has no consensus selection");
     if (slimt_hip_ctx_set_fanout_consensus(ctx_, consensus->max_order, consensus->beta2, consensus->best, consensus->utility))
       raise("slimt_hip_ctx_set_fanout_consensus");
   }

@@ -241,6 +241,62 @@ Service::~Service() {
   }
 }
 
+// ---- what the synchronous calls (score, score_candidates, fanout_samples) share ------------------------------------------
+
+void Service::check_sentence(const Words &s) const {
+  if (s.empty()) throw std::invalid_argument("empty sentence (a sentence holds at least its EOS)");
+  if (s.size() > longest_)
+    throw std::invalid_argument("sentence of " + std::to_string(s.size()) + " tokens: longer than " +
+                                std::to_string(longest_) + " (wrap it first)");
+}
+
+LengthQueue Service::request_queue(const std::vector<Words> &sentences) const {
+  if (sentences.size() >= (1u << 24)) throw std::invalid_argument("request of more than 2^24 sentences");
+  LengthQueue queue(config_.max_words, longest_);  // the batch-forming rule of translate()
+  for (size_t i = 0; i < sentences.size(); ++i) {
+    Unit u;
+    u.order = i;
+    u.index = static_cast<uint32_t>(i);
+    u.length = static_cast<uint32_t>(sentences[i].size());
+    queue.push(std::move(u));
+  }
+  return queue;
+}
+
+std::unique_lock<std::mutex> Service::lock_score_worker() {
+  std::unique_lock<std::mutex> lock(score_mu_);
+  if (!score_worker_) score_worker_ = std::make_unique<Worker>(*score_model_, config_.max_words, longest_, config_.max_words);
+  return lock;
+}
+
+void Service::stage_sources(const std::vector<Words> &sentences, const Unit *units, size_t B, size_t S, Sources &src) const {
+  src.ids.assign(B * S, config_.pad_id);
+  src.lengths.resize(B);
+  for (size_t b = 0; b < B; ++b) {
+    const Words &s = sentences[units[b].index];
+    std::copy(s.begin(), s.end(), src.ids.begin() + static_cast<std::ptrdiff_t>(b * S));
+    src.lengths[b] = static_cast<uint32_t>(s.size());
+  }
+}
+
+std::pair<const uint32_t *, size_t> Service::fixed_shortlist() const {
+  const bool fixed = config_.shortlist && !score_generator_;
+  return {fixed ? config_.shortlist->data() : nullptr, fixed ? config_.shortlist->size() : 0};
+}
+
+Histories Service::collect_scored(const uint32_t *tokens, const std::vector<uint32_t> &len, const std::vector<uint32_t> &row_len,
+                                  size_t S, size_t T, const std::vector<float> &scores, const std::vector<float> &align) {
+  const uint64_t serial = batches_.fetch_add(1);
+  Histories hs = collect(tokens, len.data(), config_.alignments ? align.data() : nullptr, row_len.data(), len.size(), S, T,
+                         config_.flat_alignments);
+  for (size_t r = 0; r < hs.size(); ++r) {
+    const float *row = scores.data() + r * T;
+    hs[r]->scores.assign(row, row + len[r]);
+    hs[r]->batch = serial;
+  }
+  return hs;
+}
+
 Histories Service::score(std::vector<Words> sentences, std::vector<Words> targets, size_t alternatives) {
   constexpr size_t kLongestTarget = 65536;  // include/slimt_hip.h, slimt_hip_score
   if (alternatives > SLIMT_HIP_MAX_ALTERNATIVES)
@@ -249,30 +305,18 @@ Histories Service::score(std::vector<Words> sentences, std::vector<Words> target
   if (targets.size() != sentences.size())
     throw std::invalid_argument(std::to_string(targets.size()) + " targets for " + std::to_string(sentences.size()) + " sentences");
   for (size_t i = 0; i < sentences.size(); ++i) {
-    const Words &s = sentences[i];
-    if (s.empty()) throw std::invalid_argument("empty sentence (a sentence holds at least its EOS)");
-    if (s.size() > longest_)
-      throw std::invalid_argument("sentence of " + std::to_string(s.size()) + " tokens: longer than " +
-                                  std::to_string(longest_) + " (wrap it first)");
+    check_sentence(sentences[i]);
     if (targets[i].size() > kLongestTarget)
       throw std::invalid_argument("target of sentence " + std::to_string(i) + ": " + std::to_string(targets[i].size()) +
                                   " tokens, more than " + std::to_string(kLongestTarget));
   }
-  const size_t n = sentences.size();
-  Histories results(n);
-  if (n == 0) return results;
-  if (n >= (1u << 24)) throw std::invalid_argument("request of more than 2^24 sentences");
-  LengthQueue queue(config_.max_words, longest_);  // the batch-forming rule of translate()
-  for (size_t i = 0; i < n; ++i) {
-    Unit u;
-    u.order = i;
-    u.index = static_cast<uint32_t>(i);
-    u.length = static_cast<uint32_t>(sentences[i].size());
-    queue.push(std::move(u));
-  }
-  std::lock_guard<std::mutex> lock(score_mu_);
-  if (!score_worker_) score_worker_ = std::make_unique<Worker>(*score_model_, config_.max_words, longest_, config_.max_words);
-  std::vector<uint32_t> ids, lengths, tgt, tlen;
+  Histories results(sentences.size());
+  if (sentences.empty()) return results;
+  LengthQueue queue = request_queue(sentences);
+  const std::unique_lock<std::mutex> lock = lock_score_worker();
+  const auto [shortlist, n_shortlist] = fixed_shortlist();
+  Sources src;
+  std::vector<uint32_t> tgt, tlen;
   std::vector<float> sc, al, alt_sc;
   std::vector<uint32_t> alt_id, rank;
   for (;;) {
@@ -284,20 +328,16 @@ Histories Service::score(std::vector<Words> sentences, std::vector<Words> target
       S = std::max<size_t>(S, u.length);
       T = std::max(T, targets[u.index].size());
     }
-    ids.assign(B * S, config_.pad_id);
-    lengths.resize(B);
+    stage_sources(sentences, batch.data(), B, S, src);
     tgt.assign(B * T, 0);
     tlen.resize(B);
     sc.assign(B * T, 0.0f);
     if (config_.alignments) al.assign(B * T * S, 0.0f);
     for (size_t b = 0; b < B; ++b) {
-      const Words &s = sentences[batch[b].index], &t = targets[batch[b].index];
-      std::copy(s.begin(), s.end(), ids.begin() + static_cast<std::ptrdiff_t>(b * S));
+      const Words &t = targets[batch[b].index];
       std::copy(t.begin(), t.end(), tgt.begin() + static_cast<std::ptrdiff_t>(b * T));
-      lengths[b] = static_cast<uint32_t>(s.size());
       tlen[b] = static_cast<uint32_t>(t.size());
     }
-    const bool fixed = config_.shortlist && !score_generator_;
     ScoreAlternatives alt;
     if (k) {
       alt_id.assign(B * T * k, 0xFFFFFFFFu);
@@ -308,16 +348,11 @@ Histories Service::score(std::vector<Words> sentences, std::vector<Words> target
       alt.alt_scores = alt_sc.data();
       alt.rank = rank.data();
     }
-    score_worker_->score(score_generator_, ids.data(), lengths.data(), B, S, fixed ? config_.shortlist->data() : nullptr,
-                         fixed ? config_.shortlist->size() : 0, tgt.data(), tlen.data(), T, sc.data(),
-                         config_.alignments ? al.data() : nullptr, k ? &alt : nullptr);
-    const uint64_t serial = batches_.fetch_add(1);
+    score_worker_->score(score_generator_, src.ids.data(), src.lengths.data(), B, S, shortlist, n_shortlist, tgt.data(), tlen.data(), T,
+                         sc.data(), config_.alignments ? al.data() : nullptr, k ? &alt : nullptr);
     // the given tokens as the recorded ones: collect() cuts rows at tgt_len and alignment rows at the sentence's length
-    Histories hs = collect(tgt.data(), tlen.data(), config_.alignments ? al.data() : nullptr, lengths.data(), B, S, T,
-                           config_.flat_alignments);
+    Histories hs = collect_scored(tgt.data(), tlen, src.lengths, S, T, sc, al);
     for (size_t b = 0; b < B; ++b) {
-      hs[b]->scores.assign(sc.begin() + static_cast<std::ptrdiff_t>(b * T), sc.begin() + static_cast<std::ptrdiff_t>(b * T + tlen[b]));
-      hs[b]->batch = serial;
       if (k) {
         const auto at = [](size_t i) { return static_cast<std::ptrdiff_t>(i); };
         hs[b]->alternatives = static_cast<uint32_t>(k);
@@ -341,11 +376,7 @@ Service::CandidateScores Service::score_candidates(std::vector<Words> sentences,
   const size_t n = sentences.size();
   std::vector<size_t> first(n + 1, 0);  // sentence i's candidates in the result
   for (size_t i = 0; i < n; ++i) {
-    const Words &s = sentences[i];
-    if (s.empty()) throw std::invalid_argument("empty sentence (a sentence holds at least its EOS)");
-    if (s.size() > longest_)
-      throw std::invalid_argument("sentence of " + std::to_string(s.size()) + " tokens: longer than " +
-                                  std::to_string(longest_) + " (wrap it first)");
+    check_sentence(sentences[i]);
     for (const Words &t : candidates[i])
       if (t.size() > kLongestTarget)
         throw std::invalid_argument("candidate of sentence " + std::to_string(i) + ": " + std::to_string(t.size()) +
@@ -357,18 +388,11 @@ Service::CandidateScores Service::score_candidates(std::vector<Words> sentences,
   out.totals.assign(first[n], 0.0f);
   out.best.assign(n, 0xFFFFFFFFu);
   if (n == 0) return out;
-  if (n >= (1u << 24)) throw std::invalid_argument("request of more than 2^24 sentences");
-  LengthQueue queue(config_.max_words, longest_);  // the batch-forming rule of translate()
-  for (size_t i = 0; i < n; ++i) {
-    Unit u;
-    u.order = i;
-    u.index = static_cast<uint32_t>(i);
-    u.length = static_cast<uint32_t>(sentences[i].size());
-    queue.push(std::move(u));
-  }
-  std::lock_guard<std::mutex> lock(score_mu_);
-  if (!score_worker_) score_worker_ = std::make_unique<Worker>(*score_model_, config_.max_words, longest_, config_.max_words);
-  std::vector<uint32_t> ids, lengths, tgt, tlen, src, clen;
+  LengthQueue queue = request_queue(sentences);
+  const std::unique_lock<std::mutex> lock = lock_score_worker();
+  const auto [shortlist, n_shortlist] = fixed_shortlist();
+  Sources src;
+  std::vector<uint32_t> tgt, tlen, cand_src, clen;
   std::vector<float> sc, al;
   for (;;) {
     const std::vector<Unit> batch = queue.take();
@@ -381,44 +405,32 @@ Service::CandidateScores Service::score_candidates(std::vector<Words> sentences,
       for (const Words &t : candidates[u.index]) T = std::max(T, t.size());
     }
     if (N == 0) continue;  // (sentences without candidates: nothing to encode for)
-    ids.assign(B * S, config_.pad_id);
-    lengths.resize(B);
+    stage_sources(sentences, batch.data(), B, S, src);
     tgt.assign(N * T, 0);
     tlen.resize(N);
-    src.resize(N);
+    cand_src.resize(N);
     clen.resize(N);
     sc.assign(N * T, 0.0f);
     if (config_.alignments) al.assign(N * T * S, 0.0f);
     size_t c = 0;
-    for (size_t b = 0; b < B; ++b) {
-      const Words &s = sentences[batch[b].index];
-      std::copy(s.begin(), s.end(), ids.begin() + static_cast<std::ptrdiff_t>(b * S));
-      lengths[b] = static_cast<uint32_t>(s.size());
+    for (size_t b = 0; b < B; ++b)
       for (const Words &t : candidates[batch[b].index]) {  // sorted by source
         std::copy(t.begin(), t.end(), tgt.begin() + static_cast<std::ptrdiff_t>(c * T));
         tlen[c] = static_cast<uint32_t>(t.size());
-        src[c] = static_cast<uint32_t>(b);
-        clen[c] = lengths[b];
+        cand_src[c] = static_cast<uint32_t>(b);
+        clen[c] = src.lengths[b];
         ++c;
       }
-    }
-    const bool fixed = config_.shortlist && !score_generator_;
-    score_worker_->score_candidates(score_generator_, ids.data(), lengths.data(), B, S, fixed ? config_.shortlist->data() : nullptr,
-                                    fixed ? config_.shortlist->size() : 0, tgt.data(), tlen.data(), T, src.data(), N, sc.data(),
-                                    config_.alignments ? al.data() : nullptr);
-    const uint64_t serial = batches_.fetch_add(1);
-    Histories hs = collect(tgt.data(), tlen.data(), config_.alignments ? al.data() : nullptr, clen.data(), N, S, T,
-                           config_.flat_alignments);
+    score_worker_->score_candidates(score_generator_, src.ids.data(), src.lengths.data(), B, S, shortlist, n_shortlist, tgt.data(),
+                                    tlen.data(), T, cand_src.data(), N, sc.data(), config_.alignments ? al.data() : nullptr);
+    Histories hs = collect_scored(tgt.data(), tlen, clen, S, T, sc, al);
     c = 0;
     for (size_t b = 0; b < B; ++b) {
       const size_t i = batch[b].index;
       float top = 0.0f;
       for (size_t j = 0; j < candidates[i].size(); ++j, ++c) {
-        const float *row = sc.data() + c * T;
         float total = 0.0f;  // ascending t from +0, one f32 add per term
-        for (size_t t = 0; t < tlen[c]; ++t) total = total + row[t];
-        hs[c]->scores.assign(row, row + tlen[c]);
-        hs[c]->batch = serial;
+        for (const float s : hs[c]->scores) total = total + s;
         out.totals[first[i] + j] = total;
         out.candidates[first[i] + j] = std::move(hs[c]);
         if (tlen[c] == 0) continue;
@@ -463,30 +475,18 @@ Histories Service::fanout_samples(std::vector<Words> sentences, size_t n, uint64
   const size_t max_rows = config_.max_words;  // max_batch of the context below: a batch's rows must fit it
   if (n == 0 || n > max_rows)
     throw std::invalid_argument(std::to_string(n) + " samples per sentence: not in 1.." + std::to_string(max_rows));
-  for (const Words &s : sentences) {
-    if (s.empty()) throw std::invalid_argument("empty sentence (a sentence holds at least its EOS)");
-    if (s.size() > longest_)
-      throw std::invalid_argument("sentence of " + std::to_string(s.size()) + " tokens: longer than " +
-                                  std::to_string(longest_) + " (wrap it first)");
-  }
+  for (const Words &s : sentences) check_sentence(s);
   const size_t count = sentences.size();
   Histories results(select ? count : count * n);
   if (count == 0) return results;
-  if (count >= (1u << 24)) throw std::invalid_argument("request of more than 2^24 sentences");
+  LengthQueue queue = request_queue(sentences);
   std::vector<uint32_t> best;    // (select) per source of a call: its consensus row
   std::vector<double> utility;   // (select) per row of a call
-  LengthQueue queue(config_.max_words, longest_);  // the batch-forming rule of translate()
-  for (size_t i = 0; i < count; ++i) {
-    Unit u;
-    u.order = i;
-    u.index = static_cast<uint32_t>(i);
-    u.length = static_cast<uint32_t>(sentences[i].size());
-    queue.push(std::move(u));
-  }
-  std::lock_guard<std::mutex> lock(score_mu_);
-  if (!score_worker_) score_worker_ = std::make_unique<Worker>(*score_model_, config_.max_words, longest_, config_.max_words);
+  const std::unique_lock<std::mutex> lock = lock_score_worker();
+  const auto [shortlist, n_shortlist] = fixed_shortlist();
   const size_t per_call = max_rows / n;  // sentences of one fan-out call: n rows each, at most max_batch rows
-  std::vector<uint32_t> ids, lengths, src, rlen, out_ids, out_len;
+  Sources src;
+  std::vector<uint32_t> row_src, rlen, out_ids, out_len;
   std::vector<uint64_t> keys;
   std::vector<float> sc, al;
   for (;;) {
@@ -498,9 +498,8 @@ Histories Service::fanout_samples(std::vector<Words> sentences, size_t n, uint64
     const size_t T = Tmax ? Tmax : 1;
     for (size_t b0 = 0; b0 < batch.size(); b0 += per_call) {
       const size_t B = std::min(per_call, batch.size() - b0), N = B * n;
-      ids.assign(B * S, config_.pad_id);
-      lengths.resize(B);
-      src.resize(N);
+      stage_sources(sentences, batch.data() + b0, B, S, src);
+      row_src.resize(N);
       rlen.resize(N);
       keys.resize(N);
       out_ids.assign(N * T, 0);
@@ -509,12 +508,9 @@ Histories Service::fanout_samples(std::vector<Words> sentences, size_t n, uint64
       if (config_.alignments) al.assign(N * T * S, 0.0f);
       for (size_t b = 0; b < B; ++b) {
         const size_t i = batch[b0 + b].index;
-        const Words &s = sentences[i];
-        std::copy(s.begin(), s.end(), ids.begin() + static_cast<std::ptrdiff_t>(b * S));
-        lengths[b] = static_cast<uint32_t>(s.size());
         for (size_t j = 0; j < n; ++j) {  // sorted by source; the key goes by the request's numbering, not by the row
-          src[b * n + j] = static_cast<uint32_t>(b);
-          rlen[b * n + j] = lengths[b];
+          row_src[b * n + j] = static_cast<uint32_t>(b);
+          rlen[b * n + j] = src.lengths[b];
           keys[b * n + j] = Worker::sampling_key(seed, static_cast<uint64_t>(i) * n + j);
         }
       }
@@ -523,7 +519,6 @@ Histories Service::fanout_samples(std::vector<Words> sentences, size_t n, uint64
       score_worker_->arm_sampling(temperature, &kp, 1);
       if (top_k != 0 || top_p != 1.0f) score_worker_->arm_sampling_truncation(top_k, top_p);
       score_worker_->arm_scores(&sp, 1);
-      const bool fixed = config_.shortlist && !score_generator_;
       Worker::FanoutConsensus cs;
       if (select) {  // the pick among each sentence's rows, on the device behind the last step
         best.assign(B, 0xFFFFFFFFu);
@@ -533,19 +528,11 @@ Histories Service::fanout_samples(std::vector<Words> sentences, size_t n, uint64
         cs.best = best.data();
         cs.utility = utility.data();
       }
-      score_worker_->translate_fanout(score_generator_, ids.data(), lengths.data(), B, S, src.data(), N,
-                                      fixed ? config_.shortlist->data() : nullptr, fixed ? config_.shortlist->size() : 0,
-                                      config_.tgt_length_limit_factor, out_ids.data(), out_len.data(),
+      score_worker_->translate_fanout(score_generator_, src.ids.data(), src.lengths.data(), B, S, row_src.data(), N, shortlist,
+                                      n_shortlist, config_.tgt_length_limit_factor, out_ids.data(), out_len.data(),
                                       config_.alignments ? al.data() : nullptr, select ? &cs : nullptr);
-      const uint64_t serial = batches_.fetch_add(1);
-      Histories hs = collect(out_ids.data(), out_len.data(), config_.alignments ? al.data() : nullptr, rlen.data(), N, S, T,
-                             config_.flat_alignments);
-      for (size_t r = 0; r < N; ++r) {
-        const float *row = sc.data() + r * T;
-        hs[r]->scores.assign(row, row + out_len[r]);
-        hs[r]->batch = serial;
-        if (!select) results[static_cast<size_t>(batch[b0 + r / n].index) * n + r % n] = std::move(hs[r]);
-      }
+      Histories hs = collect_scored(out_ids.data(), out_len, rlen, S, T, sc, al);
+      for (size_t r = 0; !select && r < N; ++r) results[static_cast<size_t>(batch[b0 + r / n].index) * n + r % n] = std::move(hs[r]);
       for (size_t b = 0; select && b < B; ++b) {  // (rows b n .. b n + n are sentence b's; no competing row: sample 0)
         const size_t r = best[b] >= b * n && best[b] < (b + 1) * n ? best[b] : b * n;
         hs[r]->utility = best[b] == r ? utility[r] : 0.0;
@@ -597,12 +584,7 @@ std::future<Histories> Service::translate(std::vector<Words> sentences, std::vec
                                     " tokens, more than " + std::to_string(limit));
     }
   }
-  for (const Words &s : sentences) {
-    if (s.empty()) throw std::invalid_argument("empty sentence (a sentence holds at least its EOS)");
-    if (s.size() > longest_)
-      throw std::invalid_argument("sentence of " + std::to_string(s.size()) + " tokens: longer than " +
-                                  std::to_string(longest_) + " (wrap it first)");
-  }
+  for (const Words &s : sentences) check_sentence(s);
   auto pending = std::make_shared<Pending>(std::move(sentences), std::move(prefixes), seed);
   std::future<Histories> result = pending->future();
   if (pending->size() == 0) return result;

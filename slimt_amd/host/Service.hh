@@ -29,6 +29,7 @@
 #include <mutex>
 #include <optional>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "Model.hh"
@@ -221,6 +222,19 @@ class Service {
  private:
   // translate_samples (select = false: n entries per sentence) and translate_consensus (select = true: the winner alone)
   Histories fanout_samples(std::vector<Words> sentences, size_t n, uint64_t seed, bool select, int max_order, int beta2);
+  // what score(), score_candidates() and fanout_samples() share (and translate(): the first)
+  void check_sentence(const Words &sentence) const;  // throws for an empty one or one longer than the service accepts
+  LengthQueue request_queue(const std::vector<Words> &sentences) const;  // a request's own queue: translate()'s batches
+  std::unique_lock<std::mutex> lock_score_worker();  // score_mu_ held, score_worker_ built
+  struct Sources {  // a call's sources: ids [B][S] padded with pad_id, lengths [B]; reused from batch to batch
+    std::vector<uint32_t> ids, lengths;
+  };
+  void stage_sources(const std::vector<Words> &sentences, const Unit *units, size_t B, size_t S, Sources &sources) const;
+  std::pair<const uint32_t *, size_t> fixed_shortlist() const;  // the service's fixed list, or (nullptr, 0)
+  // a call's N rows of T tokens as Histories, numbered as the next batch: tokens cut at len[r], alignment rows at
+  // row_len[r], scores [N][T] cut at len[r]
+  Histories collect_scored(const uint32_t *tokens, const std::vector<uint32_t> &len, const std::vector<uint32_t> &row_len, size_t S,
+                           size_t T, const std::vector<float> &scores, const std::vector<float> &align);
   struct Slot;
   void work(const Model *model, slimt_hip_shortlist *generator);
   std::vector<Unit> next_batch(bool may_block, std::vector<size_t> *parts = nullptr);

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <initializer_list>
 #include <memory>
 #include <vector>
 
@@ -152,28 +153,51 @@ int flatten(const slimt::Histories &hs, size_t n, bool scored, std::unique_ptr<s
   return 0;
 }
 
+// tokens + offsets -> one Words per sentence. Several arrays (the sentences with their prefixes or targets) are walked
+// together, sentence by sentence, so the first decreasing offset of any of them is the one reported: "<label> decrease"
+struct Ragged {
+  const uint32_t *tokens;
+  const uint64_t *offsets;
+  const char *label;
+  std::vector<slimt::Words> *rows;
+};
+int to_rows(std::initializer_list<Ragged> arrays, size_t n) {
+  for (const Ragged &a : arrays) a.rows->assign(n, slimt::Words());
+  for (size_t i = 0; i < n; ++i)
+    for (const Ragged &a : arrays) {
+      if (a.offsets[i + 1] < a.offsets[i]) return fail("%s decrease at sentence %zu", a.label, i);
+      if (a.offsets[i + 1] > a.offsets[i]) (*a.rows)[i].assign(a.tokens + a.offsets[i], a.tokens + a.offsets[i + 1]);
+    }
+  return 0;
+}
+
+// The shell of every call that returns a result: *out is what `fill` leaves (status 0), else NULL with the message of
+// what it refused or threw.
+template <class Fill>
+int result_of(slimt_hip_result **out, Fill &&fill) {
+  *out = nullptr;
+  try {
+    std::unique_ptr<slimt_hip_result> r;
+    if (const int rc = fill(r)) return rc;
+    *out = r.release();
+    return 0;
+  } catch (const std::exception &e) {
+    return fail("%s", e.what());
+  }
+}
+
 // slimt_hip_service_translate[_prefixed]: prefix_tokens / prefix_offsets NULL = no prefixes
 int translate(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets, const uint32_t *prefix_tokens,
               const uint64_t *prefix_offsets, size_t n, slimt_hip_result **out, uint64_t seed = 0) {
-  *out = nullptr;
-  try {
+  return result_of(out, [&](std::unique_ptr<slimt_hip_result> &r) {
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<slimt::Words> sentences(n), prefixes(prefix_offsets ? n : 0);
-    for (size_t i = 0; i < n; ++i) {
-      if (offsets[i + 1] < offsets[i]) return fail("offsets decrease at sentence %zu", i);
-      sentences[i].assign(tokens + offsets[i], tokens + offsets[i + 1]);
-      if (prefix_offsets) {
-        if (prefix_offsets[i + 1] < prefix_offsets[i]) return fail("prefix offsets decrease at sentence %zu", i);
-        if (prefix_offsets[i + 1] > prefix_offsets[i])
-          prefixes[i].assign(prefix_tokens + prefix_offsets[i], prefix_tokens + prefix_offsets[i + 1]);
-      }
-    }
+    std::vector<slimt::Words> sentences, prefixes;
+    const Ragged src{tokens, offsets, "offsets", &sentences}, pre{prefix_tokens, prefix_offsets, "prefix offsets", &prefixes};
+    if (const int rc = prefix_offsets ? to_rows({src, pre}, n) : to_rows({src}, n)) return rc;
     const auto t1 = std::chrono::steady_clock::now();
     slimt::Histories hs = service->service->translate(std::move(sentences), std::move(prefixes), seed).get();
     const auto t2 = std::chrono::steady_clock::now();
-    std::unique_ptr<slimt_hip_result> r;
     if (const int rc = flatten(hs, n, service->scores, r)) return rc;
-    *out = r.release();
     if (std::getenv("SLIMT_SERVICE_STATS")) {
       const auto t3 = std::chrono::steady_clock::now();
       auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -181,9 +205,7 @@ int translate(slimt_hip_service *service, const uint32_t *tokens, const uint64_t
                    ms(t0, t1), ms(t1, t2), ms(t2, t3));
     }
     return 0;
-  } catch (const std::exception &e) {
-    return fail("%s", e.what());
-  }
+  });
 }
 }  // namespace
 
@@ -206,23 +228,13 @@ int score(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *of
           const uint64_t *tgt_offsets, size_t n, uint32_t alternatives, slimt_hip_result **out) {
   if (!service || !out || (n && (!tokens || !offsets || !tgt_offsets)) || (n && tgt_offsets[n] > tgt_offsets[0] && !tgt_tokens))
     return fail("null argument");
-  *out = nullptr;
-  try {
-    std::vector<slimt::Words> sentences(n), targets(n);
-    for (size_t i = 0; i < n; ++i) {
-      if (offsets[i + 1] < offsets[i]) return fail("offsets decrease at sentence %zu", i);
-      if (tgt_offsets[i + 1] < tgt_offsets[i]) return fail("target offsets decrease at sentence %zu", i);
-      sentences[i].assign(tokens + offsets[i], tokens + offsets[i + 1]);
-      if (tgt_offsets[i + 1] > tgt_offsets[i]) targets[i].assign(tgt_tokens + tgt_offsets[i], tgt_tokens + tgt_offsets[i + 1]);
-    }
+  return result_of(out, [&](std::unique_ptr<slimt_hip_result> &r) {
+    std::vector<slimt::Words> sentences, targets;
+    if (const int rc = to_rows({{tokens, offsets, "offsets", &sentences}, {tgt_tokens, tgt_offsets, "target offsets", &targets}}, n))
+      return rc;
     const slimt::Histories hs = service->service->score(std::move(sentences), std::move(targets), alternatives);
-    std::unique_ptr<slimt_hip_result> r;
-    if (const int rc = flatten(hs, n, true, r, alternatives)) return rc;
-    *out = r.release();
-    return 0;
-  } catch (const std::exception &e) {
-    return fail("%s", e.what());
-  }
+    return flatten(hs, n, true, r, alternatives);
+  });
 }
 }  // namespace
 
@@ -246,11 +258,10 @@ extern "C" int slimt_hip_service_score_candidates(slimt_hip_service *service, co
   const size_t N = n ? cand_offsets[n] : 0;
   if (n && cand_offsets[0] != 0) return fail("candidate offsets start at %llu, not 0", (unsigned long long)cand_offsets[0]);
   if (N && (!tgt_offsets || (tgt_offsets[N] > tgt_offsets[0] && !tgt_tokens))) return fail("null argument");
-  *out = nullptr;
-  try {
+  return result_of(out, [&](std::unique_ptr<slimt_hip_result> &r) {
     std::vector<slimt::Words> sentences(n);
     std::vector<std::vector<slimt::Words>> candidates(n);
-    for (size_t i = 0; i < n; ++i) {
+    for (size_t i = 0; i < n; ++i) {  // (its own walk: two levels of offsets, checked sentence by sentence)
       if (offsets[i + 1] < offsets[i]) return fail("offsets decrease at sentence %zu", i);
       if (cand_offsets[i + 1] < cand_offsets[i]) return fail("candidate offsets decrease at sentence %zu", i);
       sentences[i].assign(tokens + offsets[i], tokens + offsets[i + 1]);
@@ -260,16 +271,12 @@ extern "C" int slimt_hip_service_score_candidates(slimt_hip_service *service, co
       }
     }
     slimt::Service::CandidateScores cs = service->service->score_candidates(std::move(sentences), std::move(candidates), mode);
-    std::unique_ptr<slimt_hip_result> r;
     if (const int rc = flatten(cs.candidates, cs.candidates.size(), true, r)) return rc;
     r->ranked = true;
     r->totals = std::move(cs.totals);
     r->best = std::move(cs.best);
-    *out = r.release();
     return 0;
-  } catch (const std::exception &e) {
-    return fail("%s", e.what());
-  }
+  });
 }
 
 extern "C" int slimt_hip_result_candidates(const slimt_hip_result *r, const float **totals, const uint32_t **best) {
@@ -283,22 +290,14 @@ extern "C" int slimt_hip_result_candidates(const slimt_hip_result *r, const floa
 extern "C" int slimt_hip_service_translate_samples(slimt_hip_service *service, const uint32_t *tokens, const uint64_t *offsets,
                                                    size_t n, size_t samples, uint64_t seed, slimt_hip_result **out) {
   if (!service || !out || (n && (!tokens || !offsets))) return fail("null argument");
-  *out = nullptr;
-  try {
-    std::vector<slimt::Words> sentences(n);
-    for (size_t i = 0; i < n; ++i) {
-      if (offsets[i + 1] < offsets[i]) return fail("offsets decrease at sentence %zu", i);
-      sentences[i].assign(tokens + offsets[i], tokens + offsets[i + 1]);
-    }
+  return result_of(out, [&](std::unique_ptr<slimt_hip_result> &r) {
+    std::vector<slimt::Words> sentences;
+    if (const int rc = to_rows({{tokens, offsets, "offsets", &sentences}}, n)) return rc;
     const slimt::Histories hs = service->service->translate_samples(std::move(sentences), samples, seed);
-    std::unique_ptr<slimt_hip_result> r;
     if (const int rc = flatten(hs, hs.size(), true, r)) return rc;
     r->samples = samples;
-    *out = r.release();
     return 0;
-  } catch (const std::exception &e) {
-    return fail("%s", e.what());
-  }
+  });
 }
 
 extern "C" int slimt_hip_result_samples(const slimt_hip_result *r, size_t *samples) {
@@ -312,15 +311,10 @@ extern "C" int slimt_hip_service_translate_consensus(slimt_hip_service *service,
                                                      size_t n, size_t samples, uint64_t seed, int max_order, int beta2,
                                                      slimt_hip_result **out) {
   if (!service || !out || (n && (!tokens || !offsets))) return fail("null argument");
-  *out = nullptr;
-  try {
-    std::vector<slimt::Words> sentences(n);
-    for (size_t i = 0; i < n; ++i) {
-      if (offsets[i + 1] < offsets[i]) return fail("offsets decrease at sentence %zu", i);
-      sentences[i].assign(tokens + offsets[i], tokens + offsets[i + 1]);
-    }
+  return result_of(out, [&](std::unique_ptr<slimt_hip_result> &r) {
+    std::vector<slimt::Words> sentences;
+    if (const int rc = to_rows({{tokens, offsets, "offsets", &sentences}}, n)) return rc;
     const slimt::Histories hs = service->service->translate_consensus(std::move(sentences), samples, seed, max_order, beta2);
-    std::unique_ptr<slimt_hip_result> r;
     if (const int rc = flatten(hs, hs.size(), true, r)) return rc;
     r->selected = true;
     r->utility.reserve(hs.size());
@@ -329,11 +323,8 @@ extern "C" int slimt_hip_service_translate_consensus(slimt_hip_service *service,
       r->utility.push_back(h->utility);
       r->sample_index.push_back(h->sample_index);
     }
-    *out = r.release();
     return 0;
-  } catch (const std::exception &e) {
-    return fail("%s", e.what());
-  }
+  });
 }
 
 extern "C" int slimt_hip_result_consensus(const slimt_hip_result *r, const double **utility, const uint32_t **sample_index) {

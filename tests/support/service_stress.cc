@@ -1,6 +1,7 @@
 // CPU stress of host/Service over the fake engine (fake_hip_engine.cc): many client threads, many
-// workers on two "replicas", every sentence checked, then the failure modes. Built with
-// -fsanitize=thread or address by tests/test_service_sanitizers.py.
+// workers on two "replicas", every sentence checked, then the failure modes, then every other call kind
+// of the service and of its C face (service_calls.cc). Built with -fsanitize=thread or address by
+// tests/test_service_sanitizers.py.
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +12,8 @@
 #include "Service.hh"
 
 using namespace slimt;
+
+int service_calls(const Model &a, const Model &b, slimt_hip_model *handle, int clients, int requests);  // service_calls.cc
 
 static bool check(const Words &src, const Hypothesis &h, float limit, bool with_align) {
   const size_t S = h.padded_length, T = std::max<size_t>(1, (size_t)(limit * (float)S));
@@ -137,6 +140,7 @@ int main(int argc, char **argv) {
     for (auto &t : ts) t.join();
     std::printf("Model::forward: %d sentences on %zu pooled contexts\n", fwd.load(), a.contexts_built());
   }
+  const int wrong_calls = service_calls(a, b, ha, clients, requests);
   for (slimt_hip_model *h : {ha, hb, h2, h3}) slimt_hip_model_destroy(h);
-  return bad.load() ? 1 : 0;
+  return bad.load() || wrong_calls ? 1 : 0;
 }
