@@ -875,6 +875,13 @@ int slimt_hip_debug_cross_attention(slimt_hip_ctx *ctx, int layer, int literal, 
  * slimt_hip_ctx_synchronize, or the blocking translate calls -- FAILS: the batch's results are
  * not to be used. Tests use it to reach that path. */
 int slimt_hip_debug_break_shortlist_handoff(slimt_hip_ctx *ctx, int broken, unsigned poll_limit);
+/* Diagnostic: put ctx's launch bookkeeping where it would be after `value` tickets. Waits for ctx's
+ * stream, then sets the device's decoder and encoder ticket counters and both halves of the 64-bit
+ * XCD-affine claim word to `value`, the host's bases of all four to the same, the epoch of the
+ * in-launch shortlist hand-over to `value`, and clears the hand-over's flags where they exist. The
+ * counters run modulo 2^32, so results do not depend on it; tests start a context shortly before
+ * 2^32 (and the epoch before its reserved 0xffffffff), which a loaded service reaches in a day. */
+int slimt_hip_debug_ctx_set_counters(slimt_hip_ctx *ctx, uint32_t value);
 /* Diagnostic: what ctx's shortlist buffer holds after a *_generated call: waits for ctx's stream, then for j < n_batches writes
  * counts[j] (the device's count of sub-batch j; j = 0 for an unmerged call) and the first min(counts[j], capacity) ids
  * of that list to ids + j * capacity. Reads only what the context has reserved; fails otherwise (n_batches not in 1..8,

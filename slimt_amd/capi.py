@@ -45,7 +45,7 @@ SYMBOLS = [
     "slimt_hip_ctx_set_scores", "slimt_hip_ctx_set_target_prefix", "slimt_hip_ctx_set_sampling", "slimt_hip_sampling_key",
     "slimt_hip_ctx_set_sampling_truncation", "slimt_hip_sample_truncated",
     "slimt_hip_score", "slimt_hip_score_async", "slimt_hip_score_device", "slimt_hip_score_async_generated",
-    "slimt_hip_ctx_set_score_alternatives", "slimt_hip_debug_ctx_shortlists",
+    "slimt_hip_ctx_set_score_alternatives", "slimt_hip_debug_ctx_shortlists", "slimt_hip_debug_ctx_set_counters",
     "slimt_hip_score_candidates", "slimt_hip_score_candidates_async", "slimt_hip_score_candidates_device",
     "slimt_hip_score_candidates_async_generated", "slimt_hip_candidates_rank", "slimt_hip_candidates_rank_device",
     "slimt_hip_translate_fanout", "slimt_hip_translate_fanout_async", "slimt_hip_translate_fanout_device",
@@ -252,6 +252,7 @@ def lib():
     L.slimt_hip_model_set_kv_centres.argtypes = [vp, vp, sz]
     L.slimt_hip_debug_break_shortlist_handoff.argtypes = [vp, i32, u32]
     L.slimt_hip_debug_ctx_shortlists.argtypes = [vp, sz, vp, sz, vp]
+    L.slimt_hip_debug_ctx_set_counters.argtypes = [vp, u32]
     L.slimt_hip_debug_cross_attention.argtypes = [vp, i32, i32, vp, vp, vp]
     L.slimt_hip_model_set_decoder_budget.argtypes = [vp, i32]
     L.slimt_hip_model_set_kv_cache_policy.argtypes = [vp, i32]
@@ -1433,6 +1434,11 @@ class Context:
     def debug_break_shortlist_handoff(self, broken: bool, poll_limit: int = 1 << 24):
         """The waiters of an in-launch shortlist look for a publication that never comes (tests: the timeout path)."""
         _chk(lib().slimt_hip_debug_break_shortlist_handoff(self.h, 1 if broken else 0, int(poll_limit)))
+
+    def debug_set_counters(self, value: int):
+        """slimt_hip_debug_ctx_set_counters: the ticket and claim counters, their host bases and the shortlist hand-over's
+        epoch as they would be after `value` (uint32) tickets (tests: the wrap-around at 2^32)."""
+        _chk(lib().slimt_hip_debug_ctx_set_counters(self.h, int(value) & 0xFFFFFFFF))
 
     def debug_shortlists(self, n_batches: int = 1, capacity: Optional[int] = None, with_counts: bool = False):
         """slimt_hip_debug_ctx_shortlists: the lists the last *_generated call left in this context, one uint32 array per

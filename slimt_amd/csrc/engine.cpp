@@ -1009,6 +1009,21 @@ extern "C" int slimt_hip_debug_break_shortlist_handoff(slimt_hip_ctx *ctx, int b
   return 0;
 }
 
+extern "C" int slimt_hip_debug_ctx_set_counters(slimt_hip_ctx *ctx, uint32_t value) {
+  if (!ctx) return fail(-1, "ctx is NULL");
+  if (!ctx->ticket.p) return fail(-1, "the context has no ticket counters");
+  HIPCHK(hipSetDevice(ctx->model->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  // the device words (engine.cpp, slimt_hip_ctx_create): [0] decoder, [1] fused encoder, [2..3] the two halves of the claim word
+  const uint32_t words[4] = {value, value, value, value};
+  HIPCHK(hipMemcpy(ctx->ticket.p, words, sizeof(words), hipMemcpyHostToDevice));
+  ctx->ticket_base = ctx->enc_ticket_base = ctx->xarr_base = ctx->xclaim_base = value;
+  // (an epoch of 0xffffffff is never carried from one launch to the next: encode_device turns it into 0 when it is used)
+  ctx->gen_epoch = value == 0xffffffffu ? 0u : value;
+  if (ctx->gen_flag.p) HIPCHK(hipMemset(ctx->gen_flag.p, 0, 64));
+  return 0;
+}
+
 extern "C" int slimt_hip_debug_ctx_shortlists(slimt_hip_ctx *ctx, size_t n_batches, uint32_t *ids, size_t capacity, uint32_t *counts) {
   if (!ctx || !ids || !counts) return fail(-1, "null argument");
   if (n_batches == 0 || n_batches > (size_t)kMaxMerge) return fail(-1, "%zu shortlists not in 1..%d", n_batches, kMaxMerge);
@@ -3250,11 +3265,11 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
                             nullptr, 0, nullptr, &mp);
   for (size_t j = 0; j < n_batches; ++j) {  // batch by batch, in order, on the same stream
     const slimt_hip_batch &b = batches[j];
-    // (a truncated call is never merged, so it must give here what a merged launch gives: the launch's step budget is the
-    // longest batch's, and a shorter batch takes at most its own Tmax_j -- build_merge_plan's rule. Other calls that come
-    // this way keep the budget as given, as before.)
+    // (a call that comes this way must give what a merged launch gives: the launch's step budget is the longest batch's,
+    // and a shorter batch takes at most its own Tmax_j -- build_merge_plan's rule. With the budget as given, a sentence
+    // of a shorter batch that had not ended by Tmax_j went on counting steps: out_len[b] > Tmax_j, past its row of out_ids.)
     const size_t Sj = b.S ? b.S : S, Tj = std::max<size_t>(1, (size_t)(limit_factor * (float)Sj));
-    const int hint = ctx->call.truncated && steps_hint > 0 ? std::min(steps_hint, (int)Tj) : steps_hint;
+    const int hint = steps_hint > 0 ? std::min(steps_hint, (int)Tj) : steps_hint;
     RCCHK(translate_device_batch(ctx, opt.user[j], b.src_ids, b.lengths, b.B, Sj, b.shortlist, b.n_shortlist, limit_factor,
                                  eos_id, b.out_ids, b.out_len, b.align, hint));
   }
