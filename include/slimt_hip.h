@@ -904,6 +904,13 @@ int slimt_hip_debug_kv_watch(slimt_hip_model *model, int *switched_to_24_bit, ui
  * maximum 2^19, what 20 bits hold). Tests lower it so that some sentences of a batch take the
  * 24-bit form next to narrow ones. Results do not depend on it. */
 int slimt_hip_debug_kv_narrow_limit(slimt_hip_model *model, int limit);
+/* Diagnostic: whether the model's load proved that its tied output layer (Wemb dequantised and re-quantised by
+ * its own multiplier) equals the int8 table byte for byte -- true for every table without a -128. The fused
+ * decoder then takes a step's next embedding row from the output layer's packed tile (the same bytes, addressed
+ * by the winning column) instead of from the table. Results do not depend on it. */
+int slimt_hip_debug_out_tied_exact(slimt_hip_model *model, int *exact);
+/* ... and the proof alone, on a caller's table [rows][cols] with its multiplier: host code, needs no device. */
+int slimt_hip_debug_tied_output_proof(const int8_t *wemb, size_t rows, size_t cols, float multiplier, int *exact);
 /* Diagnostic: the tight (16-bit) form below the 20-bit one. Where the decoder has a reader for it (D = 256 /
  * F = 1536 with sentences of up to 128 tokens, D = 512 / F = 2048 up to 32) format 0 caches a
  * sentence-layer whose K and V accumulators, less their columns' centres (slimt_hip_model_set_kv_centres),

@@ -30,7 +30,7 @@ SYMBOLS = [
     "slimt_hip_ctx_synchronize", "slimt_hip_ctx_set_decode_mode", "slimt_hip_ctx_set_encode_rows", "slimt_hip_ctx_plan", "slimt_hip_translate", "slimt_hip_translate_device",
     "slimt_hip_encode", "slimt_hip_decode_begin", "slimt_hip_decode_step",
     "slimt_hip_profile_enable", "slimt_hip_profile_read", "slimt_hip_profile_reset",
-    "slimt_hip_debug_decode_stamps", "slimt_hip_debug_kv_formats", "slimt_hip_debug_kv_narrow_limit", "slimt_hip_debug_kv_tight_limit", "slimt_hip_debug_kv_tight_watch", "slimt_hip_debug_kv_centres", "slimt_hip_model_set_kv_centres", "slimt_hip_debug_kv_watch", "slimt_hip_debug_break_shortlist_handoff", "slimt_hip_debug_cross_attention",
+    "slimt_hip_debug_decode_stamps", "slimt_hip_debug_kv_formats", "slimt_hip_debug_kv_narrow_limit", "slimt_hip_debug_kv_tight_limit", "slimt_hip_debug_out_tied_exact", "slimt_hip_debug_tied_output_proof", "slimt_hip_debug_kv_tight_watch", "slimt_hip_debug_kv_centres", "slimt_hip_model_set_kv_centres", "slimt_hip_debug_kv_watch", "slimt_hip_debug_break_shortlist_handoff", "slimt_hip_debug_cross_attention",
     "slimt_hip_debug_occupancy_trace", "slimt_hip_debug_decoder_plan", "slimt_hip_model_set_decoder_budget",
     "slimt_hip_model_set_kv_cache_policy",
     "slimt_hip_model_set_xcd_affinity", "slimt_hip_model_device",
@@ -247,6 +247,8 @@ def lib():
     L.slimt_hip_debug_kv_watch.argtypes = [vp, vp, vp, vp]
     L.slimt_hip_debug_kv_tight_limit.argtypes = [vp, i32]
     L.slimt_hip_debug_kv_tight_watch.argtypes = [vp, vp, vp, vp]
+    L.slimt_hip_debug_out_tied_exact.argtypes = [vp, vp]
+    L.slimt_hip_debug_tied_output_proof.argtypes = [vp, sz, sz, f32, vp]
     L.slimt_hip_debug_kv_recalibrations.argtypes = [vp, vp, i32]
     L.slimt_hip_debug_kv_centres.argtypes = [vp, vp, sz, vp]
     L.slimt_hip_model_set_kv_centres.argtypes = [vp, vp, sz]
@@ -448,6 +450,16 @@ def affine_acc_i32(x, W_nk, a_quant: float):
     return acc
 
 
+def debug_tied_output_proof(wemb, multiplier: float) -> bool:
+    """The load-time proof on an int8 table [V][D] alone (host code, no device): re-quantising the dequantised table
+    by its multiplier gives every byte back."""
+    w = np.ascontiguousarray(wemb, dtype=np.int8)
+    rows, cols = w.shape
+    out = C.c_int(0)
+    _chk(lib().slimt_hip_debug_tied_output_proof(_p(w), rows, cols, float(multiplier), C.byref(out)))
+    return bool(out.value)
+
+
 def prepare_weight_transposed(weights, quant_mult: float):
     w = _f32(weights)
     rows, cols = w.shape
@@ -565,6 +577,13 @@ class Model:
     def debug_kv_tight_limit(self, limit: int):
         """Signed accumulators must lie in [-limit, limit) for the 16-bit cache form (default and maximum 2**15; 0 = never tried)."""
         _chk(lib().slimt_hip_debug_kv_tight_limit(self.h, int(limit)))
+
+    def debug_out_tied_exact(self) -> bool:
+        """Whether the load proved the tied output layer byte-equal to the embedding table (the fused decoder then
+        reads the next embedding row from the output layer's tile)."""
+        out = C.c_int(0)
+        _chk(lib().slimt_hip_debug_out_tied_exact(self.h, C.byref(out)))
+        return bool(out.value)
 
     def set_kv_centres(self, centres):
         """The 16-bit cache form's per-column centres, int32 [Ld][2][D] (else calibrated from the first large batch)."""

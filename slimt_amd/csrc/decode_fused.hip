@@ -96,6 +96,7 @@ __device__ __forceinline__ Dequant4 dequant4(const v4i &acc, int colsum, float u
 // past the last tile return zeros, so prefetches need no predicate and the
 // compiler's s_waitcnt counts stay exact.
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
+typedef __attribute__((address_space(3))) void *lds_void_ptr;  // (the destination of a buffer load that writes LDS)
 __device__ __forceinline__ rsrc_t make_rsrc(const void *p, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, bytes, 0x00020000);
 }
@@ -1893,6 +1894,11 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
       const int row = 16 * rr + wave;
       uint32_t tok = 0;
       [[maybe_unused]] float score = 0.0f;  // SC: the token's log-probability (lane 0's)
+      constexpr int EW = (KSD + 3) / 4;  // dwords of an embedding row per lane
+      // (not in the two instantiations that were spill-free without it and spilled one register with it -- the unmerged
+      // 16-sentence tiling with the tight cache form inlined, plain and scored: they keep the table; profiles/r21_seam_resources.txt)
+      constexpr bool TILE_EMBED = !(!MG && KSD == 4 && !LONG && !NT && RT == 1 && KV24 && MID == 0 && SPW == 16 && CL == 1 && KVI == 16 && !FP && !SM);
+      bool from_tile = false;
       {
         int ix;
         if constexpr (CL > 1) {
@@ -1929,6 +1935,35 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
           ix = lane < NW ? red_i[lane * R + row] : 0x7fffffff;
           row16_argmax(v, ix);
           ix = __builtin_amdgcn_readfirstlane(ix);
+        }
+        // The next step's embedding row from the output layer's packed tile (kernels.h, out_tied_exact): column ix of
+        // outw holds the 4 KSD 16-byte pieces of wemb[sl[ix]] -- piece (ks, lg) at ((tile KSD + ks) 1024 + (lg 16 + lr) 16),
+        // tile = ix >> 4, lr = ix & 15 (device_common.h, pack_weight_tile) --, which the logits have just streamed
+        // through this XCD's L2. A lane takes dword w = lane (+ 64) of the row, bytes d = 4 w .. 4 w + 3: dword w & 3 of
+        // piece w >> 2. Requested before the token's own load, which only record() waits for, and straight into LDS
+        // (no register is free to hold a load across record() in the headline's instantiation: held in registers the
+        // row and the positions were spilled where they were requested, i.e. waited for there): the row's bytes in
+        // order into this sentence's row of A2, the position row into its row of pre -- both dead until the next
+        // step's SSRU rewrites them. Forced rows, rows whose column is the NaN rule's, and finished ones keep the
+        // table (wave-uniform: one branch).
+        {
+          bool forced_now = false;
+          if constexpr (FP) forced_now = ftok[rr] != 0xffffffffu;
+          from_tile = TILE_EMBED && a.out_tied_exact && t + 1 < max_steps && live[rr] && !finished[rr] && !forced_now && ix != 0x7fffffff && !nan0;
+        }
+        if (from_tile) {
+          const rsrc_t rw = make_rsrc(outw.Wp, (unsigned)outw.n_tiles * KSD * 1024u);
+          const rsrc_t rp = make_rsrc(a.emb.pos, D * 4u);
+#pragma unroll
+          for (int i = 0; i < EW; ++i) {
+            const int w = lane + 64 * i;
+            if (w < 16 * KSD) {  // (the destination is the wave-uniform base + 4 / 16 bytes per lane)
+              __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_void_ptr)(A2 + row * LDA + 256 * i), 4,
+                                                       (w >> 4) * 1024 + ((w >> 2) & 3) * 256 + (ix & 15) * 16 + (w & 3) * 4,
+                                                       (ix >> 4) * (KSD * 1024), 0, 0);
+              __builtin_amdgcn_raw_ptr_buffer_load_lds(rp, (lds_void_ptr)(pre + row * LDF + 256 * i), 16, w * 16, 0, 0, 0);
+            }
+          }
         }
         // no column beat the start value (every logit NaN or -inf): class 0, where the reference's scan
         // starts and stays (Transformer.cc:287-298) -- and never an index past the shortlist
@@ -1971,15 +2006,36 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
       }
       if (t + 1 < max_steps) {
         // next target embedding (Transformer.cc:146-160): position is always 0
+        if (from_tile) {  // the same integers through the same three operations as below, four consecutive columns per lane
+          // (the compiler does not order LDS reads behind loads that write LDS: the wave's loads have all landed)
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-        for (int i = 0; i < KSD; ++i) {
-          float v = 0.0f;
-          if (live[rr]) {
-            const float e = (float)a.emb.wemb[(size_t)embed_row(a.emb, tok) * D + lane + 64 * i] * a.emb.inv_mult;
-            const float sc = e * a.emb.sqrt_d;
-            v = sc + a.emb.pos[lane + 64 * i];
+          for (int i = 0; i < EW; ++i) {
+            const int w = lane + 64 * i;
+            if (w < 16 * KSD) {
+              const int q = *reinterpret_cast<const int *>(A2 + row * LDA + 4 * w);
+              const f4 p = *reinterpret_cast<const f4 *>(pre + row * LDF + 4 * w);
+              f4 v;
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                const float e = (float)(int8_t)(q >> (8 * j)) * a.emb.inv_mult;
+                const float sc = e * a.emb.sqrt_d;
+                v[j] = sc + p[j];
+              }
+              *reinterpret_cast<f4 *>(xs + row * LDF + 4 * w) = v;
+            }
           }
-          xs[row * LDF + lane + 64 * i] = v;
+        } else {
+#pragma unroll
+          for (int i = 0; i < KSD; ++i) {
+            float v = 0.0f;
+            if (live[rr]) {
+              const float e = (float)a.emb.wemb[(size_t)embed_row(a.emb, tok) * D + lane + 64 * i] * a.emb.inv_mult;
+              const float sc = e * a.emb.sqrt_d;
+              v = sc + a.emb.pos[lane + 64 * i];
+            }
+            xs[row * LDF + lane + 64 * i] = v;
+          }
         }
       }
     }

@@ -764,6 +764,7 @@ int model_build(slimt_hip_model *m, const slimt_hip_param *params, size_t n,
                                               (size_t)V));
     HIPCHK(m->out_raw.reserve(VD));
     HIPCHK(hipMemcpy(m->out_raw.p, prepared.data(), VD, hipMemcpyHostToDevice));
+    m->out_tied_exact = memcmp(prepared.data(), wq, VD) == 0;  // (both [V][D]: the preparation keeps the layout)
   }
   RCCHK(scalar_f32(t, "none_QuantMultA", &m->out_a_quant));
   RCCHK(upload_f32(m->out_bias, t, "decoder_ff_logit_out_b", (size_t)V));
@@ -1040,6 +1041,26 @@ extern "C" int slimt_hip_debug_ctx_shortlists(slimt_hip_ctx *ctx, size_t n_batch
     const size_t n = std::min(std::min((size_t)counts[j], capacity), V);  // (a count above V is reported as it is, never followed)
     if (n) HIPCHK(hipMemcpy(ids + j * capacity, ctx->shortlist.as<uint32_t>() + j * V, n * 4, hipMemcpyDeviceToHost));
   }
+  return 0;
+}
+
+extern "C" int slimt_hip_debug_out_tied_exact(slimt_hip_model *model, int *exact) {
+  if (!model || !exact) return fail(-1, "null argument");
+  *exact = model->out_tied_exact ? 1 : 0;
+  return 0;
+}
+
+// The proof model_build runs on a model's Wemb, on the caller's table [rows][cols] alone (no device): the table
+// dequantised, re-quantised by its own multiplier, compared byte for byte.
+extern "C" int slimt_hip_debug_tied_output_proof(const int8_t *wemb, size_t rows, size_t cols, float multiplier, int *exact) {
+  if (!wemb || !exact) return fail(-1, "null argument");
+  const size_t n = rows * cols;
+  std::vector<float> E(n);
+  const float inv = 1 / multiplier;
+  for (size_t i = 0; i < n; ++i) E[i] = static_cast<float>(wemb[i]) * inv;
+  std::vector<int8_t> prepared(n);
+  RCCHK(slimt_hip_prepare_weight_transposed(E.data(), prepared.data(), multiplier, cols, rows));
+  *exact = memcmp(prepared.data(), wemb, n) == 0 ? 1 : 0;
   return 0;
 }
 
@@ -2481,6 +2502,7 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     f.out_n_dev = d_n_sl;
     f.shortlist = ds.shortlist;
     f.emb = embed_args(c);
+    f.out_tied_exact = m->out_tied_exact;
     f.kv = c->kv.as<float>();
     f.kv24 = kv24;
     if (kv24 && c->kv_fmt_valid && c->kv_fmt_B == (int)B) f.kv_fmt = c->kv_fmt.as<unsigned char>();

@@ -106,6 +106,9 @@ struct slimt_hip_model {
   slimt_hip::DevBuf wemb;      // int8 [V][D] (embedding lookup, Io.cc:191-200)
   float wemb_mult = 0.f;       // quantisation multiplier of Wemb
   slimt_hip::DevBuf out_raw;   // Wemb_intgemm8: int8 [V][D] (Io.cc:206-224)
+  // out_raw equals the table byte for byte (proved at load: re-quantising float(q) / m by m gives q back for every
+  // |q| <= 127, a -128 comes back as -127): the fused decoder may read an embedding row from the output layer's tile
+  bool out_tied_exact = false;
   slimt_hip::DevBuf out_bias;  // decoder_ff_logit_out_b [V]
   float out_a_quant = 0.f;     // none_QuantMultA (Transformer.cc:111-113)
   slimt_hip::AffineW out_full; // full-vocabulary output layer

@@ -386,6 +386,11 @@ struct FusedDecodeArgs {
   const uint32_t *out_n_dev = nullptr;  // nullable: number of output columns, on the device
   const uint32_t *shortlist = nullptr;  // nullable: column -> vocabulary id
   EmbedArgs emb;
+  // The output layer is the embedding table re-quantised (engine.cpp, model_build), and the model's load proved that
+  // every byte came back: column c of `out` (whichever pack: a shortlist's, a merged job's, the full vocabulary's) then
+  // holds the D bytes of emb.wemb[shortlist[c]], and the row-wave takes the next step's embedding from there -- L2-hot
+  // behind the logits and addressed by the column alone -- instead of waiting for shortlist[c] first. false: the table.
+  bool out_tied_exact = false;
   const float *kv = nullptr;            // [Ld][2][B*S*D]: K as [B][H][dh/4][S][4], V as [B*S][D]; values float(accS)
   float *cells = nullptr;               // [Ld][B][D] SSRU cells, used (and zeroed) when D > 256
   const uint32_t *lengths = nullptr;

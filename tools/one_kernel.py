@@ -13,7 +13,7 @@ while args:
     elif a == "--src": srcf = args.pop(0)
     else: extra.append(a)
 s = open(srcf).read()
-cut = s.index("template <bool MG, int KSD, int KSF, int DH>\nstatic auto decode_fused_pick")
+cut = s.rindex("template <", 0, s.index("static constexpr auto dfk()"))  # (everything from the kernel pickers on goes)
 s = s[:cut] + "template __global__ void decode_fused_kernel<%s>(FusedDecodeArgs);\n}  // namespace slimt_hip\n" % targs
 tmp = os.path.join(ROOT, "slimt_amd/csrc/_one_kernel.hip")
 open(tmp, "w").write(s)
