@@ -911,6 +911,13 @@ int slimt_hip_debug_kv_narrow_limit(slimt_hip_model *model, int limit);
 int slimt_hip_debug_out_tied_exact(slimt_hip_model *model, int *exact);
 /* ... and the proof alone, on a caller's table [rows][cols] with its multiplier: host code, needs no device. */
 int slimt_hip_debug_tied_output_proof(const int8_t *wemb, size_t rows, size_t cols, float multiplier, int *exact);
+/* Diagnostic: the dynamic LDS the persistent decoder's launcher asks for, for a shape (D, F, decoder layers), the
+ * sentences per workgroup (32 / 16 / 8 / 4), a packed cache (kv24), a sentence-length class (mid: 0 = up to 32 tokens,
+ * 1 = 33..64, 2 = 65..128), the tight cache form and what else picks the kernel (flags: bit 0 merged, 1 non-temporal
+ * cache loads, 2 scored, 3 forced, 4 sampled) -- and whether the LayerNorm constants and the output layer's epilogue
+ * constants are part of it. Host code, needs no device. */
+int slimt_hip_debug_fused_decode_lds_bytes(int D, int F, int Ld, int sentences_per_wg, int kv24, int mid, int tight,
+                                           unsigned flags, size_t *bytes, int *ln_in_lds, int *epi_in_lds);
 /* Diagnostic: the tight (16-bit) form below the 20-bit one. Where the decoder has a reader for it (D = 256 /
  * F = 1536 with sentences of up to 128 tokens, D = 512 / F = 2048 up to 32) format 0 caches a
  * sentence-layer whose K and V accumulators, less their columns' centres (slimt_hip_model_set_kv_centres),

@@ -30,7 +30,7 @@ SYMBOLS = [
     "slimt_hip_ctx_synchronize", "slimt_hip_ctx_set_decode_mode", "slimt_hip_ctx_set_encode_rows", "slimt_hip_ctx_plan", "slimt_hip_translate", "slimt_hip_translate_device",
     "slimt_hip_encode", "slimt_hip_decode_begin", "slimt_hip_decode_step",
     "slimt_hip_profile_enable", "slimt_hip_profile_read", "slimt_hip_profile_reset",
-    "slimt_hip_debug_decode_stamps", "slimt_hip_debug_kv_formats", "slimt_hip_debug_kv_narrow_limit", "slimt_hip_debug_kv_tight_limit", "slimt_hip_debug_out_tied_exact", "slimt_hip_debug_tied_output_proof", "slimt_hip_debug_kv_tight_watch", "slimt_hip_debug_kv_centres", "slimt_hip_model_set_kv_centres", "slimt_hip_debug_kv_watch", "slimt_hip_debug_break_shortlist_handoff", "slimt_hip_debug_cross_attention",
+    "slimt_hip_debug_decode_stamps", "slimt_hip_debug_kv_formats", "slimt_hip_debug_kv_narrow_limit", "slimt_hip_debug_kv_tight_limit", "slimt_hip_debug_out_tied_exact", "slimt_hip_debug_tied_output_proof", "slimt_hip_debug_fused_decode_lds_bytes", "slimt_hip_debug_kv_tight_watch", "slimt_hip_debug_kv_centres", "slimt_hip_model_set_kv_centres", "slimt_hip_debug_kv_watch", "slimt_hip_debug_break_shortlist_handoff", "slimt_hip_debug_cross_attention",
     "slimt_hip_debug_occupancy_trace", "slimt_hip_debug_decoder_plan", "slimt_hip_model_set_decoder_budget",
     "slimt_hip_model_set_kv_cache_policy",
     "slimt_hip_model_set_xcd_affinity", "slimt_hip_model_device",
@@ -249,6 +249,7 @@ def lib():
     L.slimt_hip_debug_kv_tight_watch.argtypes = [vp, vp, vp, vp]
     L.slimt_hip_debug_out_tied_exact.argtypes = [vp, vp]
     L.slimt_hip_debug_tied_output_proof.argtypes = [vp, sz, sz, f32, vp]
+    L.slimt_hip_debug_fused_decode_lds_bytes.argtypes = [C.c_int] * 7 + [C.c_uint, vp, vp, vp]
     L.slimt_hip_debug_kv_recalibrations.argtypes = [vp, vp, i32]
     L.slimt_hip_debug_kv_centres.argtypes = [vp, vp, sz, vp]
     L.slimt_hip_model_set_kv_centres.argtypes = [vp, vp, sz]
@@ -458,6 +459,18 @@ def debug_tied_output_proof(wemb, multiplier: float) -> bool:
     out = C.c_int(0)
     _chk(lib().slimt_hip_debug_tied_output_proof(_p(w), rows, cols, float(multiplier), C.byref(out)))
     return bool(out.value)
+
+
+def debug_fused_decode_lds_bytes(D: int, F: int, Ld: int, sentences_per_wg: int, kv24: bool = True, mid: int = 0, tight: bool = False,
+                                 merged: bool = False, nt: bool = False, scores: bool = False, forced: bool = False,
+                                 sampled: bool = False) -> dict:
+    """The dynamic LDS the persistent decoder's launcher asks for (host code, no device): bytes, and whether the LayerNorm
+    constants / the output layer's epilogue constants are resident in it."""
+    n, ln, epi = C.c_size_t(0), C.c_int(0), C.c_int(0)
+    flags = (1 if merged else 0) | (2 if nt else 0) | (4 if scores else 0) | (8 if forced else 0) | (16 if sampled else 0)
+    _chk(lib().slimt_hip_debug_fused_decode_lds_bytes(D, F, Ld, sentences_per_wg, 1 if kv24 else 0, mid, 1 if tight else 0, flags,
+                                                      C.byref(n), C.byref(ln), C.byref(epi)))
+    return dict(bytes=int(n.value), ln_in_lds=bool(ln.value), epi_in_lds=bool(epi.value))
 
 
 def prepare_weight_transposed(weights, quant_mult: float):

@@ -123,14 +123,21 @@ __device__ __forceinline__ v4i load_frag(rsrc_t r, int voff, int soff) {
 // RT row tiles (16 RT rows of A): every weight fragment feeds RT MFMAs; epi(tile, rt, ...)
 // runs once per finished (column tile, row tile).
 // The stream's descriptors and this lane's offsets.
-template <int KS, int NT, bool PAIRED = false>
+// EL (the 8- and 4-sentence tilings, PAIRED streams only): the pair constants of this launch are resident in LDS (`el`: a copy
+// of the weight's cp4 array, staged once by the kernel's prologue) and a chunk takes its quad from there -- no request
+// on the address path.
+template <int KS, int NT, bool PAIRED = false, bool EL = false>
 struct StreamSrc {
+  static_assert(!EL || PAIRED, "resident epilogue constants: the pair layout");
   rsrc_t rw, rc, rp;
   int voff, eoff, n_tiles;
-  __device__ __forceinline__ StreamSrc(const PreparedWeight &w, int lane) {
+  const char *el;
+  __device__ __forceinline__ StreamSrc(const PreparedWeight &w, int lane, const char *el_ = nullptr) : el(el_) {
     n_tiles = NT > 0 ? NT * NW : w.n_tiles;
     rw = make_rsrc(w.Wp, (unsigned)n_tiles * KS * 1024u);
-    if constexpr (PAIRED) {  // pair constants (kernels.h, PreparedWeight::cp4): one descriptor, 16 bytes per lane
+    if constexpr (EL) {
+      eoff = (lane & 15) * 16;
+    } else if constexpr (PAIRED) {  // pair constants (kernels.h, PreparedWeight::cp4): one descriptor, 16 bytes per lane
       rc = make_rsrc(w.cp4, (unsigned)(16 * ((n_tiles + 31) / 32)) * 256u);
       rp = rc;
       eoff = (lane & 15) * 16;
@@ -154,7 +161,14 @@ struct StreamSrc {
     for (int ks = 0; ks < KS; ++ks) bb.f[ks] = load_frag(rw, voff, (tile * KS + ks) * 1024);
 #ifndef SLIMT_EXP_NOEPI
     if constexpr (HOLD) {
-      const v4i q = load_frag(rc, eoff, (NW * (c >> 1) + wave) * 256);
+      v4i q;
+      if constexpr (EL) {  // (a padded round's chunks past the last pair re-read the last one: their tiles are ignored)
+        const int pairs = (n_tiles + 31) / 32;
+        const int pr = NT > 0 ? (c >> 1) : ((c >> 1) < pairs ? (c >> 1) : pairs - 1);
+        q = *reinterpret_cast<const v4i *>(el + (NW * pr + wave) * 256 + eoff);
+      } else {
+        q = load_frag(rc, eoff, (NW * (c >> 1) + wave) * 256);
+      }
       // (__int_as_float on a copy: __builtin_bit_cast(float, q.y) of a vector ELEMENT reads element 0 with this compiler)
       const int y = q.y, w4 = q.w;
       bb.cs[0] = q.x;
@@ -197,10 +211,10 @@ struct StreamSrc {
 // on the phase before, so a wave asks for them as soon as its own work in that phase is done
 // (or before it, where that pays) and the round trip runs under the barrier wait (lds_barrier
 // keeps global loads in flight).
-template <int KS, int NB, int NT = 0, bool PADDED = false>
-__device__ __forceinline__ void stream_prologue(const PreparedWeight &w, int wave, int lane, Frags (&b)[NB]) {
+template <int KS, int NB, int NT = 0, bool PADDED = false, bool EL = false>
+__device__ __forceinline__ void stream_prologue(const PreparedWeight &w, int wave, int lane, Frags (&b)[NB], const char *el = nullptr) {
   constexpr bool PAIRED = KS == CH && (NT > 0 || (PADDED && NB % 2 == 0));  // epilogue constants fetched per two chunks
-  const StreamSrc<KS, NT, PAIRED> src(w, lane);
+  const StreamSrc<KS, NT, PAIRED, EL> src(w, lane, el);
   if constexpr (NT > 0) {
     constexpr int NCH = KS <= CH ? (NT + CH / KS - 1) / (CH / KS) : NT * (KS / CH);
 #pragma unroll
@@ -238,11 +252,11 @@ __device__ __forceinline__ void stream_prologue(const PreparedWeight &w, int wav
 }
 
 // The stream proper; b holds the chunks stream_prologue requested.
-template <int KS, int NB, int NT = 0, bool PADDED = false, int RT = 1, class Epi>
+template <int KS, int NB, int NT = 0, bool PADDED = false, int RT = 1, bool EL = false, class Epi>
 __device__ __forceinline__ void stream_gemm_from(const char *A, int lda, const PreparedWeight &w, int wave,
-                                                 int lane, Frags (&b)[NB], Epi &&epi) {
+                                                 int lane, Frags (&b)[NB], Epi &&epi, const char *el = nullptr) {
   constexpr bool PAIRED = KS == CH && (NT > 0 || (PADDED && NB % 2 == 0));
-  const StreamSrc<KS, NT, PAIRED> src(w, lane);
+  const StreamSrc<KS, NT, PAIRED, EL> src(w, lane, el);
   const int n_tiles = src.n_tiles;
   const int lr = lane & 15, lg = lane >> 4;
   const int ntw = n_tiles > wave ? (n_tiles - wave + NW - 1) / NW : 0;  // my tiles
@@ -979,11 +993,23 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
   // [Ld][B][D]; 1 KiB per sentence and layer, read and written once per step).
   constexpr bool LEAN = KSD * RT > 4;
   constexpr bool CELLS_GLOBAL = LEAN || MID == 2;  // SSRU cells in a.cells instead of LDS
+  // The 8- and 4-sentence tilings at D = 256 (TRIM) keep what only live sentences use at the live sentences' size: the f32
+  // rows and the SSRU cells as RS rows plus FOUR rows that the accumulator lanes of the MFMA rows no wave owns read and
+  // write instead of rows RS .. 15 (SLIMT_ROW4 below: no branch in any epilogue, nothing reads what lands there), and the
+  // attention scratch of the RS row waves. The int8 operands keep their 16 rows (the rows no wave owns are zero: measured
+  // with RS rows and one shared zero row, every lane of those rows reading one address cost each projection more than
+  // the trim freed). The LDS that frees holds the output layer's epilogue constants of the launch (epc_out below;
+  // fused_decode_lds_bytes has the same carve-up).
+  // (not the merged twins: 12 spilled registers for 1 with it; not the 4-sentence tiling with non-temporal cache loads and the
+  // tight form inlined: 59 for 56 -- they keep the parent's layout; kernels.h, fused_decode_trimmed: the launcher asks the same)
+  constexpr bool TRIM = fused_decode_trimmed(MG, KSD, SPW, NT, MID, KVI == 16);
+  constexpr int RF = TRIM ? RS + 4 : R;  // f32 rows, rows of SSRU cells per layer
+  constexpr int PW = TRIM ? RS : NW;     // slots of attention scratch
   float *xs = reinterpret_cast<float *>(smem);  // layer input rows (post-LN); reused for q
-  float *hs = xs + R * LDF;                     // h / o rows (post-LN residual source)
-  float *pre = LEAN ? hs : hs + R * LDF;        // pre-LN accumulation
-  float *cs = pre + R * LDF;                    // SSRU cells [Ld][R][D] (full layout only)
-  char *A1 = reinterpret_cast<char *>(cs + (CELLS_GLOBAL ? 0 : (size_t)Ld * R * D));
+  float *hs = xs + RF * LDF;                    // h / o rows (post-LN residual source)
+  float *pre = LEAN ? hs : hs + RF * LDF;       // pre-LN accumulation
+  float *cs = pre + RF * LDF;                   // SSRU cells [Ld][RF][D] (full layout only)
+  char *A1 = reinterpret_cast<char *>(cs + (CELLS_GLOBAL ? 0 : (size_t)Ld * RF * D));
   char *A2 = A1 + R * LDA;
   char *A3 = A2 + R * LDA;
   float *red_v = reinterpret_cast<float *>(A3 + R * LDA3);  // [NW][R]
@@ -996,7 +1022,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
   [[maybe_unused]] uint32_t *seed_s = reinterpret_cast<uint32_t *>(red_z + NW * R);  // SM: [2][R] the rows' hash words of the step
   int *flags = red_i + NW * R + (SC ? NW * R : 0) + (FP ? 2 * R : 0) + (SM ? 2 * NW * R + 2 * R : 0);  // [0] = number of finished sentences of this tile
   float *pbufs = reinterpret_cast<float *>(flags + 16);  // [NW][256] attention scratch
-  float *kvpb = pbufs + NW * PBW;  // KV24: [Ld][K pb, V pb][D], or at D = 512 [Ld][K pb, K c127, V pb, V c127][D]
+  float *kvpb = pbufs + PW * PBW;  // KV24: [Ld][K pb, V pb][D], or at D = 512 [Ld][K pb, K c127, V pb, V c127][D]
   // LayerNorm scale / bias of every layer in LDS ([Ld][rnn, attn, ffn][scale, bias][D]) where it fits:
   // fetched per phase they are vector-memory loads that return IN ORDER behind whatever the wave
   // asked for before -- a weight prefetch in front of a LayerNorm would stall it by its whole transfer
@@ -1004,6 +1030,26 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
   float *lnc = kvpb + (KV24 ? Ld * KVC * D : 0);
   const bool ln_lds = LN_LDS && a.ln_in_lds;  // (the launcher: only where the 160 KiB allow it)
   float *kvc127 = lnc + (ln_lds ? Ld * 6 * D : 0);  // KVI == 16: [Ld][K, V][D] float(centre) (attention_packed32 with Form16)
+  // TRIM: the output layer's epilogue constants of this launch, copied once by the prologue below (a.epi_in_lds: the
+  // launcher, where the 160 KiB allow it) -- its pair constants (PreparedWeight::cp4, as they lie in global memory) of up
+  // to EPC_OUT_TILES column tiles; a wider layer keeps its loads. A 64-byte load holds the CU's address path like a 1 KiB
+  // one, and these were one per two tiles of every step.
+  constexpr int EPC_OUT_TILES = kFusedEpiOutTiles;
+  [[maybe_unused]] char *epc_out = reinterpret_cast<char *>(kvc127 + (KVI == 16 ? Ld * (RT == 1 ? 2 : 1) * D : 0));
+  const bool epi_lds = TRIM && a.epi_in_lds;
+  if constexpr (TRIM) {  // the kernel's constants against the launcher's carve-up (Ld = 2; the terms are linear in Ld)
+    constexpr size_t mine = (size_t)3 * RF * LDF * 4 + (CELLS_GLOBAL ? 0 : (size_t)2 * RF * D * 4) + 2 * R * LDA + R * LDA3 + 2 * NW * R * 4 + 64 +
+                            (size_t)PW * PBW * 4 + 2 * KVC * D * 4 + (LN_LDS ? 2 * 6 * D * 4 : 0) + (KVI == 16 ? 2 * 2 * D * 4 : 0) +
+                            EPC_OUT_TILES / 32 * NW * 256;
+    static_assert(!LEAN && !SC && RT == 1, "the trimmed layout: three f32 row buffers, unscored, one row tile");
+    static_assert(mine == fused_decode_lds_bytes(D, F, 2, 16, true, MID, nullptr, KVI == 16, false, false, false, SPW),
+                  "the kernel's pointers end where fused_decode_lds_bytes says");
+    static_assert(mine <= 160 * 1024, "the headline's two layers keep the output layer's constants resident");
+  }
+  // the row block of this lane's four accumulator rows in the f32 buffers and the cells (TRIM: the lanes of rows RS .. 15
+  // share the four rows behind the live ones)
+  // (re-derived per phase: held across the loop it cost the headline's instantiation 11 more spilled registers)
+#define SLIMT_ROW4 (TRIM && lg * 4 >= RS ? RS : lg * 4)
 
   // Which R sentences? With a ticket counter the grid is over-subscribed and the first
   // workgroups to START claim the tiles; the rest leave at once. A workgroup needs a whole
@@ -1123,7 +1169,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
     for (int l = 0; l < Ld; ++l)
       for (int i = tid; i < valid_rows * D; i += 1024) a.cells[((size_t)l * B + m0) * D + i] = 0.0f;
   } else {
-    for (int i = tid; i < Ld * R * D; i += 1024) cs[i] = 0.0f;
+    for (int i = tid; i < Ld * RF * D; i += 1024) cs[i] = 0.0f;
   }
   if (tid == 0) flags[0] = 0;
   if constexpr (SPW < 16) {  // operand rows no wave owns: defined (zero) for the whole loop
@@ -1170,7 +1216,8 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
 #pragma unroll
     for (int i = 0; i < KSD; ++i) {
       const float z = 0.0f * a.emb.sqrt_d;
-      xs[(16 * rr + wave) * LDF + lane + 64 * i] = live[rr] ? z + a.emb.pos[lane + 64 * i] : 0.0f;
+      // (TRIM: the f32 buffers have the row waves' rows and four rows nothing reads)
+      if (!TRIM || row_wave) xs[(16 * rr + wave) * LDF + lane + 64 * i] = live[rr] ? z + a.emb.pos[lane + 64 * i] : 0.0f;
     }
   }
   __syncthreads();
@@ -1193,6 +1240,17 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
   // from logits[0] and only moves on `value > max`, so it stays at class 0 (Transformer.cc:287-298); the arg-max
   // below skips NaNs, so the rule is applied where the token is taken
   const bool nan0 = outw.pb[0] != outw.pb[0] || a.out.u != a.out.u;
+  // TRIM: the output layer's epilogue constants of this launch into LDS (whichever pack it uses; a column count known
+  // only here decides here, for the whole workgroup alike, whether they are resident). The barriers of the first step's
+  // layers order the copy before its first reader.
+  const bool out_lds = epi_lds && outw.n_tiles >= 1 && outw.n_tiles <= EPC_OUT_TILES;
+  if constexpr (TRIM) {
+    if (out_lds) {
+      const int quads = (outw.n_tiles + 31) / 32 * NW * 16;  // (bytes past the pack's last pair read as zero)
+      const rsrc_t rc = make_rsrc(outw.cp4, (unsigned)quads * 16u);
+      for (int i = tid; i < quads; i += 1024) reinterpret_cast<v4i *>(epc_out)[i] = load_frag(rc, i * 16, 0);
+    }
+  }
   // FP: each row's prefix length (clamped to its row of outputs) and the token forced at the current step (0xffffffff:
   // none); step 0's column goes to fcol_s here -- the barriers of the step's layers order it before the epilogue
   [[maybe_unused]] uint32_t plen[RT], ftok[RT];
@@ -1244,7 +1302,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
     for (int l = 0; l < Ld; ++l) {
       SLIMT_PHASE_LANE;
       const FusedLayerW &L = a.L[l];
-      float *cl = CELLS_GLOBAL ? a.cells + ((size_t)l * B + m0) * D : cs + (size_t)l * R * D;
+      float *cl = CELLS_GLOBAL ? a.cells + ((size_t)l * B + m0) * D : cs + (size_t)l * RF * D;
       const int sb = 1 + 10 * l;
       // ---- SSRU (Modules.cc:190-235) ------------------------------------
       // quantise x twice (Wf / W have their own multipliers)
@@ -1298,7 +1356,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
           const Dequant4 f4v = dequant4(accf, csf, L.rnn_f.u, pbf), w4v = dequant4(accw, csw, L.rnn_w.u, pbw);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int rl = 16 * rt + lg * 4 + r;
+            const int rl = 16 * rt + SLIMT_ROW4 + r;
             const float f = f4v.v[r];
             const float wx = w4v.v[r];
             const bool cell_ok = !CELLS_GLOBAL || rl < valid_rows;  // global cells: rows of this batch only
@@ -1339,7 +1397,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
                                              const Dequant4 q4v = dequant4(acc, cq, L.q.u, pb);
 #pragma unroll
                                              for (int r = 0; r < 4; ++r)
-                                               xs[(16 * rt + lg * 4 + r) * LDF + col] = q4v.v[r];
+                                               xs[(16 * rt + SLIMT_ROW4 + r) * LDF + col] = q4v.v[r];
                                            });
       lds_barrier();
       SLIMT_STAMP(sb + 3);
@@ -1524,7 +1582,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
                                              const Dequant4 o4v = dequant4(acc, co, L.o.u, pb);
 #pragma unroll
                                              for (int r = 0; r < 4; ++r) {
-                                               const int rl = 16 * rt + lg * 4 + r;
+                                               const int rl = 16 * rt + SLIMT_ROW4 + r;
                                                pre[rl * LDF + col] = o4v.v[r] + hs[rl * LDF + col];
                                              }
                                            });
@@ -1572,7 +1630,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
             const Dequant4 y4v = dequant4(acc, c2, L.ffn2.u, pb);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              const int rl = 16 * rt + lg * 4 + r;
+              const int rl = 16 * rt + SLIMT_ROW4 + r;
               pre[rl * LDF + col] = y4v.v[r] + hs[rl * LDF + col];
             }
           });
@@ -1796,9 +1854,11 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
       }
     } else {
     Frags fl[NB_OUT];  // requested before the barrier that ends the last LayerNorm
-    stream_prologue<KSD, NB_OUT, 0, (KSD >= 4)>(outw, wave, lane, fl);
-    lds_barrier();
-    SLIMT_STAMP(43);
+    if constexpr (!TRIM) {
+      stream_prologue<KSD, NB_OUT, 0, (KSD >= 4)>(outw, wave, lane, fl);
+      lds_barrier();
+      SLIMT_STAMP(43);
+    }
     float bv[RT][4];
     int bi[RT][4];
     [[maybe_unused]] float bs[RT][4];  // SC: sum of exp(logit - bv) over this lane's columns so far
@@ -1818,8 +1878,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
           zw[rt][r] = 0.0f;
         }
       }
-    stream_gemm_from<KSD, NB_OUT, 0, (KSD >= 4), RT>(
-        A1, LDA, outw, wave, lane, fl, [&](int tile, int rt, const v4i &acc, int co, float pb) {
+    auto out_epi = [&](int tile, int rt, const v4i &acc, int co, float pb) {
           const int col = tile * 16 + lr;
           const bool in_range = col < outw.N;  // no branch: the streaming loop stays one block
           const Dequant4 l4v = dequant4(acc, co, a.out.u, pb);
@@ -1861,7 +1920,24 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
             bv[rt][r] = better ? v : bv[rt][r];
             bi[rt][r] = better ? col : bi[rt][r];
           }
-        });
+        };
+    if constexpr (TRIM) {
+      // two copies of the whole phase, chosen once (the workgroup alike): a branch inside the loop would cost it its exact
+      // wait counts, and one between the requests and the loop made the chunks in flight change registers (100 spilled)
+      if (out_lds) {
+        stream_prologue<KSD, NB_OUT, 0, true, true>(outw, wave, lane, fl, epc_out);
+        lds_barrier();
+        SLIMT_STAMP(43);
+        stream_gemm_from<KSD, NB_OUT, 0, true, RT, true>(A1, LDA, outw, wave, lane, fl, out_epi, epc_out);
+      } else {
+        stream_prologue<KSD, NB_OUT, 0, true>(outw, wave, lane, fl);
+        lds_barrier();
+        SLIMT_STAMP(43);
+        stream_gemm_from<KSD, NB_OUT, 0, true, RT>(A1, LDA, outw, wave, lane, fl, out_epi);
+      }
+    } else {
+      stream_gemm_from<KSD, NB_OUT, 0, (KSD >= 4), RT>(A1, LDA, outw, wave, lane, fl, out_epi);
+    }
     SLIMT_STAMP(44);
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
@@ -2083,6 +2159,7 @@ __global__ __launch_bounds__(1024) void decode_fused_kernel(FusedDecodeArgs a) {
     }
   }
   if (tid == 0) occ_trace_event(a.trace, 1, 1);
+#undef SLIMT_ROW4
 }
 
 // sentences per workgroup the fused decoder uses: 32 (two row tiles) on request (decode mode 3, or the
@@ -2104,32 +2181,6 @@ int fused_decode_rows(int D, int F, int H, int Ld, int S, int B, int forced, boo
 int fused_decode_grid(int B, bool tickets, int rows) {
   const int tiles = (B + rows - 1) / rows;
   return tickets ? tiles * (rows <= 16 ? 2 : 4) : tiles;
-}
-
-// ln_in_lds (out, nullable): whether the LayerNorm constants of all layers (LN_LDS in the kernel: the
-// D = 256, 16-row, non-MID variants) still fit the 160 KiB; the returned size includes them then.
-// tight: the kernels with the 16-bit cache form inlined (KVI = 16) keep its column terms [Ld][K, V][D] behind everything else.
-// scores: the scored kernels (SC) keep one more [NW][rows] float array beside the arg-max's (red_s)
-// forced: the forced kernels (FP) one float (ycap) and one int (fcol_s) per row
-// sampled: the sampled kernels (SM) two more [NW][rows] float arrays (red_m, red_z) and two words per row (seed_s)
-size_t fused_decode_lds_bytes(int D, int F, int Ld, int rows, bool kv24 = false, int mid = 0,
-                              bool *ln_in_lds = nullptr, bool tight = false, bool scores = false, bool forced = false,
-                              bool sampled = false) {
-  // D * rows > 256 * 16: two f32 row buffers, SSRU cells in global memory (see the kernel)
-  const size_t R = (size_t)rows;
-  const bool lean = (size_t)D * R > 256 * 16;
-  const size_t cells = (lean || mid == 2) ? 0 : (size_t)Ld * R * D * 4;
-  const size_t f32rows = (lean ? 2 : 3) * R * (D + 4) * 4 + cells;
-  const size_t base = f32rows + 2 * R * (size_t)(D + 32) + R * (size_t)(F + 32) + 2 * NW * R * 4 + 64 +
-                      NW * (mid == 2 ? 1024 : mid == 1 ? 512 : 256) * 4 + (kv24 ? (size_t)Ld * (D == 512 ? 4 : 2) * D * 4 : 0) +
-                      (tight ? (size_t)Ld * (rows > 16 ? 1 : 2) * D * 4 : 0) +  // (32 sentences: the K centres only)
-                      (scores ? (size_t)NW * R * 4 : 0) +
-                      (forced ? 2 * R * 4 : 0) +  // (FP: ycap and fcol_s, 128 bytes at 16 rows)
-                      (sampled ? 2 * (size_t)NW * R * 4 + 2 * R * 4 : 0);
-  const size_t ln = (D == 256 && rows == 16 && !mid) ? (size_t)Ld * 6 * D * 4 : 0;
-  const bool fits = ln > 0 && base + ln <= 160 * 1024;
-  if (ln_in_lds) *ln_in_lds = fits;
-  return fits ? base + ln : base;
 }
 
 // the tight (16-bit) cache form: the short-sentence tilings of 16 / 8 / 4 sentences, D = 256 / F = 1536 and D = 512 / F = 2048
@@ -2254,7 +2305,7 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
   }
   if (mid) {
     if (rows > 16 || F != 1536) return hipErrorInvalidValue;
-    const size_t ldsm = fused_decode_lds_bytes(D, F, a.Ld, 16, true, mid, nullptr, a.kv_tight, SC, FP, SM);
+    const size_t ldsm = fused_decode_launch_lds_bytes(D, F, a.Ld, rows, true, mid, a.kv_tight, SC, FP, SM, MG, a.kv_nt, nullptr, &a.epi_in_lds);
     if (ldsm > 160 * 1024) return hipErrorInvalidValue;
     if (a.kv_tight) {
 #define SLIMT_KV16_PICK(MID_, SPW_)                                                                \
@@ -2271,7 +2322,7 @@ static hipError_t launch_decode_fused_t(const FusedDecodeArgs &a_in, int D, int 
     if (only24) return go(SLIMT_KV24_ONLY(4, 24, 32, 1), ldsm);
     return go(SLIMT_KV24_PICK(4, 24, 32, 1), ldsm);
   }
-  const size_t lds = fused_decode_lds_bytes(D, F, a.Ld, rows <= 16 ? 16 : rows, kv24, 0, &a.ln_in_lds, a.kv_tight, SC, FP, SM);
+  const size_t lds = fused_decode_launch_lds_bytes(D, F, a.Ld, rows, kv24, 0, a.kv_tight, SC, FP, SM, MG, a.kv_nt, &a.ln_in_lds, &a.epi_in_lds);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   if (kv24 && D == 512) {
     if (F != 2048) return hipErrorInvalidValue;

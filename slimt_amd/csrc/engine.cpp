@@ -1064,6 +1064,20 @@ extern "C" int slimt_hip_debug_tied_output_proof(const int8_t *wemb, size_t rows
   return 0;
 }
 
+// The fused decoder's dynamic LDS as its launcher asks for it (kernels.h, fused_decode_launch_lds_bytes) for a shape, the
+// sentences per workgroup (32 / 16 / 8 / 4), a sentence-length class (mid), the cache form (tight) and what else picks the
+// instantiation (flags: bit 0 merged, 1 non-temporal cache loads, 2 scored, 3 forced, 4 sampled): host code, needs no device.
+extern "C" int slimt_hip_debug_fused_decode_lds_bytes(int D, int F, int Ld, int sentences_per_wg, int kv24, int mid, int tight,
+                                                      unsigned flags, size_t *bytes, int *ln_in_lds, int *epi_in_lds) {
+  if (!bytes || !ln_in_lds || !epi_in_lds) return fail(-1, "null argument");
+  bool ln = false, epi = false;
+  *bytes = fused_decode_launch_lds_bytes(D, F, Ld, sentences_per_wg, kv24 != 0, mid, tight != 0, (flags & 4u) != 0, (flags & 8u) != 0,
+                                         (flags & 16u) != 0, (flags & 1u) != 0, (flags & 2u) != 0, mid ? nullptr : &ln, &epi);
+  *ln_in_lds = ln ? 1 : 0;
+  *epi_in_lds = epi ? 1 : 0;
+  return 0;
+}
+
 extern "C" int slimt_hip_debug_kv_narrow_limit(slimt_hip_model *model, int limit) {
   if (!model) return fail(-1, "model is NULL");
   if (limit < 1 || limit > (1 << 19)) return fail(-1, "narrow-form limit %d not in 1..2^19 (20 bits hold [-2^19, 2^19))", limit);

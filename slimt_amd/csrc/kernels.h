@@ -479,6 +479,9 @@ struct FusedDecodeArgs {
   MergeOut sub[kMaxMerge];
   size_t out_stride_wp = 0, out_stride_cs = 0, out_stride_pb = 0;
   bool ln_in_lds = false;  // set by the launcher: the LayerNorm constants of all layers fit LDS beside the rest
+  // set by the launcher (the 8- and 4-sentence tilings at D = 256): the output layer's epilogue constants of the launch fit
+  // LDS as well and are copied there once (fused_decode_lds_bytes)
+  bool epi_in_lds = false;
   bool kv_nt = false;  // non-temporal K/V cache loads (d_head 32 / 64 shapes; see decode_fused.hip)
   // with kv_nt: which caches are still read temporally, in eighths of a layer: sentence b's cache of
   // layer l is kept iff 8 l + (b mod 8) < kv_temporal_eighths (8 = all of layer 0, 12 = layer 0 and
@@ -520,6 +523,59 @@ bool fused_decode_tight_rows32_supported(int D, int F, int H, int Ld);
 bool fused_decode_tight_mid_supported(int D, int F, int H, int Ld, int mid);
 bool fused_decode_long24_supported(int D, int F, int H, int Ld);
 int fused_decode_rows(int D, int F, int H, int Ld, int S, int B, int forced, bool kv24);
+// Dynamic LDS of decode_fused_kernel, in the order of its carve-up. rows: rows of the operand tiles (16 / 32); spw: sentences
+// per workgroup (16: a full tile; 8 / 4 at D = 256, the trimmed layout: f32 rows and SSRU cells for spw sentences plus
+// four rows that the accumulator lanes of the other MFMA rows share, attention scratch for spw sentences).
+// ln_in_lds (out, nullable): whether the LayerNorm constants of all layers (LN_LDS in the kernel: the
+// D = 256, 16-row, non-MID variants) still fit the 160 KiB; the returned size includes them then.
+// tight: the kernels with the 16-bit cache form inlined (KVI = 16) keep its column terms [Ld][K, V][D] behind everything else.
+// scores: the scored kernels (SC) keep one more [NW][rows] float array beside the arg-max's (red_s)
+// forced: the forced kernels (FP) one float (ycap) and one int (fcol_s) per row
+// sampled: the sampled kernels (SM) two more [NW][rows] float arrays (red_m, red_z) and two words per row (seed_s)
+// epi_in_lds (out, nullable): the trimmed layout only -- whether the output layer's epilogue constants of a launch (its
+// pair constants of up to kFusedEpiOutTiles column tiles) fit behind all that; included then.
+constexpr int kFusedEpiOutTiles = 256;
+constexpr size_t fused_decode_lds_bytes(int D, int F, int Ld, int rows, bool kv24 = false, int mid = 0,
+                                        bool *ln_in_lds = nullptr, bool tight = false, bool scores = false, bool forced = false,
+                                        bool sampled = false, int spw = 16, bool *epi_in_lds = nullptr) {
+  constexpr size_t NW = 16;  // waves per workgroup
+  // D * rows > 256 * 16: two f32 row buffers, SSRU cells in global memory (see the kernel)
+  const size_t R = (size_t)rows;
+  const bool trim = spw < 16 && rows == 16 && D == 256;
+  const size_t RF = trim ? (size_t)spw + 4 : R, PW = trim ? (size_t)spw : NW;
+  const bool lean = (size_t)D * R > 256 * 16;
+  const size_t cells = (lean || mid == 2) ? 0 : (size_t)Ld * RF * D * 4;
+  const size_t f32rows = (lean ? 2 : 3) * RF * (D + 4) * 4 + cells;
+  const size_t base = f32rows + 2 * R * (size_t)(D + 32) + R * (size_t)(F + 32) + 2 * NW * R * 4 + 64 +
+                      PW * (mid == 2 ? 1024 : mid == 1 ? 512 : 256) * 4 + (kv24 ? (size_t)Ld * (D == 512 ? 4 : 2) * D * 4 : 0) +
+                      (tight ? (size_t)Ld * (rows > 16 ? 1 : 2) * D * 4 : 0) +  // (32 sentences: the K centres only)
+                      (scores ? (size_t)NW * R * 4 : 0) +
+                      (forced ? 2 * R * 4 : 0) +  // (FP: ycap and fcol_s, 128 bytes at 16 rows)
+                      (sampled ? 2 * (size_t)NW * R * 4 + 2 * R * 4 : 0);
+  const size_t ln = (D == 256 && rows == 16 && !mid) ? (size_t)Ld * 6 * D * 4 : 0;
+  const bool fits = ln > 0 && base + ln <= 160 * 1024;
+  if (ln_in_lds) *ln_in_lds = fits;
+  const size_t with_ln = fits ? base + ln : base;
+  const size_t epi = trim ? (size_t)kFusedEpiOutTiles / 32 * NW * 256 : 0;
+  const bool epi_fits = epi > 0 && with_ln + epi <= 160 * 1024;
+  if (epi_in_lds) *epi_in_lds = epi_fits;
+  return epi_fits ? with_ln + epi : with_ln;
+}
+// which instantiations of the 8- and 4-sentence tilings have the trimmed layout (decode_fused_kernel, TRIM): the unmerged
+// D = 256 ones, except the 4-sentence tiling with non-temporal cache loads and the tight form inlined (it spilled more
+// registers with it) -- the kernel asks with its template parameters, the launcher with the launch's
+constexpr bool fused_decode_trimmed(bool merged, int ksd, int spw, bool nt, int mid, bool tight) {
+  return !merged && spw < 16 && ksd == 4 && !(nt && spw == 4 && mid == 0 && tight);
+}
+// ... and the size the launcher asks for: sentences_per_wg as fused_decode_rows gives it (32 / 16 / 8 / 4), merged / nt /
+// tight / scores / forced / sampled as they pick the instantiation
+constexpr size_t fused_decode_launch_lds_bytes(int D, int F, int Ld, int sentences_per_wg, bool kv24, int mid, bool tight,
+                                               bool scores, bool forced, bool sampled, bool merged, bool nt,
+                                               bool *ln_in_lds = nullptr, bool *epi_in_lds = nullptr) {
+  const int spw = fused_decode_trimmed(merged, D / 64, sentences_per_wg, nt, mid, tight) ? sentences_per_wg : 16;
+  return fused_decode_lds_bytes(D, F, Ld, sentences_per_wg <= 16 ? 16 : sentences_per_wg, kv24, mid, ln_in_lds, tight, scores,
+                                forced, sampled, spw, epi_in_lds);
+}
 hipError_t launch_decode_fused(const FusedDecodeArgs &a, int D, int F, int H, hipStream_t st);
 
 // ---- lexical shortlist generation (shortlist.hip) -------------------------------

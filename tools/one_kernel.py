@@ -15,7 +15,9 @@ while args:
 s = open(srcf).read()
 cut = s.rindex("template <", 0, s.index("static constexpr auto dfk()"))  # (everything from the kernel pickers on goes)
 s = s[:cut] + "template __global__ void decode_fused_kernel<%s>(FusedDecodeArgs);\n}  // namespace slimt_hip\n" % targs
-tmp = os.path.join(ROOT, "slimt_amd/csrc/_one_kernel.hip")
+import tempfile
+tmpdir = tempfile.mkdtemp(prefix="one_kernel_")  # (outside the source tree: the includes resolve through -I)
+tmp = os.path.join(tmpdir, "_one_kernel.hip")
 open(tmp, "w").write(s)
 try:
     env = dict(os.environ, SLIMT_HIPCC_EXTRA=" ".join(extra))
@@ -25,3 +27,4 @@ try:
                         tmp, "-I", os.path.join(ROOT, "slimt_amd/csrc"), "-I", os.path.join(ROOT, "include"), "-o", asm] + extra, stderr=subprocess.DEVNULL, check=True)
 finally:
     os.remove(tmp)
+    os.rmdir(tmpdir)
