@@ -832,6 +832,74 @@ int slimt_hip_consensus_select_device(slimt_hip_ctx *ctx, const uint32_t *d_ids,
  * given, max_order or beta2 out of range, a NULL array. An armed fan-out call whose Tmax exceeds SLIMT_HIP_CONSENSUS_MAX_T is refused with a message. */
 int slimt_hip_ctx_set_fanout_consensus(slimt_hip_ctx *ctx, int max_order, int beta2, uint32_t *best, double *utility);
 
+/* ---- beam search with n-best output ---------------------------------------- */
+/* slimt_hip_translate over B sources with `beam` = k slots per source, 1 <= k <= SLIMT_HIP_MAX_BEAM: a fan-out call of
+ * B k decoder rows (row r = b k + s belongs to source b) whose every step ends in one selection. THE CONTRACT, which a
+ * host checker reproduces bit for bit (slimt_amd/csrc/beam.h is host-compilable; every fused operation is an fmaf and
+ * nothing else is contracted):
+ * Arithmetic, for one decoder row with logits l_c over the output layer's N columns (the shortlist's, or the
+ * vocabulary's) as the logits GEMM forms them:
+ *   - the row is usable if no logit is NaN and its maximum M (-0 read as +0) is finite; an unusable row contributes no
+ *     candidate;
+ *   - weight bm_weight(l, M): 2^40 if l == M (tested first); else with d = l - M, 0 if d <= -28.0f; else
+ *     (uint64_t)((double)tr_exp(d) * 1099511627776.0) (tr_exp: truncation.h);
+ *   - Q is the sum of the row's weights as uint64 (exact in any order; below 2^60 for N < 2^20 -- an output layer of 2^20
+ *     columns or more is refused) and L = sm_log((float)((double)Q * 0x1p-40)) (sm_log: sampling.h);
+ *   - the column's score lp_c = (l_c - M) - L: two f32 subtractions, in this order.
+ *   tr_exp on (-28, 0] is normal and monotone with relative error 8.3e-8 against float64; on random rows of 1 to 32,000
+ *   columns lp is within 3.6e-6 of the float64 log-softmax where that is above -64 (tests/test_beam_checker.py measures
+ *   both and asserts the project's score tolerance 5e-5).
+ * Search. A slot is dead (flag 0), live (1) or finished (2) and carries a total C (f32). Before step 0, slot 0 is live
+ * with C = +0.0f and the other slots are dead. Candidates at step t: for every live slot s with a usable row and every
+ * column c, cand = C_s + lp_c (one f32 add), candidates equal to -inf dropped; for every finished slot, itself with
+ * cand = C_s unchanged. Candidates are ordered by cand descending, compared as floats (+0 equals -0); then slot
+ * ascending; then logit descending (as floats); then column ascending -- within one slot the arg-max's first-maximum
+ * rule continued, and cand is monotone in the logit, so beam 1 is greedy decoding. The first k candidates become the new
+ * slots 0..k-1 in that order, each with parent = the candidate's slot, token = the column's vocabulary id, token
+ * score = lp_c and C = cand. A new slot whose token is EOS is finished with length t + 1; a carried finished slot keeps
+ * its length and tokens; with fewer than k candidates the remaining slots are dead. A source is done when no slot is
+ * live; the call runs until every source is done, or for Tmax steps (Tmax follows slimt_hip_translate's rule); a slot
+ * still live at the end is reported with length Tmax and no EOS.
+ * Output, n-best with n = k per source: out_ids [B][k][Tmax], out_len [B][k] (0 for a dead slot), totals [B][k] (C; -inf
+ * for a dead slot), and the nullable token_scores [B][k][Tmax] and align [B][k][Tmax][S]. The k hypotheses are sorted by
+ * key descending, ties to the lower final slot, dead slots last; the key is totals (length_mode 0) or
+ * totals / (float)out_len (length_mode 1) -- the two modes of slimt_hip_candidates_rank; any other mode is refused.
+ * Alignment row t of a hypothesis is the row the decoder computed at step t for the slot that hypothesis was extended
+ * from (head 0 of the last layer over the source's lengths[b] keys). Entries at t >= out_len are not written by the
+ * search (host calls and _device zero out_ids, out_len and align first, as slimt_hip_translate does; a host call's
+ * token_scores come back 0 there). A source's result depends on the source, the output layer, k and the mode only: not
+ * on its place in the batch or on its neighbours.
+ * A beam call is a translate call: it consumes whatever is armed on the context, and is refused with a message if
+ * scores, a prefix, sampling, truncation or consensus are armed. It decodes with the per-stage kernels whatever the
+ * context's decode mode, like a fan-out call; K/V cache format 3 works. Bounds: B * beam <= max_batch (the per-row
+ * workspaces are sized by it), B * S within the context's padded tokens. Host calls check ids and lengths as
+ * slimt_hip_translate does; _async, _device (steps_hint as there: at most Tmax steps run) and _async_generated are as the
+ * fan-out call's. */
+#define SLIMT_HIP_MAX_BEAM 8
+int slimt_hip_translate_beam(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S, int beam,
+                             int length_mode, const uint32_t *shortlist, size_t n_shortlist, float limit_factor, uint32_t eos_id,
+                             uint32_t *out_ids, uint32_t *out_len, float *totals, float *token_scores, float *align);
+int slimt_hip_translate_beam_async(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                                   int beam, int length_mode, const uint32_t *shortlist, size_t n_shortlist, float limit_factor,
+                                   uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *totals, float *token_scores,
+                                   float *align);
+int slimt_hip_translate_beam_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids, const uint32_t *d_lengths, size_t B, size_t S,
+                                    int beam, int length_mode, const uint32_t *d_shortlist, size_t n_shortlist,
+                                    float limit_factor, uint32_t eos_id, uint32_t *d_out_ids, uint32_t *d_out_len,
+                                    float *d_totals, float *d_token_scores, float *d_align, int steps_hint);
+int slimt_hip_translate_beam_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *shortlist, const uint32_t *src_ids,
+                                             const uint32_t *lengths, size_t B, size_t S, int beam, int length_mode,
+                                             float limit_factor, uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len,
+                                             float *totals, float *token_scores, float *align);
+/* One selection of the search above over the caller's arrays: host pointers, stateless, waits. logits [B beam][N], ids [N]
+ * (NULL: the column is the id), totals_in / flags_in [B beam] (a live slot's total finite, a finished one's not NaN;
+ * the step-0 state is flags 1, 0, 0, ... and totals +0, -inf, -inf, ...). Writes, each [B beam]: parent (the slot within
+ * the source), token, token_score, totals_out, flags_out. A carried finished slot has token 0xFFFFFFFF and token score
+ * 0; a dead slot has parent and token 0xFFFFFFFF, token score 0, total -inf and flag 0. */
+int slimt_hip_beam_step(const float *logits, size_t B, int beam, size_t N, const uint32_t *ids, const float *totals_in,
+                        const uint32_t *flags_in, uint32_t eos_id, uint32_t *parent, uint32_t *token, float *token_score,
+                        float *totals_out, uint32_t *flags_out);
+
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, HIP events bracket every launch of kernel family `kernel_id`
  * on the ctx stream; slimt_hip_profile_read returns the number of launches

@@ -51,6 +51,8 @@ SYMBOLS = [
     "slimt_hip_translate_fanout", "slimt_hip_translate_fanout_async", "slimt_hip_translate_fanout_device",
     "slimt_hip_translate_fanout_async_generated",
     "slimt_hip_consensus_select", "slimt_hip_consensus_select_device", "slimt_hip_ctx_set_fanout_consensus",
+    "slimt_hip_translate_beam", "slimt_hip_translate_beam_async", "slimt_hip_translate_beam_device",
+    "slimt_hip_translate_beam_async_generated", "slimt_hip_beam_step",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -295,6 +297,11 @@ def lib():
     L.slimt_hip_consensus_select.argtypes = [vp, vp, vp, sz, sz, sz, i32, i32, vp, vp]
     L.slimt_hip_consensus_select_device.argtypes = [vp, vp, vp, vp, sz, sz, sz, i32, i32, vp, vp]
     L.slimt_hip_ctx_set_fanout_consensus.argtypes = [vp, i32, i32, vp, vp]
+    L.slimt_hip_translate_beam.argtypes = [vp, vp, vp, sz, sz, i32, i32, vp, sz, f32, u32, vp, vp, vp, vp, vp]
+    L.slimt_hip_translate_beam_async.argtypes = [vp, vp, vp, sz, sz, i32, i32, vp, sz, f32, u32, vp, vp, vp, vp, vp]
+    L.slimt_hip_translate_beam_device.argtypes = [vp, vp, vp, sz, sz, i32, i32, vp, sz, f32, u32, vp, vp, vp, vp, vp, i32]
+    L.slimt_hip_translate_beam_async_generated.argtypes = [vp, vp, vp, vp, sz, sz, i32, i32, f32, u32, vp, vp, vp, vp, vp]
+    L.slimt_hip_beam_step.argtypes = [vp, sz, i32, sz, vp, vp, vp, u32, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("slimt_hip_abi_version",):
@@ -329,6 +336,32 @@ def sample_truncated(logits, temperature: float = 1.0, top_k: int = 0, top_p: fl
     _chk(lib().slimt_hip_sample_truncated(_p(logits), M, N, _p(ids), float(temperature), int(top_k), float(top_p), _p(keys),
                                           _p(steps), _p(cols), _p(thr), _p(kept), _p(sc)))
     return cols, thr, kept, sc
+
+
+MAX_BEAM = 8  # SLIMT_HIP_MAX_BEAM
+BEAM_DEAD, BEAM_LIVE, BEAM_FINISHED = 0, 1, 2
+BEAM_NONE = 0xFFFFFFFF
+
+
+def beam_step(logits, totals, flags, beam: int, eos_id: int = 0, ids=None):
+    """slimt_hip_beam_step: one selection of the beam search over logits [B * beam, N] (float32), the slots' totals
+    [B * beam] float32 and flags [B * beam] uint32 (0 dead, 1 live, 2 finished). ids: the columns' vocabulary ids (uint32
+    [N]; None: the column). Returns (parent, token, token_score, totals, flags), each [B * beam]."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    totals = np.ascontiguousarray(totals, dtype=np.float32)
+    flags = np.ascontiguousarray(flags, dtype=np.uint32)
+    beam = int(beam)
+    if logits.ndim != 2 or beam < 1 or logits.shape[0] % beam or totals.shape != (logits.shape[0],) or flags.shape != totals.shape:
+        raise ValueError("beam_step: logits [B * beam, N], totals [B * beam] and flags [B * beam] expected")
+    R, N = logits.shape
+    ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32)
+    if ids is not None and ids.shape != (N,):
+        raise ValueError("beam_step: ids [N] expected")
+    parent, token, flags_out = np.zeros(R, np.uint32), np.zeros(R, np.uint32), np.zeros(R, np.uint32)
+    score, totals_out = np.zeros(R, np.float32), np.zeros(R, np.float32)
+    _chk(lib().slimt_hip_beam_step(_p(logits), R // beam, beam, N, _p(ids), _p(totals), _p(flags), int(eos_id), _p(parent),
+                                   _p(token), _p(score), _p(totals_out), _p(flags_out)))
+    return parent, token, score, totals_out, flags_out
 
 
 def candidates_rank(scores, tgt_len, cand_src, B: int, mean: bool = False, mode=None):
@@ -1064,6 +1097,116 @@ class Context:
                                                      vp(d_shortlist) if n_shortlist else None, n_shortlist, limit_factor,
                                                      eos_id, vp(d_out_ids), vp(d_out_len), vp(d_align) if d_align else None,
                                                      steps_hint))
+
+    # ---- beam search with n-best output (include/slimt_hip.h, slimt_hip_translate_beam*) ----
+    @staticmethod
+    def _beam_mode(mean, mode) -> int:
+        return int(mode) if mode is not None else (1 if mean else 0)
+
+    def translate_beam(self, ids, lengths, beam: int, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
+                       mean: bool = False, want_align: bool = False, want_scores: bool = True, mode=None):
+        """slimt_hip_translate_beam: beam search over the B sources ids [B,S] / lengths [B] with `beam` slots each. Returns
+        the n-best, best first: out_ids [B,beam,Tmax], out_len [B,beam] (0: a dead slot), totals [B,beam] (-inf: a dead
+        slot), token_scores [B,beam,Tmax] | None, align [B,beam,Tmax,S] | None. mean: order by totals / out_len."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        if ids.ndim != 2 or lengths.shape != (ids.shape[0],):
+            raise ValueError("translate_beam: ids [B, S] and lengths [B] expected")
+        B, S = ids.shape
+        k = int(beam)
+        T = max(int(np.float32(limit_factor) * np.float32(S)), 1)
+        kk = max(k, 0)
+        sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
+        out_ids = np.zeros((B, kk, T), dtype=np.uint32)
+        out_len = np.zeros((B, kk), dtype=np.uint32)
+        totals = np.zeros((B, kk), dtype=np.float32)
+        sc = np.zeros((B, kk, T), dtype=np.float32) if want_scores else None
+        align = np.zeros((B, kk, T, S), dtype=np.float32) if want_align else None
+        _chk(lib().slimt_hip_translate_beam(self.h, _p(ids), _p(lengths), B, S, k, self._beam_mode(mean, mode), _p(sl),
+                                            0 if sl is None else sl.size, limit_factor, eos_id, _p(out_ids), _p(out_len),
+                                            _p(totals), _p(sc), _p(align)))
+        return out_ids, out_len, totals, sc, align
+
+    def beam_buffers(self, B: int, S: int, beam: int, limit_factor: float = 1.5, want_align: bool = False):
+        """This context's pinned arrays for translate_beam_async: (ids [B,S], lengths [B], out_ids [B,beam,Tmax], out_len
+        [B,beam], totals [B,beam], token_scores [B,beam,Tmax], align [B,beam,Tmax,S] | None)."""
+        T = max(int(np.float32(limit_factor) * np.float32(S)), 1)
+        pin = lambda name: self._pinned.setdefault(name, _Pinned())
+        return (pin("bm_ids").array(np.uint32, (B, S)), pin("bm_len").array(np.uint32, (B,)),
+                pin("bm_out").array(np.uint32, (B, beam, T)), pin("bm_ol").array(np.uint32, (B, beam)),
+                pin("bm_tot").array(np.float32, (B, beam)), pin("bm_sc").array(np.float32, (B, beam, T)),
+                pin("bm_al").array(np.float32, (B, beam, T, S)) if want_align else None)
+
+    def translate_beam_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
+                             mean: bool = False, mode=None):
+        """slimt_hip_translate_beam_async[_generated] on (ids, lengths, out_ids, out_len, totals, token_scores | None,
+        align | None) host arrays (already filled; those of beam_buffers() are pinned); synchronize() before reading."""
+        ids, lengths, out_ids, out_len, totals, sc, align = bufs
+        for a in (ids, lengths, out_ids, out_len):
+            if a.dtype != np.uint32 or not a.flags.c_contiguous:
+                raise ValueError("translate_beam_async: C-contiguous uint32 arrays expected")
+        if ids.ndim != 2 or out_ids.ndim != 3:
+            raise ValueError("translate_beam_async: ids [B, S] and out_ids [B, beam, Tmax] expected")
+        (B, S), k = ids.shape, out_ids.shape[1]
+        T = max(int(np.float32(limit_factor) * np.float32(S)), 1)
+        if lengths.shape != (B,) or out_ids.shape != (B, k, T) or out_len.shape != (B, k):
+            raise ValueError("translate_beam_async: mismatched shapes")
+        for a, shape in ((totals, (B, k)), (sc, (B, k, T)), (align, (B, k, T, S))):
+            if a is None and shape != (B, k):
+                continue
+            if a is None or a.dtype != np.float32 or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError("translate_beam_async: a C-contiguous float32 array of shape %s expected" % (shape,))
+        m = self._beam_mode(mean, mode)
+        if generator is not None:
+            _chk(lib().slimt_hip_translate_beam_async_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, k, m,
+                                                                limit_factor, eos_id, _p(out_ids), _p(out_len), _p(totals),
+                                                                _p(sc), _p(align)))
+            return
+        sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
+        _chk(lib().slimt_hip_translate_beam_async(self.h, _p(ids), _p(lengths), B, S, k, m, _p(sl), 0 if sl is None else sl.size,
+                                                  limit_factor, eos_id, _p(out_ids), _p(out_len), _p(totals), _p(sc), _p(align)))
+
+    def translate_beam_pinned(self, ids, lengths, beam: int, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
+                              mean: bool = False, want_align: bool = False, generator=None, mode=None):
+        """translate_beam() through this context's pinned arrays and slimt_hip_translate_beam_async; returns copies."""
+        ids = np.asarray(ids)
+        B, S = ids.shape
+        bufs = self.beam_buffers(B, S, int(beam), limit_factor, want_align)
+        bufs[0][...] = ids
+        bufs[1][...] = lengths
+        for a in bufs[2:]:
+            if a is not None:
+                a[...] = 0
+        self.translate_beam_async(bufs, shortlist, generator, limit_factor, eos_id, mean, mode)
+        self.synchronize()
+        return tuple(None if a is None else a.copy() for a in bufs[2:])
+
+    def translate_beam_generated(self, generator, ids, lengths, beam: int, limit_factor: float = 1.5, eos_id: int = 0,
+                                 mean: bool = False, want_align: bool = False, mode=None):
+        """slimt_hip_translate_beam_async_generated on pageable arrays, waited for: the batch's lexical shortlist comes
+        from `generator`. Returns what translate_beam() returns."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        if ids.ndim != 2 or lengths.shape != (ids.shape[0],) or int(beam) < 0:
+            raise ValueError("translate_beam_generated: ids [B, S], lengths [B] and a beam >= 0 expected")
+        (B, S), k = ids.shape, int(beam)
+        T = max(int(np.float32(limit_factor) * np.float32(S)), 1)
+        bufs = (ids, lengths, np.zeros((B, k, T), np.uint32), np.zeros((B, k), np.uint32), np.zeros((B, k), np.float32),
+                np.zeros((B, k, T), np.float32), np.zeros((B, k, T, S), np.float32) if want_align else None)
+        self.translate_beam_async(bufs, None, generator, limit_factor, eos_id, mean, mode)
+        self.synchronize()
+        return bufs[2:]
+
+    def translate_beam_device(self, d_ids: int, d_lengths: int, B: int, S: int, beam: int, d_shortlist: int, n_shortlist: int,
+                              limit_factor: float, eos_id: int, d_out_ids: int, d_out_len: int, d_totals: int,
+                              d_token_scores: int = 0, d_align: int = 0, steps_hint: int = 0, mean: bool = False, mode=None):
+        """slimt_hip_translate_beam_device: device pointers (ints) in and out, like translate_fanout_device()."""
+        vp = C.c_void_p
+        _chk(lib().slimt_hip_translate_beam_device(self.h, vp(d_ids), vp(d_lengths), B, S, int(beam), self._beam_mode(mean, mode),
+                                                   vp(d_shortlist) if n_shortlist else None, n_shortlist, limit_factor, eos_id,
+                                                   vp(d_out_ids), vp(d_out_len), vp(d_totals),
+                                                   vp(d_token_scores) if d_token_scores else None,
+                                                   vp(d_align) if d_align else None, steps_hint))
 
     @staticmethod
     def _score_host(ids, lengths, tgt_ids, tgt_len):

@@ -4,6 +4,7 @@
 #include "sampling.h"
 #include "scores.h"
 #include "truncation.h"
+#include "beam.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1223,7 +1224,7 @@ void ctx_free(slimt_hip_ctx *c) {
                     &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->tr_logits, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag,
-                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage, &c->cs_stage};
+                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage, &c->cs_stage, &c->bm_state, &c->bm_slots, &c->bm_hist, &c->bm_align, &c->bm_stage};
   for (auto *b : bufs) b->release();
   free_affine(c->out_sl);
   if (c->n_finished_host) (void)hipHostFree(c->n_finished_host);
@@ -1744,6 +1745,24 @@ struct CallOptions {
     c->call.rows = (int)N;
     return 0;
   }
+  // A beam call (slimt_hip_translate_beam*): a fan-out call of B beam rows, source-major, row_src[r] = r / beam. It keeps
+  // its own token scores and selects by them: whatever else was armed is a refusal (and consumed, as always).
+  int open_beam(size_t B, int beam, int mode) {
+    if (!c) return 0;
+    const CallState &call = c->call;
+    if (call.scored) return fail(-1, "beam: scores are armed (slimt_hip_ctx_set_scores); a beam call returns its own token scores");
+    if (call.forced) return fail(-1, "beam: a target prefix is armed (slimt_hip_ctx_set_target_prefix); prefix-constrained beams are not supported");
+    if (call.sampled) return fail(-1, "beam: sampling is armed (slimt_hip_ctx_set_sampling); a beam call is not sampled");
+    if (B * (size_t)beam > c->max_B)
+      return fail(-1, "beam: %zu sources of beam %d exceed the context's max_batch %zu", B, beam, c->max_B);
+    if (B == 0) return fail(-1, "empty batch");
+    RCCHK(open_fanout(B * (size_t)beam));
+    c->call.beam = beam;
+    c->call.beam_mode = mode;
+    c->bm_row_src.resize(B * (size_t)beam);
+    for (size_t r = 0; r < c->bm_row_src.size(); ++r) c->bm_row_src[r] = (uint32_t)(r / (size_t)beam);
+    return 0;
+  }
 
  private:
   int take(const ArmedOptions &a, size_t n, bool fanout) {
@@ -2196,7 +2215,7 @@ int decoder_layers(slimt_hip_ctx *c, float *d_align, int Tmax, const uint32_t *d
     s.B = N; s.D = D;
     s.x = xin;
     s.wf = L.rnn_f.w; s.w = L.rnn_w.w;
-    s.state = c->state.as<float>() + (size_t)l * N * D;
+    s.state = (c->call.bm_state_cur ? c->call.bm_state_cur : c->state.as<float>()) + (size_t)l * N * D;  // (a beam call: the step's block)
     s.h_pre = c->dh.as<float>();
     {
       ProfScope p(c, SLIMT_HIP_K_SSRU, 2.0 * N * D * D, 2.0 * D * D);
@@ -2282,6 +2301,94 @@ int decoder_layers(slimt_hip_ctx *c, float *d_align, int Tmax, const uint32_t *d
       HIPCHK(launch_dgemm(f2, EPI_PLAIN, st));
     }
   }
+  return 0;
+}
+
+// The steps of a beam call (include/slimt_hip.h, slimt_hip_translate_beam*) behind translate_device's
+// encoder and decode_setup: R = B beam rows, source-major, whose sources call.row_src names. A step is decoder_layers with
+// the fan-out attention, the logits gemm with EPI_PLAIN into tr_logits, and ONE launch of beam_select.hip's kernel, which
+// also gathers the SSRU states by parent from the step's block into the other and embeds the next tokens. The attention
+// writes its alignment rows into a history [R][Tmax][S] at the rows' step word; the finish kernel behind the last step
+// orders the hypotheses and collects tokens, scores and alignment rows along the back-pointers.
+int beam_steps(slimt_hip_ctx *c, size_t B, size_t S, size_t Tmax, uint32_t eos_id, const uint32_t *d_shortlist, uint32_t *d_out_ids,
+               uint32_t *d_out_len, float *d_align, int steps_hint) {
+  const slimt_hip_model *m = c->model;
+  hipStream_t st = c->stream;
+  CallState &call = c->call;
+  const size_t k = (size_t)call.beam, R = B * k;
+  const AffineW &out = output_layer(c);
+  if (!call.fanout || (size_t)call.rows != R || !call.row_src || !call.bm_dev_totals) return fail(-1, "beam: not a beam call");
+  if ((uint32_t)out.w.N >= kBeamMaxN) return fail(-1, "beam: an output layer of %d columns (2^20 or more)", out.w.N);
+  const size_t T = std::min(Tmax, steps_hint > 0 ? (size_t)steps_hint : Tmax);
+  HIPCHK(c->tr_logits.reserve(R * (size_t)out.w.N * 4));
+  HIPCHK(c->bm_state.reserve((size_t)m->Ld * R * m->D * 4));
+  HIPCHK(c->bm_slots.reserve((4 * R + B) * 4));
+  HIPCHK(c->bm_hist.reserve(3 * T * R * 4));
+  if (d_align) HIPCHK(c->bm_align.reserve(R * Tmax * S * 4));
+  float *const totals = c->bm_slots.as<float>();
+  uint32_t *const flags = c->bm_slots.as<uint32_t>() + R, *const len = flags + R, *const step_word = len + R, *const done = step_word + R;
+  uint32_t *const h_parent = c->bm_hist.as<uint32_t>(), *const h_token = h_parent + T * R;
+  float *const h_score = reinterpret_cast<float *>(h_token + T * R);
+  float *const blocks[2] = {c->state.as<float>(), c->bm_state.as<float>()};
+  BeamSelectArgs sa;
+  sa.logits = c->tr_logits.as<float>();
+  sa.B = (int)B; sa.k = (int)k; sa.N = out.w.N;
+  sa.ids = d_shortlist;
+  sa.eos = eos_id;
+  sa.totals_in = sa.totals_out = totals;
+  sa.flags_in = sa.flags_out = flags;
+  sa.len_in = sa.len_out = len;
+  sa.step_word = step_word;
+  sa.Ld = m->Ld;
+  sa.emb = embed_args(c);
+  sa.dx = c->dx.as<float>();
+  sa.done = done;
+  sa.n_finished = c->n_finished.as<int>();
+  {
+    BeamSelectArgs ia = sa;  // the start state: slot 0 live at +0, the zero embedding (decode_setup zeroed block 0's states)
+    ia.init = 1;
+    const hipError_t he = launch_beam_select(ia, st);
+    if (he != hipSuccess) return fail((int)he, "beam start: %s", hipGetErrorString(he));
+  }
+  size_t t = 0;
+  for (; t < T; ++t) {
+    if (steps_hint <= 0 && t > 0 && (t % 8) == 0) {  // stop as soon as every source is done
+      HIPCHK(hipMemcpyAsync(c->n_finished_host, c->n_finished.p, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (*c->n_finished_host >= (int)B) break;
+    }
+    call.bm_state_cur = blocks[t & 1];
+    RCCHK(decoder_layers(c, d_align ? c->bm_align.as<float>() : nullptr, (int)Tmax, step_word, nullptr));
+    DGemmArgs g;
+    g.B = (int)R;
+    g.D = m->D;
+    g.a = decoder_out_rows(c);
+    g.w = out.w;
+    g.y = c->tr_logits.as<float>();
+    g.ldy = out.w.N;
+    {
+      ProfScope p(c, SLIMT_HIP_K_LOGITS, gemm_macs((int)R, out.w), gemm_bytes(out.w));
+      HIPCHK(launch_dgemm(g, EPI_PLAIN, st));
+    }
+    sa.t = (int)t;
+    sa.parent = h_parent + t * R;
+    sa.token = h_token + t * R;
+    sa.token_score = h_score + t * R;
+    sa.state_src = blocks[t & 1];
+    sa.state_dst = blocks[(t + 1) & 1];
+    const hipError_t he = launch_beam_select(sa, st);
+    if (he != hipSuccess) return fail((int)he, "beam selection: %s", hipGetErrorString(he));
+  }
+  BeamFinishArgs fa;
+  fa.B = (int)B; fa.k = (int)k; fa.T = (int)t; fa.Tmax = (int)Tmax; fa.S = (int)S; fa.mode = call.beam_mode;
+  fa.parent = h_parent; fa.token = h_token; fa.token_score = h_score;
+  fa.totals = totals; fa.flags = flags; fa.len = len;
+  fa.align_hist = d_align ? c->bm_align.as<float>() : nullptr;
+  fa.lengths = c->lengths.as<uint32_t>();
+  fa.out_ids = d_out_ids; fa.out_len = d_out_len;
+  fa.out_totals = call.bm_dev_totals; fa.out_scores = call.bm_dev_scores; fa.out_align = d_align;
+  const hipError_t he = launch_beam_finish(fa, st);
+  if (he != hipSuccess) return fail((int)he, "beam finish: %s", hipGetErrorString(he));
   return 0;
 }
 
@@ -2742,6 +2849,7 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     c->ticket_base += tickets;
     return 0;
   }
+  if (call.beam) return beam_steps(c, B, S, Tmax, eos_id, ds.shortlist, d_out_ids, d_out_len, d_align, steps_hint);
   // a truncated call stores each step's logits and selects over them: one partial per row (sample_truncate.hip)
   const bool truncated = sampled && call.truncated;
   if (call.truncated && !truncated) return fail(-1, "sampling truncation: the call is not sampled");
@@ -3037,6 +3145,12 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const BatchOpti
     call.cs_dev_util = ctx->cs_stage.as<double>();
     call.cs_dev_best = reinterpret_cast<uint32_t *>(ctx->cs_stage.as<char>() + R * 8);
   }
+  if (call.beam) {  // (a beam call: totals [R], then token scores [R][Tmax] where asked for, staged on the device)
+    HIPCHK(ctx->bm_stage.reserve(R * 4 + (call.bm_scores ? R * Tmax * 4 : 0)));
+    call.bm_dev_totals = ctx->bm_stage.as<float>();
+    call.bm_dev_scores = call.bm_scores ? ctx->bm_stage.as<float>() + R : nullptr;
+    if (call.bm_scores) HIPCHK(hipMemsetAsync(call.bm_dev_scores, 0, R * Tmax * 4, st));
+  }
   float *const scores = user.scores;  // (a scored call: the caller's [B][Tmax] host array)
   if (!wait && persistent) {
     void *v_ids = host_device_view(src_ids), *v_len = host_device_view(lengths), *v_out = host_device_view(out_ids),
@@ -3072,6 +3186,10 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const BatchOpti
   if (call.consensus) {
     HIPCHK(hipMemcpyAsync(call.cs_util, call.cs_dev_util, R * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(call.cs_best, call.cs_dev_best, B * 4, hipMemcpyDeviceToHost, st));
+  }
+  if (call.beam) {
+    HIPCHK(hipMemcpyAsync(call.bm_totals, call.bm_dev_totals, R * 4, hipMemcpyDeviceToHost, st));
+    if (call.bm_scores) HIPCHK(hipMemcpyAsync(call.bm_scores, call.bm_dev_scores, R * Tmax * 4, hipMemcpyDeviceToHost, st));
   }
   if (wait) RCCHK(slimt_hip_ctx_synchronize(ctx));  // sleeps on a blocking-sync event (a worker per context: no spinning)
   return 0;
@@ -3164,6 +3282,131 @@ extern "C" int slimt_hip_translate_fanout_device(slimt_hip_ctx *ctx, const uint3
   options_in_place(ctx, opt.user[0]);  // (scores [N][Tmax], prefix and keys by row)
   return translate_device(ctx, d_src_ids, d_lengths, d_shortlist, B, S, n_shortlist, limit_factor, eos_id, d_out_ids, d_out_len,
                           d_align, steps_hint);
+}
+
+// ---- beam search with n-best output (include/slimt_hip.h, slimt_hip_translate_beam*) --------------------
+// A fan-out call of B beam rows whose steps end in beam_select.hip's selection (beam_steps above); the outputs count
+// [B][beam] hypotheses, best first.
+namespace {
+int beam_arguments(int beam, int length_mode) {
+  if (beam < 1 || beam > SLIMT_HIP_MAX_BEAM) return fail(-1, "beam: a beam of %d is not in 1..%d", beam, SLIMT_HIP_MAX_BEAM);
+  if (length_mode != 0 && length_mode != 1) return fail(-1, "beam: length_mode %d is not 0 (sum) or 1 (mean per token)", length_mode);
+  return 0;
+}
+
+int translate_beam_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
+                        size_t S, int beam, int length_mode, const uint32_t *shortlist, size_t n_shortlist, float limit_factor,
+                        uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *totals, float *token_scores, float *align,
+                        bool wait) {
+  CallOptions opt(ctx, 1);
+  // (what needs no context is checked first: these refusals say what is wrong with the arguments, context or not)
+  RCCHK(beam_arguments(beam, length_mode));
+  if (!ctx || !totals) return fail(-1, "null argument");
+  RCCHK(opt.rc);
+  RCCHK(opt.open_beam(B, beam, length_mode));
+  ctx->call.bm_totals = totals;
+  ctx->call.bm_scores = token_scores;
+  return translate_host(ctx, gen, opt.user[0], src_ids, lengths, B, S, shortlist, n_shortlist, limit_factor, eos_id, out_ids,
+                        out_len, align, wait, ctx->bm_row_src.data());
+}
+}  // namespace
+
+extern "C" int slimt_hip_translate_beam(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B, size_t S,
+                                        int beam, int length_mode, const uint32_t *shortlist, size_t n_shortlist,
+                                        float limit_factor, uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *totals,
+                                        float *token_scores, float *align) {
+  return translate_beam_host(ctx, nullptr, src_ids, lengths, B, S, beam, length_mode, shortlist, n_shortlist, limit_factor, eos_id,
+                             out_ids, out_len, totals, token_scores, align, true);
+}
+
+extern "C" int slimt_hip_translate_beam_async(slimt_hip_ctx *ctx, const uint32_t *src_ids, const uint32_t *lengths, size_t B,
+                                              size_t S, int beam, int length_mode, const uint32_t *shortlist, size_t n_shortlist,
+                                              float limit_factor, uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len,
+                                              float *totals, float *token_scores, float *align) {
+  return translate_beam_host(ctx, nullptr, src_ids, lengths, B, S, beam, length_mode, shortlist, n_shortlist, limit_factor, eos_id,
+                             out_ids, out_len, totals, token_scores, align, false);
+}
+
+extern "C" int slimt_hip_translate_beam_async_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *shortlist, const uint32_t *src_ids,
+                                                        const uint32_t *lengths, size_t B, size_t S, int beam, int length_mode,
+                                                        float limit_factor, uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len,
+                                                        float *totals, float *token_scores, float *align) {
+  if (!shortlist) return fail(-1, "null argument");
+  return translate_beam_host(ctx, shortlist, src_ids, lengths, B, S, beam, length_mode, nullptr, 0, limit_factor, eos_id, out_ids,
+                             out_len, totals, token_scores, align, false);
+}
+
+extern "C" int slimt_hip_translate_beam_device(slimt_hip_ctx *ctx, const uint32_t *d_src_ids, const uint32_t *d_lengths, size_t B,
+                                               size_t S, int beam, int length_mode, const uint32_t *d_shortlist, size_t n_shortlist,
+                                               float limit_factor, uint32_t eos_id, uint32_t *d_out_ids, uint32_t *d_out_len,
+                                               float *d_totals, float *d_token_scores, float *d_align, int steps_hint) {
+  CallOptions opt(ctx, 1);
+  RCCHK(beam_arguments(beam, length_mode));
+  if (!ctx || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len || !d_totals) return fail(-1, "null argument");
+  RCCHK(opt.rc);
+  RCCHK(opt.open_beam(B, beam, length_mode));
+  RCCHK(check_batch(ctx, B, S));
+  if (n_shortlist > (size_t)ctx->model->V) return fail(-1, "shortlist larger than the vocabulary");
+  if (n_shortlist && !d_shortlist) return fail(-1, "shortlist is NULL");
+  HIPCHK(hipSetDevice(ctx->model->device));
+  const size_t R = B * (size_t)beam;
+  HIPCHK(ctx->fo_stage.reserve(R * 4));  // (the rows' sources, written once)
+  HIPCHK(hipMemcpyAsync(ctx->fo_stage.p, ctx->bm_row_src.data(), R * 4, hipMemcpyHostToDevice, ctx->stream));
+  ctx->call.row_src = ctx->fo_stage.as<uint32_t>();
+  ctx->call.bm_dev_totals = d_totals;
+  ctx->call.bm_dev_scores = d_token_scores;
+  return translate_device(ctx, d_src_ids, d_lengths, d_shortlist, B, S, n_shortlist, limit_factor, eos_id, d_out_ids, d_out_len,
+                          d_align, steps_hint);
+}
+
+// One selection over the caller's arrays: host pointers, stateless, waits (like slimt_hip_sample_truncated).
+extern "C" int slimt_hip_beam_step(const float *logits, size_t B, int beam, size_t N, const uint32_t *ids, const float *totals_in,
+                                   const uint32_t *flags_in, uint32_t eos_id, uint32_t *parent, uint32_t *token, float *token_score,
+                                   float *totals_out, uint32_t *flags_out) {
+  RCCHK(beam_arguments(beam, 0));
+  if (!logits || !totals_in || !flags_in || !parent || !token || !token_score || !totals_out || !flags_out || !B || !N)
+    return fail(-1, "bad argument");
+  if (N >= (size_t)slimt_hip::kBeamMaxN) return fail(-1, "beam: an output layer of %zu columns (2^20 or more)", N);
+  const size_t R = B * (size_t)beam;
+  if (B > 0x7fffffffu / (size_t)beam) return fail(-1, "beam_step: more than %d rows", 0x7fffffff);
+  for (size_t r = 0; r < R; ++r) {
+    if (flags_in[r] > slimt_hip::kBeamFinished) return fail(-1, "beam_step: flag %u of row %zu is not 0 (dead), 1 (live) or 2 (finished)", flags_in[r], r);
+    if (flags_in[r] == slimt_hip::kBeamLive && !std::isfinite(totals_in[r])) return fail(-1, "beam_step: the total of live row %zu is not finite", r);
+    if (flags_in[r] == slimt_hip::kBeamFinished && totals_in[r] != totals_in[r]) return fail(-1, "beam_step: the total of finished row %zu is NaN", r);
+  }
+  Tmp3 t;
+  hipStream_t st = nullptr;
+  HIPCHK(t.a.reserve(R * N * 4));
+  HIPCHK(t.b.reserve(N * 4));
+  HIPCHK(t.c.reserve(2 * R * 4));
+  HIPCHK(t.d.reserve(5 * R * 4));
+  HIPCHK(hipMemcpyAsync(t.a.p, logits, R * N * 4, hipMemcpyHostToDevice, st));
+  if (ids) HIPCHK(hipMemcpyAsync(t.b.p, ids, N * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.p, totals_in, R * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.as<char>() + R * 4, flags_in, R * 4, hipMemcpyHostToDevice, st));
+  BeamSelectArgs a;
+  a.logits = t.a.as<float>();
+  a.B = (int)B;
+  a.k = beam;
+  a.N = (int)N;
+  a.ids = ids ? t.b.as<uint32_t>() : nullptr;
+  a.eos = eos_id;
+  a.totals_in = t.c.as<float>();
+  a.flags_in = t.c.as<uint32_t>() + R;
+  uint32_t *o = t.d.as<uint32_t>();
+  a.parent = o;
+  a.token = o + R;
+  a.token_score = reinterpret_cast<float *>(o + 2 * R);
+  a.totals_out = reinterpret_cast<float *>(o + 3 * R);
+  a.flags_out = o + 4 * R;
+  HIPCHK(launch_beam_select(a, st));
+  HIPCHK(hipMemcpyAsync(parent, o, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(token, o + R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(token_score, o + 2 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(totals_out, o + 3 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(flags_out, o + 4 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
 }
 
 // ---- several batches in one launch pair (include/slimt_hip.h, slimt_hip_translate_many*) ----------------------------

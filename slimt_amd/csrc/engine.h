@@ -91,6 +91,12 @@ struct CallState {
   const uint32_t *row_src = nullptr;  // ... [rows] as the kernels read it (device memory)
   uint32_t *cs_best = nullptr, *cs_dev_best = nullptr;  // consensus: best [B] and utility [rows] as the caller gave
   double *cs_util = nullptr, *cs_dev_util = nullptr;    // them, and as the kernel writes them (the caller's, or cs_stage)
+  // a beam call (slimt_hip_translate_beam*): a fan-out call of B beam rows, row_src[r] = r / beam, whose steps end in
+  // beam_select.hip's selection; totals [B][beam] and token scores [B][beam][Tmax] (nullable) as the caller gave them and
+  // as the finish kernel writes them (the caller's, or bm_stage)
+  int beam = 0, beam_mode = 0;
+  float *bm_totals = nullptr, *bm_scores = nullptr, *bm_dev_totals = nullptr, *bm_dev_scores = nullptr;
+  float *bm_state_cur = nullptr;  // ... and the SSRU state block [Ld][rows][D] of the step in progress
   BatchOptions dev;  // the current unmerged batch's options as the kernels address them (a merged launch: MergePlan::opt)
 };
 
@@ -247,6 +253,11 @@ struct slimt_hip_ctx {
   slimt_hip::DevBuf tr_logits;           // truncation: [B][N] f32, the step's logits, reserved by the first truncated call
   slimt_hip::DevBuf fo_stage;            // fan-out: device staging of a host call's row_src
   slimt_hip::DevBuf cs_stage;            // consensus: device staging of a host call's utility [N] f64 + best [B] u32
+  // beam search, reserved by the first beam call: the second SSRU state block (the steps gather from one into the other),
+  // the slots' totals / flags / lengths / step words and the sources' done words, the steps' records [Tmax][rows] x 3, the
+  // decoder's alignment rows [rows][Tmax][S], device staging of a host call's totals and token scores; the rows' sources
+  slimt_hip::DevBuf bm_state, bm_slots, bm_hist, bm_align, bm_stage;
+  std::vector<uint32_t> bm_row_src;
   slimt_hip::DevBuf prev, out_ids, out_len, finished, n_finished, align;
   slimt_hip::DevBuf shortlist;
   slimt_hip::DevBuf sl_scratch;  // bitmaps of slimt_hip_shortlist_generate_device (kept zeroed)

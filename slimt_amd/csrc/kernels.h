@@ -835,6 +835,56 @@ struct SampleTruncArgs {
 constexpr int kSampleTruncMaxN = 0x7fffffff - 256;  // the column loops step an int by the workgroup's 256 threads
 hipError_t launch_sample_truncated(const SampleTruncArgs &a, hipStream_t st);
 
+// ---- beam search: one selection per step over stored logits, and the back-pointer walk (beam_select.hip) ----------------
+// One step of B sources with k slots each (rows r = b k + s, source-major) whose logits [B k][N] are in memory: the
+// selection of include/slimt_hip.h (slimt_hip_beam_step; beam.h). One workgroup per source reads its slots' totals, flags
+// and lengths (the *_in arrays), then writes the new slots (the *_out arrays, which may be the same memory) and the
+// step's parent / token / score records. The rest is the engine's and nullable as a whole (state_dst == nullptr): the
+// rows' step word, the k SSRU states of every decoder layer gathered by parent from one block into another, the next
+// token's embedding of every row (embed1's expression, position 0) and the count of sources that became done.
+// init: nothing is selected; the start state of every source (slot 0 live with total +0, the others dead with -inf, the
+// zero embedding, step word 0, done 0) is written instead.
+struct BeamSelectArgs {
+  const float *logits = nullptr;  // [B k][N]
+  int B = 0, k = 0, N = 0;
+  const uint32_t *ids = nullptr;  // [N] the columns' vocabulary ids (nullptr: the column)
+  uint32_t eos = 0;
+  int t = 0;     // the step: a slot that ends here has length t + 1
+  int init = 0;
+  const float *totals_in = nullptr;
+  const uint32_t *flags_in = nullptr, *len_in = nullptr;  // (len_in / len_out: both or neither)
+  float *totals_out = nullptr;
+  uint32_t *flags_out = nullptr, *len_out = nullptr;
+  uint32_t *parent = nullptr, *token = nullptr;  // [B k] this step's records
+  float *token_score = nullptr;
+  uint32_t *step_word = nullptr;  // [B k] <- t + 1
+  const float *state_src = nullptr;  // [Ld][B k][D]
+  float *state_dst = nullptr;
+  int Ld = 0;
+  EmbedArgs emb;
+  float *dx = nullptr;            // [B k][D]
+  uint32_t *done = nullptr;       // [B]
+  int *n_finished = nullptr;      // [1]
+};
+hipError_t launch_beam_select(const BeamSelectArgs &a, hipStream_t st);
+
+// The end of a beam call: per source, the k slots ordered by the final key (mode 0: the total, 1: the total over the
+// length; ties to the lower slot, dead slots last) and each one's tokens, scores and alignment rows collected along its
+// back-pointers through the T steps' records [T][B k]. Entries at t >= out_len are not written.
+struct BeamFinishArgs {
+  int B = 0, k = 0, T = 0, Tmax = 0, S = 0, mode = 0;
+  const uint32_t *parent = nullptr, *token = nullptr;  // [T][B k]
+  const float *token_score = nullptr;
+  const float *totals = nullptr;                       // [B k] the final slots
+  const uint32_t *flags = nullptr, *len = nullptr;
+  const float *align_hist = nullptr;   // nullable [B k][Tmax][S]: row (r, t) as the decoder computed it at step t for row r
+  const uint32_t *lengths = nullptr;   // [B] the sources' lengths
+  uint32_t *out_ids = nullptr, *out_len = nullptr;  // [B][k][Tmax], [B][k]
+  float *out_totals = nullptr;                       // [B][k]
+  float *out_scores = nullptr, *out_align = nullptr;  // nullable [B][k][Tmax], [B][k][Tmax][S]
+};
+hipError_t launch_beam_finish(const BeamFinishArgs &a, hipStream_t st);
+
 // the column means (rounded) of an f32 K/V cache [Ld][K, V][B * S][D]: centre[(2 l + p) * D + d] (FusedDecodeArgs::kv_centre)
 hipError_t launch_kv_centres(const float *kv, int Ld, int B, int S, int D, unsigned long long *sums, int *centre, hipStream_t st);
 

@@ -81,11 +81,16 @@ class Response:  # Response.hh: source / target with sentence + token ranges, so
     # its index j among them; empty otherwise
     utility: List[float] = field(default_factory=list)
     sample_index: List[int] = field(default_factory=list)
+    # beam_search(): the k alternatives of this text, each a Response of its own (alternative j holds the rank-j hypothesis
+    # of every sentence, with scores); this Response is rank 0. hypothesis_scores: per sentence, the hypothesis' total
+    # log-probability as the engine returned it (-inf where a sentence has fewer than j + 1 hypotheses). Empty otherwise
+    nbest: List["Response"] = field(default_factory=list)
+    hypothesis_scores: List[float] = field(default_factory=list)
 
     def to(self, encoding: Encoding) -> None:
         self.source.to(encoding)
         self.target.to(encoding)
-        for r in self.samples:
+        for r in self.samples + self.nbest:
             if r is not self:
                 r.to(encoding)
 
@@ -207,6 +212,7 @@ class Service:
         self.limit_factor = tgt_length_limit_factor
         self.pipeline_documents = 256  # translate(): documents per pipelined chunk (one chunk: no pipeline)
         self._engines = {}  # model id -> capi.BatchService (host/Service over its C ABI)
+        self._beam_contexts = {}  # model id -> capi.Context (beam_search)
         self._lock = threading.Lock()
 
     # -- batching ---------------------------------------------------------------------------------
@@ -576,6 +582,69 @@ class Service:
             resp.to(encoding)
         return out
 
+    def beam_search(self, model: Model, texts: Sequence[str], beam: int, mean: bool = False,
+                    encoding: Encoding = Encoding.UTF8) -> List[Response]:
+        """Beam search with n-best output (include/slimt_hip.h, slimt_hip_translate_beam): every sentence is decoded with
+        `beam` = k slots (1..capi.MAX_BEAM) from one encoding of it and comes back as its k best hypotheses, ordered by their
+        summed log-probability (mean=True: per token). Each Response carries `nbest`, its k alternatives as Responses
+        (alternative j holds the rank-j hypothesis of every sentence, always with scores; a sentence with fewer
+        hypotheses has an empty one there), and `hypothesis_scores`, the engine's total per sentence; the Response returned
+        is rank 0. Batches follow _batches' rule with at most max_words / beam sentences per call; the calls go through one
+        capi.Context per model on model.engine, under the Service's lock, with the model's lexical shortlist generated per
+        batch where it has one. A segment above ENGINE_LIMIT tokens is refused."""
+        k = int(beam)
+        if k < 1 or k > capi.MAX_BEAM:
+            raise ValueError(f"beam_search: a beam of 1..{capi.MAX_BEAM} expected, not {beam}")
+        processed = model.processor.process_many(texts, self.wrap_length, self.workers)
+        per_request = [segs for _, segs in processed]
+        units = [_Unit(r, i, list(seg)) for r, segs in enumerate(per_request) for i, seg in enumerate(segs)]
+        if any(len(u.words) > self.ENGINE_LIMIT for u in units):
+            raise ValueError(f"beam_search: a segment has more than {self.ENGINE_LIMIT} tokens")
+        eos = model.vocabulary.eos_id()
+        ranked = [[[None] * len(segs) for segs in per_request] for _ in range(k)]
+        totals_of = [[[0.0] * len(segs) for segs in per_request] for _ in range(k)]
+        per_call = max(1, self.max_words // k)
+        batches, cur = [], []
+        for u in sorted(units, key=lambda u: (len(u.words), u.request, u.index)):  # (_batches' walk, the rows bounded too)
+            if cur and ((len(cur) + 1) * len(u.words) > self.max_words or len(cur) + 1 > per_call):
+                batches.append(cur)
+                cur = []
+            cur.append(u)
+        if cur:
+            batches.append(cur)
+        with self._lock:
+            ctx = self._beam_contexts.get(model.id)
+            if ctx is None and batches:
+                rows = max(self.max_words, capi.MAX_BEAM)
+                ctx = capi.Context(model.engine, rows, self.ENGINE_LIMIT, max_tokens=max(self.max_words, self.ENGINE_LIMIT))
+                self._beam_contexts[model.id] = ctx
+            for batch in batches:
+                B, S = len(batch), max(len(u.words) for u in batch)
+                ids, lens = np.zeros((B, S), np.uint32), np.zeros(B, np.uint32)
+                for b, u in enumerate(batch):
+                    ids[b, :len(u.words)] = u.words
+                    lens[b] = len(u.words)
+                if model.shortlist_generator is not None:
+                    out, ln, tot, sc, al = ctx.translate_beam_generated(model.shortlist_generator, ids, lens, k, self.limit_factor,
+                                                                        eos, mean, want_align=True)
+                else:
+                    out, ln, tot, sc, al = ctx.translate_beam(ids, lens, k, None, self.limit_factor, eos, mean, want_align=True)
+                for b, u in enumerate(batch):
+                    for j in range(k):
+                        n, L = int(ln[b, j]), int(lens[b])
+                        ranked[j][u.request][u.index] = (out[b, j, :n].tolist(), al[b, j, :n, :L].copy(), sc[b, j, :n].copy())
+                        totals_of[j][u.request][u.index] = float(tot[b, j])
+        sources = [src for src, _ in processed]
+        alts = [self._respond_many(model, sources, h) for h in ranked]
+        out = alts[0]
+        for j, alt in enumerate(alts):
+            for r, resp in enumerate(alt):
+                resp.hypothesis_scores = totals_of[j][r]
+        for r, resp in enumerate(out):
+            resp.nbest = [a[r] for a in alts]
+            resp.to(encoding)
+        return out
+
     def pivot(self, first: Model, second: Model, texts: Sequence[str], html: bool = False,
               scores: bool = False, sampling=None, truncation=None) -> List[Response]:
         """sampling: (temperature, seed) -- both hops sample, the first under seed and the second under seed + 1;
@@ -596,6 +665,9 @@ class Service:
         for eng in self._engines.values():
             eng.close()
         self._engines.clear()
+        for ctx in self._beam_contexts.values():
+            ctx.close()
+        self._beam_contexts.clear()
 
 
 # -------------------------------------------------------------------------------------------------
