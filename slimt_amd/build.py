@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("SLIMT_HIP_LIB") or os.path.join(LIB_DIR, "libslimt_hi
 
 SOURCES = ["kernels.hip", "gemm_tile.hip", "decode_kernels.hip", "decode_fused.hip", "encode_fused.hip", "encode_wide.hip", "encode_tall.hip", "shortlist.hip", "score_tall.hip", "score_alternatives.hip", "score_candidates.hip", "decode_fanout.hip", "consensus.hip", "sample_truncate.hip", "beam_select.hip",
            "engine.cpp"]
-HEADERS = ["kernels.h", "engine.h", "decoder_plan.h", "device_common.h", "scores.h", "sampling.h", "truncation.h", "beam.h", "shortlist_device.h", "decode_attention_packed.inl.h", "decode_rows.h",
+HEADERS = ["kernels.h", "engine.h", "launch_choice.h", "decoder_plan.h", "device_common.h", "scores.h", "sampling.h", "truncation.h", "beam.h", "shortlist_device.h", "decode_attention_packed.inl.h", "decode_rows.h",
            os.path.join(ROOT, "include", "slimt_hip.h")]
 
 # -ffp-contract=off: the float epilogues are written operation by operation

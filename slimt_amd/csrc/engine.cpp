@@ -5,6 +5,7 @@
 #include "scores.h"
 #include "truncation.h"
 #include "beam.h"
+#include "launch_choice.h"
 
 #include <algorithm>
 #include <atomic>
@@ -51,6 +52,52 @@ static std::atomic<bool> g_hip_called{false};
     if (rc_) return rc_;   \
   } while (0)
 
+// ---------------------------------------------------------------------------
+// environment knobs
+// ---------------------------------------------------------------------------
+// Every SLIMT_* variable the engine reads, read once, when env() is first called. (GPU_MAX_HW_QUEUES is not one of them: it
+// is the runtime's, read by slimt_hip_hw_queues alone.) DESIGN.md has the table.
+struct EnvKnobs {
+  bool kv_watch = true;             // SLIMT_KV_WATCH=0: format 0's watches never switch a form off (measurements of the fallbacks)
+  bool kv_tight = true;             // SLIMT_KV_TIGHT=0: the tight (16-bit) K/V form is never tried
+  bool host_timing = false;         // SLIMT_HOST_TIMING set: where a translate call's host time goes, printed at model destroy
+  bool submit_lock = true;          // SLIMT_SUBMIT_LOCK=0: persistent translates are queued without the model's submit lock
+  bool kv_store_nt = false;         // SLIMT_KV_STORE_NT=1: encoders write a cache non-temporally when its decoder will stream it
+  double rows_oversub = 1.0;        // SLIMT_ROWS_OVERSUB: decoder workgroups in flight the plan allows, as a multiple of the budget
+  double kv_budget = 300e6;         // SLIMT_KV_BUDGET_MB: K/V bytes in flight that stay temporal (per-layer rule)
+  int kv_grain = 8;                 // SLIMT_KV_GRAIN: ... in steps of this many eighths of a layer's caches (at least 1)
+  int kv_by_launch = -1;            // SLIMT_KV_BY_LAUNCH: 0 = the per-layer rule only, 1..8 = keep that many launches of every 8
+  double kv_launch_budget = 300e6;  // SLIMT_KV_LAUNCH_BUDGET_MB: K/V bytes in flight the by-launch rule keeps temporal
+  bool shortlist_fold = true;       // SLIMT_SHORTLIST_FOLD=0: a generated shortlist is a launch of its own, not inside the encoder's
+  bool merge_dense = true;          // SLIMT_MERGE_DENSE=0: sub-batches that share an output layer are still tile-aligned (A/B)
+  bool idle_streams = true;         // SLIMT_IDLE_STREAMS=0: no idle streams level the hardware queues before the first context
+  bool quiet = false;               // SLIMT_HIP_QUIET=1: the warning about too many contexts on a device is not printed
+};
+
+static const EnvKnobs &env() {
+  static const EnvKnobs knobs = [] {
+    EnvKnobs k;
+    auto is = [](const char *name, char c) { return std::getenv(name) && std::getenv(name)[0] == c; };
+    auto real = [](const char *name, double otherwise) { return std::getenv(name) ? std::atof(std::getenv(name)) : otherwise; };
+    k.kv_watch = !is("SLIMT_KV_WATCH", '0');
+    k.kv_tight = !is("SLIMT_KV_TIGHT", '0');
+    k.host_timing = std::getenv("SLIMT_HOST_TIMING") != nullptr;
+    k.submit_lock = !is("SLIMT_SUBMIT_LOCK", '0');
+    k.kv_store_nt = is("SLIMT_KV_STORE_NT", '1');
+    k.rows_oversub = real("SLIMT_ROWS_OVERSUB", 1.0);
+    k.kv_budget = real("SLIMT_KV_BUDGET_MB", 300.0) * 1e6;
+    k.kv_grain = std::getenv("SLIMT_KV_GRAIN") ? std::max(1, std::atoi(std::getenv("SLIMT_KV_GRAIN"))) : 8;
+    k.kv_by_launch = std::getenv("SLIMT_KV_BY_LAUNCH") ? std::atoi(std::getenv("SLIMT_KV_BY_LAUNCH")) : -1;
+    k.kv_launch_budget = real("SLIMT_KV_LAUNCH_BUDGET_MB", 300.0) * 1e6;
+    k.shortlist_fold = !is("SLIMT_SHORTLIST_FOLD", '0');
+    k.merge_dense = !is("SLIMT_MERGE_DENSE", '0');
+    k.idle_streams = !is("SLIMT_IDLE_STREAMS", '0');
+    k.quiet = is("SLIMT_HIP_QUIET", '1');
+    return k;
+  }();
+  return knobs;
+}
+
 // The persistent decoder runs the hoisted cross-attention order over a cache of accumulators; the reference's literal
 // sequence (K/V cache format 3) exists in the stage-wise attention kernel only (decode_kernels.hip, DQAttnArgs::literal)
 // ... and a truncated sampled call needs each step's whole row of logits, which only the stage-wise decoder stores; a
@@ -93,7 +140,7 @@ static bool kv_narrow_wanted(slimt_hip_model *m, unsigned long long **count_dev)
   const unsigned long long total = m->kv_layers_submitted.load(std::memory_order_relaxed);
   // one sentence-layer in 32 is enough to make most 16-sentence workgroups wait for a fallback call every step
   // (SLIMT_KV_WATCH=0: never switch -- measurements of the fallback itself)
-  static const bool watch = !(std::getenv("SLIMT_KV_WATCH") && std::getenv("SLIMT_KV_WATCH")[0] == '0');
+  const bool watch = env().kv_watch;
   if (watch && total >= 1024 && wide * 32 > total) {
     m->kv_auto_wide.store(true, std::memory_order_relaxed);
     return false;
@@ -104,26 +151,24 @@ static bool kv_narrow_wanted(slimt_hip_model *m, unsigned long long **count_dev)
   return true;
 }
 
-static bool kv_tight_enabled() {
-  static const bool enabled = !(std::getenv("SLIMT_KV_TIGHT") && std::getenv("SLIMT_KV_TIGHT")[0] == '0');
-  return enabled;
-}
-
-// Where the tight form has a writer and a reader: D = 256 / F = 1536 (S <= 128; the 32-sentence tiling: S <= 32) and D = 512 /
-// F = 2048 (S <= 32), not clusters, and an encoder with a writer for it (`writer`: kv_tight_writer).
+// Where the tight form has a writer and a reader (launch_choice.h, kv_tight_shape), for this context's next batch of
+// sentences padded to S tokens behind an encoder with (`writer`: kv_tight_writer) or without a writer for it.
 static bool kv_tight_shape(const slimt_hip_ctx *c, int S, bool writer) {
   const slimt_hip_model *m = c->model;
-  if (!kv_tight_enabled() || !writer || m->kv_tight_limit <= 0 || m->kv_format != 0) return false;
-  if (S > 32)  // longer sentences: D = 256 only (33..64 tokens: one per 64-row workgroup; 65..128: the per-sentence encoder)
-    return S <= 128 && m->D == 256 && c->decode_mode != 3 && c->decode_mode != 6 && c->decode_mode != 1 &&
-           fused_decode_tight_mid_supported(m->D, m->F, m->H, m->Ld, S > 64 ? 2 : 1);
-  // (the 32-sentence tiling -- mode 3, or mode 0 with a large output layer, which only the decoder launch knows: what this
-  // context's last one saw stands in for it -- has the reader too where its LDS allows; else a batch that meets it is
-  // decoded by the 16-sentence tiling)
-  const bool rows32 = m->D == 256 && (c->decode_mode == 3 || (c->decode_mode == 0 && c->expect_large_output));
-  if (rows32) return fused_decode_tight_rows32_supported(m->D, m->F, m->H, m->Ld);
-  if (!(c->decode_mode == 0 || c->decode_mode == 2 || c->decode_mode == 3 || c->decode_mode == 4 || c->decode_mode == 5)) return false;
-  return fused_decode_tight_supported(m->D, m->F, m->H, m->Ld);
+  KvTightIn in;
+  in.enabled = env().kv_tight;
+  in.writer = writer;
+  in.tight_limit = m->kv_tight_limit;
+  in.kv_format = m->kv_format;
+  in.D = m->D;
+  in.S = S;
+  in.decode_mode = c->decode_mode;
+  in.expect_large_output = c->expect_large_output;
+  // (only the reader a batch of this length could take is asked about: the rule reads mid_ok for S > 32 alone)
+  in.mid_ok = S > 32 && fused_decode_tight_mid_supported(m->D, m->F, m->H, m->Ld, S > 64 ? 2 : 1);
+  in.rows32_ok = S <= 32 && fused_decode_tight_rows32_supported(m->D, m->F, m->H, m->Ld);
+  in.tight_ok = S <= 32 && fused_decode_tight_supported(m->D, m->F, m->H, m->Ld);
+  return slimt_hip::kv_tight_shape(in);
 }
 
 static bool kv_centres_ready(slimt_hip_model *m) {
@@ -143,7 +188,7 @@ static unsigned kv_tight_wanted(slimt_hip_ctx *c, int S, bool writer, unsigned l
   slimt_hip_model *m = c->model;
   *count_dev = nullptr;
   if (!kv_tight_shape(c, S, writer) || !m->kv_wide_count || !kv_centres_ready(m)) return 0;
-  static const bool watch = !(std::getenv("SLIMT_KV_WATCH") && std::getenv("SLIMT_KV_WATCH")[0] == '0');
+  const bool watch = env().kv_watch;
   unsigned off = m->kv_tight_off.load(std::memory_order_relaxed);
   const int gen = m->kv_gen.load(std::memory_order_relaxed);
   unsigned tripped = 0;
@@ -187,6 +232,35 @@ static void kv_watch_restart(slimt_hip_model *model) {
     for (int i = 0; i < 32; ++i) static_cast<volatile unsigned long long *>(model->kv_wide_count)[i] = 0;
 }
 
+// A translate call's claim on calibrating the current generation's centres. A call that took it and leaves before its
+// reduction is queued -- an error on the way -- gives it back: a claim without centres would keep every batch from
+// calibrating, and the form would silently never be used.
+struct ClaimGuard {
+  slimt_hip_model *m;
+  bool armed = false;
+  explicit ClaimGuard(slimt_hip_model *model) : m(model) {}
+  void take() { armed = !m->kv_centre_claimed.exchange(true, std::memory_order_acq_rel); }
+  ~ClaimGuard() {
+    if (armed && m->kv_centre_state.load(std::memory_order_acquire) == 0) m->kv_centre_claimed.store(false, std::memory_order_release);
+  }
+};
+
+// The claimed batch's column means into this generation's buffer, behind its encoder on the context's stream. No centres
+// -- an allocation or a launch failed --: the state stays 0, the guard gives the claim back and the next suitable batch
+// tries again; this one goes on with its f32 cache.
+static void queue_centre_reduction(slimt_hip_ctx *c, int B, int S) {
+  slimt_hip_model *gm = c->model;
+  hipStream_t st = c->stream;
+  DevBuf &centres = gm->kv_centre[gm->kv_gen.load(std::memory_order_relaxed)];  // this generation's own buffer
+  if (centres.reserve((size_t)gm->Ld * 2 * gm->D * 4) != hipSuccess || gm->kv_centre_sums.reserve((size_t)gm->Ld * 2 * gm->D * 8) != hipSuccess ||
+      (!gm->kv_centre_ev && hipEventCreateWithFlags(&gm->kv_centre_ev, hipEventDisableTiming) != hipSuccess) ||
+      launch_kv_centres(c->kv.as<float>(), gm->Ld, B, S, gm->D, gm->kv_centre_sums.as<unsigned long long>(), centres.as<int>(), st) != hipSuccess ||
+      hipEventRecord(gm->kv_centre_ev, st) != hipSuccess)
+    (void)hipGetLastError();
+  else
+    gm->kv_centre_state.store(1, std::memory_order_release);
+}
+
 hipError_t DevBuf::reserve(size_t n) {
   if (n <= bytes && p) return hipSuccess;
   g_hip_called.store(true, std::memory_order_relaxed);
@@ -211,7 +285,6 @@ void DevBuf::release() {
 namespace {
 // SLIMT_HOST_TIMING=1: where a translate call's host time goes (printed when a model is destroyed)
 struct HostTiming {
-  bool on = std::getenv("SLIMT_HOST_TIMING") != nullptr;
   std::atomic<uint64_t> ns[8] = {};
   std::atomic<uint64_t> calls{0};
 } g_timing;
@@ -219,16 +292,16 @@ const char *kTimingNames[8] = {"validate", "encode: prepare + launch", "submit +
                                "decoder launch call", "gate: event record", "pinned-pointer views", "other"};
 struct StageClock {
   std::chrono::steady_clock::time_point t;
-  StageClock() { if (g_timing.on) t = std::chrono::steady_clock::now(); }
+  StageClock() { if (env().host_timing) t = std::chrono::steady_clock::now(); }
   void lap(int stage) {
-    if (!g_timing.on) return;
+    if (!env().host_timing) return;
     const auto now = std::chrono::steady_clock::now();
     g_timing.ns[stage] += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(now - t).count();
     t = now;
   }
 };
 void timing_report() {
-  if (!g_timing.on || g_timing.calls == 0) return;
+  if (!env().host_timing || g_timing.calls == 0) return;
   std::fprintf(stderr, "host-timing: %llu translate calls; us per call:", (unsigned long long)g_timing.calls.load());
   for (int i = 0; i < 8; ++i)
     if (g_timing.ns[i]) std::fprintf(stderr, " [%s %.1f]", kTimingNames[i], 1e-3 * g_timing.ns[i] / g_timing.calls);
@@ -319,7 +392,6 @@ extern "C" int slimt_hip_prepare_weight_quantized_transposed(const int8_t *input
 // ---------------------------------------------------------------------------
 // process-wide diagnostic switch (slimt_hip_debug_occupancy_trace)
 static slimt_hip::OccTrace g_occ_trace;
-
 
 namespace {
 
@@ -1320,8 +1392,7 @@ static void count_context(int device, int delta) {
   const int now = g_live_ctx[device].fetch_add(delta, std::memory_order_relaxed) + delta;
   if (delta > 0 && now > kContextCliff) {
     static std::atomic<bool> warned{false};
-    const char *quiet = std::getenv("SLIMT_HIP_QUIET");
-    if (!(quiet && quiet[0] == '1') && !warned.exchange(true))
+    if (!env().quiet && !warned.exchange(true))
       std::fprintf(stderr,
                    "slimt_hip: %d contexts on device %d in one process: past %d the device's hardware queues are "
                    "time-sliced (24 contexts measured 30 %% below 20); use fewer workers with larger batches, or one "
@@ -1351,8 +1422,7 @@ static void level_hardware_queues(int device, int queues) {
   static std::mutex mu;
   static bool done[kMaxDevices];
   static std::vector<hipStream_t> idle;  // (never destroyed: a destroyed one would tilt the queues again)
-  static const bool off = std::getenv("SLIMT_IDLE_STREAMS") && std::getenv("SLIMT_IDLE_STREAMS")[0] == '0';
-  if (off || device < 0 || device >= kMaxDevices || queues < 2 || queues > 8) return;
+  if (!env().idle_streams || device < 0 || device >= kMaxDevices || queues < 2 || queues > 8) return;
   std::lock_guard<std::mutex> lock(mu);
   if (done[device]) return;
   done[device] = true;
@@ -1811,7 +1881,15 @@ struct CallOptions {
 // A batch whose options are device memory (the _device entry points): the kernels address them where they are.
 void options_in_place(slimt_hip_ctx *c, const BatchOptions &user) { c->call.dev = user; }
 
-void *host_device_view(const void *p);  // (below)
+// the device view of a pinned host allocation (hipHostMalloc / slimt_hip_host_alloc), else nullptr
+void *host_device_view(const void *p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return a.type == hipMemoryTypeHost ? a.devicePointer : nullptr;
+}
 
 // A host prefix of B sentences with rows Tmax apart: every length <= Tmax, every id of the prefix < V.
 int prefix_check(const slimt_hip_ctx *c, const uint32_t *ids, const uint32_t *len, size_t B, size_t Tmax) {
@@ -1879,6 +1957,50 @@ int stage_options(slimt_hip_ctx *c, const slimt_hip_batch *batches, size_t n, si
   return stage_options(c, n, user, rows, Tmax, dev);
 }
 
+// every encoder layer's weights, and the decoder layers' K / V projections the persistent encoders cache
+void fill_encoder_layers(const slimt_hip_model *m, FusedEncodeArgs &f) {
+  for (int l = 0; l < m->Le; ++l) {
+    const EncLayerW &L = m->enc[(size_t)l];
+    FusedEncLayerW &fl = f.L[l];
+    fl.q = L.attn.q.w; fl.k = L.attn.k.w; fl.v = L.attn.v.w; fl.o = L.attn.o.w;
+    fl.ffn1 = L.ffn1.w; fl.ffn2 = L.ffn2.w;
+    fl.attn_ln_s = L.attn.ln.scale.as<float>(); fl.attn_ln_b = L.attn.ln.bias.as<float>();
+    fl.ffn_ln_s = L.ffn_ln.scale.as<float>(); fl.ffn_ln_b = L.ffn_ln.bias.as<float>();
+  }
+  for (int l = 0; l < m->Ld; ++l) {
+    f.dec_k[l] = m->dec[(size_t)l].attn.k.w;
+    f.dec_v[l] = m->dec[(size_t)l].attn.v.w;
+  }
+}
+
+// The narrow (20-bit) form of a batch's packed cache where `narrow` allows it (launch_choice.h, kv_narrow_shape, behind a
+// kv24 launch) and the model's watch still wants it -- the forms are then recorded in ctx->kv_fmt -- and below it the tight
+// (16-bit) form for the decoder layers that try it. The watches' counters (kv_layers_submitted, kv_tight_submitted) take
+// this batch here, once, before its launch.
+int arm_kv_forms(slimt_hip_ctx *c, FusedEncodeArgs &f, int B, int S, bool narrow) {
+  const slimt_hip_model *m = c->model;
+  c->kv_fmt_valid = narrow && kv_narrow_wanted(c->model, &f.kv_wide_count);
+#ifdef SLIMT_EXP_NO_KV20  // A/B builds: the 24-bit form only
+  c->kv_fmt_valid = false;
+#endif
+  if (!c->kv_fmt_valid) return 0;
+  HIPCHK(c->kv_fmt.reserve((size_t)m->Ld * c->max_B));
+  f.kv_fmt = c->kv_fmt.as<unsigned char>();
+  f.kv_narrow_limit = std::min(m->kv_narrow_limit, 1 << 19);
+  c->kv_fmt_B = B;
+  c->model->kv_layers_submitted.fetch_add((unsigned long long)B * m->Ld, std::memory_order_relaxed);
+  f.kv_tight_layers = kv_tight_wanted(c, S, kv_tight_writer(c, B, S), &f.kv_not16_count);
+  if (f.kv_tight_layers) {
+    f.kv_tight_limit = std::min(m->kv_tight_limit, 1 << 15);
+    for (int l = 0; l < m->Ld; ++l)
+      for (int p = 0; p < 2; ++p) f.kv_centre[l][p] = m->kv_centre_of(c->kv_gen, l, p);
+    c->kv_tight = true;
+    for (int l = 0; l < m->Ld; ++l)
+      if ((f.kv_tight_layers >> l) & 1u) c->model->kv_tight_submitted[l].fetch_add((unsigned long long)B, std::memory_order_relaxed);
+  }
+  return 0;
+}
+
 // gen (nullable; only where fused_encoder_chosen): the batch's shortlist is generated inside the encoder launch
 // (kernels.h, FusedEncodeArgs::gen) -- its ids / count are pack->idx / pack->n_dev.
 int encode_device(slimt_hip_ctx *c, int B, int S, float *h_embed, float *h_layers,
@@ -1894,7 +2016,7 @@ int encode_device(slimt_hip_ctx *c, int B, int S, float *h_embed, float *h_layer
   hipStream_t st = c->stream;
   const int M = B * S, D = m->D;
   const size_t nbytes = (size_t)M * D * 4;
-  c->kv_fmt_valid = false;  // set below by the one path that records the forms of a packed cache
+  c->kv_fmt_valid = false;  // set by arm_kv_forms, where a persistent encoder records the forms of a packed cache
   c->kv_tight = false;
   c->B = B;
   c->S = S;
@@ -1908,18 +2030,7 @@ int encode_device(slimt_hip_ctx *c, int B, int S, float *h_embed, float *h_layer
     // embedding + every encoder layer + the decoder's K/V cache in one launch
     FusedEncodeArgs f;
     f.B = B; f.S = S; f.Le = m->Le; f.Ld = m->Ld;
-    for (int l = 0; l < m->Le; ++l) {
-      const EncLayerW &L = m->enc[(size_t)l];
-      FusedEncLayerW &fl = f.L[l];
-      fl.q = L.attn.q.w; fl.k = L.attn.k.w; fl.v = L.attn.v.w; fl.o = L.attn.o.w;
-      fl.ffn1 = L.ffn1.w; fl.ffn2 = L.ffn2.w;
-      fl.attn_ln_s = L.attn.ln.scale.as<float>(); fl.attn_ln_b = L.attn.ln.bias.as<float>();
-      fl.ffn_ln_s = L.ffn_ln.scale.as<float>(); fl.ffn_ln_b = L.ffn_ln.bias.as<float>();
-    }
-    for (int l = 0; l < m->Ld; ++l) {
-      f.dec_k[l] = m->dec[(size_t)l].attn.k.w;
-      f.dec_v[l] = m->dec[(size_t)l].attn.v.w;
-    }
+    fill_encoder_layers(m, f);
     f.emb = embed_args(c);
     f.ids = d_ids ? d_ids : c->ids.as<uint32_t>();
     f.lengths = d_lengths ? d_lengths : c->lengths.as<uint32_t>();
@@ -1931,27 +2042,7 @@ int encode_device(slimt_hip_ctx *c, int B, int S, float *h_embed, float *h_layer
     // the narrow (20-bit) form where the writer and the reader have it -- D = 256 or 512, S <= 32 -- and where a
     // sentence's V block (groups of eight keys) fits the slot of its 24-bit form (groups of four): not S = 1..4, 9..12
     // (... and S = 33..64 at D = 256: the 64-row encoder with one sentence per workgroup, attention_packed64 with Form20)
-    c->kv_fmt_valid = kv24 && ((D == 256 && S <= 64) || (D == 512 && S <= 32)) &&
-                      ((S + 7) / 8) * 5120 <= ((S + 3) / 4) * 3072 && kv_narrow_wanted(c->model, &f.kv_wide_count);
-#ifdef SLIMT_EXP_NO_KV20  // A/B builds: the 24-bit form only
-    c->kv_fmt_valid = false;
-#endif
-    if (c->kv_fmt_valid) {
-      HIPCHK(c->kv_fmt.reserve((size_t)m->Ld * c->max_B));
-      f.kv_fmt = c->kv_fmt.as<unsigned char>();
-      f.kv_narrow_limit = std::min(m->kv_narrow_limit, 1 << 19);
-      c->kv_fmt_B = B;
-      c->model->kv_layers_submitted.fetch_add((unsigned long long)B * m->Ld, std::memory_order_relaxed);
-      f.kv_tight_layers = kv_tight_wanted(c, S, kv_tight_writer(c, B, S), &f.kv_not16_count);
-      if (f.kv_tight_layers) {
-        f.kv_tight_limit = std::min(m->kv_tight_limit, 1 << 15);
-        for (int l = 0; l < m->Ld; ++l)
-          for (int p = 0; p < 2; ++p) f.kv_centre[l][p] = m->kv_centre_of(c->kv_gen, l, p);
-        c->kv_tight = true;
-        for (int l = 0; l < m->Ld; ++l)
-          if ((f.kv_tight_layers >> l) & 1u) c->model->kv_tight_submitted[l].fetch_add((unsigned long long)B, std::memory_order_relaxed);
-      }
-    }
+    RCCHK(arm_kv_forms(c, f, B, S, kv24 && kv_narrow_shape(D, S, /*long_encoder=*/false)));
     f.enc_out = keep_out ? c->x0.as<float>() : nullptr;
     if (pack) {
       f.pack = *pack;
@@ -2019,18 +2110,7 @@ int encode_device(slimt_hip_ctx *c, int B, int S, float *h_embed, float *h_layer
     LongEncodeArgs a;
     FusedEncodeArgs &f = a.f;
     f.B = B; f.S = S; f.Le = m->Le; f.Ld = m->Ld;
-    for (int l = 0; l < m->Le; ++l) {
-      const EncLayerW &L = m->enc[(size_t)l];
-      FusedEncLayerW &fl = f.L[l];
-      fl.q = L.attn.q.w; fl.k = L.attn.k.w; fl.v = L.attn.v.w; fl.o = L.attn.o.w;
-      fl.ffn1 = L.ffn1.w; fl.ffn2 = L.ffn2.w;
-      fl.attn_ln_s = L.attn.ln.scale.as<float>(); fl.attn_ln_b = L.attn.ln.bias.as<float>();
-      fl.ffn_ln_s = L.ffn_ln.scale.as<float>(); fl.ffn_ln_b = L.ffn_ln.bias.as<float>();
-    }
-    for (int l = 0; l < m->Ld; ++l) {
-      f.dec_k[l] = m->dec[(size_t)l].attn.k.w;
-      f.dec_v[l] = m->dec[(size_t)l].attn.v.w;
-    }
+    fill_encoder_layers(m, f);
     f.emb = embed_args(c);
     f.ids = d_ids ? d_ids : c->ids.as<uint32_t>();
     f.lengths = d_lengths ? d_lengths : c->lengths.as<uint32_t>();
@@ -2038,27 +2118,7 @@ int encode_device(slimt_hip_ctx *c, int B, int S, float *h_embed, float *h_layer
     f.kv = c->kv.as<float>();
     f.kv24 = kv24;
     // (the narrow form of the packed cache: the first path above has the note; here every S up to 128)
-    c->kv_fmt_valid = kv24 && D == 256 && ((S + 7) / 8) * 5120 <= ((S + 3) / 4) * 3072 &&
-                      kv_narrow_wanted(c->model, &f.kv_wide_count);
-#ifdef SLIMT_EXP_NO_KV20
-    c->kv_fmt_valid = false;
-#endif
-    if (c->kv_fmt_valid) {
-      HIPCHK(c->kv_fmt.reserve((size_t)m->Ld * c->max_B));
-      f.kv_fmt = c->kv_fmt.as<unsigned char>();
-      f.kv_narrow_limit = std::min(m->kv_narrow_limit, 1 << 19);
-      c->kv_fmt_B = B;
-      c->model->kv_layers_submitted.fetch_add((unsigned long long)B * m->Ld, std::memory_order_relaxed);
-      f.kv_tight_layers = kv_tight_wanted(c, S, kv_tight_writer(c, B, S), &f.kv_not16_count);
-      if (f.kv_tight_layers) {
-        f.kv_tight_limit = std::min(m->kv_tight_limit, 1 << 15);
-        for (int l = 0; l < m->Ld; ++l)
-          for (int p = 0; p < 2; ++p) f.kv_centre[l][p] = m->kv_centre_of(c->kv_gen, l, p);
-        c->kv_tight = true;
-        for (int l = 0; l < m->Ld; ++l)
-          if ((f.kv_tight_layers >> l) & 1u) c->model->kv_tight_submitted[l].fetch_add((unsigned long long)B, std::memory_order_relaxed);
-      }
-    }
+    RCCHK(arm_kv_forms(c, f, B, S, kv24 && kv_narrow_shape(D, S, /*long_encoder=*/true)));
     f.enc_out = c->x0.as<float>();
     if (pack) {
       f.pack = *pack;
@@ -2392,84 +2452,328 @@ int beam_steps(slimt_hip_ctx *c, size_t B, size_t S, size_t Tmax, uint32_t eos_i
   return 0;
 }
 
-// d_ids / d_lengths / d_shortlist: device pointers (the caller's, or the
-// context's staging buffers). When both persistent kernels apply, a translate
-// call is exactly two launches: [encoder + K/V cache + shortlist packing] and
-// [decode loop]; nothing is copied or memset in between (small helper kernels
-// queue behind the long-running decoders of the other workers).
-int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_lengths,
-                     const uint32_t *d_shortlist, size_t B, size_t S, size_t n_sl,
-                     float limit_factor, uint32_t eos_id, uint32_t *d_out_ids, uint32_t *d_out_len,
-                     float *d_align, int steps_hint, const uint32_t *d_n_sl = nullptr,
-                     float *align_out = nullptr, size_t n_sl_hint = 0, const ShortlistArgs *gen = nullptr,
-                     MergePlan *mp = nullptr) {
-  // mp (merged launch; lean path only, checked by the caller): B = the launch's global sentences, n_sl = the widest job's
-  // columns (0 = full vocabulary for every sub-batch); d_ids / d_lengths / d_shortlist / d_out_* / d_align are not used
-  // gen (with d_n_sl, lean path, 64-row encoder): the shortlist is generated inside the encoder launch
-  // n_sl_hint (with d_n_sl): what the host expects the device-side shortlist size to be (the size of
-  // this context's previous generated shortlist): tuning decisions only
-  // align_out != nullptr (persistent decoder only): d_align is a staging buffer in device memory and
-  // the decoder copies each sentence's rows from there to align_out when its loop ends (see
-  // FusedDecodeArgs::align_out)
-  // d_n_sl != nullptr: the shortlist was generated on this stream; its size is on
-  // the device and n_sl is only the capacity of d_shortlist (persistent kernels only)
+// The slot a lean translate call draws when it starts, and the k (kept launches of every 8) of the admission before it: the
+// K/V cache policy of THIS call, known to its encoder before its decoder is admitted (launch_choice.h, kv_launch_eighths).
+struct KvCallSlot {
+  unsigned long long slot = 0;
+  int k = 8;
+};
+// The persistent decoder's launch in three steps (translate_device): the tiling asked for, the arguments, the admission.
+struct FusedTiling {
+  bool tight = false, clusters = false;
+  int rows_per_wg = 0;
+};
+
+// ---- the persistent decoder: the whole greedy loop in one launch (decode_fused.hip) ---------------------------------
+// The tiling a launch asks for (launch_choice.h), from what the call and this context's last encoder left.
+FusedTiling choose_fused_tiling(slimt_hip_ctx *c, size_t B, size_t S, bool kv24, bool scored, bool merged, size_t n_expected) {
+  const slimt_hip_model *m = c->model;
+  // 32 sentences per workgroup (where the kernel has it) once the output layer dominates the
+  // weights a step streams: with the full 32k vocabulary it is 8 of 10 MB per workgroup and step, and
+  // halving it per sentence beats the longer attention chain (B = 512, full vocabulary: 20.4 -> 23-24 M
+  // tok/s; at 16k columns the two are level, below that 16 rows win)
+  // ... and 8 or 4 (decode_fused.hip, SPW) when the decoders in flight would leave most of the chip idle:
+  // decided in admit_and_launch_fused, under the admission lock, from the contexts that have a decoder pending
+  // Round 5: where the kernel has it, output layers that wide are SHARED by clusters of four 16-sentence workgroups
+  // instead (decode_fused.hip, CL: each member streams a quarter of the columns for all 64 sentences) -- under the
+  // decoder admission only: the members wait for each other, and the admission is what guarantees every admitted
+  // workgroup a CU without waiting for another decoder (decode mode 6 forces clusters, 3 the 32-sentence tiling)
+  // Measured on config 4 (B = 512, 32,000 columns, 20 workers; profiles/r05_cluster_logits.txt): clusters 23.4 M tok/s,
+  // the 32-sentence tiling 24.9 M, the 16-sentence one 22.0 M -- a member's quarter of the columns takes 27 us + 14 us of
+  // skew between its waves + 6 us of hand-overs where the whole layer took 70, but the 32-sentence tiling's per-sentence
+  // cost is lower still: the phase is bound by the arg-max epilogue's issue slots and the address path's load
+  // instructions (six per column tile here, four and a half there), not by the bytes the split saves. So: on request only.
+  // a batch whose encoder was allowed the tight cache form: the tilings with its reader, whatever is asked for now (the
+  // encoder is only allowed it when this context's decoders take those: kv_tight_wanted; a mode changed between the two
+  // calls, or a first large output layer, ends up here)
+  // (scored calls: the 16-sentence tilings without clusters, the only ones with the scored twin -- decode modes 2-6 and
+  // the adaptive rows are "16 rows" for them)
+  FusedTiling t;
+  t.tight = kv_tight_launch(kv24, c->kv_tight, c->kv_fmt_valid, c->kv_fmt_B, (int)B);
+  t.clusters = clusters_chosen(cluster_ok(kv24, m->D, m->F, S, m->decoder_budget), c->decode_mode, t.tight, merged, scored);
+  c->expect_large_output = n_expected > 16384;
+  t.rows_per_wg = fused_rows_requested(t.clusters, scored, c->decode_mode, n_expected, t.tight, S,
+                                       fused_decode_tight_rows32_supported(m->D, m->F, m->H, m->Ld), merged);
+  return t;
+}
+
+// Weights, K/V constants, the call's options and a merged launch's tables. No lock, no decision: those are
+// choose_fused_tiling before it and admit_and_launch_fused behind it. d_shortlist: nullptr for the full vocabulary.
+int fill_fused_decode_args(slimt_hip_ctx *c, FusedDecodeArgs &f, const FusedTiling &tiling, size_t B, size_t S, size_t Tmax,
+                           int steps_hint, const uint32_t *d_lengths, const uint32_t *d_shortlist, const uint32_t *d_n_sl,
+                           uint32_t eos_id, uint32_t *d_out_ids, uint32_t *d_out_len, float *d_align, float *align_out,
+                           float *d_scores, bool kv24, const MergePlan *mp) {
   const slimt_hip_model *m = c->model;
   hipStream_t st = c->stream;
-  // Model.cc:144-161: the first step is unconditional (one token is always recorded), the
-  // loop then runs while i < (size_t)(limit_factor * S): at least one output column
-  const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
-  const bool lean = persistent_path(c, S);
-  // R decoder rows over the B sources: B, but in a fan-out call (never lean, never merged). The caller's outputs, the
-  // per-call options and every decoder workspace are per row; ids, lengths, the encoder and the K / V per source.
   const CallState &call = c->call;
-  const size_t R = call.fanout ? (size_t)call.rows : B;
-  if (call.consensus) {  // (a fan-out call; the selection runs behind the last step, below)
-    if (!call.fanout || !call.cs_dev_best || !call.cs_dev_util) return fail(-1, "consensus: not a fan-out call");
-    if (Tmax > (size_t)SLIMT_HIP_CONSENSUS_MAX_T)
-      return fail(-1, "consensus: the call's Tmax %zu exceeds %d", Tmax, SLIMT_HIP_CONSENSUS_MAX_T);
+  const bool forced = call.forced, sampled = call.sampled, scored = call.scored || forced || sampled;
+  const AffineW &out = output_layer(c);
+  f.B = (int)B; f.S = (int)S; f.Ld = m->Ld;
+  f.max_steps = steps_hint > 0 ? steps_hint : (int)(Tmax > 1 ? Tmax : 1);
+  f.Tmax = (int)Tmax;
+  f.kv_tight = tiling.tight;
+  f.rows_per_wg = tiling.rows_per_wg;
+  if (tiling.clusters) {
+    const size_t tiles = (B + 15) / 16, n_clusters = (tiles + 3) / 4;
+    HIPCHK(c->cl_act.reserve(tiles * 16 * (size_t)m->D));
+    HIPCHK(c->cl_part.reserve(tiles * (16 * 4 + 1) * 8));
+    HIPCHK(c->cl_sync.reserve(n_clusters * 4));
+    HIPCHK(hipMemsetAsync(c->cl_sync.p, 0, n_clusters * 4, st));
+    f.cluster = 4;
+    f.cl_act = c->cl_act.as<unsigned char>();
+    f.cl_part = c->cl_part.as<int>();
+    f.cl_sync = c->cl_sync.as<unsigned>();
+    f.dev_error = dev_error_device_view(c);
   }
-  // packed 24-bit K/V cache: fused encoder -> fused decoder, D = 256 / d_head 32 or D = 512 / d_head 64, S <= 32
-  // (V is cached in groups of four keys: S = 1, 2, 5 would not fit the f32 form's plane)
-  // ... and for 33..64-token sentences of the D = 256 / F = 1536 shape (64-row encoder, one sentence per workgroup)
-  const bool kv24_mid = S > 32 && S <= 64 && c->encode_rows != 32 && c->decode_mode != 3 &&
-                        fused_decode_mid_supported(m->D, m->F, m->H, m->Ld) &&
-                        tall_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S);
-  // ... and for 65..128-token sentences of that shape (the per-sentence encoder, attention_packed128 with Form24)
-  const bool kv24_long = S > 64 && S <= 128 && c->decode_mode != 3 && fused_decode_long24_supported(m->D, m->F, m->H, m->Ld) &&
-                         long_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S);
-  const bool kv_packed = lean && (m->kv_format == 0 || m->kv_format == 2) &&
-                    ((m->D == 256 && m->D / m->H == 32) || (m->D == 512 && m->D / m->H == 64 && m->F == 2048)) &&
-                    ((S <= 32 && ((S + 3) & ~(size_t)3) * 3 <= S * 4 &&
-                      fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S) &&
-                      fused_decode_packed_supported(m->D, m->F, m->H, m->Ld)) || kv24_mid || kv24_long);
-  // The tight form's centres (engine.h, kv_centre): the first batch of enough rows that could take the form is cached as
-  // f32 instead, and its column means become the centres (behind the encoder, on this stream).
-  bool calibrate = false;
-  if (kv_packed && c->model->kv_centre_state.load(std::memory_order_acquire) == 0 && B * S >= 1024 &&
-      kv_tight_shape(c, (int)S, kv_tight_writer(c, (int)B, (int)S)) &&
-      !c->model->kv_centre_claimed.exchange(true, std::memory_order_acq_rel))
-    calibrate = true;
-  // (a call that claimed the calibration and leaves before its reduction is queued -- an error on the way -- gives the claim back)
-  struct ClaimGuard {
-    slimt_hip_model *m;
-    bool armed;
-    ~ClaimGuard() {
-      if (armed && m->kv_centre_state.load(std::memory_order_acquire) == 0) m->kv_centre_claimed.store(false, std::memory_order_release);
+  for (int l = 0; l < m->Ld; ++l) {
+    const DecLayerW &L = m->dec[(size_t)l];
+    FusedLayerW &fl = f.L[l];
+    fl.rnn_f = L.rnn_f.w; fl.rnn_w = L.rnn_w.w; fl.q = L.attn.q.w; fl.o = L.attn.o.w;
+    fl.ffn1 = L.ffn1.w; fl.ffn2 = L.ffn2.w;
+    fl.rnn_ln_s = L.rnn_ln.scale.as<float>(); fl.rnn_ln_b = L.rnn_ln.bias.as<float>();
+    fl.attn_ln_s = L.attn.ln.scale.as<float>(); fl.attn_ln_b = L.attn.ln.bias.as<float>();
+    fl.ffn_ln_s = L.ffn_ln.scale.as<float>(); fl.ffn_ln_b = L.ffn_ln.bias.as<float>();
+  }
+  f.out = out.w;
+  f.out_n_dev = d_n_sl;
+  f.shortlist = d_shortlist;
+  f.emb = embed_args(c);
+  f.out_tied_exact = m->out_tied_exact;
+  f.kv = c->kv.as<float>();
+  f.kv24 = kv24;
+  if (kv24 && c->kv_fmt_valid && c->kv_fmt_B == (int)B) f.kv_fmt = c->kv_fmt.as<unsigned char>();
+  for (int l = 0; l < m->Ld; ++l) {  // the projections' constants, applied after the attention's sums (kernels.h, kv24)
+    const AffineW &wk = m->dec[(size_t)l].attn.k, &wv = m->dec[(size_t)l].attn.v;
+    f.kv_pb[l][0] = wk.w.pb;
+    f.kv_pb[l][1] = wv.w.pb;
+    f.kv_cs[l][0] = wk.w.colsum;
+    f.kv_cs[l][1] = wv.w.colsum;
+    f.kv_u[l][0] = wk.w.u;
+    f.kv_u[l][1] = wv.w.u;
+    f.kv_u256[l][0] = wk.w.u * (1.0f / 256.0f);  // exact scalings: the packed integers come back
+    f.kv_u256[l][1] = wv.w.u * (1.0f / 256.0f);  // as accS * 256 (decode_fused.hip, unpack24f)
+    f.kv_centre[l][0] = m->kv_centre_of(c->kv_gen, l, 0);  // (the tight form, the generation this batch's encoder wrote
+    f.kv_centre[l][1] = m->kv_centre_of(c->kv_gen, l, 1);  //  it against; null until calibrated, not read then)
+    f.kv_u4096[l][0] = wk.w.u * (1.0f / 4096.0f);  // ... as accS * 4096 from the narrow form (unpack20)
+    f.kv_u4096[l][1] = wv.w.u * (1.0f / 4096.0f);
+  }
+  f.scores = d_scores;
+  if (sampled) {
+    f.inv_T = call.inv_T;
+    f.keys = mp ? nullptr : call.dev.keys;
+    for (int j = 0; mp && j < mp->n; ++j) f.sub_keys[j] = mp->opt[j].keys;
+  }
+  if (forced && !mp) {
+    f.prefix_ids = call.dev.prefix_ids;
+    f.prefix_len = call.dev.prefix_len;
+  }
+  if (mp) {
+    f.n_sub = mp->n;
+    f.sub_dense = mp->dense ? 1 : 0;
+    for (int j = 0; j < mp->n; ++j) f.sub[j] = mp->out[j];
+    for (int j = 0; scored && j < mp->n; ++j) f.sub_scores[j] = mp->opt[j].scores;
+    for (int j = 0; forced && j < mp->n; ++j) {
+      f.sub_prefix_ids[j] = mp->opt[j].prefix_ids;
+      f.sub_prefix_len[j] = mp->opt[j].prefix_len;
     }
-  } claim_guard{c->model, calibrate};
-  const bool kv24 = kv_packed && !calibrate;
-  // One thread at a time queues a persistent translate (a few runtime calls, ~50 us): the runtime
-  // serialises launches internally anyway, and a dozen worker threads contending inside it take
-  // far longer per call than the same calls made one after the other (Service, 10 workers: 2.1 ms
-  // per launch call against 0.05 ms with two).
-  static const bool submit_lock = !(std::getenv("SLIMT_SUBMIT_LOCK") && std::getenv("SLIMT_SUBMIT_LOCK")[0] == '0');
-  std::unique_lock<std::mutex> submit(c->model->submit_mu, std::defer_lock);
-  StageClock clk;
-  if (lean && submit_lock) submit.lock();
-  clk.lap(2);
-  if (g_timing.on) g_timing.calls += 1;
-  unsigned long long call_slot = 0;
-  int call_k = 8;
+    f.out_stride_wp = mp->stride_wp;
+    f.out_stride_cs = mp->stride_cs;
+    f.out_stride_pb = mp->stride_pb;
+    f.shortlist = nullptr;
+  }
+  f.cells = c->state.as<float>();
+  f.lengths = d_lengths;
+  f.alpha = 1.0f / std::sqrt(static_cast<float>(m->D / m->H));
+  f.eos = eos_id;
+  f.out_ids = d_out_ids;
+  f.out_len = d_out_len;
+  f.align = d_align;
+  f.align_out = d_align ? align_out : nullptr;
+  f.trace = g_occ_trace;
+  f.ticket = c->ticket.as<unsigned>();
+  f.ticket_base = c->ticket_base;  // advanced by admit_and_launch_fused, once the launch is in the stream
+  if (c->stamp_step >= 0 && c->stamps.p) {
+    f.stamps = c->stamps.as<unsigned long long>();
+    f.stamp_step = c->stamp_step;
+  }
+  return 0;
+}
+
+// The launch: everything the model's contexts decide together, under gate_mu -- the pending contexts, the plan
+// (decoder_plan.h), the K/V temporal policy, the XCD homes, the admission wait, the launch and the gate event -- or, without
+// a decoder budget, the launch alone.
+int admit_and_launch_fused(slimt_hip_ctx *c, FusedDecodeArgs &f, size_t B, size_t S, bool kv24, const KvCallSlot &drawn,
+                           StageClock &clk) {
+  const slimt_hip_model *m = c->model;
+  hipStream_t st = c->stream;
+  int rows = fused_decode_rows(m->D, m->F, m->H, m->Ld, (int)S, (int)B, f.rows_per_wg, kv24);
+  unsigned tickets = (unsigned)fused_decode_grid((int)B, true, rows);
+  const double macs = (double)B * f.max_steps *
+                      (m->Ld * (4.0 * m->D * m->D + 2.0 * m->D * m->F) + (double)m->D * f.out.N);
+  double wbytes = (double)f.max_steps * ((B + rows - 1) / rows) *
+                  (m->Ld * (4.0 * m->D * m->D + 2.0 * m->D * m->F) + (double)m->D * f.out.n_tiles * 16);
+  slimt_hip_model *gm = c->model;
+  int wgs = ((int)B + rows - 1) / rows;
+  if (gm->decoder_budget > 0) {
+    // decoder admission (engine.h): launch k waits for launch k - n on its own stream
+    constexpr size_t kRing = 64;
+    clk.lap(7);
+    std::lock_guard<std::mutex> lock(gm->gate_mu);
+    clk.lap(2);
+    while (gm->gate_ev.size() < kRing) {
+      hipEvent_t ev;
+      HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      gm->gate_ev.push_back(ev);
+    }
+    // K/V cache policy (decode_fused.hip, KV_AUX). The caches that are being read at any
+    // moment are those of the decoders that run: at most one per context (a context is a
+    // stream), one per hardware queue and n by admission. While they fit the 256 MB Infinity Cache every
+    // step re-reads them from there and non-temporal loads only lose that; beyond it the
+    // cache streams from HBM anyway and non-temporal loads keep it from displacing the
+    // weights. In between, the first layers' caches stay temporal (they then fit) and the
+    // rest stream: t_layers = as many of the Ld per-layer caches as 300 MB cover.
+    // Measured (tok/s, t_layers 0 / 1 / 2, Ld = 2): B=256, S=32 at 8 workers 17.1 / - /
+    // 18.8 M, 12: 21.9 / 22.5 / 22.1, 16: 23.6 / 24.2 / 22.6, 20: 23.9 / 24.5 / 23.5;
+    // B=512 full vocabulary 16.7 / 17.1 / 15.8; B=128, S=64 9.0 / 8.5 / 7.9; B=64, S=32
+    // 11.9 / - / 13.6; base 6.4 / 5.9 / 5.7.
+    // Which contexts have a decoder pending is judged from when they launched last (a translate
+    // call takes a few milliseconds), not by asking the runtime: one hipEventQuery per context
+    // under this lock made every launch O(contexts) runtime calls, and with a dozen worker threads
+    // the launches queued behind each other (Service, 16 workers: 9.9 ms per launch call).
+    // (the narrow form is what the model's sentences are expected to take where the kernels have it: 2.5 bytes per value)
+    const double kv_bytes = (double)m->Ld * 2.0 * (double)B * (double)S * m->D * kv_bytes_per_value(f.kv_tight, f.kv_fmt != nullptr, kv24);
+    const auto now = std::chrono::steady_clock::now();
+    double pending = kv_bytes;
+    size_t contexts = 1;
+    bool known = false;
+    for (auto &g : gm->gate_ctx) {
+      if (g.ctx == c) {
+        g.seq = gm->gate_seq;
+        g.kv_bytes = kv_bytes;
+        g.when = now;
+        known = true;
+      } else if (gm->gate_seq - g.seq < kRing && now - g.when < std::chrono::milliseconds(25)) {
+        pending += g.kv_bytes;
+        contexts += 1;
+      }
+    }
+    if (!known) gm->gate_ctx.push_back({c, gm->gate_seq, kv_bytes, now});
+    // The plan (decoder_plan.h): sentences per workgroup (decode mode 0: the fewest of 16 / 8 / 4 with which the
+    // decoders in flight still fit the budget -- one batch of 256 alone runs on 64 CUs instead of 16; a workgroup of
+    // fewer sentences streams the same weights for them: worth it only for CUs that would idle; results do not depend
+    // on it), the admission depth n and the K/V policy below. Decoders in flight = min(pending contexts, hardware
+    // queues): with GPU_MAX_HW_QUEUES = 32 the headline's twenty contexts are twenty decoders and stay at 16
+    // sentences, n = 14; with the runtime's default four queues only four run, and they take the 8-sentence tiling
+    // (4 x 32 workgroups) with no admission waits ("queue-bound").
+    // (SLIMT_ROWS_OVERSUB loosens "fit the budget")
+    // ... the K/V caches in eighths of a layer's caches (kernels.h, kv_temporal_eighths): SLIMT_KV_BUDGET_MB /
+    // SLIMT_KV_GRAIN tune the rule (defaults: 300 MB in whole layers, the measured optimum above)
+    // Round 4: WHICH caches stay temporal. "Layer 0 of every decoder" (the rule above) makes every workgroup pay one
+    // cached and one streamed attention per step; keeping BOTH layers of k of every 8 launches (by admission order)
+    // and streaming both layers of the others holds the same bytes but lets the kept decoders run their whole step
+    // at the cached speed (and finish together, so no CU idles inside a launch): 32.35 -> 33.05-33.26 M tok/s at
+    // k = 6, 32.5-32.9 at k = 5, 32.3-32.6 at k = 7, 31.7 all temporal (profiles/archive/r04_v3_kv_by_launch.txt).
+    // k = as many eighths of the pending decoders as SLIMT_KV_LAUNCH_BUDGET_MB covers (round 4: 270, the 24-bit form;
+    // round 5: 300 -- with the narrow form the headline's decoders hold 232 MB, k = 6 / 7 / 8 measure the same
+    // (35.8 / 35.7 / 35.6 M tok/s, profiles/r05_kv_keep_sweep.txt), and every launch then runs the kept instantiation);
+    // SLIMT_KV_BY_LAUNCH: 0 = the per-layer rule, 1..8 = that k.
+    // (sentences of up to 32 tokens; longer ones measured 2-3 % slower this way and keep the per-layer rule:
+    // S = 64 18.5 -> 17.9 M, S = 128 8.2 -> 8.0 M)
+    // ... and launches of which at least four fit the budget: ONE batch of 4096 holds 400 MB by itself, and keeping
+    // "all of it" thrashes where "its layer 0" fits (29.8 -> 27.2 M tok/s). With four queues the four decoders in
+    // flight hold 4 x 13-17 MB at the headline: every launch stays temporal.
+    DecoderPlanIn pin;
+    pin.B = (int)B; pin.S = (int)S; pin.Ld = m->Ld;
+    pin.rows = rows;
+    pin.adaptive = c->decode_mode == 0 && f.rows_per_wg == 0 && gm->adaptive_rows;
+    pin.narrow_ok = fused_decode_rows(m->D, m->F, m->H, m->Ld, (int)S, (int)B, 4, kv24) == 4 &&
+                    fused_decode_rows(m->D, m->F, m->H, m->Ld, (int)S, (int)B, 8, kv24) == 8;
+    pin.kv_bytes = kv_bytes;
+    pin.pending_kv = pending;
+    pin.contexts = contexts;
+    pin.queues = gm->hw_queues;
+    pin.budget = gm->decoder_budget;
+    pin.kv_policy = gm->kv_policy;
+    pin.ring = kRing;
+    pin.rows_oversub = env().rows_oversub;
+    pin.kv_budget = env().kv_budget;
+    pin.kv_grain = env().kv_grain;
+    pin.by_launch = env().kv_by_launch;
+    pin.launch_budget = env().kv_launch_budget;
+    const DecoderPlan plan = decoder_plan(pin);
+    if (plan.rows != rows) {
+      f.rows_per_wg = plan.rows;
+      rows = plan.rows;
+      tickets = (unsigned)fused_decode_grid((int)B, true, rows);
+      wgs = plan.wgs;
+      wbytes = (double)f.max_steps * wgs *
+               (m->Ld * (4.0 * m->D * m->D + 2.0 * m->D * m->F) + (double)m->D * f.out.n_tiles * 16);
+    }
+    const size_t n = plan.n;
+    const int all = 8 * m->Ld;
+    // (the slot was drawn when the call started, with the k of the admission before it: the encoder of a call
+    // whose cache will be streamed can then write it non-temporally, SLIMT_KV_STORE_NT=1)
+    const int eighths = kv_launch_eighths(plan.by_launch, plan.eighths, plan.k, drawn.slot, drawn.k, env().kv_store_nt, all);
+    gm->kv_k_last.store(plan.by_launch ? plan.k : 8, std::memory_order_relaxed);
+    f.kv_nt = eighths < all;
+    f.kv_temporal_eighths = eighths;
+    c->plan_last[0] = rows;
+    c->plan_last[1] = (int)contexts;
+    c->plan_last[2] = (int)plan.in_flight;
+    c->plan_last[3] = plan.wait ? (int)n : 0;
+    c->plan_last[4] = eighths;
+    c->plan_last[5] = gm->hw_queues;
+    if (plan.wait && gm->gate_seq >= n) HIPCHK(hipStreamWaitEvent(st, gm->gate_ev[(gm->gate_seq - n) % kRing], 0));
+    clk.lap(3);
+    const int n_home = gm->xcd_affinity;
+    const bool affine = n_home > 0 && rows == 16 && wgs <= 16 * n_home;
+    if (affine) {
+      if (gm->gate_home.size() < kRing) gm->gate_home.assign(kRing, 0u);
+      unsigned mask = gm->gate_seq >= n ? gm->gate_home[(gm->gate_seq - n) % kRing] : 0u;
+      if (!mask || __builtin_popcount(mask) != n_home) {
+        const unsigned slot = (unsigned)(gm->gate_seq % (size_t)(8 / n_home));
+        mask = n_home == 1 ? 1u << slot : n_home == 2 ? 3u << (2 * slot) : 0xfu << (4 * (slot & 1));
+      }
+      gm->gate_home[gm->gate_seq % kRing] = mask;
+      f.home_mask = mask;
+      f.xstate = reinterpret_cast<unsigned long long *>(c->ticket.as<unsigned>() + 2);
+      f.xarr_base = c->xarr_base;
+      f.xclaim_base = c->xclaim_base;
+      f.xgrid = 8u * (unsigned)((wgs + n_home - 1) / n_home);
+    } else if (!gm->gate_home.empty()) {
+      gm->gate_home[gm->gate_seq % kRing] = 0u;
+    }
+    {
+      ProfScope p(c, SLIMT_HIP_K_DECODE_FUSED, macs, wbytes);
+      HIPCHK(launch_decode_fused(f, m->D, m->F, m->H, st));
+    }
+    clk.lap(4);
+    if (affine) {
+      c->xarr_base += f.xgrid;
+      c->xclaim_base += (unsigned)wgs;
+    } else {
+      c->ticket_base += tickets;
+    }
+    HIPCHK(hipEventRecord(gm->gate_ev[gm->gate_seq % kRing], st));
+    clk.lap(5);
+    gm->gate_seq += 1;
+    return 0;
+  }
+  ProfScope p(c, SLIMT_HIP_K_DECODE_FUSED, macs, wbytes);
+  HIPCHK(launch_decode_fused(f, m->D, m->F, m->H, st));
+  c->ticket_base += tickets;
+  return 0;
+}
+
+// ---- the step-wise loop: every call the persistent decoder refuses (truncated, fan-out, beam, consensus; decode mode 1,
+// K/V format 3, shapes without the kernel) ----------------------------------------------------------------------------
+int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax, const uint32_t *d_shortlist, uint32_t eos_id,
+                    uint32_t *d_out_ids, uint32_t *d_out_len, float *d_align, float *d_scores, int steps_hint, bool merged) {
+  const slimt_hip_model *m = c->model;
+  hipStream_t st = c->stream;
+  const CallState &call = c->call;
+  const bool forced = call.forced, sampled = call.sampled;
+  const AffineW &out = output_layer(c);
   DecodeState ds;
   ds.prev = c->prev.as<uint32_t>();
   ds.out_ids = d_out_ids;
@@ -2478,377 +2782,9 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   ds.n_finished = c->n_finished.as<int>();
   ds.Tmax = (int)Tmax;
   ds.eos = eos_id;
-  // The batch's options as the kernels address them (the entry points set them): call.dev, or in a merged launch each
-  // sub-batch's mp->opt[j].
-  // a scored call: each recorded token's log-probability goes beside it
-  // a forced call takes the scored kernels' forced twins: scored as well, into a context-owned scratch when the caller did
-  // not ask for scores (merged: sub-batch j's rows of it from its first sentence on, Tmax_j <= Tmax)
-  // a sampled call takes their sampled twins, with or without a prefix: scored in the same way
-  const bool forced = call.forced;
-  const bool sampled = call.sampled;
-  const bool scored = call.scored || forced || sampled;
-  if ((forced || sampled) && !call.scored) {
-    HIPCHK(c->fp_scratch.reserve(R * Tmax * 4));
-    for (int j = 0; mp && j < mp->n; ++j) mp->opt[j].scores = c->fp_scratch.as<float>() + (size_t)mp->out[j].first * Tmax;
-  }
-  float *const d_scores = scored && !mp ? (call.scored ? call.dev.scores : c->fp_scratch.as<float>()) : nullptr;
-  if (scored && !mp && !d_scores) return fail(-1, "scores: no destination for this batch");
-  for (int j = 0; scored && mp && j < mp->n; ++j)
-    if (!mp->opt[j].scores) return fail(-1, "scores: no destination for batch %d", j);
-  if (forced && !mp && !(call.dev.prefix_ids && call.dev.prefix_len)) return fail(-1, "target prefix: none for this batch");
-  for (int j = 0; forced && mp && j < mp->n; ++j)
-    if (!mp->opt[j].prefix_ids || !mp->opt[j].prefix_len) return fail(-1, "target prefix: none for batch %d", j);
-  if (lean) {
-    PackArgs job;
-    if (n_sl && mp) {
-      // one allocation for the launch's jobs, job j at j strides (a stride holds the widest job)
-      mp->stride_wp = (packed_weight_bytes(m->D, (int)n_sl) + 255) / 256 * 256;
-      mp->stride_cs = (colsum_alloc_bytes((int)n_sl) + 255) / 256 * 256;
-      mp->stride_pb = (((size_t)n_sl + 15) / 16 * 16 * sizeof(float) + 255) / 256 * 256;
-      HIPCHK(c->out_sl.Wp.reserve(mp->stride_wp * mp->n_jobs));
-      HIPCHK(c->out_sl.colsum.reserve(mp->stride_cs * mp->n_jobs));
-      HIPCHK(c->out_sl.pb.reserve(mp->stride_pb * mp->n_jobs));
-      RCCHK(prepare_affine_meta(c->out_sl, m->out_raw.as<int8_t>(), m->D, mp->jobs[0].N, mp->jobs[0].idx,
-                                m->out_bias.as<float>(), m->out_a_quant, m->wemb_mult, job, m->V));
-    } else if (n_sl) {
-      RCCHK(prepare_affine_meta(c->out_sl, m->out_raw.as<int8_t>(), m->D, (int)n_sl, d_shortlist,
-                                m->out_bias.as<float>(), m->out_a_quant, m->wemb_mult, job, m->V));
-    }
-    job.n_dev = d_n_sl;
-    // the decoder's cache policy of THIS call (decided further down, under the admission lock, from the same two
-    // numbers): will its caches be kept in the Infinity Cache, or streamed? Streamed ones are also WRITTEN past it
-    call_slot = c->model->kv_call_seq.fetch_add(1, std::memory_order_relaxed);
-    call_k = c->model->kv_k_last.load(std::memory_order_relaxed);
-    static const bool store_nt = std::getenv("SLIMT_KV_STORE_NT") && std::getenv("SLIMT_KV_STORE_NT")[0] == '1';
-    RCCHK(encode_device(c, (int)B, (int)S, nullptr, nullptr, d_ids, d_lengths, n_sl ? &job : nullptr, false, false,
-                        kv24, gen, store_nt && kv24 && call_k < 8 && (int)(call_slot % 8) >= call_k, mp));
-    c->n_sl = (int)n_sl;
-    if (calibrate) {
-      slimt_hip_model *gm = c->model;
-      int rc = 0;
-      DevBuf &centres = gm->kv_centre[gm->kv_gen.load(std::memory_order_relaxed)];  // this generation's own buffer
-      if (centres.reserve((size_t)m->Ld * 2 * m->D * 4) != hipSuccess || gm->kv_centre_sums.reserve((size_t)m->Ld * 2 * m->D * 8) != hipSuccess ||
-          (!gm->kv_centre_ev && hipEventCreateWithFlags(&gm->kv_centre_ev, hipEventDisableTiming) != hipSuccess) ||
-          launch_kv_centres(c->kv.as<float>(), m->Ld, (int)B, (int)S, m->D, gm->kv_centre_sums.as<unsigned long long>(), centres.as<int>(), st) != hipSuccess ||
-          hipEventRecord(gm->kv_centre_ev, st) != hipSuccess)
-        rc = 1;
-      if (rc)  // (no centres: the next suitable batch tries again -- claim_guard --; this one goes on with its f32 cache)
-        (void)hipGetLastError();
-      else
-        gm->kv_centre_state.store(1, std::memory_order_release);
-    }
-    clk.lap(1);
-  } else {
-    if (d_ids != c->ids.as<uint32_t>())
-      HIPCHK(hipMemcpyAsync(c->ids.p, d_ids, B * S * 4, hipMemcpyDeviceToDevice, st));
-    if (d_lengths != c->lengths.as<uint32_t>())
-      HIPCHK(hipMemcpyAsync(c->lengths.p, d_lengths, B * 4, hipMemcpyDeviceToDevice, st));
-    if (n_sl && d_shortlist != c->shortlist.as<uint32_t>()) {
-      c->sl_host.clear();  // ctx->shortlist no longer holds what translate_host uploaded last
-      HIPCHK(hipMemcpyAsync(c->shortlist.p, d_shortlist, n_sl * 4, hipMemcpyDeviceToDevice, st));
-    }
-    d_lengths = c->lengths.as<uint32_t>();
-    d_shortlist = c->shortlist.as<uint32_t>();
-    RCCHK(encode_device(c, (int)B, (int)S, nullptr, nullptr));
-    RCCHK(decode_setup(c, n_sl));
-    HIPCHK(hipMemsetAsync(d_out_ids, 0, R * (Tmax ? Tmax : 1) * 4, st));
-    HIPCHK(hipMemsetAsync(d_out_len, 0, R * 4, st));
-    HIPCHK(hipMemsetAsync(c->finished.p, 0, R, st));
-    HIPCHK(hipMemsetAsync(c->n_finished.p, 0, 16, st));
-    if (d_align) HIPCHK(hipMemsetAsync(d_align, 0, R * Tmax * S * 4, st));
-  }
-  ds.shortlist = n_sl ? d_shortlist : nullptr;
-  const AffineW &out = output_layer(c);
+  ds.shortlist = d_shortlist;
   ds.pb0 = out.w.pb;
   ds.u_out = out.w.u;
-  if (fused_decoder_allowed(c) && fused_decode_supported(m->D, m->F, m->H, m->Ld)) {
-    // the whole greedy loop in one persistent launch (decode_fused.hip)
-    FusedDecodeArgs f;
-    f.B = (int)B; f.S = (int)S; f.Ld = m->Ld;
-    f.max_steps = steps_hint > 0 ? steps_hint : (int)(Tmax > 1 ? Tmax : 1);
-    f.Tmax = (int)Tmax;
-    // 32 sentences per workgroup (where the kernel has it) once the output layer dominates the
-    // weights a step streams: with the full 32k vocabulary it is 8 of 10 MB per workgroup and step, and
-    // halving it per sentence beats the longer attention chain (B = 512, full vocabulary: 20.4 -> 23-24 M
-    // tok/s; at 16k columns the two are level, below that 16 rows win)
-    const size_t n_expected = d_n_sl && n_sl_hint ? n_sl_hint : mp ? (size_t)(n_sl ? mp->max_N : m->V) : (size_t)out.w.N;
-    // ... and 8 or 4 (decode_fused.hip, SPW) when the decoders in flight would leave most of the chip idle:
-    // decided below, under the admission lock, from the contexts that have a decoder pending
-    // Round 5: where the kernel has it, output layers that wide are SHARED by clusters of four 16-sentence workgroups
-    // instead (decode_fused.hip, CL: each member streams a quarter of the columns for all 64 sentences) -- under the
-    // decoder admission only: the members wait for each other, and the admission is what guarantees every admitted
-    // workgroup a CU without waiting for another decoder (decode mode 6 forces clusters, 3 the 32-sentence tiling)
-    const bool cluster_ok = kv24 && m->D == 256 && m->F == 1536 && S <= 32 && c->model->decoder_budget > 0;
-    // Measured on config 4 (B = 512, 32,000 columns, 20 workers; profiles/r05_cluster_logits.txt): clusters 23.4 M tok/s,
-    // the 32-sentence tiling 24.9 M, the 16-sentence one 22.0 M -- a member's quarter of the columns takes 27 us + 14 us of
-    // skew between its waves + 6 us of hand-overs where the whole layer took 70, but the 32-sentence tiling's per-sentence
-    // cost is lower still: the phase is bound by the arg-max epilogue's issue slots and the address path's load
-    // instructions (six per column tile here, four and a half there), not by the bytes the split saves. So: on request only.
-    // a batch whose encoder was allowed the tight cache form: the tilings with its reader, whatever is asked for now (the
-    // encoder is only allowed it when this context's decoders take those: kv_tight_wanted; a mode changed between the two
-    // calls, or a first large output layer, ends up here)
-    const bool tight = kv24 && c->kv_tight && c->kv_fmt_valid && c->kv_fmt_B == (int)B;
-    // (scored calls: the 16-sentence tilings without clusters, the only ones with the scored twin -- decode modes 2-6 and
-    // the adaptive rows are "16 rows" for them)
-    const bool clusters = cluster_ok && c->decode_mode == 6 && !tight && !mp && !scored;
-    c->expect_large_output = n_expected > 16384;
-    f.kv_tight = tight;
-    f.rows_per_wg = clusters || scored ? 16 : c->decode_mode == 2 ? 16 : c->decode_mode == 3 ? 32 : c->decode_mode == 4 ? 8 : c->decode_mode == 5 ? 4
-                    : (n_expected > 16384 ? 32 : 0);
-    if (tight && f.rows_per_wg == 32 && !(S <= 32 && fused_decode_tight_rows32_supported(m->D, m->F, m->H, m->Ld))) f.rows_per_wg = 16;
-    if (mp && f.rows_per_wg == 32) f.rows_per_wg = 16;  // (merged launches: the 16-row tilings only, decode_fused.hip)
-    int rows = fused_decode_rows(m->D, m->F, m->H, m->Ld, (int)S, (int)B, f.rows_per_wg, kv24);
-    if (clusters) {
-      const size_t tiles = (B + 15) / 16, n_clusters = (tiles + 3) / 4;
-      HIPCHK(c->cl_act.reserve(tiles * 16 * (size_t)m->D));
-      HIPCHK(c->cl_part.reserve(tiles * (16 * 4 + 1) * 8));
-      HIPCHK(c->cl_sync.reserve(n_clusters * 4));
-      HIPCHK(hipMemsetAsync(c->cl_sync.p, 0, n_clusters * 4, st));
-      f.cluster = 4;
-      f.cl_act = c->cl_act.as<unsigned char>();
-      f.cl_part = c->cl_part.as<int>();
-      f.cl_sync = c->cl_sync.as<unsigned>();
-      f.dev_error = dev_error_device_view(c);
-    }
-    for (int l = 0; l < m->Ld; ++l) {
-      const DecLayerW &L = m->dec[(size_t)l];
-      FusedLayerW &fl = f.L[l];
-      fl.rnn_f = L.rnn_f.w; fl.rnn_w = L.rnn_w.w; fl.q = L.attn.q.w; fl.o = L.attn.o.w;
-      fl.ffn1 = L.ffn1.w; fl.ffn2 = L.ffn2.w;
-      fl.rnn_ln_s = L.rnn_ln.scale.as<float>(); fl.rnn_ln_b = L.rnn_ln.bias.as<float>();
-      fl.attn_ln_s = L.attn.ln.scale.as<float>(); fl.attn_ln_b = L.attn.ln.bias.as<float>();
-      fl.ffn_ln_s = L.ffn_ln.scale.as<float>(); fl.ffn_ln_b = L.ffn_ln.bias.as<float>();
-    }
-    f.out = out.w;
-    f.out_n_dev = d_n_sl;
-    f.shortlist = ds.shortlist;
-    f.emb = embed_args(c);
-    f.out_tied_exact = m->out_tied_exact;
-    f.kv = c->kv.as<float>();
-    f.kv24 = kv24;
-    if (kv24 && c->kv_fmt_valid && c->kv_fmt_B == (int)B) f.kv_fmt = c->kv_fmt.as<unsigned char>();
-    for (int l = 0; l < m->Ld; ++l) {  // the projections' constants, applied after the attention's sums (kernels.h, kv24)
-      const AffineW &wk = m->dec[(size_t)l].attn.k, &wv = m->dec[(size_t)l].attn.v;
-      f.kv_pb[l][0] = wk.w.pb;
-      f.kv_pb[l][1] = wv.w.pb;
-      f.kv_cs[l][0] = wk.w.colsum;
-      f.kv_cs[l][1] = wv.w.colsum;
-      f.kv_u[l][0] = wk.w.u;
-      f.kv_u[l][1] = wv.w.u;
-      f.kv_u256[l][0] = wk.w.u * (1.0f / 256.0f);  // exact scalings: the packed integers come back
-      f.kv_u256[l][1] = wv.w.u * (1.0f / 256.0f);  // as accS * 256 (decode_fused.hip, unpack24f)
-      f.kv_centre[l][0] = m->kv_centre_of(c->kv_gen, l, 0);  // (the tight form, the generation this batch's encoder wrote
-      f.kv_centre[l][1] = m->kv_centre_of(c->kv_gen, l, 1);  //  it against; null until calibrated, not read then)
-      f.kv_u4096[l][0] = wk.w.u * (1.0f / 4096.0f);  // ... as accS * 4096 from the narrow form (unpack20)
-      f.kv_u4096[l][1] = wv.w.u * (1.0f / 4096.0f);
-    }
-    f.scores = d_scores;
-    if (sampled) {
-      f.inv_T = call.inv_T;
-      f.keys = mp ? nullptr : call.dev.keys;
-      for (int j = 0; mp && j < mp->n; ++j) f.sub_keys[j] = mp->opt[j].keys;
-    }
-    if (forced && !mp) {
-      f.prefix_ids = call.dev.prefix_ids;
-      f.prefix_len = call.dev.prefix_len;
-    }
-    if (mp) {
-      f.n_sub = mp->n;
-      f.sub_dense = mp->dense ? 1 : 0;
-      for (int j = 0; j < mp->n; ++j) f.sub[j] = mp->out[j];
-      for (int j = 0; scored && j < mp->n; ++j) f.sub_scores[j] = mp->opt[j].scores;
-      for (int j = 0; forced && j < mp->n; ++j) {
-        f.sub_prefix_ids[j] = mp->opt[j].prefix_ids;
-        f.sub_prefix_len[j] = mp->opt[j].prefix_len;
-      }
-      f.out_stride_wp = mp->stride_wp;
-      f.out_stride_cs = mp->stride_cs;
-      f.out_stride_pb = mp->stride_pb;
-      f.shortlist = nullptr;
-    }
-    f.cells = c->state.as<float>();
-    f.lengths = d_lengths;
-    f.alpha = 1.0f / std::sqrt(static_cast<float>(m->D / m->H));
-    f.eos = eos_id;
-    f.out_ids = d_out_ids;
-    f.out_len = d_out_len;
-    f.align = d_align;
-    f.align_out = d_align ? align_out : nullptr;
-    f.trace = g_occ_trace;
-    f.ticket = c->ticket.as<unsigned>();
-    f.ticket_base = c->ticket_base;  // advanced below, once the launch is in the stream
-    unsigned tickets = (unsigned)fused_decode_grid((int)B, true, rows);
-    if (c->stamp_step >= 0 && c->stamps.p) {
-      f.stamps = c->stamps.as<unsigned long long>();
-      f.stamp_step = c->stamp_step;
-    }
-    const double macs = (double)B * f.max_steps *
-                        (m->Ld * (4.0 * m->D * m->D + 2.0 * m->D * m->F) + (double)m->D * out.w.N);
-    double wbytes = (double)f.max_steps * ((B + rows - 1) / rows) *
-                    (m->Ld * (4.0 * m->D * m->D + 2.0 * m->D * m->F) + (double)m->D * out.w.n_tiles * 16);
-    slimt_hip_model *gm = c->model;
-    int wgs = ((int)B + rows - 1) / rows;
-    if (gm->decoder_budget > 0) {
-      // decoder admission (engine.h): launch k waits for launch k - n on its own stream
-      constexpr size_t kRing = 64;
-      clk.lap(7);
-      std::lock_guard<std::mutex> lock(gm->gate_mu);
-      clk.lap(2);
-      while (gm->gate_ev.size() < kRing) {
-        hipEvent_t ev;
-        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        gm->gate_ev.push_back(ev);
-      }
-      // K/V cache policy (decode_fused.hip, KV_AUX). The caches that are being read at any
-      // moment are those of the decoders that run: at most one per context (a context is a
-      // stream), one per hardware queue and n by admission. While they fit the 256 MB Infinity Cache every
-      // step re-reads them from there and non-temporal loads only lose that; beyond it the
-      // cache streams from HBM anyway and non-temporal loads keep it from displacing the
-      // weights. In between, the first layers' caches stay temporal (they then fit) and the
-      // rest stream: t_layers = as many of the Ld per-layer caches as 300 MB cover.
-      // Measured (tok/s, t_layers 0 / 1 / 2, Ld = 2): B=256, S=32 at 8 workers 17.1 / - /
-      // 18.8 M, 12: 21.9 / 22.5 / 22.1, 16: 23.6 / 24.2 / 22.6, 20: 23.9 / 24.5 / 23.5;
-      // B=512 full vocabulary 16.7 / 17.1 / 15.8; B=128, S=64 9.0 / 8.5 / 7.9; B=64, S=32
-      // 11.9 / - / 13.6; base 6.4 / 5.9 / 5.7.
-      // Which contexts have a decoder pending is judged from when they launched last (a translate
-      // call takes a few milliseconds), not by asking the runtime: one hipEventQuery per context
-      // under this lock made every launch O(contexts) runtime calls, and with a dozen worker threads
-      // the launches queued behind each other (Service, 16 workers: 9.9 ms per launch call).
-      // (the narrow form is what the model's sentences are expected to take where the kernels have it: 2.5 bytes per value)
-      const double kv_bytes = (double)m->Ld * 2.0 * (double)B * (double)S * m->D * (f.kv_tight ? 2.0 : f.kv_fmt ? 2.5 : kv24 ? 3.0 : 4.0);
-      const auto now = std::chrono::steady_clock::now();
-      double pending = kv_bytes;
-      size_t contexts = 1;
-      bool known = false;
-      for (auto &g : gm->gate_ctx) {
-        if (g.ctx == c) {
-          g.seq = gm->gate_seq;
-          g.kv_bytes = kv_bytes;
-          g.when = now;
-          known = true;
-        } else if (gm->gate_seq - g.seq < kRing && now - g.when < std::chrono::milliseconds(25)) {
-          pending += g.kv_bytes;
-          contexts += 1;
-        }
-      }
-      if (!known) gm->gate_ctx.push_back({c, gm->gate_seq, kv_bytes, now});
-      // The plan (decoder_plan.h): sentences per workgroup (decode mode 0: the fewest of 16 / 8 / 4 with which the
-      // decoders in flight still fit the budget -- one batch of 256 alone runs on 64 CUs instead of 16; a workgroup of
-      // fewer sentences streams the same weights for them: worth it only for CUs that would idle; results do not depend
-      // on it), the admission depth n and the K/V policy below. Decoders in flight = min(pending contexts, hardware
-      // queues): with GPU_MAX_HW_QUEUES = 32 the headline's twenty contexts are twenty decoders and stay at 16
-      // sentences, n = 14; with the runtime's default four queues only four run, and they take the 8-sentence tiling
-      // (4 x 32 workgroups) with no admission waits ("queue-bound").
-      static const double oversub = std::getenv("SLIMT_ROWS_OVERSUB") ? std::atof(std::getenv("SLIMT_ROWS_OVERSUB")) : 1.0;
-      // ... the K/V caches in eighths of a layer's caches (kernels.h, kv_temporal_eighths): SLIMT_KV_BUDGET_MB /
-      // SLIMT_KV_GRAIN tune the rule (defaults: 300 MB in whole layers, the measured optimum above)
-      static const double budget = (std::getenv("SLIMT_KV_BUDGET_MB") ? std::atof(std::getenv("SLIMT_KV_BUDGET_MB")) : 300.0) * 1e6;
-      static const int grain = std::getenv("SLIMT_KV_GRAIN") ? std::max(1, std::atoi(std::getenv("SLIMT_KV_GRAIN"))) : 8;
-      // Round 4: WHICH caches stay temporal. "Layer 0 of every decoder" (the rule above) makes every workgroup pay one
-      // cached and one streamed attention per step; keeping BOTH layers of k of every 8 launches (by admission order)
-      // and streaming both layers of the others holds the same bytes but lets the kept decoders run their whole step
-      // at the cached speed (and finish together, so no CU idles inside a launch): 32.35 -> 33.05-33.26 M tok/s at
-      // k = 6, 32.5-32.9 at k = 5, 32.3-32.6 at k = 7, 31.7 all temporal (profiles/archive/r04_v3_kv_by_launch.txt).
-      // k = as many eighths of the pending decoders as SLIMT_KV_LAUNCH_BUDGET_MB covers (round 4: 270, the 24-bit form;
-      // round 5: 300 -- with the narrow form the headline's decoders hold 232 MB, k = 6 / 7 / 8 measure the same
-      // (35.8 / 35.7 / 35.6 M tok/s, profiles/r05_kv_keep_sweep.txt), and every launch then runs the kept instantiation);
-      // SLIMT_KV_BY_LAUNCH: 0 = the per-layer rule, 1..8 = that k.
-      // (sentences of up to 32 tokens; longer ones measured 2-3 % slower this way and keep the per-layer rule:
-      // S = 64 18.5 -> 17.9 M, S = 128 8.2 -> 8.0 M)
-      // ... and launches of which at least four fit the budget: ONE batch of 4096 holds 400 MB by itself, and keeping
-      // "all of it" thrashes where "its layer 0" fits (29.8 -> 27.2 M tok/s). With four queues the four decoders in
-      // flight hold 4 x 13-17 MB at the headline: every launch stays temporal.
-      static const bool store_nt_rule = std::getenv("SLIMT_KV_STORE_NT") && std::getenv("SLIMT_KV_STORE_NT")[0] == '1';
-      static const int by_launch = std::getenv("SLIMT_KV_BY_LAUNCH") ? std::atoi(std::getenv("SLIMT_KV_BY_LAUNCH")) : -1;
-      static const double launch_budget =
-          (std::getenv("SLIMT_KV_LAUNCH_BUDGET_MB") ? std::atof(std::getenv("SLIMT_KV_LAUNCH_BUDGET_MB")) : 300.0) * 1e6;
-      DecoderPlanIn pin;
-      pin.B = (int)B; pin.S = (int)S; pin.Ld = m->Ld;
-      pin.rows = rows;
-      pin.adaptive = c->decode_mode == 0 && f.rows_per_wg == 0 && gm->adaptive_rows;
-      pin.narrow_ok = fused_decode_rows(m->D, m->F, m->H, m->Ld, (int)S, (int)B, 4, kv24) == 4 &&
-                      fused_decode_rows(m->D, m->F, m->H, m->Ld, (int)S, (int)B, 8, kv24) == 8;
-      pin.kv_bytes = kv_bytes;
-      pin.pending_kv = pending;
-      pin.contexts = contexts;
-      pin.queues = gm->hw_queues;
-      pin.budget = gm->decoder_budget;
-      pin.kv_policy = gm->kv_policy;
-      pin.ring = kRing;
-      pin.rows_oversub = oversub;
-      pin.kv_budget = budget;
-      pin.kv_grain = grain;
-      pin.by_launch = by_launch;
-      pin.launch_budget = launch_budget;
-      const DecoderPlan plan = decoder_plan(pin);
-      if (plan.rows != rows) {
-        f.rows_per_wg = plan.rows;
-        rows = plan.rows;
-        tickets = (unsigned)fused_decode_grid((int)B, true, rows);
-        wgs = plan.wgs;
-        wbytes = (double)f.max_steps * wgs *
-                 (m->Ld * (4.0 * m->D * m->D + 2.0 * m->D * m->F) + (double)m->D * out.w.n_tiles * 16);
-      }
-      const size_t n = plan.n;
-      const int all = 8 * m->Ld;
-      int eighths = plan.eighths;
-      if (plan.by_launch) {
-        // (the slot was drawn when the call started, with the k of the admission before it: the encoder of a call
-        // whose cache will be streamed can then write it non-temporally, SLIMT_KV_STORE_NT=1)
-        eighths = (int)(call_slot % 8) < (store_nt_rule ? call_k : plan.k) ? all : 0;
-        gm->kv_k_last.store(plan.k, std::memory_order_relaxed);
-      } else {
-        gm->kv_k_last.store(8, std::memory_order_relaxed);
-      }
-      f.kv_nt = eighths < all;
-      f.kv_temporal_eighths = eighths;
-      c->plan_last[0] = rows;
-      c->plan_last[1] = (int)contexts;
-      c->plan_last[2] = (int)plan.in_flight;
-      c->plan_last[3] = plan.wait ? (int)n : 0;
-      c->plan_last[4] = eighths;
-      c->plan_last[5] = gm->hw_queues;
-      if (plan.wait && gm->gate_seq >= n) HIPCHK(hipStreamWaitEvent(st, gm->gate_ev[(gm->gate_seq - n) % kRing], 0));
-      clk.lap(3);
-      const int n_home = gm->xcd_affinity;
-      const bool affine = n_home > 0 && rows == 16 && wgs <= 16 * n_home;
-      if (affine) {
-        if (gm->gate_home.size() < kRing) gm->gate_home.assign(kRing, 0u);
-        unsigned mask = gm->gate_seq >= n ? gm->gate_home[(gm->gate_seq - n) % kRing] : 0u;
-        if (!mask || __builtin_popcount(mask) != n_home) {
-          const unsigned slot = (unsigned)(gm->gate_seq % (size_t)(8 / n_home));
-          mask = n_home == 1 ? 1u << slot : n_home == 2 ? 3u << (2 * slot) : 0xfu << (4 * (slot & 1));
-        }
-        gm->gate_home[gm->gate_seq % kRing] = mask;
-        f.home_mask = mask;
-        f.xstate = reinterpret_cast<unsigned long long *>(c->ticket.as<unsigned>() + 2);
-        f.xarr_base = c->xarr_base;
-        f.xclaim_base = c->xclaim_base;
-        f.xgrid = 8u * (unsigned)((wgs + n_home - 1) / n_home);
-      } else if (!gm->gate_home.empty()) {
-        gm->gate_home[gm->gate_seq % kRing] = 0u;
-      }
-      {
-        ProfScope p(c, SLIMT_HIP_K_DECODE_FUSED, macs, wbytes);
-        HIPCHK(launch_decode_fused(f, m->D, m->F, m->H, st));
-      }
-      clk.lap(4);
-      if (affine) {
-        c->xarr_base += f.xgrid;
-        c->xclaim_base += (unsigned)wgs;
-      } else {
-        c->ticket_base += tickets;
-      }
-      HIPCHK(hipEventRecord(gm->gate_ev[gm->gate_seq % kRing], st));
-      clk.lap(5);
-      gm->gate_seq += 1;
-      return 0;
-    }
-    ProfScope p(c, SLIMT_HIP_K_DECODE_FUSED, macs, wbytes);
-    HIPCHK(launch_decode_fused(f, m->D, m->F, m->H, st));
-    c->ticket_base += tickets;
-    return 0;
-  }
   if (call.beam) return beam_steps(c, B, S, Tmax, eos_id, ds.shortlist, d_out_ids, d_out_len, d_align, steps_hint);
   // a truncated call stores each step's logits and selects over them: one partial per row (sample_truncate.hip)
   const bool truncated = sampled && call.truncated;
@@ -2858,8 +2794,8 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   const EmbedArgs e = embed_args(c);
   if (d_scores) HIPCHK(c->part_sum.reserve(R * (size_t)n_parts * 4));
   float *const part_sum = d_scores ? c->part_sum.as<float>() : nullptr;
-  if (forced && mp) return fail(-1, "target prefix: merged launches decode with the persistent kernels only");
-  if (sampled && mp) return fail(-1, "sampling: merged launches decode with the persistent kernels only");
+  if (forced && merged) return fail(-1, "target prefix: merged launches decode with the persistent kernels only");
+  if (sampled && merged) return fail(-1, "sampling: merged launches decode with the persistent kernels only");
   SampledStep ss;  // (sampled: the keys, the steps' hash words and the partials beside the arg-max's, kernels.h)
   if (sampled) {
     HIPCHK(c->sm_seeds.reserve(2 * R * 4));
@@ -2972,6 +2908,182 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   return rc;
 }
 
+// The batch's options as the kernels address them (the entry points set them): call.dev, or in a merged launch each
+// sub-batch's mp->opt[j].
+// a scored call: each recorded token's log-probability goes beside it
+// a forced call takes the scored kernels' forced twins: scored as well, into a context-owned scratch when the caller did
+// not ask for scores (merged: sub-batch j's rows of it from its first sentence on, Tmax_j <= Tmax)
+// a sampled call takes their sampled twins, with or without a prefix: scored in the same way
+int check_call_destinations(slimt_hip_ctx *c, size_t R, size_t Tmax, MergePlan *mp, float **d_scores_out) {
+  const CallState &call = c->call;
+  const bool forced = call.forced;
+  const bool sampled = call.sampled;
+  const bool scored = call.scored || forced || sampled;
+  if ((forced || sampled) && !call.scored) {
+    HIPCHK(c->fp_scratch.reserve(R * Tmax * 4));
+    for (int j = 0; mp && j < mp->n; ++j) mp->opt[j].scores = c->fp_scratch.as<float>() + (size_t)mp->out[j].first * Tmax;
+  }
+  float *const d_scores = scored && !mp ? (call.scored ? call.dev.scores : c->fp_scratch.as<float>()) : nullptr;
+  if (scored && !mp && !d_scores) return fail(-1, "scores: no destination for this batch");
+  for (int j = 0; scored && mp && j < mp->n; ++j)
+    if (!mp->opt[j].scores) return fail(-1, "scores: no destination for batch %d", j);
+  if (forced && !mp && !(call.dev.prefix_ids && call.dev.prefix_len)) return fail(-1, "target prefix: none for this batch");
+  for (int j = 0; forced && mp && j < mp->n; ++j)
+    if (!mp->opt[j].prefix_ids || !mp->opt[j].prefix_len) return fail(-1, "target prefix: none for batch %d", j);
+  *d_scores_out = d_scores;
+  return 0;
+}
+
+// The lean path's first launch: the output layer's packing job (one per distinct shortlist in a merged launch), the
+// call's slot in the by-launch K/V policy, the persistent encoder, and -- for the batch that claimed it -- the centres'
+// reduction behind it.
+int encode_lean_for_translate(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_lengths, const uint32_t *d_shortlist,
+                              size_t B, size_t S, size_t n_sl, const uint32_t *d_n_sl, const ShortlistArgs *gen, MergePlan *mp,
+                              bool kv24, bool calibrate, KvCallSlot &slot) {
+  const slimt_hip_model *m = c->model;
+  PackArgs job;
+  if (n_sl && mp) {
+    // one allocation for the launch's jobs, job j at j strides (a stride holds the widest job)
+    mp->stride_wp = (packed_weight_bytes(m->D, (int)n_sl) + 255) / 256 * 256;
+    mp->stride_cs = (colsum_alloc_bytes((int)n_sl) + 255) / 256 * 256;
+    mp->stride_pb = (((size_t)n_sl + 15) / 16 * 16 * sizeof(float) + 255) / 256 * 256;
+    HIPCHK(c->out_sl.Wp.reserve(mp->stride_wp * mp->n_jobs));
+    HIPCHK(c->out_sl.colsum.reserve(mp->stride_cs * mp->n_jobs));
+    HIPCHK(c->out_sl.pb.reserve(mp->stride_pb * mp->n_jobs));
+    RCCHK(prepare_affine_meta(c->out_sl, m->out_raw.as<int8_t>(), m->D, mp->jobs[0].N, mp->jobs[0].idx,
+                              m->out_bias.as<float>(), m->out_a_quant, m->wemb_mult, job, m->V));
+  } else if (n_sl) {
+    RCCHK(prepare_affine_meta(c->out_sl, m->out_raw.as<int8_t>(), m->D, (int)n_sl, d_shortlist,
+                              m->out_bias.as<float>(), m->out_a_quant, m->wemb_mult, job, m->V));
+  }
+  job.n_dev = d_n_sl;
+  // the decoder's cache policy of THIS call (decided in admit_and_launch_fused, under the admission lock, from the same
+  // two numbers): will its caches be kept in the Infinity Cache, or streamed? Streamed ones are also WRITTEN past it
+  slot.slot = c->model->kv_call_seq.fetch_add(1, std::memory_order_relaxed);
+  slot.k = c->model->kv_k_last.load(std::memory_order_relaxed);
+  RCCHK(encode_device(c, (int)B, (int)S, nullptr, nullptr, d_ids, d_lengths, n_sl ? &job : nullptr, false, false, kv24, gen,
+                      kv_store_streamed(env().kv_store_nt, kv24, slot.slot, slot.k), mp));
+  c->n_sl = (int)n_sl;
+  if (calibrate) queue_centre_reduction(c, (int)B, (int)S);
+  return 0;
+}
+
+// The stage-wise path: the batch into the context's own buffers (d_lengths / d_shortlist then name those), the per-stage
+// encoder, decode_setup, and the outputs cleared for R decoder rows.
+int encode_stagewise_for_translate(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t **d_lengths_io,
+                                   const uint32_t **d_shortlist_io, size_t B, size_t S, size_t R, size_t Tmax, size_t n_sl,
+                                   uint32_t *d_out_ids, uint32_t *d_out_len, float *d_align) {
+  hipStream_t st = c->stream;
+  const uint32_t *d_lengths = *d_lengths_io, *d_shortlist = *d_shortlist_io;
+  if (d_ids != c->ids.as<uint32_t>())
+    HIPCHK(hipMemcpyAsync(c->ids.p, d_ids, B * S * 4, hipMemcpyDeviceToDevice, st));
+  if (d_lengths != c->lengths.as<uint32_t>())
+    HIPCHK(hipMemcpyAsync(c->lengths.p, d_lengths, B * 4, hipMemcpyDeviceToDevice, st));
+  if (n_sl && d_shortlist != c->shortlist.as<uint32_t>()) {
+    c->sl_host.clear();  // ctx->shortlist no longer holds what translate_host uploaded last
+    HIPCHK(hipMemcpyAsync(c->shortlist.p, d_shortlist, n_sl * 4, hipMemcpyDeviceToDevice, st));
+  }
+  *d_lengths_io = c->lengths.as<uint32_t>();
+  *d_shortlist_io = c->shortlist.as<uint32_t>();
+  RCCHK(encode_device(c, (int)B, (int)S, nullptr, nullptr));
+  RCCHK(decode_setup(c, n_sl));
+  HIPCHK(hipMemsetAsync(d_out_ids, 0, R * (Tmax ? Tmax : 1) * 4, st));
+  HIPCHK(hipMemsetAsync(d_out_len, 0, R * 4, st));
+  HIPCHK(hipMemsetAsync(c->finished.p, 0, R, st));
+  HIPCHK(hipMemsetAsync(c->n_finished.p, 0, 16, st));
+  if (d_align) HIPCHK(hipMemsetAsync(d_align, 0, R * Tmax * S * 4, st));
+  return 0;
+}
+
+// d_ids / d_lengths / d_shortlist: device pointers (the caller's, or the
+// context's staging buffers). When both persistent kernels apply, a translate
+// call is exactly two launches: [encoder + K/V cache + shortlist packing] and
+// [decode loop]; nothing is copied or memset in between (small helper kernels
+// queue behind the long-running decoders of the other workers).
+int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_lengths,
+                     const uint32_t *d_shortlist, size_t B, size_t S, size_t n_sl,
+                     float limit_factor, uint32_t eos_id, uint32_t *d_out_ids, uint32_t *d_out_len,
+                     float *d_align, int steps_hint, const uint32_t *d_n_sl = nullptr,
+                     float *align_out = nullptr, size_t n_sl_hint = 0, const ShortlistArgs *gen = nullptr,
+                     MergePlan *mp = nullptr) {
+  // mp (merged launch; lean path only, checked by the caller): B = the launch's global sentences, n_sl = the widest job's
+  // columns (0 = full vocabulary for every sub-batch); d_ids / d_lengths / d_shortlist / d_out_* / d_align are not used
+  // gen (with d_n_sl, lean path, 64-row encoder): the shortlist is generated inside the encoder launch
+  // n_sl_hint (with d_n_sl): what the host expects the device-side shortlist size to be (the size of
+  // this context's previous generated shortlist): tuning decisions only
+  // align_out != nullptr (persistent decoder only): d_align is a staging buffer in device memory and
+  // the decoder copies each sentence's rows from there to align_out when its loop ends (see
+  // FusedDecodeArgs::align_out)
+  // d_n_sl != nullptr: the shortlist was generated on this stream; its size is on
+  // the device and n_sl is only the capacity of d_shortlist (persistent kernels only)
+  const slimt_hip_model *m = c->model;
+  // Model.cc:144-161: the first step is unconditional (one token is always recorded), the
+  // loop then runs while i < (size_t)(limit_factor * S): at least one output column
+  const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
+  const bool lean = persistent_path(c, S);
+  // R decoder rows over the B sources: B, but in a fan-out call (never lean, never merged). The caller's outputs, the
+  // per-call options and every decoder workspace are per row; ids, lengths, the encoder and the K / V per source.
+  const CallState &call = c->call;
+  const size_t R = call.fanout ? (size_t)call.rows : B;
+  if (call.consensus) {  // (a fan-out call; the selection runs behind the last step, in decode_stepwise)
+    if (!call.fanout || !call.cs_dev_best || !call.cs_dev_util) return fail(-1, "consensus: not a fan-out call");
+    if (Tmax > (size_t)SLIMT_HIP_CONSENSUS_MAX_T)
+      return fail(-1, "consensus: the call's Tmax %zu exceeds %d", Tmax, SLIMT_HIP_CONSENSUS_MAX_T);
+  }
+  // The K/V cache form (launch_choice.h, kv_cache_form): packed where the persistent pair has it for this shape and S.
+  KvFormIn form;
+  form.D = m->D; form.F = m->F; form.H = m->H;
+  form.kv_format = m->kv_format;
+  form.S = S;
+  form.encode_rows = c->encode_rows;
+  form.decode_mode = c->decode_mode;
+  form.lean = lean;
+  form.fused_encode_ok = fused_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S);
+  form.tall_encode_ok = tall_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S);
+  form.long_encode_ok = long_encode_supported(m->D, m->F, m->H, m->Le, m->Ld, (int)S);
+  form.decode_packed_ok = fused_decode_packed_supported(m->D, m->F, m->H, m->Ld);
+  form.decode_mid_ok = fused_decode_mid_supported(m->D, m->F, m->H, m->Ld);
+  form.decode_long24_ok = fused_decode_long24_supported(m->D, m->F, m->H, m->Ld);
+  const bool kv_packed = kv_cache_form(form).packed;
+  // The tight form's centres (engine.h, kv_centre): the first batch of enough rows that could take the form is cached as
+  // f32 instead, and its column means become the centres (behind the encoder, on this stream).
+  ClaimGuard claim(c->model);
+  if (kv_packed && c->model->kv_centre_state.load(std::memory_order_acquire) == 0 && kv_calibration_rows(B, S) &&
+      kv_tight_shape(c, (int)S, kv_tight_writer(c, (int)B, (int)S)))
+    claim.take();
+  const bool calibrate = claim.armed;
+  const bool kv24 = kv_packed && !calibrate;
+  // One thread at a time queues a persistent translate (a few runtime calls, ~50 us): the runtime
+  // serialises launches internally anyway, and a dozen worker threads contending inside it take
+  // far longer per call than the same calls made one after the other (Service, 10 workers: 2.1 ms
+  // per launch call against 0.05 ms with two).
+  std::unique_lock<std::mutex> submit(c->model->submit_mu, std::defer_lock);
+  StageClock clk;
+  if (lean && env().submit_lock) submit.lock();
+  clk.lap(2);
+  if (env().host_timing) g_timing.calls += 1;
+  float *d_scores = nullptr;
+  RCCHK(check_call_destinations(c, R, Tmax, mp, &d_scores));
+  KvCallSlot slot;
+  if (lean) {
+    RCCHK(encode_lean_for_translate(c, d_ids, d_lengths, d_shortlist, B, S, n_sl, d_n_sl, gen, mp, kv24, calibrate, slot));
+    clk.lap(1);
+  } else {
+    RCCHK(encode_stagewise_for_translate(c, d_ids, &d_lengths, &d_shortlist, B, S, R, Tmax, n_sl, d_out_ids, d_out_len, d_align));
+  }
+  if (!n_sl) d_shortlist = nullptr;
+  if (fused_decoder_allowed(c) && fused_decode_supported(m->D, m->F, m->H, m->Ld)) {
+    const bool scored = call.scored || call.forced || call.sampled;
+    const size_t n_expected = d_n_sl && n_sl_hint ? n_sl_hint : mp ? (size_t)(n_sl ? mp->max_N : m->V) : (size_t)output_layer(c).w.N;
+    const FusedTiling tiling = choose_fused_tiling(c, B, S, kv24, scored, mp != nullptr, n_expected);
+    FusedDecodeArgs f;
+    RCCHK(fill_fused_decode_args(c, f, tiling, B, S, Tmax, steps_hint, d_lengths, d_shortlist, d_n_sl, eos_id, d_out_ids, d_out_len,
+                                 d_align, align_out, d_scores, kv24, mp));
+    return admit_and_launch_fused(c, f, B, S, kv24, slot, clk);
+  }
+  return decode_stepwise(c, B, S, R, Tmax, d_shortlist, eos_id, d_out_ids, d_out_len, d_align, d_scores, steps_hint, mp != nullptr);
+}
+
 }  // namespace
 
 namespace {
@@ -2984,20 +3096,69 @@ size_t align_staging_bytes(const slimt_hip_ctx *ctx, size_t B, size_t S, size_t 
   return std::max(worst <= ((size_t)256 << 20) ? worst : 0, B * Tmax * S * 4);
 }
 
-// the device view of a pinned host allocation (hipHostMalloc / slimt_hip_host_alloc), else nullptr
-void *host_device_view(const void *p) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
+constexpr uint64_t kShortlistMagic = 0xF11A48D5013417F5ull;  // Shortlist.hh:40
+
+// hash_combine over uint64 words from header.frequent on (Shortlist.cc:66-73,
+// Utils.hh:47-67 with libstdc++'s identity std::hash<uint64_t>)
+uint64_t shortlist_checksum(const unsigned char *blob, size_t size) {
+  uint64_t seed = 0;
+  for (size_t i = 16; i + 8 <= size; i += 8) {
+    uint64_t v;
+    std::memcpy(&v, blob + i, 8);
+    seed ^= v + 0x9e3779b9ull + (seed << 6) + (seed >> 2);
   }
-  return a.type == hipMemoryTypeHost ? a.devicePointer : nullptr;
+  return seed;
 }
 
-// (below, with the lexical shortlist)
-int upload_shortlist_if_changed(slimt_hip_ctx *ctx, const uint32_t *ids, size_t n);
+// bitmaps start zeroed and every generate call leaves them zeroed
+int shortlist_scratch(DevBuf &buf, const slimt_hip_shortlist *sl, hipStream_t st) {
+  const size_t need = shortlist_scratch_bytes((int)sl->source_vocab, (int)sl->target_vocab);
+  if (buf.bytes < need) {
+    HIPCHK(buf.reserve(need));
+    HIPCHK(hipMemsetAsync(buf.p, 0, buf.bytes, st));
+  }
+  return 0;
+}
+
+void shortlist_args(const slimt_hip_shortlist *sl, const uint32_t *d_ids, const uint32_t *d_len,
+                    size_t B, size_t S, uint32_t *d_out, uint32_t *d_n, ShortlistArgs &a) {
+  a.w2o = sl->w2o.as<unsigned long long>();
+  a.lists = sl->lists.as<uint32_t>();
+  a.frequent = sl->frequent;
+  a.shared = sl->shared ? 1 : 0;
+  a.src_vocab = (int)sl->source_vocab;
+  a.tgt_vocab = (int)sl->target_vocab;
+  a.ids = d_ids;
+  a.lengths = d_len;
+  a.B = (int)B;
+  a.S = (int)S;
+  a.out = d_out;
+  a.n_out = d_n;
+}
+
+// A caller's host shortlist of n ids in ctx->shortlist, where the kernels read it.
+int upload_shortlist_if_changed(slimt_hip_ctx *ctx, const uint32_t *ids, size_t n) {
+  if (!n || (ctx->sl_host.size() == n && std::memcmp(ctx->sl_host.data(), ids, n * 4) == 0)) return 0;
+  hipStream_t st = ctx->stream;
+  ctx->sl_host.clear();  // until the upload has succeeded the device copy is nobody's
+  HIPCHK(hipMemcpyAsync(ctx->shortlist.p, ids, n * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));  // (the caller's array may be pageable: the copy is staged; done once per shortlist)
+  ctx->sl_host.assign(ids, ids + n);
+  return 0;
+}
+
+// The generator's arguments for the batch's list in ctx->shortlist, its count in ctx->n_sl_dev, on the context's scratch.
+// n_lists > 1 (a merged launch, one list per sub-batch inside the encoder launch): that many counts, and no scratch -- the
+// bitmaps in global memory are the two-kernel generator's. Launching and reading the count back are the caller's.
 int generated_shortlist_args(slimt_hip_ctx *ctx, const slimt_hip_shortlist *sl, const uint32_t *d_ids, const uint32_t *d_len,
-                             size_t B, size_t S, ShortlistArgs &a, size_t n_lists = 1);
+                             size_t B, size_t S, ShortlistArgs &a, size_t n_lists = 1) {
+  ctx->sl_host.clear();  // ctx->shortlist no longer holds what translate_host uploaded last
+  HIPCHK(ctx->n_sl_dev.reserve(4 * n_lists));
+  if (n_lists == 1) RCCHK(shortlist_scratch(ctx->sl_scratch, sl, ctx->stream));
+  shortlist_args(sl, d_ids, d_len, B, S, ctx->shortlist.as<uint32_t>(), ctx->n_sl_dev.as<uint32_t>(), a);
+  if (n_lists == 1) a.scratch = ctx->sl_scratch.as<uint32_t>();
+  return 0;
+}
 
 int check_generator(const slimt_hip_ctx *ctx, const slimt_hip_shortlist *sl) {
   const slimt_hip_model *m = ctx->model;
@@ -3028,7 +3189,7 @@ int translate_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const uint3
   // With the 64-row encoder the generator runs INSIDE the encoder launch, by the workgroup that starts first
   // (encode_tall.hip): as a launch of its own -- one workgroup -- it waited ~0.5 ms for a CU behind the
   // other batches' persistent kernels (47 us alone). Same ids, same count, same consumers.
-  static const bool fold = !(std::getenv("SLIMT_SHORTLIST_FOLD") && std::getenv("SLIMT_SHORTLIST_FOLD")[0] == '0');
+  const bool fold = env().shortlist_fold;
   // (the persistent encoders of sentences up to 64 tokens: 64-row / 32-row tiles at D = 256, D = 512; the
   // per-sentence kernel for 65..128 tokens keeps the two-kernel generator)
   const bool in_launch = fold && lean && fused_encoder_chosen(ctx, (int)B, (int)S) &&
@@ -3431,8 +3592,7 @@ int build_merge_plan(const slimt_hip_ctx *c, const slimt_hip_batch *b, size_t n,
   mp.dense = true;
   for (size_t j = 1; j < n; ++j)
     if (b[j].shortlist != b[0].shortlist || b[j].n_shortlist != b[0].n_shortlist) mp.dense = false;
-  static const bool no_dense = std::getenv("SLIMT_MERGE_DENSE") && std::getenv("SLIMT_MERGE_DENSE")[0] == '0';  // A/B
-  if (no_dense) mp.dense = false;
+  if (!env().merge_dense) mp.dense = false;  // A/B
   if (mp.dense) align = 1;
   size_t stage_at = 0;  // floats of alignment staging handed out so far (16-byte pieces: the decoder copies whole quads)
   for (size_t j = 0; j < n; ++j) {
@@ -3579,15 +3739,17 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
     any_align = any_align || b.align != nullptr;
     rows += b.B;  // (one shortlist for all: the sub-batches follow each other densely)
   }
-  merged = merged && rows <= ctx->max_B && rows * S <= ctx->max_M && merge_supported(ctx, rows, S);
-  if (!merged) {
+  auto fits = [&](size_t r) { return r <= ctx->max_B && r * S <= ctx->max_M; };
+  auto batch_by_batch = [&]() {
     for (size_t j = 0; j < n_batches; ++j) {
       const slimt_hip_batch &b = batches[j];
       RCCHK(translate_host(ctx, nullptr, opt.user[j], b.src_ids, b.lengths, b.B, b.S ? b.S : S, b.shortlist, b.n_shortlist,
                            limit_factor, eos_id, b.out_ids, b.out_len, b.align, false));
     }
     return 0;
-  }
+  };
+  merged = merged && fits(rows) && merge_supported(ctx, rows, S);
+  if (!merged) return batch_by_batch();
   const size_t n_sl = batches[0].n_shortlist;
   const uint32_t *shortlist = batches[0].shortlist;
   if (n_sl > (size_t)m->V) return fail(-1, "shortlist larger than the vocabulary");
@@ -3601,6 +3763,9 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
     dev[j].n_shortlist = n_sl;
   }
   RCCHK(build_merge_plan(ctx, dev, n_batches, S, Tmax, limit_factor, 0, any_align ? ctx->align.as<float>() : nullptr, mp, rows));
+  // (SLIMT_MERGE_DENSE=0: the plan counted its rows again, every sub-batch from a multiple of kMergeAlign -- more than the
+  // dense sum checked above; a launch that no longer fits the workspace goes batch by batch, nothing of it is queued yet)
+  if (!fits(rows) || !merge_supported(ctx, rows, S)) return batch_by_batch();
   RCCHK(stage_options(ctx, batches, n_batches, S, limit_factor, opt.user.data(), mp.opt));
   return translate_device(ctx, dev[0].src_ids, dev[0].lengths, dev[0].shortlist, rows, S, (size_t)mp.max_N, limit_factor, eos_id,
                           dev[0].out_ids, dev[0].out_len, any_align ? ctx->align.as<float>() : nullptr, (int)Tmax, nullptr,
@@ -3697,21 +3862,6 @@ extern "C" int slimt_hip_decode_begin(slimt_hip_ctx *ctx, const uint32_t *shortl
 }
 
 static int decode_step_impl(slimt_hip_ctx *ctx, const uint32_t *prev, const float *states_in,
-                            float *logits, float *attn, float *states);
-
-extern "C" int slimt_hip_decode_step(slimt_hip_ctx *ctx, const uint32_t *prev, float *logits,
-                                     float *attn, float *states) {
-  return decode_step_impl(ctx, prev, nullptr, logits, attn, states);
-}
-
-extern "C" int slimt_hip_decode_step_states(slimt_hip_ctx *ctx, const uint32_t *prev,
-                                            const float *states_in, float *logits, float *attn,
-                                            float *states_out) {
-  if (!states_in) return fail(-1, "null argument");
-  return decode_step_impl(ctx, prev, states_in, logits, attn, states_out);
-}
-
-static int decode_step_impl(slimt_hip_ctx *ctx, const uint32_t *prev, const float *states_in,
                             float *logits, float *attn, float *states) {
   if (!ctx || !logits) return fail(-1, "null argument");
   if (!ctx->decode_ready) return fail(-1, "decode_step before decode_begin");
@@ -3748,6 +3898,18 @@ static int decode_step_impl(slimt_hip_ctx *ctx, const uint32_t *prev, const floa
     HIPCHK(hipMemcpyAsync(states, ctx->state.p, (size_t)m->Ld * B * D * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return 0;
+}
+
+extern "C" int slimt_hip_decode_step(slimt_hip_ctx *ctx, const uint32_t *prev, float *logits,
+                                     float *attn, float *states) {
+  return decode_step_impl(ctx, prev, nullptr, logits, attn, states);
+}
+
+extern "C" int slimt_hip_decode_step_states(slimt_hip_ctx *ctx, const uint32_t *prev,
+                                            const float *states_in, float *logits, float *attn,
+                                            float *states_out) {
+  if (!states_in) return fail(-1, "null argument");
+  return decode_step_impl(ctx, prev, states_in, logits, attn, states_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -3815,74 +3977,6 @@ extern "C" int slimt_hip_debug_decode_stamps(slimt_hip_ctx *ctx, int step, uint6
 // ---------------------------------------------------------------------------
 // lexical shortlist (slimt/Shortlist.{hh,cc})
 // ---------------------------------------------------------------------------
-namespace {
-
-constexpr uint64_t kShortlistMagic = 0xF11A48D5013417F5ull;  // Shortlist.hh:40
-
-// hash_combine over uint64 words from header.frequent on (Shortlist.cc:66-73,
-// Utils.hh:47-67 with libstdc++'s identity std::hash<uint64_t>)
-uint64_t shortlist_checksum(const unsigned char *blob, size_t size) {
-  uint64_t seed = 0;
-  for (size_t i = 16; i + 8 <= size; i += 8) {
-    uint64_t v;
-    std::memcpy(&v, blob + i, 8);
-    seed ^= v + 0x9e3779b9ull + (seed << 6) + (seed >> 2);
-  }
-  return seed;
-}
-
-// bitmaps start zeroed and every generate call leaves them zeroed
-int shortlist_scratch(DevBuf &buf, const slimt_hip_shortlist *sl, hipStream_t st) {
-  const size_t need = shortlist_scratch_bytes((int)sl->source_vocab, (int)sl->target_vocab);
-  if (buf.bytes < need) {
-    HIPCHK(buf.reserve(need));
-    HIPCHK(hipMemsetAsync(buf.p, 0, buf.bytes, st));
-  }
-  return 0;
-}
-
-void shortlist_args(const slimt_hip_shortlist *sl, const uint32_t *d_ids, const uint32_t *d_len,
-                    size_t B, size_t S, uint32_t *d_out, uint32_t *d_n, ShortlistArgs &a) {
-  a.w2o = sl->w2o.as<unsigned long long>();
-  a.lists = sl->lists.as<uint32_t>();
-  a.frequent = sl->frequent;
-  a.shared = sl->shared ? 1 : 0;
-  a.src_vocab = (int)sl->source_vocab;
-  a.tgt_vocab = (int)sl->target_vocab;
-  a.ids = d_ids;
-  a.lengths = d_len;
-  a.B = (int)B;
-  a.S = (int)S;
-  a.out = d_out;
-  a.n_out = d_n;
-}
-
-// A caller's host shortlist of n ids in ctx->shortlist, where the kernels read it.
-int upload_shortlist_if_changed(slimt_hip_ctx *ctx, const uint32_t *ids, size_t n) {
-  if (!n || (ctx->sl_host.size() == n && std::memcmp(ctx->sl_host.data(), ids, n * 4) == 0)) return 0;
-  hipStream_t st = ctx->stream;
-  ctx->sl_host.clear();  // until the upload has succeeded the device copy is nobody's
-  HIPCHK(hipMemcpyAsync(ctx->shortlist.p, ids, n * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));  // (the caller's array may be pageable: the copy is staged; done once per shortlist)
-  ctx->sl_host.assign(ids, ids + n);
-  return 0;
-}
-
-// The generator's arguments for the batch's list in ctx->shortlist, its count in ctx->n_sl_dev, on the context's scratch.
-// n_lists > 1 (a merged launch, one list per sub-batch inside the encoder launch): that many counts, and no scratch -- the
-// bitmaps in global memory are the two-kernel generator's. Launching and reading the count back are the caller's.
-int generated_shortlist_args(slimt_hip_ctx *ctx, const slimt_hip_shortlist *sl, const uint32_t *d_ids, const uint32_t *d_len,
-                             size_t B, size_t S, ShortlistArgs &a, size_t n_lists) {
-  ctx->sl_host.clear();  // ctx->shortlist no longer holds what translate_host uploaded last
-  HIPCHK(ctx->n_sl_dev.reserve(4 * n_lists));
-  if (n_lists == 1) RCCHK(shortlist_scratch(ctx->sl_scratch, sl, ctx->stream));
-  shortlist_args(sl, d_ids, d_len, B, S, ctx->shortlist.as<uint32_t>(), ctx->n_sl_dev.as<uint32_t>(), a);
-  if (n_lists == 1) a.scratch = ctx->sl_scratch.as<uint32_t>();
-  return 0;
-}
-
-}  // namespace
-
 extern "C" int slimt_hip_shortlist_create(const void *blob, size_t blob_size, size_t source_vocab,
                                           size_t target_vocab, int shared, int check, int device,
                                           slimt_hip_shortlist **out) {
@@ -4066,7 +4160,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
     rows += (dev[j].B + kMergeTile - 1) / kMergeTile * kMergeTile;
     any_align = any_align || dev[j].align != nullptr;
   }
-  static const bool fold = !(std::getenv("SLIMT_SHORTLIST_FOLD") && std::getenv("SLIMT_SHORTLIST_FOLD")[0] == '0');
+  const bool fold = env().shortlist_fold;
   const bool merged = n > 1 && n <= (size_t)kMaxMerge && !ctx->call.truncated && S <= ctx->max_S && rows <= ctx->max_B && rows * S <= ctx->max_M &&
                       merge_supported(ctx, rows, S) && fold &&
                       shortlist_in_launch_lds_bytes((int)sl->source_vocab, (int)sl->target_vocab) <= 64 * 1024;
