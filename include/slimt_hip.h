@@ -832,6 +832,49 @@ int slimt_hip_consensus_select_device(slimt_hip_ctx *ctx, const uint32_t *d_ids,
  * given, max_order or beta2 out of range, a NULL array. An armed fan-out call whose Tmax exceeds SLIMT_HIP_CONSENSUS_MAX_T is refused with a message. */
 int slimt_hip_ctx_set_fanout_consensus(slimt_hip_ctx *ctx, int max_order, int beta2, uint32_t *best, double *utility);
 
+/* ---- consensus over unit rows: the character n-gram F (chrF) as the utility -- */
+/* The same selection with the rows compared by what their ids spell. A UNIT TABLE maps a vocabulary id to a sequence of
+ * 32-bit units, opaque to the library (for chrF: a piece's code points with the whitespace removed): unit_off [V + 1] u32,
+ * non-decreasing from unit_off[0] = 0, and units [unit_off[V]] u32; id v < V expands to units[unit_off[v] .. unit_off[v + 1]),
+ * possibly to nothing. The UNIT ROW of row c is the concatenation of the expansions of ids[c][t] for t < min(len[c], T), and
+ * u_c is its length. The definition above holds word for word with these changes:
+ *   - the g-grams of row c are the windows of its unit row; there are c_g(c) = max(u_c - g + 1, 0);
+ *   - a row COMPETES when u_c > 0: a row whose tokens all expand to nothing (EOS only) does not;
+ *   - G = max_order lies in 1..SLIMT_HIP_CONSENSUS_UNITS_MAX_ORDER (6: chrF's orders).
+ * Clipped counts over full 32-bit units, one IEEE double division per order, orders added in ascending g from +0.0,
+ * references in ascending row index, best the lowest row of the largest utility (0xFFFFFFFF for none), beta2, at most
+ * SLIMT_HIP_CONSENSUS_MAX_ROWS rows per source, T <= SLIMT_HIP_CONSENSUS_MAX_T and N <= 65536 are unchanged: host and device
+ * agree bit for bit. With max_order 6 and beta2 4 over such a table, U(h, r) is sacreBLEU's sentence chrF of h against the
+ * reference r (as a fraction, effective order on). New bounds: a unit row of at most SLIMT_HIP_CONSENSUS_MAX_UNITS units, an
+ * expansion of at most SLIMT_HIP_CONSENSUS_MAX_EXPANSION units per id.
+ * slimt_hip_consensus_select_units takes host pointers, is stateless and waits, like slimt_hip_consensus_select; the table
+ * is uploaded for the call. It refuses, with a message, what that call refuses and: a table whose offsets do not start at 0
+ * or decrease, an expansion over the limit, an id >= V among a row's tokens, a unit row over the limit.
+ * slimt_hip_model_set_consensus_units checks a table in the same way, uploads it once for the model's device calls and
+ * replaces an earlier one (it waits for the device: no call that reads the old table may be in flight afterwards);
+ * unit_off == NULL removes it. V must be the model's vocabulary (the rows of its embedding).
+ * slimt_hip_consensus_select_units_device runs on ctx's stream over device arrays with the model's table and is refused
+ * with a message when the model has none. Device arrays cannot be checked: row_src and len are clamped as by
+ * slimt_hip_consensus_select_device, an id >= V expands to nothing, and a source with more than SLIMT_HIP_CONSENSUS_MAX_ROWS
+ * rows or with a row over SLIMT_HIP_CONSENSUS_MAX_UNITS units gets best 0xFFFFFFFF and utility 0.0 for its rows; nothing is
+ * read or written out of bounds. The context keeps a workspace of about 5 KiB per row for it, reserved on first use. */
+#define SLIMT_HIP_CONSENSUS_UNITS_MAX_ORDER 6
+#define SLIMT_HIP_CONSENSUS_MAX_UNITS 1024
+#define SLIMT_HIP_CONSENSUS_MAX_EXPANSION 255
+int slimt_hip_consensus_select_units(const uint32_t *ids, const uint32_t *len, const uint32_t *row_src, size_t N, size_t T,
+                                     size_t B, const uint32_t *unit_off, const uint32_t *units, size_t V, int max_order,
+                                     int beta2, double *utility, uint32_t *best);
+int slimt_hip_model_set_consensus_units(slimt_hip_model *model, const uint32_t *unit_off, const uint32_t *units, size_t V);
+int slimt_hip_consensus_select_units_device(slimt_hip_ctx *ctx, const uint32_t *d_ids, const uint32_t *d_len,
+                                            const uint32_t *d_row_src, size_t N, size_t T, size_t B, int max_order, int beta2,
+                                            double *d_utility, uint32_t *d_best);
+/* slimt_hip_ctx_set_fanout_consensus with the unit rows' utility: the same slot of the context's options -- the last arming
+ * of the two wins, and either's max_order = 0 with NULL arrays disarms -- consumed and refused by the same rules (the next
+ * translate call takes it whatever its outcome; a call that is not a fan-out call fails; an armed call whose Tmax exceeds
+ * SLIMT_HIP_CONSENSUS_MAX_T is refused). Also refused, here and by the call, when the model has no unit table. Every
+ * ordinary output of the armed call has the un-armed call's bits. */
+int slimt_hip_ctx_set_fanout_consensus_units(slimt_hip_ctx *ctx, int max_order, int beta2, uint32_t *best, double *utility);
+
 /* ---- beam search with n-best output ---------------------------------------- */
 /* slimt_hip_translate over B sources with `beam` = k slots per source, 1 <= k <= SLIMT_HIP_MAX_BEAM: a fan-out call of
  * B k decoder rows (row r = b k + s belongs to source b) whose every step ends in one selection. THE CONTRACT, which a

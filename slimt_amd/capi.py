@@ -51,6 +51,8 @@ SYMBOLS = [
     "slimt_hip_translate_fanout", "slimt_hip_translate_fanout_async", "slimt_hip_translate_fanout_device",
     "slimt_hip_translate_fanout_async_generated",
     "slimt_hip_consensus_select", "slimt_hip_consensus_select_device", "slimt_hip_ctx_set_fanout_consensus",
+    "slimt_hip_consensus_select_units", "slimt_hip_model_set_consensus_units", "slimt_hip_consensus_select_units_device",
+    "slimt_hip_ctx_set_fanout_consensus_units",
     "slimt_hip_translate_beam", "slimt_hip_translate_beam_async", "slimt_hip_translate_beam_device",
     "slimt_hip_translate_beam_async_generated", "slimt_hip_beam_step",
 ]
@@ -58,6 +60,7 @@ SYMBOLS = [
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
 K_CONSENSUS = 9  # (consensus selection: slimt_hip_consensus_select_device and armed fan-out calls)
 CONSENSUS_MAX_ORDER, CONSENSUS_MAX_BETA2, CONSENSUS_MAX_ROWS, CONSENSUS_MAX_T = 4, 16, 64, 256  # (include/slimt_hip.h)
+CONSENSUS_UNITS_MAX_ORDER, CONSENSUS_MAX_UNITS, CONSENSUS_MAX_EXPANSION = 6, 1024, 255  # (unit rows: the character n-gram F)
 NO_ROW = 0xFFFFFFFF  # best[b] of a source without a competing row
 KERNEL_NAMES = {K_GEMM_ENC: "gemm_enc", K_GEMM_DEC: "gemm_dec", K_LOGITS: "logits_argmax",
                 K_ATTN_ENC: "attn_enc", K_ATTN_DEC: "attn_dec", K_SSRU: "ssru"}
@@ -297,6 +300,10 @@ def lib():
     L.slimt_hip_consensus_select.argtypes = [vp, vp, vp, sz, sz, sz, i32, i32, vp, vp]
     L.slimt_hip_consensus_select_device.argtypes = [vp, vp, vp, vp, sz, sz, sz, i32, i32, vp, vp]
     L.slimt_hip_ctx_set_fanout_consensus.argtypes = [vp, i32, i32, vp, vp]
+    L.slimt_hip_consensus_select_units.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, sz, i32, i32, vp, vp]
+    L.slimt_hip_model_set_consensus_units.argtypes = [vp, vp, vp, sz]
+    L.slimt_hip_consensus_select_units_device.argtypes = [vp, vp, vp, vp, sz, sz, sz, i32, i32, vp, vp]
+    L.slimt_hip_ctx_set_fanout_consensus_units.argtypes = [vp, i32, i32, vp, vp]
     L.slimt_hip_translate_beam.argtypes = [vp, vp, vp, sz, sz, i32, i32, vp, sz, f32, u32, vp, vp, vp, vp, vp]
     L.slimt_hip_translate_beam_async.argtypes = [vp, vp, vp, sz, sz, i32, i32, vp, sz, f32, u32, vp, vp, vp, vp, vp]
     L.slimt_hip_translate_beam_device.argtypes = [vp, vp, vp, sz, sz, i32, i32, vp, sz, f32, u32, vp, vp, vp, vp, vp, i32]
@@ -396,6 +403,33 @@ def consensus_select(ids, lengths, row_src, B: int, max_order: int = 4, beta2: i
     utility, best = np.zeros(N, np.float64), np.zeros(int(B), np.uint32)
     _chk(lib().slimt_hip_consensus_select(_p(ids), _p(lengths), _p(row_src), N, T, int(B), int(max_order), int(beta2),
                                           _p(utility), _p(best)))
+    return utility, best
+
+
+def _unit_table(unit_off, units):
+    """(unit_off uint32 [V + 1], units uint32, V) of a unit table (include/slimt_hip.h), shapes checked"""
+    unit_off = np.ascontiguousarray(unit_off, dtype=np.uint32)
+    units = np.ascontiguousarray(units, dtype=np.uint32)
+    if unit_off.ndim != 1 or unit_off.size < 1 or units.ndim != 1 or units.size < int(unit_off[-1]):
+        raise ValueError("unit table: unit_off [V + 1] and units [unit_off[V]] expected, got %s, %s" % (unit_off.shape, units.shape))
+    return unit_off, units, unit_off.size - 1
+
+
+def consensus_select_units(ids, lengths, row_src, B: int, unit_off, units, max_order: int = 6, beta2: int = 4):
+    """slimt_hip_consensus_select_units: consensus_select over the rows' unit rows -- each id expanded through the table
+    unit_off [V + 1] / units (text.Vocabulary.consensus_units: a piece's characters), n-gram orders 1..max_order <= 6: with
+    the defaults the utility is the mean chrF against the source's other rows. Returns (utility float64 [N], best uint32 [B])."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    row_src = np.ascontiguousarray(row_src, dtype=np.uint32)
+    if ids.ndim != 2 or lengths.shape != ids.shape[:1] or row_src.shape != ids.shape[:1]:
+        raise ValueError("consensus_select_units: ids [N, T], lengths [N] and row_src [N] expected, got %s, %s, %s"
+                         % (ids.shape, lengths.shape, row_src.shape))
+    unit_off, units, V = _unit_table(unit_off, units)
+    N, T = ids.shape
+    utility, best = np.zeros(N, np.float64), np.zeros(int(B), np.uint32)
+    _chk(lib().slimt_hip_consensus_select_units(_p(ids), _p(lengths), _p(row_src), N, T, int(B), _p(unit_off), _p(units), V,
+                                                int(max_order), int(beta2), _p(utility), _p(best)))
     return utility, best
 
 
@@ -659,6 +693,16 @@ class Model:
         """Decode mode 0: 8 or 4 sentences per decoder workgroup while CUs would idle (default on)."""
         _chk(lib().slimt_hip_model_set_adaptive_decoder_rows(self.h, 1 if on else 0))
 
+    def set_consensus_units(self, unit_off, units=None):
+        """slimt_hip_model_set_consensus_units: the unit table (unit_off uint32 [V + 1], units) of this model's consensus
+        calls over unit rows -- checked, uploaded once, replacing an earlier one; unit_off=None removes it. V must be the
+        model's vocabulary."""
+        if unit_off is None:
+            _chk(lib().slimt_hip_model_set_consensus_units(self.h, None, None, 0))
+            return
+        unit_off, units, V = _unit_table(unit_off, units if units is not None else np.zeros(0, np.uint32))
+        _chk(lib().slimt_hip_model_set_consensus_units(self.h, _p(unit_off), _p(units), V))
+
     def set_decoder_budget(self, workgroups: int):
         """Admission of persistent decoders: ~`workgroups` decoder workgroups at a time (0 = no limit)."""
         _chk(lib().slimt_hip_model_set_decoder_budget(self.h, workgroups))
@@ -807,11 +851,12 @@ class Context:
         `truncation=(top_k, top_p)` beside `sampling=` and do this."""
         _chk(lib().slimt_hip_ctx_set_sampling_truncation(self.h, int(top_k), float(top_p)))
 
-    def set_fanout_consensus(self, max_order: int, beta2: int, best, utility):
+    def set_fanout_consensus(self, max_order: int, beta2: int, best, utility, units: bool = False):
         """slimt_hip_ctx_set_fanout_consensus: arm the consensus selection for the NEXT fan-out call -- best [B] uint32 and
         utility [N] float64, as numpy arrays (host calls; kept alive here until the next arming) or addresses (ints: device
         pointers for the device call). max_order = 0 with no arrays disarms. The translate_fanout* wrappers take
-        `consensus=` and do this."""
+        `consensus=` and do this. units: slimt_hip_ctx_set_fanout_consensus_units -- the selection over the rows' unit
+        rows through the model's table (Model.set_consensus_units); the same slot, the last arming wins."""
         keep, addr = [], []
         for a, dt in ((best, np.uint32), (utility, np.float64)):
             if isinstance(a, np.ndarray):
@@ -822,13 +867,28 @@ class Context:
             else:
                 addr.append(int(a) if a else 0)
         self._consensus_keep = keep
-        _chk(lib().slimt_hip_ctx_set_fanout_consensus(self.h, int(max_order), int(beta2), C.c_void_p(addr[0] or None),
-                                                      C.c_void_p(addr[1] or None)))
+        arm = lib().slimt_hip_ctx_set_fanout_consensus_units if units else lib().slimt_hip_ctx_set_fanout_consensus
+        _chk(arm(self.h, int(max_order), int(beta2), C.c_void_p(addr[0] or None), C.c_void_p(addr[1] or None)))
+
+    def set_fanout_consensus_units(self, max_order: int, beta2: int, best, utility):
+        """slimt_hip_ctx_set_fanout_consensus_units (set_fanout_consensus with units=True)"""
+        self.set_fanout_consensus(max_order, beta2, best, utility, units=True)
+
+    @staticmethod
+    def _consensus_kind(consensus):
+        """a wrapper's consensus= as (units, the rest): (G, beta2, ...) and ("tokens", G, beta2, ...) select over the token
+        rows, ("units", G, beta2, ...) over the unit rows"""
+        if isinstance(consensus[0], str):
+            if consensus[0] not in ("tokens", "units"):
+                raise ValueError("consensus: the kind is 'tokens' or 'units', not %r" % (consensus[0],))
+            return consensus[0] == "units", tuple(consensus[1:])
+        return False, tuple(consensus)
 
     def _arm_consensus(self, consensus, B: int, N: int):
-        """arms a host fan-out call's consensus=(max_order, beta2); returns its (best [B], utility [N]) arrays"""
+        """arms a host fan-out call's consensus=([kind,] max_order, beta2); returns its (best [B], utility [N]) arrays"""
+        units, (order, beta2) = self._consensus_kind(consensus)
         best, utility = np.full(B, NO_ROW, np.uint32), np.zeros(N, np.float64)
-        self.set_fanout_consensus(int(consensus[0]), int(consensus[1]), best, utility)
+        self.set_fanout_consensus(int(order), int(beta2), best, utility, units=units)
         return best, utility
 
     @staticmethod
@@ -1000,7 +1060,9 @@ class Context:
         (+ scores [N,Tmax]). prefix, sampling, truncation: as in translate(), shaped by N. Every row is bit for bit its row
         of translate() on ids[row_src], lengths[row_src] in decode mode 1.
         consensus: (max_order, beta2) -- the call also selects each source's consensus row on the device
-        (slimt_hip_ctx_set_fanout_consensus) and returns, last, best [B] uint32 and utility [N] float64."""
+        (slimt_hip_ctx_set_fanout_consensus) and returns, last, best [B] uint32 and utility [N] float64. With a kind in
+        front, ("units", max_order, beta2), the rows are compared by their unit rows (the character n-gram F, orders up to
+        6) through the model's unit table; ("tokens", ...) is the default."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
         row_src = np.ascontiguousarray(row_src, dtype=np.uint32)
@@ -1035,7 +1097,8 @@ class Context:
         """slimt_hip_translate_fanout_async[_generated] on (ids, lengths, row_src, out_ids, out_len, align | None) host arrays
         (already filled; those of fanout_buffers() are pinned); synchronize() before reading the outputs. scores: a float32
         [N, Tmax] array; prefix, sampling, truncation: as in translate_async(), shaped by N.
-        consensus: (max_order, beta2) -- returns (best [B] uint32, utility [N] float64), filled like the other outputs."""
+        consensus: ([kind,] max_order, beta2), as in translate_fanout() -- returns (best [B] uint32, utility [N] float64),
+        filled like the other outputs."""
         ids, lengths, row_src, out_ids, out_len, align = bufs
         for a in (ids, lengths, row_src, out_ids, out_len):
             if a.dtype != np.uint32 or not a.flags.c_contiguous:
@@ -1080,8 +1143,8 @@ class Context:
                                 d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None,
                                 truncation=None, consensus=None):
         """slimt_hip_translate_fanout_device: device pointers (ints) in and out, like translate_device(); d_row_src [N]
-        uint32 (a value >= B is taken as B - 1), outputs and options shaped by N. consensus: (max_order, beta2, d_best,
-        d_utility) with the device pointers of best [B] uint32 and utility [N] float64."""
+        uint32 (a value >= B is taken as B - 1), outputs and options shaped by N. consensus: ([kind,] max_order, beta2,
+        d_best, d_utility) with the device pointers of best [B] uint32 and utility [N] float64."""
         vp = C.c_void_p
         if scores:  # (armed right before the call that takes it)
             self.set_scores([scores])
@@ -1092,7 +1155,8 @@ class Context:
         if truncation is not None:
             self.set_sampling_truncation(*truncation)
         if consensus is not None:
-            self.set_fanout_consensus(*consensus)
+            units, rest = self._consensus_kind(consensus)
+            self.set_fanout_consensus(*rest, units=units)
         _chk(lib().slimt_hip_translate_fanout_device(self.h, vp(d_ids), vp(d_lengths), B, S, vp(d_row_src), N,
                                                      vp(d_shortlist) if n_shortlist else None, n_shortlist, limit_factor,
                                                      eos_id, vp(d_out_ids), vp(d_out_len), vp(d_align) if d_align else None,
@@ -1461,6 +1525,14 @@ class Context:
         vp = C.c_void_p
         _chk(lib().slimt_hip_consensus_select_device(self.h, vp(d_ids), vp(d_len), vp(d_row_src), N, T, B, int(max_order),
                                                      int(beta2), vp(d_utility), vp(d_best)))
+
+    def consensus_select_units_device(self, d_ids: int, d_len: int, d_row_src: int, N: int, T: int, B: int, max_order: int,
+                                      beta2: int, d_utility: int, d_best: int):
+        """slimt_hip_consensus_select_units_device: consensus_select_units over device arrays on this context's stream,
+        through the model's unit table (Model.set_consensus_units)."""
+        vp = C.c_void_p
+        _chk(lib().slimt_hip_consensus_select_units_device(self.h, vp(d_ids), vp(d_len), vp(d_row_src), N, T, B, int(max_order),
+                                                           int(beta2), vp(d_utility), vp(d_best)))
 
     def translate_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int,
                          n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int,

@@ -770,6 +770,7 @@ void model_free(slimt_hip_model *m) {
     free_attn(L.attn); free_affine(L.ffn1); free_affine(L.ffn2); free_ln(L.ffn_ln);
   }
   m->wemb.release(); m->out_raw.release(); m->out_bias.release();
+  m->cu_off.release(); m->cu_units.release();
   free_affine(m->out_full);
   for (hipEvent_t ev : m->gate_ev) (void)hipEventDestroy(ev);
   m->gate_ev.clear();
@@ -1296,7 +1297,7 @@ void ctx_free(slimt_hip_ctx *c) {
                     &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->tr_logits, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag,
-                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage, &c->cs_stage, &c->bm_state, &c->bm_slots, &c->bm_hist, &c->bm_align, &c->bm_stage};
+                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage, &c->cs_stage, &c->cu_ws, &c->bm_state, &c->bm_slots, &c->bm_hist, &c->bm_align, &c->bm_stage};
   for (auto *b : bufs) b->release();
   free_affine(c->out_sl);
   if (c->n_finished_host) (void)hipHostFree(c->n_finished_host);
@@ -1561,6 +1562,26 @@ extern "C" int slimt_hip_ctx_set_fanout_consensus(slimt_hip_ctx *ctx, int max_or
   if (!ctx) return fail(-1, "null argument");
   ctx->armed.cs_order = max_order;  // (0: nothing armed)
   ctx->armed.cs_beta2 = beta2;
+  ctx->armed.cs_units = false;
+  ctx->armed.cs_best = best;
+  ctx->armed.cs_util = utility;
+  return 0;
+}
+
+extern "C" int slimt_hip_ctx_set_fanout_consensus_units(slimt_hip_ctx *ctx, int max_order, int beta2, uint32_t *best, double *utility) {
+  // (the values first, like the temperature; the same slot as slimt_hip_ctx_set_fanout_consensus: the last arming wins)
+  if (max_order == 0 && (best || utility)) return fail(-1, "consensus units: max_order 0 disarms and takes no arrays");
+  if (max_order < 0 || max_order > SLIMT_HIP_CONSENSUS_UNITS_MAX_ORDER)
+    return fail(-1, "consensus units: max_order %d is not in 1..%d", max_order, SLIMT_HIP_CONSENSUS_UNITS_MAX_ORDER);
+  if (max_order && (beta2 < 1 || beta2 > SLIMT_HIP_CONSENSUS_MAX_BETA2))
+    return fail(-1, "consensus units: beta2 %d is not in 1..%d", beta2, SLIMT_HIP_CONSENSUS_MAX_BETA2);
+  if (max_order && (!best || !utility)) return fail(-1, "consensus units: best or utility is NULL");
+  if (!ctx) return fail(-1, "null argument");
+  if (max_order && !ctx->model->cu_off.p)
+    return fail(-1, "consensus units: the model has no unit table (slimt_hip_model_set_consensus_units)");
+  ctx->armed.cs_order = max_order;  // (0: nothing armed)
+  ctx->armed.cs_beta2 = beta2;
+  ctx->armed.cs_units = max_order != 0;
   ctx->armed.cs_best = best;
   ctx->armed.cs_util = utility;
   return 0;
@@ -1868,7 +1889,10 @@ struct CallOptions {
     }
     if (a.cs_order > 0) {
       if (!fanout) return fail(-1, "consensus: armed on a translate call that is not a fan-out call (slimt_hip_translate_fanout*)");
+      if (a.cs_units && !c->model->cu_off.p)  // (removed since the arming)
+        return fail(-1, "consensus units: the model has no unit table (slimt_hip_model_set_consensus_units)");
       call.consensus = true;
+      call.cs_units = a.cs_units;
       call.cs_order = a.cs_order;
       call.cs_beta2 = a.cs_beta2;
       call.cs_best = a.cs_best;
@@ -2889,7 +2913,25 @@ int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax,
                                              c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs, &ss);
     if (he != hipSuccess) rc = fail((int)he, "final record: %s", hipGetErrorString(he));
   }
-  if (!rc && call.consensus) {  // the selection over the rows just written (consensus.hip): one launch behind the last step
+  if (!rc && call.consensus && call.cs_units) {  // ... over their unit rows (consensus_units.hip): a clear and three launches
+    ConsensusUnitsArgs ca;
+    ca.ids = d_out_ids;
+    ca.len = d_out_len;
+    ca.row_src = c->call.row_src;
+    ca.unit_off = c->model->cu_off.as<uint32_t>();
+    ca.units = c->model->cu_units.as<uint32_t>();
+    ca.N = (uint32_t)R;
+    ca.T = (uint32_t)Tmax;
+    ca.B = (uint32_t)B;
+    ca.V = (uint32_t)c->model->V;
+    ca.max_order = call.cs_order;
+    ca.beta2 = call.cs_beta2;
+    ca.utility = call.cs_dev_util;
+    ca.best = call.cs_dev_best;
+    ProfScope p(c, SLIMT_HIP_K_CONSENSUS, 0, 0);
+    const hipError_t he = launch_consensus_units(ca, c->cu_ws.p, st);
+    if (he != hipSuccess) rc = fail((int)he, "consensus units: %s", hipGetErrorString(he));
+  } else if (!rc && call.consensus) {  // the selection over the rows just written (consensus.hip): one launch behind the last step
     ConsensusArgs ca;
     ca.ids = d_out_ids;
     ca.len = d_out_len;
@@ -3029,6 +3071,10 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
     if (!call.fanout || !call.cs_dev_best || !call.cs_dev_util) return fail(-1, "consensus: not a fan-out call");
     if (Tmax > (size_t)SLIMT_HIP_CONSENSUS_MAX_T)
       return fail(-1, "consensus: the call's Tmax %zu exceeds %d", Tmax, SLIMT_HIP_CONSENSUS_MAX_T);
+    if (call.cs_units) {  // (the unit rows' workspace, sized by the call's rows: reserved on first use, like bm_state)
+      if (!m->cu_off.p) return fail(-1, "consensus units: the model has no unit table");
+      HIPCHK(c->cu_ws.reserve(consensus_units_workspace_bytes((uint32_t)R)));
+    }
   }
   // The K/V cache form (launch_choice.h, kv_cache_form): packed where the persistent pair has it for this shape and S.
   KvFormIn form;
@@ -4847,5 +4893,150 @@ extern "C" int slimt_hip_consensus_select_device(slimt_hip_ctx *ctx, const uint3
   HIPCHK(hipSetDevice(ctx->model->device));
   ProfScope p(ctx, SLIMT_HIP_K_CONSENSUS, 0, 0);
   HIPCHK(launch_consensus(consensus_args(d_ids, d_len, d_row_src, N, T, B, max_order, beta2, d_utility, d_best), ctx->stream));
+  return 0;
+}
+
+// ---- ... over unit rows: the character n-gram F (slimt_hip_consensus_select_units*; consensus_units.hip) --------------------
+static_assert(kConsensusUnitsMaxOrder == SLIMT_HIP_CONSENSUS_UNITS_MAX_ORDER && kConsensusMaxUnits == SLIMT_HIP_CONSENSUS_MAX_UNITS &&
+                  kConsensusMaxExpansion == SLIMT_HIP_CONSENSUS_MAX_EXPANSION,
+              "include/slimt_hip.h and kernels.h disagree on the unit consensus limits");
+namespace {
+// the checks of consensus_check with the unit orders' bound
+int consensus_units_check(const void *ids, const void *len, const void *row_src, size_t N, size_t T, size_t B, int max_order,
+                          int beta2, const void *utility, const void *best) {
+  if (max_order < 1 || max_order > SLIMT_HIP_CONSENSUS_UNITS_MAX_ORDER)
+    return fail(-1, "consensus units: max_order %d is not in 1..%d", max_order, SLIMT_HIP_CONSENSUS_UNITS_MAX_ORDER);
+  return consensus_check(ids, len, row_src, N, T, B, 1, beta2, utility, best);
+}
+
+// A host unit table: offsets from 0, non-decreasing, no expansion over the limit.
+int unit_table_check(const uint32_t *unit_off, const uint32_t *units, size_t V) {
+  if (!unit_off) return fail(-1, "null argument");
+  if (V >= 0xFFFFFFFFull) return fail(-1, "unit table: %zu ids", V);
+  if (unit_off[0] != 0) return fail(-1, "unit table: unit_off[0] is %u, not 0", unit_off[0]);
+  for (size_t v = 0; v < V; ++v) {
+    if (unit_off[v + 1] < unit_off[v]) return fail(-1, "unit table: the offsets decrease at id %zu (%u -> %u)", v, unit_off[v], unit_off[v + 1]);
+    if (unit_off[v + 1] - unit_off[v] > (uint32_t)SLIMT_HIP_CONSENSUS_MAX_EXPANSION)
+      return fail(-1, "unit table: id %zu expands to %u units, more than %d", v, unit_off[v + 1] - unit_off[v], SLIMT_HIP_CONSENSUS_MAX_EXPANSION);
+  }
+  if (unit_off[V] && !units) return fail(-1, "null argument");
+  return 0;
+}
+
+// The table in device memory: off [V + 1], units [max(1, unit_off[V])]
+int unit_table_upload(DevBuf &off, DevBuf &un, const uint32_t *unit_off, const uint32_t *units, size_t V, hipStream_t st) {
+  HIPCHK(off.reserve((V + 1) * 4));
+  HIPCHK(un.reserve(std::max<size_t>(1, unit_off[V]) * 4));
+  HIPCHK(hipMemcpyAsync(off.p, unit_off, (V + 1) * 4, hipMemcpyHostToDevice, st));
+  if (unit_off[V]) HIPCHK(hipMemcpyAsync(un.p, units, (size_t)unit_off[V] * 4, hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+ConsensusUnitsArgs consensus_units_args(const uint32_t *ids, const uint32_t *len, const uint32_t *row_src, size_t N, size_t T,
+                                        size_t B, const uint32_t *unit_off, const uint32_t *units, size_t V, int max_order,
+                                        int beta2, double *utility, uint32_t *best) {
+  ConsensusUnitsArgs a;
+  a.ids = ids;
+  a.len = len;
+  a.row_src = row_src;
+  a.unit_off = unit_off;
+  a.units = units;
+  a.N = (uint32_t)N;
+  a.T = (uint32_t)T;
+  a.B = (uint32_t)B;
+  a.V = (uint32_t)V;
+  a.max_order = max_order;
+  a.beta2 = beta2;
+  a.utility = utility;
+  a.best = best;
+  return a;
+}
+}  // namespace
+
+extern "C" int slimt_hip_consensus_select_units(const uint32_t *ids, const uint32_t *len, const uint32_t *row_src, size_t N,
+                                                size_t T, size_t B, const uint32_t *unit_off, const uint32_t *units, size_t V,
+                                                int max_order, int beta2, double *utility, uint32_t *best) {
+  RCCHK(consensus_units_check(ids, len, row_src, N, T, B, max_order, beta2, utility, best));
+  RCCHK(unit_table_check(unit_off, units, V));
+  {
+    std::map<uint32_t, uint32_t> rows;  // (N <= 65536 entries, whatever B)
+    for (size_t c = 0; c < N; ++c) {
+      if (row_src[c] >= B) return fail(-1, "consensus units: row %zu names source %u of %zu", c, row_src[c], B);
+      if (len[c] > T) return fail(-1, "consensus units: length %u of row %zu > T %zu", len[c], c, T);
+      if (++rows[row_src[c]] > (uint32_t)SLIMT_HIP_CONSENSUS_MAX_ROWS)
+        return fail(-1, "consensus units: source %u has more than %d rows", row_src[c], SLIMT_HIP_CONSENSUS_MAX_ROWS);
+      size_t u = 0;
+      for (size_t t = 0; t < len[c]; ++t) {
+        const uint32_t id = ids[c * T + t];
+        if (id >= V) return fail(-1, "consensus units: id %u of row %zu is not below V %zu", id, c, V);
+        u += unit_off[id + 1] - unit_off[id];
+      }
+      if (u > (size_t)SLIMT_HIP_CONSENSUS_MAX_UNITS)
+        return fail(-1, "consensus units: row %zu expands to %zu units, more than %d", c, u, SLIMT_HIP_CONSENSUS_MAX_UNITS);
+    }
+  }
+  Tmp3 t;
+  DevBuf off, un, ws;
+  struct Free {
+    DevBuf &a, &b, &c;
+    ~Free() { a.release(); b.release(); c.release(); }
+  } free_them{off, un, ws};
+  hipStream_t st = nullptr;
+  HIPCHK(t.a.reserve(std::max<size_t>(1, N * T) * 4));
+  HIPCHK(t.b.reserve(std::max<size_t>(1, N) * 4));
+  HIPCHK(t.c.reserve(std::max<size_t>(1, N) * 4));
+  HIPCHK(t.d.reserve(std::max<size_t>(1, N) * 8));
+  HIPCHK(t.e.reserve(B * 4));
+  HIPCHK(ws.reserve(consensus_units_workspace_bytes((uint32_t)N)));
+  RCCHK(unit_table_upload(off, un, unit_off, units, V, st));
+  if (N) {
+    HIPCHK(hipMemcpyAsync(t.a.p, ids, N * T * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(t.b.p, len, N * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(t.c.p, row_src, N * 4, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(launch_consensus_units(consensus_units_args(t.a.as<uint32_t>(), t.b.as<uint32_t>(), t.c.as<uint32_t>(), N, T, B,
+                                                     off.as<uint32_t>(), un.as<uint32_t>(), V, max_order, beta2,
+                                                     t.d.as<double>(), t.e.as<uint32_t>()), ws.p, st));
+  if (N) HIPCHK(hipMemcpyAsync(utility, t.d.p, N * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(best, t.e.p, B * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+extern "C" int slimt_hip_model_set_consensus_units(slimt_hip_model *model, const uint32_t *unit_off, const uint32_t *units, size_t V) {
+  if (!model) return fail(-1, "null argument");
+  HIPCHK(hipSetDevice(model->device));
+  if (!unit_off) {  // removes the table
+    HIPCHK(hipDeviceSynchronize());  // (a call in flight may still read it)
+    model->cu_off.release();
+    model->cu_units.release();
+    return 0;
+  }
+  if (V != (size_t)model->V) return fail(-1, "unit table: V %zu is not the model's vocabulary %d", V, model->V);
+  RCCHK(unit_table_check(unit_off, units, V));
+  HIPCHK(hipDeviceSynchronize());  // (replaces an earlier table: no call in flight reads it any more)
+  const int rc = unit_table_upload(model->cu_off, model->cu_units, unit_off, units, V, nullptr);
+  const hipError_t e = rc ? hipSuccess : hipStreamSynchronize(nullptr);
+  if (rc || e != hipSuccess) {  // (no half-written table stays behind)
+    model->cu_off.release();
+    model->cu_units.release();
+    return rc ? rc : fail((int)e, "unit table: %s", hipGetErrorString(e));
+  }
+  return 0;
+}
+
+extern "C" int slimt_hip_consensus_select_units_device(slimt_hip_ctx *ctx, const uint32_t *d_ids, const uint32_t *d_len,
+                                                       const uint32_t *d_row_src, size_t N, size_t T, size_t B, int max_order,
+                                                       int beta2, double *d_utility, uint32_t *d_best) {
+  RCCHK(consensus_units_check(d_ids, d_len, d_row_src, N, T, B, max_order, beta2, d_utility, d_best));
+  if (!ctx) return fail(-1, "null argument");
+  const slimt_hip_model *m = ctx->model;
+  if (!m->cu_off.p) return fail(-1, "consensus units: the model has no unit table (slimt_hip_model_set_consensus_units)");
+  HIPCHK(hipSetDevice(m->device));
+  HIPCHK(ctx->cu_ws.reserve(consensus_units_workspace_bytes((uint32_t)N)));
+  ProfScope p(ctx, SLIMT_HIP_K_CONSENSUS, 0, 0);
+  HIPCHK(launch_consensus_units(consensus_units_args(d_ids, d_len, d_row_src, N, T, B, m->cu_off.as<uint32_t>(),
+                                                     m->cu_units.as<uint32_t>(), (size_t)m->V, max_order, beta2, d_utility,
+                                                     d_best), ctx->cu_ws.p, ctx->stream));
   return 0;
 }

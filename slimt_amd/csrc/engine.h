@@ -73,6 +73,7 @@ struct ArmedOptions {
   uint32_t top_k = 0;
   float top_p = 1.0f;
   int cs_order = 0, cs_beta2 = 0;
+  bool cs_units = false;  // the selection over unit rows (slimt_hip_ctx_set_fanout_consensus_units): same slot, last arming wins
   uint32_t *cs_best = nullptr;
   double *cs_util = nullptr;
 };
@@ -87,6 +88,7 @@ struct CallState {
   uint32_t top_k = 0;
   float top_p = 1.0f;
   int cs_order = 0, cs_beta2 = 0;
+  bool cs_units = false;  // ... over the rows' unit rows through the model's unit table (consensus_units.hip)
   int rows = 0;                       // fan-out: N <= max_B (the per-row decoder workspaces are sized by max_B)
   const uint32_t *row_src = nullptr;  // ... [rows] as the kernels read it (device memory)
   uint32_t *cs_best = nullptr, *cs_dev_best = nullptr;  // consensus: best [B] and utility [rows] as the caller gave
@@ -118,6 +120,9 @@ struct slimt_hip_model {
   slimt_hip::DevBuf out_bias;  // decoder_ff_logit_out_b [V]
   float out_a_quant = 0.f;     // none_QuantMultA (Transformer.cc:111-113)
   slimt_hip::AffineW out_full; // full-vocabulary output layer
+  // the unit table of the consensus selection over unit rows (slimt_hip_model_set_consensus_units): unit_off [V + 1] and
+  // units, checked on the host before the upload; empty buffers (cu_off.p == nullptr): the model has none
+  slimt_hip::DevBuf cu_off, cu_units;
   // Admission of persistent decoders (all contexts of this model): at most
   // `decoder_budget` decoder workgroups are meant to run at a time; launch k waits
   // (on its stream, not the host) for launch k - n, n = budget / its workgroups.
@@ -253,6 +258,7 @@ struct slimt_hip_ctx {
   slimt_hip::DevBuf tr_logits;           // truncation: [B][N] f32, the step's logits, reserved by the first truncated call
   slimt_hip::DevBuf fo_stage;            // fan-out: device staging of a host call's row_src
   slimt_hip::DevBuf cs_stage;            // consensus: device staging of a host call's utility [N] f64 + best [B] u32
+  slimt_hip::DevBuf cu_ws;               // ... over unit rows: the launches' workspace, reserved by the first such call (kernels.h)
   // beam search, reserved by the first beam call: the second SSRU state block (the steps gather from one into the other),
   // the slots' totals / flags / lengths / step words and the sources' done words, the steps' records [Tmax][rows] x 3, the
   // decoder's alignment rows [rows][Tmax][S], device staging of a host call's totals and token scores; the rows' sources

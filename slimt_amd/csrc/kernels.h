@@ -809,6 +809,39 @@ struct ConsensusArgs {
 size_t consensus_lds_bytes(int rows, int T);
 hipError_t launch_consensus(const ConsensusArgs &a, hipStream_t st);
 
+// ---- the same selection over unit rows: character n-gram F, orders 1..6 (consensus_units.hip; slimt_hip_consensus_select_units*) --
+// A row's ids are expanded through the unit table (unit_off [V + 1], units) into a unit row of at most kConsensusMaxUnits
+// units, and the definition above is applied to the unit rows. A clear kernel and three launches over a workspace the caller owns
+// (consensus_units_workspace_bytes(N), carved by launch_consensus_units): expand, pair counts, finish. Device arrays are not
+// checked: row_src and len are clamped as above, an id >= V expands to nothing, and a source with more than
+// kConsensusMaxRows rows or a row over kConsensusMaxUnits units gets best 0xFFFFFFFF, utility 0. The table is the host's
+// (checked where it was uploaded): offsets non-decreasing from 0, an expansion of at most kConsensusMaxExpansion units.
+constexpr int kConsensusUnitsMaxOrder = 6;   // == SLIMT_HIP_CONSENSUS_UNITS_MAX_ORDER
+constexpr int kConsensusMaxUnits = 1024;     // == SLIMT_HIP_CONSENSUS_MAX_UNITS
+constexpr int kConsensusMaxExpansion = 255;  // == SLIMT_HIP_CONSENSUS_MAX_EXPANSION
+struct ConsensusUnitsArgs {
+  const uint32_t *ids = nullptr;       // [N][T]
+  const uint32_t *len = nullptr;       // [N], clamped to T
+  const uint32_t *row_src = nullptr;   // [N], clamped to B - 1
+  const uint32_t *unit_off = nullptr;  // [V + 1]
+  const uint32_t *units = nullptr;     // [unit_off[V]]
+  uint32_t N = 0, T = 0, B = 0, V = 0;
+  int max_order = 0, beta2 = 0;
+  double *utility = nullptr;  // [N]; may be NULL when N = 0
+  uint32_t *best = nullptr;   // [B]
+  // (set by launch_consensus_units: the workspace's carves)
+  uint32_t *ws_units = nullptr;  // [N][kConsensusMaxUnits + 5] the unit rows, five zeros behind a row's length
+  uint32_t *ws_ulen = nullptr;   // [N] their lengths
+  uint32_t *ws_head = nullptr;   // [N] at a selected source's lowest row: its row count (other entries are not written)
+  uint32_t *ws_heads = nullptr;  // [N] the selected sources' lowest rows, in any order; *ws_count of them
+  uint32_t *ws_count = nullptr;  // [1]
+  int chunks = 0;                // workgroups per source of the pair launch
+  uint32_t *ws_list = nullptr;   // [N][64] at a source's lowest row: its rows, ascending
+  uint16_t *ws_M = nullptr;      // [N][64][6] row c against the j-th row of its source: the clipped match counts
+};
+size_t consensus_units_workspace_bytes(uint32_t N);
+hipError_t launch_consensus_units(const ConsensusUnitsArgs &a, void *workspace, hipStream_t st);
+
 // ---- truncated sampling: top-k / nucleus selection over stored logits (sample_truncate.hip) -------------------------------
 // One sampled step of B rows whose output-layer logits [B][N] are in memory (the logits gemm with EPI_PLAIN): the kept set
 // of include/slimt_hip.h (slimt_hip_ctx_set_sampling_truncation; truncation.h) and, over it, one partial per row in

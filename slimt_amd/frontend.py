@@ -143,6 +143,7 @@ class Model:
         capi.request_hw_queues(32)  # a Service runs `workers` x 2 streams on this device (no-op once HIP is up)
         self.engine = capi.Model(host, device)
         self.dims = (host.D, host.F, host.V)
+        self._consensus_units = None  # (consensus_units(): built and uploaded on first use)
         self.shortlist_generator = None
         self.shortlist_blob = b""
         if package.shortlist:  # Model::make_shortlist_generator, Model.cc:60-72
@@ -150,6 +151,16 @@ class Model:
             # ShortlistGenerator(view, source, target): shared = false, check = false (Model.cc:73-80, Shortlist.hh:47-52)
             self.shortlist_generator = capi.ShortlistGenerator(self.shortlist_blob, host.V, host.V,
                                                                shared=False, check=False, device=device)
+
+    def consensus_units(self):
+        """The vocabulary's unit table for the consensus selection over characters (text.Vocabulary.consensus_units, sized
+        by the model's embedding rows): built on first use and uploaded to the engine once
+        (slimt_hip_model_set_consensus_units), so that the device and armed calls on self.engine find it."""
+        if self._consensus_units is None:
+            table = self.vocabulary.consensus_units(self.dims[2])
+            self.engine.set_consensus_units(*table)
+            self._consensus_units = table
+        return self._consensus_units
 
     def close(self) -> None:
         if self.shortlist_generator is not None:
@@ -549,16 +560,27 @@ class Service:
         ranked = self.rerank(model, sources, [[a.target.text for a in r.samples] for r in responses], mean=mean)
         return responses, ranked
 
-    def sample_and_select(self, model: Model, sources: Sequence[str], n: int, sampling, truncation=None, max_order: int = 4,
-                          beta2: int = 4, encoding: Encoding = Encoding.UTF8) -> List[Response]:
+    def sample_and_select(self, model: Model, sources: Sequence[str], n: int, sampling, truncation=None,
+                          max_order: Optional[int] = None, beta2: int = 4, encoding: Encoding = Encoding.UTF8,
+                          utility: str = "tokens") -> List[Response]:
         """translate(samples=n) followed by the consensus (minimum-Bayes-risk) pick: of the n draws of every sentence, the one
         that agrees most with the others -- the mean token n-gram F (orders 1..max_order, integer beta2 = beta^2; 4 is chrF's)
         against the sentence's other draws (include/slimt_hip.h, slimt_hip_consensus_select). The pick is made on the device
         behind the fan-out call that drew the samples: no second encoding and no scorer pass (sample_and_rerank makes both).
         Returns one Response per source, built from the winners (always with scores), carrying `utility` and `sample_index`
-        per sentence: sentence i's winner is sample sample_index[i] of translate(samples=n) under the same sampling. n <= 64."""
+        per sentence: sentence i's winner is sample sample_index[i] of translate(samples=n) under the same sampling. n <= 64.
+        utility: "tokens" (max_order up to 4, default 4) as above, or "chrf" (max_order up to 6, default 6): the draws are
+        compared by the characters they spell, whitespace removed -- the mean chrF against the other draws
+        (slimt_hip_consensus_select_units over model.consensus_units()), so two segmentations of the same words count as the
+        same translation. The "chrf" pick runs on the device over the samples translate(samples=n) returns, in a call of its
+        own behind the fan-out calls; a draw of more than 1024 characters or 256 tokens is refused (the engine's message; a
+        segment of at most ENGINE_LIMIT tokens yields at most 192)."""
         if sampling is None or int(n) < 1:
             raise ValueError("sample_and_select: n >= 1 and sampling=(temperature, seed)")
+        if utility not in ("tokens", "chrf"):
+            raise ValueError(f"sample_and_select: utility is 'tokens' or 'chrf', not {utility!r}")
+        if max_order is None:
+            max_order = 6 if utility == "chrf" else 4
         processed = model.processor.process_many(sources, self.wrap_length, self.workers)
         per_request = [segs for _, segs in processed]
         flat = [seg for segs in per_request for seg in segs]
@@ -566,14 +588,34 @@ class Service:
             raise ValueError(f"samples: a segment has more than {self.ENGINE_LIMIT} tokens")
         histories = [[None] * len(segs) for segs in per_request]
         picked = [([0.0] * len(segs), [0] * len(segs)) for segs in per_request]
-        if flat:
-            res, utility, index = self._engine(model, False, sampling[0], truncation).translate_consensus(
+        if flat and utility == "chrf":
+            n = int(n)
+            if n > capi.CONSENSUS_MAX_ROWS:
+                raise ValueError(f"sample_and_select: at most {capi.CONSENSUS_MAX_ROWS} samples, not {n}")
+            drawn = self._translate_samples(model, per_request, n, sampling, truncation)  # [sample][request][segment]
+            where = [(r, i) for r, segs in enumerate(per_request) for i in range(len(segs))]
+            unit_off, units = model.consensus_units()
+            per_call = 65536 // n  # (the call's bound on its rows)
+            for at in range(0, len(where), per_call):
+                part = where[at:at + per_call]
+                rows = [drawn[j][r][i][0] for r, i in part for j in range(n)]
+                ids = np.zeros((len(rows), max(1, max(len(x) for x in rows))), np.uint32)
+                for c, x in enumerate(rows):
+                    ids[c, :len(x)] = x
+                u, best = capi.consensus_select_units(ids, [len(x) for x in rows], np.repeat(np.arange(len(part)), n),
+                                                      len(part), unit_off, units, max_order, beta2)
+                for e, (r, i) in enumerate(part):
+                    c = e * n if best[e] == capi.NO_ROW else int(best[e])  # (every draw empty: the first)
+                    histories[r][i] = drawn[c - e * n][r][i]
+                    picked[r][0][i], picked[r][1][i] = float(u[c]), c - e * n
+        elif flat:
+            res, util, index = self._engine(model, False, sampling[0], truncation).translate_consensus(
                 flat, int(n), seed=int(sampling[1]), max_order=max_order, beta2=beta2)
             e = 0
             for r, segs in enumerate(per_request):
                 for i in range(len(segs)):
                     histories[r][i] = (res.target(e).tolist(), res.alignment(e).copy(), res.token_scores(e).copy())
-                    picked[r][0][i], picked[r][1][i] = float(utility[e]), int(index[e])
+                    picked[r][0][i], picked[r][1][i] = float(util[e]), int(index[e])
                     e += 1
             res.close()
         out = self._respond_many(model, [src for src, _ in processed], histories)

@@ -236,6 +236,28 @@ class Vocabulary:
         word = int(word)
         return self.sp.id_to_piece(word) if 0 <= word < self.size() else ""
 
+    def consensus_units(self, size: int = 0):
+        """The unit table of the consensus selection over unit rows (include/slimt_hip.h, slimt_hip_consensus_select_units):
+        (unit_off uint32 [V + 1], units uint32) with V = max(size, this vocabulary's size) -- `size` is the model's
+        vocabulary where its embedding has padding rows, which expand to nothing. A piece expands to its code points with
+        U+2581 and Unicode whitespace removed, so a row's units are the characters chrF counts n-grams of; a byte-fallback
+        piece <0xXX> to the single unit 0x110000 + XX (above every code point); control, unknown and unused pieces (EOS,
+        pad, unk) to nothing. A piece of more than 255 characters is refused."""
+        import numpy as np
+        n = self.size()
+        off, units = np.zeros(max(int(size), n) + 1, np.uint32), []
+        for v in range(n):
+            if self.sp.is_byte(v):
+                units.append(0x110000 + int(self.sp.id_to_piece(v)[3:5], 16))
+            elif not (self.sp.is_control(v) or self.sp.is_unknown(v) or self.sp.is_unused(v)):
+                chars = [ord(ch) for ch in self.sp.id_to_piece(v) if ch != "▁" and not ch.isspace()]
+                if len(chars) > 255:
+                    raise ValueError(f"consensus_units: piece {v} has {len(chars)} characters, more than 255")
+                units.extend(chars)
+            off[v + 1] = len(units)
+        off[n + 1:] = len(units)
+        return off, np.asarray(units, dtype=np.uint32)
+
     def encode(self, line: bytes | str, add_eos: bool = False) -> Tuple[List[int], List[Tuple[int, int]]]:
         """ids and, per id, the (begin, end) byte range of its surface in `line`
         (Vocabulary.cc:34-75; the appended EOS has no range, as there)."""
