@@ -943,6 +943,44 @@ int slimt_hip_beam_step(const float *logits, size_t B, int beam, size_t N, const
                         const uint32_t *flags_in, uint32_t eos_id, uint32_t *parent, uint32_t *token, float *token_score,
                         float *totals_out, uint32_t *flags_out);
 
+/* ---- sampling without replacement on a beam call (stochastic beam search) ---- */
+/* Arms the NEXT beam call (slimt_hip_translate_beam*) to draw its k hypotheses per source WITHOUT REPLACEMENT from the
+ * model's distribution over sequences (truncated at Tmax), each with its exact log-probability as its total: stochastic
+ * beam search (Kool, van Hoof and Welling 2019), a beam search whose selection runs on Gumbel-perturbed totals. THE
+ * CONTRACT (slimt_amd/csrc/beam_sampled.h is host-compilable and is the definition; everything of the beam's contract
+ * above holds word for word -- usable rows, weights, Q, L, lp, flags, totals C as f32 sums of lp):
+ *   - a slot also carries a perturbed value G (f32), a source a 64-bit key K (keys[b]; keys NULL:
+ *     slimt_hip_sampling_key(0, b)). Before step 0, slot 0 is live with C = +0 and G = +0;
+ *   - noise: at step t slot s has the row key k_s = slimt_hip_sampling_key(K, s) and the step's two words of sampled
+ *     decoding (sampling.h, sm_step_words(k_s, t)); column c with vocabulary id y_c gets g_c = sm_gumbel(s0, s1, y_c): a
+ *     pure function of (K, s, t, id);
+ *   - perturbation: for a live slot with a usable row and every column with lp_c > -inf, phi_c = C_s + lp_c and
+ *     psi_c = (phi_c + g_c) + 0.0f (two f32 adds). A slot's columns are ordered by psi descending as floats, then column
+ *     ascending; only the first k are the slot's candidates, and the first one's psi is Z_s;
+ *   - conditioning: candidate j of slot s gets cand = sb_condition(G_s, Z_s, psi), the function
+ *     -log(exp(-G_s) - exp(-Z_s) + exp(-psi)) in the paper's stable form, built from tr_exp, sm_log and fmaf; psi == Z_s
+ *     gives exactly G_s, the result never exceeds G_s, and it is within 5e-5 of float64
+ *     (tests/test_beam_sampled_checker.py measures it); a finished slot is a candidate itself with cand = G_s;
+ *   - selection: candidates ordered by cand descending as floats, then slot ascending, then the within-slot rank
+ *     ascending; the first k become slots 0..k-1 with parent, token and token score = lp_c as in the beam, C = phi_c and
+ *     G = cand (a carried slot keeps both). EOS, dead slots, the done count, Tmax and the outputs are the beam's; the
+ *     hypotheses are ordered as an un-armed call orders them (totals, or totals / length).
+ * Live and finished hypotheses of a source are pairwise distinct. A source's result depends on the source, the output
+ * layer, k, the mode and its key only. perturbed (nullable): [B][beam], each hypothesis's final G in the output's order
+ * (-inf for a dead slot). n is the call's B (a beam call with another B is refused); n = 0 with NULL arrays disarms.
+ * Host beam calls read host arrays (_async: read and written until the context is synchronised; pinned keys are read in
+ * place), _device takes device arrays. The option is consumed by the next translate entry point whatever its outcome; one
+ * that is not a beam call fails with a message. A beam call refuses what it refuses un-armed: scores, a prefix,
+ * slimt_hip_ctx_set_sampling, truncation, consensus. Not offered: a temperature other than 1, truncation, beam > 8. */
+int slimt_hip_ctx_set_beam_sampling(slimt_hip_ctx *ctx, const uint64_t *keys, size_t n, float *perturbed);
+/* slimt_hip_beam_step with the selection above: keys [B] (NULL as above), the step t, and the slots' perturbed values
+ * perturbed_in / perturbed_out [B beam] beside the totals (a live slot's finite, a finished one's not NaN; the step-0
+ * state has +0, -inf, -inf, ...; a dead new slot gets -inf). Host pointers, stateless, waits. */
+int slimt_hip_beam_step_sampled(const float *logits, size_t B, int beam, size_t N, const uint32_t *ids, const uint64_t *keys,
+                                uint32_t step, const float *totals_in, const float *perturbed_in, const uint32_t *flags_in,
+                                uint32_t eos_id, uint32_t *parent, uint32_t *token, float *token_score, float *totals_out,
+                                float *perturbed_out, uint32_t *flags_out);
+
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, HIP events bracket every launch of kernel family `kernel_id`
  * on the ctx stream; slimt_hip_profile_read returns the number of launches

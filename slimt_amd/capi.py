@@ -55,6 +55,7 @@ SYMBOLS = [
     "slimt_hip_ctx_set_fanout_consensus_units",
     "slimt_hip_translate_beam", "slimt_hip_translate_beam_async", "slimt_hip_translate_beam_device",
     "slimt_hip_translate_beam_async_generated", "slimt_hip_beam_step",
+    "slimt_hip_ctx_set_beam_sampling", "slimt_hip_beam_step_sampled",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -309,6 +310,8 @@ def lib():
     L.slimt_hip_translate_beam_device.argtypes = [vp, vp, vp, sz, sz, i32, i32, vp, sz, f32, u32, vp, vp, vp, vp, vp, i32]
     L.slimt_hip_translate_beam_async_generated.argtypes = [vp, vp, vp, vp, sz, sz, i32, i32, f32, u32, vp, vp, vp, vp, vp]
     L.slimt_hip_beam_step.argtypes = [vp, sz, i32, sz, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.slimt_hip_ctx_set_beam_sampling.argtypes = [vp, vp, sz, vp]
+    L.slimt_hip_beam_step_sampled.argtypes = [vp, sz, i32, sz, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("slimt_hip_abi_version",):
@@ -369,6 +372,31 @@ def beam_step(logits, totals, flags, beam: int, eos_id: int = 0, ids=None):
     _chk(lib().slimt_hip_beam_step(_p(logits), R // beam, beam, N, _p(ids), _p(totals), _p(flags), int(eos_id), _p(parent),
                                    _p(token), _p(score), _p(totals_out), _p(flags_out)))
     return parent, token, score, totals_out, flags_out
+
+
+def beam_step_sampled(logits, totals, perturbed, flags, beam: int, keys=None, step: int = 0, eos_id: int = 0, ids=None):
+    """slimt_hip_beam_step_sampled: beam_step() with the selection of sampling without replacement -- perturbed [B * beam]
+    float32 (the slots' values G) beside the totals, keys uint64 [B] (None: sampling_key(0, b)) and the step. Returns
+    (parent, token, token_score, totals, perturbed, flags), each [B * beam]."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    totals = np.ascontiguousarray(totals, dtype=np.float32)
+    perturbed = np.ascontiguousarray(perturbed, dtype=np.float32)
+    flags = np.ascontiguousarray(flags, dtype=np.uint32)
+    beam = int(beam)
+    if (logits.ndim != 2 or beam < 1 or logits.shape[0] % beam or totals.shape != (logits.shape[0],) or flags.shape != totals.shape
+            or perturbed.shape != totals.shape):
+        raise ValueError("beam_step_sampled: logits [B * beam, N], totals, perturbed and flags [B * beam] expected")
+    R, N = logits.shape
+    ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32)
+    keys = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint64)
+    if (ids is not None and ids.shape != (N,)) or (keys is not None and keys.shape != (R // beam,)):
+        raise ValueError("beam_step_sampled: ids [N] and keys [B] expected")
+    parent, token, flags_out = np.zeros(R, np.uint32), np.zeros(R, np.uint32), np.zeros(R, np.uint32)
+    score, totals_out, perturbed_out = np.zeros(R, np.float32), np.zeros(R, np.float32), np.zeros(R, np.float32)
+    _chk(lib().slimt_hip_beam_step_sampled(_p(logits), R // beam, beam, N, _p(ids), _p(keys), int(step), _p(totals), _p(perturbed),
+                                           _p(flags), int(eos_id), _p(parent), _p(token), _p(score), _p(totals_out),
+                                           _p(perturbed_out), _p(flags_out)))
+    return parent, token, score, totals_out, perturbed_out, flags_out
 
 
 def candidates_rank(scores, tgt_len, cand_src, B: int, mean: bool = False, mode=None):
@@ -1167,11 +1195,51 @@ class Context:
     def _beam_mode(mean, mode) -> int:
         return int(mode) if mode is not None else (1 if mean else 0)
 
+    def set_beam_sampling(self, keys, n: int, perturbed=None):
+        """slimt_hip_ctx_set_beam_sampling: arm the NEXT beam call to sample its hypotheses without replacement. keys: the
+        sources' keys as a numpy uint64 [n] array (host calls; kept alive here until the next arming), an address (int: a
+        device pointer for the device call) or None (sampling_key(0, b)); perturbed: float32 [n, beam] (array or address) or
+        None. n = 0 with no arrays disarms. The translate_beam* wrappers take `sampling_keys=` / `perturbed=` and do this."""
+        keep, addr = [], []
+        for a, dt in ((keys, np.uint64), (perturbed, np.float32)):
+            if isinstance(a, np.ndarray):
+                if a.dtype != dt or not a.flags.c_contiguous:
+                    raise ValueError("beam sampling: C-contiguous uint64 keys and float32 perturbed expected")
+                keep.append(a)
+                addr.append(a.ctypes.data)
+            else:
+                addr.append(int(a) if a else 0)
+        self._beam_sampling_keep = keep
+        _chk(lib().slimt_hip_ctx_set_beam_sampling(self.h, C.c_void_p(addr[0] or None), int(n), C.c_void_p(addr[1] or None)))
+
+    def _arm_beam_sampling(self, sampling_keys, perturbed, B: int, k: int):
+        """arms a host beam call's sampling_keys= (True: the default keys; or uint64 [B]) and perturbed= (True: a new
+        array; or float32 [B, beam]); returns the perturbed array or None"""
+        if sampling_keys is None:
+            if perturbed is not None:
+                raise ValueError("translate_beam: perturbed= needs sampling_keys=")
+            return None
+        if sampling_keys is True:
+            keys = None
+        else:
+            keys = np.ascontiguousarray(sampling_keys, dtype=np.uint64)
+            if keys.shape != (B,):
+                raise ValueError("translate_beam: sampling_keys [B] expected")
+        if perturbed is True:
+            perturbed = np.zeros((B, k), np.float32)
+        if perturbed is not None and (not isinstance(perturbed, np.ndarray) or perturbed.shape != (B, k)):
+            raise ValueError("translate_beam: perturbed [B, beam] float32 expected")
+        self.set_beam_sampling(keys, B, perturbed)
+        return perturbed
+
     def translate_beam(self, ids, lengths, beam: int, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                       mean: bool = False, want_align: bool = False, want_scores: bool = True, mode=None):
+                       mean: bool = False, want_align: bool = False, want_scores: bool = True, mode=None,
+                       sampling_keys=None, perturbed=None):
         """slimt_hip_translate_beam: beam search over the B sources ids [B,S] / lengths [B] with `beam` slots each. Returns
         the n-best, best first: out_ids [B,beam,Tmax], out_len [B,beam] (0: a dead slot), totals [B,beam] (-inf: a dead
-        slot), token_scores [B,beam,Tmax] | None, align [B,beam,Tmax,S] | None. mean: order by totals / out_len."""
+        slot), token_scores [B,beam,Tmax] | None, align [B,beam,Tmax,S] | None. mean: order by totals / out_len.
+        sampling_keys (uint64 [B], or True for the default keys): the hypotheses are sampled without replacement
+        (slimt_hip_ctx_set_beam_sampling) and a sixth array follows, perturbed [B,beam] (the one given, or a new one)."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
         if ids.ndim != 2 or lengths.shape != (ids.shape[0],):
@@ -1186,9 +1254,13 @@ class Context:
         totals = np.zeros((B, kk), dtype=np.float32)
         sc = np.zeros((B, kk, T), dtype=np.float32) if want_scores else None
         align = np.zeros((B, kk, T, S), dtype=np.float32) if want_align else None
+        if sampling_keys is not None:
+            perturbed = self._arm_beam_sampling(sampling_keys, True if perturbed is None else perturbed, B, kk)
         _chk(lib().slimt_hip_translate_beam(self.h, _p(ids), _p(lengths), B, S, k, self._beam_mode(mean, mode), _p(sl),
                                             0 if sl is None else sl.size, limit_factor, eos_id, _p(out_ids), _p(out_len),
                                             _p(totals), _p(sc), _p(align)))
+        if sampling_keys is not None:
+            return out_ids, out_len, totals, sc, align, perturbed
         return out_ids, out_len, totals, sc, align
 
     def beam_buffers(self, B: int, S: int, beam: int, limit_factor: float = 1.5, want_align: bool = False):
@@ -1202,9 +1274,11 @@ class Context:
                 pin("bm_al").array(np.float32, (B, beam, T, S)) if want_align else None)
 
     def translate_beam_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
-                             mean: bool = False, mode=None):
+                             mean: bool = False, mode=None, sampling_keys=None, perturbed=None):
         """slimt_hip_translate_beam_async[_generated] on (ids, lengths, out_ids, out_len, totals, token_scores | None,
-        align | None) host arrays (already filled; those of beam_buffers() are pinned); synchronize() before reading."""
+        align | None) host arrays (already filled; those of beam_buffers() are pinned); synchronize() before reading.
+        sampling_keys (uint64 [B] or True) / perturbed (float32 [B,beam] or None): sampled without replacement; both arrays
+        are the caller's and are read / written until synchronize()."""
         ids, lengths, out_ids, out_len, totals, sc, align = bufs
         for a in (ids, lengths, out_ids, out_len):
             if a.dtype != np.uint32 or not a.flags.c_contiguous:
@@ -1221,6 +1295,7 @@ class Context:
             if a is None or a.dtype != np.float32 or a.shape != shape or not a.flags.c_contiguous:
                 raise ValueError("translate_beam_async: a C-contiguous float32 array of shape %s expected" % (shape,))
         m = self._beam_mode(mean, mode)
+        self._arm_beam_sampling(sampling_keys, perturbed, B, k)
         if generator is not None:
             _chk(lib().slimt_hip_translate_beam_async_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, k, m,
                                                                 limit_factor, eos_id, _p(out_ids), _p(out_len), _p(totals),
@@ -1231,8 +1306,9 @@ class Context:
                                                   limit_factor, eos_id, _p(out_ids), _p(out_len), _p(totals), _p(sc), _p(align)))
 
     def translate_beam_pinned(self, ids, lengths, beam: int, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                              mean: bool = False, want_align: bool = False, generator=None, mode=None):
-        """translate_beam() through this context's pinned arrays and slimt_hip_translate_beam_async; returns copies."""
+                              mean: bool = False, want_align: bool = False, generator=None, mode=None, sampling_keys=None):
+        """translate_beam() through this context's pinned arrays and slimt_hip_translate_beam_async; returns copies.
+        sampling_keys: as translate_beam()'s -- the keys and the perturbed values go through pinned arrays too."""
         ids = np.asarray(ids)
         B, S = ids.shape
         bufs = self.beam_buffers(B, S, int(beam), limit_factor, want_align)
@@ -1241,9 +1317,17 @@ class Context:
         for a in bufs[2:]:
             if a is not None:
                 a[...] = 0
-        self.translate_beam_async(bufs, shortlist, generator, limit_factor, eos_id, mean, mode)
+        keys = pert = None
+        if sampling_keys is not None:
+            pert = self._pinned.setdefault("bm_pert", _Pinned()).array(np.float32, (B, int(beam)))
+            pert[...] = 0
+            keys = True
+            if sampling_keys is not True:
+                keys = self._pinned.setdefault("bm_keys", _Pinned()).array(np.uint64, (B,))
+                keys[...] = sampling_keys
+        self.translate_beam_async(bufs, shortlist, generator, limit_factor, eos_id, mean, mode, keys, pert)
         self.synchronize()
-        return tuple(None if a is None else a.copy() for a in bufs[2:])
+        return tuple(None if a is None else a.copy() for a in bufs[2:] + ((pert,) if pert is not None else ()))
 
     def translate_beam_generated(self, generator, ids, lengths, beam: int, limit_factor: float = 1.5, eos_id: int = 0,
                                  mean: bool = False, want_align: bool = False, mode=None):
@@ -1263,9 +1347,14 @@ class Context:
 
     def translate_beam_device(self, d_ids: int, d_lengths: int, B: int, S: int, beam: int, d_shortlist: int, n_shortlist: int,
                               limit_factor: float, eos_id: int, d_out_ids: int, d_out_len: int, d_totals: int,
-                              d_token_scores: int = 0, d_align: int = 0, steps_hint: int = 0, mean: bool = False, mode=None):
-        """slimt_hip_translate_beam_device: device pointers (ints) in and out, like translate_fanout_device()."""
+                              d_token_scores: int = 0, d_align: int = 0, steps_hint: int = 0, mean: bool = False, mode=None,
+                              sampling_keys=None, perturbed: int = 0):
+        """slimt_hip_translate_beam_device: device pointers (ints) in and out, like translate_fanout_device().
+        sampling_keys: the device address of uint64 [B] keys, or True for the default keys; perturbed: the device address of
+        float32 [B,beam], or 0 -- sampled without replacement."""
         vp = C.c_void_p
+        if sampling_keys is not None:
+            self.set_beam_sampling(None if sampling_keys is True else int(sampling_keys), B, int(perturbed))
         _chk(lib().slimt_hip_translate_beam_device(self.h, vp(d_ids), vp(d_lengths), B, S, int(beam), self._beam_mode(mean, mode),
                                                    vp(d_shortlist) if n_shortlist else None, n_shortlist, limit_factor, eos_id,
                                                    vp(d_out_ids), vp(d_out_len), vp(d_totals),

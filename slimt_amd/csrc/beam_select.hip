@@ -15,12 +15,14 @@
 // beam_finish_kernel: one workgroup per source behind the last step; the first k threads rank the slots by the final key, then a
 // wave per hypothesis walks its back-pointers from the last step to the first and writes token, score and alignment row
 // of every step at which the chain took a column (a carried finished slot records kBeamNone and only passes the walk on).
+// A sampled beam call (beam_sampled.hip) also hands it the slots' perturbed values, which leave in the same order.
 //
 // Every barrier is reached by every thread; no workgroup waits for another. No out-of-line device functions, no dynamic
-// stack: helpers are __forceinline__.
+// stack: helpers are __forceinline__ (beam_tail.h holds those that beam_sampled.hip's selection shares).
 #include <hip/hip_runtime.h>
 
 #include "beam.h"
+#include "beam_tail.h"
 #include "device_common.h"
 #include "kernels.h"
 
@@ -40,37 +42,13 @@ struct BmShared {
   uint32_t n_flag[kBeamMax], n_parent[kBeamMax], n_tok[kBeamMax];  // the new slots
 };
 
-// a float's order as an unsigned word: -inf < ... < -0 == +0 < ... < +inf (not for NaN); never 0
-__device__ __forceinline__ uint32_t bm_ordered(float v) {
-  const uint32_t b = __float_as_uint(v + 0.0f);  // (-0 + 0 = +0)
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ unsigned long long bm_shfl_xor_u64(unsigned long long v, int m) {
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
 __global__ __launch_bounds__(kBmThreads) void beam_select_kernel(BeamSelectArgs a) {
   __shared__ BmShared sh;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int k = a.k, N = a.N, r0 = b * k, D = a.emb.D;
+  const int k = a.k, N = a.N, r0 = b * k;
   const float ninf = -__builtin_inff();
   if (a.init) {  // (the whole grid: no barrier below is skipped by part of a workgroup)
-    if (tid < k) {
-      a.totals_out[r0 + tid] = tid == 0 ? 0.0f : ninf;
-      a.flags_out[r0 + tid] = tid == 0 ? kBeamLive : kBeamDead;
-      if (a.len_out) a.len_out[r0 + tid] = 0u;
-      if (a.step_word) a.step_word[r0 + tid] = 0u;
-    }
-    if (tid == 0 && a.done) a.done[b] = 0u;
-    if (a.dx) {
-      for (int u = tid; u < k * D; u += kBmThreads) {
-        const float z = 0.0f * a.emb.sqrt_d;
-        a.dx[(size_t)r0 * D + u] = z + a.emb.pos[u % D];
-      }
-    }
+    bm_start_state<kBmThreads>(a, b, tid);
     return;
   }
   if (tid < kBeamMax) {
@@ -122,15 +100,7 @@ __global__ __launch_bounds__(kBmThreads) void beam_select_kernel(BeamSelectArgs 
       const uint32_t ov = bm_ordered(v);
       const uint32_t th = __hip_atomic_load(&sh.thr[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       if (v > ninf && ov >= th) {  // the slow path: rare once the list is full (a stale threshold is a lower one)
-        unsigned long long carry = ((unsigned long long)ov << 32) | (uint32_t)~(uint32_t)c;
-        int i = k;  // the first slot the key beats (slots only rise: those before it stay above the key)
-        for (int j = k - 1; j >= 0; --j) i = L[j] < carry ? j : i;
-        for (; i < k && carry != 0ull; ++i) {
-          const unsigned long long old = __hip_atomic_fetch_max(L + i, carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          const unsigned long long top = old > carry ? old : carry;
-          carry = old > carry ? carry : old;
-          if (i == k - 1) __hip_atomic_fetch_max(&sh.thr[s], (uint32_t)(top >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
+        bm_list_insert(L, &sh.thr[s], k, ov, (uint32_t)c);
       }
     }
 #pragma unroll
@@ -164,92 +134,25 @@ __global__ __launch_bounds__(kBmThreads) void beam_select_kernel(BeamSelectArgs 
         }
       }
     }
-    // a lane's place in the order: a candidate still to be taken is below 64
     uint32_t ord = valid ? (uint32_t)lane : 64u + (uint32_t)lane;
-    uint32_t my_flag = kBeamDead, my_parent = kBeamNone, my_tok = kBeamNone, my_len = 0u;
-    float my_lp = 0.0f, my_C = ninf;
+    BmNewSlot mine = bm_dead_slot();
     for (int i = 0; i < k; ++i) {
-      float bc = cand;
-      uint32_t bo = ord;
-#pragma unroll
-      for (int x = 1; x < 64; x <<= 1) {
-        const float oc = __shfl_xor(bc, x, 64);
-        const uint32_t oo = (uint32_t)__shfl_xor((int)bo, x, 64);
-        const bool ov = oo < 64u, bv = bo < 64u;
-        const bool better = ov != bv ? ov : (ov ? (oc > bc || (oc == bc && oo < bo)) : oo < bo);
-        bc = better ? oc : bc;
-        bo = better ? oo : bo;
-      }
+      const uint32_t bo = bm_best_lane(cand, ord);
       if (bo >= 64u) break;  // (uniform: every lane holds the same winner) fewer than k candidates: the rest stay dead
       const int w = (int)bo;
-      const int ws = w >> 3;
       const uint32_t wcol = (uint32_t)__shfl((int)col, w, 64);
       const float wlp = __shfl(lp, w, 64);
       const float wcand = __shfl(cand, w, 64);
       const int wcar = __shfl((int)carried, w, 64);
       if (lane == w) ord = 64u + (uint32_t)lane;
-      if (lane == i) {
-        my_parent = (uint32_t)ws;
-        my_C = wcand;
-        if (wcar) {
-          my_flag = kBeamFinished;
-          my_len = sh.len[ws];
-        } else {
-          my_tok = a.ids ? a.ids[wcol] : wcol;
-          my_lp = wlp;
-          my_flag = my_tok == a.eos ? kBeamFinished : kBeamLive;
-          my_len = (uint32_t)a.t + 1u;
-        }
-      }
+      if (lane == i) bm_fill_slot(a, mine, w >> 3, wcar != 0, wcol, wlp, wcand, sh.len);
     }
-    if (lane < k) {
-      const int r = r0 + lane;
-      a.parent[r] = my_parent;
-      a.token[r] = my_tok;
-      a.token_score[r] = my_lp;
-      a.totals_out[r] = my_C;
-      a.flags_out[r] = my_flag;
-      if (a.len_out) a.len_out[r] = my_len;
-      if (a.step_word) a.step_word[r] = (uint32_t)a.t + 1u;
-      sh.n_flag[lane] = my_flag;
-      sh.n_parent[lane] = my_parent;
-      sh.n_tok[lane] = my_tok;
-    }
+    if (lane < k) bm_store_slot(a, r0 + lane, lane, mine, sh.n_flag, sh.n_parent, sh.n_tok);
   }
   __syncthreads();
   if (!a.state_dst) return;  // (the whole grid) the op-level call ends here
 
-  if (tid == 0) {  // a source is done when no slot is live: counted once
-    bool live = false;
-    for (int i = 0; i < k; ++i) live = live || sh.n_flag[i] == kBeamLive;
-    if (!live && a.done[b] == 0u) {
-      a.done[b] = 1u;
-      atomicAdd(a.n_finished, 1);
-    }
-  }
-  // the SSRU states by parent, from one block into the other (a dead slot: zeros)
-  const size_t R = (size_t)a.B * k;
-  const int D4 = D >> 2;
-  for (int u = tid; u < a.Ld * k * D4; u += kBmThreads) {
-    const int l = u / (k * D4), rem = u - l * (k * D4);
-    const int i = rem / D4, d4 = rem - i * D4;
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (sh.n_flag[i] != kBeamDead)
-      v = reinterpret_cast<const float4 *>(a.state_src + ((size_t)l * R + (size_t)(r0 + (int)sh.n_parent[i])) * D)[d4];
-    reinterpret_cast<float4 *>(a.state_dst + ((size_t)l * R + (size_t)(r0 + i)) * D)[d4] = v;
-  }
-  // the next step's input rows: the token's embedding of a live slot (embed1's expression), the zero embedding otherwise
-  for (int u = tid; u < k * D; u += kBmThreads) {
-    const int i = u / D, d = u - i * D;
-    float x;
-    if (sh.n_flag[i] == kBeamLive) {
-      const float v = (float)a.emb.wemb[(size_t)embed_row(a.emb, sh.n_tok[i]) * D + d] * a.emb.inv_mult;
-      x = v * a.emb.sqrt_d;
-    } else {
-      x = 0.0f * a.emb.sqrt_d;
-    }
-    a.dx[(size_t)r0 * D + u] = x + a.emb.pos[d];
-  }
+  bm_step_tail<kBmThreads>(a, b, tid, sh.n_flag, sh.n_parent, sh.n_tok);
 }
 
 __global__ __launch_bounds__(kBmThreads) void beam_finish_kernel(BeamFinishArgs a) {
@@ -285,6 +188,7 @@ __global__ __launch_bounds__(kBmThreads) void beam_finish_kernel(BeamFinishArgs 
     if (lane == 0) {
       a.out_len[o] = al ? a.len[r0 + f] : 0u;
       a.out_totals[o] = al ? a.totals[r0 + f] : ninf;
+      if (a.out_perturbed) a.out_perturbed[o] = al ? a.perturbed[r0 + f] : ninf;
     }
     if (!al) continue;
     int cur = f;
@@ -335,6 +239,7 @@ hipError_t launch_beam_finish(const BeamFinishArgs &a, hipStream_t st) {
   if (!a.parent || !a.token || !a.token_score || !a.totals || !a.flags || !a.len || !a.lengths || !a.out_ids || !a.out_len || !a.out_totals)
     return hipErrorInvalidValue;
   if (a.out_align && !a.align_hist) return hipErrorInvalidValue;
+  if (a.out_perturbed && !a.perturbed) return hipErrorInvalidValue;
   hipLaunchKernelGGL(beam_finish_kernel, dim3(a.B), dim3(kBmThreads), 0, st, a);
   return hipGetLastError();
 }

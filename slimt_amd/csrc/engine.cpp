@@ -5,6 +5,7 @@
 #include "scores.h"
 #include "truncation.h"
 #include "beam.h"
+#include "beam_sampled.h"
 #include "launch_choice.h"
 
 #include <algorithm>
@@ -1297,7 +1298,7 @@ void ctx_free(slimt_hip_ctx *c) {
                     &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->tr_logits, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag,
-                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage, &c->cs_stage, &c->cu_ws, &c->bm_state, &c->bm_slots, &c->bm_hist, &c->bm_align, &c->bm_stage};
+                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage, &c->cs_stage, &c->cu_ws, &c->bm_state, &c->bm_slots, &c->bm_hist, &c->bm_align, &c->bm_stage, &c->bm_sampled};
   for (auto *b : bufs) b->release();
   free_affine(c->out_sl);
   if (c->n_finished_host) (void)hipHostFree(c->n_finished_host);
@@ -1587,6 +1588,15 @@ extern "C" int slimt_hip_ctx_set_fanout_consensus_units(slimt_hip_ctx *ctx, int 
   return 0;
 }
 
+extern "C" int slimt_hip_ctx_set_beam_sampling(slimt_hip_ctx *ctx, const uint64_t *keys, size_t n, float *perturbed) {
+  if (n == 0 && (keys || perturbed)) return fail(-1, "beam sampling: n = 0 disarms and takes no arrays");
+  if (!ctx) return fail(-1, "null argument");
+  ctx->armed.sb_n = n;  // (checked against the call's sources by the beam call that takes it; 0: nothing armed)
+  ctx->armed.sb_keys = keys;
+  ctx->armed.sb_perturbed = perturbed;
+  return 0;
+}
+
 extern "C" int slimt_hip_ctx_set_score_alternatives(slimt_hip_ctx *ctx, uint32_t k, uint32_t *alt_ids, float *alt_scores,
                                                     uint32_t *rank) {
   // (the value first, like the temperature)
@@ -1805,8 +1815,9 @@ struct MergePlan {
 // ctx->armed here -- consumed whether or not the call then succeeds -- checked against the call's n batches, and becomes
 // ctx->call, the record every inner function reads; `user` holds the per-batch arrays as the caller gave them, one entry per
 // batch, for the entry point to hand on: as they are where they are device memory (options_in_place), through
-// stage_options where they are host memory. The checks run scores -> prefix -> sampling -> truncation -> consensus and the
-// first refusal is the call's (rc); a truncated call must be sampled, so the truncation is looked at behind the sampling.
+// stage_options where they are host memory. The checks run scores -> prefix -> sampling -> truncation -> consensus -> beam
+// sampling and the first refusal is the call's (rc); a truncated call must be sampled, so the truncation is looked at behind
+// the sampling. Beam sampling (slimt_hip_ctx_set_beam_sampling) is for the beam entry points (beam) only.
 // While call.truncated or call.fanout is set fused_decoder_allowed() is false: the call decodes with the per-stage kernels
 // and is never merged; the context's decode mode is not touched and still chooses the encoder. Consensus is for the
 // fan-out entry points (fanout) only: any other call that finds it armed is refused. The destructor empties ctx->call.
@@ -1815,12 +1826,12 @@ struct CallOptions {
   slimt_hip_ctx *c;
   std::vector<BatchOptions> user;
   int rc = 0;
-  CallOptions(slimt_hip_ctx *ctx, size_t n, bool fanout = false) : c(ctx), user(n) {
+  CallOptions(slimt_hip_ctx *ctx, size_t n, bool fanout = false, bool beam = false) : c(ctx), user(n) {
     if (!c) return;
     const ArmedOptions a = std::move(c->armed);
     c->armed = {};
     c->call = {};
-    rc = take(a, n, fanout);
+    rc = take(a, n, fanout, beam);
     if (rc) c->call = {};
   }
   ~CallOptions() {
@@ -1847,6 +1858,7 @@ struct CallOptions {
     if (B * (size_t)beam > c->max_B)
       return fail(-1, "beam: %zu sources of beam %d exceed the context's max_batch %zu", B, beam, c->max_B);
     if (B == 0) return fail(-1, "empty batch");
+    if (call.sb_n && call.sb_n != B) return fail(-1, "beam sampling: %zu sources armed, the call has %zu", call.sb_n, B);
     RCCHK(open_fanout(B * (size_t)beam));
     c->call.beam = beam;
     c->call.beam_mode = mode;
@@ -1856,7 +1868,7 @@ struct CallOptions {
   }
 
  private:
-  int take(const ArmedOptions &a, size_t n, bool fanout) {
+  int take(const ArmedOptions &a, size_t n, bool fanout, bool beam) {
     CallState &call = c->call;
     if (!a.scores.empty()) {
       if (a.scores.size() != n) return fail(-1, "scores: %zu destinations armed, the call has %zu batches", a.scores.size(), n);
@@ -1897,6 +1909,12 @@ struct CallOptions {
       call.cs_beta2 = a.cs_beta2;
       call.cs_best = a.cs_best;
       call.cs_util = a.cs_util;
+    }
+    if (a.sb_n) {
+      if (!beam) return fail(-1, "beam sampling: armed on a translate call that is not a beam call (slimt_hip_translate_beam*)");
+      call.sb_n = a.sb_n;  // (checked against the call's sources by open_beam)
+      call.sb_keys = a.sb_keys;
+      call.sb_perturbed = a.sb_perturbed;
     }
     return 0;
   }
@@ -2428,10 +2446,24 @@ int beam_steps(slimt_hip_ctx *c, size_t B, size_t S, size_t Tmax, uint32_t eos_i
   sa.dx = c->dx.as<float>();
   sa.done = done;
   sa.n_finished = c->n_finished.as<int>();
+  // sampled without replacement (slimt_hip_ctx_set_beam_sampling): beam_sampled.hip's selection in place of beam_select.hip's,
+  // over the slots' perturbed values beside their totals; everything else is the un-armed call's path
+  const bool sampled = call.sb_n != 0;
+  BeamSampledArgs ss;
+  if (sampled) {
+    HIPCHK(c->bm_sampled.reserve(R * 4));
+    ss.keys = call.sb_dev_keys;
+    ss.perturbed_in = ss.perturbed_out = c->bm_sampled.as<float>();
+  }
+  auto select = [&](const BeamSelectArgs &step) {
+    if (!sampled) return launch_beam_select(step, st);
+    ss.step = step;
+    return launch_beam_select_sampled(ss, st);
+  };
   {
     BeamSelectArgs ia = sa;  // the start state: slot 0 live at +0, the zero embedding (decode_setup zeroed block 0's states)
     ia.init = 1;
-    const hipError_t he = launch_beam_select(ia, st);
+    const hipError_t he = select(ia);
     if (he != hipSuccess) return fail((int)he, "beam start: %s", hipGetErrorString(he));
   }
   size_t t = 0;
@@ -2460,7 +2492,7 @@ int beam_steps(slimt_hip_ctx *c, size_t B, size_t S, size_t Tmax, uint32_t eos_i
     sa.token_score = h_score + t * R;
     sa.state_src = blocks[t & 1];
     sa.state_dst = blocks[(t + 1) & 1];
-    const hipError_t he = launch_beam_select(sa, st);
+    const hipError_t he = select(sa);
     if (he != hipSuccess) return fail((int)he, "beam selection: %s", hipGetErrorString(he));
   }
   BeamFinishArgs fa;
@@ -2471,6 +2503,10 @@ int beam_steps(slimt_hip_ctx *c, size_t B, size_t S, size_t Tmax, uint32_t eos_i
   fa.lengths = c->lengths.as<uint32_t>();
   fa.out_ids = d_out_ids; fa.out_len = d_out_len;
   fa.out_totals = call.bm_dev_totals; fa.out_scores = call.bm_dev_scores; fa.out_align = d_align;
+  if (sampled && call.sb_dev_perturbed) {
+    fa.perturbed = c->bm_sampled.as<float>();
+    fa.out_perturbed = call.sb_dev_perturbed;
+  }
   const hipError_t he = launch_beam_finish(fa, st);
   if (he != hipSuccess) return fail((int)he, "beam finish: %s", hipGetErrorString(he));
   return 0;
@@ -3357,6 +3393,16 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const BatchOpti
     call.bm_dev_totals = ctx->bm_stage.as<float>();
     call.bm_dev_scores = call.bm_scores ? ctx->bm_stage.as<float>() + R : nullptr;
     if (call.bm_scores) HIPCHK(hipMemsetAsync(call.bm_dev_scores, 0, R * Tmax * 4, st));
+    if (call.sb_n) {  // (sampled: the slots' values [R], then the perturbed values [R] staged, then the keys [B] unless pinned)
+      HIPCHK(ctx->bm_sampled.reserve(2 * R * 4 + B * 8));
+      call.sb_dev_perturbed = call.sb_perturbed ? ctx->bm_sampled.as<float>() + R : nullptr;
+      call.sb_dev_keys = call.sb_keys ? static_cast<const uint64_t *>(host_device_view(call.sb_keys)) : nullptr;
+      if (call.sb_keys && !call.sb_dev_keys) {
+        uint64_t *staged = reinterpret_cast<uint64_t *>(ctx->bm_sampled.as<float>() + 2 * R);
+        HIPCHK(hipMemcpyAsync(staged, call.sb_keys, B * 8, hipMemcpyHostToDevice, st));
+        call.sb_dev_keys = staged;
+      }
+    }
   }
   float *const scores = user.scores;  // (a scored call: the caller's [B][Tmax] host array)
   if (!wait && persistent) {
@@ -3397,6 +3443,7 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const BatchOpti
   if (call.beam) {
     HIPCHK(hipMemcpyAsync(call.bm_totals, call.bm_dev_totals, R * 4, hipMemcpyDeviceToHost, st));
     if (call.bm_scores) HIPCHK(hipMemcpyAsync(call.bm_scores, call.bm_dev_scores, R * Tmax * 4, hipMemcpyDeviceToHost, st));
+    if (call.sb_perturbed) HIPCHK(hipMemcpyAsync(call.sb_perturbed, call.sb_dev_perturbed, R * 4, hipMemcpyDeviceToHost, st));
   }
   if (wait) RCCHK(slimt_hip_ctx_synchronize(ctx));  // sleeps on a blocking-sync event (a worker per context: no spinning)
   return 0;
@@ -3505,7 +3552,7 @@ int translate_beam_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const uint
                         size_t S, int beam, int length_mode, const uint32_t *shortlist, size_t n_shortlist, float limit_factor,
                         uint32_t eos_id, uint32_t *out_ids, uint32_t *out_len, float *totals, float *token_scores, float *align,
                         bool wait) {
-  CallOptions opt(ctx, 1);
+  CallOptions opt(ctx, 1, false, true);
   // (what needs no context is checked first: these refusals say what is wrong with the arguments, context or not)
   RCCHK(beam_arguments(beam, length_mode));
   if (!ctx || !totals) return fail(-1, "null argument");
@@ -3547,7 +3594,7 @@ extern "C" int slimt_hip_translate_beam_device(slimt_hip_ctx *ctx, const uint32_
                                                size_t S, int beam, int length_mode, const uint32_t *d_shortlist, size_t n_shortlist,
                                                float limit_factor, uint32_t eos_id, uint32_t *d_out_ids, uint32_t *d_out_len,
                                                float *d_totals, float *d_token_scores, float *d_align, int steps_hint) {
-  CallOptions opt(ctx, 1);
+  CallOptions opt(ctx, 1, false, true);
   RCCHK(beam_arguments(beam, length_mode));
   if (!ctx || !d_src_ids || !d_lengths || !d_out_ids || !d_out_len || !d_totals) return fail(-1, "null argument");
   RCCHK(opt.rc);
@@ -3562,6 +3609,8 @@ extern "C" int slimt_hip_translate_beam_device(slimt_hip_ctx *ctx, const uint32_
   ctx->call.row_src = ctx->fo_stage.as<uint32_t>();
   ctx->call.bm_dev_totals = d_totals;
   ctx->call.bm_dev_scores = d_token_scores;
+  ctx->call.sb_dev_keys = ctx->call.sb_keys;  // (device memory, like the other arrays of this entry point)
+  ctx->call.sb_dev_perturbed = ctx->call.sb_perturbed;
   return translate_device(ctx, d_src_ids, d_lengths, d_shortlist, B, S, n_shortlist, limit_factor, eos_id, d_out_ids, d_out_len,
                           d_align, steps_hint);
 }
@@ -3612,6 +3661,71 @@ extern "C" int slimt_hip_beam_step(const float *logits, size_t B, int beam, size
   HIPCHK(hipMemcpyAsync(token_score, o + 2 * R, R * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(totals_out, o + 3 * R, R * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(flags_out, o + 4 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// slimt_hip_beam_step with beam_sampled.hip's selection: the sources' keys, the step and the slots' perturbed values beside it.
+extern "C" int slimt_hip_beam_step_sampled(const float *logits, size_t B, int beam, size_t N, const uint32_t *ids, const uint64_t *keys,
+                                           uint32_t step, const float *totals_in, const float *perturbed_in, const uint32_t *flags_in,
+                                           uint32_t eos_id, uint32_t *parent, uint32_t *token, float *token_score, float *totals_out,
+                                           float *perturbed_out, uint32_t *flags_out) {
+  RCCHK(beam_arguments(beam, 0));
+  if (!logits || !totals_in || !perturbed_in || !flags_in || !parent || !token || !token_score || !totals_out || !perturbed_out ||
+      !flags_out || !B || !N)
+    return fail(-1, "bad argument");
+  if (N >= (size_t)slimt_hip::kBeamMaxN) return fail(-1, "beam: an output layer of %zu columns (2^20 or more)", N);
+  if (step > 0x7fffffffu) return fail(-1, "beam_step_sampled: step %u is above %d", step, 0x7fffffff);
+  const size_t R = B * (size_t)beam;
+  if (B > 0x7fffffffu / (size_t)beam) return fail(-1, "beam_step_sampled: more than %d rows", 0x7fffffff);
+  for (size_t r = 0; r < R; ++r) {
+    if (flags_in[r] > slimt_hip::kBeamFinished)
+      return fail(-1, "beam_step_sampled: flag %u of row %zu is not 0 (dead), 1 (live) or 2 (finished)", flags_in[r], r);
+    if (flags_in[r] == slimt_hip::kBeamLive && !(std::isfinite(totals_in[r]) && std::isfinite(perturbed_in[r])))
+      return fail(-1, "beam_step_sampled: the total or the perturbed value of live row %zu is not finite", r);
+    if (flags_in[r] == slimt_hip::kBeamFinished && (totals_in[r] != totals_in[r] || perturbed_in[r] != perturbed_in[r]))
+      return fail(-1, "beam_step_sampled: the total or the perturbed value of finished row %zu is NaN", r);
+  }
+  Tmp3 t;
+  hipStream_t st = nullptr;
+  HIPCHK(t.a.reserve(R * N * 4));
+  HIPCHK(t.b.reserve(N * 4));
+  HIPCHK(t.c.reserve(3 * R * 4));
+  HIPCHK(t.d.reserve(6 * R * 4));
+  HIPCHK(t.e.reserve(B * 8));
+  HIPCHK(hipMemcpyAsync(t.a.p, logits, R * N * 4, hipMemcpyHostToDevice, st));
+  if (ids) HIPCHK(hipMemcpyAsync(t.b.p, ids, N * 4, hipMemcpyHostToDevice, st));
+  if (keys) HIPCHK(hipMemcpyAsync(t.e.p, keys, B * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.p, totals_in, R * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.as<char>() + R * 4, flags_in, R * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.as<char>() + 2 * R * 4, perturbed_in, R * 4, hipMemcpyHostToDevice, st));
+  BeamSampledArgs sa;
+  BeamSelectArgs &a = sa.step;
+  a.logits = t.a.as<float>();
+  a.B = (int)B;
+  a.k = beam;
+  a.N = (int)N;
+  a.ids = ids ? t.b.as<uint32_t>() : nullptr;
+  a.eos = eos_id;
+  a.t = (int)step;
+  a.totals_in = t.c.as<float>();
+  a.flags_in = t.c.as<uint32_t>() + R;
+  sa.perturbed_in = t.c.as<float>() + 2 * R;
+  sa.keys = keys ? t.e.as<uint64_t>() : nullptr;
+  uint32_t *o = t.d.as<uint32_t>();
+  a.parent = o;
+  a.token = o + R;
+  a.token_score = reinterpret_cast<float *>(o + 2 * R);
+  a.totals_out = reinterpret_cast<float *>(o + 3 * R);
+  a.flags_out = o + 4 * R;
+  sa.perturbed_out = reinterpret_cast<float *>(o + 5 * R);
+  HIPCHK(launch_beam_select_sampled(sa, st));
+  HIPCHK(hipMemcpyAsync(parent, o, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(token, o + R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(token_score, o + 2 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(totals_out, o + 3 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(flags_out, o + 4 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(perturbed_out, o + 5 * R, R * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return 0;
 }

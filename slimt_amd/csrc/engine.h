@@ -76,6 +76,10 @@ struct ArmedOptions {
   bool cs_units = false;  // the selection over unit rows (slimt_hip_ctx_set_fanout_consensus_units): same slot, last arming wins
   uint32_t *cs_best = nullptr;
   double *cs_util = nullptr;
+  // sampling without replacement on a beam call (slimt_hip_ctx_set_beam_sampling): armed for sb_n > 0 sources
+  size_t sb_n = 0;
+  const uint64_t *sb_keys = nullptr;  // [sb_n], NULL: slimt_hip_sampling_key(0, b)
+  float *sb_perturbed = nullptr;      // nullable [sb_n][beam]
 };
 
 // The translate call in progress: filled by its CallOptions (engine.cpp), reset as a whole when the entry point returns.
@@ -99,6 +103,11 @@ struct CallState {
   int beam = 0, beam_mode = 0;
   float *bm_totals = nullptr, *bm_scores = nullptr, *bm_dev_totals = nullptr, *bm_dev_scores = nullptr;
   float *bm_state_cur = nullptr;  // ... and the SSRU state block [Ld][rows][D] of the step in progress
+  // ... sampled without replacement (slimt_hip_ctx_set_beam_sampling; beam_sampled.hip's selection): the sources' keys [B]
+  // (nullable) and the hypotheses' perturbed values [B][beam] (nullable) as the caller gave them, and as the kernels address them
+  size_t sb_n = 0;  // the armed count of sources (0: not armed)
+  const uint64_t *sb_keys = nullptr, *sb_dev_keys = nullptr;
+  float *sb_perturbed = nullptr, *sb_dev_perturbed = nullptr;
   BatchOptions dev;  // the current unmerged batch's options as the kernels address them (a merged launch: MergePlan::opt)
 };
 
@@ -263,6 +272,9 @@ struct slimt_hip_ctx {
   // the slots' totals / flags / lengths / step words and the sources' done words, the steps' records [Tmax][rows] x 3, the
   // decoder's alignment rows [rows][Tmax][S], device staging of a host call's totals and token scores; the rows' sources
   slimt_hip::DevBuf bm_state, bm_slots, bm_hist, bm_align, bm_stage;
+  // ... sampled without replacement, reserved by the first armed beam call: the slots' perturbed values [rows], then the device
+  // staging of a host call's perturbed values [rows] and of its pageable keys [B]
+  slimt_hip::DevBuf bm_sampled;
   std::vector<uint32_t> bm_row_src;
   slimt_hip::DevBuf prev, out_ids, out_len, finished, n_finished, align;
   slimt_hip::DevBuf shortlist;

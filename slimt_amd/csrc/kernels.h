@@ -915,8 +915,25 @@ struct BeamFinishArgs {
   uint32_t *out_ids = nullptr, *out_len = nullptr;  // [B][k][Tmax], [B][k]
   float *out_totals = nullptr;                       // [B][k]
   float *out_scores = nullptr, *out_align = nullptr;  // nullable [B][k][Tmax], [B][k][Tmax][S]
+  // a sampled beam call (both or neither): the final slots' perturbed values [B k] and their place in the order [B][k]
+  const float *perturbed = nullptr;
+  float *out_perturbed = nullptr;
 };
 hipError_t launch_beam_finish(const BeamFinishArgs &a, hipStream_t st);
+
+// ---- sampling without replacement on a beam call: the selection over Gumbel-perturbed totals (beam_sampled.hip) --------
+// One step of stochastic beam search (beam_sampled.h; include/slimt_hip.h, slimt_hip_ctx_set_beam_sampling): `step` is
+// launch_beam_select's step with every column of every live slot perturbed and the survivors conditioned on their
+// parent's value. keys [B]: the sources' keys (nullptr: slimt_hip_sampling_key(0, b)); perturbed_in / _out [B k]: the
+// slots' values G (may be the same memory). step.init: the start state, which also sets G (+0 for slot 0, -inf otherwise).
+// One 1024-thread workgroup per source, its 16 waves dealt to the live slots.
+struct BeamSampledArgs {
+  BeamSelectArgs step;
+  const uint64_t *keys = nullptr;
+  const float *perturbed_in = nullptr;
+  float *perturbed_out = nullptr;
+};
+hipError_t launch_beam_select_sampled(const BeamSampledArgs &a, hipStream_t st);
 
 // the column means (rounded) of an f32 K/V cache [Ld][K, V][B * S][D]: centre[(2 l + p) * D + d] (FusedDecodeArgs::kv_centre)
 hipError_t launch_kv_centres(const float *kv, int Ld, int B, int S, int D, unsigned long long *sums, int *centre, hipStream_t st);

@@ -562,7 +562,7 @@ class Service:
 
     def sample_and_select(self, model: Model, sources: Sequence[str], n: int, sampling, truncation=None,
                           max_order: Optional[int] = None, beta2: int = 4, encoding: Encoding = Encoding.UTF8,
-                          utility: str = "tokens") -> List[Response]:
+                          utility: str = "tokens", without_replacement: bool = False) -> List[Response]:
         """translate(samples=n) followed by the consensus (minimum-Bayes-risk) pick: of the n draws of every sentence, the one
         that agrees most with the others -- the mean token n-gram F (orders 1..max_order, integer beta2 = beta^2; 4 is chrF's)
         against the sentence's other draws (include/slimt_hip.h, slimt_hip_consensus_select). The pick is made on the device
@@ -574,7 +574,12 @@ class Service:
         (slimt_hip_consensus_select_units over model.consensus_units()), so two segmentations of the same words count as the
         same translation. The "chrf" pick runs on the device over the samples translate(samples=n) returns, in a call of its
         own behind the fan-out calls; a draw of more than 1024 characters or 256 tokens is refused (the engine's message; a
-        segment of at most ENGINE_LIMIT tokens yields at most 192)."""
+        segment of at most ENGINE_LIMIT tokens yields at most 192).
+        without_replacement: the n draws of a sentence are n DISTINCT translations, sampled without replacement by
+        beam_search(beam=n, sample_seed=seed) (temperature 1, no truncation, n <= capi.MAX_BEAM); the consensus pick is
+        made in a call of its own over the returned rows, as the "chrf" path's is, so no pick is decided by duplicates."""
+        if without_replacement:
+            return self._select_without_replacement(model, sources, n, sampling, truncation, max_order, beta2, encoding, utility)
         if sampling is None or int(n) < 1:
             raise ValueError("sample_and_select: n >= 1 and sampling=(temperature, seed)")
         if utility not in ("tokens", "chrf"):
@@ -624,8 +629,48 @@ class Service:
             resp.to(encoding)
         return out
 
+    def _select_without_replacement(self, model, sources, n, sampling, truncation, max_order, beta2, encoding, utility):
+        """sample_and_select(without_replacement=True): _beam_ranked draws n distinct rows per sentence, one consensus call
+        over the returned rows picks, and the Responses are built from the winners"""
+        n = int(n)
+        if n < 1 or n > capi.MAX_BEAM:
+            raise ValueError(f"sample_and_select: without replacement at most {capi.MAX_BEAM} samples are drawn, not {n}")
+        if sampling is None or float(sampling[0]) != 1.0 or truncation is not None:
+            raise ValueError("sample_and_select: without replacement takes sampling=(1.0, seed) and no truncation")
+        if utility not in ("tokens", "chrf"):
+            raise ValueError(f"sample_and_select: utility is 'tokens' or 'chrf', not {utility!r}")
+        if max_order is None:
+            max_order = 6 if utility == "chrf" else 4
+        processed, ranked, _ = self._beam_ranked(model, sources, n, False, int(sampling[1]))
+        per_request = [segs for _, segs in processed]
+        histories = [[None] * len(segs) for segs in per_request]
+        picked = [([0.0] * len(segs), [0] * len(segs)) for segs in per_request]
+        where = [(r, i) for r, segs in enumerate(per_request) for i in range(len(segs))]
+        per_call = 65536 // n  # (the call's bound on its rows)
+        for at in range(0, len(where), per_call):
+            part = where[at:at + per_call]
+            rows = [ranked[j][r][i][0] for r, i in part for j in range(n)]
+            ids = np.zeros((len(rows), max(1, max(len(x) for x in rows))), np.uint32)
+            for c, x in enumerate(rows):
+                ids[c, :len(x)] = x
+            src = np.repeat(np.arange(len(part)), n)
+            if utility == "chrf":
+                unit_off, units = model.consensus_units()
+                u, best = capi.consensus_select_units(ids, [len(x) for x in rows], src, len(part), unit_off, units, max_order, beta2)
+            else:
+                u, best = capi.consensus_select(ids, [len(x) for x in rows], src, len(part), max_order, beta2)
+            for e, (r, i) in enumerate(part):
+                c = e * n if best[e] == capi.NO_ROW else int(best[e])  # (every draw empty: the first)
+                histories[r][i] = ranked[c - e * n][r][i]
+                picked[r][0][i], picked[r][1][i] = float(u[c]), c - e * n
+        out = self._respond_many(model, [src for src, _ in processed], histories)
+        for resp, (u, j) in zip(out, picked):
+            resp.utility, resp.sample_index = u, j
+            resp.to(encoding)
+        return out
+
     def beam_search(self, model: Model, texts: Sequence[str], beam: int, mean: bool = False,
-                    encoding: Encoding = Encoding.UTF8) -> List[Response]:
+                    encoding: Encoding = Encoding.UTF8, sample_seed: Optional[int] = None) -> List[Response]:
         """Beam search with n-best output (include/slimt_hip.h, slimt_hip_translate_beam): every sentence is decoded with
         `beam` = k slots (1..capi.MAX_BEAM) from one encoding of it and comes back as its k best hypotheses, ordered by their
         summed log-probability (mean=True: per token). Each Response carries `nbest`, its k alternatives as Responses
@@ -633,16 +678,36 @@ class Service:
         hypotheses has an empty one there), and `hypothesis_scores`, the engine's total per sentence; the Response returned
         is rank 0. Batches follow _batches' rule with at most max_words / beam sentences per call; the calls go through one
         capi.Context per model on model.engine, under the Service's lock, with the model's lexical shortlist generated per
-        batch where it has one. A segment above ENGINE_LIMIT tokens is refused."""
+        batch where it has one. A segment above ENGINE_LIMIT tokens is refused.
+        sample_seed: the k hypotheses of every sentence are SAMPLED WITHOUT REPLACEMENT from the model's distribution
+        (stochastic beam search; slimt_hip_ctx_set_beam_sampling) -- k distinct translations, each with its exact
+        log-probability, still ordered by it. Sentence i of the request (counted over all texts) is searched under
+        capi.sampling_key(sample_seed, i), wherever the batcher puts it."""
         k = int(beam)
         if k < 1 or k > capi.MAX_BEAM:
             raise ValueError(f"beam_search: a beam of 1..{capi.MAX_BEAM} expected, not {beam}")
+        processed, ranked, totals_of = self._beam_ranked(model, texts, k, mean, sample_seed)
+        sources = [src for src, _ in processed]
+        alts = [self._respond_many(model, sources, h) for h in ranked]
+        out = alts[0]
+        for j, alt in enumerate(alts):
+            for r, resp in enumerate(alt):
+                resp.hypothesis_scores = totals_of[j][r]
+        for r, resp in enumerate(out):
+            resp.nbest = [a[r] for a in alts]
+            resp.to(encoding)
+        return out
+
+    def _beam_ranked(self, model: Model, texts: Sequence[str], k: int, mean: bool, sample_seed: Optional[int]):
+        """beam_search's calls: (the processed texts, ranked[j][request][segment] = rank j's (token ids, alignment, token
+        scores), totals_of[j][request][segment])"""
         processed = model.processor.process_many(texts, self.wrap_length, self.workers)
         per_request = [segs for _, segs in processed]
         units = [_Unit(r, i, list(seg)) for r, segs in enumerate(per_request) for i, seg in enumerate(segs)]
         if any(len(u.words) > self.ENGINE_LIMIT for u in units):
             raise ValueError(f"beam_search: a segment has more than {self.ENGINE_LIMIT} tokens")
         eos = model.vocabulary.eos_id()
+        key_of = {} if sample_seed is None else {(u.request, u.index): capi.sampling_key(sample_seed, i) for i, u in enumerate(units)}
         ranked = [[[None] * len(segs) for segs in per_request] for _ in range(k)]
         totals_of = [[[0.0] * len(segs) for segs in per_request] for _ in range(k)]
         per_call = max(1, self.max_words // k)
@@ -666,6 +731,8 @@ class Service:
                 for b, u in enumerate(batch):
                     ids[b, :len(u.words)] = u.words
                     lens[b] = len(u.words)
+                if key_of:  # (armed for the next call, which is this batch's)
+                    ctx.set_beam_sampling(np.array([key_of[u.request, u.index] for u in batch], np.uint64), B)
                 if model.shortlist_generator is not None:
                     out, ln, tot, sc, al = ctx.translate_beam_generated(model.shortlist_generator, ids, lens, k, self.limit_factor,
                                                                         eos, mean, want_align=True)
@@ -676,16 +743,7 @@ class Service:
                         n, L = int(ln[b, j]), int(lens[b])
                         ranked[j][u.request][u.index] = (out[b, j, :n].tolist(), al[b, j, :n, :L].copy(), sc[b, j, :n].copy())
                         totals_of[j][u.request][u.index] = float(tot[b, j])
-        sources = [src for src, _ in processed]
-        alts = [self._respond_many(model, sources, h) for h in ranked]
-        out = alts[0]
-        for j, alt in enumerate(alts):
-            for r, resp in enumerate(alt):
-                resp.hypothesis_scores = totals_of[j][r]
-        for r, resp in enumerate(out):
-            resp.nbest = [a[r] for a in alts]
-            resp.to(encoding)
-        return out
+        return processed, ranked, totals_of
 
     def pivot(self, first: Model, second: Model, texts: Sequence[str], html: bool = False,
               scores: bool = False, sampling=None, truncation=None) -> List[Response]:
