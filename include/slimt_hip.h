@@ -107,6 +107,17 @@ int slimt_hip_sample_truncated(const float *logits, size_t M, size_t N, const ui
                                float temperature, uint32_t top_k, float top_p,
                                const uint64_t *keys, const uint32_t *steps,
                                uint32_t *columns, float *thresholds, uint32_t *kept, float *scores);
+/* One floored sampled step over the caller's logits [M][N] (host pointers; the
+ * kernel of slimt_hip_ctx_set_sampling_floor alone, which states the rule). N below
+ * 2^29. ids, keys, steps: as in slimt_hip_sample_truncated. min_p and epsilon are
+ * checked as by slimt_hip_ctx_set_sampling_floor; both 0 keeps every valid column.
+ * columns[r]: the drawn column, or 0 with scores[r] NaN when nothing is kept or
+ * logit 0 of the row is NaN; maxima[r] = M, the row's maximum valid z (-inf where
+ * there is none); kept[r] = |K|; scores[r]: the step's score. */
+int slimt_hip_sample_floor(const float *logits, size_t M, size_t N, const uint32_t *ids,
+                           float temperature, float min_p, float epsilon,
+                           const uint64_t *keys, const uint32_t *steps,
+                           uint32_t *columns, float *maxima, uint32_t *kept, float *scores);
 /* highway (TensorOps.cc:662-682): out = sigmoid(g)*x + (1-sigmoid(g))*y */
 int slimt_hip_highway(const float *x, const float *y, const float *g, size_t n,
                       float *out);
@@ -383,6 +394,55 @@ int slimt_hip_ctx_set_sampling(slimt_hip_ctx *ctx, float temperature, const uint
  * The _many_ entry points do not merge a truncated call: it is translated batch by
  * batch, in order, on the same stream, each batch within its own step limit. */
 int slimt_hip_ctx_set_sampling_truncation(slimt_hip_ctx *ctx, uint32_t top_k, float top_p);
+/* Min-p and epsilon floors under the sampling of the NEXT translate call on ctx,
+ * which must be a sampled one (slimt_hip_ctx_set_sampling): armed for that call,
+ * which consumes it whether it succeeds or fails, like every other per-call option.
+ * min_p: drop every token whose probability is below min_p times the most probable
+ * token's; epsilon: drop every token whose probability is below epsilon. 0 turns a
+ * floor off; with both 0 nothing is armed and the call is the plain sampled call,
+ * same kernels included. Both must be finite with 0 <= min_p <= 1 and
+ * 0 <= epsilon < 1, else a negative status at once. A translate call that finds a
+ * floor armed fails with a negative status and a message, and still consumes the
+ * setting, when no sampling is armed, when top-k / top-p truncation
+ * (slimt_hip_ctx_set_sampling_truncation) is armed too -- the two families are not
+ * combined -- or when it is a beam call (slimt_hip_translate_beam*).
+ *
+ * One drawn step. l_c, inv_T and z_c = l_c * inv_T are as for the truncation above;
+ * the definition is slimt_amd/csrc/floor.h.
+ *  1. Validity and n_valid as there. With n_valid == 0 nothing is kept: class 0 and
+ *     score NaN.
+ *  2. Weights. M is the maximum valid z and w_c = tr_weight(z_c, M) for EVERY valid
+ *     c (slimt_amd/csrc/truncation.h: the scale 2^24, the cut at -17 and tr_exp are
+ *     unchanged). Q = sum of w_c over the valid columns as uint64: exact in any
+ *     order, and below 2^53 because the output layer must have fewer than 2^29
+ *     columns (a wider one is refused).
+ *  3. min-p (skipped when min_p == 0). Column c passes iff
+ *       (double)w_c >= (double)min_p * 16777216.0        (the product is exact).
+ *  4. epsilon (skipped when epsilon == 0). Column c passes iff
+ *       (double)w_c >= (double)epsilon * (double)Q
+ *     (one IEEE double product; the left side and Q are exact integers).
+ *  5. K holds the valid columns that pass every armed test, plus every column with
+ *     z_c == M: the fallback when epsilon exceeds the largest probability, so K is
+ *     never empty. K depends on values alone, never on column order; ties at a
+ *     boundary are all in or all out.
+ *  6. Token and score are steps 4 and 5 of the truncation above over this K: the
+ *     first maximum of fmaf(l_c, inv_T, g(k_b, t, y_c)) from -FLT_MAX with strict >,
+ *     the lower column on a tie, and
+ *     forced_score(sum over K of exp(z_c - M), z_token - M, none). A NaN anywhere in
+ *     the row makes the score NaN.
+ * Forced steps (slimt_hip_ctx_set_target_prefix) draw nothing and are not floored:
+ * they are scored over the WHOLE layer, as in a truncated call.
+ * A sentence's floored translation depends on its key, the temperature, min_p and
+ * epsilon and on nothing else: not on its row, its neighbours, the decode mode, the
+ * entry point, fan-out or the shortlist's layout.
+ * Execution: like a truncated call a floored one DECODES with the per-stage kernels
+ * whatever mode the context is in (K/V cache format 3 included), the logits gemm
+ * storing the row, with one selection kernel per step
+ * (slimt_amd/csrc/sample_floor.hip: the row is read once and held in registers up
+ * to 4096 columns, streamed above); on a fan-out call per decoder row. The
+ * context's mode is not changed and slimt_hip_ctx_plan keeps reporting it. The
+ * _many_ entry points do not merge a floored call. */
+int slimt_hip_ctx_set_sampling_floor(slimt_hip_ctx *ctx, float min_p, float epsilon);
 /* Which kernels a translate call with source length S would use in the current
  * mode: *encoder_fused / *decoder_fused = 1 for the persistent kernels, 0 for
  * the per-stage ones. */

@@ -3,6 +3,7 @@
 #include "decoder_plan.h"
 #include "sampling.h"
 #include "scores.h"
+#include "floor.h"
 #include "truncation.h"
 #include "beam.h"
 #include "beam_sampled.h"
@@ -101,12 +102,12 @@ static const EnvKnobs &env() {
 
 // The persistent decoder runs the hoisted cross-attention order over a cache of accumulators; the reference's literal
 // sequence (K/V cache format 3) exists in the stage-wise attention kernel only (decode_kernels.hip, DQAttnArgs::literal)
-// ... and a truncated sampled call needs each step's whole row of logits, which only the stage-wise decoder stores; a
+// ... and a truncated or floored sampled call needs each step's whole row of logits, which only the stage-wise decoder stores; a
 // fan-out call's cross-attention looks a row's source up, which only the stage-wise one does (decode_fanout.hip). Every
 // decision that hangs on the persistent decoder -- the lean path, pinned arrays read in place, merged launches -- asks here;
 // the encoder is chosen as the context's mode says.
 static bool fused_decoder_allowed(const slimt_hip_ctx *c) {
-  return c->decode_mode != 1 && c->model->kv_format != 3 && !c->call.truncated && !c->call.fanout;
+  return c->decode_mode != 1 && c->model->kv_format != 3 && !c->call.truncated && !c->call.floored && !c->call.fanout;
 }
 // The decoder rows of the call in progress: a fan-out call's N, else one per source.
 static int decoder_rows(const slimt_hip_ctx *c) { return c->call.fanout ? c->call.rows : c->B; }
@@ -610,6 +611,64 @@ extern "C" int slimt_hip_sample_truncated(const float *logits, size_t M, size_t 
     scores[r] = slimt_hip::forced_score(h[2 * M + r], h[4 * M + r] - h[3 * M + r], none);
     thresholds[r] = h[5 * M + r];
     memcpy(&kept[r], &h[6 * M + r], 4);
+  }
+  return 0;
+}
+
+extern "C" int slimt_hip_sample_floor(const float *logits, size_t M, size_t N, const uint32_t *ids, float temperature, float min_p,
+                                      float epsilon, const uint64_t *keys, const uint32_t *steps, uint32_t *columns, float *maxima,
+                                      uint32_t *kept, float *scores) {
+  if (!(temperature > 0.0f) || !std::isfinite(temperature)) return fail(-1, "sampling: temperature %g is not finite and > 0", (double)temperature);
+  const float inv_T = 1.0f / temperature;
+  if (!(inv_T > 0.0f) || !std::isfinite(inv_T)) return fail(-1, "sampling: 1 / temperature %g is not finite and > 0", (double)temperature);
+  if (!slimt_hip::fl_valid(min_p, epsilon))
+    return fail(-1, "sampling floor: min_p %g is not in [0, 1] or epsilon %g is not in [0, 1)", (double)min_p, (double)epsilon);
+  if (!logits || !columns || !maxima || !kept || !scores || !M || !N) return fail(-1, "bad argument");
+  if (M > 0x7fffffffu || N > (size_t)kFloorMaxN) return fail(-1, "sample_floor: more than %d rows or %d columns", 0x7fffffff, kFloorMaxN);
+  std::vector<uint32_t> seeds(2 * M);  // the rows' hash words (sampling.h), as decode_begin_step_sm_kernel writes them
+  for (size_t r = 0; r < M; ++r) {
+    const uint64_t w = slimt_hip::sm_step_words(keys ? keys[r] : (uint64_t)r, steps ? steps[r] : 0u);
+    seeds[r] = (uint32_t)w;
+    seeds[M + r] = (uint32_t)(w >> 32);
+  }
+  Tmp3 t;
+  hipStream_t st = nullptr;
+  HIPCHK(t.a.reserve(M * N * 4));
+  HIPCHK(t.b.reserve(N * 4));
+  HIPCHK(t.c.reserve(2 * M * 4));
+  HIPCHK(t.d.reserve(6 * M * 4));
+  HIPCHK(hipMemcpyAsync(t.a.p, logits, M * N * 4, hipMemcpyHostToDevice, st));
+  if (ids) HIPCHK(hipMemcpyAsync(t.b.p, ids, N * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.p, seeds.data(), 2 * M * 4, hipMemcpyHostToDevice, st));
+  SampleFloorArgs a;
+  a.logits = t.a.as<float>();
+  a.B = (int)M;
+  a.N = (int)N;
+  a.inv_T = inv_T;
+  a.min_p = min_p;
+  a.epsilon = epsilon;
+  a.seeds = t.c.as<uint32_t>();
+  a.shortlist = ids ? t.b.as<uint32_t>() : nullptr;
+  float *o = t.d.as<float>();
+  a.part_val = o;
+  a.part_idx = reinterpret_cast<int *>(o + M);
+  a.part_sum = o + 2 * M;
+  a.part_mz = o + 3 * M;
+  a.part_zw = o + 4 * M;
+  a.kept = reinterpret_cast<uint32_t *>(o + 5 * M);
+  HIPCHK(launch_sample_floor(a, st));
+  std::vector<float> h(6 * M);
+  HIPCHK(hipMemcpyAsync(h.data(), t.d.p, 6 * M * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (size_t r = 0; r < M; ++r) {
+    int col;
+    memcpy(&col, &h[M + r], 4);
+    // the "none" rule of decode_begin_step_sm_kernel: no key beat the start value, or logit 0 is NaN -- class 0, score NaN
+    const bool none = col == 0x7fffffff || logits[r * N] != logits[r * N];
+    columns[r] = none ? 0u : (uint32_t)col;
+    scores[r] = slimt_hip::forced_score(h[2 * M + r], h[4 * M + r] - h[3 * M + r], none);
+    maxima[r] = h[3 * M + r];
+    memcpy(&kept[r], &h[5 * M + r], 4);
   }
   return 0;
 }
@@ -1552,6 +1611,16 @@ extern "C" int slimt_hip_ctx_set_sampling_truncation(slimt_hip_ctx *ctx, uint32_
   return 0;
 }
 
+extern "C" int slimt_hip_ctx_set_sampling_floor(slimt_hip_ctx *ctx, float min_p, float epsilon) {
+  // (the values first, like the temperature)
+  if (!slimt_hip::fl_valid(min_p, epsilon))
+    return fail(-1, "sampling floor: min_p %g is not in [0, 1] or epsilon %g is not in [0, 1)", (double)min_p, (double)epsilon);
+  if (!ctx) return fail(-1, "null argument");
+  ctx->armed.min_p = min_p;  // (both 0: nothing armed, the call is a plain sampled call)
+  ctx->armed.epsilon = epsilon;
+  return 0;
+}
+
 extern "C" int slimt_hip_ctx_set_fanout_consensus(slimt_hip_ctx *ctx, int max_order, int beta2, uint32_t *best, double *utility) {
   // (the values first, like the temperature)
   if (max_order == 0 && (best || utility)) return fail(-1, "consensus: max_order 0 disarms and takes no arrays");
@@ -1815,10 +1884,10 @@ struct MergePlan {
 // ctx->armed here -- consumed whether or not the call then succeeds -- checked against the call's n batches, and becomes
 // ctx->call, the record every inner function reads; `user` holds the per-batch arrays as the caller gave them, one entry per
 // batch, for the entry point to hand on: as they are where they are device memory (options_in_place), through
-// stage_options where they are host memory. The checks run scores -> prefix -> sampling -> truncation -> consensus -> beam
+// stage_options where they are host memory. The checks run scores -> prefix -> sampling -> truncation -> floor -> consensus -> beam
 // sampling and the first refusal is the call's (rc); a truncated call must be sampled, so the truncation is looked at behind
 // the sampling. Beam sampling (slimt_hip_ctx_set_beam_sampling) is for the beam entry points (beam) only.
-// While call.truncated or call.fanout is set fused_decoder_allowed() is false: the call decodes with the per-stage kernels
+// While call.truncated, call.floored or call.fanout is set fused_decoder_allowed() is false: the call decodes with the per-stage kernels
 // and is never merged; the context's decode mode is not touched and still chooses the encoder. Consensus is for the
 // fan-out entry points (fanout) only: any other call that finds it armed is refused. The destructor empties ctx->call.
 // The score entry points (slimt_hip_score*) open no CallOptions: they neither read nor consume what was armed.
@@ -1898,6 +1967,15 @@ struct CallOptions {
       call.truncated = true;
       call.top_k = a.top_k;
       call.top_p = a.top_p;
+    }
+    if (fl_armed(a.min_p, a.epsilon)) {
+      if (beam) return fail(-1, "sampling floor: armed on a beam call (slimt_hip_translate_beam*); a beam call is not sampled");
+      if (!call.sampled) return fail(-1, "sampling floor: armed without sampling (slimt_hip_ctx_set_sampling)");
+      if (call.truncated)
+        return fail(-1, "sampling floor: top-k / top-p truncation is armed too (slimt_hip_ctx_set_sampling_truncation); the two are not combined");
+      call.floored = true;
+      call.min_p = a.min_p;
+      call.epsilon = a.epsilon;
     }
     if (a.cs_order > 0) {
       if (!fanout) return fail(-1, "consensus: armed on a translate call that is not a fan-out call (slimt_hip_translate_fanout*)");
@@ -2825,7 +2903,7 @@ int admit_and_launch_fused(slimt_hip_ctx *c, FusedDecodeArgs &f, size_t B, size_
   return 0;
 }
 
-// ---- the step-wise loop: every call the persistent decoder refuses (truncated, fan-out, beam, consensus; decode mode 1,
+// ---- the step-wise loop: every call the persistent decoder refuses (truncated, floored, fan-out, beam, consensus; decode mode 1,
 // K/V format 3, shapes without the kernel) ----------------------------------------------------------------------------
 int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax, const uint32_t *d_shortlist, uint32_t eos_id,
                     uint32_t *d_out_ids, uint32_t *d_out_len, float *d_align, float *d_scores, int steps_hint, bool merged) {
@@ -2849,8 +2927,13 @@ int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax,
   // a truncated call stores each step's logits and selects over them: one partial per row (sample_truncate.hip)
   const bool truncated = sampled && call.truncated;
   if (call.truncated && !truncated) return fail(-1, "sampling truncation: the call is not sampled");
-  const int n_parts = truncated ? 1 : dgemm_col_blocks(out.w.K, out.w.N, (int)R);
-  if (truncated) HIPCHK(c->tr_logits.reserve(R * (size_t)out.w.N * 4));
+  // ... and so does a floored call, with a selection of its own (sample_floor.hip)
+  const bool floored = sampled && call.floored;
+  if (call.floored && !floored) return fail(-1, "sampling floor: the call is not sampled");
+  if (floored && out.w.N > kFloorMaxN) return fail(-1, "sampling floor: an output layer of %d columns exceeds %d", out.w.N, kFloorMaxN);
+  const bool stored = truncated || floored;  // the logits gemm writes the rows and leaves the selection to the next launch
+  const int n_parts = stored ? 1 : dgemm_col_blocks(out.w.K, out.w.N, (int)R);
+  if (stored) HIPCHK(c->tr_logits.reserve(R * (size_t)out.w.N * 4));
   const EmbedArgs e = embed_args(c);
   if (d_scores) HIPCHK(c->part_sum.reserve(R * (size_t)n_parts * 4));
   float *const part_sum = d_scores ? c->part_sum.as<float>() : nullptr;
@@ -2914,13 +2997,13 @@ int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax,
       g.part_mz = c->sm_part_mz.as<float>();
       g.part_zw = c->sm_part_zw.as<float>();
     }
-    if (truncated) {
+    if (stored) {
       g.y = c->tr_logits.as<float>();
       g.ldy = out.w.N;
     }
     {
       ProfScope p(c, SLIMT_HIP_K_LOGITS, gemm_macs((int)R, out.w), gemm_bytes(out.w));
-      he = launch_dgemm(g, truncated ? EPI_PLAIN : sampled ? EPI_ARGMAX_SM : fs.ids ? EPI_ARGMAX_FP : d_scores ? EPI_ARGMAX_SC : EPI_ARGMAX, st);
+      he = launch_dgemm(g, stored ? EPI_PLAIN : sampled ? EPI_ARGMAX_SM : fs.ids ? EPI_ARGMAX_FP : d_scores ? EPI_ARGMAX_SC : EPI_ARGMAX, st);
     }
     if (he != hipSuccess) { rc = fail((int)he, "logits gemm: %s", hipGetErrorString(he)); break; }
     if (truncated) {
@@ -2942,6 +3025,26 @@ int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax,
       ta.part_y = g.part_y;
       he = launch_sample_truncated(ta, st);
       if (he != hipSuccess) { rc = fail((int)he, "truncated sampling: %s", hipGetErrorString(he)); break; }
+    }
+    if (floored) {
+      SampleFloorArgs fa;
+      fa.logits = c->tr_logits.as<float>();
+      fa.B = (int)R;
+      fa.N = out.w.N;
+      fa.inv_T = ss.inv_T;
+      fa.min_p = call.min_p;
+      fa.epsilon = call.epsilon;
+      fa.seeds = ss.seeds;
+      fa.shortlist = ds.shortlist;
+      fa.fcol = g.fcol;
+      fa.part_val = g.part_val;
+      fa.part_idx = g.part_idx;
+      fa.part_sum = g.part_sum;
+      fa.part_mz = g.part_mz;
+      fa.part_zw = g.part_zw;
+      fa.part_y = g.part_y;
+      he = launch_sample_floor(fa, st);
+      if (he != hipSuccess) { rc = fail((int)he, "floored sampling: %s", hipGetErrorString(he)); break; }
     }
   }
   if (!rc && !all_done) {
@@ -3854,7 +3957,7 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
   MergePlan mp;
   size_t rows = 0;
-  const bool mergeable = n_batches > 1 && n_batches <= (size_t)kMaxMerge && !ctx->call.truncated;  // (truncated: batch by batch)
+  const bool mergeable = n_batches > 1 && n_batches <= (size_t)kMaxMerge && !ctx->call.truncated && !ctx->call.floored;  // (truncated, floored: batch by batch)
   if (mergeable)
     RCCHK(build_merge_plan(ctx, batches, n_batches, S, Tmax, limit_factor, steps_hint, nullptr, mp, rows, kMergeTile));
   for (size_t j = 0; mergeable && j < n_batches; ++j) mp.opt[j] = opt.user[j];  // (device memory: addressed where it is)
@@ -3883,7 +3986,7 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   const slimt_hip_model *m = ctx->model;
   HIPCHK(hipSetDevice(m->device));
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
-  bool merged = n_batches > 1 && n_batches <= (size_t)kMaxMerge && S <= ctx->max_S && !ctx->call.truncated;
+  bool merged = n_batches > 1 && n_batches <= (size_t)kMaxMerge && S <= ctx->max_S && !ctx->call.truncated && !ctx->call.floored;
   slimt_hip_batch dev[kMaxMerge];
   MergePlan mp;  // (its opt[j].scores: the device views of the pinned score arrays)
   bool any_align = false;
@@ -4321,7 +4424,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
     any_align = any_align || dev[j].align != nullptr;
   }
   const bool fold = env().shortlist_fold;
-  const bool merged = n > 1 && n <= (size_t)kMaxMerge && !ctx->call.truncated && S <= ctx->max_S && rows <= ctx->max_B && rows * S <= ctx->max_M &&
+  const bool merged = n > 1 && n <= (size_t)kMaxMerge && !ctx->call.truncated && !ctx->call.floored && S <= ctx->max_S && rows <= ctx->max_B && rows * S <= ctx->max_M &&
                       merge_supported(ctx, rows, S) && fold &&
                       shortlist_in_launch_lds_bytes((int)sl->source_vocab, (int)sl->target_vocab) <= 64 * 1024;
   if (!merged && o.host_batches) {

@@ -868,6 +868,30 @@ struct SampleTruncArgs {
 constexpr int kSampleTruncMaxN = 0x7fffffff - 256;  // the column loops step an int by the workgroup's 256 threads
 hipError_t launch_sample_truncated(const SampleTruncArgs &a, hipStream_t st);
 
+// ---- floored sampling: min-p / epsilon selection over stored logits (sample_floor.hip) ------------------------------------
+// The same step with the kept set of slimt_hip_ctx_set_sampling_floor (floor.h): the same partial per row, from one read of
+// the row where N <= kFloorResidentN and from three above it. N <= kFloorMaxN (floor.h). A row with fcol[b] >= 0 keeps
+// every valid column.
+struct SampleFloorArgs {
+  const float *logits = nullptr;  // [B][N]
+  int B = 0, N = 0;
+  float inv_T = 0.0f;
+  float min_p = 0.0f;    // 0: none
+  float epsilon = 0.0f;  // 0: none (and no total is formed)
+  const uint32_t *seeds = nullptr;      // [2][B] the rows' hash words of this step (SampledStep::seeds)
+  const uint32_t *shortlist = nullptr;  // [N] the columns' vocabulary ids (nullptr: the column)
+  const int *fcol = nullptr;            // nullable [B]
+  float *part_val = nullptr;            // [B] best key over the kept set (-FLT_MAX: none)
+  int *part_idx = nullptr;              // [B] ... its column (0x7fffffff: none)
+  float *part_sum = nullptr;            // [B] sum of exp(z - M) over the kept set; NaN where the row holds a NaN
+  float *part_mz = nullptr;             // [B] M, the maximum valid z
+  float *part_zw = nullptr;             // [B] z of the best key's column
+  float *part_y = nullptr;              // nullable [B] z at fcol[b], -inf where there is none
+  uint32_t *kept = nullptr;             // nullable [B] the size of the kept set
+};
+constexpr int kFloorResidentN = 4096;  // the widest row a workgroup holds in registers (256 threads x 16 columns)
+hipError_t launch_sample_floor(const SampleFloorArgs &a, hipStream_t st);
+
 // ---- beam search: one selection per step over stored logits, and the back-pointer walk (beam_select.hip) ----------------
 // One step of B sources with k slots each (rows r = b k + s, source-major) whose logits [B k][N] are in memory: the
 // selection of include/slimt_hip.h (slimt_hip_beam_step; beam.h). One workgroup per source reads its slots' totals, flags

@@ -304,6 +304,51 @@ class Service:
         res.close()
         return out
 
+    def _floored_samples(self, model: Model, per_request: List[List[List[int]]], samples: int, sampling, floor):
+        """_translate_samples under a min-p / epsilon floor (capi.Context.set_sampling_floor): the same lists and the same
+        keys, drawn by fan-out calls (`samples` decoder rows per segment, one encoding of it) on the Service's capi.Context
+        for the model, under the Service's lock, batched as _beam_ranked batches. The C++ service is not involved."""
+        n = int(samples)
+        units = [_Unit(r, i, list(seg)) for r, segs in enumerate(per_request) for i, seg in enumerate(segs)]
+        if any(len(u.words) > self.ENGINE_LIMIT for u in units):
+            raise ValueError(f"samples: a segment has more than {self.ENGINE_LIMIT} tokens")
+        if n < 1 or n > self.max_words:
+            raise ValueError(f"samples: 1..{self.max_words} samples per call, not {n}")
+        key_of = {(u.request, u.index): [capi.sampling_key(int(sampling[1]), e * n + j) for j in range(n)] for e, u in enumerate(units)}
+        out = [[[None] * len(segs) for segs in per_request] for _ in range(n)]
+        per_call = max(1, self.max_words // n)
+        batches, cur = [], []
+        for u in sorted(units, key=lambda u: (len(u.words), u.request, u.index)):
+            if cur and ((len(cur) + 1) * len(u.words) > self.max_words or len(cur) + 1 > per_call):
+                batches.append(cur)
+                cur = []
+            cur.append(u)
+        if cur:
+            batches.append(cur)
+        eos = model.vocabulary.eos_id()
+        with self._lock:
+            ctx = self._beam_contexts.get(model.id)
+            if ctx is None and batches:
+                rows = max(self.max_words, capi.MAX_BEAM)
+                ctx = capi.Context(model.engine, rows, self.ENGINE_LIMIT, max_tokens=max(self.max_words, self.ENGINE_LIMIT))
+                self._beam_contexts[model.id] = ctx
+            for batch in batches:
+                B, S = len(batch), max(len(u.words) for u in batch)
+                ids, lens = np.zeros((B, S), np.uint32), np.zeros(B, np.uint32)
+                for b, u in enumerate(batch):
+                    ids[b, :len(u.words)] = u.words
+                    lens[b] = len(u.words)
+                keys = np.array([k for u in batch for k in key_of[u.request, u.index]], np.uint64)
+                got, ln, al, sc = ctx.translate_fanout_pinned(ids, lens, np.repeat(np.arange(B, dtype=np.uint32), n), None,
+                                                              self.limit_factor, eos, want_align=True,
+                                                              generator=model.shortlist_generator, scores=True,
+                                                              sampling=(float(sampling[0]), keys), floor=floor)
+                for b, u in enumerate(batch):
+                    for j in range(n):
+                        c, L = b * n + j, int(lens[b])
+                        out[j][u.request][u.index] = (got[c, :ln[c]].tolist(), al[c, :ln[c], :L].copy(), sc[c, :ln[c]].copy())
+        return out
+
     def _translate_segments(self, model: Model, per_request: List[List[List[int]]], scores: bool = False, sampling=None,
                             truncation=None):
         """per request, per segment: (target ids, alignment, token scores | None). sampling: (temperature, seed) -- one
@@ -551,18 +596,32 @@ class Service:
         res.close()
         return out
 
-    def sample_and_rerank(self, model: Model, sources: Sequence[str], n: int, sampling, truncation=None, mean: bool = False):
+    def sample_and_rerank(self, model: Model, sources: Sequence[str], n: int, sampling, truncation=None, mean: bool = False,
+                          floor=None):
         """translate(samples=n) followed by rerank() of each source's n samples: draws n translations of every source from
         one encoding of it, then scores them teacher-forced from one encoding again (greedy log-probabilities: the model's
         own, not the draws' at the sampling temperature). sources: each ONE sentence, as for rerank(). Returns (responses,
-        ranked): translate()'s Responses with their `samples`, and rerank()'s list over the samples' target texts."""
-        responses = self.translate(model, sources, sampling=sampling, truncation=truncation, samples=n)
+        ranked): translate()'s Responses with their `samples`, and rerank()'s list over the samples' target texts.
+        floor: (min_p, epsilon) -- the samples are drawn above that floor (_floored_samples), not with truncation."""
+        if floor is not None:
+            if truncation is not None or sampling is None:
+                raise ValueError("sample_and_rerank: floor takes sampling=(temperature, seed) and no truncation")
+            processed = model.processor.process_many(sources, self.wrap_length, self.workers)
+            drawn = self._floored_samples(model, [segs for _, segs in processed], n, sampling, floor)
+            texts = [src for src, _ in processed]
+            alts = [self._respond_many(model, texts, h) for h in drawn]
+            responses = alts[0]
+            for r, resp in enumerate(responses):
+                resp.samples = [a[r] for a in alts]
+                resp.to(Encoding.UTF8)
+        else:
+            responses = self.translate(model, sources, sampling=sampling, truncation=truncation, samples=n)
         ranked = self.rerank(model, sources, [[a.target.text for a in r.samples] for r in responses], mean=mean)
         return responses, ranked
 
     def sample_and_select(self, model: Model, sources: Sequence[str], n: int, sampling, truncation=None,
                           max_order: Optional[int] = None, beta2: int = 4, encoding: Encoding = Encoding.UTF8,
-                          utility: str = "tokens", without_replacement: bool = False) -> List[Response]:
+                          utility: str = "tokens", without_replacement: bool = False, floor=None) -> List[Response]:
         """translate(samples=n) followed by the consensus (minimum-Bayes-risk) pick: of the n draws of every sentence, the one
         that agrees most with the others -- the mean token n-gram F (orders 1..max_order, integer beta2 = beta^2; 4 is chrF's)
         against the sentence's other draws (include/slimt_hip.h, slimt_hip_consensus_select). The pick is made on the device
@@ -577,7 +636,13 @@ class Service:
         segment of at most ENGINE_LIMIT tokens yields at most 192).
         without_replacement: the n draws of a sentence are n DISTINCT translations, sampled without replacement by
         beam_search(beam=n, sample_seed=seed) (temperature 1, no truncation, n <= capi.MAX_BEAM); the consensus pick is
-        made in a call of its own over the returned rows, as the "chrf" path's is, so no pick is decided by duplicates."""
+        made in a call of its own over the returned rows, as the "chrf" path's is, so no pick is decided by duplicates.
+        floor: (min_p, epsilon) -- the draws keep only the tokens above that floor (capi.Context.set_sampling_floor: min-p and
+        epsilon sampling). They come from fan-out calls on the Service's capi.Context for the model, under the same keys as
+        translate(samples=n), and the pick of either utility runs in a call of its own over the returned rows. Not with
+        truncation, and not without replacement."""
+        if floor is not None and (truncation is not None or without_replacement):
+            raise ValueError("sample_and_select: floor is not combined with truncation or without_replacement")
         if without_replacement:
             return self._select_without_replacement(model, sources, n, sampling, truncation, max_order, beta2, encoding, utility)
         if sampling is None or int(n) < 1:
@@ -593,13 +658,16 @@ class Service:
             raise ValueError(f"samples: a segment has more than {self.ENGINE_LIMIT} tokens")
         histories = [[None] * len(segs) for segs in per_request]
         picked = [([0.0] * len(segs), [0] * len(segs)) for segs in per_request]
-        if flat and utility == "chrf":
+        if flat and (utility == "chrf" or floor is not None):
             n = int(n)
             if n > capi.CONSENSUS_MAX_ROWS:
                 raise ValueError(f"sample_and_select: at most {capi.CONSENSUS_MAX_ROWS} samples, not {n}")
-            drawn = self._translate_samples(model, per_request, n, sampling, truncation)  # [sample][request][segment]
+            if floor is not None:
+                drawn = self._floored_samples(model, per_request, n, sampling, floor)  # [sample][request][segment]
+            else:
+                drawn = self._translate_samples(model, per_request, n, sampling, truncation)
             where = [(r, i) for r, segs in enumerate(per_request) for i in range(len(segs))]
-            unit_off, units = model.consensus_units()
+            unit_off, units = model.consensus_units() if utility == "chrf" else (None, None)
             per_call = 65536 // n  # (the call's bound on its rows)
             for at in range(0, len(where), per_call):
                 part = where[at:at + per_call]
@@ -607,8 +675,11 @@ class Service:
                 ids = np.zeros((len(rows), max(1, max(len(x) for x in rows))), np.uint32)
                 for c, x in enumerate(rows):
                     ids[c, :len(x)] = x
-                u, best = capi.consensus_select_units(ids, [len(x) for x in rows], np.repeat(np.arange(len(part)), n),
-                                                      len(part), unit_off, units, max_order, beta2)
+                src = np.repeat(np.arange(len(part)), n)
+                if utility == "chrf":
+                    u, best = capi.consensus_select_units(ids, [len(x) for x in rows], src, len(part), unit_off, units, max_order, beta2)
+                else:
+                    u, best = capi.consensus_select(ids, [len(x) for x in rows], src, len(part), max_order, beta2)
                 for e, (r, i) in enumerate(part):
                     c = e * n if best[e] == capi.NO_ROW else int(best[e])  # (every draw empty: the first)
                     histories[r][i] = drawn[c - e * n][r][i]
