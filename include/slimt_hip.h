@@ -443,6 +443,76 @@ int slimt_hip_ctx_set_sampling_truncation(slimt_hip_ctx *ctx, uint32_t top_k, fl
  * context's mode is not changed and slimt_hip_ctx_plan keeps reporting it. The
  * _many_ entry points do not merge a floored call. */
 int slimt_hip_ctx_set_sampling_floor(slimt_hip_ctx *ctx, float min_p, float epsilon);
+/* Step constraints: the NEXT translate call's choices conditioned on what each row
+ * has already emitted. Armed for that call, which consumes the setting whether it
+ * succeeds or fails, like every other per-call option; the suppress list is copied
+ * when armed. All-off values, or NULL, disarm. Invalid values (an n-gram size above
+ * SLIMT_HIP_CONSTRAINT_MAX_NGRAM, a repetition_penalty that is not finite and > 0,
+ * more than SLIMT_HIP_CONSTRAINT_MAX_SUPPRESS ids, n_suppress > 0 with a NULL list)
+ * are refused at once with a negative status.
+ *
+ * A row has the history h[0 .. L): the tokens recorded so far, forced-prefix tokens
+ * included. One step that is not forced (the definition is
+ * slimt_amd/csrc/constraints.h):
+ *  1. Banned ids: the suppress list; eos_id while L < min_length; and, for
+ *     n = no_repeat_ngram >= 1 and L >= n - 1, every h[q + n - 1] with
+ *     0 <= q <= L - n and h[q .. q + n - 2] == h[L - n + 1 .. L - 1]. Windows may
+ *     overlap the suffix; n = 1 bans every emitted token.
+ *  2. Seen ids: every h[q].
+ *  3. An id maps to its output-layer column as a forced-prefix token does: itself
+ *     without a shortlist, its place in the sorted shortlist with one. An id with no
+ *     column constrains nothing.
+ *  4. Penalty theta = repetition_penalty: a seen column's logit l becomes
+ *     l > 0 ? l * inv_theta : l * theta, inv_theta = 1.0f / theta formed once on the
+ *     host; one float32 product, once per column. Then z = l' * inv_T (inv_T = 1 in a
+ *     greedy call).
+ *  5. Candidates C: the valid (non-NaN) columns that are not banned; when that leaves
+ *     none while a valid column exists, all valid columns (the bans are lifted for the
+ *     step, the penalty stays).
+ *  6. Greedy: the first maximum of z over C from -FLT_MAX with strict >. Sampled: the
+ *     first maximum of fmaf(l', inv_T, g(k_b, t, y_c)) over C, as in a plain sampled
+ *     call. The score is log softmax(z over C) at the chosen column, through the
+ *     float path of the scored calls; a NaN anywhere in the row makes it NaN.
+ * Forced steps (slimt_hip_ctx_set_target_prefix) are not constrained; their tokens
+ * count as history. The step limit is unchanged: a row whose min_length is at or
+ * above Tmax ends at Tmax without EOS.
+ * Refused by the translate call (negative status, message, setting consumed):
+ * together with top-k / top-p truncation or with the min-p / epsilon floors; on a
+ * beam call (slimt_hip_translate_beam*); Tmax above
+ * SLIMT_HIP_CONSTRAINT_MAX_HISTORY; an output layer of more than 2^19 columns.
+ * Execution: like a floored call a constrained one DECODES with the per-stage kernels
+ * whatever mode the context is in, the logits gemm storing the row -- a greedy call
+ * too -- with one selection kernel per step (slimt_amd/csrc/step_constrain.hip); on a
+ * fan-out call per decoder row. slimt_hip_ctx_plan keeps reporting the context's
+ * mode, the _many_ entry points translate a constrained call batch by batch, and the
+ * score entry points neither read nor consume the setting. */
+#define SLIMT_HIP_CONSTRAINT_MAX_NGRAM 8
+#define SLIMT_HIP_CONSTRAINT_MAX_SUPPRESS 64
+#define SLIMT_HIP_CONSTRAINT_MAX_HISTORY 1024
+#define SLIMT_HIP_CONSTRAINT_FALLBACK 0x80000000u
+typedef struct slimt_hip_step_constraints {
+  uint32_t no_repeat_ngram;  /* 0: off */
+  float repetition_penalty;  /* 1: off */
+  uint32_t min_length;       /* 0: off */
+  const uint32_t *suppress;  /* [n_suppress] vocabulary ids */
+  size_t n_suppress;         /* 0: off */
+} slimt_hip_step_constraints;
+int slimt_hip_ctx_set_step_constraints(slimt_hip_ctx *ctx, const slimt_hip_step_constraints *constraints);
+/* One constrained step over the caller's logits [M][N] (host pointers; the kernel of
+ * slimt_hip_ctx_set_step_constraints alone). N at most 2^19. ids: the columns'
+ * vocabulary ids [N], sorted (NULL: the column). history [M][Th] and hist_len [M]:
+ * the rows' histories, Th in 1 .. SLIMT_HIP_CONSTRAINT_MAX_HISTORY; a length above Th
+ * counts as Th. keys == NULL: a greedy step (temperature must be 1); else the rows'
+ * sentence keys [M] and steps [M] (NULL: 0) as in slimt_hip_sample_floor.
+ * columns[r]: the chosen column, or 0 with scores[r] NaN when no candidate beats the
+ * start value or logit 0 of the row is NaN; scores[r]: the step's score;
+ * n_banned[r]: the row's banned columns, with SLIMT_HIP_CONSTRAINT_FALLBACK set
+ * when the step lifted its bans. */
+int slimt_hip_constrained_step(const float *logits, size_t M, size_t N, const uint32_t *ids,
+                               const uint32_t *history, const uint32_t *hist_len, size_t Th,
+                               const slimt_hip_step_constraints *constraints, uint32_t eos_id,
+                               float temperature, const uint64_t *keys, const uint32_t *steps,
+                               uint32_t *columns, float *scores, uint32_t *n_banned);
 /* Which kernels a translate call with source length S would use in the current
  * mode: *encoder_fused / *decoder_fused = 1 for the persistent kernels, 0 for
  * the per-stage ones. */

@@ -45,6 +45,7 @@ SYMBOLS = [
     "slimt_hip_ctx_set_scores", "slimt_hip_ctx_set_target_prefix", "slimt_hip_ctx_set_sampling", "slimt_hip_sampling_key",
     "slimt_hip_ctx_set_sampling_truncation", "slimt_hip_sample_truncated",
     "slimt_hip_ctx_set_sampling_floor", "slimt_hip_sample_floor",
+    "slimt_hip_ctx_set_step_constraints", "slimt_hip_constrained_step",
     "slimt_hip_score", "slimt_hip_score_async", "slimt_hip_score_device", "slimt_hip_score_async_generated",
     "slimt_hip_ctx_set_score_alternatives", "slimt_hip_debug_ctx_shortlists", "slimt_hip_debug_ctx_set_counters",
     "slimt_hip_score_candidates", "slimt_hip_score_candidates_async", "slimt_hip_score_candidates_device",
@@ -233,6 +234,8 @@ def lib():
     L.slimt_hip_sample_truncated.argtypes = [vp, sz, sz, vp, f32, u32, f32, vp, vp, vp, vp, vp, vp]
     L.slimt_hip_ctx_set_sampling_floor.argtypes = [vp, f32, f32]
     L.slimt_hip_sample_floor.argtypes = [vp, sz, sz, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp]
+    L.slimt_hip_ctx_set_step_constraints.argtypes = [vp, vp]
+    L.slimt_hip_constrained_step.argtypes = [vp, sz, sz, vp, vp, vp, sz, vp, u32, f32, vp, vp, vp, vp, vp]
     L.slimt_hip_ctx_plan.argtypes = [vp, sz, vp, vp]
     L.slimt_hip_translate.argtypes = [vp, vp, vp, sz, sz, vp, sz, f32, u32, vp, vp, vp]
     L.slimt_hip_translate_async.argtypes = [vp, vp, vp, sz, sz, vp, sz, f32, u32, vp, vp, vp]
@@ -366,6 +369,48 @@ def sample_floor(logits, temperature: float = 1.0, min_p: float = 0.0, epsilon: 
     _chk(lib().slimt_hip_sample_floor(_p(logits), M, N, _p(ids), float(temperature), float(min_p), float(epsilon), _p(keys),
                                       _p(steps), _p(cols), _p(mx), _p(kept), _p(sc)))
     return cols, mx, kept, sc
+
+
+CONSTRAINT_MAX_NGRAM, CONSTRAINT_MAX_SUPPRESS, CONSTRAINT_MAX_HISTORY = 8, 64, 1024  # (include/slimt_hip.h)
+CONSTRAINT_FALLBACK = 0x80000000  # SLIMT_HIP_CONSTRAINT_FALLBACK
+
+
+class StepConstraints(C.Structure):
+    """slimt_hip_step_constraints"""
+    _fields_ = [("no_repeat_ngram", C.c_uint32), ("repetition_penalty", C.c_float), ("min_length", C.c_uint32),
+                ("suppress", C.c_void_p), ("n_suppress", C.c_size_t)]
+
+
+def _step_constraints(no_repeat_ngram: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress=()):
+    """(the C struct, the array its suppress list points into)"""
+    ids = np.ascontiguousarray(suppress, dtype=np.uint32).reshape(-1)
+    return StepConstraints(int(no_repeat_ngram), float(repetition_penalty), int(min_length), ids.ctypes.data if ids.size else None,
+                           ids.size), ids
+
+
+def constrained_step(logits, history, hist_len, constraints, eos_id: int = 0, temperature: float = 1.0, ids=None, keys=None,
+                     steps=None):
+    """slimt_hip_constrained_step: one step under step constraints over logits [M, N] (float32) and the rows' histories
+    [M, Th] / hist_len [M] (uint32). constraints: the keywords of Context.set_step_constraints, as a dict. keys None: a greedy
+    step; else uint64 [M] with steps [M] as in sample_floor. Returns (columns uint32 [M], scores float32 [M], banned columns
+    uint32 [M], fallback bool [M]: the step lifted its bans)."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    M, N = logits.shape
+    history = np.ascontiguousarray(history, dtype=np.uint32)
+    hist_len = np.ascontiguousarray(hist_len, dtype=np.uint32)
+    ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32)
+    keys = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint64)
+    steps = None if steps is None else np.ascontiguousarray(steps, dtype=np.uint32)
+    if history.ndim != 2 or history.shape[0] != M or hist_len.shape != (M,):
+        raise ValueError("constrained_step: history [M, Th] and hist_len [M] expected")
+    if (ids is not None and ids.shape != (N,)) or (keys is not None and keys.shape != (M,)) or (steps is not None and steps.shape != (M,)):
+        raise ValueError("constrained_step: ids [N], keys [M] and steps [M] expected")
+    cn, keep = _step_constraints(**constraints)
+    cols, sc, nb = np.zeros(M, np.uint32), np.zeros(M, np.float32), np.zeros(M, np.uint32)
+    _chk(lib().slimt_hip_constrained_step(_p(logits), M, N, _p(ids), _p(history), _p(hist_len), history.shape[1], C.addressof(cn),
+                                          int(eos_id), float(temperature), _p(keys), _p(steps), _p(cols), _p(sc), _p(nb)))
+    del keep
+    return cols, sc, nb & np.uint32(CONSTRAINT_FALLBACK - 1), (nb & np.uint32(CONSTRAINT_FALLBACK)) != 0
 
 
 MAX_BEAM = 8  # SLIMT_HIP_MAX_BEAM
@@ -906,6 +951,16 @@ class Context:
         `sampling=` and do this."""
         _chk(lib().slimt_hip_ctx_set_sampling_floor(self.h, float(min_p), float(epsilon)))
 
+    def set_step_constraints(self, no_repeat_ngram: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress=()):
+        """slimt_hip_ctx_set_step_constraints: condition the NEXT translate call's steps, greedy or sampled, on what each row
+        has emitted: no token that would repeat an n-gram of size no_repeat_ngram (0: off; at most 8), the logits of emitted
+        tokens penalised by repetition_penalty (1: off), no EOS before min_length tokens, and never a token of `suppress`
+        (at most 64 vocabulary ids, copied here). All off disarms. Not combined with set_sampling_truncation,
+        set_sampling_floor or a beam call. The translate wrappers take `constraints=` (a dict of these keywords) and do this."""
+        cn, keep = _step_constraints(no_repeat_ngram, repetition_penalty, min_length, suppress)
+        _chk(lib().slimt_hip_ctx_set_step_constraints(self.h, C.addressof(cn)))
+        del keep
+
     def set_fanout_consensus(self, max_order: int, beta2: int, best, utility, units: bool = False):
         """slimt_hip_ctx_set_fanout_consensus: arm the consensus selection for the NEXT fan-out call -- best [B] uint32 and
         utility [N] float64, as numpy arrays (host calls; kept alive here until the next arming) or addresses (ints: device
@@ -978,13 +1033,15 @@ class Context:
         return bool(e.value), bool(d.value)
 
     def translate(self, ids, lengths, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                  want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None, floor=None):
+                  want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None, floor=None,
+                  constraints=None):
         """Model::forward. Returns out_ids [B,Tmax], out_len [B], align|None (+ scores [B,Tmax] float32 with
         scores=True: the log-probability of each recorded token, include/slimt_hip.h slimt_hip_ctx_set_scores).
         prefix: (ids [B,Tmax], lens [B]) uint32 -- forced target prefixes (slimt_hip_ctx_set_target_prefix).
         sampling: (temperature, keys uint64 [B] | None) -- temperature sampling under per-sentence keys
         (slimt_hip_ctx_set_sampling; None: the row indices); the other translate wrappers take it in the same form, the
-        device ones with a device pointer for the keys, the _many_ ones with one entry per batch."""
+        device ones with a device pointer for the keys, the _many_ ones with one entry per batch.
+        constraints: a dict of set_step_constraints' keywords (slimt_hip_ctx_set_step_constraints)."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
         B, S = ids.shape
@@ -1007,6 +1064,8 @@ class Context:
             self.set_sampling_truncation(*truncation)
         if floor is not None:
             self.set_sampling_floor(*floor)
+        if constraints is not None:
+            self.set_step_constraints(**constraints)
         _chk(lib().slimt_hip_translate(self.h, _p(ids), _p(lengths), B, S, _p(sl),
                                        0 if sl is None else sl.size, limit_factor, eos_id,
                                        _p(out_ids), _p(out_len), _p(align)))
@@ -1022,7 +1081,7 @@ class Context:
                 pin("al").array(np.float32, (B, T, S)) if want_align else None)
 
     def translate_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
-                        scores=None, prefix=None, sampling=None, truncation=None, floor=None):
+                        scores=None, prefix=None, sampling=None, truncation=None, floor=None, constraints=None):
         """slimt_hip_translate_async[_generated] on arrays from pinned_buffers() (already filled);
         synchronize() before reading the outputs. `generator`: a ShortlistGenerator -- the batch's
         lexical shortlist is then generated on this context's stream (Model.cc:117-120).
@@ -1045,6 +1104,8 @@ class Context:
             self.set_sampling_truncation(*truncation)
         if floor is not None:
             self.set_sampling_floor(*floor)
+        if constraints is not None:
+            self.set_step_constraints(**constraints)
         if generator is not None:
             _chk(lib().slimt_hip_translate_async_generated(self.h, generator.h, _p(p_ids), _p(p_len), B, S,
                                                            limit_factor, eos_id, _p(p_out), _p(p_ol), _p(p_al)))
@@ -1053,7 +1114,8 @@ class Context:
                                              limit_factor, eos_id, _p(p_out), _p(p_ol), _p(p_al)))
 
     def translate_pinned(self, ids, lengths, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
-                         want_align: bool = False, generator=None, scores: bool = False, prefix=None, sampling=None, truncation=None, floor=None):
+                         want_align: bool = False, generator=None, scores: bool = False, prefix=None, sampling=None, truncation=None, floor=None,
+                         constraints=None):
         """translate() through this context's pinned staging buffers and slimt_hip_translate_async:
         the persistent kernels then read and write host memory themselves, no copy is queued (host
         pipelines with several contexts: copies of one stream wait behind other streams' kernels).
@@ -1065,7 +1127,7 @@ class Context:
         bufs[1][...] = lengths
         sc = self._pinned.setdefault("sc", _Pinned()).array(np.float32, bufs[2].shape) if scores else None
         self.translate_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix, sampling=sampling,
-                             truncation=truncation, floor=floor)
+                             truncation=truncation, floor=floor, constraints=constraints)
         self.synchronize()
         out = bufs[2].copy(), bufs[3].copy(), (bufs[4].copy() if want_align else None)
         return out + (sc.copy(),) if scores else out
@@ -1100,7 +1162,7 @@ class Context:
         return (out_ids, out_len, align, sc) if scores else (out_ids, out_len, align)
 
     # ---- fan-out: N decoder rows over B sources encoded once (include/slimt_hip.h, slimt_hip_translate_fanout*) ----
-    def _arm(self, N: int, scores, prefix, sampling, truncation, T: int, floor=None):
+    def _arm(self, N: int, scores, prefix, sampling, truncation, T: int, floor=None, constraints=None):
         """arms a one-batch call's options, shaped by its N rows (right before the call that takes them)"""
         pre = self._prefix_host(prefix, N, T) if prefix is not None else None
         if scores is not None:
@@ -1114,10 +1176,12 @@ class Context:
             self.set_sampling_truncation(*truncation)
         if floor is not None:
             self.set_sampling_floor(*floor)
+        if constraints is not None:
+            self.set_step_constraints(**constraints)
 
     def translate_fanout(self, ids, lengths, row_src, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
                          want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None,
-                         consensus=None, floor=None):
+                         consensus=None, floor=None, constraints=None):
         """slimt_hip_translate_fanout: translate() with N decoder rows over the B sources ids [B,S] / lengths [B], encoded
         once; row_src [N] uint32 names each row's source. Returns out_ids [N,Tmax], out_len [N], align [N,Tmax,S] | None
         (+ scores [N,Tmax]). prefix, sampling, truncation: as in translate(), shaped by N. Every row is bit for bit its row
@@ -1138,7 +1202,7 @@ class Context:
         out_len = np.zeros(N, dtype=np.uint32)
         align = np.zeros((N, T, S), dtype=np.float32) if want_align else None
         sc = np.full((N, T), np.nan, dtype=np.float32) if scores else None
-        self._arm(N, sc, prefix, sampling, truncation, T, floor)
+        self._arm(N, sc, prefix, sampling, truncation, T, floor, constraints)
         cs = self._arm_consensus(consensus, B, N) if consensus is not None else ()
         _chk(lib().slimt_hip_translate_fanout(self.h, _p(ids), _p(lengths), B, S, _p(row_src), N, _p(sl),
                                               0 if sl is None else sl.size, limit_factor, eos_id, _p(out_ids), _p(out_len),
@@ -1156,7 +1220,8 @@ class Context:
                 pin("fo_ol").array(np.uint32, (N,)), pin("fo_al").array(np.float32, (N, T, S)) if want_align else None)
 
     def translate_fanout_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
-                               scores=None, prefix=None, sampling=None, truncation=None, consensus=None, floor=None):
+                               scores=None, prefix=None, sampling=None, truncation=None, consensus=None, floor=None,
+                               constraints=None):
         """slimt_hip_translate_fanout_async[_generated] on (ids, lengths, row_src, out_ids, out_len, align | None) host arrays
         (already filled; those of fanout_buffers() are pinned); synchronize() before reading the outputs. scores: a float32
         [N, Tmax] array; prefix, sampling, truncation: as in translate_async(), shaped by N.
@@ -1173,7 +1238,7 @@ class Context:
         if align is not None and (align.dtype != np.float32 or align.shape != (N, T, S) or not align.flags.c_contiguous):
             raise ValueError("translate_fanout_async: a C-contiguous float32 align of shape %s expected" % ((N, T, S),))
         sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
-        self._arm(N, scores, prefix, sampling, truncation, T, floor)
+        self._arm(N, scores, prefix, sampling, truncation, T, floor, constraints)
         cs = self._arm_consensus(consensus, B, N) if consensus is not None else None
         if generator is not None:
             _chk(lib().slimt_hip_translate_fanout_async_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, _p(row_src),
@@ -1186,7 +1251,7 @@ class Context:
 
     def translate_fanout_pinned(self, ids, lengths, row_src, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
                                 want_align: bool = False, generator=None, scores: bool = False, prefix=None, sampling=None,
-                                truncation=None, consensus=None, floor=None):
+                                truncation=None, consensus=None, floor=None, constraints=None):
         """translate_fanout() through this context's pinned arrays and slimt_hip_translate_fanout_async; returns copies."""
         ids, row_src = np.asarray(ids), np.asarray(row_src)
         B, S = ids.shape
@@ -1196,7 +1261,8 @@ class Context:
         bufs[2][...] = row_src
         sc = self._pinned.setdefault("fo_sc", _Pinned()).array(np.float32, bufs[3].shape) if scores else None
         cs = self.translate_fanout_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix,
-                                         sampling=sampling, truncation=truncation, floor=floor, consensus=consensus)
+                                         sampling=sampling, truncation=truncation, floor=floor, consensus=consensus,
+                                         constraints=constraints)
         self.synchronize()
         out = bufs[3].copy(), bufs[4].copy(), (bufs[5].copy() if want_align else None)
         return (out + (sc.copy(),) if scores else out) + tuple(cs or ())

@@ -3,6 +3,7 @@
 #include "decoder_plan.h"
 #include "sampling.h"
 #include "scores.h"
+#include "constraints.h"
 #include "floor.h"
 #include "truncation.h"
 #include "beam.h"
@@ -102,12 +103,13 @@ static const EnvKnobs &env() {
 
 // The persistent decoder runs the hoisted cross-attention order over a cache of accumulators; the reference's literal
 // sequence (K/V cache format 3) exists in the stage-wise attention kernel only (decode_kernels.hip, DQAttnArgs::literal)
-// ... and a truncated or floored sampled call needs each step's whole row of logits, which only the stage-wise decoder stores; a
+// ... and a truncated or floored sampled call needs each step's whole row of logits, which only the stage-wise decoder stores,
+// as does a call under step constraints (constraints.h), greedy or sampled; a
 // fan-out call's cross-attention looks a row's source up, which only the stage-wise one does (decode_fanout.hip). Every
 // decision that hangs on the persistent decoder -- the lean path, pinned arrays read in place, merged launches -- asks here;
 // the encoder is chosen as the context's mode says.
 static bool fused_decoder_allowed(const slimt_hip_ctx *c) {
-  return c->decode_mode != 1 && c->model->kv_format != 3 && !c->call.truncated && !c->call.floored && !c->call.fanout;
+  return c->decode_mode != 1 && c->model->kv_format != 3 && !c->call.truncated && !c->call.floored && !c->call.constrained && !c->call.fanout;
 }
 // The decoder rows of the call in progress: a fan-out call's N, else one per source.
 static int decoder_rows(const slimt_hip_ctx *c) { return c->call.fanout ? c->call.rows : c->B; }
@@ -669,6 +671,93 @@ extern "C" int slimt_hip_sample_floor(const float *logits, size_t M, size_t N, c
     scores[r] = slimt_hip::forced_score(h[2 * M + r], h[4 * M + r] - h[3 * M + r], none);
     maxima[r] = h[3 * M + r];
     memcpy(&kept[r], &h[5 * M + r], 4);
+  }
+  return 0;
+}
+
+// the caller's setting as the kernel takes it, checked (constraints.h); NULL: all off
+static int step_constraints_from(const slimt_hip_step_constraints *in, slimt_hip::StepConstraints &out) {
+  out = {};
+  if (!in) return 0;
+  if (in->n_suppress > slimt_hip::kConstraintMaxSuppress || !slimt_hip::cn_valid(in->no_repeat_ngram, in->repetition_penalty, (uint32_t)in->n_suppress))
+    return fail(-1, "step constraints: no_repeat_ngram %u is not in 0..%u, repetition_penalty %g is not finite and > 0, or %zu suppressed ids exceed %u",
+                in->no_repeat_ngram, slimt_hip::kConstraintMaxNgram, (double)in->repetition_penalty, in->n_suppress, slimt_hip::kConstraintMaxSuppress);
+  if (in->n_suppress && !in->suppress) return fail(-1, "step constraints: suppress is NULL with n_suppress %zu", in->n_suppress);
+  const float inv_theta = 1.0f / in->repetition_penalty;
+  if (!(inv_theta > 0.0f) || !std::isfinite(inv_theta))
+    return fail(-1, "step constraints: 1 / repetition_penalty %g is not finite and > 0", (double)in->repetition_penalty);
+  out.no_repeat_ngram = in->no_repeat_ngram;
+  out.theta = in->repetition_penalty;
+  out.inv_theta = inv_theta;
+  out.min_length = in->min_length;
+  out.n_suppress = (uint32_t)in->n_suppress;
+  for (size_t i = 0; i < in->n_suppress; ++i) out.suppress[i] = in->suppress[i];
+  return 0;
+}
+
+extern "C" int slimt_hip_constrained_step(const float *logits, size_t M, size_t N, const uint32_t *ids, const uint32_t *history,
+                                          const uint32_t *hist_len, size_t Th, const slimt_hip_step_constraints *constraints,
+                                          uint32_t eos_id, float temperature, const uint64_t *keys, const uint32_t *steps,
+                                          uint32_t *columns, float *scores, uint32_t *n_banned) {
+  if (!(temperature > 0.0f) || !std::isfinite(temperature)) return fail(-1, "sampling: temperature %g is not finite and > 0", (double)temperature);
+  const float inv_T = 1.0f / temperature;
+  if (!(inv_T > 0.0f) || !std::isfinite(inv_T)) return fail(-1, "sampling: 1 / temperature %g is not finite and > 0", (double)temperature);
+  if (!keys && temperature != 1.0f) return fail(-1, "constrained_step: a greedy step (keys NULL) has no temperature");
+  slimt_hip::StepConstraints cn;
+  RCCHK(step_constraints_from(constraints, cn));
+  if (!logits || !history || !hist_len || !columns || !scores || !n_banned || !M || !N) return fail(-1, "bad argument");
+  if (M > 0x7fffffffu || N > (size_t)kConstraintMaxN) return fail(-1, "constrained_step: more than %d rows or %d columns", 0x7fffffff, kConstraintMaxN);
+  if (Th < 1 || Th > (size_t)kConstraintMaxHistory) return fail(-1, "constrained_step: a history row of %zu tokens is not in 1..%d", Th, kConstraintMaxHistory);
+  std::vector<uint32_t> seeds(2 * M);  // the rows' hash words (sampling.h), as decode_begin_step_sm_kernel writes them
+  for (size_t r = 0; keys && r < M; ++r) {
+    const uint64_t w = slimt_hip::sm_step_words(keys[r], steps ? steps[r] : 0u);
+    seeds[r] = (uint32_t)w;
+    seeds[M + r] = (uint32_t)(w >> 32);
+  }
+  Tmp3 t;
+  hipStream_t st = nullptr;
+  HIPCHK(t.a.reserve(M * N * 4));
+  HIPCHK(t.b.reserve(N * 4));
+  HIPCHK(t.c.reserve(2 * M * 4));
+  HIPCHK(t.d.reserve(6 * M * 4));
+  HIPCHK(t.e.reserve((M * Th + M) * 4));
+  HIPCHK(hipMemcpyAsync(t.a.p, logits, M * N * 4, hipMemcpyHostToDevice, st));
+  if (ids) HIPCHK(hipMemcpyAsync(t.b.p, ids, N * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.p, seeds.data(), 2 * M * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.e.p, history, M * Th * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.e.as<uint32_t>() + M * Th, hist_len, M * 4, hipMemcpyHostToDevice, st));
+  StepConstrainArgs a;
+  a.logits = t.a.as<float>();
+  a.B = (int)M;
+  a.N = (int)N;
+  a.inv_T = inv_T;
+  a.seeds = keys ? t.c.as<uint32_t>() : nullptr;
+  a.shortlist = ids ? t.b.as<uint32_t>() : nullptr;
+  a.history = t.e.as<uint32_t>();
+  a.hist_len = t.e.as<uint32_t>() + M * Th;
+  a.ld_hist = (int)Th;
+  a.eos = eos_id;
+  a.c = cn;
+  float *o = t.d.as<float>();
+  a.part_val = o;
+  a.part_idx = reinterpret_cast<int *>(o + M);
+  a.part_sum = o + 2 * M;
+  a.part_mz = o + 3 * M;
+  a.part_zw = o + 4 * M;
+  a.n_banned = reinterpret_cast<uint32_t *>(o + 5 * M);
+  HIPCHK(launch_step_constrain(a, st));
+  std::vector<float> h(6 * M);
+  HIPCHK(hipMemcpyAsync(h.data(), t.d.p, 6 * M * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (size_t r = 0; r < M; ++r) {
+    int col;
+    memcpy(&col, &h[M + r], 4);
+    // the "none" rule of the decode_begin_step kernels: nothing beat the start value, or logit 0 is NaN -- class 0, score NaN
+    const bool none = col == 0x7fffffff || logits[r * N] != logits[r * N];
+    columns[r] = none ? 0u : (uint32_t)col;
+    // greedy: the chosen column is the maximum (lse_score); sampled: forced_score at the drawn column's z - M
+    scores[r] = keys ? slimt_hip::forced_score(h[2 * M + r], h[4 * M + r] - h[3 * M + r], none) : slimt_hip::lse_score(h[2 * M + r], none);
+    memcpy(&n_banned[r], &h[5 * M + r], 4);
   }
   return 0;
 }
@@ -1621,6 +1710,15 @@ extern "C" int slimt_hip_ctx_set_sampling_floor(slimt_hip_ctx *ctx, float min_p,
   return 0;
 }
 
+extern "C" int slimt_hip_ctx_set_step_constraints(slimt_hip_ctx *ctx, const slimt_hip_step_constraints *constraints) {
+  // (the values first, like the temperature)
+  slimt_hip::StepConstraints cn;
+  RCCHK(step_constraints_from(constraints, cn));
+  if (!ctx) return fail(-1, "null argument");
+  ctx->armed.cn = cn;  // (all off: nothing armed)
+  return 0;
+}
+
 extern "C" int slimt_hip_ctx_set_fanout_consensus(slimt_hip_ctx *ctx, int max_order, int beta2, uint32_t *best, double *utility) {
   // (the values first, like the temperature)
   if (max_order == 0 && (best || utility)) return fail(-1, "consensus: max_order 0 disarms and takes no arrays");
@@ -1884,10 +1982,10 @@ struct MergePlan {
 // ctx->armed here -- consumed whether or not the call then succeeds -- checked against the call's n batches, and becomes
 // ctx->call, the record every inner function reads; `user` holds the per-batch arrays as the caller gave them, one entry per
 // batch, for the entry point to hand on: as they are where they are device memory (options_in_place), through
-// stage_options where they are host memory. The checks run scores -> prefix -> sampling -> truncation -> floor -> consensus -> beam
+// stage_options where they are host memory. The checks run scores -> prefix -> sampling -> truncation -> floor -> step constraints -> consensus -> beam
 // sampling and the first refusal is the call's (rc); a truncated call must be sampled, so the truncation is looked at behind
 // the sampling. Beam sampling (slimt_hip_ctx_set_beam_sampling) is for the beam entry points (beam) only.
-// While call.truncated, call.floored or call.fanout is set fused_decoder_allowed() is false: the call decodes with the per-stage kernels
+// While call.truncated, call.floored, call.constrained or call.fanout is set fused_decoder_allowed() is false: the call decodes with the per-stage kernels
 // and is never merged; the context's decode mode is not touched and still chooses the encoder. Consensus is for the
 // fan-out entry points (fanout) only: any other call that finds it armed is refused. The destructor empties ctx->call.
 // The score entry points (slimt_hip_score*) open no CallOptions: they neither read nor consume what was armed.
@@ -1976,6 +2074,15 @@ struct CallOptions {
       call.floored = true;
       call.min_p = a.min_p;
       call.epsilon = a.epsilon;
+    }
+    if (cn_armed(a.cn)) {
+      if (beam) return fail(-1, "step constraints: armed on a beam call (slimt_hip_translate_beam*); beams are not constrained");
+      if (call.truncated)
+        return fail(-1, "step constraints: top-k / top-p truncation is armed too (slimt_hip_ctx_set_sampling_truncation); the two are not combined");
+      if (call.floored)
+        return fail(-1, "step constraints: a sampling floor is armed too (slimt_hip_ctx_set_sampling_floor); the two are not combined");
+      call.constrained = true;
+      call.cn = a.cn;
     }
     if (a.cs_order > 0) {
       if (!fanout) return fail(-1, "consensus: armed on a translate call that is not a fan-out call (slimt_hip_translate_fanout*)");
@@ -2903,7 +3010,7 @@ int admit_and_launch_fused(slimt_hip_ctx *c, FusedDecodeArgs &f, size_t B, size_
   return 0;
 }
 
-// ---- the step-wise loop: every call the persistent decoder refuses (truncated, floored, fan-out, beam, consensus; decode mode 1,
+// ---- the step-wise loop: every call the persistent decoder refuses (truncated, floored, constrained, fan-out, beam, consensus; decode mode 1,
 // K/V format 3, shapes without the kernel) ----------------------------------------------------------------------------
 int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax, const uint32_t *d_shortlist, uint32_t eos_id,
                     uint32_t *d_out_ids, uint32_t *d_out_len, float *d_align, float *d_scores, int steps_hint, bool merged) {
@@ -2931,7 +3038,11 @@ int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax,
   const bool floored = sampled && call.floored;
   if (call.floored && !floored) return fail(-1, "sampling floor: the call is not sampled");
   if (floored && out.w.N > kFloorMaxN) return fail(-1, "sampling floor: an output layer of %d columns exceeds %d", out.w.N, kFloorMaxN);
-  const bool stored = truncated || floored;  // the logits gemm writes the rows and leaves the selection to the next launch
+  // ... and a call under step constraints, greedy or sampled, with the selection that reads the rows' histories (step_constrain.hip)
+  const bool constrained = call.constrained;
+  if (constrained && out.w.N > kConstraintMaxN)
+    return fail(-1, "step constraints: an output layer of %d columns exceeds %d", out.w.N, kConstraintMaxN);
+  const bool stored = truncated || floored || constrained;  // the logits gemm writes the rows and leaves the selection to the next launch
   const int n_parts = stored ? 1 : dgemm_col_blocks(out.w.K, out.w.N, (int)R);
   if (stored) HIPCHK(c->tr_logits.reserve(R * (size_t)out.w.N * 4));
   const EmbedArgs e = embed_args(c);
@@ -3045,6 +3156,29 @@ int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax,
       fa.part_y = g.part_y;
       he = launch_sample_floor(fa, st);
       if (he != hipSuccess) { rc = fail((int)he, "floored sampling: %s", hipGetErrorString(he)); break; }
+    }
+    if (constrained) {  // (the record at this step's start made d_out_ids[r][0 .. d_out_len[r]) the row's history)
+      StepConstrainArgs ca;
+      ca.logits = c->tr_logits.as<float>();
+      ca.B = (int)R;
+      ca.N = out.w.N;
+      ca.inv_T = sampled ? ss.inv_T : 1.0f;
+      ca.seeds = sampled ? ss.seeds : nullptr;
+      ca.shortlist = ds.shortlist;
+      ca.fcol = g.fcol;
+      ca.history = d_out_ids;
+      ca.hist_len = d_out_len;
+      ca.ld_hist = (int)Tmax;
+      ca.eos = eos_id;
+      ca.c = call.cn;
+      ca.part_val = g.part_val;
+      ca.part_idx = g.part_idx;
+      ca.part_sum = g.part_sum;
+      ca.part_mz = g.part_mz;
+      ca.part_zw = g.part_zw;
+      ca.part_y = g.part_y;
+      he = launch_step_constrain(ca, st);
+      if (he != hipSuccess) { rc = fail((int)he, "step constraints: %s", hipGetErrorString(he)); break; }
     }
   }
   if (!rc && !all_done) {
@@ -3215,6 +3349,8 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
       HIPCHK(c->cu_ws.reserve(consensus_units_workspace_bytes((uint32_t)R)));
     }
   }
+  if (call.constrained && Tmax > (size_t)kConstraintMaxHistory)  // (before anything is queued; the kernel's launcher guards its bound too)
+    return fail(-1, "step constraints: Tmax %zu exceeds the history bound %d", Tmax, kConstraintMaxHistory);
   // The K/V cache form (launch_choice.h, kv_cache_form): packed where the persistent pair has it for this shape and S.
   KvFormIn form;
   form.D = m->D; form.F = m->F; form.H = m->H;
@@ -3957,7 +4093,7 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
   MergePlan mp;
   size_t rows = 0;
-  const bool mergeable = n_batches > 1 && n_batches <= (size_t)kMaxMerge && !ctx->call.truncated && !ctx->call.floored;  // (truncated, floored: batch by batch)
+  const bool mergeable = n_batches > 1 && n_batches <= (size_t)kMaxMerge && !ctx->call.truncated && !ctx->call.floored && !ctx->call.constrained;  // (truncated, floored, constrained: batch by batch)
   if (mergeable)
     RCCHK(build_merge_plan(ctx, batches, n_batches, S, Tmax, limit_factor, steps_hint, nullptr, mp, rows, kMergeTile));
   for (size_t j = 0; mergeable && j < n_batches; ++j) mp.opt[j] = opt.user[j];  // (device memory: addressed where it is)
@@ -3986,7 +4122,7 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   const slimt_hip_model *m = ctx->model;
   HIPCHK(hipSetDevice(m->device));
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
-  bool merged = n_batches > 1 && n_batches <= (size_t)kMaxMerge && S <= ctx->max_S && !ctx->call.truncated && !ctx->call.floored;
+  bool merged = n_batches > 1 && n_batches <= (size_t)kMaxMerge && S <= ctx->max_S && !ctx->call.truncated && !ctx->call.floored && !ctx->call.constrained;
   slimt_hip_batch dev[kMaxMerge];
   MergePlan mp;  // (its opt[j].scores: the device views of the pinned score arrays)
   bool any_align = false;
@@ -4424,7 +4560,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
     any_align = any_align || dev[j].align != nullptr;
   }
   const bool fold = env().shortlist_fold;
-  const bool merged = n > 1 && n <= (size_t)kMaxMerge && !ctx->call.truncated && !ctx->call.floored && S <= ctx->max_S && rows <= ctx->max_B && rows * S <= ctx->max_M &&
+  const bool merged = n > 1 && n <= (size_t)kMaxMerge && !ctx->call.truncated && !ctx->call.floored && !ctx->call.constrained && S <= ctx->max_S && rows <= ctx->max_B && rows * S <= ctx->max_M &&
                       merge_supported(ctx, rows, S) && fold &&
                       shortlist_in_launch_lds_bytes((int)sl->source_vocab, (int)sl->target_vocab) <= 64 * 1024;
   if (!merged && o.host_batches) {

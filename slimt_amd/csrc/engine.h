@@ -74,6 +74,7 @@ struct ArmedOptions {
   uint32_t top_k = 0;
   float top_p = 1.0f;
   float min_p = 0.0f, epsilon = 0.0f;  // the sampling floor (slimt_hip_ctx_set_sampling_floor): armed by either above 0
+  StepConstraints cn;                  // step constraints (slimt_hip_ctx_set_step_constraints): armed by cn_armed (constraints.h)
   int cs_order = 0, cs_beta2 = 0;
   bool cs_units = false;  // the selection over unit rows (slimt_hip_ctx_set_fanout_consensus_units): same slot, last arming wins
   uint32_t *cs_best = nullptr;
@@ -90,6 +91,8 @@ struct CallState {
   bool truncated = false;  // sampled, to the top_k largest and the nucleus of mass top_p: per-stage decoder, never merged
   bool floored = false;    // sampled, above the min-p / epsilon floor (floor.h): per-stage decoder, never merged, like a truncated call
   bool fanout = false;     // `rows` decoder rows over the B sources: per-stage decoder, never merged, like a truncated call
+  bool constrained = false;  // greedy or sampled, under step constraints (constraints.h): per-stage decoder, never merged
+  StepConstraints cn;
   bool consensus = false;  // a fan-out call that selects among each source's rows
   float inv_T = 0.0f;
   uint32_t top_k = 0;

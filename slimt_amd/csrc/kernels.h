@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "constraints.h"
+
 namespace slimt_hip {
 
 // A prepared (device-resident) int8 weight: MFMA-B-fragment tiling + the
@@ -891,6 +893,35 @@ struct SampleFloorArgs {
 };
 constexpr int kFloorResidentN = 4096;  // the widest row a workgroup holds in registers (256 threads x 16 columns)
 hipError_t launch_sample_floor(const SampleFloorArgs &a, hipStream_t st);
+
+// ---- step constraints: a selection over stored logits that reads the row's history too (step_constrain.hip) --------------
+// One step of B rows whose logits [B][N] are in memory, under the setting of slimt_hip_ctx_set_step_constraints
+// (constraints.h): row b's history is history[b][0 .. min(hist_len[b], ld_hist)). seeds == nullptr is a greedy step, whose
+// partial has EPI_ARGMAX_SC's format (part_val the maximum z over the candidates, part_sum nullable); with seeds the step
+// is sampled and the partial has EPI_ARGMAX_SM's, as from sample_floor.hip. A row with fcol[b] >= 0 (a forced step) is not
+// constrained. N <= kConstraintMaxN, ld_hist <= kConstraintMaxHistory.
+struct StepConstrainArgs {
+  const float *logits = nullptr;  // [B][N]
+  int B = 0, N = 0;
+  float inv_T = 1.0f;                   // (greedy: 1)
+  const uint32_t *seeds = nullptr;      // nullable [2][B] the rows' hash words of this step (SampledStep::seeds)
+  const uint32_t *shortlist = nullptr;  // [N] the columns' vocabulary ids, sorted (nullptr: the column)
+  const int *fcol = nullptr;            // nullable [B]
+  const uint32_t *history = nullptr;    // [B][ld_hist]
+  const uint32_t *hist_len = nullptr;   // [B]
+  int ld_hist = 0;
+  uint32_t eos = 0;
+  StepConstraints c;
+  float *part_val = nullptr;   // [B] greedy: the best z; sampled: the best key (-FLT_MAX: none)
+  int *part_idx = nullptr;     // [B] ... its column (0x7fffffff: none)
+  float *part_sum = nullptr;   // [B] (greedy: nullable) sum of exp(z - M) over the candidates; NaN where the row holds a NaN
+  float *part_mz = nullptr;    // sampled [B] M, the maximum z over the candidates
+  float *part_zw = nullptr;    // sampled [B] z of the best key's column
+  float *part_y = nullptr;     // nullable [B] z at fcol[b], -inf where there is none
+  uint32_t *n_banned = nullptr;  // nullable [B] banned columns, | kConstraintFallback where the step lifted its bans
+};
+constexpr int kConstrainResidentN = 4096;  // the widest row a workgroup holds in registers (256 threads x 16 columns)
+hipError_t launch_step_constrain(const StepConstrainArgs &a, hipStream_t st);
 
 // ---- beam search: one selection per step over stored logits, and the back-pointer walk (beam_select.hip) ----------------
 // One step of B sources with k slots each (rows r = b k + s, source-major) whose logits [B k][N] are in memory: the

@@ -304,17 +304,20 @@ class Service:
         res.close()
         return out
 
-    def _floored_samples(self, model: Model, per_request: List[List[List[int]]], samples: int, sampling, floor):
+    def _floored_samples(self, model: Model, per_request: List[List[List[int]]], samples: int, sampling, floor, constraints=None):
         """_translate_samples under a min-p / epsilon floor (capi.Context.set_sampling_floor): the same lists and the same
         keys, drawn by fan-out calls (`samples` decoder rows per segment, one encoding of it) on the Service's capi.Context
-        for the model, under the Service's lock, batched as _beam_ranked batches. The C++ service is not involved."""
+        for the model, under the Service's lock, batched as _beam_ranked batches. The C++ service is not involved.
+        constraints: a dict of capi.Context.set_step_constraints' keywords for those calls (floor None then); with
+        sampling None the rows are greedy (samples = 1)."""
         n = int(samples)
         units = [_Unit(r, i, list(seg)) for r, segs in enumerate(per_request) for i, seg in enumerate(segs)]
         if any(len(u.words) > self.ENGINE_LIMIT for u in units):
             raise ValueError(f"samples: a segment has more than {self.ENGINE_LIMIT} tokens")
         if n < 1 or n > self.max_words:
             raise ValueError(f"samples: 1..{self.max_words} samples per call, not {n}")
-        key_of = {(u.request, u.index): [capi.sampling_key(int(sampling[1]), e * n + j) for j in range(n)] for e, u in enumerate(units)}
+        seed = int(sampling[1]) if sampling is not None else 0
+        key_of = {(u.request, u.index): [capi.sampling_key(seed, e * n + j) for j in range(n)] for e, u in enumerate(units)}
         out = [[[None] * len(segs) for segs in per_request] for _ in range(n)]
         per_call = max(1, self.max_words // n)
         batches, cur = [], []
@@ -342,7 +345,8 @@ class Service:
                 got, ln, al, sc = ctx.translate_fanout_pinned(ids, lens, np.repeat(np.arange(B, dtype=np.uint32), n), None,
                                                               self.limit_factor, eos, want_align=True,
                                                               generator=model.shortlist_generator, scores=True,
-                                                              sampling=(float(sampling[0]), keys), floor=floor)
+                                                              sampling=(float(sampling[0]), keys) if sampling is not None else None,
+                                                              floor=floor, constraints=constraints)
                 for b, u in enumerate(batch):
                     for j in range(n):
                         c, L = b * n + j, int(lens[b])
@@ -469,7 +473,7 @@ class Service:
 
     def translate(self, model: Model, texts: Sequence[str], html: bool = False,
                   encoding: Encoding = Encoding.UTF8, scores: bool = False, sampling=None, truncation=None,
-                  samples: Optional[int] = None) -> List[Response]:
+                  samples: Optional[int] = None, constraints=None) -> List[Response]:
         """scores: every Response also carries token_scores (per target sentence, each target token's log-probability,
         EOS included; a wrapped segment's pieces concatenated) and sentence_scores (their sums).
         sampling: (temperature, seed) -- each sentence is one draw from the model at that temperature instead of the
@@ -482,9 +486,26 @@ class Service:
         samples: n >= 1 with sampling -- n draws of every sentence from ONE encoding of it (include/slimt_hip.h,
         slimt_hip_translate_fanout): each Response carries `samples`, its n alternatives as Responses (alternative j holds
         sample j of every sentence, always with scores; the Response returned is alternative 0). Sample j of the call's
-        segment i is drawn under capi.sampling_key(seed, i * n + j)."""
+        segment i is drawn under capi.sampling_key(seed, i * n + j).
+        constraints: a dict of capi.Context.set_step_constraints' keywords (no_repeat_ngram, repetition_penalty, min_length,
+        suppress) -- every step of the call, greedy or sampled, is conditioned on what its sentence has emitted
+        (include/slimt_hip.h, slimt_hip_ctx_set_step_constraints). The call then runs on the Service's capi.Context for the
+        model, as sample_and_select(floor=) does, always with scores (whatever `scores` says); not with truncation or
+        samples. Unlike the plain call it does not split a segment above ENGINE_LIMIT tokens but refuses it, and the engine
+        refuses a length limit (tgt_length_limit_factor x the padded length) above 1024 tokens."""
         if html:
             raise NotImplementedError("HTML markup transfer is outside the ported path (SURVEY.md §2)")
+        if constraints is not None:
+            if truncation is not None or samples is not None:
+                raise ValueError("translate: constraints are not combined with truncation or samples")
+            processed = model.processor.process_many(texts, self.wrap_length, self.workers)
+            if any(len(seg) > self.ENGINE_LIMIT for _, segs in processed for seg in segs):
+                raise ValueError(f"translate: under constraints a segment may have at most {self.ENGINE_LIMIT} tokens")
+            histories = self._floored_samples(model, [segs for _, segs in processed], 1, sampling, None, constraints)[0]
+            out = self._respond_many(model, [src for src, _ in processed], histories)
+            for r in out:
+                r.to(encoding)
+            return out
         if samples is not None:
             if sampling is None or int(samples) < 1:
                 raise ValueError("samples: n >= 1, and only with sampling=(temperature, seed)")
@@ -621,7 +642,7 @@ class Service:
 
     def sample_and_select(self, model: Model, sources: Sequence[str], n: int, sampling, truncation=None,
                           max_order: Optional[int] = None, beta2: int = 4, encoding: Encoding = Encoding.UTF8,
-                          utility: str = "tokens", without_replacement: bool = False, floor=None) -> List[Response]:
+                          utility: str = "tokens", without_replacement: bool = False, floor=None, constraints=None) -> List[Response]:
         """translate(samples=n) followed by the consensus (minimum-Bayes-risk) pick: of the n draws of every sentence, the one
         that agrees most with the others -- the mean token n-gram F (orders 1..max_order, integer beta2 = beta^2; 4 is chrF's)
         against the sentence's other draws (include/slimt_hip.h, slimt_hip_consensus_select). The pick is made on the device
@@ -640,9 +661,13 @@ class Service:
         floor: (min_p, epsilon) -- the draws keep only the tokens above that floor (capi.Context.set_sampling_floor: min-p and
         epsilon sampling). They come from fan-out calls on the Service's capi.Context for the model, under the same keys as
         translate(samples=n), and the pick of either utility runs in a call of its own over the returned rows. Not with
-        truncation, and not without replacement."""
+        truncation, and not without replacement.
+        constraints: a dict of capi.Context.set_step_constraints' keywords -- the draws are made under those step constraints,
+        by the same fan-out calls as with floor=; not with floor, truncation or without replacement."""
         if floor is not None and (truncation is not None or without_replacement):
             raise ValueError("sample_and_select: floor is not combined with truncation or without_replacement")
+        if constraints is not None and (floor is not None or truncation is not None or without_replacement):
+            raise ValueError("sample_and_select: constraints are not combined with floor, truncation or without_replacement")
         if without_replacement:
             return self._select_without_replacement(model, sources, n, sampling, truncation, max_order, beta2, encoding, utility)
         if sampling is None or int(n) < 1:
@@ -658,12 +683,12 @@ class Service:
             raise ValueError(f"samples: a segment has more than {self.ENGINE_LIMIT} tokens")
         histories = [[None] * len(segs) for segs in per_request]
         picked = [([0.0] * len(segs), [0] * len(segs)) for segs in per_request]
-        if flat and (utility == "chrf" or floor is not None):
+        if flat and (utility == "chrf" or floor is not None or constraints is not None):
             n = int(n)
             if n > capi.CONSENSUS_MAX_ROWS:
                 raise ValueError(f"sample_and_select: at most {capi.CONSENSUS_MAX_ROWS} samples, not {n}")
-            if floor is not None:
-                drawn = self._floored_samples(model, per_request, n, sampling, floor)  # [sample][request][segment]
+            if floor is not None or constraints is not None:
+                drawn = self._floored_samples(model, per_request, n, sampling, floor, constraints)  # [sample][request][segment]
             else:
                 drawn = self._translate_samples(model, per_request, n, sampling, truncation)
             where = [(r, i) for r, segs in enumerate(per_request) for i in range(len(segs))]
