@@ -118,6 +118,16 @@ int slimt_hip_sample_floor(const float *logits, size_t M, size_t N, const uint32
                            float temperature, float min_p, float epsilon,
                            const uint64_t *keys, const uint32_t *steps,
                            uint32_t *columns, float *maxima, uint32_t *kept, float *scores);
+/* One locally typical sampled step over the caller's logits [M][N] (host pointers;
+ * the kernel of slimt_hip_ctx_set_sampling_typical alone, which states the rule). N at
+ * most 2^19. ids, keys, steps: as in slimt_hip_sample_truncated. mass is checked as
+ * by slimt_hip_ctx_set_sampling_typical; at mass 1 the rule itself runs and keeps
+ * every column of weight above 0. columns, maxima, kept, scores: as in
+ * slimt_hip_sample_floor. mean_gap (nullable): mean_gap[r] = Ebar, the row's expected
+ * gap to its maximum in units of 2^-16 (0 where the row has no valid column). */
+int slimt_hip_sample_typical(const float *logits, size_t M, size_t N, const uint32_t *ids,
+                             float temperature, float mass, const uint64_t *keys, const uint32_t *steps,
+                             uint32_t *columns, float *maxima, uint32_t *kept, float *scores, uint32_t *mean_gap);
 /* highway (TensorOps.cc:662-682): out = sigmoid(g)*x + (1-sigmoid(g))*y */
 int slimt_hip_highway(const float *x, const float *y, const float *g, size_t n,
                       float *out);
@@ -443,6 +453,57 @@ int slimt_hip_ctx_set_sampling_truncation(slimt_hip_ctx *ctx, uint32_t top_k, fl
  * context's mode is not changed and slimt_hip_ctx_plan keeps reporting it. The
  * _many_ entry points do not merge a floored call. */
 int slimt_hip_ctx_set_sampling_floor(slimt_hip_ctx *ctx, float min_p, float epsilon);
+/* Locally typical sampling (Meister et al. 2022) for the NEXT translate call on ctx,
+ * which must be a sampled one (slimt_hip_ctx_set_sampling): a drawn step keeps the
+ * tokens whose surprisal is closest to the step's entropy, up to the probability
+ * mass `mass`. Armed for that call, which consumes it whether it succeeds or fails,
+ * like every other per-call option. mass must be finite with 0 < mass <= 1, else a
+ * negative status at once; mass == 1 arms nothing and the call is the plain sampled
+ * call, same kernels included. A translate call that finds it armed fails with a
+ * negative status and a message, and still consumes the setting, when no sampling is
+ * armed, when top-k / top-p truncation, a min-p / epsilon floor or step constraints
+ * are armed too -- none of them is combined with it --, when it is a beam call
+ * (slimt_hip_translate_beam*), or when the output layer has more than 2^19 columns.
+ * The score entry points neither read nor consume the setting.
+ *
+ * One drawn step. l_c, inv_T, z_c = l_c * inv_T, validity and n_valid are as for the
+ * truncation above; M is the maximum valid z and w_c = tr_weight(z_c, M) in
+ * [0, 2^24] (slimt_amd/csrc/truncation.h, unchanged). With p_c = w_c / Q the
+ * surprisal minus the entropy is (M - z_c) - E[M - z]: the log-partition cancels, so
+ * only the expected gap is needed, and it is an integer. The definition is
+ * slimt_amd/csrc/typical.h.
+ *  1. Gap. G_c = 0 if z_c == M (tested first: M = +-inf never forms inf - inf);
+ *     otherwise d = z_c - M, the float subtraction tr_weight makes, and
+ *     G_c = (uint32_t)(-d * 65536.0f): the product is exact and the conversion
+ *     truncates. G is read only where w_c > 0; there d > -17 and G < 17 * 2^16 < 2^21.
+ *  2. Totals. Q = sum of w_c and A = sum of w_c * G_c over the valid columns, both
+ *     uint64. Each product is below 2^45, so both sums are exact in any order for
+ *     N <= 2^19. Ebar = A / Q by uint64 floor division (Q >= 2^24 whenever a valid
+ *     column exists).
+ *  3. Key. key_c = G_c >= Ebar ? G_c - Ebar : Ebar - G_c, a uint32.
+ *  4. Threshold. kappa is the smallest value v among { key_c : w_c > 0 } with
+ *       (double)(sum of w_c over w_c > 0, key_c <= v) >= (double)mass * (double)Q
+ *     (one IEEE double product; both sums are exact below 2^53: the nucleus's
+ *     comparison).
+ *  5. K = { valid c : w_c > 0 and key_c <= kappa }. Ties at the boundary are all in;
+ *     K depends on values alone; K is never empty while a valid column exists; K need
+ *     not hold the most probable column -- that is the method, not a defect. With
+ *     n_valid == 0 nothing is kept: class 0 and score NaN.
+ *  6. Token and score are steps 4 and 5 of the truncation above over this K: the
+ *     first maximum of fmaf(l_c, inv_T, g(k_b, t, y_c)) from -FLT_MAX with strict >,
+ *     and forced_score(sum over K of exp(z_c - M), z_token - M, none). A NaN anywhere
+ *     in the row makes the score NaN.
+ * Forced steps (slimt_hip_ctx_set_target_prefix) draw nothing and are not cut: they
+ * are scored over the WHOLE layer, as in a truncated call.
+ * Execution: like a truncated or floored call a typical one DECODES with the
+ * per-stage kernels whatever mode the context is in (K/V cache format 3 included),
+ * the logits gemm storing the row, with one selection kernel per step
+ * (slimt_amd/csrc/sample_typical.hip: one read of the row, weights and keys in
+ * registers up to 4096 columns, an ascending radix descent on the 21-bit key); on a
+ * fan-out call per decoder row. The context's mode is not changed and
+ * slimt_hip_ctx_plan keeps reporting it. The _many_ entry points do not merge a
+ * typical call: it goes batch by batch. */
+int slimt_hip_ctx_set_sampling_typical(slimt_hip_ctx *ctx, float mass);
 /* Step constraints: the NEXT translate call's choices conditioned on what each row
  * has already emitted. Armed for that call, which consumes the setting whether it
  * succeeds or fails, like every other per-call option; the suppress list is copied

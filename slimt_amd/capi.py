@@ -45,6 +45,7 @@ SYMBOLS = [
     "slimt_hip_ctx_set_scores", "slimt_hip_ctx_set_target_prefix", "slimt_hip_ctx_set_sampling", "slimt_hip_sampling_key",
     "slimt_hip_ctx_set_sampling_truncation", "slimt_hip_sample_truncated",
     "slimt_hip_ctx_set_sampling_floor", "slimt_hip_sample_floor",
+    "slimt_hip_ctx_set_sampling_typical", "slimt_hip_sample_typical",
     "slimt_hip_ctx_set_step_constraints", "slimt_hip_constrained_step",
     "slimt_hip_score", "slimt_hip_score_async", "slimt_hip_score_device", "slimt_hip_score_async_generated",
     "slimt_hip_ctx_set_score_alternatives", "slimt_hip_debug_ctx_shortlists", "slimt_hip_debug_ctx_set_counters",
@@ -234,6 +235,8 @@ def lib():
     L.slimt_hip_sample_truncated.argtypes = [vp, sz, sz, vp, f32, u32, f32, vp, vp, vp, vp, vp, vp]
     L.slimt_hip_ctx_set_sampling_floor.argtypes = [vp, f32, f32]
     L.slimt_hip_sample_floor.argtypes = [vp, sz, sz, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp]
+    L.slimt_hip_ctx_set_sampling_typical.argtypes = [vp, f32]
+    L.slimt_hip_sample_typical.argtypes = [vp, sz, sz, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp]
     L.slimt_hip_ctx_set_step_constraints.argtypes = [vp, vp]
     L.slimt_hip_constrained_step.argtypes = [vp, sz, sz, vp, vp, vp, sz, vp, u32, f32, vp, vp, vp, vp, vp]
     L.slimt_hip_ctx_plan.argtypes = [vp, sz, vp, vp]
@@ -369,6 +372,24 @@ def sample_floor(logits, temperature: float = 1.0, min_p: float = 0.0, epsilon: 
     _chk(lib().slimt_hip_sample_floor(_p(logits), M, N, _p(ids), float(temperature), float(min_p), float(epsilon), _p(keys),
                                       _p(steps), _p(cols), _p(mx), _p(kept), _p(sc)))
     return cols, mx, kept, sc
+
+
+def sample_typical(logits, temperature: float = 1.0, mass: float = 1.0, ids=None, keys=None, steps=None):
+    """slimt_hip_sample_typical: one locally typical sampled step of mass `mass` over logits [M, N] (float32); ids, keys, steps
+    as in sample_truncated. Returns (columns uint32 [M], maxima float32 [M], kept uint32 [M], scores float32 [M], mean_gap
+    uint32 [M]: the rows' expected gap to the maximum in units of 2^-16)."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    M, N = logits.shape
+    ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32)
+    keys = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint64)
+    steps = None if steps is None else np.ascontiguousarray(steps, dtype=np.uint32)
+    if (ids is not None and ids.shape != (N,)) or (keys is not None and keys.shape != (M,)) or (steps is not None and steps.shape != (M,)):
+        raise ValueError("sample_typical: ids [N], keys [M] and steps [M] expected")
+    cols, mx, gap = np.zeros(M, np.uint32), np.zeros(M, np.float32), np.zeros(M, np.uint32)
+    kept, sc = np.zeros(M, np.uint32), np.zeros(M, np.float32)
+    _chk(lib().slimt_hip_sample_typical(_p(logits), M, N, _p(ids), float(temperature), float(mass), _p(keys), _p(steps), _p(cols),
+                                        _p(mx), _p(kept), _p(sc), _p(gap)))
+    return cols, mx, kept, sc, gap
 
 
 CONSTRAINT_MAX_NGRAM, CONSTRAINT_MAX_SUPPRESS, CONSTRAINT_MAX_HISTORY = 8, 64, 1024  # (include/slimt_hip.h)
@@ -951,6 +972,13 @@ class Context:
         `sampling=` and do this."""
         _chk(lib().slimt_hip_ctx_set_sampling_floor(self.h, float(min_p), float(epsilon)))
 
+    def set_sampling_typical(self, mass: float = 1.0):
+        """slimt_hip_ctx_set_sampling_typical: keep, in the NEXT translate call's sampling (armed with set_sampling), the tokens
+        whose surprisal is closest to the step's entropy, up to the probability mass `mass` in (0, 1] (1: off). Not combined
+        with set_sampling_truncation, set_sampling_floor or set_step_constraints. The translate wrappers take `typical=mass`
+        beside `sampling=` and do this."""
+        _chk(lib().slimt_hip_ctx_set_sampling_typical(self.h, float(mass)))
+
     def set_step_constraints(self, no_repeat_ngram: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress=()):
         """slimt_hip_ctx_set_step_constraints: condition the NEXT translate call's steps, greedy or sampled, on what each row
         has emitted: no token that would repeat an n-gram of size no_repeat_ngram (0: off; at most 8), the logits of emitted
@@ -1034,7 +1062,7 @@ class Context:
 
     def translate(self, ids, lengths, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
                   want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None, floor=None,
-                  constraints=None):
+                  constraints=None, typical=None):
         """Model::forward. Returns out_ids [B,Tmax], out_len [B], align|None (+ scores [B,Tmax] float32 with
         scores=True: the log-probability of each recorded token, include/slimt_hip.h slimt_hip_ctx_set_scores).
         prefix: (ids [B,Tmax], lens [B]) uint32 -- forced target prefixes (slimt_hip_ctx_set_target_prefix).
@@ -1064,6 +1092,8 @@ class Context:
             self.set_sampling_truncation(*truncation)
         if floor is not None:
             self.set_sampling_floor(*floor)
+        if typical is not None:
+            self.set_sampling_typical(typical)
         if constraints is not None:
             self.set_step_constraints(**constraints)
         _chk(lib().slimt_hip_translate(self.h, _p(ids), _p(lengths), B, S, _p(sl),
@@ -1081,7 +1111,7 @@ class Context:
                 pin("al").array(np.float32, (B, T, S)) if want_align else None)
 
     def translate_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
-                        scores=None, prefix=None, sampling=None, truncation=None, floor=None, constraints=None):
+                        scores=None, prefix=None, sampling=None, truncation=None, floor=None, constraints=None, typical=None):
         """slimt_hip_translate_async[_generated] on arrays from pinned_buffers() (already filled);
         synchronize() before reading the outputs. `generator`: a ShortlistGenerator -- the batch's
         lexical shortlist is then generated on this context's stream (Model.cc:117-120).
@@ -1104,6 +1134,8 @@ class Context:
             self.set_sampling_truncation(*truncation)
         if floor is not None:
             self.set_sampling_floor(*floor)
+        if typical is not None:
+            self.set_sampling_typical(typical)
         if constraints is not None:
             self.set_step_constraints(**constraints)
         if generator is not None:
@@ -1115,7 +1147,7 @@ class Context:
 
     def translate_pinned(self, ids, lengths, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
                          want_align: bool = False, generator=None, scores: bool = False, prefix=None, sampling=None, truncation=None, floor=None,
-                         constraints=None):
+                         constraints=None, typical=None):
         """translate() through this context's pinned staging buffers and slimt_hip_translate_async:
         the persistent kernels then read and write host memory themselves, no copy is queued (host
         pipelines with several contexts: copies of one stream wait behind other streams' kernels).
@@ -1127,13 +1159,13 @@ class Context:
         bufs[1][...] = lengths
         sc = self._pinned.setdefault("sc", _Pinned()).array(np.float32, bufs[2].shape) if scores else None
         self.translate_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix, sampling=sampling,
-                             truncation=truncation, floor=floor, constraints=constraints)
+                             truncation=truncation, floor=floor, constraints=constraints, typical=typical)
         self.synchronize()
         out = bufs[2].copy(), bufs[3].copy(), (bufs[4].copy() if want_align else None)
         return out + (sc.copy(),) if scores else out
 
     def translate_generated(self, generator, ids, lengths, limit_factor: float = 1.5, eos_id: int = 0,
-                            want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None, floor=None):
+                            want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None, floor=None, typical=None):
         """Model::forward with its shortlist step (slimt_hip_translate_generated): host arrays, blocking.
         prefix: as in translate()."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
@@ -1156,13 +1188,15 @@ class Context:
             self.set_sampling_truncation(*truncation)
         if floor is not None:
             self.set_sampling_floor(*floor)
+        if typical is not None:
+            self.set_sampling_typical(typical)
         _chk(lib().slimt_hip_translate_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, limit_factor,
                                                  eos_id, _p(out_ids), _p(out_len), _p(align)))
         self._prefix_keep = []  # (a blocking call: done with its prefix)
         return (out_ids, out_len, align, sc) if scores else (out_ids, out_len, align)
 
     # ---- fan-out: N decoder rows over B sources encoded once (include/slimt_hip.h, slimt_hip_translate_fanout*) ----
-    def _arm(self, N: int, scores, prefix, sampling, truncation, T: int, floor=None, constraints=None):
+    def _arm(self, N: int, scores, prefix, sampling, truncation, T: int, floor=None, constraints=None, typical=None):
         """arms a one-batch call's options, shaped by its N rows (right before the call that takes them)"""
         pre = self._prefix_host(prefix, N, T) if prefix is not None else None
         if scores is not None:
@@ -1176,12 +1210,14 @@ class Context:
             self.set_sampling_truncation(*truncation)
         if floor is not None:
             self.set_sampling_floor(*floor)
+        if typical is not None:
+            self.set_sampling_typical(typical)
         if constraints is not None:
             self.set_step_constraints(**constraints)
 
     def translate_fanout(self, ids, lengths, row_src, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
                          want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None,
-                         consensus=None, floor=None, constraints=None):
+                         consensus=None, floor=None, constraints=None, typical=None):
         """slimt_hip_translate_fanout: translate() with N decoder rows over the B sources ids [B,S] / lengths [B], encoded
         once; row_src [N] uint32 names each row's source. Returns out_ids [N,Tmax], out_len [N], align [N,Tmax,S] | None
         (+ scores [N,Tmax]). prefix, sampling, truncation: as in translate(), shaped by N. Every row is bit for bit its row
@@ -1202,7 +1238,7 @@ class Context:
         out_len = np.zeros(N, dtype=np.uint32)
         align = np.zeros((N, T, S), dtype=np.float32) if want_align else None
         sc = np.full((N, T), np.nan, dtype=np.float32) if scores else None
-        self._arm(N, sc, prefix, sampling, truncation, T, floor, constraints)
+        self._arm(N, sc, prefix, sampling, truncation, T, floor, constraints, typical)
         cs = self._arm_consensus(consensus, B, N) if consensus is not None else ()
         _chk(lib().slimt_hip_translate_fanout(self.h, _p(ids), _p(lengths), B, S, _p(row_src), N, _p(sl),
                                               0 if sl is None else sl.size, limit_factor, eos_id, _p(out_ids), _p(out_len),
@@ -1221,7 +1257,7 @@ class Context:
 
     def translate_fanout_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
                                scores=None, prefix=None, sampling=None, truncation=None, consensus=None, floor=None,
-                               constraints=None):
+                               constraints=None, typical=None):
         """slimt_hip_translate_fanout_async[_generated] on (ids, lengths, row_src, out_ids, out_len, align | None) host arrays
         (already filled; those of fanout_buffers() are pinned); synchronize() before reading the outputs. scores: a float32
         [N, Tmax] array; prefix, sampling, truncation: as in translate_async(), shaped by N.
@@ -1238,7 +1274,7 @@ class Context:
         if align is not None and (align.dtype != np.float32 or align.shape != (N, T, S) or not align.flags.c_contiguous):
             raise ValueError("translate_fanout_async: a C-contiguous float32 align of shape %s expected" % ((N, T, S),))
         sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
-        self._arm(N, scores, prefix, sampling, truncation, T, floor, constraints)
+        self._arm(N, scores, prefix, sampling, truncation, T, floor, constraints, typical)
         cs = self._arm_consensus(consensus, B, N) if consensus is not None else None
         if generator is not None:
             _chk(lib().slimt_hip_translate_fanout_async_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, _p(row_src),
@@ -1251,7 +1287,7 @@ class Context:
 
     def translate_fanout_pinned(self, ids, lengths, row_src, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
                                 want_align: bool = False, generator=None, scores: bool = False, prefix=None, sampling=None,
-                                truncation=None, consensus=None, floor=None, constraints=None):
+                                truncation=None, consensus=None, floor=None, constraints=None, typical=None):
         """translate_fanout() through this context's pinned arrays and slimt_hip_translate_fanout_async; returns copies."""
         ids, row_src = np.asarray(ids), np.asarray(row_src)
         B, S = ids.shape
@@ -1262,7 +1298,7 @@ class Context:
         sc = self._pinned.setdefault("fo_sc", _Pinned()).array(np.float32, bufs[3].shape) if scores else None
         cs = self.translate_fanout_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix,
                                          sampling=sampling, truncation=truncation, floor=floor, consensus=consensus,
-                                         constraints=constraints)
+                                         constraints=constraints, typical=typical)
         self.synchronize()
         out = bufs[3].copy(), bufs[4].copy(), (bufs[5].copy() if want_align else None)
         return (out + (sc.copy(),) if scores else out) + tuple(cs or ())
@@ -1270,7 +1306,7 @@ class Context:
     def translate_fanout_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_row_src: int, N: int, d_shortlist: int,
                                 n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int, d_out_len: int,
                                 d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None,
-                                truncation=None, consensus=None, floor=None):
+                                truncation=None, consensus=None, floor=None, typical=None):
         """slimt_hip_translate_fanout_device: device pointers (ints) in and out, like translate_device(); d_row_src [N]
         uint32 (a value >= B is taken as B - 1), outputs and options shaped by N. consensus: ([kind,] max_order, beta2,
         d_best, d_utility) with the device pointers of best [B] uint32 and utility [N] float64."""
@@ -1285,6 +1321,8 @@ class Context:
             self.set_sampling_truncation(*truncation)
         if floor is not None:
             self.set_sampling_floor(*floor)
+        if typical is not None:
+            self.set_sampling_typical(typical)
         if consensus is not None:
             units, rest = self._consensus_kind(consensus)
             self.set_fanout_consensus(*rest, units=units)
@@ -1728,7 +1766,7 @@ class Context:
 
     def translate_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_shortlist: int,
                          n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int,
-                         d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None, truncation=None, floor=None):
+                         d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None, truncation=None, floor=None, typical=None):
         """Device pointers (ints) in and out; asynchronous when steps_hint > 0. scores: a device pointer to
         [B, Tmax] floats for the tokens' log-probabilities (0 = none). prefix: (d_ids, d_lens) device pointers of a
         forced target prefix ([B, Tmax] and [B] uint32)."""
@@ -1746,10 +1784,12 @@ class Context:
             self.set_sampling_truncation(*truncation)
         if floor is not None:
             self.set_sampling_floor(*floor)
+        if typical is not None:
+            self.set_sampling_typical(typical)
         _chk(lib().slimt_hip_translate_device(*args))
 
     def translate_many_device(self, batches, S: int, limit_factor: float, eos_id: int, steps_hint: int = 0, generator=None,
-                              scores=None, prefix=None, sampling=None, truncation=None, floor=None):
+                              scores=None, prefix=None, sampling=None, truncation=None, floor=None, typical=None):
         """slimt_hip_translate_many_device: `batches` = [(d_ids, d_lengths, B, d_shortlist, n_shortlist, d_out_ids,
         d_out_len, d_align[, S_j])] of device pointers (ints; 0 = none) -- ONE encoder and ONE decoder launch for all of them;
         S_j: that batch's own padded length (<= S; default S). scores: one device pointer per batch ([B_j, Tmax_j] floats).
@@ -1770,13 +1810,15 @@ class Context:
             self.set_sampling_truncation(*truncation)
         if floor is not None:
             self.set_sampling_floor(*floor)
+        if typical is not None:
+            self.set_sampling_typical(typical)
         if generator is not None:
             _chk(lib().slimt_hip_translate_many_device_generated(self.h, generator.h, arr, len(batches), S, limit_factor, eos_id, steps_hint))
             return
         _chk(lib().slimt_hip_translate_many_device(self.h, arr, len(batches), S, limit_factor, eos_id, steps_hint))
 
     def translate_many_async(self, bufs_list, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0, generator=None,
-                             scores=None, prefix=None, sampling=None, truncation=None, floor=None):
+                             scores=None, prefix=None, sampling=None, truncation=None, floor=None, typical=None):
         """slimt_hip_translate_many_async on a list of pinned buffer tuples (ids, lengths, out_ids, out_len, align|None),
         one shortlist (host array) or none for all; synchronize() before reading the outputs.
         scores: one float32 [B_j, Tmax_j] array per batch (pinned: the merged launch writes them in place).
@@ -1812,6 +1854,8 @@ class Context:
             self.set_sampling_truncation(*truncation)
         if floor is not None:
             self.set_sampling_floor(*floor)
+        if typical is not None:
+            self.set_sampling_typical(typical)
         if generator is not None:  # every batch's own lexical shortlist, generated inside the encoder launch
             _chk(lib().slimt_hip_translate_many_async_generated(self.h, generator.h, arr, len(bufs_list), S, limit_factor, eos_id))
             return
@@ -1819,7 +1863,7 @@ class Context:
 
     def translate_device_generated(self, gen: "ShortlistGenerator", d_ids: int, d_lengths: int, B: int,
                                    S: int, limit_factor: float, eos_id: int, d_out_ids: int,
-                                   d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None, truncation=None, floor=None):
+                                   d_out_len: int, d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None, truncation=None, floor=None, typical=None):
         """Shortlist generation + translate, all on this context's stream. scores, prefix: as in translate_device."""
         vp = C.c_void_p
         args = (self.h, gen.h, vp(d_ids), vp(d_lengths), B, S, limit_factor, eos_id, vp(d_out_ids),
@@ -1834,6 +1878,8 @@ class Context:
             self.set_sampling_truncation(*truncation)
         if floor is not None:
             self.set_sampling_floor(*floor)
+        if typical is not None:
+            self.set_sampling_typical(typical)
         _chk(lib().slimt_hip_translate_device_generated(*args))
 
     def encode(self, ids, lengths, want_embed=False, want_layers=False):

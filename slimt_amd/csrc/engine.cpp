@@ -5,6 +5,7 @@
 #include "scores.h"
 #include "constraints.h"
 #include "floor.h"
+#include "typical.h"
 #include "truncation.h"
 #include "beam.h"
 #include "beam_sampled.h"
@@ -103,13 +104,13 @@ static const EnvKnobs &env() {
 
 // The persistent decoder runs the hoisted cross-attention order over a cache of accumulators; the reference's literal
 // sequence (K/V cache format 3) exists in the stage-wise attention kernel only (decode_kernels.hip, DQAttnArgs::literal)
-// ... and a truncated or floored sampled call needs each step's whole row of logits, which only the stage-wise decoder stores,
+// ... and a truncated, floored or typical sampled call needs each step's whole row of logits, which only the stage-wise decoder stores,
 // as does a call under step constraints (constraints.h), greedy or sampled; a
 // fan-out call's cross-attention looks a row's source up, which only the stage-wise one does (decode_fanout.hip). Every
 // decision that hangs on the persistent decoder -- the lean path, pinned arrays read in place, merged launches -- asks here;
 // the encoder is chosen as the context's mode says.
 static bool fused_decoder_allowed(const slimt_hip_ctx *c) {
-  return c->decode_mode != 1 && c->model->kv_format != 3 && !c->call.truncated && !c->call.floored && !c->call.constrained && !c->call.fanout;
+  return c->decode_mode != 1 && c->model->kv_format != 3 && !c->call.truncated && !c->call.floored && !c->call.typical && !c->call.constrained && !c->call.fanout;
 }
 // The decoder rows of the call in progress: a fan-out call's N, else one per source.
 static int decoder_rows(const slimt_hip_ctx *c) { return c->call.fanout ? c->call.rows : c->B; }
@@ -671,6 +672,64 @@ extern "C" int slimt_hip_sample_floor(const float *logits, size_t M, size_t N, c
     scores[r] = slimt_hip::forced_score(h[2 * M + r], h[4 * M + r] - h[3 * M + r], none);
     maxima[r] = h[3 * M + r];
     memcpy(&kept[r], &h[5 * M + r], 4);
+  }
+  return 0;
+}
+
+extern "C" int slimt_hip_sample_typical(const float *logits, size_t M, size_t N, const uint32_t *ids, float temperature, float mass,
+                                        const uint64_t *keys, const uint32_t *steps, uint32_t *columns, float *maxima, uint32_t *kept,
+                                        float *scores, uint32_t *mean_gap) {
+  if (!(temperature > 0.0f) || !std::isfinite(temperature)) return fail(-1, "sampling: temperature %g is not finite and > 0", (double)temperature);
+  const float inv_T = 1.0f / temperature;
+  if (!(inv_T > 0.0f) || !std::isfinite(inv_T)) return fail(-1, "sampling: 1 / temperature %g is not finite and > 0", (double)temperature);
+  if (!slimt_hip::ty_valid(mass)) return fail(-1, "typical sampling: mass %g is not in (0, 1]", (double)mass);
+  if (!logits || !columns || !maxima || !kept || !scores || !M || !N) return fail(-1, "bad argument");
+  if (M > 0x7fffffffu || N > (size_t)kTypicalMaxN) return fail(-1, "sample_typical: more than %d rows or %d columns", 0x7fffffff, kTypicalMaxN);
+  std::vector<uint32_t> seeds(2 * M);  // the rows' hash words (sampling.h), as decode_begin_step_sm_kernel writes them
+  for (size_t r = 0; r < M; ++r) {
+    const uint64_t w = slimt_hip::sm_step_words(keys ? keys[r] : (uint64_t)r, steps ? steps[r] : 0u);
+    seeds[r] = (uint32_t)w;
+    seeds[M + r] = (uint32_t)(w >> 32);
+  }
+  Tmp3 t;
+  hipStream_t st = nullptr;
+  HIPCHK(t.a.reserve(M * N * 4));
+  HIPCHK(t.b.reserve(N * 4));
+  HIPCHK(t.c.reserve(2 * M * 4));
+  HIPCHK(t.d.reserve(7 * M * 4));
+  HIPCHK(hipMemcpyAsync(t.a.p, logits, M * N * 4, hipMemcpyHostToDevice, st));
+  if (ids) HIPCHK(hipMemcpyAsync(t.b.p, ids, N * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.p, seeds.data(), 2 * M * 4, hipMemcpyHostToDevice, st));
+  SampleTypicalArgs a;
+  a.logits = t.a.as<float>();
+  a.B = (int)M;
+  a.N = (int)N;
+  a.inv_T = inv_T;
+  a.mass = mass;
+  a.seeds = t.c.as<uint32_t>();
+  a.shortlist = ids ? t.b.as<uint32_t>() : nullptr;
+  float *o = t.d.as<float>();
+  a.part_val = o;
+  a.part_idx = reinterpret_cast<int *>(o + M);
+  a.part_sum = o + 2 * M;
+  a.part_mz = o + 3 * M;
+  a.part_zw = o + 4 * M;
+  a.kept = reinterpret_cast<uint32_t *>(o + 5 * M);
+  a.mean_gap = reinterpret_cast<uint32_t *>(o + 6 * M);
+  HIPCHK(launch_sample_typical(a, st));
+  std::vector<float> h(7 * M);
+  HIPCHK(hipMemcpyAsync(h.data(), t.d.p, 7 * M * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (size_t r = 0; r < M; ++r) {
+    int col;
+    memcpy(&col, &h[M + r], 4);
+    // the "none" rule of decode_begin_step_sm_kernel: no key beat the start value, or logit 0 is NaN -- class 0, score NaN
+    const bool none = col == 0x7fffffff || logits[r * N] != logits[r * N];
+    columns[r] = none ? 0u : (uint32_t)col;
+    scores[r] = slimt_hip::forced_score(h[2 * M + r], h[4 * M + r] - h[3 * M + r], none);
+    maxima[r] = h[3 * M + r];
+    memcpy(&kept[r], &h[5 * M + r], 4);
+    if (mean_gap) memcpy(&mean_gap[r], &h[6 * M + r], 4);
   }
   return 0;
 }
@@ -1710,6 +1769,14 @@ extern "C" int slimt_hip_ctx_set_sampling_floor(slimt_hip_ctx *ctx, float min_p,
   return 0;
 }
 
+extern "C" int slimt_hip_ctx_set_sampling_typical(slimt_hip_ctx *ctx, float mass) {
+  // (the value first, like the temperature)
+  if (!slimt_hip::ty_valid(mass)) return fail(-1, "typical sampling: mass %g is not in (0, 1]", (double)mass);
+  if (!ctx) return fail(-1, "null argument");
+  ctx->armed.typical_mass = mass;  // (1: nothing armed, the call is a plain sampled call)
+  return 0;
+}
+
 extern "C" int slimt_hip_ctx_set_step_constraints(slimt_hip_ctx *ctx, const slimt_hip_step_constraints *constraints) {
   // (the values first, like the temperature)
   slimt_hip::StepConstraints cn;
@@ -1982,10 +2049,10 @@ struct MergePlan {
 // ctx->armed here -- consumed whether or not the call then succeeds -- checked against the call's n batches, and becomes
 // ctx->call, the record every inner function reads; `user` holds the per-batch arrays as the caller gave them, one entry per
 // batch, for the entry point to hand on: as they are where they are device memory (options_in_place), through
-// stage_options where they are host memory. The checks run scores -> prefix -> sampling -> truncation -> floor -> step constraints -> consensus -> beam
+// stage_options where they are host memory. The checks run scores -> prefix -> sampling -> truncation -> floor -> typical -> step constraints -> consensus -> beam
 // sampling and the first refusal is the call's (rc); a truncated call must be sampled, so the truncation is looked at behind
 // the sampling. Beam sampling (slimt_hip_ctx_set_beam_sampling) is for the beam entry points (beam) only.
-// While call.truncated, call.floored, call.constrained or call.fanout is set fused_decoder_allowed() is false: the call decodes with the per-stage kernels
+// While call.truncated, call.floored, call.typical, call.constrained or call.fanout is set fused_decoder_allowed() is false: the call decodes with the per-stage kernels
 // and is never merged; the context's decode mode is not touched and still chooses the encoder. Consensus is for the
 // fan-out entry points (fanout) only: any other call that finds it armed is refused. The destructor empties ctx->call.
 // The score entry points (slimt_hip_score*) open no CallOptions: they neither read nor consume what was armed.
@@ -2075,12 +2142,24 @@ struct CallOptions {
       call.min_p = a.min_p;
       call.epsilon = a.epsilon;
     }
+    if (ty_armed(a.typical_mass)) {
+      if (beam) return fail(-1, "typical sampling: armed on a beam call (slimt_hip_translate_beam*); a beam call is not sampled");
+      if (!call.sampled) return fail(-1, "typical sampling: armed without sampling (slimt_hip_ctx_set_sampling)");
+      if (call.truncated)
+        return fail(-1, "typical sampling: top-k / top-p truncation is armed too (slimt_hip_ctx_set_sampling_truncation); the two are not combined");
+      if (call.floored)
+        return fail(-1, "typical sampling: a sampling floor is armed too (slimt_hip_ctx_set_sampling_floor); the two are not combined");
+      call.typical = true;
+      call.typical_mass = a.typical_mass;
+    }
     if (cn_armed(a.cn)) {
       if (beam) return fail(-1, "step constraints: armed on a beam call (slimt_hip_translate_beam*); beams are not constrained");
       if (call.truncated)
         return fail(-1, "step constraints: top-k / top-p truncation is armed too (slimt_hip_ctx_set_sampling_truncation); the two are not combined");
       if (call.floored)
         return fail(-1, "step constraints: a sampling floor is armed too (slimt_hip_ctx_set_sampling_floor); the two are not combined");
+      if (call.typical)
+        return fail(-1, "step constraints: typical sampling is armed too (slimt_hip_ctx_set_sampling_typical); the two are not combined");
       call.constrained = true;
       call.cn = a.cn;
     }
@@ -3010,7 +3089,7 @@ int admit_and_launch_fused(slimt_hip_ctx *c, FusedDecodeArgs &f, size_t B, size_
   return 0;
 }
 
-// ---- the step-wise loop: every call the persistent decoder refuses (truncated, floored, constrained, fan-out, beam, consensus; decode mode 1,
+// ---- the step-wise loop: every call the persistent decoder refuses (truncated, floored, typical, constrained, fan-out, beam, consensus; decode mode 1,
 // K/V format 3, shapes without the kernel) ----------------------------------------------------------------------------
 int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax, const uint32_t *d_shortlist, uint32_t eos_id,
                     uint32_t *d_out_ids, uint32_t *d_out_len, float *d_align, float *d_scores, int steps_hint, bool merged) {
@@ -3038,11 +3117,15 @@ int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax,
   const bool floored = sampled && call.floored;
   if (call.floored && !floored) return fail(-1, "sampling floor: the call is not sampled");
   if (floored && out.w.N > kFloorMaxN) return fail(-1, "sampling floor: an output layer of %d columns exceeds %d", out.w.N, kFloorMaxN);
+  // ... and a typical call (sample_typical.hip)
+  const bool typical = sampled && call.typical;
+  if (call.typical && !typical) return fail(-1, "typical sampling: the call is not sampled");
+  if (typical && out.w.N > kTypicalMaxN) return fail(-1, "typical sampling: an output layer of %d columns exceeds %d", out.w.N, kTypicalMaxN);
   // ... and a call under step constraints, greedy or sampled, with the selection that reads the rows' histories (step_constrain.hip)
   const bool constrained = call.constrained;
   if (constrained && out.w.N > kConstraintMaxN)
     return fail(-1, "step constraints: an output layer of %d columns exceeds %d", out.w.N, kConstraintMaxN);
-  const bool stored = truncated || floored || constrained;  // the logits gemm writes the rows and leaves the selection to the next launch
+  const bool stored = truncated || floored || typical || constrained;  // the logits gemm writes the rows and leaves the selection to the next launch
   const int n_parts = stored ? 1 : dgemm_col_blocks(out.w.K, out.w.N, (int)R);
   if (stored) HIPCHK(c->tr_logits.reserve(R * (size_t)out.w.N * 4));
   const EmbedArgs e = embed_args(c);
@@ -3156,6 +3239,25 @@ int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax,
       fa.part_y = g.part_y;
       he = launch_sample_floor(fa, st);
       if (he != hipSuccess) { rc = fail((int)he, "floored sampling: %s", hipGetErrorString(he)); break; }
+    }
+    if (typical) {
+      SampleTypicalArgs ya;
+      ya.logits = c->tr_logits.as<float>();
+      ya.B = (int)R;
+      ya.N = out.w.N;
+      ya.inv_T = ss.inv_T;
+      ya.mass = call.typical_mass;
+      ya.seeds = ss.seeds;
+      ya.shortlist = ds.shortlist;
+      ya.fcol = g.fcol;
+      ya.part_val = g.part_val;
+      ya.part_idx = g.part_idx;
+      ya.part_sum = g.part_sum;
+      ya.part_mz = g.part_mz;
+      ya.part_zw = g.part_zw;
+      ya.part_y = g.part_y;
+      he = launch_sample_typical(ya, st);
+      if (he != hipSuccess) { rc = fail((int)he, "typical sampling: %s", hipGetErrorString(he)); break; }
     }
     if (constrained) {  // (the record at this step's start made d_out_ids[r][0 .. d_out_len[r]) the row's history)
       StepConstrainArgs ca;
@@ -4093,7 +4195,7 @@ extern "C" int slimt_hip_translate_many_device(slimt_hip_ctx *ctx, const slimt_h
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
   MergePlan mp;
   size_t rows = 0;
-  const bool mergeable = n_batches > 1 && n_batches <= (size_t)kMaxMerge && !ctx->call.truncated && !ctx->call.floored && !ctx->call.constrained;  // (truncated, floored, constrained: batch by batch)
+  const bool mergeable = n_batches > 1 && n_batches <= (size_t)kMaxMerge && !ctx->call.truncated && !ctx->call.floored && !ctx->call.typical && !ctx->call.constrained;  // (truncated, floored, typical, constrained: batch by batch)
   if (mergeable)
     RCCHK(build_merge_plan(ctx, batches, n_batches, S, Tmax, limit_factor, steps_hint, nullptr, mp, rows, kMergeTile));
   for (size_t j = 0; mergeable && j < n_batches; ++j) mp.opt[j] = opt.user[j];  // (device memory: addressed where it is)
@@ -4122,7 +4224,7 @@ extern "C" int slimt_hip_translate_many_async(slimt_hip_ctx *ctx, const slimt_hi
   const slimt_hip_model *m = ctx->model;
   HIPCHK(hipSetDevice(m->device));
   const size_t Tmax = std::max<size_t>(1, (size_t)(limit_factor * (float)S));
-  bool merged = n_batches > 1 && n_batches <= (size_t)kMaxMerge && S <= ctx->max_S && !ctx->call.truncated && !ctx->call.floored && !ctx->call.constrained;
+  bool merged = n_batches > 1 && n_batches <= (size_t)kMaxMerge && S <= ctx->max_S && !ctx->call.truncated && !ctx->call.floored && !ctx->call.typical && !ctx->call.constrained;
   slimt_hip_batch dev[kMaxMerge];
   MergePlan mp;  // (its opt[j].scores: the device views of the pinned score arrays)
   bool any_align = false;
@@ -4560,7 +4662,7 @@ int translate_many_generated(slimt_hip_ctx *ctx, slimt_hip_shortlist *sl, const 
     any_align = any_align || dev[j].align != nullptr;
   }
   const bool fold = env().shortlist_fold;
-  const bool merged = n > 1 && n <= (size_t)kMaxMerge && !ctx->call.truncated && !ctx->call.floored && !ctx->call.constrained && S <= ctx->max_S && rows <= ctx->max_B && rows * S <= ctx->max_M &&
+  const bool merged = n > 1 && n <= (size_t)kMaxMerge && !ctx->call.truncated && !ctx->call.floored && !ctx->call.typical && !ctx->call.constrained && S <= ctx->max_S && rows <= ctx->max_B && rows * S <= ctx->max_M &&
                       merge_supported(ctx, rows, S) && fold &&
                       shortlist_in_launch_lds_bytes((int)sl->source_vocab, (int)sl->target_vocab) <= 64 * 1024;
   if (!merged && o.host_batches) {

@@ -65,7 +65,7 @@ struct BatchOptions {
 
 // What the slimt_hip_ctx_set_* functions armed for the next translate call. A vector's size is the number of batches it was
 // armed for (0: not armed); truncation is armed by a top_k or top_p that truncates, the floor by a min_p or epsilon above 0,
-// consensus by an order above 0.
+// typical sampling by a mass below 1, consensus by an order above 0.
 struct ArmedOptions {
   std::vector<float *> scores;
   std::vector<const uint32_t *> prefix_ids, prefix_len;
@@ -74,6 +74,7 @@ struct ArmedOptions {
   uint32_t top_k = 0;
   float top_p = 1.0f;
   float min_p = 0.0f, epsilon = 0.0f;  // the sampling floor (slimt_hip_ctx_set_sampling_floor): armed by either above 0
+  float typical_mass = 1.0f;           // locally typical sampling (slimt_hip_ctx_set_sampling_typical): armed below 1
   StepConstraints cn;                  // step constraints (slimt_hip_ctx_set_step_constraints): armed by cn_armed (constraints.h)
   int cs_order = 0, cs_beta2 = 0;
   bool cs_units = false;  // the selection over unit rows (slimt_hip_ctx_set_fanout_consensus_units): same slot, last arming wins
@@ -90,6 +91,7 @@ struct CallState {
   bool scored = false, forced = false, sampled = false;
   bool truncated = false;  // sampled, to the top_k largest and the nucleus of mass top_p: per-stage decoder, never merged
   bool floored = false;    // sampled, above the min-p / epsilon floor (floor.h): per-stage decoder, never merged, like a truncated call
+  bool typical = false;    // sampled, to the locally typical set of mass typical_mass (typical.h): per-stage decoder, never merged
   bool fanout = false;     // `rows` decoder rows over the B sources: per-stage decoder, never merged, like a truncated call
   bool constrained = false;  // greedy or sampled, under step constraints (constraints.h): per-stage decoder, never merged
   StepConstraints cn;
@@ -98,6 +100,7 @@ struct CallState {
   uint32_t top_k = 0;
   float top_p = 1.0f;
   float min_p = 0.0f, epsilon = 0.0f;
+  float typical_mass = 1.0f;
   int cs_order = 0, cs_beta2 = 0;
   bool cs_units = false;  // ... over the rows' unit rows through the model's unit table (consensus_units.hip)
   int rows = 0;                       // fan-out: N <= max_B (the per-row decoder workspaces are sized by max_B)

@@ -894,6 +894,30 @@ struct SampleFloorArgs {
 constexpr int kFloorResidentN = 4096;  // the widest row a workgroup holds in registers (256 threads x 16 columns)
 hipError_t launch_sample_floor(const SampleFloorArgs &a, hipStream_t st);
 
+// ---- locally typical sampling: the selection over stored logits (sample_typical.hip) ---------------------------------------
+// The same step with the kept set of slimt_hip_ctx_set_sampling_typical (typical.h): the same partial per row, from one read
+// of the row where N <= kTypicalResidentN and from one per phase above it. N <= kTypicalMaxN (typical.h). A row with
+// fcol[b] >= 0 keeps every valid column.
+struct SampleTypicalArgs {
+  const float *logits = nullptr;  // [B][N]
+  int B = 0, N = 0;
+  float inv_T = 0.0f;
+  float mass = 1.0f;                    // in (0, 1]
+  const uint32_t *seeds = nullptr;      // [2][B] the rows' hash words of this step (SampledStep::seeds)
+  const uint32_t *shortlist = nullptr;  // [N] the columns' vocabulary ids (nullptr: the column)
+  const int *fcol = nullptr;            // nullable [B]
+  float *part_val = nullptr;            // [B] best key over the kept set (-FLT_MAX: none)
+  int *part_idx = nullptr;              // [B] ... its column (0x7fffffff: none)
+  float *part_sum = nullptr;            // [B] sum of exp(z - M) over the kept set; NaN where the row holds a NaN
+  float *part_mz = nullptr;             // [B] M, the maximum valid z
+  float *part_zw = nullptr;             // [B] z of the best key's column
+  float *part_y = nullptr;              // nullable [B] z at fcol[b], -inf where there is none
+  uint32_t *kept = nullptr;             // nullable [B] the size of the kept set
+  uint32_t *mean_gap = nullptr;         // nullable [B] Ebar (0 where the row is not cut)
+};
+constexpr int kTypicalResidentN = 4096;  // the widest row a workgroup holds in registers (256 threads x 16 columns)
+hipError_t launch_sample_typical(const SampleTypicalArgs &a, hipStream_t st);
+
 // ---- step constraints: a selection over stored logits that reads the row's history too (step_constrain.hip) --------------
 // One step of B rows whose logits [B][N] are in memory, under the setting of slimt_hip_ctx_set_step_constraints
 // (constraints.h): row b's history is history[b][0 .. min(hist_len[b], ld_hist)). seeds == nullptr is a greedy step, whose

@@ -304,12 +304,13 @@ class Service:
         res.close()
         return out
 
-    def _floored_samples(self, model: Model, per_request: List[List[List[int]]], samples: int, sampling, floor, constraints=None):
+    def _floored_samples(self, model: Model, per_request: List[List[List[int]]], samples: int, sampling, floor, constraints=None, typical=None):
         """_translate_samples under a min-p / epsilon floor (capi.Context.set_sampling_floor): the same lists and the same
         keys, drawn by fan-out calls (`samples` decoder rows per segment, one encoding of it) on the Service's capi.Context
         for the model, under the Service's lock, batched as _beam_ranked batches. The C++ service is not involved.
         constraints: a dict of capi.Context.set_step_constraints' keywords for those calls (floor None then); with
-        sampling None the rows are greedy (samples = 1)."""
+        sampling None the rows are greedy (samples = 1). typical: the mass of locally typical sampling
+        (capi.Context.set_sampling_typical) for those calls (floor and constraints None then)."""
         n = int(samples)
         units = [_Unit(r, i, list(seg)) for r, segs in enumerate(per_request) for i, seg in enumerate(segs)]
         if any(len(u.words) > self.ENGINE_LIMIT for u in units):
@@ -346,7 +347,7 @@ class Service:
                                                               self.limit_factor, eos, want_align=True,
                                                               generator=model.shortlist_generator, scores=True,
                                                               sampling=(float(sampling[0]), keys) if sampling is not None else None,
-                                                              floor=floor, constraints=constraints)
+                                                              floor=floor, constraints=constraints, typical=typical)
                 for b, u in enumerate(batch):
                     for j in range(n):
                         c, L = b * n + j, int(lens[b])
@@ -618,17 +619,21 @@ class Service:
         return out
 
     def sample_and_rerank(self, model: Model, sources: Sequence[str], n: int, sampling, truncation=None, mean: bool = False,
-                          floor=None):
+                          floor=None, typical=None):
         """translate(samples=n) followed by rerank() of each source's n samples: draws n translations of every source from
         one encoding of it, then scores them teacher-forced from one encoding again (greedy log-probabilities: the model's
         own, not the draws' at the sampling temperature). sources: each ONE sentence, as for rerank(). Returns (responses,
         ranked): translate()'s Responses with their `samples`, and rerank()'s list over the samples' target texts.
-        floor: (min_p, epsilon) -- the samples are drawn above that floor (_floored_samples), not with truncation."""
-        if floor is not None:
+        floor: (min_p, epsilon) -- the samples are drawn above that floor (_floored_samples), not with truncation.
+        typical: a mass in (0, 1] -- the samples are drawn from each step's locally typical set of that mass
+        (capi.Context.set_sampling_typical), by the same calls; not with truncation or floor."""
+        if typical is not None and floor is not None:
+            raise ValueError("sample_and_rerank: typical is not combined with floor")
+        if floor is not None or typical is not None:
             if truncation is not None or sampling is None:
-                raise ValueError("sample_and_rerank: floor takes sampling=(temperature, seed) and no truncation")
+                raise ValueError("sample_and_rerank: floor and typical take sampling=(temperature, seed) and no truncation")
             processed = model.processor.process_many(sources, self.wrap_length, self.workers)
-            drawn = self._floored_samples(model, [segs for _, segs in processed], n, sampling, floor)
+            drawn = self._floored_samples(model, [segs for _, segs in processed], n, sampling, floor, typical=typical)
             texts = [src for src, _ in processed]
             alts = [self._respond_many(model, texts, h) for h in drawn]
             responses = alts[0]
@@ -642,7 +647,7 @@ class Service:
 
     def sample_and_select(self, model: Model, sources: Sequence[str], n: int, sampling, truncation=None,
                           max_order: Optional[int] = None, beta2: int = 4, encoding: Encoding = Encoding.UTF8,
-                          utility: str = "tokens", without_replacement: bool = False, floor=None, constraints=None) -> List[Response]:
+                          utility: str = "tokens", without_replacement: bool = False, floor=None, constraints=None, typical=None) -> List[Response]:
         """translate(samples=n) followed by the consensus (minimum-Bayes-risk) pick: of the n draws of every sentence, the one
         that agrees most with the others -- the mean token n-gram F (orders 1..max_order, integer beta2 = beta^2; 4 is chrF's)
         against the sentence's other draws (include/slimt_hip.h, slimt_hip_consensus_select). The pick is made on the device
@@ -663,7 +668,12 @@ class Service:
         translate(samples=n), and the pick of either utility runs in a call of its own over the returned rows. Not with
         truncation, and not without replacement.
         constraints: a dict of capi.Context.set_step_constraints' keywords -- the draws are made under those step constraints,
-        by the same fan-out calls as with floor=; not with floor, truncation or without replacement."""
+        by the same fan-out calls as with floor=; not with floor, truncation or without replacement.
+        typical: a mass in (0, 1] -- the draws come from each step's locally typical set of that mass
+        (capi.Context.set_sampling_typical: the tokens whose surprisal is closest to the step's entropy), by the same fan-out
+        calls as with floor=; not with truncation, floor, constraints or without replacement."""
+        if typical is not None and (truncation is not None or floor is not None or constraints is not None or without_replacement):
+            raise ValueError("sample_and_select: typical is not combined with truncation, floor, constraints or without_replacement")
         if floor is not None and (truncation is not None or without_replacement):
             raise ValueError("sample_and_select: floor is not combined with truncation or without_replacement")
         if constraints is not None and (floor is not None or truncation is not None or without_replacement):
@@ -683,12 +693,13 @@ class Service:
             raise ValueError(f"samples: a segment has more than {self.ENGINE_LIMIT} tokens")
         histories = [[None] * len(segs) for segs in per_request]
         picked = [([0.0] * len(segs), [0] * len(segs)) for segs in per_request]
-        if flat and (utility == "chrf" or floor is not None or constraints is not None):
+        stepwise = floor is not None or constraints is not None or typical is not None  # (drawn on the Service's capi.Context)
+        if flat and (utility == "chrf" or stepwise):
             n = int(n)
             if n > capi.CONSENSUS_MAX_ROWS:
                 raise ValueError(f"sample_and_select: at most {capi.CONSENSUS_MAX_ROWS} samples, not {n}")
-            if floor is not None or constraints is not None:
-                drawn = self._floored_samples(model, per_request, n, sampling, floor, constraints)  # [sample][request][segment]
+            if stepwise:
+                drawn = self._floored_samples(model, per_request, n, sampling, floor, constraints, typical)  # [sample][request][segment]
             else:
                 drawn = self._translate_samples(model, per_request, n, sampling, truncation)
             where = [(r, i) for r, segs in enumerate(per_request) for i in range(len(segs))]
