@@ -1172,6 +1172,39 @@ int slimt_hip_beam_step_sampled(const float *logits, size_t B, int beam, size_t 
                                 uint32_t eos_id, uint32_t *parent, uint32_t *token, float *token_score, float *totals_out,
                                 float *perturbed_out, uint32_t *flags_out);
 
+/* ---- beam search under step constraints (n-gram blocking, penalty, minimum length, suppressed ids) ---- */
+#define SLIMT_HIP_BEAM_CONSTRAINT_MAX_COLUMNS 65536
+#define SLIMT_HIP_BEAM_CONSTRAINT_MAX_HISTORY 512
+/* Arms the NEXT beam call (slimt_hip_translate_beam*) with the setting of slimt_hip_ctx_set_step_constraints, validated
+ * alike; NULL or all-off values disarm. THE CONTRACT: a constrained beam step is the plain beam step above over the rows
+ * z'. A live slot at step t has the history h[0 .. t): the tokens along its parents (beam calls have no forced prefix).
+ * Its banned and seen sets and the id -> column map are those of step constraints (slimt_amd/csrc/constraints.h, rules 1
+ * to 3); z_c = l_c > 0 ? l_c * inv_theta : l_c * theta on a seen column and l_c elsewhere (rule 4); the slot's bans are
+ * lifted for the step when no valid (non-NaN z) column is unbanned while a valid column exists, the penalty stays
+ * (rule 5); and z'_c = -inf where c is banned and the bans are not lifted, z_c otherwise. Everything else is the beam's
+ * contract, not redefined: a NaN in z' makes the row unusable; M, the weights, Q and L run over z', so the scores are
+ * log-softmax over the candidates; a penalised logit that overflows makes the row unusable like any infinite maximum; the
+ * tie order's logit is z'; finished slots are carried unconstrained; beam 1 picks the constrained greedy call's tokens.
+ * Each slot has its own sets: two slots of one source generally ban different columns.
+ * The option is consumed by the next translate entry point whatever its outcome; one that is not a beam call fails with
+ * a message. Also refused with a message: together with slimt_hip_ctx_set_beam_sampling; an output layer of more than
+ * SLIMT_HIP_BEAM_CONSTRAINT_MAX_COLUMNS columns; Tmax above SLIMT_HIP_BEAM_CONSTRAINT_MAX_HISTORY. A beam call keeps
+ * refusing what it refuses un-armed -- slimt_hip_ctx_set_step_constraints included, which stays the greedy and sampled
+ * calls' option. Execution: slimt_amd/csrc/beam_constrained.hip's selection in the place of the plain one, still one
+ * launch per step; the slots' histories are rows of a double-buffered block gathered by parent in the same launch. */
+int slimt_hip_ctx_set_beam_constraints(slimt_hip_ctx *ctx, const slimt_hip_step_constraints *constraints);
+/* slimt_hip_beam_step with the selection above: history [B beam][Th] (Th in 1 .. SLIMT_HIP_BEAM_CONSTRAINT_MAX_HISTORY),
+ * step = the live slots' history length (at most Th), the setting, N at most SLIMT_HIP_BEAM_CONSTRAINT_MAX_COLUMNS; ids
+ * must ascend. history_out (nullable) [B beam][Th]: a new slot's row is its parent's row and then its token; a carried
+ * finished slot's row is copied whole; everything else is 0. n_banned (nullable) [B beam]: a live slot's banned columns,
+ * with SLIMT_HIP_CONSTRAINT_FALLBACK set where the slot lifted its bans; 0 for a slot that is not live. Host pointers,
+ * stateless, waits. */
+int slimt_hip_beam_step_constrained(const float *logits, size_t B, int beam, size_t N, const uint32_t *ids, const uint32_t *history,
+                                    size_t Th, uint32_t step, const slimt_hip_step_constraints *constraints, const float *totals_in,
+                                    const uint32_t *flags_in, uint32_t eos_id, uint32_t *parent, uint32_t *token,
+                                    float *token_score, float *totals_out, uint32_t *flags_out, uint32_t *history_out,
+                                    uint32_t *n_banned);
+
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, HIP events bracket every launch of kernel family `kernel_id`
  * on the ctx stream; slimt_hip_profile_read returns the number of launches

@@ -59,6 +59,7 @@ SYMBOLS = [
     "slimt_hip_translate_beam", "slimt_hip_translate_beam_async", "slimt_hip_translate_beam_device",
     "slimt_hip_translate_beam_async_generated", "slimt_hip_beam_step",
     "slimt_hip_ctx_set_beam_sampling", "slimt_hip_beam_step_sampled",
+    "slimt_hip_ctx_set_beam_constraints", "slimt_hip_beam_step_constrained",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -321,6 +322,8 @@ def lib():
     L.slimt_hip_beam_step.argtypes = [vp, sz, i32, sz, vp, vp, vp, u32, vp, vp, vp, vp, vp]
     L.slimt_hip_ctx_set_beam_sampling.argtypes = [vp, vp, sz, vp]
     L.slimt_hip_beam_step_sampled.argtypes = [vp, sz, i32, sz, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.slimt_hip_ctx_set_beam_constraints.argtypes = [vp, vp]
+    L.slimt_hip_beam_step_constrained.argtypes = [vp, sz, i32, sz, vp, vp, sz, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("slimt_hip_abi_version",):
@@ -483,6 +486,36 @@ def beam_step_sampled(logits, totals, perturbed, flags, beam: int, keys=None, st
                                            _p(flags), int(eos_id), _p(parent), _p(token), _p(score), _p(totals_out),
                                            _p(perturbed_out), _p(flags_out)))
     return parent, token, score, totals_out, perturbed_out, flags_out
+
+
+BEAM_CONSTRAINT_MAX_COLUMNS, BEAM_CONSTRAINT_MAX_HISTORY = 65536, 512  # (include/slimt_hip.h)
+
+
+def beam_step_constrained(logits, totals, flags, beam: int, history, step: int, constraints, eos_id: int = 0, ids=None):
+    """slimt_hip_beam_step_constrained: beam_step() over the rows z' -- history [B * beam, Th] uint32 (a live slot's first
+    `step` entries are its tokens), constraints: the keywords of Context.set_beam_constraints, as a dict; ids must ascend.
+    Returns (parent, token, token_score, totals, flags, history_out [B * beam, Th], banned columns uint32 [B * beam],
+    fallback bool [B * beam]: the slot lifted its bans)."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    totals = np.ascontiguousarray(totals, dtype=np.float32)
+    flags = np.ascontiguousarray(flags, dtype=np.uint32)
+    history = np.ascontiguousarray(history, dtype=np.uint32)
+    beam = int(beam)
+    if logits.ndim != 2 or beam < 1 or logits.shape[0] % beam or totals.shape != (logits.shape[0],) or flags.shape != totals.shape:
+        raise ValueError("beam_step_constrained: logits [B * beam, N], totals [B * beam] and flags [B * beam] expected")
+    R, N = logits.shape
+    ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32)
+    if (ids is not None and ids.shape != (N,)) or history.ndim != 2 or history.shape[0] != R:
+        raise ValueError("beam_step_constrained: ids [N] and history [B * beam, Th] expected")
+    cn, keep = _step_constraints(**constraints)
+    parent, token, flags_out, nb = (np.zeros(R, np.uint32) for _ in range(4))
+    score, totals_out, hist_out = np.zeros(R, np.float32), np.zeros(R, np.float32), np.zeros_like(history)
+    _chk(lib().slimt_hip_beam_step_constrained(_p(logits), R // beam, beam, N, _p(ids), _p(history), history.shape[1], int(step),
+                                               C.addressof(cn), _p(totals), _p(flags), int(eos_id), _p(parent), _p(token),
+                                               _p(score), _p(totals_out), _p(flags_out), _p(hist_out), _p(nb)))
+    del keep
+    return (parent, token, score, totals_out, flags_out, hist_out, nb & np.uint32(CONSTRAINT_FALLBACK - 1),
+            (nb & np.uint32(CONSTRAINT_FALLBACK)) != 0)
 
 
 def candidates_rank(scores, tgt_len, cand_src, B: int, mean: bool = False, mode=None):
@@ -1353,6 +1386,14 @@ class Context:
         self._beam_sampling_keep = keep
         _chk(lib().slimt_hip_ctx_set_beam_sampling(self.h, C.c_void_p(addr[0] or None), int(n), C.c_void_p(addr[1] or None)))
 
+    def set_beam_constraints(self, no_repeat_ngram: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress=()):
+        """slimt_hip_ctx_set_beam_constraints: set_step_constraints' setting for the NEXT beam call, each slot constrained by
+        the tokens along its own parents. All off disarms. Not combined with set_beam_sampling. translate_beam() takes
+        `constraints=` (a dict of these keywords) and does this."""
+        cn, keep = _step_constraints(no_repeat_ngram, repetition_penalty, min_length, suppress)
+        _chk(lib().slimt_hip_ctx_set_beam_constraints(self.h, C.addressof(cn)))
+        del keep
+
     def _arm_beam_sampling(self, sampling_keys, perturbed, B: int, k: int):
         """arms a host beam call's sampling_keys= (True: the default keys; or uint64 [B]) and perturbed= (True: a new
         array; or float32 [B, beam]); returns the perturbed array or None"""
@@ -1375,12 +1416,13 @@ class Context:
 
     def translate_beam(self, ids, lengths, beam: int, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
                        mean: bool = False, want_align: bool = False, want_scores: bool = True, mode=None,
-                       sampling_keys=None, perturbed=None):
+                       sampling_keys=None, perturbed=None, constraints=None):
         """slimt_hip_translate_beam: beam search over the B sources ids [B,S] / lengths [B] with `beam` slots each. Returns
         the n-best, best first: out_ids [B,beam,Tmax], out_len [B,beam] (0: a dead slot), totals [B,beam] (-inf: a dead
         slot), token_scores [B,beam,Tmax] | None, align [B,beam,Tmax,S] | None. mean: order by totals / out_len.
         sampling_keys (uint64 [B], or True for the default keys): the hypotheses are sampled without replacement
-        (slimt_hip_ctx_set_beam_sampling) and a sixth array follows, perturbed [B,beam] (the one given, or a new one)."""
+        (slimt_hip_ctx_set_beam_sampling) and a sixth array follows, perturbed [B,beam] (the one given, or a new one).
+        constraints: a dict of set_beam_constraints' keywords (slimt_hip_ctx_set_beam_constraints)."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
         if ids.ndim != 2 or lengths.shape != (ids.shape[0],):
@@ -1397,6 +1439,8 @@ class Context:
         align = np.zeros((B, kk, T, S), dtype=np.float32) if want_align else None
         if sampling_keys is not None:
             perturbed = self._arm_beam_sampling(sampling_keys, True if perturbed is None else perturbed, B, kk)
+        if constraints is not None:
+            self.set_beam_constraints(**constraints)
         _chk(lib().slimt_hip_translate_beam(self.h, _p(ids), _p(lengths), B, S, k, self._beam_mode(mean, mode), _p(sl),
                                             0 if sl is None else sl.size, limit_factor, eos_id, _p(out_ids), _p(out_len),
                                             _p(totals), _p(sc), _p(align)))

@@ -1505,7 +1505,7 @@ void ctx_free(slimt_hip_ctx *c) {
                     &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->tr_logits, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag,
-                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage, &c->cs_stage, &c->cu_ws, &c->bm_state, &c->bm_slots, &c->bm_hist, &c->bm_align, &c->bm_stage, &c->bm_sampled};
+                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage, &c->cs_stage, &c->cu_ws, &c->bm_state, &c->bm_slots, &c->bm_hist, &c->bm_align, &c->bm_stage, &c->bm_sampled, &c->bm_chist};
   for (auto *b : bufs) b->release();
   free_affine(c->out_sl);
   if (c->n_finished_host) (void)hipHostFree(c->n_finished_host);
@@ -1831,6 +1831,15 @@ extern "C" int slimt_hip_ctx_set_beam_sampling(slimt_hip_ctx *ctx, const uint64_
   return 0;
 }
 
+extern "C" int slimt_hip_ctx_set_beam_constraints(slimt_hip_ctx *ctx, const slimt_hip_step_constraints *constraints) {
+  // (the values first, like slimt_hip_ctx_set_step_constraints)
+  slimt_hip::StepConstraints cn;
+  RCCHK(step_constraints_from(constraints, cn));
+  if (!ctx) return fail(-1, "null argument");
+  ctx->armed.bc = cn;  // (all off: nothing armed)
+  return 0;
+}
+
 extern "C" int slimt_hip_ctx_set_score_alternatives(slimt_hip_ctx *ctx, uint32_t k, uint32_t *alt_ids, float *alt_scores,
                                                     uint32_t *rank) {
   // (the value first, like the temperature)
@@ -2050,8 +2059,9 @@ struct MergePlan {
 // ctx->call, the record every inner function reads; `user` holds the per-batch arrays as the caller gave them, one entry per
 // batch, for the entry point to hand on: as they are where they are device memory (options_in_place), through
 // stage_options where they are host memory. The checks run scores -> prefix -> sampling -> truncation -> floor -> typical -> step constraints -> consensus -> beam
-// sampling and the first refusal is the call's (rc); a truncated call must be sampled, so the truncation is looked at behind
-// the sampling. Beam sampling (slimt_hip_ctx_set_beam_sampling) is for the beam entry points (beam) only.
+// sampling -> beam constraints and the first refusal is the call's (rc); a truncated call must be sampled, so the truncation is looked at behind
+// the sampling. Beam sampling (slimt_hip_ctx_set_beam_sampling) and beam constraints (slimt_hip_ctx_set_beam_constraints) are
+// for the beam entry points (beam) only, and not combined with each other.
 // While call.truncated, call.floored, call.typical, call.constrained or call.fanout is set fused_decoder_allowed() is false: the call decodes with the per-stage kernels
 // and is never merged; the context's decode mode is not touched and still chooses the encoder. Consensus is for the
 // fan-out entry points (fanout) only: any other call that finds it armed is refused. The destructor empties ctx->call.
@@ -2179,6 +2189,13 @@ struct CallOptions {
       call.sb_n = a.sb_n;  // (checked against the call's sources by open_beam)
       call.sb_keys = a.sb_keys;
       call.sb_perturbed = a.sb_perturbed;
+    }
+    if (cn_armed(a.bc)) {
+      if (!beam) return fail(-1, "beam constraints: armed on a translate call that is not a beam call (slimt_hip_translate_beam*)");
+      if (a.sb_n)
+        return fail(-1, "beam constraints: beam sampling is armed too (slimt_hip_ctx_set_beam_sampling); constrained sampled beams are not supported");
+      call.bm_constrained = true;
+      call.bc = a.bc;
     }
     return 0;
   }
@@ -2719,7 +2736,28 @@ int beam_steps(slimt_hip_ctx *c, size_t B, size_t S, size_t Tmax, uint32_t eos_i
     ss.keys = call.sb_dev_keys;
     ss.perturbed_in = ss.perturbed_out = c->bm_sampled.as<float>();
   }
+  // under step constraints (slimt_hip_ctx_set_beam_constraints): beam_constrained.hip's selection, which also moves the slots'
+  // history rows from one block of bm_chist into the other; the start state is the plain kernel's (the histories are empty)
+  const bool constrained = call.bm_constrained;
+  BeamConstrainedArgs cs;
+  if (constrained) {
+    if (out.w.N > kBeamConstrainedMaxN || T > (size_t)kBeamConstrainedMaxHistory)
+      return fail(-1, "beam constraints: %zu steps or an output layer of %d columns exceeds the bounds of %d tokens and %d columns", T,
+                  out.w.N, kBeamConstrainedMaxHistory, kBeamConstrainedMaxN);
+    // (reserved by the first constrained beam call, like the blocks above, and sized by max_batch once: a context that
+    // makes no such call allocates what it always did)
+    HIPCHK(c->bm_chist.reserve(2 * c->max_B * (size_t)kBeamConstrainedMaxHistory * 4));
+    cs.Th = kBeamConstrainedMaxHistory;
+    cs.c = call.bc;
+  }
+  uint32_t *const hist_blocks[2] = {c->bm_chist.as<uint32_t>(), c->bm_chist.as<uint32_t>() + c->max_B * (size_t)kBeamConstrainedMaxHistory};
   auto select = [&](const BeamSelectArgs &step) {
+    if (constrained && !step.init) {
+      cs.step = step;
+      cs.hist_src = hist_blocks[step.t & 1];
+      cs.hist_dst = hist_blocks[(step.t + 1) & 1];
+      return launch_beam_constrained(cs, st);
+    }
     if (!sampled) return launch_beam_select(step, st);
     ss.step = step;
     return launch_beam_select_sampled(ss, st);
@@ -3453,6 +3491,9 @@ int translate_device(slimt_hip_ctx *c, const uint32_t *d_ids, const uint32_t *d_
   }
   if (call.constrained && Tmax > (size_t)kConstraintMaxHistory)  // (before anything is queued; the kernel's launcher guards its bound too)
     return fail(-1, "step constraints: Tmax %zu exceeds the history bound %d", Tmax, kConstraintMaxHistory);
+  if (call.bm_constrained && (Tmax > (size_t)kBeamConstrainedMaxHistory || (n_sl ? n_sl : (size_t)m->V) > (size_t)kBeamConstrainedMaxN))
+    return fail(-1, "beam constraints: Tmax %zu or an output layer of %zu columns exceeds the bounds of %d tokens and %d columns", Tmax,
+                n_sl ? n_sl : (size_t)m->V, kBeamConstrainedMaxHistory, kBeamConstrainedMaxN);
   // The K/V cache form (launch_choice.h, kv_cache_form): packed where the persistent pair has it for this shape and S.
   KvFormIn form;
   form.D = m->D; form.F = m->F; form.H = m->H;
@@ -4067,6 +4108,79 @@ extern "C" int slimt_hip_beam_step_sampled(const float *logits, size_t B, int be
   HIPCHK(hipMemcpyAsync(totals_out, o + 3 * R, R * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(flags_out, o + 4 * R, R * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(perturbed_out, o + 5 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// slimt_hip_beam_step over the rows z' (beam_constrained.hip): the slots' history rows, the step and the setting beside it.
+extern "C" int slimt_hip_beam_step_constrained(const float *logits, size_t B, int beam, size_t N, const uint32_t *ids,
+                                               const uint32_t *history, size_t Th, uint32_t step,
+                                               const slimt_hip_step_constraints *constraints, const float *totals_in,
+                                               const uint32_t *flags_in, uint32_t eos_id, uint32_t *parent, uint32_t *token,
+                                               float *token_score, float *totals_out, uint32_t *flags_out, uint32_t *history_out,
+                                               uint32_t *n_banned) {
+  RCCHK(beam_arguments(beam, 0));
+  slimt_hip::StepConstraints cn;
+  RCCHK(step_constraints_from(constraints, cn));
+  if (!logits || !history || !totals_in || !flags_in || !parent || !token || !token_score || !totals_out || !flags_out || !B || !N)
+    return fail(-1, "bad argument");
+  if (N > (size_t)slimt_hip::kBeamConstrainedMaxN || Th < 1 || Th > (size_t)slimt_hip::kBeamConstrainedMaxHistory)
+    return fail(-1, "beam_step_constrained: %zu columns or a history row of %zu tokens is not in 1..%d columns and 1..%d tokens", N, Th,
+                slimt_hip::kBeamConstrainedMaxN, slimt_hip::kBeamConstrainedMaxHistory);
+  if (step > Th) return fail(-1, "beam_step_constrained: step %u is above the history row's %zu tokens", step, Th);
+  const size_t R = B * (size_t)beam;
+  if (B > 0x7fffffffu / (size_t)beam) return fail(-1, "beam_step_constrained: more than %d rows", 0x7fffffff);
+  for (size_t r = 0; r < R; ++r) {
+    if (flags_in[r] > slimt_hip::kBeamFinished)
+      return fail(-1, "beam_step_constrained: flag %u of row %zu is not 0 (dead), 1 (live) or 2 (finished)", flags_in[r], r);
+    if (flags_in[r] == slimt_hip::kBeamLive && !std::isfinite(totals_in[r]))
+      return fail(-1, "beam_step_constrained: the total of live row %zu is not finite", r);
+    if (flags_in[r] == slimt_hip::kBeamFinished && totals_in[r] != totals_in[r])
+      return fail(-1, "beam_step_constrained: the total of finished row %zu is NaN", r);
+  }
+  Tmp3 t;
+  hipStream_t st = nullptr;
+  HIPCHK(t.a.reserve(R * N * 4));
+  HIPCHK(t.b.reserve(N * 4));
+  HIPCHK(t.c.reserve(2 * R * 4));
+  HIPCHK(t.d.reserve(6 * R * 4));
+  HIPCHK(t.e.reserve(2 * R * Th * 4));
+  HIPCHK(hipMemcpyAsync(t.a.p, logits, R * N * 4, hipMemcpyHostToDevice, st));
+  if (ids) HIPCHK(hipMemcpyAsync(t.b.p, ids, N * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.p, totals_in, R * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.as<char>() + R * 4, flags_in, R * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.e.p, history, R * Th * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(t.e.as<uint32_t>() + R * Th, 0, R * Th * 4, st));  // (what the step does not write reads 0)
+  BeamConstrainedArgs ca;
+  BeamSelectArgs &a = ca.step;
+  a.logits = t.a.as<float>();
+  a.B = (int)B;
+  a.k = beam;
+  a.N = (int)N;
+  a.ids = ids ? t.b.as<uint32_t>() : nullptr;
+  a.eos = eos_id;
+  a.t = (int)step;
+  a.totals_in = t.c.as<float>();
+  a.flags_in = t.c.as<uint32_t>() + R;
+  uint32_t *o = t.d.as<uint32_t>();
+  a.parent = o;
+  a.token = o + R;
+  a.token_score = reinterpret_cast<float *>(o + 2 * R);
+  a.totals_out = reinterpret_cast<float *>(o + 3 * R);
+  a.flags_out = o + 4 * R;
+  ca.n_banned = o + 5 * R;
+  ca.hist_src = t.e.as<uint32_t>();
+  ca.hist_dst = t.e.as<uint32_t>() + R * Th;
+  ca.Th = (int)Th;
+  ca.c = cn;
+  HIPCHK(launch_beam_constrained(ca, st));
+  HIPCHK(hipMemcpyAsync(parent, o, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(token, o + R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(token_score, o + 2 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(totals_out, o + 3 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(flags_out, o + 4 * R, R * 4, hipMemcpyDeviceToHost, st));
+  if (n_banned) HIPCHK(hipMemcpyAsync(n_banned, o + 5 * R, R * 4, hipMemcpyDeviceToHost, st));
+  if (history_out) HIPCHK(hipMemcpyAsync(history_out, ca.hist_dst, R * Th * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return 0;
 }

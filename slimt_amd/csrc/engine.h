@@ -84,6 +84,7 @@ struct ArmedOptions {
   size_t sb_n = 0;
   const uint64_t *sb_keys = nullptr;  // [sb_n], NULL: slimt_hip_sampling_key(0, b)
   float *sb_perturbed = nullptr;      // nullable [sb_n][beam]
+  StepConstraints bc;                 // constraints on a beam call (slimt_hip_ctx_set_beam_constraints): armed by cn_armed
 };
 
 // The translate call in progress: filled by its CallOptions (engine.cpp), reset as a whole when the entry point returns.
@@ -118,6 +119,9 @@ struct CallState {
   size_t sb_n = 0;  // the armed count of sources (0: not armed)
   const uint64_t *sb_keys = nullptr, *sb_dev_keys = nullptr;
   float *sb_perturbed = nullptr, *sb_dev_perturbed = nullptr;
+  // ... under step constraints (slimt_hip_ctx_set_beam_constraints; beam_constrained.hip's selection over the slots' history rows)
+  bool bm_constrained = false;
+  StepConstraints bc;
   BatchOptions dev;  // the current unmerged batch's options as the kernels address them (a merged launch: MergePlan::opt)
 };
 
@@ -285,6 +289,9 @@ struct slimt_hip_ctx {
   // ... sampled without replacement, reserved by the first armed beam call: the slots' perturbed values [rows], then the device
   // staging of a host call's perturbed values [rows] and of its pageable keys [B]
   slimt_hip::DevBuf bm_sampled;
+  // ... under step constraints: the slots' history rows [2][max_batch][kBeamConstrainedMaxHistory], reserved by the first armed
+  // beam call and sized by max_batch once; a step reads one block and writes the other, like the SSRU states
+  slimt_hip::DevBuf bm_chist;
   std::vector<uint32_t> bm_row_src;
   slimt_hip::DevBuf prev, out_ids, out_len, finished, n_finished, align;
   slimt_hip::DevBuf shortlist;

@@ -1014,6 +1014,29 @@ struct BeamSampledArgs {
 };
 hipError_t launch_beam_select_sampled(const BeamSampledArgs &a, hipStream_t st);
 
+// ---- beam search under step constraints: the selection over the rows z' (beam_constrained.hip) ---------------------------
+// `step` is launch_beam_select's step (never init: the start state is launch_beam_select's) over z': each live slot's logits
+// under the bans and the penalty of `c` (constraints.h), the slot's sets read from its own history row hist_src[r][0 .. t),
+// t = step.t (include/slimt_hip.h, slimt_hip_ctx_set_beam_constraints). hist_dst (nullable, another block than hist_src)
+// gets the new slots' rows: the parent's row and the token taken; a carried finished slot's row up to its length
+// (step.len_in; without lengths: the whole row) unchanged; a dead slot's row is not written. n_banned (nullable) [B k]: a live
+// slot's banned columns, | kConstraintFallback where the slot lifted its bans; 0 for a slot that is not live.
+// One 1024-thread workgroup per source, its 16 waves dealt to the slots; dynamic LDS beam_constrained_lds_bytes, hence
+// N <= kBeamConstrainedMaxN and Th <= kBeamConstrainedMaxHistory (k = 8: 128 KiB + 16 KiB of a CU's 160 KiB).
+constexpr int kBeamConstrainedMaxN = 1 << 16;
+constexpr int kBeamConstrainedMaxHistory = 512;
+constexpr int kBeamConstrainedResidentN = 4096;  // the widest row a slot's waves hold in registers (2 waves x 64 lanes x 32 columns)
+struct BeamConstrainedArgs {
+  BeamSelectArgs step;
+  const uint32_t *hist_src = nullptr;  // [B k][Th]
+  uint32_t *hist_dst = nullptr;
+  int Th = 0;
+  StepConstraints c;
+  uint32_t *n_banned = nullptr;
+};
+size_t beam_constrained_lds_bytes(int k, int N, int Th, bool penalised);
+hipError_t launch_beam_constrained(const BeamConstrainedArgs &a, hipStream_t st);
+
 // the column means (rounded) of an f32 K/V cache [Ld][K, V][B * S][D]: centre[(2 l + p) * D + d] (FusedDecodeArgs::kv_centre)
 hipError_t launch_kv_centres(const float *kv, int Ld, int B, int S, int D, unsigned long long *sums, int *centre, hipStream_t st);
 

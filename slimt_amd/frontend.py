@@ -777,7 +777,7 @@ class Service:
         return out
 
     def beam_search(self, model: Model, texts: Sequence[str], beam: int, mean: bool = False,
-                    encoding: Encoding = Encoding.UTF8, sample_seed: Optional[int] = None) -> List[Response]:
+                    encoding: Encoding = Encoding.UTF8, sample_seed: Optional[int] = None, constraints=None) -> List[Response]:
         """Beam search with n-best output (include/slimt_hip.h, slimt_hip_translate_beam): every sentence is decoded with
         `beam` = k slots (1..capi.MAX_BEAM) from one encoding of it and comes back as its k best hypotheses, ordered by their
         summed log-probability (mean=True: per token). Each Response carries `nbest`, its k alternatives as Responses
@@ -789,11 +789,16 @@ class Service:
         sample_seed: the k hypotheses of every sentence are SAMPLED WITHOUT REPLACEMENT from the model's distribution
         (stochastic beam search; slimt_hip_ctx_set_beam_sampling) -- k distinct translations, each with its exact
         log-probability, still ordered by it. Sentence i of the request (counted over all texts) is searched under
-        capi.sampling_key(sample_seed, i), wherever the batcher puts it."""
+        capi.sampling_key(sample_seed, i), wherever the batcher puts it.
+        constraints: a dict of translate(constraints=)'s keywords (no_repeat_ngram, repetition_penalty, min_length, suppress):
+        every slot is searched under those step constraints on the tokens along its own parents
+        (slimt_hip_ctx_set_beam_constraints). Not combined with sample_seed."""
+        if constraints is not None and sample_seed is not None:
+            raise ValueError("beam_search: constraints are not combined with sample_seed")
         k = int(beam)
         if k < 1 or k > capi.MAX_BEAM:
             raise ValueError(f"beam_search: a beam of 1..{capi.MAX_BEAM} expected, not {beam}")
-        processed, ranked, totals_of = self._beam_ranked(model, texts, k, mean, sample_seed)
+        processed, ranked, totals_of = self._beam_ranked(model, texts, k, mean, sample_seed, constraints)
         sources = [src for src, _ in processed]
         alts = [self._respond_many(model, sources, h) for h in ranked]
         out = alts[0]
@@ -805,7 +810,7 @@ class Service:
             resp.to(encoding)
         return out
 
-    def _beam_ranked(self, model: Model, texts: Sequence[str], k: int, mean: bool, sample_seed: Optional[int]):
+    def _beam_ranked(self, model: Model, texts: Sequence[str], k: int, mean: bool, sample_seed: Optional[int], constraints=None):
         """beam_search's calls: (the processed texts, ranked[j][request][segment] = rank j's (token ids, alignment, token
         scores), totals_of[j][request][segment])"""
         processed = model.processor.process_many(texts, self.wrap_length, self.workers)
@@ -840,6 +845,8 @@ class Service:
                     lens[b] = len(u.words)
                 if key_of:  # (armed for the next call, which is this batch's)
                     ctx.set_beam_sampling(np.array([key_of[u.request, u.index] for u in batch], np.uint64), B)
+                if constraints is not None:
+                    ctx.set_beam_constraints(**constraints)
                 if model.shortlist_generator is not None:
                     out, ln, tot, sc, al = ctx.translate_beam_generated(model.shortlist_generator, ids, lens, k, self.limit_factor,
                                                                         eos, mean, want_align=True)
