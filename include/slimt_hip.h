@@ -1205,6 +1205,38 @@ int slimt_hip_beam_step_constrained(const float *logits, size_t B, int beam, siz
                                     float *token_score, float *totals_out, uint32_t *flags_out, uint32_t *history_out,
                                     uint32_t *n_banned);
 
+/* ---- diverse beam search: groups of beams under a Hamming penalty (Vijayakumar et al. 2016) ---- */
+/* Arms the NEXT beam call (slimt_hip_translate_beam*) to search in `groups` = G groups; groups = 0 disarms. Refused at once:
+ * groups < 0 or above SLIMT_HIP_MAX_BEAM, a penalty that is not finite or not in 0 .. 1000 (so aug below stays finite when
+ * cand is). THE CONTRACT: everything of the beam's contract above holds word for word -- usable rows, M, the weights, Q, L,
+ * lp, flags, totals, EOS, Tmax, the outputs and their order; only this is new. With beam = k, G must divide k (1 <= G <= k)
+ * and g = k / G: group j owns the slots j g .. j g + g - 1. Before step 0 slot j g of every group is live with C = +0.0f
+ * and the others are dead. Group j's candidates come from its own slots only -- every live slot s with a usable row and
+ * every column c, cand = C_s + lp_c (-inf dropped), and every finished slot, itself -- so a parent never leaves its group.
+ * Within a step the groups select in ascending j. For group j and column c, n_c is the number of new slots of the groups
+ * 0 .. j - 1 at this step that were EXTENDED with column c (an extension into EOS counts; a carried finished slot and a dead
+ * slot count nothing). A carried slot has aug = C_s; an extension has aug = cand - penalty * (float)n_c (the product rounded
+ * to f32, then one f32 subtraction, not contracted; n_c = 0: cand itself). Group j's candidates are ordered by aug
+ * descending as floats, then slot ascending, then logit descending, then column ascending; the first g become its slots
+ * j g .. in that order, and with fewer than g candidates the rest are dead. A new slot's total is cand, NOT aug: totals stay
+ * the exact f32 sums of the token scores (token score = lp_c); the penalty steers the selection and enters no reported score.
+ * Special cases that follow: G = 1 is the plain beam step, bit for bit; penalty = 0 makes every group the plain beam of width
+ * g, so G = k gives k copies of greedy; at step 0 with G = k and a penalty larger than the row's logit spread the k groups take
+ * the row's k best columns in order. (k keys per slot suffice: at most k - g columns are penalised when a group selects, so
+ * a slot's g best by aug lie among its k best by plain order.)
+ * group_of (nullable) [B][beam]: the group of each hypothesis in the output's order -- its final slot / g --, 0xFFFFFFFF for a
+ * dead slot. Host calls write a host array (the _async calls until the context is synchronised), the _device call a device
+ * array. The option is consumed by the next translate entry point whatever its outcome; one that is not a beam call fails with
+ * a message. Also refused with a message: a beam that G does not divide; together with slimt_hip_ctx_set_beam_sampling or
+ * slimt_hip_ctx_set_beam_constraints. A beam call keeps refusing what it refuses un-armed. Execution:
+ * slimt_amd/csrc/beam_grouped.hip's selection in the place of the plain one, still one launch per step. */
+int slimt_hip_ctx_set_beam_groups(slimt_hip_ctx *ctx, int groups, float penalty, uint32_t *group_of);
+/* slimt_hip_beam_step with the selection above (1 <= groups <= beam, beam % groups == 0, penalty in 0 .. 1000). Host
+ * pointers, stateless, waits. */
+int slimt_hip_beam_step_grouped(const float *logits, size_t B, int beam, size_t N, const uint32_t *ids, int groups, float penalty,
+                                const float *totals_in, const uint32_t *flags_in, uint32_t eos_id, uint32_t *parent,
+                                uint32_t *token, float *token_score, float *totals_out, uint32_t *flags_out);
+
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, HIP events bracket every launch of kernel family `kernel_id`
  * on the ctx stream; slimt_hip_profile_read returns the number of launches

@@ -60,6 +60,7 @@ SYMBOLS = [
     "slimt_hip_translate_beam_async_generated", "slimt_hip_beam_step",
     "slimt_hip_ctx_set_beam_sampling", "slimt_hip_beam_step_sampled",
     "slimt_hip_ctx_set_beam_constraints", "slimt_hip_beam_step_constrained",
+    "slimt_hip_ctx_set_beam_groups", "slimt_hip_beam_step_grouped",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -324,6 +325,8 @@ def lib():
     L.slimt_hip_beam_step_sampled.argtypes = [vp, sz, i32, sz, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     L.slimt_hip_ctx_set_beam_constraints.argtypes = [vp, vp]
     L.slimt_hip_beam_step_constrained.argtypes = [vp, sz, i32, sz, vp, vp, sz, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    L.slimt_hip_ctx_set_beam_groups.argtypes = [vp, i32, f32, vp]
+    L.slimt_hip_beam_step_grouped.argtypes = [vp, sz, i32, sz, vp, i32, f32, vp, vp, u32, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("slimt_hip_abi_version",):
@@ -486,6 +489,26 @@ def beam_step_sampled(logits, totals, perturbed, flags, beam: int, keys=None, st
                                            _p(flags), int(eos_id), _p(parent), _p(token), _p(score), _p(totals_out),
                                            _p(perturbed_out), _p(flags_out)))
     return parent, token, score, totals_out, perturbed_out, flags_out
+
+
+def beam_step_grouped(logits, totals, flags, beam: int, groups: int, penalty: float, eos_id: int = 0, ids=None):
+    """slimt_hip_beam_step_grouped: beam_step() selected in `groups` groups of beam / groups slots under the Hamming
+    penalty (slimt_hip_ctx_set_beam_groups). Returns (parent, token, token_score, totals, flags), each [B * beam]."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    totals = np.ascontiguousarray(totals, dtype=np.float32)
+    flags = np.ascontiguousarray(flags, dtype=np.uint32)
+    beam = int(beam)
+    if logits.ndim != 2 or beam < 1 or logits.shape[0] % beam or totals.shape != (logits.shape[0],) or flags.shape != totals.shape:
+        raise ValueError("beam_step_grouped: logits [B * beam, N], totals [B * beam] and flags [B * beam] expected")
+    R, N = logits.shape
+    ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32)
+    if ids is not None and ids.shape != (N,):
+        raise ValueError("beam_step_grouped: ids [N] expected")
+    parent, token, flags_out = np.zeros(R, np.uint32), np.zeros(R, np.uint32), np.zeros(R, np.uint32)
+    score, totals_out = np.zeros(R, np.float32), np.zeros(R, np.float32)
+    _chk(lib().slimt_hip_beam_step_grouped(_p(logits), R // beam, beam, N, _p(ids), int(groups), float(penalty), _p(totals), _p(flags),
+                                           int(eos_id), _p(parent), _p(token), _p(score), _p(totals_out), _p(flags_out)))
+    return parent, token, score, totals_out, flags_out
 
 
 BEAM_CONSTRAINT_MAX_COLUMNS, BEAM_CONSTRAINT_MAX_HISTORY = 65536, 512  # (include/slimt_hip.h)
@@ -1394,6 +1417,21 @@ class Context:
         _chk(lib().slimt_hip_ctx_set_beam_constraints(self.h, C.addressof(cn)))
         del keep
 
+    def set_beam_groups(self, groups: int, penalty: float = 0.0, group_of=None):
+        """slimt_hip_ctx_set_beam_groups: the NEXT beam call searches in `groups` groups of beam / groups slots, a later group
+        pushed away from the tokens the earlier ones took at the same step by `penalty` (0..1000) per earlier pick. groups = 0
+        disarms. group_of: uint32 [B, beam] (a numpy array, kept alive here until the next arming, or an address) or None.
+        Not combined with set_beam_sampling or set_beam_constraints. translate_beam() takes `groups=(G, penalty)`."""
+        addr = 0
+        if isinstance(group_of, np.ndarray):
+            if group_of.dtype != np.uint32 or not group_of.flags.c_contiguous:
+                raise ValueError("beam groups: a C-contiguous uint32 group_of expected")
+            addr = group_of.ctypes.data
+        elif group_of:
+            addr = int(group_of)
+        self._beam_groups_keep = group_of
+        _chk(lib().slimt_hip_ctx_set_beam_groups(self.h, int(groups), float(penalty), C.c_void_p(addr or None)))
+
     def _arm_beam_sampling(self, sampling_keys, perturbed, B: int, k: int):
         """arms a host beam call's sampling_keys= (True: the default keys; or uint64 [B]) and perturbed= (True: a new
         array; or float32 [B, beam]); returns the perturbed array or None"""
@@ -1416,13 +1454,15 @@ class Context:
 
     def translate_beam(self, ids, lengths, beam: int, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
                        mean: bool = False, want_align: bool = False, want_scores: bool = True, mode=None,
-                       sampling_keys=None, perturbed=None, constraints=None):
+                       sampling_keys=None, perturbed=None, constraints=None, groups=None, want_groups: bool = False):
         """slimt_hip_translate_beam: beam search over the B sources ids [B,S] / lengths [B] with `beam` slots each. Returns
         the n-best, best first: out_ids [B,beam,Tmax], out_len [B,beam] (0: a dead slot), totals [B,beam] (-inf: a dead
         slot), token_scores [B,beam,Tmax] | None, align [B,beam,Tmax,S] | None. mean: order by totals / out_len.
         sampling_keys (uint64 [B], or True for the default keys): the hypotheses are sampled without replacement
         (slimt_hip_ctx_set_beam_sampling) and a sixth array follows, perturbed [B,beam] (the one given, or a new one).
-        constraints: a dict of set_beam_constraints' keywords (slimt_hip_ctx_set_beam_constraints)."""
+        constraints: a dict of set_beam_constraints' keywords (slimt_hip_ctx_set_beam_constraints).
+        groups: (G, penalty) -- diverse beam search in G groups (slimt_hip_ctx_set_beam_groups); with want_groups one more array
+        follows, group_of uint32 [B,beam] (0xFFFFFFFF: a dead slot)."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
         if ids.ndim != 2 or lengths.shape != (ids.shape[0],):
@@ -1441,11 +1481,19 @@ class Context:
             perturbed = self._arm_beam_sampling(sampling_keys, True if perturbed is None else perturbed, B, kk)
         if constraints is not None:
             self.set_beam_constraints(**constraints)
+        group_of = None
+        if groups is not None:
+            group_of = np.zeros((B, kk), np.uint32) if want_groups else None
+            self.set_beam_groups(int(groups[0]), float(groups[1]), group_of)
+        elif want_groups:
+            raise ValueError("translate_beam: want_groups needs groups=")
         _chk(lib().slimt_hip_translate_beam(self.h, _p(ids), _p(lengths), B, S, k, self._beam_mode(mean, mode), _p(sl),
                                             0 if sl is None else sl.size, limit_factor, eos_id, _p(out_ids), _p(out_len),
                                             _p(totals), _p(sc), _p(align)))
         if sampling_keys is not None:
             return out_ids, out_len, totals, sc, align, perturbed
+        if group_of is not None:
+            return out_ids, out_len, totals, sc, align, group_of
         return out_ids, out_len, totals, sc, align
 
     def beam_buffers(self, B: int, S: int, beam: int, limit_factor: float = 1.5, want_align: bool = False):

@@ -15,7 +15,8 @@
 // beam_finish_kernel: one workgroup per source behind the last step; the first k threads rank the slots by the final key, then a
 // wave per hypothesis walks its back-pointers from the last step to the first and writes token, score and alignment row
 // of every step at which the chain took a column (a carried finished slot records kBeamNone and only passes the walk on).
-// A sampled beam call (beam_sampled.hip) also hands it the slots' perturbed values, which leave in the same order.
+// A sampled beam call (beam_sampled.hip) also hands it the slots' perturbed values, which leave in the same order; a grouped
+// one (beam_grouped.hip) asks for each hypothesis's group.
 //
 // Every barrier is reached by every thread; no workgroup waits for another. No out-of-line device functions, no dynamic
 // stack: helpers are __forceinline__ (beam_tail.h holds those that beam_sampled.hip's selection shares).
@@ -189,6 +190,7 @@ __global__ __launch_bounds__(kBmThreads) void beam_finish_kernel(BeamFinishArgs 
       a.out_len[o] = al ? a.len[r0 + f] : 0u;
       a.out_totals[o] = al ? a.totals[r0 + f] : ninf;
       if (a.out_perturbed) a.out_perturbed[o] = al ? a.perturbed[r0 + f] : ninf;
+      if (a.out_group) a.out_group[o] = al ? (uint32_t)(f / a.group_size) : kBeamNone;
     }
     if (!al) continue;
     int cur = f;
@@ -240,6 +242,7 @@ hipError_t launch_beam_finish(const BeamFinishArgs &a, hipStream_t st) {
     return hipErrorInvalidValue;
   if (a.out_align && !a.align_hist) return hipErrorInvalidValue;
   if (a.out_perturbed && !a.perturbed) return hipErrorInvalidValue;
+  if (a.out_group && (a.group_size < 1 || a.k % a.group_size)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(beam_finish_kernel, dim3(a.B), dim3(kBmThreads), 0, st, a);
   return hipGetLastError();
 }

@@ -1505,7 +1505,7 @@ void ctx_free(slimt_hip_ctx *c) {
                     &c->state, &c->part_val, &c->part_idx, &c->part_sum, &c->sc_stage, &c->fp_stage, &c->fp_scratch, &c->fp_col, &c->fp_part_y, &c->sm_stage, &c->sm_seeds, &c->sm_part_mz, &c->sm_part_zw, &c->tr_logits, &c->prev, &c->out_ids, &c->out_len,
                     &c->finished, &c->n_finished, &c->align, &c->shortlist, &c->logits,
                     &c->attn_dbg, &c->stamps, &c->dbg_embed, &c->dbg_layers, &c->sl_scratch, &c->n_sl_dev, &c->gen_flag,
-                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage, &c->cs_stage, &c->cu_ws, &c->bm_state, &c->bm_slots, &c->bm_hist, &c->bm_align, &c->bm_stage, &c->bm_sampled, &c->bm_chist};
+                    &c->score_ws, &c->score_io, &c->alt_stage, &c->cand_align, &c->cand_rank, &c->fo_stage, &c->cs_stage, &c->cu_ws, &c->bm_state, &c->bm_slots, &c->bm_hist, &c->bm_align, &c->bm_stage, &c->bm_sampled, &c->bm_chist, &c->bm_groups};
   for (auto *b : bufs) b->release();
   free_affine(c->out_sl);
   if (c->n_finished_host) (void)hipHostFree(c->n_finished_host);
@@ -1840,6 +1840,18 @@ extern "C" int slimt_hip_ctx_set_beam_constraints(slimt_hip_ctx *ctx, const slim
   return 0;
 }
 
+extern "C" int slimt_hip_ctx_set_beam_groups(slimt_hip_ctx *ctx, int groups, float penalty, uint32_t *group_of) {
+  // (the values first, like the temperature)
+  if (groups < 0 || groups > SLIMT_HIP_MAX_BEAM) return fail(-1, "beam groups: %d groups are not in 0..%d", groups, SLIMT_HIP_MAX_BEAM);
+  if (!(penalty >= 0.0f && penalty <= slimt_hip::kBeamGroupedMaxPenalty))
+    return fail(-1, "beam groups: a penalty of %g is not in 0..%g", (double)penalty, (double)slimt_hip::kBeamGroupedMaxPenalty);
+  if (!ctx) return fail(-1, "null argument");
+  ctx->armed.bg_groups = groups;  // (0: nothing armed)
+  ctx->armed.bg_penalty = groups ? penalty : 0.0f;
+  ctx->armed.bg_group_of = groups ? group_of : nullptr;
+  return 0;
+}
+
 extern "C" int slimt_hip_ctx_set_score_alternatives(slimt_hip_ctx *ctx, uint32_t k, uint32_t *alt_ids, float *alt_scores,
                                                     uint32_t *rank) {
   // (the value first, like the temperature)
@@ -2059,9 +2071,10 @@ struct MergePlan {
 // ctx->call, the record every inner function reads; `user` holds the per-batch arrays as the caller gave them, one entry per
 // batch, for the entry point to hand on: as they are where they are device memory (options_in_place), through
 // stage_options where they are host memory. The checks run scores -> prefix -> sampling -> truncation -> floor -> typical -> step constraints -> consensus -> beam
-// sampling -> beam constraints and the first refusal is the call's (rc); a truncated call must be sampled, so the truncation is looked at behind
+// sampling -> beam constraints -> beam groups and the first refusal is the call's (rc); a truncated call must be sampled, so the truncation is looked at behind
 // the sampling. Beam sampling (slimt_hip_ctx_set_beam_sampling) and beam constraints (slimt_hip_ctx_set_beam_constraints) are
-// for the beam entry points (beam) only, and not combined with each other.
+// for the beam entry points (beam) only, and not combined with each other; so are beam groups (slimt_hip_ctx_set_beam_groups),
+// whose count must divide the call's beam (open_beam).
 // While call.truncated, call.floored, call.typical, call.constrained or call.fanout is set fused_decoder_allowed() is false: the call decodes with the per-stage kernels
 // and is never merged; the context's decode mode is not touched and still chooses the encoder. Consensus is for the
 // fan-out entry points (fanout) only: any other call that finds it armed is refused. The destructor empties ctx->call.
@@ -2103,6 +2116,7 @@ struct CallOptions {
       return fail(-1, "beam: %zu sources of beam %d exceed the context's max_batch %zu", B, beam, c->max_B);
     if (B == 0) return fail(-1, "empty batch");
     if (call.sb_n && call.sb_n != B) return fail(-1, "beam sampling: %zu sources armed, the call has %zu", call.sb_n, B);
+    if (call.bg_groups && beam % call.bg_groups) return fail(-1, "beam groups: %d groups do not divide a beam of %d", call.bg_groups, beam);
     RCCHK(open_fanout(B * (size_t)beam));
     c->call.beam = beam;
     c->call.beam_mode = mode;
@@ -2196,6 +2210,16 @@ struct CallOptions {
         return fail(-1, "beam constraints: beam sampling is armed too (slimt_hip_ctx_set_beam_sampling); constrained sampled beams are not supported");
       call.bm_constrained = true;
       call.bc = a.bc;
+    }
+    if (a.bg_groups) {
+      if (!beam) return fail(-1, "beam groups: armed on a translate call that is not a beam call (slimt_hip_translate_beam*)");
+      if (a.sb_n)
+        return fail(-1, "beam groups: beam sampling is armed too (slimt_hip_ctx_set_beam_sampling); grouped sampled beams are not supported");
+      if (cn_armed(a.bc))
+        return fail(-1, "beam groups: beam constraints are armed too (slimt_hip_ctx_set_beam_constraints); grouped constrained beams are not supported");
+      call.bg_groups = a.bg_groups;
+      call.bg_penalty = a.bg_penalty;
+      call.bg_group_of = a.bg_group_of;
     }
     return 0;
   }
@@ -2751,7 +2775,16 @@ int beam_steps(slimt_hip_ctx *c, size_t B, size_t S, size_t Tmax, uint32_t eos_i
     cs.c = call.bc;
   }
   uint32_t *const hist_blocks[2] = {c->bm_chist.as<uint32_t>(), c->bm_chist.as<uint32_t>() + c->max_B * (size_t)kBeamConstrainedMaxHistory};
+  // in groups (slimt_hip_ctx_set_beam_groups): beam_grouped.hip's selection and its start state, one live slot per group
+  const bool grouped = call.bg_groups != 0;
+  BeamGroupedArgs gs;
+  gs.groups = grouped ? call.bg_groups : 1;
+  gs.penalty = call.bg_penalty;
   auto select = [&](const BeamSelectArgs &step) {
+    if (grouped) {
+      gs.step = step;
+      return launch_beam_select_grouped(gs, st);
+    }
     if (constrained && !step.init) {
       cs.step = step;
       cs.hist_src = hist_blocks[step.t & 1];
@@ -2808,6 +2841,10 @@ int beam_steps(slimt_hip_ctx *c, size_t B, size_t S, size_t Tmax, uint32_t eos_i
   if (sampled && call.sb_dev_perturbed) {
     fa.perturbed = c->bm_sampled.as<float>();
     fa.out_perturbed = call.sb_dev_perturbed;
+  }
+  if (grouped && call.bg_dev_group_of) {
+    fa.out_group = call.bg_dev_group_of;
+    fa.group_size = (int)k / call.bg_groups;
   }
   const hipError_t he = launch_beam_finish(fa, st);
   if (he != hipSuccess) return fail((int)he, "beam finish: %s", hipGetErrorString(he));
@@ -3785,6 +3822,10 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const BatchOpti
         call.sb_dev_keys = staged;
       }
     }
+    if (call.bg_group_of) {  // (grouped: the hypotheses' groups [R] staged)
+      HIPCHK(ctx->bm_groups.reserve(R * 4));
+      call.bg_dev_group_of = ctx->bm_groups.as<uint32_t>();
+    }
   }
   float *const scores = user.scores;  // (a scored call: the caller's [B][Tmax] host array)
   if (!wait && persistent) {
@@ -3826,6 +3867,7 @@ int translate_host(slimt_hip_ctx *ctx, slimt_hip_shortlist *gen, const BatchOpti
     HIPCHK(hipMemcpyAsync(call.bm_totals, call.bm_dev_totals, R * 4, hipMemcpyDeviceToHost, st));
     if (call.bm_scores) HIPCHK(hipMemcpyAsync(call.bm_scores, call.bm_dev_scores, R * Tmax * 4, hipMemcpyDeviceToHost, st));
     if (call.sb_perturbed) HIPCHK(hipMemcpyAsync(call.sb_perturbed, call.sb_dev_perturbed, R * 4, hipMemcpyDeviceToHost, st));
+    if (call.bg_group_of) HIPCHK(hipMemcpyAsync(call.bg_group_of, call.bg_dev_group_of, R * 4, hipMemcpyDeviceToHost, st));
   }
   if (wait) RCCHK(slimt_hip_ctx_synchronize(ctx));  // sleeps on a blocking-sync event (a worker per context: no spinning)
   return 0;
@@ -3993,6 +4035,7 @@ extern "C" int slimt_hip_translate_beam_device(slimt_hip_ctx *ctx, const uint32_
   ctx->call.bm_dev_scores = d_token_scores;
   ctx->call.sb_dev_keys = ctx->call.sb_keys;  // (device memory, like the other arrays of this entry point)
   ctx->call.sb_dev_perturbed = ctx->call.sb_perturbed;
+  ctx->call.bg_dev_group_of = ctx->call.bg_group_of;
   return translate_device(ctx, d_src_ids, d_lengths, d_shortlist, B, S, n_shortlist, limit_factor, eos_id, d_out_ids, d_out_len,
                           d_align, steps_hint);
 }
@@ -4108,6 +4151,67 @@ extern "C" int slimt_hip_beam_step_sampled(const float *logits, size_t B, int be
   HIPCHK(hipMemcpyAsync(totals_out, o + 3 * R, R * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(flags_out, o + 4 * R, R * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(perturbed_out, o + 5 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// slimt_hip_beam_step with beam_grouped.hip's selection: the groups and the penalty beside it.
+extern "C" int slimt_hip_beam_step_grouped(const float *logits, size_t B, int beam, size_t N, const uint32_t *ids, int groups,
+                                           float penalty, const float *totals_in, const uint32_t *flags_in, uint32_t eos_id,
+                                           uint32_t *parent, uint32_t *token, float *token_score, float *totals_out,
+                                           uint32_t *flags_out) {
+  RCCHK(beam_arguments(beam, 0));
+  if (groups < 1 || groups > beam || beam % groups)
+    return fail(-1, "beam_step_grouped: %d groups do not divide a beam of %d", groups, beam);
+  if (!(penalty >= 0.0f && penalty <= slimt_hip::kBeamGroupedMaxPenalty))
+    return fail(-1, "beam_step_grouped: a penalty of %g is not in 0..%g", (double)penalty, (double)slimt_hip::kBeamGroupedMaxPenalty);
+  if (!logits || !totals_in || !flags_in || !parent || !token || !token_score || !totals_out || !flags_out || !B || !N)
+    return fail(-1, "bad argument");
+  if (N >= (size_t)slimt_hip::kBeamMaxN) return fail(-1, "beam: an output layer of %zu columns (2^20 or more)", N);
+  const size_t R = B * (size_t)beam;
+  if (B > 0x7fffffffu / (size_t)beam) return fail(-1, "beam_step_grouped: more than %d rows", 0x7fffffff);
+  for (size_t r = 0; r < R; ++r) {
+    if (flags_in[r] > slimt_hip::kBeamFinished)
+      return fail(-1, "beam_step_grouped: flag %u of row %zu is not 0 (dead), 1 (live) or 2 (finished)", flags_in[r], r);
+    if (flags_in[r] == slimt_hip::kBeamLive && !std::isfinite(totals_in[r]))
+      return fail(-1, "beam_step_grouped: the total of live row %zu is not finite", r);
+    if (flags_in[r] == slimt_hip::kBeamFinished && totals_in[r] != totals_in[r])
+      return fail(-1, "beam_step_grouped: the total of finished row %zu is NaN", r);
+  }
+  Tmp3 t;
+  hipStream_t st = nullptr;
+  HIPCHK(t.a.reserve(R * N * 4));
+  HIPCHK(t.b.reserve(N * 4));
+  HIPCHK(t.c.reserve(2 * R * 4));
+  HIPCHK(t.d.reserve(5 * R * 4));
+  HIPCHK(hipMemcpyAsync(t.a.p, logits, R * N * 4, hipMemcpyHostToDevice, st));
+  if (ids) HIPCHK(hipMemcpyAsync(t.b.p, ids, N * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.p, totals_in, R * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(t.c.as<char>() + R * 4, flags_in, R * 4, hipMemcpyHostToDevice, st));
+  BeamGroupedArgs ga;
+  ga.groups = groups;
+  ga.penalty = penalty;
+  BeamSelectArgs &a = ga.step;
+  a.logits = t.a.as<float>();
+  a.B = (int)B;
+  a.k = beam;
+  a.N = (int)N;
+  a.ids = ids ? t.b.as<uint32_t>() : nullptr;
+  a.eos = eos_id;
+  a.totals_in = t.c.as<float>();
+  a.flags_in = t.c.as<uint32_t>() + R;
+  uint32_t *o = t.d.as<uint32_t>();
+  a.parent = o;
+  a.token = o + R;
+  a.token_score = reinterpret_cast<float *>(o + 2 * R);
+  a.totals_out = reinterpret_cast<float *>(o + 3 * R);
+  a.flags_out = o + 4 * R;
+  HIPCHK(launch_beam_select_grouped(ga, st));
+  HIPCHK(hipMemcpyAsync(parent, o, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(token, o + R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(token_score, o + 2 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(totals_out, o + 3 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(flags_out, o + 4 * R, R * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return 0;
 }

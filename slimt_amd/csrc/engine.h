@@ -85,6 +85,10 @@ struct ArmedOptions {
   const uint64_t *sb_keys = nullptr;  // [sb_n], NULL: slimt_hip_sampling_key(0, b)
   float *sb_perturbed = nullptr;      // nullable [sb_n][beam]
   StepConstraints bc;                 // constraints on a beam call (slimt_hip_ctx_set_beam_constraints): armed by cn_armed
+  // diverse beam search (slimt_hip_ctx_set_beam_groups): armed for bg_groups > 0
+  int bg_groups = 0;
+  float bg_penalty = 0.0f;
+  uint32_t *bg_group_of = nullptr;    // nullable [B][beam]
 };
 
 // The translate call in progress: filled by its CallOptions (engine.cpp), reset as a whole when the entry point returns.
@@ -122,6 +126,11 @@ struct CallState {
   // ... under step constraints (slimt_hip_ctx_set_beam_constraints; beam_constrained.hip's selection over the slots' history rows)
   bool bm_constrained = false;
   StepConstraints bc;
+  // ... in groups under a Hamming penalty (slimt_hip_ctx_set_beam_groups; beam_grouped.hip's selection): the hypotheses' groups
+  // [B][beam] (nullable) as the caller gave them, and as the finish kernel writes them (the caller's, or bm_groups)
+  int bg_groups = 0;  // (0: not armed)
+  float bg_penalty = 0.0f;
+  uint32_t *bg_group_of = nullptr, *bg_dev_group_of = nullptr;
   BatchOptions dev;  // the current unmerged batch's options as the kernels address them (a merged launch: MergePlan::opt)
 };
 
@@ -292,6 +301,8 @@ struct slimt_hip_ctx {
   // ... under step constraints: the slots' history rows [2][max_batch][kBeamConstrainedMaxHistory], reserved by the first armed
   // beam call and sized by max_batch once; a step reads one block and writes the other, like the SSRU states
   slimt_hip::DevBuf bm_chist;
+  // ... in groups: the device staging of a host call's group_of [rows], reserved by the first armed call that asks for it
+  slimt_hip::DevBuf bm_groups;
   std::vector<uint32_t> bm_row_src;
   slimt_hip::DevBuf prev, out_ids, out_len, finished, n_finished, align;
   slimt_hip::DevBuf shortlist;

@@ -997,6 +997,9 @@ struct BeamFinishArgs {
   // a sampled beam call (both or neither): the final slots' perturbed values [B k] and their place in the order [B][k]
   const float *perturbed = nullptr;
   float *out_perturbed = nullptr;
+  // a grouped beam call: each hypothesis's group (final slot / group_size) in the output's order [B][k], kBeamNone for a dead slot
+  uint32_t *out_group = nullptr;
+  int group_size = 1;
 };
 hipError_t launch_beam_finish(const BeamFinishArgs &a, hipStream_t st);
 
@@ -1036,6 +1039,21 @@ struct BeamConstrainedArgs {
 };
 size_t beam_constrained_lds_bytes(int k, int N, int Th, bool penalised);
 hipError_t launch_beam_constrained(const BeamConstrainedArgs &a, hipStream_t st);
+
+// ---- diverse beam search: the selection over G groups of k / G slots under a Hamming penalty (beam_grouped.hip) -----------
+// `step` is launch_beam_select's step selected group by group (include/slimt_hip.h, slimt_hip_ctx_set_beam_groups): group j
+// owns the slots j g .. j g + g - 1, g = k / groups, draws its candidates from them alone and orders them by
+// aug = cand - penalty * n_c, n_c the new slots of the groups before it that were extended with column c at this step; a new
+// slot's total is cand. step.init: the start state with slot j g of every group live. groups = 1 is launch_beam_select's
+// selection bit for bit. One 512-thread workgroup per source: a wave per slot through the sweep, wave 0 selects.
+constexpr int kBeamGroupedResidentN = 4096;      // the widest row (a multiple of 4) a slot's wave holds in registers
+constexpr float kBeamGroupedMaxPenalty = 1000.0f;  // the setter's bound: aug stays finite when cand is
+struct BeamGroupedArgs {
+  BeamSelectArgs step;
+  int groups = 1;
+  float penalty = 0.0f;
+};
+hipError_t launch_beam_select_grouped(const BeamGroupedArgs &a, hipStream_t st);
 
 // the column means (rounded) of an f32 K/V cache [Ld][K, V][B * S][D]: centre[(2 l + p) * D + d] (FusedDecodeArgs::kv_centre)
 hipError_t launch_kv_centres(const float *kv, int Ld, int B, int S, int D, unsigned long long *sums, int *centre, hipStream_t st);

@@ -86,6 +86,8 @@ class Response:  # Response.hh: source / target with sentence + token ranges, so
     # log-probability as the engine returned it (-inf where a sentence has fewer than j + 1 hypotheses). Empty otherwise
     nbest: List["Response"] = field(default_factory=list)
     hypothesis_scores: List[float] = field(default_factory=list)
+    # beam_search(groups=): per sentence, the group that produced the hypothesis (-1 where there is none). Empty otherwise
+    group: List[int] = field(default_factory=list)
 
     def to(self, encoding: Encoding) -> None:
         self.source.to(encoding)
@@ -748,7 +750,7 @@ class Service:
             raise ValueError(f"sample_and_select: utility is 'tokens' or 'chrf', not {utility!r}")
         if max_order is None:
             max_order = 6 if utility == "chrf" else 4
-        processed, ranked, _ = self._beam_ranked(model, sources, n, False, int(sampling[1]))
+        processed, ranked, _, _ = self._beam_ranked(model, sources, n, False, int(sampling[1]))
         per_request = [segs for _, segs in processed]
         histories = [[None] * len(segs) for segs in per_request]
         picked = [([0.0] * len(segs), [0] * len(segs)) for segs in per_request]
@@ -777,7 +779,8 @@ class Service:
         return out
 
     def beam_search(self, model: Model, texts: Sequence[str], beam: int, mean: bool = False,
-                    encoding: Encoding = Encoding.UTF8, sample_seed: Optional[int] = None, constraints=None) -> List[Response]:
+                    encoding: Encoding = Encoding.UTF8, sample_seed: Optional[int] = None, constraints=None,
+                    groups: Optional[int] = None, diversity: float = 0.0) -> List[Response]:
         """Beam search with n-best output (include/slimt_hip.h, slimt_hip_translate_beam): every sentence is decoded with
         `beam` = k slots (1..capi.MAX_BEAM) from one encoding of it and comes back as its k best hypotheses, ordered by their
         summed log-probability (mean=True: per token). Each Response carries `nbest`, its k alternatives as Responses
@@ -792,27 +795,39 @@ class Service:
         capi.sampling_key(sample_seed, i), wherever the batcher puts it.
         constraints: a dict of translate(constraints=)'s keywords (no_repeat_ngram, repetition_penalty, min_length, suppress):
         every slot is searched under those step constraints on the tokens along its own parents
-        (slimt_hip_ctx_set_beam_constraints). Not combined with sample_seed."""
+        (slimt_hip_ctx_set_beam_constraints). Not combined with sample_seed.
+        groups: DIVERSE beam search (slimt_hip_ctx_set_beam_groups) -- the k slots are `groups` beam searches of k / groups
+        slots each, a later group pushed away from the tokens the earlier ones chose at the same step by `diversity` (0..1000)
+        per earlier pick; the totals stay the hypotheses' exact log-probabilities. Every `nbest` Response then carries `group`,
+        per sentence. groups must divide beam; not combined with sample_seed or constraints."""
         if constraints is not None and sample_seed is not None:
             raise ValueError("beam_search: constraints are not combined with sample_seed")
+        if groups is not None and (sample_seed is not None or constraints is not None):
+            raise ValueError("beam_search: groups are not combined with sample_seed or constraints")
+        if groups is not None and (int(groups) < 1 or int(beam) % int(groups)):
+            raise ValueError(f"beam_search: groups must divide the beam, not {groups} of {beam}")
         k = int(beam)
         if k < 1 or k > capi.MAX_BEAM:
             raise ValueError(f"beam_search: a beam of 1..{capi.MAX_BEAM} expected, not {beam}")
-        processed, ranked, totals_of = self._beam_ranked(model, texts, k, mean, sample_seed, constraints)
+        grouped = None if groups is None else (int(groups), float(diversity))
+        processed, ranked, totals_of, group_of = self._beam_ranked(model, texts, k, mean, sample_seed, constraints, grouped)
         sources = [src for src, _ in processed]
         alts = [self._respond_many(model, sources, h) for h in ranked]
         out = alts[0]
         for j, alt in enumerate(alts):
             for r, resp in enumerate(alt):
                 resp.hypothesis_scores = totals_of[j][r]
+                if grouped is not None:
+                    resp.group = group_of[j][r]
         for r, resp in enumerate(out):
             resp.nbest = [a[r] for a in alts]
             resp.to(encoding)
         return out
 
-    def _beam_ranked(self, model: Model, texts: Sequence[str], k: int, mean: bool, sample_seed: Optional[int], constraints=None):
+    def _beam_ranked(self, model: Model, texts: Sequence[str], k: int, mean: bool, sample_seed: Optional[int], constraints=None,
+                     grouped=None):
         """beam_search's calls: (the processed texts, ranked[j][request][segment] = rank j's (token ids, alignment, token
-        scores), totals_of[j][request][segment])"""
+        scores), totals_of[j][request][segment], group_of[j][request][segment] under grouped = (G, penalty), else -1)"""
         processed = model.processor.process_many(texts, self.wrap_length, self.workers)
         per_request = [segs for _, segs in processed]
         units = [_Unit(r, i, list(seg)) for r, segs in enumerate(per_request) for i, seg in enumerate(segs)]
@@ -822,6 +837,7 @@ class Service:
         key_of = {} if sample_seed is None else {(u.request, u.index): capi.sampling_key(sample_seed, i) for i, u in enumerate(units)}
         ranked = [[[None] * len(segs) for segs in per_request] for _ in range(k)]
         totals_of = [[[0.0] * len(segs) for segs in per_request] for _ in range(k)]
+        group_of = [[[-1] * len(segs) for segs in per_request] for _ in range(k)]
         per_call = max(1, self.max_words // k)
         batches, cur = [], []
         for u in sorted(units, key=lambda u: (len(u.words), u.request, u.index)):  # (_batches' walk, the rows bounded too)
@@ -847,6 +863,9 @@ class Service:
                     ctx.set_beam_sampling(np.array([key_of[u.request, u.index] for u in batch], np.uint64), B)
                 if constraints is not None:
                     ctx.set_beam_constraints(**constraints)
+                groups = np.full((B, k), capi.BEAM_NONE, np.uint32)
+                if grouped is not None:  # (written by the call below, which waits)
+                    ctx.set_beam_groups(grouped[0], grouped[1], groups)
                 if model.shortlist_generator is not None:
                     out, ln, tot, sc, al = ctx.translate_beam_generated(model.shortlist_generator, ids, lens, k, self.limit_factor,
                                                                         eos, mean, want_align=True)
@@ -857,7 +876,8 @@ class Service:
                         n, L = int(ln[b, j]), int(lens[b])
                         ranked[j][u.request][u.index] = (out[b, j, :n].tolist(), al[b, j, :n, :L].copy(), sc[b, j, :n].copy())
                         totals_of[j][u.request][u.index] = float(tot[b, j])
-        return processed, ranked, totals_of
+                        group_of[j][u.request][u.index] = -1 if groups[b, j] == capi.BEAM_NONE else int(groups[b, j])
+        return processed, ranked, totals_of, group_of
 
     def pivot(self, first: Model, second: Model, texts: Sequence[str], html: bool = False,
               scores: bool = False, sampling=None, truncation=None) -> List[Response]:

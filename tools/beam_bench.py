@@ -8,10 +8,13 @@ Shape: tiny11, S = 32 (Tmax 48), a 4096-id shortlist, 32 sources, beam k = 4 and
                each step's logits and runs one selection launch per step (sample_truncate.hip) plus the step's record /
                embed launch -- the comparable existing call;
   greedy    -- slimt_hip_translate_async of the 32 sources in the context's default mode (the persistent decoder).
+With --grouped the rounds are instead the beam call and the same call armed with slimt_hip_ctx_set_beam_groups (penalty 0.5) in
+G = 1, 2 and k groups (beam_grouped.hip's selection: a wave per slot through the sweep). G = 1 returns the plain call's bits,
+so grouped1 against beam is the k-waves-at-once sweep against the one-row-at-a-time sweep on identical results.
 Each kind is repeated `--repeats` times (a repeat = `--rounds` rounds); medians and every repeat's value are printed, then
 one JSON line per k.
 
-  python tools/beam_bench.py [--rounds 10] [--repeats 3] [--sources 32] [--beams 4,8]
+  python tools/beam_bench.py [--rounds 10] [--repeats 3] [--sources 32] [--beams 4,8] [--grouped]
 """
 import argparse
 import json
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--grouped", action="store_true", help="the beam call against the grouped call in G = 1, 2 and k groups")
     args = ap.parse_args()
 
     from slimt_amd import capi, synth
@@ -44,8 +48,8 @@ def main():
     beams = [int(x) for x in args.beams.split(",")]
     sl = synth.make_shortlist(m.V, args.shortlist)
     ids, lens = synth.make_batch(m.V, B, S, seed=4321)
-    kinds = ("beam", "truncated", "greedy")
     for k in beams:
+        kinds = ("beam", "grouped1", "grouped2", "grouped%d" % k) if args.grouped else ("beam", "truncated", "greedy")
         N = B * k
         ctx = capi.Context(gm, N, S)
         bm = ctx.beam_buffers(B, S, k)
@@ -61,7 +65,10 @@ def main():
         T = bm[2].shape[2]
 
         def submit(kind):
-            if kind == "beam":
+            if kind.startswith("grouped"):
+                ctx.set_beam_groups(int(kind[7:]), 0.5)
+                ctx.translate_beam_async(bm, sl)
+            elif kind == "beam":
                 ctx.translate_beam_async(bm, sl)
             elif kind == "truncated":
                 ctx.translate_fanout_async(fo, sl, sampling=(1.0, keys_a), truncation=(40, 0.9))
@@ -72,7 +79,7 @@ def main():
         for _ in range(args.warmup):
             for kind in kinds:
                 submit(kind)
-        assert (bm[3] == T).all() and (fo[4] == T).all()  # (every row ran all its steps)
+        assert (bm[3] == T).all() and (args.grouped or (fo[4] == T).all())  # (every row ran all its steps)
         times = {kind: [] for kind in kinds}
         for _ in range(args.repeats):
             per = {kind: [] for kind in kinds}
@@ -90,6 +97,13 @@ def main():
             out[kind] = {"call_ms_median": round(med * 1e3, 3), "call_ms_repeats": [round(t * 1e3, 3) for t in times[kind]]}
             print("k = %d %-9s %.3f ms per call (repeats %s)" % (k, kind, med * 1e3, ", ".join("%.3f" % (t * 1e3) for t in times[kind])))
         med = {kind: statistics.median(times[kind]) for kind in kinds}
+        if args.grouped:
+            out["grouped1_step_over_beam_step_us"] = round((med["grouped1"] - med["beam"]) / T * 1e6, 2)
+            print("k = %d: a grouped G = 1 step costs %+.2f us against the plain beam step" % (k, out["grouped1_step_over_beam_step_us"]))
+            print(json.dumps(out))
+            keys.free()
+            ctx.close()
+            continue
         out["beam_step_over_truncated_step_us"] = round((med["beam"] - med["truncated"]) / T * 1e6, 2)
         out["beam_over_truncated"] = round(med["beam"] / med["truncated"], 4)
         out["beam_over_greedy"] = round(med["beam"] / med["greedy"], 4)
