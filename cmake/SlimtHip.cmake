@@ -32,7 +32,7 @@ if(SLIMT_HIP_PREBUILT)
   target_include_directories(slimt_hip INTERFACE "${SLIMT_HIP_INCLUDE}")
 else()
   find_program(SLIMT_HIPCC hipcc HINTS /opt/rocm/bin ENV ROCM_PATH PATH_SUFFIXES bin REQUIRED)
-  set(SLIMT_HIP_SOURCES kernels.hip gemm_tile.hip decode_kernels.hip decode_fused.hip encode_fused.hip encode_wide.hip encode_tall.hip shortlist.hip score_tall.hip score_alternatives.hip score_candidates.hip decode_fanout.hip consensus.hip consensus_units.hip sample_truncate.hip sample_floor.hip sample_typical.hip step_constrain.hip beam_select.hip beam_sampled.hip beam_constrained.hip beam_grouped.hip engine.cpp)
+  set(SLIMT_HIP_SOURCES kernels.hip gemm_tile.hip decode_kernels.hip decode_fused.hip encode_fused.hip encode_wide.hip encode_tall.hip shortlist.hip score_tall.hip score_alternatives.hip score_candidates.hip decode_fanout.hip consensus.hip consensus_units.hip sample_truncate.hip sample_floor.hip sample_typical.hip step_constrain.hip beam_select.hip beam_sampled.hip beam_constrained.hip beam_grouped.hip combine_step.hip engine.cpp)
   set(SLIMT_HIP_HEADERS kernels.h engine.h launch_choice.h decoder_plan.h device_common.h scores.h sampling.h truncation.h floor.h typical.h constraints.h beam.h beam_sampled.h beam_tail.h shortlist_device.h decode_attention_packed.inl.h decode_rows.h)
   list(TRANSFORM SLIMT_HIP_SOURCES PREPEND "${SLIMT_HIP_CSRC}/")
   list(TRANSFORM SLIMT_HIP_HEADERS PREPEND "${SLIMT_HIP_CSRC}/")

@@ -1237,6 +1237,38 @@ int slimt_hip_beam_step_grouped(const float *logits, size_t B, int beam, size_t 
                                 const float *totals_in, const uint32_t *flags_in, uint32_t eos_id, uint32_t *parent,
                                 uint32_t *token, float *token_score, float *totals_out, uint32_t *flags_out);
 
+/* ---- combined decoding: one token per group of fan-out rows ---- */
+/* Source-contrastive decoding (Sennrich, Vamvas, Mohammadshahi 2024: argmax log p(y | x) - lambda log p(y | x'), with the
+ * plausibility cut of Li et al. 2023) and, with positive weights, multi-source ensembling, on the fan-out decoder: the rows
+ * of a group read different sources and decode ONE hypothesis.
+ * Arms the NEXT fan-out call (slimt_hip_translate_fanout / _async / _device / _async_generated); members = 0 disarms (the
+ * other arguments are then not read). Refused at once: members outside 0 .. SLIMT_HIP_MAX_COMBINE, weights NULL, a weight
+ * out of range, gap > 0 or NaN. THE CONTRACT (slimt_amd/csrc/combine.h): the armed call of N rows treats the rows
+ * g m .. g m + m - 1 as group g, m = members; member 0 is the primary. weights [m]: weights[0] finite and > 0, the others
+ * finite with |w| <= 16. gap <= 0 is a log-ratio, -inf: off. At every step, per member row j with logits l_j over the N
+ * columns of the output layer (N < 2^20), usable, M_j, Q_j, L_j and lp_j[c] = (l_j[c] - M_j) - L_j are exactly the beam
+ * contract's above. The primary is always counted; a member j > 0 is counted if weights[j] != 0 and its row is usable; a
+ * member that is not counted contributes nothing. With a usable primary, column c is a candidate when l_0[c] > -inf,
+ * l_0[c] - M_0 >= gap (one f32 subtraction) and s[c] is not NaN, where s[c] = weights[0] * lp_0[c] (one f32 multiply), then
+ * for the counted j = 1 .. m - 1 ascending s = fmaf(weights[j], lp_j[c], s), a term whose l_j[c] is -inf left out.
+ * Candidates are ordered by s descending as floats (+0 == -0), then l_0[c] descending, then the lower column; the first is
+ * the group's column. With m = 1 or every other weight 0 that is the greedy arg-max of the primary; with no candidate left
+ * the group's column is the primary's arg-max; with an unusable primary it is column 0 and s is NaN. Every member row
+ * records the group's token -- so the rows of a group get identical out_ids and out_len and reach EOS together -- and, where
+ * scores are armed (slimt_hip_ctx_set_scores), its OWN lp_j[column], bit for bit (NaN for an unusable member); each row
+ * keeps its own alignment rows over its own source.
+ * The option is consumed by the next translate entry point whatever its outcome. Refused there with a message: a call that
+ * is not a fan-out call (a beam call included); N no multiple of m; together with a target prefix, sampling (and its
+ * truncations), step constraints or consensus; an output layer of 2^20 columns or more. Execution: the step-wise decoder
+ * stores each step's logits and slimt_amd/csrc/combine_step.hip selects, one launch per step. */
+#define SLIMT_HIP_MAX_COMBINE 4
+int slimt_hip_ctx_set_fanout_combine(slimt_hip_ctx *ctx, int members, const float *weights, float gap);
+/* One selection of the contract above on host pointers: logits [G * members][N], ids (nullable) [N] the columns' vocabulary
+ * ids. Writes column [G], token [G] (ids[column], or the column), combined [G] (s at the column; NaN where no candidate was
+ * left or the primary is unusable) and member_scores [G * members] (lp_j[column]). Stateless, waits. */
+int slimt_hip_combine_step(const float *logits, size_t G, int members, size_t N, const uint32_t *ids, const float *weights,
+                           float gap, uint32_t *column, uint32_t *token, float *combined, float *member_scores);
+
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, HIP events bracket every launch of kernel family `kernel_id`
  * on the ctx stream; slimt_hip_profile_read returns the number of launches

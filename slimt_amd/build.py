@@ -18,9 +18,9 @@ LIB_DIR = os.path.join(HERE, "lib")
 # SLIMT_HIP_LIB: build/load an alternative library file (kernel experiments only)
 LIB_PATH = os.environ.get("SLIMT_HIP_LIB") or os.path.join(LIB_DIR, "libslimt_hip.so")
 
-SOURCES = ["kernels.hip", "gemm_tile.hip", "decode_kernels.hip", "decode_fused.hip", "encode_fused.hip", "encode_wide.hip", "encode_tall.hip", "shortlist.hip", "score_tall.hip", "score_alternatives.hip", "score_candidates.hip", "decode_fanout.hip", "consensus.hip", "consensus_units.hip", "sample_truncate.hip", "sample_floor.hip", "sample_typical.hip", "step_constrain.hip", "beam_select.hip", "beam_sampled.hip", "beam_constrained.hip", "beam_grouped.hip",
+SOURCES = ["kernels.hip", "gemm_tile.hip", "decode_kernels.hip", "decode_fused.hip", "encode_fused.hip", "encode_wide.hip", "encode_tall.hip", "shortlist.hip", "score_tall.hip", "score_alternatives.hip", "score_candidates.hip", "decode_fanout.hip", "consensus.hip", "consensus_units.hip", "sample_truncate.hip", "sample_floor.hip", "sample_typical.hip", "step_constrain.hip", "beam_select.hip", "beam_sampled.hip", "beam_constrained.hip", "beam_grouped.hip", "combine_step.hip",
            "engine.cpp"]
-HEADERS = ["kernels.h", "engine.h", "launch_choice.h", "decoder_plan.h", "device_common.h", "scores.h", "sampling.h", "truncation.h", "floor.h", "typical.h", "constraints.h", "beam.h", "beam_sampled.h", "beam_tail.h", "shortlist_device.h", "decode_attention_packed.inl.h", "decode_rows.h",
+HEADERS = ["kernels.h", "engine.h", "launch_choice.h", "decoder_plan.h", "device_common.h", "scores.h", "sampling.h", "truncation.h", "floor.h", "typical.h", "constraints.h", "beam.h", "beam_sampled.h", "beam_tail.h", "combine.h", "shortlist_device.h", "decode_attention_packed.inl.h", "decode_rows.h",
            os.path.join(ROOT, "include", "slimt_hip.h")]
 
 # -ffp-contract=off: the float epilogues are written operation by operation

@@ -61,6 +61,7 @@ SYMBOLS = [
     "slimt_hip_ctx_set_beam_sampling", "slimt_hip_beam_step_sampled",
     "slimt_hip_ctx_set_beam_constraints", "slimt_hip_beam_step_constrained",
     "slimt_hip_ctx_set_beam_groups", "slimt_hip_beam_step_grouped",
+    "slimt_hip_ctx_set_fanout_combine", "slimt_hip_combine_step",
 ]
 
 K_NONE, K_GEMM_ENC, K_GEMM_DEC, K_LOGITS, K_ATTN_ENC, K_ATTN_DEC, K_SSRU, K_DECODE_FUSED, K_ENCODE_FUSED = range(9)
@@ -327,6 +328,8 @@ def lib():
     L.slimt_hip_beam_step_constrained.argtypes = [vp, sz, i32, sz, vp, vp, sz, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     L.slimt_hip_ctx_set_beam_groups.argtypes = [vp, i32, f32, vp]
     L.slimt_hip_beam_step_grouped.argtypes = [vp, sz, i32, sz, vp, i32, f32, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.slimt_hip_ctx_set_fanout_combine.argtypes = [vp, i32, vp, f32]
+    L.slimt_hip_combine_step.argtypes = [vp, sz, i32, sz, vp, vp, f32, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("slimt_hip_abi_version",):
@@ -509,6 +512,30 @@ def beam_step_grouped(logits, totals, flags, beam: int, groups: int, penalty: fl
     _chk(lib().slimt_hip_beam_step_grouped(_p(logits), R // beam, beam, N, _p(ids), int(groups), float(penalty), _p(totals), _p(flags),
                                            int(eos_id), _p(parent), _p(token), _p(score), _p(totals_out), _p(flags_out)))
     return parent, token, score, totals_out, flags_out
+
+
+MAX_COMBINE = 4  # SLIMT_HIP_MAX_COMBINE
+
+
+def combine_step(logits, members: int, weights, gap: float = -np.inf, ids=None):
+    """slimt_hip_combine_step: one combined selection over logits [G * members, N] (float32), rows g m .. g m + m - 1 one
+    group with member 0 the primary; weights [members] float32, gap <= 0 a log-ratio (-inf: off); ids: the columns'
+    vocabulary ids (uint32 [N]; None: the column). Returns (column [G], token [G], combined [G], member_scores [G, members])."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    weights = np.ascontiguousarray(weights, dtype=np.float32)
+    m = int(members)
+    if logits.ndim != 2 or m < 1 or logits.shape[0] % m or weights.shape != (m,):
+        raise ValueError("combine_step: logits [G * members, N] and weights [members] expected")
+    R, N = logits.shape
+    ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32)
+    if ids is not None and ids.shape != (N,):
+        raise ValueError("combine_step: ids [N] expected")
+    G = R // m
+    column, token = np.zeros(G, np.uint32), np.zeros(G, np.uint32)
+    combined, scores = np.zeros(G, np.float32), np.zeros((G, m), np.float32)
+    _chk(lib().slimt_hip_combine_step(_p(logits), G, m, N, _p(ids), _p(weights), float(gap), _p(column), _p(token), _p(combined),
+                                      _p(scores)))
+    return column, token, combined, scores
 
 
 BEAM_CONSTRAINT_MAX_COLUMNS, BEAM_CONSTRAINT_MAX_HISTORY = 65536, 512  # (include/slimt_hip.h)
@@ -1252,7 +1279,18 @@ class Context:
         return (out_ids, out_len, align, sc) if scores else (out_ids, out_len, align)
 
     # ---- fan-out: N decoder rows over B sources encoded once (include/slimt_hip.h, slimt_hip_translate_fanout*) ----
-    def _arm(self, N: int, scores, prefix, sampling, truncation, T: int, floor=None, constraints=None, typical=None):
+    def set_fanout_combine(self, members: int, weights=(), gap: float = -np.inf):
+        """slimt_hip_ctx_set_fanout_combine: the NEXT fan-out call decodes ONE hypothesis per group of `members` consecutive
+        rows (member 0 the primary) from s = sum_j weights[j] * log p_j: a negative weight contrasts a row's source away
+        (source-contrastive decoding), positive ones ensemble several sources. weights[0] > 0, |weights[j]| <= 16; gap <= 0:
+        the plausibility cut log p_0(c) - log p_0(best) >= gap (-inf: off). members = 0 disarms. Not combined with a
+        prefix, sampling, step constraints or consensus. translate_fanout*() take `combine=(weights, gap)` and do this."""
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        if int(members) and w.size != int(members):
+            raise ValueError("fan-out combine: %d weights for %d members" % (w.size, int(members)))
+        _chk(lib().slimt_hip_ctx_set_fanout_combine(self.h, int(members), _p(w) if w.size else None, float(gap)))
+
+    def _arm(self, N: int, scores, prefix, sampling, truncation, T: int, floor=None, constraints=None, typical=None, combine=None):
         """arms a one-batch call's options, shaped by its N rows (right before the call that takes them)"""
         pre = self._prefix_host(prefix, N, T) if prefix is not None else None
         if scores is not None:
@@ -1270,10 +1308,12 @@ class Context:
             self.set_sampling_typical(typical)
         if constraints is not None:
             self.set_step_constraints(**constraints)
+        if combine is not None:  # (weights, gap)
+            self.set_fanout_combine(len(combine[0]), combine[0], -np.inf if combine[1] is None else combine[1])
 
     def translate_fanout(self, ids, lengths, row_src, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
                          want_align: bool = False, scores: bool = False, prefix=None, sampling=None, truncation=None,
-                         consensus=None, floor=None, constraints=None, typical=None):
+                         consensus=None, floor=None, constraints=None, typical=None, combine=None):
         """slimt_hip_translate_fanout: translate() with N decoder rows over the B sources ids [B,S] / lengths [B], encoded
         once; row_src [N] uint32 names each row's source. Returns out_ids [N,Tmax], out_len [N], align [N,Tmax,S] | None
         (+ scores [N,Tmax]). prefix, sampling, truncation: as in translate(), shaped by N. Every row is bit for bit its row
@@ -1281,7 +1321,9 @@ class Context:
         consensus: (max_order, beta2) -- the call also selects each source's consensus row on the device
         (slimt_hip_ctx_set_fanout_consensus) and returns, last, best [B] uint32 and utility [N] float64. With a kind in
         front, ("units", max_order, beta2), the rows are compared by their unit rows (the character n-gram F, orders up to
-        6) through the model's unit table; ("tokens", ...) is the default."""
+        6) through the model's unit table; ("tokens", ...) is the default.
+        combine: (weights [m], gap | None) -- set_fanout_combine: rows g m .. g m + m - 1 decode one hypothesis, so they
+        share out_ids / out_len; each keeps its own scores and alignment rows."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
         row_src = np.ascontiguousarray(row_src, dtype=np.uint32)
@@ -1294,7 +1336,7 @@ class Context:
         out_len = np.zeros(N, dtype=np.uint32)
         align = np.zeros((N, T, S), dtype=np.float32) if want_align else None
         sc = np.full((N, T), np.nan, dtype=np.float32) if scores else None
-        self._arm(N, sc, prefix, sampling, truncation, T, floor, constraints, typical)
+        self._arm(N, sc, prefix, sampling, truncation, T, floor, constraints, typical, combine)
         cs = self._arm_consensus(consensus, B, N) if consensus is not None else ()
         _chk(lib().slimt_hip_translate_fanout(self.h, _p(ids), _p(lengths), B, S, _p(row_src), N, _p(sl),
                                               0 if sl is None else sl.size, limit_factor, eos_id, _p(out_ids), _p(out_len),
@@ -1313,7 +1355,7 @@ class Context:
 
     def translate_fanout_async(self, bufs, shortlist=None, generator=None, limit_factor: float = 1.5, eos_id: int = 0,
                                scores=None, prefix=None, sampling=None, truncation=None, consensus=None, floor=None,
-                               constraints=None, typical=None):
+                               constraints=None, typical=None, combine=None):
         """slimt_hip_translate_fanout_async[_generated] on (ids, lengths, row_src, out_ids, out_len, align | None) host arrays
         (already filled; those of fanout_buffers() are pinned); synchronize() before reading the outputs. scores: a float32
         [N, Tmax] array; prefix, sampling, truncation: as in translate_async(), shaped by N.
@@ -1330,7 +1372,7 @@ class Context:
         if align is not None and (align.dtype != np.float32 or align.shape != (N, T, S) or not align.flags.c_contiguous):
             raise ValueError("translate_fanout_async: a C-contiguous float32 align of shape %s expected" % ((N, T, S),))
         sl = None if shortlist is None else np.ascontiguousarray(shortlist, dtype=np.uint32)
-        self._arm(N, scores, prefix, sampling, truncation, T, floor, constraints, typical)
+        self._arm(N, scores, prefix, sampling, truncation, T, floor, constraints, typical, combine)
         cs = self._arm_consensus(consensus, B, N) if consensus is not None else None
         if generator is not None:
             _chk(lib().slimt_hip_translate_fanout_async_generated(self.h, generator.h, _p(ids), _p(lengths), B, S, _p(row_src),
@@ -1343,7 +1385,7 @@ class Context:
 
     def translate_fanout_pinned(self, ids, lengths, row_src, shortlist=None, limit_factor: float = 1.5, eos_id: int = 0,
                                 want_align: bool = False, generator=None, scores: bool = False, prefix=None, sampling=None,
-                                truncation=None, consensus=None, floor=None, constraints=None, typical=None):
+                                truncation=None, consensus=None, floor=None, constraints=None, typical=None, combine=None):
         """translate_fanout() through this context's pinned arrays and slimt_hip_translate_fanout_async; returns copies."""
         ids, row_src = np.asarray(ids), np.asarray(row_src)
         B, S = ids.shape
@@ -1354,7 +1396,7 @@ class Context:
         sc = self._pinned.setdefault("fo_sc", _Pinned()).array(np.float32, bufs[3].shape) if scores else None
         cs = self.translate_fanout_async(bufs, shortlist, generator, limit_factor, eos_id, scores=sc, prefix=prefix,
                                          sampling=sampling, truncation=truncation, floor=floor, consensus=consensus,
-                                         constraints=constraints, typical=typical)
+                                         constraints=constraints, typical=typical, combine=combine)
         self.synchronize()
         out = bufs[3].copy(), bufs[4].copy(), (bufs[5].copy() if want_align else None)
         return (out + (sc.copy(),) if scores else out) + tuple(cs or ())
@@ -1362,7 +1404,7 @@ class Context:
     def translate_fanout_device(self, d_ids: int, d_lengths: int, B: int, S: int, d_row_src: int, N: int, d_shortlist: int,
                                 n_shortlist: int, limit_factor: float, eos_id: int, d_out_ids: int, d_out_len: int,
                                 d_align: int = 0, steps_hint: int = 0, scores: int = 0, prefix=None, sampling=None,
-                                truncation=None, consensus=None, floor=None, typical=None):
+                                truncation=None, consensus=None, floor=None, typical=None, combine=None):
         """slimt_hip_translate_fanout_device: device pointers (ints) in and out, like translate_device(); d_row_src [N]
         uint32 (a value >= B is taken as B - 1), outputs and options shaped by N. consensus: ([kind,] max_order, beta2,
         d_best, d_utility) with the device pointers of best [B] uint32 and utility [N] float64."""
@@ -1382,6 +1424,8 @@ class Context:
         if consensus is not None:
             units, rest = self._consensus_kind(consensus)
             self.set_fanout_consensus(*rest, units=units)
+        if combine is not None:
+            self.set_fanout_combine(len(combine[0]), combine[0], -np.inf if combine[1] is None else combine[1])
         _chk(lib().slimt_hip_translate_fanout_device(self.h, vp(d_ids), vp(d_lengths), B, S, vp(d_row_src), N,
                                                      vp(d_shortlist) if n_shortlist else None, n_shortlist, limit_factor,
                                                      eos_id, vp(d_out_ids), vp(d_out_len), vp(d_align) if d_align else None,

@@ -9,6 +9,7 @@
 #include "truncation.h"
 #include "beam.h"
 #include "beam_sampled.h"
+#include "combine.h"
 #include "launch_choice.h"
 
 #include <algorithm>
@@ -1852,6 +1853,30 @@ extern "C" int slimt_hip_ctx_set_beam_groups(slimt_hip_ctx *ctx, int groups, flo
   return 0;
 }
 
+static_assert(SLIMT_HIP_MAX_COMBINE == slimt_hip::kCombineMax, "include/slimt_hip.h and combine.h disagree");
+
+// the setting of a combined step as combine.h takes it, checked (members >= 1)
+static int combine_setting(const char *who, int members, const float *weights, float gap) {
+  if (members < 1 || members > SLIMT_HIP_MAX_COMBINE) return fail(-1, "%s: %d members are not in 1..%d", who, members, SLIMT_HIP_MAX_COMBINE);
+  if (!weights) return fail(-1, "%s: weights is NULL", who);
+  if (!(gap <= 0.0f)) return fail(-1, "%s: a gap of %g is not <= 0 (a log-ratio; -inf: off)", who, (double)gap);
+  if (!slimt_hip::cb_valid(members, weights, gap))
+    return fail(-1, "%s: weights[0] must be finite and > 0, the other weights finite and within +-%g", who, (double)slimt_hip::kCombineMaxWeight);
+  return 0;
+}
+
+extern "C" int slimt_hip_ctx_set_fanout_combine(slimt_hip_ctx *ctx, int members, const float *weights, float gap) {
+  // (the values first, like the temperature)
+  if (members < 0 || members > SLIMT_HIP_MAX_COMBINE)
+    return fail(-1, "fan-out combine: %d members are not in 0..%d", members, SLIMT_HIP_MAX_COMBINE);
+  if (members) RCCHK(combine_setting("fan-out combine", members, weights, gap));
+  if (!ctx) return fail(-1, "null argument");
+  ctx->armed.cb_members = members;  // (0: nothing armed)
+  for (int j = 0; j < SLIMT_HIP_MAX_COMBINE; ++j) ctx->armed.cb_w[j] = j < members ? weights[j] : 0.0f;
+  ctx->armed.cb_gap = members ? gap : 0.0f;
+  return 0;
+}
+
 extern "C" int slimt_hip_ctx_set_score_alternatives(slimt_hip_ctx *ctx, uint32_t k, uint32_t *alt_ids, float *alt_scores,
                                                     uint32_t *rank) {
   // (the value first, like the temperature)
@@ -2071,7 +2096,7 @@ struct MergePlan {
 // ctx->call, the record every inner function reads; `user` holds the per-batch arrays as the caller gave them, one entry per
 // batch, for the entry point to hand on: as they are where they are device memory (options_in_place), through
 // stage_options where they are host memory. The checks run scores -> prefix -> sampling -> truncation -> floor -> typical -> step constraints -> consensus -> beam
-// sampling -> beam constraints -> beam groups and the first refusal is the call's (rc); a truncated call must be sampled, so the truncation is looked at behind
+// sampling -> beam constraints -> beam groups -> fan-out combine and the first refusal is the call's (rc); a truncated call must be sampled, so the truncation is looked at behind
 // the sampling. Beam sampling (slimt_hip_ctx_set_beam_sampling) and beam constraints (slimt_hip_ctx_set_beam_constraints) are
 // for the beam entry points (beam) only, and not combined with each other; so are beam groups (slimt_hip_ctx_set_beam_groups),
 // whose count must divide the call's beam (open_beam).
@@ -2100,6 +2125,8 @@ struct CallOptions {
     if (!c) return 0;
     if (N == 0) return fail(-1, "fan-out: no rows (N = 0)");
     if (N > c->max_B) return fail(-1, "fan-out: %zu rows exceed the context's max_batch %zu", N, c->max_B);
+    if (c->call.cb_members && N % (size_t)c->call.cb_members)
+      return fail(-1, "fan-out combine: %zu rows are no multiple of the %d members of a group", N, c->call.cb_members);
     c->call.fanout = true;
     c->call.rows = (int)N;
     return 0;
@@ -2220,6 +2247,18 @@ struct CallOptions {
       call.bg_groups = a.bg_groups;
       call.bg_penalty = a.bg_penalty;
       call.bg_group_of = a.bg_group_of;
+    }
+    if (a.cb_members) {
+      if (beam) return fail(-1, "fan-out combine: armed on a beam call (slimt_hip_translate_beam*); beams are not combined");
+      if (!fanout) return fail(-1, "fan-out combine: armed on a translate call that is not a fan-out call (slimt_hip_translate_fanout*)");
+      if (call.forced) return fail(-1, "fan-out combine: a target prefix is armed too (slimt_hip_ctx_set_target_prefix); the two are not combined");
+      if (call.sampled) return fail(-1, "fan-out combine: sampling is armed too (slimt_hip_ctx_set_sampling); a combined call is not sampled");
+      if (call.constrained)
+        return fail(-1, "fan-out combine: step constraints are armed too (slimt_hip_ctx_set_step_constraints); the two are not combined");
+      if (call.consensus) return fail(-1, "fan-out combine: consensus is armed too (slimt_hip_ctx_set_fanout_consensus*); the two are not combined");
+      call.cb_members = a.cb_members;
+      for (int j = 0; j < kCombineMax; ++j) call.cb_w[j] = a.cb_w[j];
+      call.cb_gap = a.cb_gap;
     }
     return 0;
   }
@@ -3200,7 +3239,12 @@ int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax,
   const bool constrained = call.constrained;
   if (constrained && out.w.N > kConstraintMaxN)
     return fail(-1, "step constraints: an output layer of %d columns exceeds %d", out.w.N, kConstraintMaxN);
-  const bool stored = truncated || floored || typical || constrained;  // the logits gemm writes the rows and leaves the selection to the next launch
+  // ... and a combined fan-out call, whose selection reads a group's rows together and records for them (combine_step.hip)
+  const bool combined = call.cb_members > 0;
+  if (combined && (uint32_t)out.w.N >= kBeamMaxN)
+    return fail(-1, "fan-out combine: an output layer of %d columns (2^20 or more)", out.w.N);
+  if (combined && (!call.fanout || R % (size_t)call.cb_members)) return fail(-1, "fan-out combine: %zu rows are no groups of %d", R, call.cb_members);
+  const bool stored = truncated || floored || typical || constrained || combined;  // the logits gemm writes the rows and leaves the selection to the next launch
   const int n_parts = stored ? 1 : dgemm_col_blocks(out.w.K, out.w.N, (int)R);
   if (stored) HIPCHK(c->tr_logits.reserve(R * (size_t)out.w.N * 4));
   const EmbedArgs e = embed_args(c);
@@ -3235,8 +3279,10 @@ int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax,
   size_t t = 0;
   bool all_done = false;
   for (; t < max_steps && !rc; ++t) {
-    hipError_t he = launch_decode_begin_step(e, ds, (int)R, t == 0, 1, c->part_val.as<float>(),
-                                             c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs, &ss);
+    hipError_t he = hipSuccess;
+    if (!combined || t == 0)  // (a combined step has recorded its tokens and written the next input rows itself)
+      he = launch_decode_begin_step(e, ds, (int)R, t == 0, 1, c->part_val.as<float>(),
+                                    c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs, &ss);
     if (he != hipSuccess) { rc = fail((int)he, "decode_begin_step: %s", hipGetErrorString(he)); break; }
     if (steps_hint <= 0 && t > 0 && (t % 8) == 0) {
       // stop as soon as every sentence has emitted EOS (Model.cc:161)
@@ -3357,8 +3403,24 @@ int decode_stepwise(slimt_hip_ctx *c, size_t B, size_t S, size_t R, size_t Tmax,
       he = launch_step_constrain(ca, st);
       if (he != hipSuccess) { rc = fail((int)he, "step constraints: %s", hipGetErrorString(he)); break; }
     }
+    if (combined) {  // the selection, this step's record for every row of a group and the next step's input rows: one launch
+      CombineStepArgs ca;
+      ca.logits = c->tr_logits.as<float>();
+      ca.m = call.cb_members;
+      ca.G = (int)(R / (size_t)ca.m);
+      ca.N = out.w.N;
+      ca.ids = ds.shortlist;
+      for (int j = 0; j < kCombineMax; ++j) ca.w[j] = call.cb_w[j];
+      ca.gap = call.cb_gap;
+      ca.st = ds;
+      ca.emb = e;
+      ca.scores = d_scores;
+      ca.dx = c->dx.as<float>();
+      he = launch_combine_step(ca, st);
+      if (he != hipSuccess) { rc = fail((int)he, "fan-out combine: %s", hipGetErrorString(he)); break; }
+    }
   }
-  if (!rc && !all_done) {
+  if (!rc && !all_done && !combined) {
     hipError_t he = launch_decode_begin_step(e, ds, (int)R, 0, 0, c->part_val.as<float>(),
                                              c->part_idx.as<int>(), n_parts, c->dx.as<float>(), st, part_sum, d_scores, &fs, &ss);
     if (he != hipSuccess) rc = fail((int)he, "final record: %s", hipGetErrorString(he));
@@ -4212,6 +4274,43 @@ extern "C" int slimt_hip_beam_step_grouped(const float *logits, size_t B, int be
   HIPCHK(hipMemcpyAsync(token_score, o + 2 * R, R * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(totals_out, o + 3 * R, R * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(flags_out, o + 4 * R, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// One combined selection (combine_step.hip) of G groups of `members` rows on host pointers: the op-level half of the kernel.
+extern "C" int slimt_hip_combine_step(const float *logits, size_t G, int members, size_t N, const uint32_t *ids, const float *weights,
+                                      float gap, uint32_t *column, uint32_t *token, float *combined, float *member_scores) {
+  RCCHK(combine_setting("combine_step", members, weights, gap));
+  if (!logits || !column || !token || !combined || !member_scores || !G || !N) return fail(-1, "bad argument");
+  if (N >= (size_t)slimt_hip::kBeamMaxN) return fail(-1, "combine_step: an output layer of %zu columns (2^20 or more)", N);
+  if (G > 0x7fffffffu / (size_t)members) return fail(-1, "combine_step: more than %d rows", 0x7fffffff);
+  const size_t R = G * (size_t)members;
+  Tmp3 t;
+  hipStream_t st = nullptr;
+  HIPCHK(t.a.reserve(R * N * 4));
+  HIPCHK(t.b.reserve(N * 4));
+  HIPCHK(t.d.reserve((3 * G + R) * 4));
+  HIPCHK(hipMemcpyAsync(t.a.p, logits, R * N * 4, hipMemcpyHostToDevice, st));
+  if (ids) HIPCHK(hipMemcpyAsync(t.b.p, ids, N * 4, hipMemcpyHostToDevice, st));
+  CombineStepArgs a;
+  a.logits = t.a.as<float>();
+  a.G = (int)G;
+  a.m = members;
+  a.N = (int)N;
+  a.ids = ids ? t.b.as<uint32_t>() : nullptr;
+  for (int j = 0; j < slimt_hip::kCombineMax; ++j) a.w[j] = j < members ? weights[j] : 0.0f;
+  a.gap = gap;
+  uint32_t *o = t.d.as<uint32_t>();
+  a.column = o;
+  a.token = o + G;
+  a.combined = reinterpret_cast<float *>(o + 2 * G);
+  a.member_scores = reinterpret_cast<float *>(o + 3 * G);
+  HIPCHK(launch_combine_step(a, st));
+  HIPCHK(hipMemcpyAsync(column, o, G * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(token, o + G, G * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(combined, o + 2 * G, G * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(member_scores, o + 3 * G, R * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return 0;
 }

@@ -89,6 +89,9 @@ struct ArmedOptions {
   int bg_groups = 0;
   float bg_penalty = 0.0f;
   uint32_t *bg_group_of = nullptr;    // nullable [B][beam]
+  // combined decoding (slimt_hip_ctx_set_fanout_combine): armed for cb_members > 0
+  int cb_members = 0;
+  float cb_w[4] = {1.0f, 0.0f, 0.0f, 0.0f}, cb_gap = 0.0f;
 };
 
 // The translate call in progress: filled by its CallOptions (engine.cpp), reset as a whole when the entry point returns.
@@ -131,6 +134,10 @@ struct CallState {
   int bg_groups = 0;  // (0: not armed)
   float bg_penalty = 0.0f;
   uint32_t *bg_group_of = nullptr, *bg_dev_group_of = nullptr;
+  // a fan-out call whose rows g m .. g m + m - 1 decode one hypothesis (slimt_hip_ctx_set_fanout_combine; combine.h):
+  // per-stage decoder with stored logits, combine_step.hip's selection and records behind every step
+  int cb_members = 0;  // (0: not armed)
+  float cb_w[4] = {1.0f, 0.0f, 0.0f, 0.0f}, cb_gap = 0.0f;
   BatchOptions dev;  // the current unmerged batch's options as the kernels address them (a merged launch: MergePlan::opt)
 };
 

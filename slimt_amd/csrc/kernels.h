@@ -1055,6 +1055,29 @@ struct BeamGroupedArgs {
 };
 hipError_t launch_beam_select_grouped(const BeamGroupedArgs &a, hipStream_t st);
 
+// ---- combined decoding: one token per group of fan-out rows (combine_step.hip) -------------------------------------------
+// One step of G groups of m member rows (rows r = g m + j, member 0 the primary) whose logits [G m][N] are in memory: the
+// selection of combine.h (include/slimt_hip.h, slimt_hip_ctx_set_fanout_combine) over s[c] = w[0] lp_0[c] + sum w[j] lp_j[c].
+// The op-level outputs are nullable. The rest is the engine's and nullable as a whole (dx == nullptr): the group's token and
+// each row's own score lp_j[column] recorded in the rows' outputs as decode_begin_step records an arg-max (st; scores [G m][Tmax]
+// nullable), and the next step's input rows (embed1's expression, position 0). One 512-thread workgroup per group.
+constexpr int kCombineResidentN = 4096;  // the widest rows a workgroup holds in registers (512 threads x 8 columns x m rows)
+struct CombineStepArgs {
+  const float *logits = nullptr;  // [G m][N]
+  int G = 0, m = 0, N = 0;
+  const uint32_t *ids = nullptr;  // [N] the columns' vocabulary ids (nullptr: the column)
+  float w[4] = {1.0f, 0.0f, 0.0f, 0.0f};
+  float gap = -__builtin_inff();
+  uint32_t *column = nullptr, *token = nullptr;  // [G]
+  float *combined = nullptr;                     // [G] s at the column, NaN where no candidate was left
+  float *member_scores = nullptr;                // [G m] lp_j[column], NaN for an unusable member
+  DecodeState st;
+  EmbedArgs emb;
+  float *scores = nullptr;  // [G m][Tmax]
+  float *dx = nullptr;      // [G m][D]
+};
+hipError_t launch_combine_step(const CombineStepArgs &a, hipStream_t st);
+
 // the column means (rounded) of an f32 K/V cache [Ld][K, V][B * S][D]: centre[(2 l + p) * D + d] (FusedDecodeArgs::kv_centre)
 hipError_t launch_kv_centres(const float *kv, int Ld, int B, int S, int D, unsigned long long *sums, int *centre, hipStream_t st);
 

@@ -356,6 +356,49 @@ class Service:
                         out[j][u.request][u.index] = (got[c, :ln[c]].tolist(), al[c, :ln[c], :L].copy(), sc[c, :ln[c]].copy())
         return out
 
+    def _contrasted(self, model: Model, per_request: List[List[List[int]]], per_contrast: List[List[List[int]]], weight: float, gap):
+        """histories shaped like _translate_segments', always scored: segment i of request r decoded against segment
+        i mod count of per_contrast[r] by source-contrastive decoding, argmax log p(y | x) - weight log p(y | x')
+        (capi.Context.set_fanout_combine with weights (1, -weight)). One fan-out call per batch on the Service's
+        capi.Context for the model: both sources of a pair encoded once, two decoder rows, the primary row's output kept."""
+        pairs = []
+        for r, segs in enumerate(per_request):
+            if segs and not per_contrast[r]:
+                raise ValueError("contrast: a contrast text without a sentence")
+            pairs += [(_Unit(r, i, list(seg)), list(per_contrast[r][i % len(per_contrast[r])])) for i, seg in enumerate(segs)]
+        if any(max(len(u.words), len(x)) > self.ENGINE_LIMIT for u, x in pairs):
+            raise ValueError(f"contrast: a segment has more than {self.ENGINE_LIMIT} tokens")
+        histories = [[None] * len(segs) for segs in per_request]
+        batches, cur = [], []
+        for p in sorted(pairs, key=lambda p: (max(len(p[0].words), len(p[1])), p[0].request, p[0].index)):
+            if cur and 2 * (len(cur) + 1) * max(len(p[0].words), len(p[1]), 1) > self.max_words:  # (two rows a pair)
+                batches.append(cur)
+                cur = []
+            cur.append(p)
+        if cur:
+            batches.append(cur)
+        eos = model.vocabulary.eos_id()
+        with self._lock:
+            ctx = self._beam_contexts.get(model.id)
+            if ctx is None and batches:
+                rows = max(self.max_words, capi.MAX_BEAM)
+                ctx = capi.Context(model.engine, rows, self.ENGINE_LIMIT, max_tokens=max(self.max_words, self.ENGINE_LIMIT))
+                self._beam_contexts[model.id] = ctx
+            for batch in batches:
+                B, S = 2 * len(batch), max(max(len(u.words), len(x)) for u, x in batch)
+                ids, lens = np.zeros((B, S), np.uint32), np.zeros(B, np.uint32)
+                for b, (u, x) in enumerate(batch):
+                    for row, words in ((2 * b, u.words), (2 * b + 1, x)):
+                        ids[row, :len(words)] = words
+                        lens[row] = len(words)
+                got, ln, al, sc = ctx.translate_fanout_pinned(ids, lens, np.arange(B, dtype=np.uint32), None, self.limit_factor, eos,
+                                                              want_align=True, generator=model.shortlist_generator, scores=True,
+                                                              combine=((1.0, -float(weight)), gap))
+                for b, (u, _) in enumerate(batch):
+                    c, L = 2 * b, int(lens[2 * b])
+                    histories[u.request][u.index] = (got[c, :ln[c]].tolist(), al[c, :ln[c], :L].copy(), sc[c, :ln[c]].copy())
+        return histories
+
     def _translate_segments(self, model: Model, per_request: List[List[List[int]]], scores: bool = False, sampling=None,
                             truncation=None):
         """per request, per segment: (target ids, alignment, token scores | None). sampling: (temperature, seed) -- one
@@ -476,7 +519,7 @@ class Service:
 
     def translate(self, model: Model, texts: Sequence[str], html: bool = False,
                   encoding: Encoding = Encoding.UTF8, scores: bool = False, sampling=None, truncation=None,
-                  samples: Optional[int] = None, constraints=None) -> List[Response]:
+                  samples: Optional[int] = None, constraints=None, contrast=None) -> List[Response]:
         """scores: every Response also carries token_scores (per target sentence, each target token's log-probability,
         EOS included; a wrapped segment's pieces concatenated) and sentence_scores (their sums).
         sampling: (temperature, seed) -- each sentence is one draw from the model at that temperature instead of the
@@ -495,9 +538,36 @@ class Service:
         (include/slimt_hip.h, slimt_hip_ctx_set_step_constraints). The call then runs on the Service's capi.Context for the
         model, as sample_and_select(floor=) does, always with scores (whatever `scores` says); not with truncation or
         samples. Unlike the plain call it does not split a segment above ENGINE_LIMIT tokens but refuses it, and the engine
-        refuses a length limit (tgt_length_limit_factor x the padded length) above 1024 tokens."""
+        refuses a length limit (tgt_length_limit_factor x the padded length) above 1024 tokens.
+        contrast: dict(weight=lambda, texts=None, gap=None) -- source-contrastive decoding against hallucinations and
+        off-target output (include/slimt_hip.h, slimt_hip_ctx_set_fanout_combine): every step takes the token that
+        maximises log p(y | x) - lambda log p(y | x'), x' the contrast source; gap <= 0 (None: off) keeps only tokens whose
+        log-probability under x is within |gap| of the best. Sentence i of a text is contrasted with sentence i mod count
+        of its contrast text: texts[r] of `texts`, or with texts=None the request's next text, cyclic (so the result does
+        not depend on how the request is batched; a request of one text is refused). Runs on the Service's capi.Context
+        like constraints=, always with scores (the primary's own log-probabilities); not with sampling, truncation,
+        samples or constraints."""
         if html:
             raise NotImplementedError("HTML markup transfer is outside the ported path (SURVEY.md §2)")
+        if contrast is not None:
+            if sampling is not None or truncation is not None or samples is not None or constraints is not None:
+                raise ValueError("translate: contrast is not combined with sampling, truncation, samples or constraints")
+            others = contrast.get("texts")
+            if others is None and len(texts) < 2:
+                raise ValueError("translate: contrast with texts=None needs a request of at least two texts")
+            if others is not None and len(others) != len(texts):
+                raise ValueError("translate: contrast texts must match the request's texts one for one")
+            processed = model.processor.process_many(texts, self.wrap_length, self.workers)
+            segs = [s for _, s in processed]
+            if others is None:
+                against = segs[1:] + segs[:1]
+            else:
+                against = [s for _, s in model.processor.process_many(others, self.wrap_length, self.workers)]
+            histories = self._contrasted(model, segs, against, float(contrast["weight"]), contrast.get("gap"))
+            out = self._respond_many(model, [src for src, _ in processed], histories)
+            for r in out:
+                r.to(encoding)
+            return out
         if constraints is not None:
             if truncation is not None or samples is not None:
                 raise ValueError("translate: constraints are not combined with truncation or samples")
